@@ -9,12 +9,15 @@ inputs resident in HBM before the timed region.  N > 1 (launched by torch.distri
 trees are sharded by rank and the per-cell composed maps are exchanged with one RCCL all-gather per step
 (weak scaling: per-GPU batch fixed).
 
-The same JSON line carries `roofline` (dominant kernel vs its roofline, algorithmic bytes from SURVEY §8d),
-`cpu_baseline` (the CPU oracle timed on this host, rank 0, N=1 only) and, LAST, `kmeans`: the second hot path at
-BASELINE configs[2]'s full size in the reference's own arithmetic (glibc expf / logf, the reference's k-means++ draw — the pass whose
-buckets are the reference's bit for bit), with the f32 contract arithmetic on the same draw as `kmeans.contract_arithmetic` and how
-far apart the two partitions are.  The line printed by default is a compact view (compact_line) that fits the driver's stdout window;
-the whole detail object is written to gpurun_out/bench_detail.json and is the line itself under --verbose.
+A plain run sets up, warms up, times the K steps, writes the last step's outputs under --dump-outputs DIR and prints the
+contract line (metric, value, unit, ms_per_step, ..., config): nothing else.  Everything else is measured under --full only.
+
+Under --full the same JSON line carries `roofline` (dominant kernel vs its roofline, algorithmic bytes from SURVEY §8d; a
+second pass of K steps with event timing), `cpu_baseline` (the CPU oracle timed on this host, rank 0, N=1 only) and, LAST,
+`kmeans`: the second hot path at BASELINE configs[2]'s full size in the reference's own arithmetic (glibc expf / logf, the
+reference's k-means++ draw — the pass whose buckets are the reference's bit for bit), with the f32 contract arithmetic on the same
+draw as `kmeans.contract_arithmetic` and how far apart the two partitions are.  The --full line is a compact view (compact_line)
+that fits the driver's stdout window; the whole detail object is the line itself under --verbose and is written to --detail PATH.
 """
 from __future__ import annotations
 
@@ -67,9 +70,18 @@ def parse():
                          "ordered: the reference's sequential tree-id order exactly (N=1 only)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-oracle baseline sample length (0 = skip)")
     ap.add_argument("--no-kmeans", action="store_true", help="skip the secondary k-means measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the event-timed per-kernel pass and roofline, the other update mode / "
+                         "scaling, convergence, CPU baselines, k-means, the NLHE and abstraction-input legs (off by default: a plain run "
+                         "only sets up, warms up, times --steps steps and prints the contract line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed by its last step (the tables a caller receives; "
+                         "a fixed, seeded sample of rows where they are large) as DIR/<name>.npy, float32 / float64, <= 64 MB in all")
+    ap.add_argument("--detail", metavar="PATH", default=None,
+                    help="--full: also write the whole detail object (every leg, notes, per-iteration tables) to PATH as JSON")
     ap.add_argument("--verbose", action="store_true",
-                    help="print the whole detail object (per-iteration tables, notes, every leg) as the JSON line instead of the compact one; "
-                         "the detail is always written to gpurun_out/bench_detail.json as well")
+                    help="--full: print the whole detail object (per-iteration tables, notes, every leg) as the JSON line instead of the "
+                         "compact one")
     ap.add_argument("--kmeans-counter-leg", action="store_true",
                     help="also time the flop layer in the contract arithmetic with the counter-hash draw (rounds 1-5's default leg)")
     ap.add_argument("--no-kmeans-reference", action="store_true",
@@ -148,6 +160,55 @@ def host_cores():
     except (OSError, ValueError):
         pass
     return max(1, n)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(directory, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy; float32 / float64 only, at most 64 MB in all."""
+    arrays = {name: np.ascontiguousarray(a) for name, a in arrays.items()}
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: '{name}' is {a.dtype}, not float32 / float64")
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the limit of {DUMP_LIMIT_BYTES}")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+def encounter_arrays(enc):
+    """A table of Encounters as one float array per field: weight / regret / payoff as they are (f32), visits (u32) in f64, exact."""
+    return {"weight": enc["weight"].astype(np.float32), "regret": enc["regret"].astype(np.float32),
+            "payoff": enc["payoff"].astype(np.float32), "visits": enc["visits"].astype(np.float64)}
+
+
+def sample_rows(n, cap, seed):
+    """A fixed, seeded sample of min(n, cap) indices of [0, n), ascending."""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+
+
+def mccfr_outputs(solver):
+    """What a caller of Solver::step holds after the last step: the whole table (Leduc: a few KB) and the counters."""
+    nodes, infos = solver.counters()
+    return {**encounter_arrays(solver.export()), "counters": np.array([solver.epoch, nodes, infos], dtype=np.float64)}
+
+
+def nlhe_outputs(s, seed, cap=1 << 17):
+    """The NLHE blueprint rows after the last step, ordered by infoset key (past, present, choices) and sampled to `cap` rows with
+    `seed`; the keys as 32-bit halves (exact in f64) beside the Encounters, and the counters."""
+    past, present, choices, enc = s.export()
+    order = np.lexsort((choices, present, past))
+    keep = order[sample_rows(order.size, cap, seed)]
+    lo, sh = np.uint64(0xFFFFFFFF), np.uint64(32)
+    keys = np.stack([past >> sh, past & lo, present.astype(np.uint64), choices >> sh, choices & lo], axis=1)[keep]
+    nodes, infos, n_keys = s.counters()
+    return {"keys": keys.astype(np.float64), **encounter_arrays(enc[keep]),
+            "counters": np.array([s.epoch, nodes, infos, n_keys], dtype=np.float64)}
 
 
 def cpu_baseline_all_cores(args, seconds=4.0):
@@ -474,9 +535,9 @@ def _short(x, n=96):
 
 
 def compact_line(line):
-    """The default stdout line: the contract's keys whole, every extra reduced to its numbers, the k-means object LAST (the driver keeps
-    the end of stdout).  Nothing is measured here: it is a view of `line`, whose full text goes to gpurun_out/bench_detail.json (and is
-    the line itself under --verbose)."""
+    """The --full stdout line: the contract's keys whole, every extra reduced to its numbers, the k-means object LAST (the driver keeps
+    the end of stdout).  Nothing is measured here: it is a view of `line`, whose full text goes to --detail PATH (and is the line
+    itself under --verbose)."""
     out = {k: line[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                                 "vs_baseline", "dtype", "data") if k in line}
     cfg = dict(line.get("config", {}))
@@ -638,6 +699,12 @@ def nlhe_synth(args, rank, world, local_rank):
                          "note": "24 + 32*|choices| bytes per update (SURVEY §8d); the hottest row of a Zipf(1.1) batch "
                                  "receives ~12 % of the touches and is one sequential chain in the ordered mode"},
         }
+        if args.dump_outputs:
+            # the profile's rows after the last step: the first 4 096 and a seeded uniform sample of the rest
+            rows = np.unique(np.concatenate([np.arange(min(args.rows, 4096)),
+                                             np.random.default_rng(args.seed).integers(0, args.rows, 1 << 17)])).astype(np.uint32)
+            write_outputs(args.dump_outputs, {"rows": rows.astype(np.float64), **encounter_arrays(prof.rows(rows)),
+                                              "epoch": np.array([prof.epoch()], dtype=np.float64)})
         if world == 1 and args.cpu_seconds > 0:
             import oracle
 
@@ -678,8 +745,9 @@ def self_launch(args):
     return subprocess.call(cmd)
 
 
-def timed_mccfr(args, g, batch, rank, world, local_rank, sharded_mode, torch, dist):
-    """W warm-up steps, then exactly K timed steps between barrier + synchronize fences; max over ranks."""
+def timed_mccfr(args, g, batch, rank, world, local_rank, sharded_mode, torch, dist, profile=True, dump=False):
+    """W warm-up steps, then exactly K timed steps between barrier + synchronize fences; max over ranks.  `dump`: the table after
+    the last timed step (rank 0); `profile`: K more steps with per-kernel event timing."""
     from robopoker_amd.mccfr import Solver
 
     solver = Solver(g, args.regret, args.weight, args.sampling, batch=batch, seed=args.seed, device=local_rank)
@@ -749,16 +817,19 @@ def timed_mccfr(args, g, batch, rank, world, local_rank, sharded_mode, torch, di
     _, infos1 = solver.counters()
     out = {"infos_local": infos1 - infos0, "infos": infos1 - infos0, "dt": dt, "batch": batch,
            "variant": solver.kernel_variant() + ("+maps fused" if args.update == "composed" and solver.kernel_variant() == "static" else "")}
-    # per-kernel durations for the roofline: the same K steps again with a HIP event pair around every kernel group on the
-    # launch stream (the event packets cost a few microseconds per launch, so they stay out of the timed region above)
-    solver.profile(True)
-    for _ in range(args.steps):
-        step()
-    fence()
-    for name in ("traverse", "update", "compact"):
-        ms, n = solver.kernel_time(name)
-        out[name + "_ms"] = ms / max(n, 1)
-    solver.profile(False)
+    if dump and rank == 0:
+        out["outputs"] = mccfr_outputs(solver)
+    if profile:
+        # per-kernel durations for the roofline: the same K steps again with a HIP event pair around every kernel group on the
+        # launch stream (the event packets cost a few microseconds per launch, so they stay out of the timed region above)
+        solver.profile(True)
+        for _ in range(args.steps):
+            step()
+        fence()
+        for name in ("traverse", "update", "compact"):
+            ms, n = solver.kernel_time(name)
+            out[name + "_ms"] = ms / max(n, 1)
+        solver.profile(False)
     solver.close()
     if comm is not None:
         comm.close()
@@ -950,7 +1021,7 @@ def nlhe_real(args, rank, world, local_rank):
         torch.cuda.set_device(local_rank)
         init_rccl(rank, world, args.dist_backend)
 
-    def run(batch, steps, warmup, profile=False, sampling=None, hyper=None, exact=False):
+    def run(batch, steps, warmup, profile=False, sampling=None, hyper=None, exact=False, dump=False):
         s = NlheSolver(cap_log2=args.nlhe_cap, regret="linear", weight="linear", batch=batch, seed=args.seed, device=local_rank,
                        sampling=sampling or args.sampling, hyper=hyper)
         if exact:
@@ -982,6 +1053,7 @@ def nlhe_real(args, rank, world, local_rank):
             t[1], t[2] = float(infos), float(nodes)  # each rank counts the Decisions of its own trees
             dist.all_reduce(t[1:], op=dist.ReduceOp.SUM)
             dt, infos, nodes = float(t[0]), int(t[1]), int(t[2])
+        outputs = nlhe_outputs(s, args.seed) if dump and rank == 0 else None
         prof = None
         if profile and not sharded:
             # a second pass of the same number of steps with a HIP event pair around every kernel group (the event packets cost
@@ -992,15 +1064,18 @@ def nlhe_real(args, rank, world, local_rank):
             prof = {"groups": s.kernel_times(), "census": s.census(), "levels": s.last_shape()[0], "steps": steps}
             s.profile(False)
         s.close()
-        return {"infos": infos, "nodes": nodes, "dt": dt, "keys": keys, "prof": prof}
+        return {"infos": infos, "nodes": nodes, "dt": dt, "keys": keys, "prof": prof, "outputs": outputs}
 
-    big = run(args.nlhe_batch, args.steps, args.warmup, profile=True)
+    big = run(args.nlhe_batch, args.steps, args.warmup, profile=args.full, dump=bool(args.dump_outputs))
     # RP_BENCH_NO_REF=1 (profiling runs: scripts/r3_nlhe_traffic.sh): every dispatch of the process belongs to the big batch
     ref_steps = max(args.steps, 100)  # 0.36 ms a step: a hundred of them, behind ten that fill the table's first infosets
-    ref = run(128, ref_steps, 10) if not os.environ.get("RP_BENCH_NO_REF") else {"infos": 0, "dt": 1.0}
+    no_ref = os.environ.get("RP_BENCH_NO_REF") or not args.full
+    ref = run(128, ref_steps, 10) if not no_ref else {"infos": 0, "dt": 1.0}
     if rank != 0:
         dist.destroy_process_group()
         return
+    if big["outputs"] is not None:
+        write_outputs(args.dump_outputs, big["outputs"])
     trees = args.nlhe_batch * args.steps * world
     line = {
         "metric": "mccfr_infoset_updates_per_sec", "value": big["infos"] / big["dt"], "unit": "infoset-updates/s", "n_gpus": world,
@@ -1013,16 +1088,18 @@ def nlhe_real(args, rank, world, local_rank):
                    "infosets_in_table": big["keys"], "parallelism": f"tree-sharded x{world}"},
         "trees_per_s": trees / big["dt"], "nodes_per_s": big["nodes"] / big["dt"],
         "nodes_per_tree": big["nodes"] / trees, "infos_per_tree": big["infos"] / trees,
-        "reference_batch_128": {"value": ref["infos"] / ref["dt"], "unit": "infoset-updates/s",
-                                "ms_per_step": ref["dt"] / ref_steps * 1e3, "steps": ref_steps, "warmup": 10,
-                                "note": "nlhe/src/solver.rs:11 batch_size = 128: one tree per workgroup of 512, the traversal in one launch "
-                                        "(k_nl_tree, ~0.29 ms = the slowest tree: ~13 us per tree level of dependent, lane-serial work; "
-                                        "values in the reference's own order = bit-exact Decisions); its last workgroup posts the "
-                                        "Decisions count to pinned host memory; four more launches (emit, k_prep_one, block maps, fold); "
-                                        "latency bound by construction — a step depends on the previous one (DESIGN 3c, round 6)"},
     }
+    if args.full:
+        line["reference_batch_128"] = {
+            "value": ref["infos"] / ref["dt"], "unit": "infoset-updates/s", "ms_per_step": ref["dt"] / ref_steps * 1e3, "steps": ref_steps,
+            "warmup": 10,
+            "note": "nlhe/src/solver.rs:11 batch_size = 128: one tree per workgroup of 512, the traversal in one launch "
+                    "(k_nl_tree, ~0.29 ms = the slowest tree: ~13 us per tree level of dependent, lane-serial work; "
+                    "values in the reference's own order = bit-exact Decisions); its last workgroup posts the "
+                    "Decisions count to pinned host memory; four more launches (emit, k_prep_one, block maps, fold); "
+                    "latency bound by construction — a step depends on the previous one (DESIGN 3c, round 6)"}
     line["config"]["sampling"] = args.sampling
-    if not sharded and not os.environ.get("RP_BENCH_NO_REF"):
+    if not sharded and not no_ref:
         # the regime a training run spends all but its first minutes in: PluribusSampling past its warm-up (sample/pluribus.rs:72-101,
         # hyperparams/pruning.rs:45-51: 16 384 epochs, threshold -3e5, explore 0.05).  A fresh table has no regret below the
         # reference's threshold, so the leg sets the warm-up to 0 and a threshold that bites on the default regrets (fold 100,
@@ -1042,7 +1119,7 @@ def nlhe_real(args, rank, world, local_rank):
             "prune_explore": args.prune_explore, "nodes_per_tree": pr_run["nodes"] / trees, "infos_per_tree": pr_run["infos"] / trees,
             "trees_per_s": trees / pr_run["dt"],
             "note": "same batch, PluribusSampling past its warm-up with a threshold that bites on a fresh table's default regrets"}
-    if not sharded and not os.environ.get("RP_BENCH_NO_REF") and args.nlhe_batch > 2048:
+    if not sharded and not no_ref and args.nlhe_batch > 2048:
         # the same batch with the regret vectors in the reference's own float order on the batch-wide kernels (rp_nlhe_set_exact: bit-exact
         # Decisions; 192 more bytes per node for the per-ancestor reach rows).  Batches up to 2 048 trees are always evaluated that way
         ex = run(args.nlhe_batch, max(2, args.steps // 2), 2, exact=True)
@@ -1068,7 +1145,7 @@ def nlhe_real(args, rank, world, local_rank):
         line["kernel_ms_per_step"] = {name: v[0] / k for name, v in g.items()}
         line["nodes_by_kind_per_step"] = {name: v / k for name, v in c.items()}
         line["levels"] = pr["levels"]
-    else:
+    elif args.full:
         line["roofline"] = {"bound": "hbm", "kernel": "k_nl_expand", "achieved": None, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                             "frac": None, "traffic": None, "note": "not profiled in the sharded run"}
     if args.cpu_seconds > 0:
@@ -1096,9 +1173,92 @@ def nlhe_real(args, rank, world, local_rank):
         dist.destroy_process_group()
 
 
+def full_extras(args, g, m, line, batch, world, local_rank, sharded_mode, other_scaling):
+    """--full: everything the line carries beyond the headline figure, added to `line` in place (rank 0)."""
+    A, dt = g.max_actions, m["dt"]
+    # dominant kernel vs the HBM roofline.  Algorithmic bytes per infoset-update = key 24 B + A*16 B read
+    # + A*16 B written = 24 + 32*A (SURVEY.md §8d); the kernel that realises the update is "update".
+    upd_avg_ms, trav_avg_ms = m["update_ms"], m["traverse_ms"]
+    per_launch_updates = m["infos_local"] / max(args.steps, 1)
+    dom, dom_ms = ("update", upd_avg_ms) if upd_avg_ms >= trav_avg_ms else ("traverse", trav_avg_ms)
+    bytes_per_update = 24 + 32 * A
+    achieved = per_launch_updates * bytes_per_update / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+    traffic, traffic_src = profiled_traffic((dom, args.update), batch)
+    other = "ordered" if args.update == "composed" else "composed"
+    args.batch = batch
+    other_rate = side_rate(args, g, local_rank, other) if world == 1 and not args.force_sharded and not args.no_extras else None
+    valu_instr, valu_src = profiled_valu(dom)
+    hbm_alg = {"achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
+               "bytes_per_update": bytes_per_update,
+               "note": "SURVEY §8d's 24 + 32 A algorithmic bytes per infoset-update x the updates of one launch / the "
+                       "dominant kernel's event-timed duration: a nominal figure — these bytes never reach HBM here "
+                       "(see hbm_frac_measured)"}
+    hbm_measured = traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS if traffic and dom_ms > 0 else None
+    composed_small = args.update == "composed" and dom == "traverse"
+    if composed_small and valu_instr:
+        # Leduc's tables are 3.8 KB (L2 resident) and in the composed mode the Decisions never reach HBM (traversal + block
+        # maps are one kernel): the kernel is priced against what binds it, VALU issue
+        rate = valu_instr / (dom_ms * 1e-3)
+        roofline_obj = {"bound": "valu", "kernel": dom, "achieved": rate, "peak": VALU_PEAK_WAVE_INSTR,
+                        "unit": "wave-instructions/s", "frac": rate / VALU_PEAK_WAVE_INSTR,
+                        "valu_instructions_per_launch": valu_instr, "valu_source": valu_src,
+                        "valu_note": "SQ_INSTS_VALU per launch from the committed rocprofv3 --pmc reduction named in "
+                                     "valu_source (a separate profiling run of this command at this batch) / this run's "
+                                     "event-timed launch duration; peak = 256 CU x 4 SIMD x 2.4 GHz / 2 cycles per wave64 "
+                                     "instruction",
+                        "lane_instructions_per_update": valu_instr * 64.0 / per_launch_updates if per_launch_updates else None}
+    else:
+        roofline_obj = {"bound": "hbm", "kernel": dom, **{k: hbm_alg[k] for k in ("achieved", "peak", "unit", "frac")}}
+    roofline_obj.update({
+        "traffic": traffic, "traffic_source": traffic_src, "hbm_frac_measured": hbm_measured,
+        "traffic_note": "PMC bytes per launch read from the committed rocprofv3 --pmc reduction named in "
+                        "traffic_source (a separate profiling run at this batch), not measured in this run; "
+                        "hbm_frac_measured = traffic / avg_launch_ms / 8 TB/s",
+        "hbm_algorithmic": hbm_alg, "updates_per_launch": per_launch_updates, "avg_launch_ms": dom_ms,
+        "kernels_ms": {"traverse": trav_avg_ms, "compact": m["compact_ms"], "update": upd_avg_ms},
+        "traversal_kernel": m.get("variant"),
+    })
+    line["roofline"] = roofline_obj
+    line["other_update_mode"] = {"update": other, "value": other_rate, "unit": "infoset-updates/s"}
+    if other_scaling is not None:
+        line["other_scaling"] = other_scaling
+    if world == 1 and not args.force_sharded and args.game == "leduc" and not args.no_extras:
+        line["convergence"] = convergence(args, g, local_rank)
+        if args.projection:  # opt-in, under a key that cannot be mistaken for a multi-GPU result
+            try:
+                line["unmeasured"] = {"strong_scaling_projection": strong_scaling_projection(args, local_rank, dt / args.steps * 1e3)}
+            except Exception as exc:  # noqa: BLE001  (a reported extra, never fatal)
+                line["unmeasured"] = {"strong_scaling_projection": {"error": f"{type(exc).__name__}: {exc}"}}
+        try:
+            line["time_to_exploitability"] = convergence_times(args, g, local_rank)
+        except Exception as exc:  # noqa: BLE001  (a reported extra, never fatal)
+            line["time_to_exploitability"] = {"error": f"{type(exc).__name__}: {exc}"}
+    if world == 1 and args.cpu_seconds > 0:
+        line["cpu_baseline"] = cpu_baseline(args)
+        try:
+            line["cpu_baseline_all_cores"] = cpu_baseline_all_cores(args, seconds=min(5.0, args.cpu_seconds))
+        except Exception as exc:  # noqa: BLE001  (a reported extra, never fatal)
+            line["cpu_baseline_all_cores"] = {"error": f"{type(exc).__name__}: {exc}"}
+    else:
+        line["cpu_baseline"] = None
+    if world == 1 and not args.force_sharded and not args.no_kmeans:
+        km = kmeans_secondary(args)
+        if km is not None:
+            line["kmeans"] = km
+    if world == 1 and not args.force_sharded and not args.no_extras:
+        try:
+            line["nlhe"] = nlhe_extra(args, local_rank)
+        except Exception as exc:  # noqa: BLE001  (a reported extra, never fatal)
+            line["nlhe"] = {"error": f"{type(exc).__name__}: {exc}"}
+        try:
+            line["abstraction_inputs"] = abstraction_inputs(args, local_rank)
+        except Exception as exc:  # noqa: BLE001  (a reported extra, never fatal)
+            line["abstraction_inputs"] = {"error": f"{type(exc).__name__}: {exc}"}
+
+
 def main():
     args = parse()
-    if args.no_extras:
+    if args.no_extras or not args.full:  # a plain run times the headline figure and nothing else
         args.no_kmeans, args.cpu_seconds = True, 0.0
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))
@@ -1136,9 +1296,9 @@ def main():
         return max(64, args.batch // world) if mode == "strong" else args.batch
 
     batch = per_gpu_batch(args.scaling)
-    m = timed_mccfr(args, g, batch, rank, world, local_rank, sharded_mode, torch, dist)
+    m = timed_mccfr(args, g, batch, rank, world, local_rank, sharded_mode, torch, dist, profile=args.full, dump=bool(args.dump_outputs))
     other_scaling = None
-    if world > 1:  # the other scaling mode's measurement rides in the same line
+    if world > 1 and args.full:  # the other scaling mode's measurement rides in the same line
         om = "weak" if args.scaling == "strong" else "strong"
         o = timed_mccfr(args, g, per_gpu_batch(om), rank, world, local_rank, sharded_mode, torch, dist)
         other_scaling = {"scaling": om, "value": o["infos"] / o["dt"], "unit": "infoset-updates/s",
@@ -1146,48 +1306,6 @@ def main():
     infos, dt = m["infos"], m["dt"]
 
     if rank == 0:
-        # dominant kernel vs the HBM roofline.  Algorithmic bytes per infoset-update = key 24 B + A*16 B read
-        # + A*16 B written = 24 + 32*A; the kernel that realises the update is "update".
-        upd_avg_ms, trav_avg_ms = m["update_ms"], m["traverse_ms"]
-        per_launch_updates = m["infos_local"] / max(args.steps, 1)
-        dom, dom_ms = ("update", upd_avg_ms) if upd_avg_ms >= trav_avg_ms else ("traverse", trav_avg_ms)
-        bytes_per_update = 24 + 32 * A
-        achieved = per_launch_updates * bytes_per_update / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-        traffic, traffic_src = profiled_traffic((dom, args.update), batch)
-        other = "ordered" if args.update == "composed" else "composed"
-        args.batch = batch
-        other_rate = side_rate(args, g, local_rank, other) if world == 1 and not args.force_sharded and not args.no_extras else None
-        valu_instr, valu_src = profiled_valu(dom)
-        hbm_alg = {"achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
-                   "bytes_per_update": bytes_per_update,
-                   "note": "SURVEY §8d's 24 + 32 A algorithmic bytes per infoset-update x the updates of one launch / the "
-                           "dominant kernel's event-timed duration: a nominal figure — these bytes never reach HBM here "
-                           "(see hbm_frac_measured)"}
-        hbm_measured = traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS if traffic and dom_ms > 0 else None
-        composed_small = args.update == "composed" and dom == "traverse"
-        if composed_small and valu_instr:
-            # Leduc's tables are 3.8 KB (L2 resident) and in the composed mode the Decisions never reach HBM (traversal + block
-            # maps are one kernel): the kernel is priced against what binds it, VALU issue
-            rate = valu_instr / (dom_ms * 1e-3)
-            roofline_obj = {"bound": "valu", "kernel": dom, "achieved": rate, "peak": VALU_PEAK_WAVE_INSTR,
-                            "unit": "wave-instructions/s", "frac": rate / VALU_PEAK_WAVE_INSTR,
-                            "valu_instructions_per_launch": valu_instr, "valu_source": valu_src,
-                            "valu_note": "SQ_INSTS_VALU per launch from the committed rocprofv3 --pmc reduction named in "
-                                         "valu_source (a separate profiling run of this command at this batch) / this run's "
-                                         "event-timed launch duration; peak = 256 CU x 4 SIMD x 2.4 GHz / 2 cycles per wave64 "
-                                         "instruction",
-                            "lane_instructions_per_update": valu_instr * 64.0 / per_launch_updates if per_launch_updates else None}
-        else:
-            roofline_obj = {"bound": "hbm", "kernel": dom, **{k: hbm_alg[k] for k in ("achieved", "peak", "unit", "frac")}}
-        roofline_obj.update({
-            "traffic": traffic, "traffic_source": traffic_src, "hbm_frac_measured": hbm_measured,
-            "traffic_note": "PMC bytes per launch read from the committed rocprofv3 --pmc reduction named in "
-                            "traffic_source (a separate profiling run at this batch), not measured in this run; "
-                            "hbm_frac_measured = traffic / avg_launch_ms / 8 TB/s",
-            "hbm_algorithmic": hbm_alg, "updates_per_launch": per_launch_updates, "avg_launch_ms": dom_ms,
-            "kernels_ms": {"traverse": trav_avg_ms, "compact": m["compact_ms"], "update": upd_avg_ms},
-            "traversal_kernel": m.get("variant"),
-        })
         line = {
             "metric": "mccfr_infoset_updates_per_sec",
             "value": infos / dt,
@@ -1211,52 +1329,20 @@ def main():
                                     "order (tests/test_gpu_mccfr.py), visits exact; ordered: bit-exact",
                 "parallelism": f"tree-sharded x{world}",
             },
-            "roofline": roofline_obj,
-            "other_update_mode": {"update": other, "value": other_rate, "unit": "infoset-updates/s"},
         }
-        if other_scaling is not None:
-            line["other_scaling"] = other_scaling
-        if world == 1 and not args.force_sharded and args.game == "leduc" and not args.no_extras:
-            line["convergence"] = convergence(args, g, local_rank)
-            if args.projection:  # opt-in, under a key that cannot be mistaken for a multi-GPU result
-                try:
-                    line["unmeasured"] = {"strong_scaling_projection": strong_scaling_projection(args, local_rank, dt / args.steps * 1e3)}
-                except Exception as exc:  # noqa: BLE001  (a reported extra, never fatal)
-                    line["unmeasured"] = {"strong_scaling_projection": {"error": f"{type(exc).__name__}: {exc}"}}
-            try:
-                line["time_to_exploitability"] = convergence_times(args, g, local_rank)
-            except Exception as exc:  # noqa: BLE001  (a reported extra, never fatal)
-                line["time_to_exploitability"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if world == 1 and args.cpu_seconds > 0:
-            line["cpu_baseline"] = cpu_baseline(args)
-            try:
-                line["cpu_baseline_all_cores"] = cpu_baseline_all_cores(args, seconds=min(5.0, args.cpu_seconds))
-            except Exception as exc:  # noqa: BLE001  (a reported extra, never fatal)
-                line["cpu_baseline_all_cores"] = {"error": f"{type(exc).__name__}: {exc}"}
-        else:
-            line["cpu_baseline"] = None
-        if world == 1 and not args.force_sharded and not args.no_kmeans:
-            km = kmeans_secondary(args)
-            if km is not None:
-                line["kmeans"] = km
-        if world == 1 and not args.force_sharded and not args.no_extras:
-            try:
-                line["nlhe"] = nlhe_extra(args, local_rank)
-            except Exception as exc:  # noqa: BLE001  (a reported extra, never fatal)
-                line["nlhe"] = {"error": f"{type(exc).__name__}: {exc}"}
-            try:
-                line["abstraction_inputs"] = abstraction_inputs(args, local_rank)
-            except Exception as exc:  # noqa: BLE001  (a reported extra, never fatal)
-                line["abstraction_inputs"] = {"error": f"{type(exc).__name__}: {exc}"}
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, m["outputs"])
+        if args.full:
+            full_extras(args, g, m, line, batch, world, local_rank, sharded_mode, other_scaling)
         if sharded_mode:
             line["rccl_nranks"] = RCCL_NRANKS
-        try:  # the whole detail beside the line (scratch: gpurun_out/ travels back from the GPU box)
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(ROOT, "gpurun_out", "bench_detail.json"), "w") as fh:
-                json.dump(line, fh)
-        except OSError:
-            pass
-        print(json.dumps(line if args.verbose else compact_line(line)), flush=True)
+        if args.full and args.detail:
+            try:  # the whole detail beside the line
+                with open(args.detail, "w") as fh:
+                    json.dump(line, fh)
+            except OSError:
+                pass
+        print(json.dumps(line if args.verbose or not args.full else compact_line(line)), flush=True)
 
     if sharded_mode and not args.no_kmeans:
         # The k-means exchange on the same ranks, AFTER the contract line is out (stdout carries exactly one JSON

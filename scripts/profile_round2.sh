@@ -16,7 +16,7 @@ OUT=$REPO/gpurun_out/prof2
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export PYTHONPATH=$REPO
-BENCH="python $REPO/bench.py --no-extras --steps 40 --warmup 5"
+BENCH="python $REPO/bench.py --full --no-extras --steps 40 --warmup 5"
 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- $BENCH > $OUT/kt.log 2>&1
 python $REPO/scripts/rocpd_summary.py $(ls $OUT/kt/*.db | head -1) $OUT/${TAG}_bench_kernel_stats.txt "$BENCH" > /dev/null
 grep -o '{"metric.*' $OUT/kt.log > $OUT/${TAG}_bench_line_under_rocprof.json
@@ -76,12 +76,12 @@ for f, c, mul in (("$OUT/bf/pmc_counter_collection.csv", "FETCH_SIZE", 2.0), ("$
     for k in tot: print(c, k, len(n[k]), "launches", f"{tot[k] / len(n[k]) * 1024 * mul / 1e9:.3f} GB per launch")
 PY
 # 6: the NLHE traversal
-NL="python $REPO/bench.py --workload nlhe --steps 3 --warmup 1 --cpu-seconds 0"
+NL="python $REPO/bench.py --full --workload nlhe --steps 3 --warmup 1 --cpu-seconds 0"
 rocprofv3 --kernel-trace --stats -d $OUT/kn -o kn -- $NL > $OUT/kn.log 2>&1
 python $REPO/scripts/rocpd_summary.py $(ls $OUT/kn/*.db | head -1) $OUT/${TAG}_nlhe_kernel_stats.txt "$NL" > /dev/null
 grep -o '{"metric.*' $OUT/kn.log > $OUT/${TAG}_nlhe_bench_line.json
 # 7: the row-addressed profile on synthetic NLHE-scale batches (own radix sort / scan / run lengths)
-SP="python $REPO/bench.py --workload nlhe-synth --steps 20 --warmup 3 --cpu-seconds 0"
+SP="python $REPO/bench.py --full --workload nlhe-synth --steps 20 --warmup 3 --cpu-seconds 0"
 rocprofv3 --kernel-trace --stats -d $OUT/ks -o ks -- $SP > $OUT/ks.log 2>&1
 python $REPO/scripts/rocpd_summary.py $(ls $OUT/ks/*.db | head -1) $OUT/${TAG}_sparse_kernel_stats.txt "$SP" > /dev/null
 grep -o '{"metric.*' $OUT/ks.log > $OUT/${TAG}_sparse_bench_line.json

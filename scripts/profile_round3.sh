@@ -10,13 +10,13 @@ OUT=$REPO/gpurun_out/prof3
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export PYTHONPATH=$REPO
-BENCH="python $REPO/bench.py --no-extras --steps 40 --warmup 5"
+BENCH="python $REPO/bench.py --full --no-extras --steps 40 --warmup 5"
 rm -rf $OUT/kt
 timeout 150 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- $BENCH > $OUT/kt.log 2>&1
 python $REPO/scripts/rocpd_summary.py $(ls $OUT/kt/*.db | head -1) $OUT/${TAG}_bench_kernel_stats.txt "$BENCH" | head -12
 grep -o '{"metric.*' $OUT/kt.log > $OUT/${TAG}_bench_line_under_rocprof.json
 rm -rf $OUT/kt
-CMD="python $REPO/bench.py --workload nlhe --steps 8 --warmup 4 --cpu-seconds 0"
+CMD="python $REPO/bench.py --full --workload nlhe --steps 8 --warmup 4 --cpu-seconds 0"
 rm -rf $OUT/nl
 timeout 200 rocprofv3 --kernel-trace --output-format csv -d $OUT/nl -o nl -- $CMD > $OUT/nl.log 2>&1
 grep -o '{"metric.*' $OUT/nl.log > $OUT/${TAG}_nlhe_bench_line_under_rocprof.json

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 export PYTHONPATH=$REPO
 rocprofv3 -L 2>/dev/null | tr ' ,\t' '\n\n\n' | grep -E '^(TA_|TCP_|TCC_|SQ_)' | sort -u > $OUT/counters.txt
 wc -l $OUT/counters.txt
-CMD="python $REPO/bench.py --workload nlhe --nlhe-batch 65536 --steps 3 --warmup 2 --cpu-seconds 0"
+CMD="python $REPO/bench.py --full --workload nlhe --nlhe-batch 65536 --steps 3 --warmup 2 --cpu-seconds 0"
 pass() {
   rm -rf $OUT/run
   rocprofv3 --pmc $1 --kernel-trace --output-format csv -d $OUT/run -o pmc -- $CMD > $OUT/run.log 2>&1

@@ -6,7 +6,7 @@ B=${2:-65536}
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof3
 mkdir -p $OUT
-CMD="python $REPO/bench.py --workload nlhe --nlhe-batch $B --steps 3 --warmup 1 --cpu-seconds 0"
+CMD="python $REPO/bench.py --full --workload nlhe --nlhe-batch $B --steps 3 --warmup 1 --cpu-seconds 0"
 ( cd $REPO && bash scripts/pmc_sq.sh ${TAG}nlhe $CMD ) > $OUT/sq.log 2>&1
 { echo "# scripts/pmc_sq.sh: rocprofv3 --pmc <two passes> --kernel-trace of: $CMD  (sums over all dispatches of each kernel)"; grep -E "^(void )?rp::k_nl" $OUT/sq.log; } > $OUT/${TAG}_nlhe_sq_counters.txt
 cat $OUT/${TAG}_nlhe_sq_counters.txt

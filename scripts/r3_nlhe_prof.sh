@@ -9,7 +9,7 @@ OUT=$REPO/gpurun_out/prof3
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export PYTHONPATH=$REPO
-CMD="python $REPO/bench.py --workload nlhe --nlhe-batch $BIG --steps 8 --warmup 4 --cpu-seconds 0 $EXTRA"
+CMD="python $REPO/bench.py --full --workload nlhe --nlhe-batch $BIG --steps 8 --warmup 4 --cpu-seconds 0 $EXTRA"
 rm -rf $OUT/nl
 rocprofv3 --kernel-trace --output-format csv -d $OUT/nl -o nl -- $CMD > $OUT/nl.log 2>&1
 grep -o '{"metric.*' $OUT/nl.log > $OUT/${TAG}_nlhe_bench_line_under_rocprof.json

@@ -9,7 +9,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export PYTHONPATH=$REPO
 export RP_BENCH_NO_REF=1
-CMD="python $REPO/bench.py --workload nlhe --nlhe-batch $B --steps 3 --warmup 2 --cpu-seconds 0"
+CMD="python $REPO/bench.py --full --workload nlhe --nlhe-batch $B --steps 3 --warmup 2 --cpu-seconds 0"
 rm -rf $OUT/fetch $OUT/write
 timeout 50 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o pmc -- $CMD > $OUT/fetch.log 2>&1
 timeout 50 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -o pmc -- $CMD > $OUT/write.log 2>&1

@@ -12,7 +12,7 @@ export RP_FIXTURE_CACHE=/tmp
 echo "== 1 gpu tests"; date +%T
 timeout 900 python -m pytest tests -m gpu -q -x --timeout 240 --timeout-method=thread --durations=12 -p no:cacheprovider > $OUT/gpu_tests.log 2>&1; tail -20 $OUT/gpu_tests.log
 echo "== 2 default bench"; date +%T
-timeout 420 python bench.py > $OUT/${TAG}_bench_line.json 2> $OUT/bench.err; head -c 300 $OUT/${TAG}_bench_line.json; echo; tail -2 $OUT/bench.err
+timeout 420 python bench.py --full > $OUT/${TAG}_bench_line.json 2> $OUT/bench.err; head -c 300 $OUT/${TAG}_bench_line.json; echo; tail -2 $OUT/bench.err
 python - <<PY
 import json
 try:
@@ -32,7 +32,7 @@ python scripts/valu_ceiling.py $OUT/${TAG}_lloyd_sq_counters.json $OUT/${TAG}_ll
 echo "== 4 kernel trace + PMC of the Leduc loop"; date +%T
 cd /tmp && export TMPDIR=/tmp
 export PYTHONPATH=$REPO
-BENCH="python $REPO/bench.py --no-extras --steps 40 --warmup 5"
+BENCH="python $REPO/bench.py --full --no-extras --steps 40 --warmup 5"
 rm -rf $OUT/kt
 timeout 150 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- $BENCH > $OUT/kt.log 2>&1
 python $REPO/scripts/rocpd_summary.py "$(ls $OUT/kt/*.db 2>/dev/null | head -1)" $OUT/${TAG}_bench_kernel_stats.txt "$BENCH" | head -8
@@ -49,9 +49,9 @@ python $REPO/scripts/sq_reduce.py $OUT/${TAG}_mccfr_sq_counters.json "$BENCH" $O
 rm -rf $OUT/fetch $OUT/write $OUT/sq1 $OUT/sq2
 echo "== 5 nlhe bench line + the HBM traffic of its level kernels at the same batch"; date +%T
 cd $REPO
-timeout 200 python bench.py --workload nlhe --cpu-seconds 8 --steps 8 --warmup 4 > $OUT/${TAG}_nlhe_bench_line.json 2> $OUT/nlhe.err; head -c 300 $OUT/${TAG}_nlhe_bench_line.json; echo
+timeout 200 python bench.py --full --workload nlhe --cpu-seconds 8 --steps 8 --warmup 4 > $OUT/${TAG}_nlhe_bench_line.json 2> $OUT/nlhe.err; head -c 300 $OUT/${TAG}_nlhe_bench_line.json; echo
 cd /tmp
-CMD="python $REPO/bench.py --workload nlhe --steps 3 --warmup 2 --cpu-seconds 0"
+CMD="python $REPO/bench.py --full --workload nlhe --steps 3 --warmup 2 --cpu-seconds 0"
 rm -rf $OUT/nf $OUT/nw
 RP_BENCH_NO_REF=1 timeout 150 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/nf -o pmc -- $CMD > $OUT/nf.log 2>&1
 RP_BENCH_NO_REF=1 timeout 150 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/nw -o pmc -- $CMD > $OUT/nw.log 2>&1

@@ -10,7 +10,7 @@ timeout 900 python -m pytest tests -m gpu -q -x --timeout 240 --timeout-method=t
 echo "== smoke"; date +%T
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -9
 echo "== default bench"; date +%T
-timeout 420 python bench.py > $OUT/r05_bench_line.json 2> $OUT/bench.err; head -c 200 $OUT/r05_bench_line.json; echo; tail -2 $OUT/bench.err
+timeout 420 python bench.py --full > $OUT/r05_bench_line.json 2> $OUT/bench.err; head -c 200 $OUT/r05_bench_line.json; echo; tail -2 $OUT/bench.err
 python - <<PY
 import json
 d = json.load(open("$OUT/r05_bench_line.json"))

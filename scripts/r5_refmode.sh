@@ -17,5 +17,5 @@ for k in ['create_s','kmeanspp_s','init_bounds_s','elkan_total_s','lookup_s','en
 print(d['kernels_ms'])
 PY
 date +%T
-timeout 250 python bench.py --workload nlhe --cpu-seconds 8 --steps 8 --warmup 4 > $OUT/r05_nlhe_bench_line.json 2> $OUT/nlhe.err; head -c 400 $OUT/r05_nlhe_bench_line.json; echo; tail -2 $OUT/nlhe.err
+timeout 250 python bench.py --full --workload nlhe --cpu-seconds 8 --steps 8 --warmup 4 > $OUT/r05_nlhe_bench_line.json 2> $OUT/nlhe.err; head -c 400 $OUT/r05_nlhe_bench_line.json; echo; tail -2 $OUT/nlhe.err
 date +%T

@@ -10,13 +10,13 @@ cd /tmp && export TMPDIR=/tmp
 export PYTHONPATH=$REPO
 export RP_BENCH_NO_REF=1
 echo "== batch 128 trace"; date +%T
-CMD="python $REPO/bench.py --workload nlhe --nlhe-batch 128 --steps 40 --warmup 10 --cpu-seconds 0"
+CMD="python $REPO/bench.py --full --workload nlhe --nlhe-batch 128 --steps 40 --warmup 10 --cpu-seconds 0"
 rm -rf $OUT/nl
 timeout 200 rocprofv3 --kernel-trace --output-format csv -d $OUT/nl -o nl -- $CMD > $OUT/nl.log 2>&1
 python $REPO/scripts/steady_stats.py $OUT/nl/nl_kernel_trace.csv 10 40 $OUT/${TAG}_nlhe_kernel_stats_b128.txt "$CMD (the timed steps)" | head -40
 rm -rf $OUT/nl
 echo "== batch 262144 SQ pass"; date +%T
-CMD2="python $REPO/bench.py --workload nlhe --nlhe-batch 262144 --steps 3 --warmup 2 --cpu-seconds 0"
+CMD2="python $REPO/bench.py --full --workload nlhe --nlhe-batch 262144 --steps 3 --warmup 2 --cpu-seconds 0"
 rm -rf $OUT/sq
 timeout 200 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VMEM_RD SQ_INST_LEVEL_VMEM SQ_INSTS_VALU SQ_ACTIVE_INST_VALU \
   --kernel-trace --output-format csv -d $OUT/sq -o pmc -- $CMD2 > $OUT/sq.log 2>&1
@@ -25,5 +25,5 @@ rm -rf $OUT/sq
 echo "== bench line"; date +%T
 unset RP_BENCH_NO_REF
 cd $REPO
-timeout 250 python bench.py --workload nlhe --cpu-seconds 6 --steps 8 --warmup 4 > $OUT/${TAG}_nlhe_bench_line.json 2> $OUT/nlhe.err; head -c 600 $OUT/${TAG}_nlhe_bench_line.json; echo
+timeout 250 python bench.py --full --workload nlhe --cpu-seconds 6 --steps 8 --warmup 4 > $OUT/${TAG}_nlhe_bench_line.json 2> $OUT/nlhe.err; head -c 600 $OUT/${TAG}_nlhe_bench_line.json; echo
 date +%T

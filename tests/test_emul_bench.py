@@ -62,7 +62,7 @@ def built():
 @pytest.mark.parametrize("comm", ["native", "torch"])
 def test_bench_two_ranks_prints_one_contract_line(built, comm):
     res = _launch(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4096", "--no-kmeans", "--cpu-seconds", "0",
-                   "--dist-backend", "gloo", "--comm", comm])
+                   "--dist-backend", "gloo", "--comm", comm, "--full"])
     for rc, out, err in res:
         assert rc == 0, err[-3000:]
     lines = [ln for ln in res[0][1].splitlines() if ln.startswith("{")]
