@@ -493,8 +493,15 @@ RP_API int rp_kmeans_init_centroids(rp_kmeans* h, uint64_t* chosen);
  * DefaultHasher over the Street (`street` = its discriminant: 0 Pref, 1 Flop, 2 Turn, 3 Rive; deuce/src/street.rs:21-27) ->
  * SmallRng::seed_from_u64, ONE generator for the K picks, each pick WeightedIndex::<f32>::new(potentials).sample(rng): f32
  * running sums in index order (sequential by definition: one wavefront, ~4 ns per point), x = Uniform::new(0, total).sample,
- * partition_point (include/rp_refrng.h).  Single GPU: the running sums span all N points in order, so the sharded k-means++
- * (rp_kmeans_kpp_* composed across ranks) keeps the fixed-point draw.  `seed` is not used in this mode. */
+ * partition_point (include/rp_refrng.h).  `seed` is not used in this mode.  The running sum is sequential, but between two powers
+ * of two it is integer arithmetic (csrc/kpp_refpick.hpp), and a point-sharded layer continues it across ranks, per pick:
+ *   1. rank 0: rp_kmeans_kpp_ref_walk(h, 0.0f, &end); rank r > 0 receives rank r-1's end, walks from it, hands its own end on
+ *   2. the last rank's end is the reference's total_weight: broadcast it
+ *   3. every rank: rp_kmeans_kpp_ref_draw(h, total, &x) (each rank's generator advances alike; K draws from ONE seed)
+ *   4. the owner is the first rank whose end exceeds x (the last rank if none does: partition_point's fallback)
+ *   5. the owner: rp_kmeans_kpp_ref_pick(h, x, &index); its point's histogram goes to every rank (rp_kmeans_get_point)
+ *   6. every rank: rp_kmeans_set_centroid(h, k, histogram), rp_kmeans_kpp_update(h, k)
+ * One f32 handed on per rank per pick; the picks are the single layer's bit for bit (tests/test_gpu_sharded_refdraw.py). */
 RP_API int rp_kmeans_set_rng(rp_kmeans* h, rp_rng_kind kind, int street);
 /* Which exp / ln the Sinkhorn distances compute with.
  *   RP_LIBM_CONTRACT  (default) include/rp_math.h's rp_expf / rp_logf: f32 only, packed and pipelined in the softmin loops,
@@ -557,6 +564,18 @@ RP_API int rp_kmeans_kpp_begin(rp_kmeans* h);
 RP_API int rp_kmeans_kpp_total(rp_kmeans* h, uint64_t* total);
 RP_API int rp_kmeans_kpp_pick(rp_kmeans* h, uint64_t r, uint64_t* index);
 RP_API int rp_kmeans_kpp_update(rp_kmeans* h, uint32_t k);
+/* The same family after rp_kmeans_set_rng(h, RP_RNG_REFERENCE, street) and rp_kmeans_kpp_begin, which in that mode also seeds the
+ * handle's SmallRng from the street exactly as rp_kmeans_init_centroids does (the protocol: at rp_kmeans_set_rng); without those
+ * two calls RP_ERR_INVALID, the message names the missing one.
+ * ref_walk: this shard's potentials walked in index order from the exact running sum in front of it (0.0f on the first shard) */
+RP_API int rp_kmeans_kpp_ref_walk(rp_kmeans* h, float prefix_in, float* prefix_out);
+/* every rank, once per pick, with the LAST shard's prefix_out: advances the handle's SmallRng by one u32 and returns
+ * x = value0_1 * UniformFloat::new(0, total).scale + 0 (rp_refrng.h).  total == 0 (or not > 0): RP_ERR_INVALID ("the reference
+ * panics here"), the generator still advanced identically on all ranks */
+RP_API int rp_kmeans_kpp_ref_draw(rp_kmeans* h, float total, float* x);
+/* after ref_walk with unchanged potentials: the first local index whose running sum exceeds x, its potential <- 0;
+ * *index = N if none does (nothing written) */
+RP_API int rp_kmeans_kpp_ref_pick(rp_kmeans* h, float x, uint64_t* index);
 /* Elkan::init_bounds (elkan.rs:39-47) */
 RP_API int rp_kmeans_init_bounds(rp_kmeans* h);
 /* Kmeans::next (kmeans.rs:82-110): step_elkan (elkan.rs:153-168), install centroids, Prior::tally.

@@ -84,6 +84,14 @@ RP_API int rp_kmeans_pairwise_last(rp_kmeans* h, float* pairw);
  * construction.  out[0] = the index (n if the total is 0), out[1] = the bits of the total weight, out[2] = chunks of 256 terms that
  * mode 1 walked term by term (ties, binade crossings, mispredictions).  Both modes must agree with a host loop on every input. */
 RP_API int rp_weighted_index_probe(int device, uint64_t n, const float* weights, float v01, int mode, uint64_t* out);
+/* The same draw by the kernels of the sharded protocol (rp_kmeans_kpp_ref_walk / _draw / _pick; rp_mi355x.h at rp_kmeans_set_rng) on
+ * n host weights cut into nshards contiguous non-empty shards [cuts[s], cuts[s+1]) on one device, cuts[0] = 0, cuts[nshards] = n:
+ * every shard walked from the exact end sum of the one in front of it, x drawn from the last end sum, the pick on the first shard
+ * whose end sum exceeds x.  out_index_total_walked = [global index, bits of the total, chunks walked term by term over all shards];
+ * end_sums[s] = the running sum after shard s, the reference's cumulative weight at cuts[s+1] - 1 bit for bit.  A total that is
+ * not > 0: RP_ERR_INVALID (end_sums and out are still filled, the index is n). */
+RP_API int rp_weighted_index_probe_shards(int device, uint64_t n, const float* weights, uint32_t nshards, const uint64_t* cuts, float v01,
+                                          uint64_t* out_index_total_walked, float* end_sums);
 /* the layer's raw counters, out[5]: [0] distances evaluated (rp_kmeans_stats), [1] Sinkhorn iterations, [2] softmin + cost terms,
  * [3] distances the reference evaluates at that point of Elkan::step_elkan (elkan.rs:153-168) and this library remembers instead of
  * solving again (same centroid content, same point: the value is a pure function of the two), [4] variation distances computed
@@ -92,7 +100,8 @@ RP_API int rp_weighted_index_probe(int device, uint64_t n, const float* weights,
 RP_API int rp_kmeans_stats_ex(rp_kmeans* h, uint64_t* out5);
 
 RP_API int rp_kmeans_profile(rp_kmeans* h, int enable);
-/* name in {"pairwise","step","recompute","bounds","neighbor","selfcost","kpp","drift","mfma_bound","kpp_bound"} */
+/* name in {"pairwise","step","recompute","bounds","neighbor","selfcost","kpp","drift","mfma_bound","kpp_bound","refresh_bound","ref_draw"};
+ * "ref_draw" = the launches of the reference-seed k-means++ draw alone (csrc/kpp_refpick.hpp), which "kpp" also contains */
 RP_API int rp_kmeans_kernel_time(rp_kmeans* h, const char* name, double* total_ms, uint64_t* launches);
 
 #ifdef __cplusplus

@@ -224,6 +224,9 @@ _SIGNATURES = {
     "rp_kmeans_kpp_total": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rp_kmeans_kpp_pick": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "rp_kmeans_kpp_update": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rp_kmeans_kpp_ref_walk": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(C.c_float)]),
+    "rp_kmeans_kpp_ref_draw": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(C.c_float)]),
+    "rp_kmeans_kpp_ref_pick": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(C.c_uint64)]),
     "rp_kmeans_init_bounds": (C.c_int, [C.c_void_p]),
     "rp_kmeans_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "rp_kmeans_step_naive": (C.c_int, [C.c_void_p]),
@@ -242,6 +245,8 @@ _SIGNATURES = {
     "rp_kmeans_upper_interval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rp_kmeans_pairwise_last": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rp_weighted_index_probe": (C.c_int, [C.c_int, C.c_uint64, C.c_void_p, C.c_float, C.c_int, C.c_void_p]),
+    "rp_weighted_index_probe_shards": (C.c_int, [C.c_int, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_void_p,
+                                                  C.c_void_p]),
     "rp_kmeans_stats_ex": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rp_kmeans_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rp_kmeans_profile": (C.c_int, [C.c_void_p, C.c_int]),

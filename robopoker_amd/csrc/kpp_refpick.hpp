@@ -13,10 +13,16 @@
 //   k_kr_sums    approximate chunk sums (one wavefront per chunk of 256 potentials)
 //   k_kr_scan    exclusive scan of those: the binade e_c each chunk is EXPECTED to start in (a prediction, checked later)
 //   k_kr_chunks  per chunk, for u = 2^(e_c - 23): D_c, and a flag if any term is a tie, is not finite or is >= 2^23 u
-//   k_kr_pick    one wavefront walks the CHUNKS in order with the exact running sum: where the prediction holds (the sum's exponent
+//   kr_walk      one wavefront walks the CHUNKS in order with the exact running sum: where the prediction holds (the sum's exponent
 //                is e_c, no flag, m + D_c <= 2^24 - 1) the chunk is one exact addition run += D_c u; everywhere else (the first
-//                chunk, the ~20 binade crossings, the ~ln N ties, a misprediction) it walks the chunk's 256 additions as the
-//                reference does.  Chunk-end sums are kept; the partition point is a binary search over them and one re-walked chunk.
+//                chunk of a layer, the ~20 binade crossings, the ~ln N ties, a misprediction) it walks the chunk's 256 additions as
+//                the reference does.  Chunk-end sums are kept.
+//   kr_find      the partition point for a drawn x: a binary search over the chunk-end sums and one re-walked chunk.
+//   k_kr_pick    kr_walk from 0, the draw, kr_find: one layer on one device (rp_kmeans_init_centroids).
+//   k_kr_walk / k_kr_find   the two halves as launches of their own: a point-sharded layer (rp_kmeans_kpp_ref_*).  The walk starts
+//                from `prefix_in`, the exact end sum of the shard in front (the identity holds for any run in the binade, so nothing
+//                in the argument changes; scan and chunk summaries are predicted from the same prefix), and x is drawn from the
+//                GLOBAL total, which exists only after the last shard's walk.
 // The result is the reference's running sum bit for bit by construction, not by tolerance: every shortcut is taken only under the
 // conditions of the identity above, checked against the exact sum at the chunk's start.  tests/test_reference_seed.py compares the
 // picks and the total with a host walk of the N additions on adversarial weight sets (ties, crossings, zeros, huge terms).
@@ -39,8 +45,8 @@ __global__ __launch_bounds__(256) void k_kr_sums(const float* pot, uint64_t N, u
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
     if (lane == 0) csum[c] = s;
 }
-// one workgroup: start[c] = csum[0] + ... + csum[c-1] (any bracketing: a prediction), kept as the biased exponent of that float
-__global__ __launch_bounds__(1024) void k_kr_scan(const float* csum, uint32_t nchunks, uint32_t* expo) {
+// one workgroup: start[c] = prefix_in + csum[0] + ... + csum[c-1] (any bracketing: a prediction), kept as the biased exponent of that float
+__global__ __launch_bounds__(1024) void k_kr_scan(const float* csum, uint32_t nchunks, float prefix_in, uint32_t* expo) {
     __shared__ float part[1024];
     const uint32_t t = threadIdx.x, per = (nchunks + 1023u) / 1024u, lo = t * per, hi = min(lo + per, nchunks);
     float s = 0.0f;
@@ -53,7 +59,7 @@ __global__ __launch_bounds__(1024) void k_kr_scan(const float* csum, uint32_t nc
         part[t] += v;
         __syncthreads();
     }
-    float run = t ? part[t - 1] : 0.0f;
+    float run = prefix_in + (t ? part[t - 1] : 0.0f);  // 0 + s = s: a first shard predicts what a whole layer does
     for (uint32_t c = lo; c < hi; ++c) {
         expo[c] = (rp_f2u(run) >> 23) & 0xffu;
         run += csum[c];
@@ -83,30 +89,20 @@ __global__ __launch_bounds__(256) void k_kr_chunks(const float* pot, uint64_t N,
     if (lane == 0) meta[c] = make_uint2(d, be | (any ? 0x80000000u : 0u));
 }
 
-// cum[c] = the running sum after chunk c (exact).  picked[0] = the index, picked[1] = the total's bits, picked[2] = chunks walked
-__global__ __launch_bounds__(64) void k_kr_pick(float* pot, float* kpp_d, uint64_t N, uint32_t nchunks, const uint2* meta, float* cum, float v01,
-                                                unsigned long long* picked) {
-    __shared__ __attribute__((aligned(16))) float buf[KR_ELEMS];
-    const uint32_t ln = threadIdx.x;
-    auto load_chunk = [&](uint32_t c) {
-        __syncthreads();
+// shared by the three kernels below: ONE wavefront; buf = KR_ELEMS floats of LDS
+__device__ __forceinline__ void kr_load_chunk(float* buf, const float* pot, uint64_t N, uint32_t c, uint32_t ln) {
+    __syncthreads();
 #pragma unroll
-        for (uint32_t q = 0; q < 4; ++q) {
-            const uint64_t i = (uint64_t)c * KR_ELEMS + q * 64u + ln;
-            buf[q * 64u + ln] = i < N ? pot[i] : 0.0f;  // + 0 past the end leaves the sum as it is
-        }
-        __syncthreads();
-    };
-    auto walk = [&](float run) {  // the reference's additions over the chunk in buf
-#pragma unroll 8
-        for (uint32_t j = 0; j < KR_ELEMS; j += 4) {
-            const float4 w4 = *reinterpret_cast<const float4*>(buf + j);
-            run += w4.x; run += w4.y; run += w4.z; run += w4.w;
-        }
-        return run;
-    };
-    float run = 0.0f;  // total_weight (0 + w0 = w0 exactly)
-    uint32_t walked = 0;
+    for (uint32_t q = 0; q < 4; ++q) {
+        const uint64_t i = (uint64_t)c * KR_ELEMS + q * 64u + ln;
+        buf[q * 64u + ln] = i < N ? pot[i] : 0.0f;  // + 0 past the end leaves the sum as it is
+    }
+    __syncthreads();
+}
+// cum[c] = the running sum after chunk c (exact), the walk starting from prefix_in; returns the end sum
+__device__ __forceinline__ float kr_walk(const float* pot, uint64_t N, uint32_t nchunks, const uint2* meta, float* cum, float prefix_in,
+                                         float* buf, uint32_t ln, uint32_t& walked) {
+    float run = prefix_in;  // total_weight so far (0 + w0 = w0 exactly)
     for (uint32_t c0 = 0; c0 < nchunks; c0 += 64u) {
         const uint32_t mine = c0 + ln;
         const uint2 mm = mine < nchunks ? meta[mine] : make_uint2(0u, 0x80000000u);
@@ -116,51 +112,94 @@ __global__ __launch_bounds__(64) void k_kr_pick(float* pot, float* kpp_d, uint64
             const uint32_t d = (uint32_t)__shfl((int)mm.x, (int)j, 64), info = (uint32_t)__shfl((int)mm.y, (int)j, 64);
             const uint32_t rb = rp_f2u(run), be = rb >> 23;  // run >= 0: no sign bit
             const uint32_t m = (rb & 0x7fffffu) | 0x800000u;
-            const bool fast = info == be && be >= 24u && be <= 254u && d <= 0xffffffu - m;  // prediction holds, no flag, stays in the binade
+            // prediction holds, no flag, stays in the binade (& not &&: three compares and one branch on the chain from chunk to chunk)
+            const bool fast = (info == be) & (be - 24u <= 230u) & (d <= 0xffffffu - m);
             if (fast) {
                 run += (float)d * rp_u2f((be - 23u) << 23);  // both exact: d < 2^24, and m + d <= 2^24 - 1 is representable at this ulp
             } else {  // wave uniform
-                load_chunk(c0 + j);
-                run = walk(run);
+                kr_load_chunk(buf, pot, N, c0 + j, ln);
+#pragma unroll 8
+                for (uint32_t t = 0; t < KR_ELEMS; t += 4) {  // the reference's additions over the chunk in buf
+                    const float4 w4 = *reinterpret_cast<const float4*>(buf + t);
+                    run += w4.x; run += w4.y; run += w4.z; run += w4.w;
+                }
                 walked += 1;
             }
             if (ln == j) my_end = run;
         }
         if (mine < nchunks) cum[mine] = my_end;
     }
-    const float total = run;
+    return run;
+}
+// partition_point(|w| w <= x) over this shard's running sums: the first LOCAL index whose sum exceeds x, N if none does
+__device__ __forceinline__ uint64_t kr_find(const float* pot, uint64_t N, uint32_t nchunks, const float* cum, float prefix_in, float x,
+                                            float* buf, uint32_t ln) {
+    const uint32_t* cb = reinterpret_cast<const uint32_t*>(cum);
+    uint32_t lo = 0, hi = nchunks;  // first chunk whose END sum exceeds x
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        // (an agent-scope load: k_kr_pick's own wavefront wrote the sums a moment ago)
+        if (rp_u2f(__hip_atomic_load(cb + mid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) <= x) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo >= nchunks) return N;
+    float r2 = lo ? rp_u2f(__hip_atomic_load(cb + lo - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : prefix_in;
+    kr_load_chunk(buf, pot, N, lo, ln);
+    uint32_t at = KR_ELEMS;
+    for (uint32_t j = 0; j < KR_ELEMS; ++j) {  // the reference's adds from the exact sum in front of the chunk
+        r2 += buf[j];
+        if (at == KR_ELEMS && r2 > x) at = j;
+    }
+    return at < KR_ELEMS ? min((uint64_t)lo * KR_ELEMS + at, N - 1) : N;
+}
+__device__ __forceinline__ void kr_take(float* pot, float* kpp_d, uint64_t win) {
+    pot[win] = 0.0f;                // potentials[i] = 0 (layer.rs:168)
+    if (kpp_d) kpp_d[win] = -1.0f;  // no solve stands behind that 0
+}
+
+// one layer on one device.  picked[0] = the index, picked[1] = the total's bits, picked[2] = chunks walked
+__global__ __launch_bounds__(64) void k_kr_pick(float* pot, float* kpp_d, uint64_t N, uint32_t nchunks, const uint2* meta, float* cum, float v01,
+                                                unsigned long long* picked) {
+    __shared__ __attribute__((aligned(16))) float buf[KR_ELEMS];
+    const uint32_t ln = threadIdx.x;
+    uint32_t walked = 0;
+    const float total = kr_walk(pot, N, nchunks, meta, cum, 0.0f, buf, ln, walked);
     uint64_t win = N;  // invalid weights (total == 0): the reference panics ("valid weights array"); the host falls back
     if (total > 0.0f) {  // wave uniform
         const float x = v01 * rp_uniform_f32_scale(total) + 0.0f;  // UniformFloat::sample: value0_1 * scale + low
-        // partition_point(|w| w <= x) over cum[0 .. N-1): the first index whose running sum exceeds x, N - 1 if none does
         __threadfence();
         __syncthreads();  // every lane's chunk-end sums are stored before any lane searches them
-        uint32_t lo = 0, hi = nchunks;  // first chunk whose END sum exceeds x
-        while (lo < hi) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            // (an agent-scope load: the sums were written by this wavefront a moment ago)
-            if (rp_u2f(__hip_atomic_load(reinterpret_cast<const uint32_t*>(cum) + mid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) <= x) lo = mid + 1;
-            else hi = mid;
-        }
-        win = N - 1;
-        if (lo < nchunks) {
-            float r2 = lo ? rp_u2f(__hip_atomic_load(reinterpret_cast<const uint32_t*>(cum) + lo - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : 0.0f;
-            load_chunk(lo);
-            uint32_t at = KR_ELEMS;
-            for (uint32_t j = 0; j < KR_ELEMS; ++j) {  // the reference's adds from the exact sum in front of the chunk
-                r2 += buf[j];
-                if (at == KR_ELEMS && r2 > x) at = j;
-            }
-            if (at < KR_ELEMS) win = min((uint64_t)lo * KR_ELEMS + at, N - 1);
-        }
-        if (ln == 0) {
-            pot[win] = 0.0f;                // potentials[i] = 0 (layer.rs:168)
-            if (kpp_d) kpp_d[win] = -1.0f;  // no solve stands behind that 0
-        }
+        win = kr_find(pot, N, nchunks, cum, 0.0f, x, buf, ln);
+        if (win == N) win = N - 1;  // partition_point over cum[0 .. N-1): N - 1 if no sum exceeds x
+        if (ln == 0) kr_take(pot, kpp_d, win);
     }
     if (ln == 0) {
         picked[0] = win;
         picked[1] = rp_f2u(total);
         picked[2] = walked;
+    }
+}
+// a shard: out[1] = the bits of the end sum (the next shard's prefix_in), out[2] = chunks walked
+__global__ __launch_bounds__(64) void k_kr_walk(const float* pot, uint64_t N, uint32_t nchunks, const uint2* meta, float* cum, float prefix_in,
+                                                unsigned long long* out) {
+    __shared__ __attribute__((aligned(16))) float buf[KR_ELEMS];
+    const uint32_t ln = threadIdx.x;
+    uint32_t walked = 0;
+    const float end = kr_walk(pot, N, nchunks, meta, cum, prefix_in, buf, ln, walked);
+    if (ln == 0) {
+        out[1] = rp_f2u(end);
+        out[2] = walked;
+    }
+}
+// after k_kr_walk on unchanged potentials: out[0] = the first local index whose running sum exceeds x (taken: its potential is
+// zeroed), or N and nothing written: "not here"
+__global__ __launch_bounds__(64) void k_kr_find(float* pot, float* kpp_d, uint64_t N, uint32_t nchunks, const float* cum, float prefix_in, float x,
+                                                unsigned long long* out) {
+    __shared__ __attribute__((aligned(16))) float buf[KR_ELEMS];
+    const uint32_t ln = threadIdx.x;
+    const uint64_t win = kr_find(pot, N, nchunks, cum, prefix_in, x, buf, ln);
+    if (ln == 0) {
+        if (win < N) kr_take(pot, kpp_d, win);
+        out[0] = win;
     }
 }

@@ -62,26 +62,51 @@ using namespace rp;
 namespace {
 struct Clock {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> shared;  // pairs another clock owns (ck_begin's `also`): read here, destroyed there
     double total_ms = 0.0;
     uint64_t launches = 0;
 };
-const char* const CLOCK_NAMES[] = {"pairwise", "step", "recompute", "bounds", "neighbor", "selfcost", "kpp", "drift", "mfma_bound", "kpp_bound", "refresh_bound"};
-enum { CK_PAIRWISE, CK_STEP, CK_RECOMPUTE, CK_BOUNDS, CK_NEIGHBOR, CK_SELF, CK_KPP, CK_DRIFT, CK_BOUND, CK_KPP_BOUND, CK_REFRESH_BOUND, CK_COUNT };
+const char* const CLOCK_NAMES[] = {"pairwise", "step", "recompute", "bounds", "neighbor", "selfcost", "kpp", "drift", "mfma_bound", "kpp_bound", "refresh_bound", "ref_draw"};
+enum { CK_PAIRWISE, CK_STEP, CK_RECOMPUTE, CK_BOUNDS, CK_NEIGHBOR, CK_SELF, CK_KPP, CK_DRIFT, CK_BOUND, CK_KPP_BOUND, CK_REFRESH_BOUND, CK_REF_DRAW, CK_COUNT };
 }  // namespace
 
-// the reference-seed k-means++ draw (kpp_refpick.hpp): four launches on `stream`; out = [picked index, total bits, chunks walked]
+// the reference-seed k-means++ draw (kpp_refpick.hpp) on `stream`; work = ref_pick_work_floats(N) floats, 8-byte aligned;
+// out = [picked index, total / end sum bits, chunks walked]
 namespace {
 uint32_t ref_pick_chunks(uint64_t N) { return (uint32_t)((N + KR_ELEMS - 1) / KR_ELEMS); }
 size_t ref_pick_work_floats(uint64_t N) { return (size_t)5 * ref_pick_chunks(N) + 64; }
-void ref_pick_launch(hipStream_t stream, float* pot, float* kpp_d, uint64_t N, float* work, float v01, unsigned long long* out) {
+struct RefWork {
+    float *cum, *csum;
+    uint32_t* expo;
+    uint2* meta;
+    uint32_t nc;
+};
+RefWork ref_work(float* work, uint64_t N) {
     const uint32_t nc = ref_pick_chunks(N);
-    float *cum = work, *csum = work + nc;
-    uint32_t* expo = reinterpret_cast<uint32_t*>(work + 2 * (size_t)nc);
-    uint2* meta = reinterpret_cast<uint2*>(work + 3 * (size_t)nc + (nc & 1u));  // 8-byte aligned
-    hipLaunchKernelGGL(k_kr_sums, dim3((nc + 3) / 4), dim3(256), 0, stream, pot, N, nc, csum);
-    hipLaunchKernelGGL(k_kr_scan, dim3(1), dim3(1024), 0, stream, csum, nc, expo);
-    hipLaunchKernelGGL(k_kr_chunks, dim3((nc + 3) / 4), dim3(256), 0, stream, pot, N, nc, expo, meta);
-    hipLaunchKernelGGL(k_kr_pick, dim3(1), dim3(64), 0, stream, pot, kpp_d, N, nc, meta, cum, v01, out);
+    return {work, work + nc, reinterpret_cast<uint32_t*>(work + 2 * (size_t)nc),
+            reinterpret_cast<uint2*>(work + 3 * (size_t)nc + (nc & 1u)), nc};  // 8-byte aligned
+}
+// the chunk summaries for a walk that starts from prefix_in
+void ref_summaries(hipStream_t stream, const float* pot, uint64_t N, const RefWork& w, float prefix_in) {
+    hipLaunchKernelGGL(k_kr_sums, dim3((w.nc + 3) / 4), dim3(256), 0, stream, pot, N, w.nc, w.csum);
+    hipLaunchKernelGGL(k_kr_scan, dim3(1), dim3(1024), 0, stream, w.csum, w.nc, prefix_in, w.expo);
+    hipLaunchKernelGGL(k_kr_chunks, dim3((w.nc + 3) / 4), dim3(256), 0, stream, pot, N, w.nc, w.expo, w.meta);
+}
+// one layer on one device: walk from 0, draw, pick in one launch
+void ref_pick_launch(hipStream_t stream, float* pot, float* kpp_d, uint64_t N, float* work, float v01, unsigned long long* out) {
+    const RefWork w = ref_work(work, N);
+    ref_summaries(stream, pot, N, w, 0.0f);
+    hipLaunchKernelGGL(k_kr_pick, dim3(1), dim3(64), 0, stream, pot, kpp_d, N, w.nc, w.meta, w.cum, v01, out);
+}
+// a shard: the walk from the exact sum in front of it, and (after the draw from the global total) the pick on the sums it left
+void ref_walk_launch(hipStream_t stream, const float* pot, uint64_t N, float* work, float prefix_in, unsigned long long* out) {
+    const RefWork w = ref_work(work, N);
+    ref_summaries(stream, pot, N, w, prefix_in);
+    hipLaunchKernelGGL(k_kr_walk, dim3(1), dim3(64), 0, stream, pot, N, w.nc, w.meta, w.cum, prefix_in, out);
+}
+void ref_find_launch(hipStream_t stream, float* pot, float* kpp_d, uint64_t N, float* work, float prefix_in, float x, unsigned long long* out) {
+    const RefWork w = ref_work(work, N);
+    hipLaunchKernelGGL(k_kr_find, dim3(1), dim3(64), 0, stream, pot, kpp_d, N, w.nc, w.cum, prefix_in, x, out);
 }
 }  // namespace
 
@@ -100,6 +125,10 @@ struct rp_kmeans {
     float* kpp_cum = nullptr;          // reference-seed draw (kpp_refpick.hpp): [5 x chunks] chunk-end sums, approximate sums, exponents, summaries
     unsigned long long* kr_out = nullptr;  // [4] picked index, total bits, chunks walked term by term
     uint64_t kr_walked = 0, kr_chunks = 0;  // over the layer's picks
+    rp_smallrng kr_rng{};              // ONE generator for the K picks, seeded from the street by rp_kmeans_kpp_begin
+    bool kr_begun = false;             // ... which has happened in reference mode
+    bool kr_walk_valid = false;        // kpp_cum holds the sums of rp_kmeans_kpp_ref_walk and the potentials have not changed since
+    float kr_prefix = 0.0f;            // that walk's prefix_in
     std::vector<void*> allocs;
     bool owns_counts = true;
     Points P{};
@@ -197,26 +226,37 @@ int dev_alloc(rp_kmeans* h, T** out, size_t count) {
     return RP_OK;
 }
 
-void ck_begin(rp_kmeans* h, int id) {
+// `also`: a second clock that counts the same interval (the reference draw is part of "kpp" and all of "ref_draw"): the SAME pair of
+// events, so that a clock inside a clock puts nothing more on the stream
+void ck_begin(rp_kmeans* h, int id, int also = -1) {
     if (!h->profiling) return;
     hipEvent_t a, b;
     (void)hipEventCreate(&a);
     (void)hipEventCreate(&b);
     (void)hipEventRecord(a, h->stream);
     h->clk[id].pending.emplace_back(a, b);
+    if (also >= 0) h->clk[also].shared.emplace_back(a, b);
 }
-void ck_end(rp_kmeans* h, int id) {
+void ck_end(rp_kmeans* h, int id, int also = -1) {
     if (!h->profiling) return;
     (void)hipEventRecord(h->clk[id].pending.back().second, h->stream);
     h->clk[id].launches += 1;
+    if (also >= 0) h->clk[also].launches += 1;
 }
 void ck_drain(rp_kmeans* h) {
+    auto elapsed = [](const std::pair<hipEvent_t, hipEvent_t>& pr) {
+        float ms = 0.0f;
+        (void)hipEventSynchronize(pr.second);
+        (void)hipEventElapsedTime(&ms, pr.first, pr.second);
+        return ms;
+    };
+    for (auto& c : h->clk) {  // every reader first: a shared pair is destroyed by the clock that owns it
+        for (auto& pr : c.shared) c.total_ms += elapsed(pr);
+        c.shared.clear();
+    }
     for (auto& c : h->clk) {
         for (auto& pr : c.pending) {
-            float ms = 0.0f;
-            (void)hipEventSynchronize(pr.second);
-            (void)hipEventElapsedTime(&ms, pr.first, pr.second);
-            c.total_ms += ms;
+            c.total_ms += elapsed(pr);
             (void)hipEventDestroy(pr.first);
             (void)hipEventDestroy(pr.second);
         }
@@ -913,6 +953,7 @@ int rp_kmeans_set_rng(rp_kmeans* h, rp_rng_kind kind, int street) {
         return rp::fail(RP_ERR_INVALID, "rp_kmeans_set_rng: bad argument");
     h->rng = kind;
     h->street = street;
+    h->kr_begun = h->kr_walk_valid = false;  // the generator is seeded by the next rp_kmeans_kpp_begin
     return RP_OK;
 }
 
@@ -969,6 +1010,74 @@ int rp_kmeans_kpp_begin(rp_kmeans* h) {
     h->bounds_ready = false;
     h->pot_is_min_d2 = false;
     std::fill(h->cent_m.begin(), h->cent_m.end(), 0u);
+    h->kr_begun = h->kr_walk_valid = false;
+    if (h->rng == RP_RNG_REFERENCE) {  // DefaultHasher::default(); self.street().hash(hasher); SmallRng::seed_from_u64(hasher.finish())
+        int rc;
+        rp_sip sh;
+        rp_defaulthasher_new(&sh);
+        rp_defaulthasher_write_u64(&sh, (uint64_t)(int64_t)h->street);  // a fieldless enum hashes its discriminant as isize
+        rp_smallrng_seed(&h->kr_rng, rp_defaulthasher_finish(&sh));
+        if (!h->kpp_cum && (rc = dev_alloc(h, &h->kpp_cum, ref_pick_work_floats(h->N)))) return rc;
+        if (!h->kr_out && (rc = dev_alloc(h, &h->kr_out, 4))) return rc;
+        h->kr_walked = h->kr_chunks = 0;
+        h->kr_begun = true;
+    }
+    return RP_OK;
+}
+
+// ---- the reference-seed draw of a point-sharded layer (rp_mi355x.h at rp_kmeans_set_rng) ----
+static int need_ref_begun(rp_kmeans* h, const char* who) {
+    if (h->rng != RP_RNG_REFERENCE)
+        return rp::fail(RP_ERR_INVALID, "%s: the layer draws with the counter generator; call rp_kmeans_set_rng(h, RP_RNG_REFERENCE, street) first", who);
+    if (!h->kr_begun) return rp::fail(RP_ERR_INVALID, "%s: call rp_kmeans_kpp_begin first (it seeds the generator from the street)", who);
+    return RP_OK;
+}
+int rp_kmeans_kpp_ref_walk(rp_kmeans* h, float prefix_in, float* prefix_out) {
+    if (!h || !prefix_out) return rp::fail(RP_ERR_INVALID, "rp_kmeans_kpp_ref_walk: NULL argument");
+    if (!(prefix_in >= 0.0f)) return rp::fail(RP_ERR_INVALID, "rp_kmeans_kpp_ref_walk: prefix_in is a running sum of weights >= 0");
+    int rc = need_ref_begun(h, "rp_kmeans_kpp_ref_walk");
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    h->kr_walk_valid = false;
+    ck_begin(h, CK_KPP, CK_REF_DRAW);
+    ref_walk_launch(h->stream, h->pot, h->N, h->kpp_cum, prefix_in, h->kr_out);
+    ck_end(h, CK_KPP, CK_REF_DRAW);
+    HIP_TRY(hipGetLastError());
+    unsigned long long out[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(out, h->kr_out, 24, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->kr_walked += out[2], h->kr_chunks += ref_pick_chunks(h->N);
+    h->kr_prefix = prefix_in;
+    h->kr_walk_valid = true;
+    *prefix_out = rp_u2f((uint32_t)out[1]);
+    return RP_OK;
+}
+int rp_kmeans_kpp_ref_draw(rp_kmeans* h, float total, float* x) {
+    if (!h || !x) return rp::fail(RP_ERR_INVALID, "rp_kmeans_kpp_ref_draw: NULL argument");
+    int rc = need_ref_begun(h, "rp_kmeans_kpp_ref_draw");
+    if (rc) return rc;
+    const float v01 = rp_u2f((rp_smallrng_next_u32(&h->kr_rng) >> 9) | 0x3f800000u) - 1.0f;  // UniformFloat<f32>: [1, 2) - 1
+    if (!(total > 0.0f))
+        return rp::fail(RP_ERR_INVALID, "rp_kmeans_kpp_ref_draw: every potential is zero (fewer distinct points than K; the reference panics here)");
+    *x = v01 * rp_uniform_f32_scale(total) + 0.0f;  // UniformFloat::sample: value0_1 * scale + low
+    return RP_OK;
+}
+int rp_kmeans_kpp_ref_pick(rp_kmeans* h, float x, uint64_t* index) {
+    if (!h || !index) return rp::fail(RP_ERR_INVALID, "rp_kmeans_kpp_ref_pick: NULL argument");
+    int rc = need_ref_begun(h, "rp_kmeans_kpp_ref_pick");
+    if (rc) return rc;
+    if (!h->kr_walk_valid)
+        return rp::fail(RP_ERR_INVALID, "rp_kmeans_kpp_ref_pick: call rp_kmeans_kpp_ref_walk first (and again after the potentials change)");
+    HIP_TRY(hipSetDevice(h->device));
+    ck_begin(h, CK_KPP, CK_REF_DRAW);
+    ref_find_launch(h->stream, h->pot, h->M.kpp_d, h->N, h->kpp_cum, h->kr_prefix, x, h->kr_out);
+    ck_end(h, CK_KPP, CK_REF_DRAW);
+    HIP_TRY(hipGetLastError());
+    unsigned long long win = 0;
+    HIP_TRY(hipMemcpyAsync(&win, h->kr_out, 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (win < h->N) h->kr_walk_valid = false;  // that potential is 0 now
+    *index = win;
     return RP_OK;
 }
 
@@ -1005,6 +1114,7 @@ int rp_kmeans_kpp_pick(rp_kmeans* h, uint64_t r, uint64_t* index) {
 int rp_kmeans_kpp_update(rp_kmeans* h, uint32_t k) {
     if (!h || k >= h->K) return rp::fail(RP_ERR_INVALID, "rp_kmeans_kpp_update: bad argument");
     HIP_TRY(hipSetDevice(h->device));
+    h->kr_walk_valid = false;  // the potentials change
     ck_begin(h, CK_KPP);
     if (h->kind == RP_METRIC_VARIATION)
         hipLaunchKernelGGL(k_kpp_update_var, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, h->P, h->cs[h->cur], k, h->K,
@@ -1127,23 +1237,13 @@ int rp_kmeans_init_centroids(rp_kmeans* h, uint64_t* chosen) {
     int rc = rp_kmeans_kpp_begin(h);
     if (rc) return rc;
     std::vector<uint32_t> hist(h->bins);
-    rp_smallrng rng;
-    if (h->rng == RP_RNG_REFERENCE) {  // DefaultHasher::default(); self.street().hash(hasher); SmallRng::seed_from_u64(hasher.finish())
-        rp_sip sh;
-        rp_defaulthasher_new(&sh);
-        rp_defaulthasher_write_u64(&sh, (uint64_t)(int64_t)h->street);  // a fieldless enum hashes its discriminant as isize
-        rp_smallrng_seed(&rng, rp_defaulthasher_finish(&sh));
-        if (!h->kpp_cum && (rc = dev_alloc(h, &h->kpp_cum, ref_pick_work_floats(h->N)))) return rc;
-        if (!h->kr_out && (rc = dev_alloc(h, &h->kr_out, 4))) return rc;
-        h->kr_walked = h->kr_chunks = 0;
-    }
     for (uint32_t k = 0; k < h->K; ++k) {
         uint64_t total = 0, pick = 0;
         if (h->rng == RP_RNG_REFERENCE) {
-            const float v01 = rp_u2f((rp_smallrng_next_u32(&rng) >> 9) | 0x3f800000u) - 1.0f;  // UniformFloat<f32>: [1, 2) - 1
-            ck_begin(h, CK_KPP);
+            const float v01 = rp_u2f((rp_smallrng_next_u32(&h->kr_rng) >> 9) | 0x3f800000u) - 1.0f;  // UniformFloat<f32>: [1, 2) - 1
+            ck_begin(h, CK_KPP, CK_REF_DRAW);
             ref_pick_launch(h->stream, h->pot, h->M.kpp_d, h->N, h->kpp_cum, v01, h->kr_out);
-            ck_end(h, CK_KPP);
+            ck_end(h, CK_KPP, CK_REF_DRAW);
             HIP_TRY(hipGetLastError());
             unsigned long long out[3] = {0, 0, 0};
             HIP_TRY(hipMemcpyAsync(out, h->kr_out, 24, hipMemcpyDeviceToHost, h->stream));
@@ -1589,9 +1689,10 @@ int rp_weighted_index_probe(int device, uint64_t n, const float* weights, float 
     HIP_TRY(hipSetDevice(device));
     float* d = nullptr;
     const size_t work = mode ? ref_pick_work_floats(n) : (size_t)((n + KR_CHUNK - 1) / KR_CHUNK);
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), (n + work + 8) * 4));
-    float* d_work = d + n;
-    unsigned long long* d_out = reinterpret_cast<unsigned long long*>(d_work + work + ((n + work) & 1u));
+    const size_t n_even = (size_t)((n + 1) & ~(uint64_t)1);  // the work buffers hold uint2 / u64: 8-byte aligned whatever n's parity
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), (n_even + work + 8) * 4));
+    float* d_work = d + n_even;
+    unsigned long long* d_out = reinterpret_cast<unsigned long long*>(d_work + work + (work & 1u));
     hipError_t e = hipMemcpy(d, weights, n * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(d_out, 0, 24);
     if (e == hipSuccess) {
@@ -1604,6 +1705,65 @@ int rp_weighted_index_probe(int device, uint64_t n, const float* weights, float 
     (void)hipFree(d);
     if (e != hipSuccess) return rp::fail(RP_ERR_HIP, "rp_weighted_index_probe: %s", hipGetErrorString(e));
     for (int i = 0; i < 3; ++i) out[i] = got[i];
+    return RP_OK;
+}
+
+// diagnostics (rp_mi355x_diag.h): the sharded protocol of rp_kmeans_kpp_ref_walk / _draw / _pick on n host weights cut into
+// nshards contiguous shards on one device: the chain of walks, x from the last end sum, the pick on the first shard whose end sum
+// exceeds x (the last point of the last shard if none does); out = [global index (n if the total is not > 0), bits of the total,
+// chunks walked term by term over all shards]
+int rp_weighted_index_probe_shards(int device, uint64_t n, const float* weights, uint32_t nshards, const uint64_t* cuts, float v01,
+                                   uint64_t* out, float* end_sums) {
+    if (!weights || !cuts || !out || !end_sums || n == 0 || nshards == 0 || cuts[0] != 0 || cuts[nshards] != n)
+        return rp::fail(RP_ERR_INVALID, "rp_weighted_index_probe_shards: bad argument");
+    for (uint32_t s = 0; s < nshards; ++s)
+        if (cuts[s + 1] <= cuts[s]) return rp::fail(RP_ERR_INVALID, "rp_weighted_index_probe_shards: shard %u is empty (cuts must increase)", s);
+    if (rp_device_count() <= 0) return rp::fail(RP_ERR_NO_DEVICE, "rp_weighted_index_probe_shards: no HIP device");
+    HIP_TRY(hipSetDevice(device));
+    // one allocation: [weights, padded to an even count][per shard: its work buffer, an even count][out: 3 u64]
+    const size_t n_even = (size_t)((n + 1) & ~(uint64_t)1);
+    std::vector<size_t> woff(nshards + 1, 0);
+    for (uint32_t s = 0; s < nshards; ++s) {
+        const size_t wf = ref_pick_work_floats(cuts[s + 1] - cuts[s]);
+        woff[s + 1] = woff[s] + ((wf + 1) & ~(size_t)1);
+    }
+    float* d = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), (n_even + woff[nshards] + 8) * 4));
+    float* d_work = d + n_even;
+    unsigned long long* d_out = reinterpret_cast<unsigned long long*>(d_work + woff[nshards]);
+    unsigned long long got[3] = {0, 0, 0};
+    uint64_t walked = 0, index = n;
+    float run = 0.0f;
+    hipError_t e = hipMemcpy(d, weights, n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d_out, 0, 24);
+    for (uint32_t s = 0; s < nshards && e == hipSuccess; ++s) {  // the hand-off: shard s starts from shard s-1's exact end sum
+        ref_walk_launch(nullptr, d + cuts[s], cuts[s + 1] - cuts[s], d_work + woff[s], run, d_out);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpy(got, d_out, 24, hipMemcpyDeviceToHost);
+        run = rp_u2f((uint32_t)got[1]);
+        end_sums[s] = run;
+        walked += got[2];
+    }
+    const float total = run;
+    if (e == hipSuccess && total > 0.0f) {
+        const float x = v01 * rp_uniform_f32_scale(total) + 0.0f;
+        uint32_t owner = 0;
+        while (owner < nshards && !(end_sums[owner] > x)) ++owner;
+        index = n - 1;  // partition_point's fallback
+        if (owner < nshards) {
+            const uint64_t ns = cuts[owner + 1] - cuts[owner];
+            ref_find_launch(nullptr, d + cuts[owner], nullptr, ns, d_work + woff[owner], owner ? end_sums[owner - 1] : 0.0f, x, d_out);
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpy(got, d_out, 8, hipMemcpyDeviceToHost);
+            if (got[0] < ns) index = cuts[owner] + got[0];
+        }
+    }
+    (void)hipFree(d);
+    if (e != hipSuccess) return rp::fail(RP_ERR_HIP, "rp_weighted_index_probe_shards: %s", hipGetErrorString(e));
+    out[0] = index;
+    out[1] = rp_f2u(total);
+    out[2] = walked;
+    if (!(total > 0.0f)) return rp::fail(RP_ERR_INVALID, "rp_weighted_index_probe_shards: the total weight is not > 0 (the reference panics here)");
     return RP_OK;
 }
 

@@ -107,6 +107,27 @@ class Layer:
     def kpp_update(self, k: int):
         _lib.check(self._lib.rp_kmeans_kpp_update(self._h, k))
 
+    # the same family in reference mode (set_rng("reference", street), then kpp_begin): WeightedIndex<f32>'s sequential running sum
+    # continued from shard to shard.  The sums and x cross as np.float32, bit for bit, never through Python arithmetic.
+    def kpp_ref_walk(self, prefix) -> np.float32:
+        """this shard's potentials walked in index order from ``prefix``, the exact end sum of the shard in front (0 on the first);
+        returns this shard's end sum"""
+        end = C.c_float()
+        _lib.check(self._lib.rp_kmeans_kpp_ref_walk(self._h, C.c_float(np.float32(prefix)), C.byref(end)))
+        return np.float32(end.value)
+
+    def kpp_ref_draw(self, total) -> np.float32:
+        """every rank, once per pick, with the LAST shard's end sum: one u32 of the layer's SmallRng -> x in [0, total)"""
+        x = C.c_float()
+        _lib.check(self._lib.rp_kmeans_kpp_ref_draw(self._h, C.c_float(np.float32(total)), C.byref(x)))
+        return np.float32(x.value)
+
+    def kpp_ref_pick(self, x) -> int | None:
+        """after kpp_ref_walk: the first local index whose running sum exceeds x (its potential becomes 0), None if none does"""
+        i = C.c_uint64()
+        _lib.check(self._lib.rp_kmeans_kpp_ref_pick(self._h, C.c_float(np.float32(x)), C.byref(i)))
+        return None if i.value >= self.N else i.value
+
     def init_bounds(self):
         _lib.check(self._lib.rp_kmeans_init_bounds(self._h))
 

@@ -177,9 +177,16 @@ class ShardedSolver:
 class ShardedLayer:
     """Point-sharded Elkan k-means: this rank owns the contiguous point range [lo, hi) of the global set."""
 
-    def __init__(self, engine, K: int, bins: int, seed: int, device="cpu", group=None):
+    def __init__(self, engine, K: int, bins: int, seed: int, device="cpu", group=None, rng="counter", street=1):
+        """``rng="reference"``: the k-means++ draw is Layer::init_centroids' own (DefaultHasher(street) -> SmallRng, one
+        WeightedIndex<f32> per pick), its running sum handed from rank to rank; ``street`` = the Street discriminant (1 = Flop)."""
+        if rng not in ("counter", "reference"):
+            raise ValueError(f"rng must be 'counter' or 'reference', not {rng!r}")
         self.engine = engine
         self.K, self.bins, self.seed = K, bins, seed
+        self.rng = rng
+        if rng == "reference":
+            engine.set_rng("reference", street)
         self.group = group
         self.rank = dist.get_rank(group)
         self.world = dist.get_world_size(group)
@@ -193,7 +200,10 @@ class ShardedLayer:
         self.off64 = ((self.words32 * 4) + 7) & ~7
 
     def init_centroids(self):
-        """Layer::init_centroids (k-means++, layer.rs:140-181) with a global exact-integer draw."""
+        """Layer::init_centroids (k-means++, layer.rs:140-181) with a global exact-integer draw, or (rng="reference") with the
+        reference's own WeightedIndex<f32> draw."""
+        if self.rng == "reference":
+            return self._init_centroids_reference()
         e = self.engine
         e.kpp_begin()
         chosen = []
@@ -232,6 +242,56 @@ class ShardedLayer:
             e.kpp_update(k)
             chosen.append((owner, idx if owner == self.rank else None))
         return chosen
+
+    def _init_centroids_reference(self):
+        """Per pick: the walks in rank order (rank r receives rank r-1's exact end sum as one f32, walks, hands its own on), every
+        rank's end sum gathered (the last one is the reference's total_weight), the same draw on every rank, the pick on the first
+        rank whose end sum exceeds x.  W - 1 hand-offs + 1 all-gather + the histogram broadcast per pick."""
+        e = self.engine
+        e.kpp_begin()
+        chosen = []
+        carry = torch.zeros(1, dtype=torch.float32)
+        if self.device != "cpu":
+            carry = carry.to(self.device)
+        for k in range(self.K):
+            prefix = np.float32(0)
+            if self.rank > 0:
+                dist.recv(carry, src=self._peer(self.rank - 1), group=self.group)
+                prefix = carry.cpu().numpy()[0]
+            end = e.kpp_ref_walk(prefix)
+            if self.rank + 1 < self.world:
+                carry.copy_(torch.from_numpy(np.array([end], dtype=np.float32)))
+                dist.send(carry, dst=self._peer(self.rank + 1), group=self.group)
+            ends = torch.zeros(self.world, dtype=torch.float32)
+            mine = torch.from_numpy(np.array([end], dtype=np.float32))
+            if self.device != "cpu":
+                ends, mine = ends.to(self.device), mine.to(self.device)
+            _all_gather_bytes(ends.view(torch.uint8), mine.view(torch.uint8), self.group, self.flat)
+            ends = ends.cpu().numpy()
+            x = e.kpp_ref_draw(ends[-1])  # raises where the reference panics (every potential 0), on every rank alike
+            owner = next((r for r in range(self.world) if ends[r] > x), None)
+            idx = e.kpp_ref_pick(x) if owner == self.rank else None
+            if owner is None:
+                # partition_point's fallback, the last point of the last shard: not reachable with finite weights >= 0 (end sums
+                # never decrease and x < total); kept for the non-finite cases the single kernel tolerates (the draw then zeroes
+                # no potential: kpp_update below lowers it to the point's distance from itself)
+                owner = self.world - 1
+                idx = e.N - 1 if owner == self.rank else None
+            elif owner == self.rank and idx is None:
+                raise RuntimeError("ShardedLayer: the owner's walk does not contain the drawn sum (potentials changed between walk and pick?)")
+            hist = torch.zeros(self.bins, dtype=torch.int64)
+            if owner == self.rank:
+                hist = torch.from_numpy(e.get_point(idx).astype(np.int64))
+            if self.device != "cpu":
+                hist = hist.to(self.device)
+            dist.broadcast(hist, src=self._peer(owner), group=self.group)
+            e.set_centroid(k, hist.cpu().numpy().astype(np.uint32))
+            e.kpp_update(k)
+            chosen.append((owner, idx))
+        return chosen
+
+    def _peer(self, rank_in_group: int) -> int:
+        return rank_in_group if self.group is None else dist.get_global_rank(self.group, rank_in_group)
 
     def _point_counts(self):
         n = torch.tensor([self.engine.N], dtype=torch.int64)

@@ -210,10 +210,11 @@ def cluster_river_sharded(device, group=None) -> Artifacts:
 
 
 def cluster_layer_sharded(street: str, below: Artifacts, tri=None, K=None, iterations=None, seed=None, log=None, group=None,
-                          limit=None) -> Artifacts:
+                          limit=None, libm="contract", rng="counter") -> Artifacts:
     """Layer::cluster with the points (and their Elkan bounds) sharded by rank: the table of the street below is
     replicated, each rank projects and owns a contiguous slice of this street's isomorphisms, centroid sums are
-    all-reduced every iteration (robopoker_amd.parallel.ShardedLayer), the final assignments are all-gathered."""
+    all-reduced every iteration (robopoker_amd.parallel.ShardedLayer), the final assignments are all-gathered.
+    libm="glibc" / rng="reference": as in ``cluster_layer``; the reference's draw runs its sums from rank to rank."""
     import torch.distributed as dist
 
     from .parallel import ShardedLayer
@@ -236,7 +237,9 @@ def cluster_layer_sharded(street: str, below: Artifacts, tri=None, K=None, itera
     table.close()
     seed = deuce.STREETS[street] if seed is None else seed
     engine = Layer(K, None, kind, tri, seed=seed, device=dev.index or 0, counts_dev_ptr=points.data_ptr(), shape=tuple(points.shape))
-    layer = ShardedLayer(engine, K, bins, seed, device=str(dev), group=group)
+    if libm != "contract":
+        engine.set_libm(libm)
+    layer = ShardedLayer(engine, K, bins, seed, device=str(dev), group=group, rng=rng, street=deuce.STREETS[street])
     t0 = time.perf_counter()
     layer.init_centroids()
     tm["init_s"] = time.perf_counter() - t0
@@ -259,11 +262,13 @@ def cluster_layer_sharded(street: str, below: Artifacts, tri=None, K=None, itera
     return Artifacts(street, obs, bucket, metric, future, weight, tm)
 
 
-def run_sharded(device=0, group=None, log=None, flop_iterations=None, turn_iterations=None) -> dict[str, Artifacts]:
+def run_sharded(device=0, group=None, log=None, flop_iterations=None, turn_iterations=None, libm="contract",
+                rng="counter") -> dict[str, Artifacts]:
     """``run`` with one process per GPU (launch with torch.distributed.run; backend nccl = RCCL over xGMI).  Every rank
     returns the same artifacts."""
     out = {"rive": cluster_river_sharded(device, group)}
-    out["turn"] = cluster_layer_sharded("turn", out["rive"], iterations=turn_iterations, log=log, group=group)
-    out["flop"] = cluster_layer_sharded("flop", out["turn"], tri=out["turn"].metric, iterations=flop_iterations, log=log, group=group)
+    out["turn"] = cluster_layer_sharded("turn", out["rive"], iterations=turn_iterations, log=log, group=group, libm=libm, rng=rng)
+    out["flop"] = cluster_layer_sharded("flop", out["turn"], tri=out["turn"].metric, iterations=flop_iterations, log=log, group=group,
+                                        libm=libm, rng=rng)
     out["pref"] = cluster_preflop(device, out["flop"], out["flop"].metric)  # 169 points: every rank computes them
     return out
