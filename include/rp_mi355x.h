@@ -312,6 +312,10 @@ RP_API int rp_mccfr_step_comm(rp_mccfr* h, rp_comm* c, uint32_t steps, uint32_t 
  * game), 1 = per-lane DFS with the tree in LDS (small games), 2 = instantiated over the game's compile-time action
  * skeleton (Kuhn / Leduc shapes, external sampling; csrc/traverse_static.hpp).  All three produce identical Decisions. */
 RP_API int rp_mccfr_traversal_variant(rp_mccfr* h, int* out);
+/* Variant 2 only: the size of the table of packed rows (one row of infoset ids, payoffs and draw keys per sequence of chance
+ * outcomes) the traversal reads the game through; 0 when it follows the child records node by node instead (chance nodes of one
+ * skeleton node with different numbers of outcomes, or RP_TRAV_NO_FLAT=1: the independent cross-check).  Same Decisions. */
+RP_API int rp_mccfr_traversal_rows_bytes(rp_mccfr* h, size_t* out);
 /* Which compile-time action skeleton a game table matches node for node, for every chance outcome (host only, no device
  * needed): 0 none (the generic traversal kernels), 1 Kuhn's, 2 Leduc's (any number of ranks). */
 RP_API int rp_game_skeleton(const rp_game_table* game, int* out);

@@ -325,6 +325,8 @@ struct DevInfoTab {
     float* total;    // [n_infos]
     uint32_t* keep;  // [n_infos] edges with cum_regret > prune_threshold
     float2* sq;      // [n_infos][A] (sigma, q) side by side: one load per edge in the traversal's sweeps
+    float* row2;     // [n_infos][8] two-action games (NULL otherwise): {sigma0, sigma1, q0, q1, total, cum0, keep, 0} — all a node of
+                     // the skeleton traversal needs of its infoset, in one 32-byte row (traverse_static.hpp)
 };
 
 __device__ __forceinline__ void prepare_one(const DevGame& g, const DevTables& t, const StepParams& p, const DevInfoTab& it,
@@ -340,12 +342,22 @@ __device__ __forceinline__ void prepare_one(const DevGame& g, const DevTables& t
         const float qa = d_sampling_weight(t, A, info, a, denom, p) / z;
         it.q[info * A + a] = qa;
         it.sq[info * A + a] = make_float2(it.sigma[info * A + a], qa);
+        if (it.row2) {
+            it.row2[info * 8u + a] = it.sigma[info * A + a];
+            it.row2[info * 8u + 2u + a] = qa;
+        }
         total += rp_maxf(qa, RP_EPSILON);
         it.cum[info * A + a] = total;
         if (t.regret[info * A + a] > p.prune_threshold) keep |= 1u << a;
     }
     it.total[info] = total;
     it.keep[info] = keep;
+    if (it.row2) {
+        it.row2[info * 8u + 4u] = total;
+        it.row2[info * 8u + 5u] = it.cum[info * A];
+        it.row2[info * 8u + 6u] = rp_u2f(keep);
+        it.row2[info * 8u + 7u] = 0.0f;
+    }
 }
 __global__ void k_prepare_infos(DevGame g, DevTables t, StepParams p, DevInfoTab it) {
     const uint32_t info = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1648,7 +1660,8 @@ struct rp_mccfr {
     void* d_states = nullptr;
     void* d_children = nullptr;
     void* d_kids = nullptr;
-    void* d_flat = nullptr;  // DevGame::flat
+    void* d_rows = nullptr;  // DevGame::rows
+    size_t rows_bytes = 0;
     void* d_payoffs = nullptr;
     void* d_info_actions = nullptr;
     void* d_info_player = nullptr;
@@ -1898,15 +1911,17 @@ bool skel_matches(const rp_game_table* game, const std::vector<uint32_t>& childr
     return match(game->train_root, 0);
 }
 
-// DevGame::flat for a game that matches skeleton G: records re-indexed by (skeleton node, chance outcomes on its path).  Returns
-// false (no table) when two instances of a skeleton chance node differ in their number of outcomes.
+// DevGame::rows for a game that matches skeleton G: the words of every group of nodes (RowLayout, traverse_static.hpp), one row per
+// sequence of chance outcomes on the path.  Returns false (no table) when two instances of a skeleton chance node differ in their
+// number of outcomes, or when the table would be unreasonably large.
 template <class G>
-bool build_flat(const rp_game_table* game, const std::vector<uint32_t>& children, const std::function<uint4(uint32_t)>& rec_of,
-                std::vector<uint4>& flat, uint32_t* base, uint32_t* fan) {
+bool build_rows(const rp_game_table* game, const std::vector<uint32_t>& children, const std::function<uint4(uint32_t)>& rec_of,
+                std::vector<uint32_t>& rows, uint32_t* base, uint32_t* fan) {
     constexpr Skeleton S = SkelOf<G>::S;
+    constexpr RowLayout R = SkelOf<G>::R;
     std::vector<std::vector<int>> kids(S.n);
     for (int s = 1; s < S.n; ++s) kids[S.parent[s]].push_back(s);
-    for (int s = 0; s < S.n; ++s) fan[s] = 0;
+    for (int s = 0; s < S.n; ++s) fan[s] = base[s] = 0;
     bool uniform = true;
     std::function<void(uint32_t, int)> fans = [&](uint32_t sid, int s) {
         const rp_state& st = game->states[sid];
@@ -1920,20 +1935,33 @@ bool build_flat(const rp_game_table* game, const std::vector<uint32_t>& children
     };
     fans(game->train_root, 0);
     if (!uniform) return false;
-    // entries of node s = product of the fans of its chance ancestors
-    std::vector<uint64_t> count(S.n, 1);
-    uint64_t total = 0;
-    for (int s = 0; s < S.n; ++s) {
-        for (int c = 0; c < s; ++c)
-            if (S.kind[c] == SK_CHANCE && s <= S.end[c]) count[s] *= fan[c];
-        base[s] = (uint32_t)total;
-        total += count[s];
+    // rows of chance node c = product of the fans of c and of its chance ancestors; every group starts on a 128-byte line
+    uint64_t total = 0;  // words
+    for (int c = 0; c < S.n; ++c) {
+        if (S.kind[c] != SK_CHANCE) continue;
+        uint64_t count = 1;
+        for (int a = 0; a <= c; ++a)
+            if (S.kind[a] == SK_CHANCE && c <= S.end[a]) count *= fan[a];
+        base[c] = (uint32_t)(total / 4);
+        total += (count * (uint64_t)R.stride[c] + 31) & ~(uint64_t)31;
+        if (total > (1ull << 28)) return false;  // 1 GB; also keeps a row's byte offset in 32 bits
     }
-    if (total > (1ull << 26)) return false;
-    flat.assign(total, make_uint4(0, 0, 0, 0));
-    std::function<void(uint32_t, int, uint64_t)> fill = [&](uint32_t sid, int s, uint64_t idx) {
+    rows.assign(total, 0u);
+    std::function<void(uint32_t, int, uint64_t)> fill = [&](uint32_t sid, int s, uint64_t idx) {  // idx: the outcomes above s
         const rp_state& st = game->states[sid];
-        flat[base[s] + idx] = rec_of(sid);
+        if (const int c = R.group[s]; c >= 0) {
+            uint32_t* row = &rows[(size_t)base[c] * 4 + idx * (uint64_t)R.stride[c]];
+            const uint4 r = rec_of(sid);
+            if (S.kind[s] == SK_CHANCE) {
+                row[R.word[s]] = r.w;
+                row[R.word2[s]] = r.y;
+            } else if (S.kind[s] == SK_TERMINAL) {
+                row[R.word[s]] = r.y;
+                row[R.word2[s]] = r.z;
+            } else {
+                row[R.word[s]] = r.y;
+            }
+        }
         if (S.kind[s] == SK_CHANCE) {
             for (uint32_t k = 0; k < st.n_children; ++k) fill(children[st.offset + k], kids[s][0], idx * fan[s] + k);
         } else if (S.kind[s] != SK_TERMINAL) {
@@ -2325,7 +2353,7 @@ int rp_mccfr_create(const rp_game_table* game, rp_regret_kind r, rp_weight_kind 
     CREATE_TRY(hipMalloc(&h->d_counters, (size_t)METRIC_STRIPES * METRIC_STRIDE * sizeof(unsigned long long)));
     CREATE_TRY(hipMemset(h->d_counters, 0, (size_t)METRIC_STRIPES * METRIC_STRIDE * sizeof(unsigned long long)));
     CREATE_TRY(hipMalloc(&h->d_summary, summary_bytes_of(h)));
-    CREATE_TRY(hipMalloc(&h->d_itab, (5 * cells + 2 * (size_t)game->n_infos + 4) * 4));
+    CREATE_TRY(hipMalloc(&h->d_itab, (5 * cells + 2 * (size_t)game->n_infos + 4 + 8 * (size_t)game->n_infos + 8) * 4));
     {
         float* f = reinterpret_cast<float*>(h->d_itab);
         h->itab.sigma = f;
@@ -2335,6 +2363,8 @@ int rp_mccfr_create(const rp_game_table* game, rp_regret_kind r, rp_weight_kind 
         h->itab.keep = reinterpret_cast<uint32_t*>(f + 3 * cells + game->n_infos);
         const size_t used = 3 * cells + 2 * (size_t)game->n_infos;
         h->itab.sq = reinterpret_cast<float2*>(f + ((used + 3) & ~(size_t)3));  // 16-byte aligned: a two-action row is one float4
+        const size_t used2 = ((used + 3) & ~(size_t)3) + 2 * cells;
+        h->itab.row2 = game->max_actions == 2 ? f + ((used2 + 7) & ~(size_t)7) : nullptr;  // 32-byte aligned rows
     }
     uint32_t maxstack = 1;
     sampled_tree_bounds(h, &h->maxdec, &maxstack, &h->maxint);
@@ -2354,8 +2384,8 @@ int rp_mccfr_create(const rp_game_table* game, rp_regret_kind r, rp_weight_kind 
         if (skel_matches<KuhnSkel>(game, h->children)) h->static_skel = 1;
         else if (skel_matches<LeducSkel>(game, h->children)) h->static_skel = 2;
     }
-    h->g.flat = nullptr;
-    if (h->static_skel) {
+    h->g.rows = nullptr;
+    if (h->static_skel && getenv("RP_TRAV_NO_FLAT") == nullptr) {
         const std::function<uint4(uint32_t)> rec_of = [&](uint32_t sid) {
             uint4 r = packed[sid];
             r.w = sid;
@@ -2365,13 +2395,14 @@ int rp_mccfr_create(const rp_game_table* game, rp_regret_kind r, rp_weight_kind 
             }
             return r;
         };
-        std::vector<uint4> flat;
-        const bool ok = h->static_skel == 1 ? build_flat<KuhnSkel>(game, h->children, rec_of, flat, h->g.flat_base, h->g.flat_fan)
-                                            : build_flat<LeducSkel>(game, h->children, rec_of, flat, h->g.flat_base, h->g.flat_fan);
+        std::vector<uint32_t> rows;
+        const bool ok = h->static_skel == 1 ? build_rows<KuhnSkel>(game, h->children, rec_of, rows, h->g.row_base, h->g.row_fan)
+                                            : build_rows<LeducSkel>(game, h->children, rec_of, rows, h->g.row_base, h->g.row_fan);
         if (ok) {
-            CREATE_TRY(hipMalloc(&h->d_flat, flat.size() * sizeof(uint4)));
-            CREATE_TRY(hipMemcpy(h->d_flat, flat.data(), flat.size() * sizeof(uint4), hipMemcpyHostToDevice));
-            h->g.flat = reinterpret_cast<const uint4*>(h->d_flat);
+            CREATE_TRY(hipMalloc(&h->d_rows, rows.size() * 4));
+            CREATE_TRY(hipMemcpy(h->d_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
+            h->g.rows = reinterpret_cast<const uint4*>(h->d_rows);
+            h->rows_bytes = rows.size() * 4;
         }
     }
     rc = alloc_batch_buffers(h, batch_size);
@@ -2394,7 +2425,7 @@ int rp_mccfr_destroy(rp_mccfr* h) {
     clock_drain(h->clk_traverse);
     clock_drain(h->clk_compact);
     clock_drain(h->clk_update);
-    void* ptrs[] = {h->d_info_streams, h->d_chance_streams, h->d_ref_mid, h->d_flat, h->d_states, h->d_children, h->d_kids, h->d_payoffs, h->d_info_actions, h->d_info_player, h->d_scratch,
+    void* ptrs[] = {h->d_info_streams, h->d_chance_streams, h->d_ref_mid, h->d_rows, h->d_states, h->d_children, h->d_kids, h->d_payoffs, h->d_info_actions, h->d_info_player, h->d_scratch,
                     h->d_dec, h->d_sorted, h->d_bmaps, h->d_itab, h->d_summary, h->d_window, h->d_counters, h->t.regret, h->t.weight, h->t.payoff,
                     h->t.visits};
     for (void* p : ptrs)
@@ -2841,6 +2872,12 @@ int rp_game_skeleton(const rp_game_table* game, int* out) {
     if (rc) return rc;
     const std::vector<uint32_t> children(game->children, game->children + game->n_children);
     *out = skel_matches<KuhnSkel>(game, children) ? 1 : (skel_matches<LeducSkel>(game, children) ? 2 : 0);
+    return RP_OK;
+}
+
+int rp_mccfr_traversal_rows_bytes(rp_mccfr* h, size_t* out) {
+    if (!h || !out) return rp::fail(RP_ERR_INVALID, "rp_mccfr_traversal_rows_bytes: NULL argument");
+    *out = h->rows_bytes;
     return RP_OK;
 }
 

@@ -26,12 +26,15 @@ struct DevGame {
     uint32_t root;                // train_root
     uint4 root_rec;               // states[root] with w = root
     // games that match a compile-time skeleton (traverse_static.hpp), when every instance of a skeleton chance node has the
-    // same number of outcomes: the record of skeleton node s for the chance outcomes (o_1, o_2, ...) on its path, root first,
-    // sits at flat[flat_base[s] + ((o_1 * fan_2 + o_2) * fan_3 + ...)] — a node's record then depends on the sampled outcomes
-    // only, not on its parent's record (a chain of ten dependent loads becomes four)
-    const uint4* flat;            // NULL: follow the child records
-    uint32_t flat_base[48];
-    uint32_t flat_fan[48];        // outcomes of skeleton chance node s
+    // same number of outcomes: the words the traversal needs of the nodes below skeleton chance node c, down to the next chance
+    // nodes (infoset ids, payoffs, the next draws' keys: RowLayout, traverse_static.hpp), side by side in one row per sequence of
+    // chance outcomes (o_1, o_2, ..., o_c) on the path, root first: row (o_1 * fan_2 + o_2) * fan_3 + ... of the rows at
+    // rows + row_base[c], RowLayout::stride[c] words apart.  What a node holds then depends on the sampled outcomes only, not on
+    // its parent's record (a chain of ten dependent loads becomes four), and a lane fetches one row per chance outcome instead of
+    // one record per node (Leduc: 13 16-byte loads from 5 rows instead of 37 from 37 records; the table is 25 KB, not 56)
+    const uint4* rows;            // NULL: follow the child records
+    uint32_t row_base[48];        // by skeleton chance node, in 16-byte units; a multiple of 8 (128-byte lines)
+    uint32_t row_fan[48];         // outcomes of skeleton chance node s
 };
 
 // regret/strategy tables, SoA by field, row-major [info][A] (Encounter, solver/encounter.rs:22-27)

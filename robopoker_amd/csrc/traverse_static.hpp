@@ -114,10 +114,68 @@ struct LeducSkel {
     }
 };
 
+// ---- the packed rows of a skeleton (DevGame::rows) -------------------------------------------------------------------
+// The nodes between a chance node c and the next chance nodes below it (c's GROUP: every node whose nearest chance ancestor is
+// c) are reached under the same sampled outcomes, so the words the traversal needs of them sit side by side in one row per
+// (c, outcomes on the path down to and including c's).  A decision node has one word (its infoset id), a chance node two (its
+// state id = the hash key of its draw; chance_info for the reference-seed draw), a terminal node two (the two players' payoffs).
+// The words are ordered by class — infoset ids, state ids, player 0's payoffs, player 1's payoffs, chance_infos — so that an
+// instantiation for one walker / one draw kind finds what it uses in as few 16-byte slices as possible.  A row is padded to a
+// power of two words (to a multiple of 32 above 32): 16-byte aligned slices that never straddle a 128-byte line.
+struct RowLayout {
+    int group[SK_MAXN] = {};   // node s: its nearest chance ancestor, -1 at the root
+    int word[SK_MAXN] = {};    // node s: decision: infoset id; chance: state id; terminal: payoff of player 0
+    int word2[SK_MAXN] = {};   // node s: chance: chance_info; terminal: payoff of player 1
+    int words[SK_MAXN] = {};   // chance node c: words of its group
+    int stride[SK_MAXN] = {};  // chance node c: words from one row to the next
+};
+constexpr RowLayout make_rows(const Skeleton& S) {
+    RowLayout L;
+    for (int s = 0; s < S.n; ++s) {
+        int p = S.parent[s];
+        while (p >= 0 && S.kind[p] != SK_CHANCE) p = S.parent[p];
+        L.group[s] = p;
+    }
+    for (int c = 0; c < S.n; ++c) {
+        if (S.kind[c] != SK_CHANCE) continue;
+        int at = 0;
+        for (int cls = 0; cls < 5; ++cls)
+            for (int s = c + 1; s <= S.end[c]; ++s) {
+                if (L.group[s] != c) continue;
+                const bool dec = S.kind[s] == SK_P0 || S.kind[s] == SK_P1;
+                if ((cls == 0 && dec) || (cls == 1 && S.kind[s] == SK_CHANCE) || (cls == 2 && S.kind[s] == SK_TERMINAL)) L.word[s] = at++;
+                if ((cls == 3 && S.kind[s] == SK_TERMINAL) || (cls == 4 && S.kind[s] == SK_CHANCE)) L.word2[s] = at++;
+            }
+        L.words[c] = at;
+        const int padded = (at + 3) & ~3;
+        int st = 4;
+        while (st < padded && st < 32) st *= 2;
+        L.stride[c] = padded <= 32 ? st : (padded + 31) & ~31;
+    }
+    return L;
+}
+
 template <class G>
 struct SkelOf {
     static constexpr Skeleton S = G::make();
+    static constexpr RowLayout R = make_rows(S);
 };
+
+// does an instantiation (walker W, reference draws or not) use a word of slice k (words 4k .. 4k+3) of group c's row?
+template <class G, int W, bool REF>
+constexpr bool sk_slice_used(int c, int k) {
+    constexpr Skeleton S = SkelOf<G>::S;
+    constexpr RowLayout R = SkelOf<G>::R;
+    for (int s = c + 1; s <= S.end[c]; ++s) {
+        if (R.group[s] != c) continue;
+        if (S.kind[s] == SK_TERMINAL) {
+            if ((W == 0 ? R.word[s] : R.word2[s]) / 4 == k) return true;
+        } else if (R.word[s] / 4 == k || (S.kind[s] == SK_CHANCE && REF && R.word2[s] / 4 == k)) {
+            return true;
+        }
+    }
+    return false;
+}
 
 // the skeleton child of node s along edge e is a terminal node?  (walker nodes: the Pluribus exemption, pluribus.rs:96)
 template <class G>
@@ -130,6 +188,9 @@ constexpr bool sk_child_terminal(int s, int e) {
 static_assert(SkelOf<KuhnSkel>::S.n == 11, "Kuhn: two deals, four decision nodes, five terminals");
 static_assert(SkelOf<LeducSkel>::S.n == 38, "Leduc: two deals, 4 + 3 x 4 decision nodes, three board draws, 2 + 3 x 5 terminals");
 static_assert(SkelOf<LeducSkel>::S.end[0] == 37 && SkelOf<LeducSkel>::S.kind[2] == SK_P0, "pre-order, the first decision is P0's");
+static_assert(SkelOf<LeducSkel>::R.words[0] == 2 && SkelOf<LeducSkel>::R.words[1] == 14 && SkelOf<LeducSkel>::R.stride[1] == 16,
+              "Leduc: the second deal alone below the first; round 1 = 4 infosets, 3 board deals, 2 folds in a 64-byte row");
+static_assert(SkelOf<KuhnSkel>::R.words[1] == 14 && SkelOf<KuhnSkel>::R.stride[1] == 16, "Kuhn: 4 infosets, 5 terminals");
 
 // compile-time loops: f(std::integral_constant<int, I>) for I = LO .. HI-1, ascending / descending
 template <int I, int HI, class F>
@@ -153,7 +214,10 @@ __device__ __forceinline__ void sk_for_down(F&& f) {  // I = HI-1 down to LO
 // ascending node index (= the order of Tree::partition's spans).  Returns the number of nodes of the sampled tree.
 // on_decision's `mask`: the expanded edges (3 under external sampling).
 // REF: the draws come from the reference's own chain (rp_rng_kind RP_RNG_REFERENCE, mccfr_kernels.hpp d_draw_*).
-template <class G, int W, bool PRUNED, bool REF, class OnBuilt, class OnDecision>
+// ROWS: what a node holds comes from the packed rows (DevGame::rows), one row per chance outcome; else from the child records
+// (DevGame::kids), one dependent load per node.  The kernels branch once, on g.rows (wave-uniform), around the whole traversal:
+// with the choice made per load, the two variants' loads are merged behind the join and lose their width.
+template <class G, int W, bool PRUNED, bool REF, bool ROWS, class OnBuilt, class OnDecision>
 __device__ __forceinline__ uint32_t static_traverse(const DevGame& g, const DevInfoTab& it, const StepParams& p, uint64_t tree_id,
                                                     bool present, OnBuilt&& on_built, OnDecision&& on_decision) {
     using SK = SkelOf<G>;
@@ -162,57 +226,90 @@ __device__ __forceinline__ uint32_t static_traverse(const DevGame& g, const DevI
     constexpr int K_OPP = W == 0 ? SK_P1 : SK_P0;
 
     // ---- TreeBuilder::build over the skeleton ----------------------------------------------------------------------
-    uint32_t rx[N], ry[N], rz[N], rw[N];  // the node's record (DevGame::kids): turn | n_children << 8, info / payoff0, offset / payoff1, state
-    uint32_t pick[N];                     // chance: the sampled outcome; opponent: the sampled action; walker (PRUNED): the surviving edges
+    uint32_t ry[N], rz[N], rw[N];  // the node's words: infoset id / chance_info, child offset (the child-record chain only), state id
+    uint32_t pay[N];               // terminal: the walker's payoff (bits)
+    uint32_t nout[N];              // chance: the number of outcomes
+    uint32_t ridx[N];              // chance: the row index of its group = the outcomes on the path, mixed radix, root first
+    uint32_t pick[N];              // chance: the sampled outcome; opponent: the sampled action; walker (PRUNED): the surviving edges
     bool live[N];
     float sg0[N], sg1[N], q0[N], q1[N];   // (sigma, q) of a player node's two edges
     // every draw of this tree: rp_node_hash(seed, epoch, tree, key) with the (seed, epoch, tree) part hashed once
     const uint64_t th = rp_node_hash_tree(rp_node_hash_step(p.seed, p.epoch), tree_id);
-    rx[0] = g.root_rec.x;
+    const char* const irows = reinterpret_cast<const char*>(it.row2);
     ry[0] = g.root_rec.y;
     rz[0] = g.root_rec.z;
     rw[0] = g.root_rec.w;
     live[0] = present;
+    nout[0] = ROWS ? g.row_fan[0] : (g.root_rec.x >> 8) & 0xffu;
     sk_for<0, N>([&](auto I) __attribute__((always_inline)) {
         constexpr int s = I;
         constexpr int par = SK::S.parent[s];
         if constexpr (par >= 0) {
-            uint4 r;
-            if (g.flat) {  // wave-uniform: the record by the chance outcomes on the path (DevGame::flat)
-                uint32_t idx = 0;
-                sk_for<0, s>([&](auto C) __attribute__((always_inline)) {
-                    constexpr int c = C;
-                    if constexpr (SK::S.kind[c] == SK_CHANCE && s <= SK::S.end[c]) idx = idx * g.flat_fan[c] + pick[c];
-                });
-                r = g.flat[g.flat_base[s] + idx];
-            } else {
+            if constexpr (!ROWS) {
                 uint32_t k = (uint32_t)SK::S.edge[s];
                 if constexpr (SK::S.kind[par] == SK_CHANCE) k = pick[par];
-                r = g.kids[rz[par] + k];
+                const uint4 r = g.kids[rz[par] + k];
+                ry[s] = r.y;
+                rz[s] = r.z;
+                rw[s] = r.w;
+                pay[s] = W == 0 ? r.y : r.z;
+                nout[s] = (r.x >> 8) & 0xffu;
+            } else if constexpr (SK::S.kind[par] == SK_CHANCE) {  // the first node of par's group: the whole row, by slices
+                constexpr int c = par;
+                constexpr int up = SK::R.group[c];
+                if constexpr (up >= 0) ridx[c] = ridx[up] * g.row_fan[c] + pick[c];
+                else ridx[c] = pick[c];
+                // one scalar base, one 32-bit lane offset, the slices at immediate offsets
+                const char* const row = reinterpret_cast<const char*>(g.rows + g.row_base[c]);
+                const uint32_t off = ridx[c] * (uint32_t)(SK::R.stride[c] * 4);
+                constexpr int NS = (SK::R.words[c] + 3) / 4;
+                uint32_t w[NS * 4];
+                sk_for<0, NS>([&](auto K) __attribute__((always_inline)) {
+                    constexpr int k = K;
+                    if constexpr (sk_slice_used<G, W, REF>(c, k)) {
+                        const uint4 v = *reinterpret_cast<const uint4*>(row + off + (uint32_t)(k * 16));
+                        w[4 * k + 0] = v.x;
+                        w[4 * k + 1] = v.y;
+                        w[4 * k + 2] = v.z;
+                        w[4 * k + 3] = v.w;
+                    }
+                });
+                sk_for<s, SK::S.end[c] + 1>([&](auto M) __attribute__((always_inline)) {
+                    constexpr int m = M;
+                    if constexpr (SK::R.group[m] == c) {
+                        if constexpr (SK::S.kind[m] == SK_TERMINAL) {
+                            pay[m] = w[W == 0 ? SK::R.word[m] : SK::R.word2[m]];
+                        } else if constexpr (SK::S.kind[m] == SK_CHANCE) {
+                            rw[m] = w[SK::R.word[m]];
+                            if constexpr (REF) ry[m] = w[SK::R.word2[m]];
+                            nout[m] = g.row_fan[m];
+                        } else {
+                            ry[m] = w[SK::R.word[m]];
+                        }
+                    }
+                });
             }
-            rx[s] = r.x;
-            ry[s] = r.y;
-            rz[s] = r.z;
-            rw[s] = r.w;
             if constexpr (SK::S.kind[par] == K_OPP) live[s] = live[par] && pick[par] == (uint32_t)SK::S.edge[s];
             else if constexpr (PRUNED && SK::S.kind[par] == K_WALKER) live[s] = live[par] && ((pick[par] >> SK::S.edge[s]) & 1u);
             else live[s] = live[par];
         }
         if constexpr (SK::S.kind[s] == SK_CHANCE) {  // SamplingScheme::sample at a chance node: uniform (external.rs:41-64)
-            const uint32_t nout = (rx[s] >> 8) & 0xffu, ci = ry[s];  // a chance record's y = chance_info; 0: the root deal (thread RNG in the reference)
-            if (REF && ci) pick[s] = rp_ref_draw_range(rp_ref_seed_finish(&p.ref_chance[ci - 1u], tree_id), nout);
-            else pick[s] = rp_pick_uniform(rp_node_hash_key(th, 0x80000000ull | rw[s]), nout);
+            // ry = chance_info (read under REF only); 0: the root deal (thread RNG in the reference)
+            if (REF && ry[s]) pick[s] = rp_ref_draw_range(rp_ref_seed_finish(&p.ref_chance[ry[s] - 1u], tree_id), nout[s]);
+            else pick[s] = rp_pick_uniform(rp_node_hash_key(th, 0x80000000ull | rw[s]), nout[s]);
         } else if constexpr (SK::S.kind[s] == SK_P0 || SK::S.kind[s] == SK_P1) {
             const uint32_t info = ry[s];
-            const float4 f = *reinterpret_cast<const float4*>(&it.sq[info * 2u]);
+            const char* const ir = irows + info * 32u;  // DevInfoTab::row2: {sigma0, sigma1, q0, q1, total, cum0, keep, 0}
+            const float4 f = *reinterpret_cast<const float4*>(ir);
             sg0[s] = f.x;
-            q0[s] = f.y;
-            sg1[s] = f.z;
+            sg1[s] = f.y;
+            q0[s] = f.z;
             q1[s] = f.w;
             if constexpr (SK::S.kind[s] == K_OPP) {  // WeightedIndex over max(q, EPSILON): two actions = one threshold
-                const float x = REF ? rp_ref_draw_weight(rp_ref_seed_finish(&p.ref_info[info], tree_id), it.total[info])
-                                    : rp_u01(rp_node_hash_key(th, info)) * it.total[info];
-                pick[s] = it.cum[info * 2u] <= x ? 1u : 0u;
+                const float2 tc = *reinterpret_cast<const float2*>(ir + 16);  // (total, cum[0])
+                const float x = REF ? rp_ref_draw_weight(rp_ref_seed_finish(&p.ref_info[info], tree_id), tc.x)
+                                    : rp_u01(rp_node_hash_key(th, info)) * tc.x;
+                pick[s] = tc.y <= x ? 1u : 0u;
             } else if constexpr (PRUNED) {  // SamplingScheme::sample at a walker node (d_sample_mask_tab, the same draw and masks)
                 uint32_t mask = 3u;
                 bool prune = true;
@@ -221,7 +318,7 @@ __device__ __forceinline__ uint32_t static_traverse(const DevGame& g, const DevI
                             !((REF ? rp_ref_draw_f32(rp_ref_seed_finish(&p.ref_info[info], tree_id)) : rp_u01(rp_node_hash_key(th, info))) <
                               p.prune_explore);
                 if (prune) {
-                    mask = it.keep[info] & 3u;
+                    mask = *reinterpret_cast<const uint32_t*>(ir + 24) & 3u;
                     if (p.S == RP_SAMPLING_PLURIBUS)
                         mask |= (sk_child_terminal<G>(s, 0) ? 1u : 0u) | (sk_child_terminal<G>(s, 1) ? 2u : 0u);
                     mask = mask ? mask : 3u;  // pruning.rs:64, pluribus.rs:99
@@ -258,7 +355,7 @@ __device__ __forceinline__ uint32_t static_traverse(const DevGame& g, const DevI
                     }
                 }
                 if constexpr (SK::S.kind[n] == SK_TERMINAL) {
-                    const float v = r / sm * rp_u2f(W == 0 ? ry[n] : rz[n]);
+                    const float v = r / sm * rp_u2f(pay[n]);
                     if constexpr (par == j) tv[e] = v;
                     else acc[par] = live[n] ? acc[par] + v : acc[par];
                 } else {
@@ -324,8 +421,8 @@ __global__ __launch_bounds__(256) void k_traverse_static(DevGame g, DevInfoTab i
     if (lane >= p.batch) return;
     const size_t D = dc.stride;
     uint32_t ndec = 0;
-    const uint32_t nn = static_traverse<G, W, PRUNED, REF>(
-        g, it, p, p.tree_base + lane, true, [](auto, auto) __attribute__((always_inline)) {},
+    auto on_built = [](auto, auto) __attribute__((always_inline)) {};
+    auto on_decision =
         [&](auto, uint32_t info, float g0, float g1, float s0, float s1, float payoff, uint32_t mask) __attribute__((always_inline)) {
             const uint32_t slot = ndec;
             dc.regret[((size_t)slot * 2u + 0u) * D + lane] = g0;
@@ -337,7 +434,10 @@ __global__ __launch_bounds__(256) void k_traverse_static(DevGame g, DevInfoTab i
             dc.payoff[(size_t)slot * D + lane] = payoff;
             if (dc.slotmap) dc.slotmap[(size_t)info * D + lane] = (uint8_t)(slot + 1u);
             ndec += 1u;
-        });
+        };
+    const uint64_t tree_id = p.tree_base + lane;
+    const uint32_t nn = g.rows ? static_traverse<G, W, PRUNED, REF, true>(g, it, p, tree_id, true, on_built, on_decision)
+                               : static_traverse<G, W, PRUNED, REF, false>(g, it, p, tree_id, true, on_built, on_decision);
     dc.ndec[lane] = (uint8_t)ndec;
     count_metrics(p, nn, ndec, 0u);
 }
@@ -379,8 +479,7 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
     const uint32_t lane = chunk * 256u + lt;
     const float tf = (float)p.epoch;
     uint32_t ndec = 0;
-    const uint32_t nn = static_traverse<G, W, PRUNED, REF>(
-        g, it, p, p.tree_base + lane, lane < p.batch,
+    auto on_built =
         [&](auto info_of, auto live_of) __attribute__((always_inline)) {
             sk_for<0, SkelOf<G>::S.n>([&](auto J) __attribute__((always_inline)) {
                 if constexpr (SkelOf<G>::S.kind[decltype(J)::value] == (W == 0 ? SK_P0 : SK_P1)) {
@@ -411,7 +510,8 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
                 const uint32_t run = lcount[info];
                 order[atomicAdd(&cls_at[15u - (run ? 32u - (uint32_t)__builtin_clz(run) : 0u)], 1u)] = (uint16_t)info;
             }
-        },
+        };
+    auto on_decision =
         [&](auto, uint32_t info, float g0, float g1, float s0, float s1, float payoff, uint32_t mask) __attribute__((always_inline)) {
             const uint32_t pos = lbase[info] + pre[info * 8u + (lt >> 5)] + __popc(bits[info * 8u + (lt >> 5)] & ((1u << (lt & 31u)) - 1u));
             if constexpr (PRUNED) lmask[pos] = mask;
@@ -421,7 +521,11 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
             vals[3u * L + pos] = p.W == RP_WEIGHT_LINEAR ? s1 * tf : (p.W == RP_WEIGHT_QUADRATIC ? s1 * tf * tf : s1);
             vals[4u * L + pos] = payoff;
             ndec += 1u;
-        });
+        };
+    const uint64_t tree_id = p.tree_base + lane;
+    const bool present = lane < p.batch;
+    const uint32_t nn = g.rows ? static_traverse<G, W, PRUNED, REF, true>(g, it, p, tree_id, present, on_built, on_decision)
+                               : static_traverse<G, W, PRUNED, REF, false>(g, it, p, tree_id, present, on_built, on_decision);
     __syncthreads();
     // the chains: task = (cell c, infoset); cells 0,1 regret, 2,3 weight, 4 the payoff sum.  The payoff sums are handed out after all
     // the map chains, so that no wavefront mixes the two loops (measured round 4: 0.582 -> 0.562 ms per launch against task % 5)

@@ -198,6 +198,12 @@ class Solver:
         _lib.check(self._lib.rp_mccfr_traversal_variant(self._h, C.byref(v)))
         return ("hbm", "lds", "static")[v.value]
 
+    def traversal_rows_bytes(self) -> int:
+        """size of the packed-row game table of the "static" traversal; 0: it follows the child records (RP_TRAV_NO_FLAT=1)"""
+        n = C.c_size_t()
+        _lib.check(self._lib.rp_mccfr_traversal_rows_bytes(self._h, C.byref(n)))
+        return n.value
+
     def kernel_time(self, name: str):
         ms, n = C.c_double(), C.c_uint64()
         _lib.check(self._lib.rp_mccfr_kernel_time(self._h, name.encode(), C.byref(ms), C.byref(n)))
