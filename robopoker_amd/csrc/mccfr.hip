@@ -1,4 +1,6 @@
-// mccfr.hip — external-sampling MCCFR on MI355X (gfx950): kernels + the rp_mccfr_* C ABI.
+// mccfr.hip — external-sampling MCCFR on MI355X (gfx950): the host side — the solver handle, the launchers, the rp_mccfr_* C ABI,
+// exploitability.  The kernels are in headers, in dependency order: mccfr_kernels.hpp (layouts, the per-cell map algebra and the
+// steps the kernels share), mccfr_traverse.hpp, mccfr_update.hpp, traverse_static.hpp.
 //
 // Reference path (crates/mccfr): Solver::step (solver/solver.rs:96-105) = batch() (:225-250) then the
 // sequential update_{regret,weight,payoff,visits} (:143-192).  MI355X mapping:
@@ -18,1617 +20,23 @@
 //
 // Everything f32 is spelled with the primitives of include/rp_math.h and compiled -ffp-contract=off.
 #include "mccfr_kernels.hpp"
+#include "mccfr_traverse.hpp"
+#include "mccfr_update.hpp"
+#include "traverse_static.hpp"
 
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
 #include <functional>
 #include <string>
+#include <type_traits>
 #include <vector>
-
-namespace rp {
 
 #define HIP_TRY(expr)                                                                                 \
     do {                                                                                              \
         hipError_t _e = (expr);                                                                       \
         if (_e != hipSuccess) return rp::fail(RP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
-
-// ------------------------------------------------------------------------------------------------
-// device: profile reads (RefProf::{regret,weight} profile.rs:31-37; CfrFlow flow.rs:20-59)
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float d_regret(const DevTables& t, uint32_t A, uint32_t info, uint32_t a) {
-    return rp_maxf(t.regret[info * A + a], RP_EPSILON);
-}
-__device__ __forceinline__ float d_weight(const DevTables& t, uint32_t A, uint32_t info, uint32_t a) {
-    return rp_maxf(t.weight[info * A + a], RP_EPSILON);
-}
-__device__ __forceinline__ float d_regret_denom(const DevTables& t, uint32_t A, uint32_t info, uint32_t n) {
-    float s = 0.0f;
-    for (uint32_t a = 0; a < n; ++a) s += d_regret(t, A, info, a);
-    return s;
-}
-__device__ __forceinline__ float d_weight_denom(const DevTables& t, uint32_t A, uint32_t info, uint32_t n,
-                                                float smoothing) {
-    float s = 0.0f;
-    for (uint32_t a = 0; a < n; ++a) s += d_weight(t, A, info, a);
-    return s + smoothing;
-}
-__device__ __forceinline__ float d_sampling_weight(const DevTables& t, uint32_t A, uint32_t info, uint32_t a,
-                                                   float denom, const StepParams& p) {
-    return rp_maxf((d_weight(t, A, info, a) / p.temperature + p.smoothing) / denom, p.curiosity);
-}
-__device__ __forceinline__ float d_sampling_z(const DevTables& t, uint32_t A, uint32_t info, uint32_t n,
-                                              float denom, const StepParams& p) {
-    float z = 0.0f;
-    for (uint32_t a = 0; a < n; ++a) z += d_sampling_weight(t, A, info, a, denom, p);
-    return z;
-}
-
-// SamplingScheme::sample as a bitmask over child slots (sample/{mod,external,pruning,pluribus}.rs)
-__device__ uint32_t d_sample_mask(const DevGame& g, const DevTables& t, const StepParams& p, uint64_t tree_id,
-                                  uint32_t state, uint32_t turn, uint32_t n, uint32_t info, uint32_t off) {
-    const uint32_t all = (1u << n) - 1u;
-    const bool ref = p.ref_info != nullptr;
-    if (n == 0) return 0;
-    if (turn == RP_TURN_CHANCE) return 1u << d_draw_chance(p, ref, tree_id, state, n, info);  // a chance record carries chance_info in y
-    if (turn != p.walker) {
-        // weighted (external.rs:41-64): WeightedIndex over sampling_distribution().max(EPSILON)
-        const float denom = d_weight_denom(t, g.A, info, n, p.smoothing);
-        const float z = d_sampling_z(t, g.A, info, n, denom, p);
-        float total = 0.0f;
-        for (uint32_t a = 0; a < n; ++a)
-            total += rp_maxf(d_sampling_weight(t, g.A, info, a, denom, p) / z, RP_EPSILON);
-        const float x = d_draw_weight(p, ref, tree_id, info, total);
-        float cum = 0.0f;
-        uint32_t idx = 0;
-        bool open = true;
-        for (uint32_t a = 0; a + 1 < n; ++a) {
-            cum += rp_maxf(d_sampling_weight(t, g.A, info, a, denom, p) / z, RP_EPSILON);
-            open = open && (cum <= x);
-            if (open) idx = a + 1;
-        }
-        return 1u << idx;
-    }
-    if (p.S == RP_SAMPLING_EXTERNAL) return all;
-    if (p.S == RP_SAMPLING_PLURIBUS) {
-        if (p.epoch < p.prune_warmup) return all;
-        if (d_draw_coin(p, ref, tree_id, info) < p.prune_explore) return all;
-    }
-    uint32_t mask = 0;
-    for (uint32_t a = 0; a < n; ++a) {
-        bool keep = t.regret[info * g.A + a] > p.prune_threshold;
-        if (p.S == RP_SAMPLING_PLURIBUS) {
-            const uint4 c = g.states[g.children[off + a]];
-            keep = keep || ((c.x & 0xffu) == RP_TURN_TERMINAL);
-        }
-        if (keep) mask |= 1u << a;
-    }
-    return mask ? mask : all;
-}
-
-__device__ __forceinline__ uint32_t lane_of() { return threadIdx.x & 63u; }
-
-// Metrics (metrics/mod.rs:21-80; solver.rs:273): nodes / infos, one atomic per WAVE — a million lanes adding to the
-// same two addresses would serialise in the L2 atomic unit
-// The counters are STRIPED: 16 384 waves adding to ONE address serialise at its L2 channel (~9 ns per atomic: 0.29 ms
-// of a 0.52 ms launch was spent there, found by ablation); stripe s owns its own 128-byte line, the host sums them.
-#define METRIC_STRIPES 256u
-#define METRIC_STRIDE 16u  // u64 per stripe (128 B)
-__device__ __forceinline__ void count_metrics(const StepParams& p, uint32_t nn, uint32_t ndec, uint32_t err) {
-    unsigned long long* c = p.counters + (size_t)(blockIdx.x % METRIC_STRIPES) * METRIC_STRIDE;
-    if (__ballot(1) == ~0ull) {
-        uint32_t a = nn, b = ndec;
-        for (int d = 32; d > 0; d >>= 1) {
-            a += __shfl_xor(a, d, 64);
-            b += __shfl_xor(b, d, 64);
-        }
-        if (lane_of() == 0) {
-            atomicAdd(&c[0], (unsigned long long)a);
-            atomicAdd(&c[1], (unsigned long long)b);
-        }
-    } else {  // the ragged last wave
-        atomicAdd(&c[0], (unsigned long long)nn);
-        atomicAdd(&c[1], (unsigned long long)ndec);
-    }
-    if (err) atomicOr(&c[2], (unsigned long long)err);
-}
-
-#define META_PARENT(m) ((m)&0xffu)
-#define META_EDGE(m) (((m) >> 8) & 0xffu)
-#define META_PTYPE(m) (((m) >> 16) & 3u)
-#define META_LEAF(m) (((m) >> 18) & 1u)
-#define META_WALKER(m) (((m) >> 19) & 1u)
-#define META_NACT(m) (((m) >> 24) & 0xffu)
-#define NO_PARENT 0xffu
-
-// ------------------------------------------------------------------------------------------------
-// k_traverse: Solver::batch for one shard of trees
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_traverse(DevGame g, DevTables t, DevScratch sc, DevDecisions dc,
-                                                  StepParams p) {
-    const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;
-    if (lane >= p.batch) return;
-    const uint64_t tree_id = p.tree_base + lane;
-    const size_t S = sc.stride;
-    uint32_t err = 0;
-
-    // ---- TreeBuilder::build (builder.rs:74-87,141-161): pop-last DFS -----------------------------
-    uint32_t nn = 0, sp = 0;
-    uint32_t cur_state = g.root;
-    uint32_t cur_meta_in = NO_PARENT | (PT_NONE << 16);
-    float cur_frel = 1.0f, cur_fsmp = 1.0f;
-    for (;;) {
-        const uint4 st = g.states[cur_state];
-        const uint32_t turn = st.x & 0xffu, nch = (st.x >> 8) & 0xffu, info = st.y, off = st.z;
-        const uint32_t me = nn;
-        if (nn >= sc.maxn) {
-            err |= ERR_NODE_CAPACITY;
-            break;
-        }
-        const bool is_walker = turn == p.walker;
-        uint32_t meta = cur_meta_in | ((nch == 0 ? 1u : 0u) << 18) | ((is_walker ? 1u : 0u) << 19) | (nch << 24);
-        sc.n_meta[me * S + lane] = meta;
-        sc.n_info[me * S + lane] = info;
-        sc.n_frel[me * S + lane] = cur_frel;
-        sc.n_fsmp[me * S + lane] = cur_fsmp;
-        if (nch == 0) sc.n_pay[me * S + lane] = g.payoffs[off * g.n_players + p.walker];
-        nn += 1;
-        if (nch > 0) {
-            const uint32_t mask = d_sample_mask(g, t, p, tree_id, cur_state, turn, nch, info, off);
-            const bool chance = turn == RP_TURN_CHANCE;
-            const uint32_t ptype = chance ? PT_CHANCE : (is_walker ? PT_WALKER : PT_OPP);
-            float rd = 0.0f, denom = 0.0f, z = 0.0f;
-            if (!chance) rd = d_regret_denom(t, g.A, info, nch);
-            if (ptype == PT_OPP) {
-                denom = d_weight_denom(t, g.A, info, nch, p.smoothing);
-                z = d_sampling_z(t, g.A, info, nch, denom, p);
-            }
-            for (uint32_t k = 0; k < nch; ++k) {
-                if (!((mask >> k) & 1u)) continue;
-                if (sp >= sc.maxs) {
-                    err |= ERR_STACK_CAPACITY;
-                    break;
-                }
-                // reach factors of the edge parent->child (flow.rs:195-212)
-                const float frel = chance ? 1.0f : d_regret(t, g.A, info, k) / rd;
-                const float fsmp = ptype == PT_OPP ? d_sampling_weight(t, g.A, info, k, denom, p) / z : 1.0f;
-                sc.s_state[sp * S + lane] = g.children[off + k];
-                sc.s_meta[sp * S + lane] = me | (k << 8) | (ptype << 16);
-                sc.s_frel[sp * S + lane] = frel;
-                sc.s_fsmp[sp * S + lane] = fsmp;
-                sp += 1;
-            }
-        }
-        if (sp == 0 || err) break;
-        sp -= 1;
-        cur_state = sc.s_state[sp * S + lane];
-        cur_meta_in = sc.s_meta[sp * S + lane];
-        cur_frel = sc.s_frel[sp * S + lane];
-        cur_fsmp = sc.s_fsmp[sp * S + lane];
-    }
-
-    // ---- Tree::partition + CfrFlow::dfs per walker infoset (tree.rs:88-98, flow.rs:64-87) --------
-    uint32_t ndec = 0;
-    if (!err) {
-        for (uint32_t i = 0; i < nn; ++i) {
-            const uint32_t mi = sc.n_meta[i * S + lane];
-            if (!META_WALKER(mi) || META_LEAF(mi)) continue;
-            const uint32_t info = sc.n_info[i * S + lane];
-            bool head = true;
-            for (uint32_t j = 0; j < i; ++j) {
-                const uint32_t mj = sc.n_meta[j * S + lane];
-                if (META_WALKER(mj) && !META_LEAF(mj) && sc.n_info[j * S + lane] == info) head = false;
-            }
-            if (!head) continue;
-            if (ndec >= dc.maxdec) {
-                err |= ERR_DEC_CAPACITY;
-                break;
-            }
-            const uint32_t nact = META_NACT(mi);
-            const uint32_t slot = ndec++;
-            const size_t D = dc.stride;
-            const float rd = d_regret_denom(t, g.A, info, nact);
-            for (uint32_t a = 0; a < nact; ++a) {  // policy_vector = iterated_distribution (profile.rs:47-51)
-                dc.policy[(slot * g.A + a) * D + lane] = d_regret(t, g.A, info, a) / rd;
-                dc.regret[(slot * g.A + a) * D + lane] = 0.0f;
-            }
-            float payoff = 0.0f;
-            uint32_t expanded = 0;
-            for (uint32_t j = i; j < nn; ++j) {  // span in ascending node index
-                const uint32_t mj = sc.n_meta[j * S + lane];
-                if (!META_WALKER(mj) || META_LEAF(mj) || sc.n_info[j * S + lane] != info) continue;
-                // top-down: reach products below root j, starting at 1 on j's children (flow.rs:72)
-                uint32_t end = j;
-                for (uint32_t n = j + 1; n < nn; ++n) {
-                    const uint32_t mn = sc.n_meta[n * S + lane];
-                    const uint32_t par = META_PARENT(mn);
-                    if (par < j) break;
-                    float rel = 1.0f, smp = 1.0f;
-                    if (par != j) {
-                        rel = sc.n_rel[par * S + lane] * sc.n_frel[n * S + lane];
-                        smp = sc.n_smp[par * S + lane] * sc.n_fsmp[n * S + lane];
-                    }
-                    sc.n_rel[n * S + lane] = rel;
-                    sc.n_smp[n * S + lane] = smp;
-                    sc.n_acc[n * S + lane] = 0.0f;
-                    end = n;
-                }
-                // bottom-up: children were created in reverse choices() order, so descending node index
-                // adds them to the parent's sum in choices() order, as node.edges() does (node.rs:103-107)
-                uint32_t kids = 0;
-                for (uint32_t n = end; n > j; --n) {
-                    const uint32_t mn = sc.n_meta[n * S + lane];
-                    const float v = META_LEAF(mn)
-                                        ? sc.n_rel[n * S + lane] / sc.n_smp[n * S + lane] * sc.n_pay[n * S + lane]
-                                        : sc.n_acc[n * S + lane];
-                    const uint32_t par = META_PARENT(mn);
-                    if (par == j) {
-                        sc.t_v[META_EDGE(mn) * S + lane] = v;
-                        kids |= 1u << META_EDGE(mn);
-                    } else {
-                        sc.n_acc[par * S + lane] = sc.n_acc[par * S + lane] + v;
-                    }
-                }
-                // ancestor_reach (flow.rs:166-174): upward over opponent decision ancestors
-                float cf = 1.0f, sm = 1.0f;
-                for (uint32_t n = j;;) {
-                    const uint32_t mn = sc.n_meta[n * S + lane];
-                    const uint32_t par = META_PARENT(mn);
-                    if (par == NO_PARENT) break;
-                    if (META_PTYPE(mn) == PT_OPP) {
-                        cf = cf * sc.n_frel[n * S + lane];
-                        sm = sm * sc.n_fsmp[n * S + lane];
-                    }
-                    n = par;
-                }
-                const float reach = cf / sm;
-                float ev = 0.0f;
-                for (uint32_t a = 0; a < nact; ++a) {
-                    if (!((kids >> a) & 1u)) continue;
-                    const float v = reach * sc.t_v[a * S + lane];
-                    sc.t_v[a * S + lane] = v;
-                }
-                for (uint32_t a = 0; a < nact; ++a) {
-                    if (!((kids >> a) & 1u)) continue;
-                    ev += d_regret(t, g.A, info, a) / rd * sc.t_v[a * S + lane];
-                }
-                payoff += ev;
-                for (uint32_t a = 0; a < nact; ++a) {
-                    if (!((kids >> a) & 1u)) continue;
-                    const size_t k = (slot * g.A + a) * D + lane;
-                    dc.regret[k] = dc.regret[k] + (sc.t_v[a * S + lane] - ev);
-                }
-                expanded |= kids;
-            }
-            dc.info[slot * D + lane] = info;
-            dc.mask[slot * D + lane] = expanded;
-            dc.payoff[slot * D + lane] = payoff;
-            if (dc.slotmap) dc.slotmap[(size_t)info * D + lane] = (uint8_t)(slot + 1);
-        }
-    }
-    dc.ndec[lane] = (uint8_t)ndec;
-    // Metrics: nodes / infos (metrics/mod.rs:21-80; solver.rs:273)
-    count_metrics(p, nn, ndec, err);
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_prepare_infos: everything a node needs from its infoset, computed ONCE per epoch per infoset instead of at
-// every visited node: regret-matching policy sigma(a) = regret(a)/sum (profile.rs:47-51), the normalised sampling
-// distribution q(a) (flow.rs:33-42), the cumulative weights WeightedIndex draws from (external.rs:52-62) and the
-// regret-based pruning mask (pruning.rs:57-63).  Same expressions, same order => same bits as the per-node code.
-// ------------------------------------------------------------------------------------------------
-struct DevInfoTab {
-    float* sigma;    // [n_infos][A]
-    float* q;        // [n_infos][A]
-    float* cum;      // [n_infos][A] inclusive cumulative of max(q, EPSILON)
-    float* total;    // [n_infos]
-    uint32_t* keep;  // [n_infos] edges with cum_regret > prune_threshold
-    float2* sq;      // [n_infos][A] (sigma, q) side by side: one load per edge in the traversal's sweeps
-    float* row2;     // [n_infos][8] two-action games (NULL otherwise): {sigma0, sigma1, q0, q1, total, cum0, keep, 0} — all a node of
-                     // the skeleton traversal needs of its infoset, in one 32-byte row (traverse_static.hpp)
-};
-
-__device__ __forceinline__ void prepare_one(const DevGame& g, const DevTables& t, const StepParams& p, const DevInfoTab& it,
-                                            uint32_t info) {
-    const uint32_t A = g.A, n = g.info_actions[info];
-    const float rd = d_regret_denom(t, A, info, n);
-    const float denom = d_weight_denom(t, A, info, n, p.smoothing);
-    const float z = d_sampling_z(t, A, info, n, denom, p);
-    float total = 0.0f;
-    uint32_t keep = 0;
-    for (uint32_t a = 0; a < n; ++a) {
-        it.sigma[info * A + a] = d_regret(t, A, info, a) / rd;
-        const float qa = d_sampling_weight(t, A, info, a, denom, p) / z;
-        it.q[info * A + a] = qa;
-        it.sq[info * A + a] = make_float2(it.sigma[info * A + a], qa);
-        if (it.row2) {
-            it.row2[info * 8u + a] = it.sigma[info * A + a];
-            it.row2[info * 8u + 2u + a] = qa;
-        }
-        total += rp_maxf(qa, RP_EPSILON);
-        it.cum[info * A + a] = total;
-        if (t.regret[info * A + a] > p.prune_threshold) keep |= 1u << a;
-    }
-    it.total[info] = total;
-    it.keep[info] = keep;
-    if (it.row2) {
-        it.row2[info * 8u + 4u] = total;
-        it.row2[info * 8u + 5u] = it.cum[info * A];
-        it.row2[info * 8u + 6u] = rp_u2f(keep);
-        it.row2[info * 8u + 7u] = 0.0f;
-    }
-}
-__global__ void k_prepare_infos(DevGame g, DevTables t, StepParams p, DevInfoTab it) {
-    const uint32_t info = blockIdx.x * blockDim.x + threadIdx.x;
-    if (info >= g.n_infos) return;
-    prepare_one(g, t, p, it, info);
-}
-
-// reference-seed mode: DefaultHasher after t.hash() and info.hash() for every infoset and every in-tree chance info
-// (flow.rs:290-293); a node continues with node.seed().hash() and finish() (rp_ref_seed_finish).  Depends on the epoch: every step.
-__global__ void k_prepare_ref(const rp_hash_stream* infos, uint32_t n_infos, const rp_hash_stream* chance, uint32_t n_chance,
-                              uint64_t epoch, rp_sip_mid* info_mid, rp_sip_mid* chance_mid) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_infos) rp_ref_seed_prefix(&info_mid[i], epoch, infos[i].bytes, infos[i].len);
-    else if (i < n_infos + n_chance) rp_ref_seed_prefix(&chance_mid[i - n_infos], epoch, chance[i - n_infos].bytes, chance[i - n_infos].len);
-}
-
-// SamplingScheme::sample with the per-infoset tables
-__device__ __forceinline__ uint32_t d_sample_mask_tab(const DevGame& g, const DevInfoTab& it, const StepParams& p,
-                                                      uint64_t tree_id, uint32_t state, uint32_t turn, uint32_t n,
-                                                      uint32_t info, uint32_t off) {
-    const uint32_t all = (1u << n) - 1u;
-    const bool ref = p.ref_info != nullptr;
-    if (turn == RP_TURN_CHANCE) return 1u << d_draw_chance(p, ref, tree_id, state, n, info);  // a chance record carries chance_info in y
-    if (turn != p.walker) {
-        const float x = d_draw_weight(p, ref, tree_id, info, it.total[info]);
-        uint32_t idx = 0;
-        bool open = true;
-        for (uint32_t a = 0; a + 1 < n; ++a) {
-            open = open && (it.cum[info * g.A + a] <= x);
-            if (open) idx = a + 1;
-        }
-        return 1u << idx;
-    }
-    if (p.S == RP_SAMPLING_EXTERNAL) return all;
-    if (p.S == RP_SAMPLING_PLURIBUS) {
-        if (p.epoch < p.prune_warmup) return all;
-        if (d_draw_coin(p, ref, tree_id, info) < p.prune_explore) return all;
-    }
-    uint32_t mask = it.keep[info] & all;
-    if (p.S == RP_SAMPLING_PLURIBUS) {
-        for (uint32_t a = 0; a < n; ++a) {
-            if ((g.kids[off + a].x & 0xffu) == RP_TURN_TERMINAL) mask |= 1u << a;
-        }
-    }
-    return mask ? mask : all;
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_traverse_lds: the same traversal with the per-tree scratch in LDS instead of HBM.
-//
-// The HBM variant moves ~1.1 GB per 262 144-tree launch (profiles/r01_mccfr_hbm_traffic.json) against ~72 MB of
-// algorithmic bytes: the multi-pass evaluation re-reads the node list.  Here a node is 4 dwords
-// (meta | frel | fsmp | value) in a lane-interleaved LDS array (bank = lane: conflict free), the leaf stack 4
-// dwords per entry; reach products of a leaf are rebuilt by walking its (<= 10 node) path instead of being stored.
-// One wave per workgroup; 4*maxn + 4*maxs + A dwords per lane (Leduc: 472 B/lane, 30 KB/wave, 5 waves/CU).
-// Used when the game fits: <= 62 nodes per sampled tree, depth <= 10, <= 8191 infosets, <= 16 actions.
-// ------------------------------------------------------------------------------------------------
-#define LM_PARENT(m) ((m)&63u)
-#define LM_EDGE(m) (((m) >> 6) & 15u)
-#define LM_PTYPE(m) (((m) >> 10) & 3u)
-#define LM_LEAF(m) (((m) >> 12) & 1u)
-#define LM_WALKER(m) (((m) >> 13) & 1u)
-#define LM_ISLOT(m) (((m) >> 14) & 31u)  // internal nodes: rank among the internal nodes (their reach-prefix slot)
-#define LM_INFO(m) ((m) >> 19)
-#define LM_NO_PARENT 63u
-
-// TVREG:  at most 4 actions, the per-action values of a root live in registers, not LDS.
-// The per-infoset sigma / q tables are read through L1 (a per-wave LDS copy measured slower on Leduc: 0.57 vs 0.54 ms per 2^20 trees).
-// A node is TWO dwords (meta, value): the reach factor of its incoming edge is not stored but looked up as
-// table[infoset(parent)][edge] whenever a sweep needs it.  Leduc: 78 dwords per lane = 8 waves/CU.
-template <bool TVREG>
-__global__ __launch_bounds__(64) void k_traverse_lds(DevGame g, DevInfoTab it, DevDecisions dc, StepParams p, uint32_t maxn,
-                                                     uint32_t maxs, uint32_t maxi) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    const uint32_t ln = threadIdx.x;
-    const uint32_t lane = blockIdx.x * 64 + ln;
-    uint32_t* nm = lds;                                              // [maxn][64] meta
-    float* nv = reinterpret_cast<float*>(nm + (size_t)maxn * 64);    // [maxn][64] leaf: payoff; internal: child-value sum
-    float* tv = nv + (size_t)maxn * 64;                              // [A][64] (absent when TVREG)
-    float tvr[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    auto tv_set = [&](uint32_t e, float v) {
-        if (TVREG) {
-#pragma unroll
-            for (uint32_t q = 0; q < 4; ++q) tvr[q] = e == q ? v : tvr[q];
-        } else {
-            tv[e * 64 + ln] = v;
-        }
-    };
-    auto tv_get = [&](uint32_t e) -> float {
-        if (TVREG) {
-            float r = tvr[0];
-#pragma unroll
-            for (uint32_t q = 1; q < 4; ++q) r = e == q ? tvr[q] : r;
-            return r;
-        }
-        return tv[e * 64 + ln];
-    };
-    // build phase: the DFS stack; evaluation phase: per-root reach prefixes of internal nodes (same storage)
-    uint32_t* ss = reinterpret_cast<uint32_t*>(tv + (TVREG ? 0 : (size_t)g.A * 64));  // [maxs][4][64] stack: record x | meta << 16, y, z, w
-    // reach prefixes exist for INTERNAL nodes only: slot = rank of the node among the internal nodes (popcount of a
-    // register mask)
-    float* xr = reinterpret_cast<float*>(ss);                        // [maxi][64] relative reach root's child -> node
-    float* xs = xr + (size_t)maxi * 64;                              // [maxi][64] sampling reach root's child -> node
-    const uint32_t cells = g.n_infos * g.A;
-    auto SIG = [&](uint32_t e) -> float { return it.sigma[e]; };
-    if (lane >= p.batch) return;
-    const uint64_t tree_id = p.tree_base + lane;
-    uint32_t err = 0;
-#define L(arr, slot) arr[(slot)*64 + ln]
-#define STK(e, f) ss[((e)*4u + (f)) * 64u + ln]
-    // reach factors of the edge into a node (meta mn): sigma / q of the parent's infoset at the node's edge
-    // (sigma, q) of the edge into a node: (1, 1) below chance, (sigma, 1) below the walker, (sigma, q) below an opponent
-    // mp: the meta of mn's parent
-    auto f_of = [&](uint32_t mn, uint32_t mp) -> float2 {
-        const uint32_t pt = LM_PTYPE(mn);
-        if (pt != PT_WALKER && pt != PT_OPP) return make_float2(1.0f, 1.0f);
-        const uint32_t e = LM_INFO(mp) * g.A + LM_EDGE(mn);
-        float2 f = it.sq[e];
-        if (pt != PT_OPP) f.y = 1.0f;
-        return f;
-    };
-    // the same lookup issued AHEAD of its use, for metas that may lie past the subtree (stale LDS): a bounds-checked
-    // buffer load (out of range -> 0) of the raw (sigma, q) pair; f_fix applies the parent-type rule once it is used
-    const __amdgpu_buffer_rsrc_t sq_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float2*>(it.sq), 0, (int)(cells * 8u), 0x00020000);
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-    auto f_issue = [&](uint32_t mn, uint32_t mp) -> float2 {
-        const uint32_t e = LM_INFO(mp) * g.A + LM_EDGE(mn);
-        const u32x2 raw = __builtin_amdgcn_raw_buffer_load_b64(sq_rsrc, (int)(e * 8u), 0, 0);
-        return make_float2(rp_u2f(raw.x), rp_u2f(raw.y));
-    };
-    auto f_fix = [&](uint32_t mn, float2 f) -> float2 {
-        const uint32_t pt = LM_PTYPE(mn);
-        if (pt != PT_WALKER && pt != PT_OPP) return make_float2(1.0f, 1.0f);
-        if (pt != PT_OPP) f.y = 1.0f;
-        return f;
-    };
-
-    // ---- TreeBuilder::build (builder.rs:74-87,141-161): pop-last DFS -----------------------------
-    // A node arrives as its RECORD (DevGame::kids): the records of all sampled children are requested together
-    // when their parent is expanded, so a tree pays one L2 round trip per internal node, not two or three per node.
-    // The last child pushed is the next node popped: it is carried in registers instead of through the stack.
-    uint32_t nn = 0, sp = 0;
-    uint4 rec = g.root_rec;
-    uint32_t cur_in = LM_NO_PARENT | (PT_NONE << 10);
-    unsigned long long wmask = 0;  // walker decision nodes
-    uint32_t n_int = 0;            // internal nodes so far
-    for (;;) {
-        const uint32_t turn = rec.x & 0xffu, nch = (rec.x >> 8) & 0xffu, info = rec.y, off = rec.z;
-        const uint32_t me = nn;
-        if (nn >= maxn) {
-            err |= ERR_NODE_CAPACITY;
-            break;
-        }
-        const bool is_walker = turn == p.walker;
-        L(nm, me) = cur_in | ((nch == 0 ? 1u : 0u) << 12) | ((is_walker ? 1u : 0u) << 13) | ((n_int & 31u) << 14) |
-                    ((turn < RP_TURN_CHANCE ? info : 0u) << 19);
-        nn += 1;
-        if (nch > 0) {
-            n_int += 1;
-            if (is_walker) wmask |= 1ull << me;
-            uint32_t mask = d_sample_mask_tab(g, it, p, tree_id, rec.w, turn, nch, info, off);
-            const bool chance = turn == RP_TURN_CHANCE;
-            const uint32_t ptype = chance ? PT_CHANCE : (is_walker ? PT_WALKER : PT_OPP);
-            const uint32_t last = 31u - (uint32_t)__builtin_clz(mask);
-            mask &= ~(1u << last);
-            rec = g.kids[off + last];
-            while (mask) {
-                const uint32_t k = (uint32_t)__builtin_ctz(mask);
-                mask &= mask - 1u;
-                if (sp >= maxs) {
-                    err |= ERR_STACK_CAPACITY;
-                    break;
-                }
-                const uint4 kr = g.kids[off + k];
-                STK(sp, 0) = kr.x | ((me | (k << 6) | (ptype << 10)) << 16);
-                STK(sp, 1) = kr.y;
-                STK(sp, 2) = kr.z;
-                STK(sp, 3) = kr.w;
-                sp += 1;
-            }
-            if (err) break;
-            cur_in = me | (last << 6) | (ptype << 10);
-            continue;
-        }
-        L(nv, me) = g.n_players == 2 ? rp_u2f(p.walker == 0 ? rec.y : rec.z) : g.payoffs[off * g.n_players + p.walker];
-        if (sp == 0) break;
-        sp -= 1;
-        const uint32_t xm = STK(sp, 0);
-        rec = make_uint4(xm & 0xffffu, STK(sp, 1), STK(sp, 2), STK(sp, 3));
-        cur_in = xm >> 16;
-    }
-#undef STK
-
-    // ---- Tree::partition + CfrFlow::dfs per walker infoset (tree.rs:88-98, flow.rs:64-87) --------
-    const bool fuse = g.A <= 2;  // every node has at most two children
-    uint32_t ndec = 0;
-    if (n_int > maxi || n_int > 32u) err |= ERR_NODE_CAPACITY;
-    if (!err) {
-        unsigned long long todo = wmask;
-        while (todo) {
-            const uint32_t i = (uint32_t)__builtin_ctzll(todo);  // head of the next infoset span
-            const uint32_t mi = L(nm, i);
-            const uint32_t info = LM_INFO(mi);
-            if (ndec >= dc.maxdec) {
-                err |= ERR_DEC_CAPACITY;
-                break;
-            }
-            const uint32_t nact = g.info_actions[info];
-            const uint32_t slot = ndec++;
-            const size_t D = dc.stride;
-            float payoff = 0.0f;
-            uint32_t expanded = 0;
-            unsigned long long span = todo;
-            while (span) {  // roots of the span in ascending node index
-                const uint32_t j = (uint32_t)__builtin_ctzll(span);
-                span &= span - 1ull;
-                if (j != i && LM_INFO(L(nm, j)) != info) continue;
-                todo &= ~(1ull << j);
-                // top-down over the (contiguous) subtree of j: reach products from j's child (flow.rs:195-212),
-                // which start at 1 there; internal nodes also start their child-value sum at 0
-                // With at most two children per node (fuse) a sum of child values does not depend on the order of its
-                // additions (0 + x = x, x + y = y + x exactly), so a leaf hands its value to its parent right here and
-                // the bottom-up sweep only moves the internal nodes' sums: one factor lookup per node instead of two.
-                // The sweep is a three-stage software pipeline: while node n is processed, the factor pair of node n + 1,
-                // the parent meta of node n + 2 and the meta of node n + 3 are in flight (a lone wave per SIMD pays every
-                // LDS / L1 round trip in full otherwise).  Stages may run past the subtree: they only read.
-                uint32_t end = j;
-                uint32_t kids = 0;
-                uint32_t mnA = L(nm, j + 1), mnB = L(nm, j + 2), mnC = L(nm, j + 3);
-                uint32_t mpA = L(nm, LM_PARENT(mnA)), mpB = L(nm, LM_PARENT(mnB));
-                float2 fA = f_issue(mnA, mpA);
-                for (uint32_t n = j + 1; n < nn; ++n) {
-                    const uint32_t mn = mnA, mp = mpA;
-                    const float2 fraw = fA;
-                    fA = f_issue(mnB, mpB);
-                    mpA = mpB;
-                    mpB = L(nm, LM_PARENT(mnC));
-                    mnA = mnB;
-                    mnB = mnC;
-                    mnC = L(nm, n + 3);
-                    const uint32_t par = LM_PARENT(mn);
-                    if (par < j) break;
-                    end = n;
-                    const bool leaf = LM_LEAF(mn);
-                    if (leaf && !fuse) continue;
-                    float rel = 1.0f, smp = 1.0f;
-                    if (par != j) {
-                        const uint32_t ps = LM_ISLOT(mp);
-                        const float2 f = f_fix(mn, fraw);
-                        rel = L(xr, ps) * f.x;
-                        smp = L(xs, ps) * f.y;
-                    }
-                    if (leaf) {
-                        const float v = rel / smp * L(nv, n);
-                        if (par == j) {
-                            tv_set(LM_EDGE(mn), v);
-                            kids |= 1u << LM_EDGE(mn);
-                        } else {
-                            L(nv, par) = L(nv, par) + v;
-                        }
-                        continue;
-                    }
-                    const uint32_t ns = LM_ISLOT(mn);
-                    L(xr, ns) = rel;
-                    L(xs, ns) = smp;
-                    L(nv, n) = 0.0f;
-                }
-                // bottom-up: descending node index adds children in choices() order (node.rs:103-107)
-                uint32_t mn_prev = L(nm, end);
-                float v_prev = L(nv, end);
-                for (uint32_t n = end; n > j; --n) {
-                    const uint32_t mn = mn_prev;
-                    const uint32_t par = LM_PARENT(mn);
-                    float v = v_prev;
-                    mn_prev = L(nm, n - 1);  // one node ahead; its value is patched below if this node is its child
-                    v_prev = L(nv, n - 1);
-                    if (fuse && LM_LEAF(mn)) continue;  // already with its parent
-                    if (LM_LEAF(mn)) {
-                        float rel = 1.0f, smp = 1.0f;
-                        if (par != j) {
-                            const uint32_t mp = L(nm, par), ps = LM_ISLOT(mp);
-                            const float2 f = f_of(mn, mp);
-                            rel = L(xr, ps) * f.x;
-                            smp = L(xs, ps) * f.y;
-                        }
-                        v = rel / smp * v;
-                    }
-                    if (par == j) {
-                        tv_set(LM_EDGE(mn), v);
-                        kids |= 1u << LM_EDGE(mn);
-                    } else {
-                        const float sum = (par == n - 1 ? v_prev : L(nv, par)) + v;
-                        L(nv, par) = sum;
-                        if (par == n - 1) v_prev = sum;
-                    }
-                }
-                // ancestor_reach (flow.rs:166-174)
-                float cf = 1.0f, sm_ = 1.0f;
-                for (uint32_t mn = L(nm, j);;) {
-                    const uint32_t par = LM_PARENT(mn);
-                    if (par == LM_NO_PARENT) break;
-                    const uint32_t mp = L(nm, par);
-                    if (LM_PTYPE(mn) == PT_OPP) {
-                        const float2 f = f_of(mn, mp);
-                        cf = cf * f.x;
-                        sm_ = sm_ * f.y;
-                    }
-                    mn = mp;
-                }
-                const float reach = cf / sm_;
-                float ev = 0.0f;
-                for (uint32_t a = 0; a < nact; ++a) {
-                    if (!((kids >> a) & 1u)) continue;
-                    const float u = reach * tv_get(a);
-                    tv_set(a, u);
-                    ev += SIG(info * g.A + a) * u;
-                }
-                payoff += ev;
-                for (uint32_t a = 0; a < nact; ++a) {
-                    if (!((kids >> a) & 1u)) continue;
-                    const size_t k = (slot * g.A + a) * D + lane;
-                    // first root of the span writes, later roots accumulate (0 + x = x exactly)
-                    const float prev = (expanded >> a) & 1u ? dc.regret[k] : 0.0f;
-                    dc.regret[k] = prev + (tv_get(a) - ev);
-                }
-                expanded |= kids;
-            }
-            for (uint32_t a = 0; a < nact; ++a) {  // policy_vector = iterated_distribution (profile.rs:47-51)
-                dc.policy[(slot * g.A + a) * D + lane] = SIG(info * g.A + a);
-                if (!((expanded >> a) & 1u)) dc.regret[(slot * g.A + a) * D + lane] = 0.0f;
-            }
-            dc.info[slot * D + lane] = info;
-            dc.mask[slot * D + lane] = expanded;
-            dc.payoff[slot * D + lane] = payoff;
-            if (dc.slotmap) dc.slotmap[(size_t)info * D + lane] = (uint8_t)(slot + 1);
-        }
-    }
-#undef L
-    dc.ndec[lane] = (uint8_t)ndec;
-    count_metrics(p, nn, ndec, err);
-}
-
-// ------------------------------------------------------------------------------------------------
-// schedules (regret/*.rs, policy/*.rs)
-// ------------------------------------------------------------------------------------------------
-// d_regret_gain / d_weight_learn / regret_floor_of live in mccfr_kernels.hpp (shared with sparse.hip)
-
-// ------------------------------------------------------------------------------------------------
-// Update pipeline (Solver::update_{regret,weight,payoff,visits}, solver.rs:96-105,143-192):
-//   k_count    per (infoset, 1024-tree chunk): how many trees of the chunk produced Decisions for it
-//   k_scan     per infoset: exclusive scan of the chunk counts -> offsets, segment length
-//   k_compact  scatter the Decisions into ONE tree-id-ordered segment per infoset (stable counting sort)
-//   k_chain    per infoset: stream the segment through LDS tiles and apply the touches sequentially,
-//              one lane per table cell (the reference's order-dependent semantics, bit for bit)
-// ------------------------------------------------------------------------------------------------
-#define CH_TREES 256u     // trees per compaction chunk == RP_COMPOSE_CHUNK (a block of the composed update)
-#define CH_THREADS 256u   // small-game kernels: one tree per thread
-#define SLOT_THREADS (CH_TREES / 4u)  // slot-map kernels: four slot-map bytes per thread
-
-struct DevSorted {
-    float* rw;         // [cap][2A]  per Decisions: regret delta a=0..A-1, then weight delta a=0..A-1
-    uint32_t* mask;    // [cap]      edges present in the regret vector
-    float* payoff;     // [cap]
-    uint32_t* counts;  // [n_infos][n_chunks]
-    uint32_t* offs;    // [n_infos][n_chunks]
-    uint32_t* total;   // [n_infos]  segment length
-    uint32_t n_chunks;
-};
-
-__device__ __forceinline__ uint32_t chunk_slots(const DevDecisions& dc, uint32_t info, uint32_t t0, uint32_t batch) {
-    uint32_t slots = 0;
-    if (t0 + 4 <= batch) {
-        slots = *reinterpret_cast<const uint32_t*>(&dc.slotmap[(size_t)info * dc.stride + t0]);
-    } else {
-        for (uint32_t k = 0; k < 4; ++k)
-            if (t0 + k < batch) slots |= (uint32_t)dc.slotmap[(size_t)info * dc.stride + t0 + k] << (8 * k);
-    }
-    return slots;
-}
-__device__ __forceinline__ uint32_t nonzero_bytes(uint32_t v) {
-    return ((v & 0xffu) != 0) + ((v & 0xff00u) != 0) + ((v & 0xff0000u) != 0) + ((v & 0xff000000u) != 0);
-}
-// block-wide exclusive scan over the blockDim.x threads in thread order; returns (exclusive prefix, total)
-__device__ __forceinline__ uint32_t block_exscan(uint32_t v, uint32_t* wave_tot, uint32_t* total) {
-    const uint32_t tid = threadIdx.x;
-    uint32_t incl = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d, 64);
-        if ((int)(tid & 63) >= d) incl += o;
-    }
-    if ((tid & 63) == 63) wave_tot[tid >> 6] = incl;
-    __syncthreads();
-    uint32_t wbase = 0, tot = 0;
-    for (uint32_t w = 0; w < blockDim.x / 64; ++w) {
-        const uint32_t c = wave_tot[w];
-        if (w < (tid >> 6)) wbase += c;
-        tot += c;
-    }
-    __syncthreads();
-    *total = tot;
-    return wbase + incl - v;
-}
-
-__global__ __launch_bounds__(SLOT_THREADS) void k_count(DevGame g, DevDecisions dc, DevSorted so, StepParams p) {
-    __shared__ uint32_t wave_tot[CH_THREADS / 64];
-    const uint32_t info = blockIdx.y, chunk = blockIdx.x;
-    if (g.info_player[info] != p.walker) return;
-    const uint32_t t0 = chunk * CH_TREES + threadIdx.x * 4;
-    uint32_t cnt = nonzero_bytes(chunk_slots(dc, info, t0, p.batch));
-    for (int d = 32; d > 0; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
-    if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t c = 0;
-        for (uint32_t w = 0; w < blockDim.x / 64; ++w) c += wave_tot[w];
-        so.counts[(size_t)info * so.n_chunks + chunk] = c;
-    }
-}
-
-__global__ __launch_bounds__(CH_THREADS) void k_scan(DevGame g, DevSorted so, StepParams p) {
-    __shared__ uint32_t wave_tot[CH_THREADS / 64];
-    const uint32_t info = blockIdx.x;
-    if (g.info_player[info] != p.walker) {
-        if (threadIdx.x == 0) so.total[info] = 0;
-        return;
-    }
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < so.n_chunks; base += CH_THREADS) {
-        const uint32_t c = base + threadIdx.x;
-        const uint32_t v = c < so.n_chunks ? so.counts[(size_t)info * so.n_chunks + c] : 0u;
-        uint32_t tot;
-        const uint32_t ex = block_exscan(v, wave_tot, &tot);
-        if (c < so.n_chunks) so.offs[(size_t)info * so.n_chunks + c] = carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) so.total[info] = carry;
-}
-
-__global__ __launch_bounds__(SLOT_THREADS) void k_compact(DevGame g, DevDecisions dc, DevSorted so, StepParams p) {
-    __shared__ uint32_t wave_tot[CH_THREADS / 64];
-    __shared__ uint32_t sh_base;
-    const uint32_t info = blockIdx.y, chunk = blockIdx.x;
-    if (g.info_player[info] != p.walker) return;
-    // segment base = sum of the lengths of all lower infosets
-    uint32_t part = 0;
-    for (uint32_t i = threadIdx.x; i < info; i += blockDim.x) part += so.total[i];
-    for (int d = 32; d > 0; d >>= 1) part += __shfl_xor(part, d, 64);
-    if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = part;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t b0 = so.offs[(size_t)info * so.n_chunks + chunk];
-        for (uint32_t w = 0; w < blockDim.x / 64; ++w) b0 += wave_tot[w];
-        sh_base = b0;
-    }
-    __syncthreads();
-    const uint32_t A = g.A, nact = g.info_actions[info];
-    const uint32_t t0 = chunk * CH_TREES + threadIdx.x * 4;
-    const uint32_t slots = chunk_slots(dc, info, t0, p.batch);
-    uint32_t tot;
-    uint32_t rank = block_exscan(nonzero_bytes(slots), wave_tot, &tot);
-    const float tf = (float)p.epoch;
-    for (uint32_t k = 0; k < 4; ++k) {
-        const uint32_t sl = (slots >> (8 * k)) & 0xffu;
-        if (!sl) continue;
-        const uint32_t tree = t0 + k, slot = sl - 1;
-        const size_t pos = (size_t)sh_base + rank;
-        for (uint32_t a = 0; a < A; ++a) {
-            float rd = 0.0f, wd = 0.0f;
-            if (a < nact) {
-                rd = dc.regret[(slot * A + a) * dc.stride + tree];
-                const float sg = dc.policy[(slot * A + a) * dc.stride + tree];
-                // WeightSchedule::accumulate's immediate term (policy/{linear,quadratic}.rs): sigma * t, sigma * t * t
-                wd = p.W == RP_WEIGHT_LINEAR ? sg * tf : (p.W == RP_WEIGHT_QUADRATIC ? sg * tf * tf : sg);
-            }
-            so.rw[pos * 2 * A + a] = rd;
-            so.rw[pos * 2 * A + A + a] = wd;
-        }
-        so.mask[pos] = dc.mask[slot * dc.stride + tree];
-        so.payoff[pos] = dc.payoff[slot * dc.stride + tree];
-        rank += 1;
-    }
-}
-
-// ---- games whose per-chunk bitmap fits in LDS (56 B per infoset): the same stable counting sort without the
-// per-infoset slot map in HBM --------
-// One workgroup per chunk of CH_TREES trees.  A tree's Decisions are marked in an LDS bitmap [infoset][tree]; the
-// rank of a Decisions inside its (chunk, infoset) bucket — its place in tree-id order — is a prefix popcount of that
-// bitmap row.  Every Decisions is read once; nothing is scanned per infoset.
-static_assert(CH_TREES == RP_COMPOSE_CHUNK, "a block of the composed update is one compaction chunk of trees");
-#define SM_WORDS (CH_TREES / 32u)
-#define CM_PASSES 4u  // k_chunk_maps: infosets per thread; 4 * 256 infosets * 56 B is past its 64 KB LDS budget
-__device__ __forceinline__ void chunk_bitmap(const DevDecisions& dc, uint32_t n_infos, uint32_t chunk, uint32_t batch,
-                                             uint32_t* bits) {
-    for (uint32_t e = threadIdx.x; e < n_infos * SM_WORDS; e += CH_THREADS) bits[e] = 0;
-    __syncthreads();
-    for (uint32_t lt = threadIdx.x; lt < CH_TREES; lt += CH_THREADS) {
-        const uint32_t tree = chunk * CH_TREES + lt;  // coalesced over threads
-        if (tree >= batch) continue;
-        const uint32_t nd = dc.ndec[tree];
-        for (uint32_t slot = 0; slot < nd; ++slot)
-            atomicOr(&bits[dc.info[slot * dc.stride + tree] * SM_WORDS + (lt >> 5)], 1u << (lt & 31u));
-    }
-    __syncthreads();
-}
-// exclusive scan of in[0..n) into out[0..n) (both LDS), any n, by the whole workgroup
-__device__ __forceinline__ void lds_exscan(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* wave_tot) {
-    uint32_t carry = 0;
-    for (uint32_t b0 = 0; b0 < n; b0 += blockDim.x) {
-        const uint32_t i = b0 + threadIdx.x;
-        uint32_t tot;
-        const uint32_t ex = block_exscan(i < n ? in[i] : 0u, wave_tot, &tot);
-        if (i < n) out[i] = carry + ex;
-        carry += tot;
-    }
-    __syncthreads();
-}
-__global__ __launch_bounds__(CH_THREADS) void k_count_small(DevGame g, DevDecisions dc, DevSorted so, StepParams p) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t sm_lds[];
-    uint32_t* bits = sm_lds;  // [n_infos][SM_WORDS]
-    const uint32_t chunk = blockIdx.x;
-    chunk_bitmap(dc, g.n_infos, chunk, p.batch, bits);
-    for (uint32_t info = threadIdx.x; info < g.n_infos; info += CH_THREADS) {
-        uint32_t c = 0;
-        for (uint32_t w = 0; w < SM_WORDS; ++w) c += __popc(bits[info * SM_WORDS + w]);
-        so.counts[(size_t)info * so.n_chunks + chunk] = c;
-    }
-}
-__global__ __launch_bounds__(CH_THREADS) void k_compact_small(DevGame g, DevDecisions dc, DevSorted so, StepParams p) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t sm_lds[];
-    __shared__ uint32_t wave_tot[CH_THREADS / 64];
-    const uint32_t NI = g.n_infos;
-    uint32_t* bits = sm_lds;                                        // [NI][SM_WORDS]
-    uint32_t* base = bits + NI * SM_WORDS;                          // [NI] first position of the (chunk, infoset) bucket
-    uint32_t* tots = base + NI;                                     // [NI] segment lengths
-    uint16_t* pre = reinterpret_cast<uint16_t*>(tots + NI);         // [NI][SM_WORDS] trees before word w that visited the infoset
-    const uint32_t chunk = blockIdx.x;
-    chunk_bitmap(dc, g.n_infos, chunk, p.batch, bits);
-    for (uint32_t info = threadIdx.x; info < g.n_infos; info += CH_THREADS) {
-        uint32_t run = 0;
-        for (uint32_t w = 0; w < SM_WORDS; ++w) {
-            pre[info * SM_WORDS + w] = (uint16_t)run;
-            run += __popc(bits[info * SM_WORDS + w]);
-        }
-    }
-    // bucket base = sum of the lengths of all lower infosets + this chunk's offset inside the infoset's segment
-    for (uint32_t info = threadIdx.x; info < NI; info += CH_THREADS) tots[info] = so.total[info];
-    __syncthreads();
-    lds_exscan(tots, base, NI, wave_tot);
-    for (uint32_t info = threadIdx.x; info < NI; info += CH_THREADS) base[info] += so.offs[(size_t)info * so.n_chunks + chunk];
-    __syncthreads();
-    const uint32_t A = g.A;
-    const float tf = (float)p.epoch;
-    for (uint32_t lt = threadIdx.x; lt < CH_TREES; lt += CH_THREADS) {
-        const uint32_t tree = chunk * CH_TREES + lt;
-        if (tree >= p.batch) continue;
-        const uint32_t nd = dc.ndec[tree];
-        for (uint32_t slot = 0; slot < nd; ++slot) {
-            const uint32_t info = dc.info[slot * dc.stride + tree];
-            const uint32_t nact = g.info_actions[info];
-            const uint32_t rank = pre[info * SM_WORDS + (lt >> 5)] + __popc(bits[info * SM_WORDS + (lt >> 5)] & ((1u << (lt & 31u)) - 1u));
-            const size_t pos = (size_t)base[info] + rank;
-            for (uint32_t a = 0; a < A; ++a) {
-                float rd = 0.0f, wd = 0.0f;
-                if (a < nact) {
-                    rd = dc.regret[(slot * A + a) * dc.stride + tree];
-                    const float sg = dc.policy[(slot * A + a) * dc.stride + tree];
-                    wd = p.W == RP_WEIGHT_LINEAR ? sg * tf : (p.W == RP_WEIGHT_QUADRATIC ? sg * tf * tf : sg);
-                }
-                so.rw[pos * 2 * A + a] = rd;
-                so.rw[pos * 2 * A + A + a] = wd;
-            }
-            so.mask[pos] = dc.mask[slot * dc.stride + tree];
-            so.payoff[pos] = dc.payoff[slot * dc.stride + tree];
-        }
-    }
-}
-
-// per-epoch discount constants of a RegretSchedule (regret/{linear,discounted,asymmetric}.rs)
-struct Discount {
-    float pos, neg, zero;
-};
-__device__ __forceinline__ Discount regret_discount(int R, float t, float pow15, float pow05) {
-    Discount d{1.0f, 1.0f, 1.0f};
-    const float lin = t / (t + 1.0f);
-    if (R == RP_REGRET_LINEAR) d = Discount{lin, lin, lin};
-    else if (R == RP_REGRET_ASYMMETRIC) d = Discount{1.0f, lin, lin};
-    else if (R == RP_REGRET_DISCOUNTED) {
-        const float xp = pow15, xn = pow05, xz = t / 1.0f;
-        d = Discount{xp / (xp + 1.0f), xn / (xn + 1.0f), xz / (xz + 1.0f)};
-    }
-    return d;
-}
-__device__ __forceinline__ uint32_t seg_base(const DevSorted& so, uint32_t info) {
-    uint32_t part = 0;
-    for (uint32_t i = lane_of(); i < info; i += 64) part += so.total[i];
-    for (int d = 32; d > 0; d >>= 1) part += __shfl_xor(part, d, 64);
-    return part;
-}
-
-#define TILE_FLOATS 1024u  // regret/weight deltas per LDS tile (16 per lane)
-#define TILE_REGS (TILE_FLOATS / 64u)
-#define TILE_PAD 4u        // row padding of the stream-major tile (keeps 16-B alignment, staggers banks)
-#define PTILE 1024u        // payoffs per LDS tile
-
-// LDS carve of k_chain (bytes): regret/weight tiles, mask tiles, payoff / reciprocal / divisor tiles
-#define CHAIN_TILE_WORDS (TILE_FLOATS + 2u * RP_MAX_ACTIONS * TILE_PAD)
-#define CHAIN_LDS_WORDS (2u * CHAIN_TILE_WORDS + 2u * (TILE_FLOATS / 2u) + 7u * PTILE)
-
-// wave 0: regret + weight cells, universal op acc <- max(acc * d + delta, floor) (x * 1.0f is exact, so Summed /
-// Floored / Constant / Linear-weight schedules are the same instruction stream with d = 1).  wave 1: payoff + visits.
-// Tiles are double buffered: the global loads of tile t+1 are issued into registers BEFORE the chain over tile t
-// and committed to LDS after it, so HBM/L2 latency hides under the serial chain.  In LDS a tile is stream-major
-// ([cell][entry]) so each chain lane reads its own stream 4 entries at a time (ds_read_b128), 16 entries ahead.
-template <bool SIGNED, bool PRUNED>
-__global__ __launch_bounds__(128) void k_chain(DevGame g, DevTables t, DevSorted so, StepParams p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const uint32_t info = blockIdx.x;
-    if (g.info_player[info] != p.walker) return;
-    const uint32_t len = so.total[info];
-    if (len == 0) return;
-    const uint32_t A = g.A, nact = g.info_actions[info], W2 = 2 * A;
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const size_t base = seg_base(so, info);
-    const float tf = (float)p.epoch;
-    float* tile = reinterpret_cast<float*>(smem);                                  // [2][CHAIN_TILE_WORDS]
-    uint32_t* mtile = reinterpret_cast<uint32_t*>(tile + 2 * CHAIN_TILE_WORDS);    // [2][TILE_FLOATS / 2]
-    float* ptile = reinterpret_cast<float*>(mtile + TILE_FLOATS);                  // [2][3][PTILE]: payoff, 1/b, b
-    if (wave == 0) {
-        const uint32_t T = (TILE_FLOATS / W2) & ~3u;  // Decisions per tile, multiple of 4
-        const uint32_t TP = T + TILE_PAD;             // row stride of the stream-major tile
-        const bool isreg = lane < A;
-        const uint32_t a = lane % A;
-        const bool chain = lane < W2 && a < nact;
-        const size_t cell = (size_t)info * A + a;
-        float acc = 0.0f, fl = RP_EPSILON;
-        Discount d{1.0f, 1.0f, 1.0f};
-        if (chain) {
-            if (isreg) {
-                acc = t.regret[cell];
-                fl = regret_floor_of(p.R, p.regret_min);
-                d = regret_discount(p.R, tf, p.pow15, p.pow05);
-            } else {
-                acc = t.weight[cell];
-                const float dw = p.W == RP_WEIGHT_EXPONENTIAL ? 0.9999f : 1.0f;
-                d = Discount{dw, dw, dw};
-            }
-        }
-        const uint32_t ntiles = (len + T - 1) / T;
-        float rg[TILE_REGS];
-        uint32_t mk[TILE_REGS / 2];
-        auto issue = [&](uint32_t tl) {
-            const size_t e0 = (base + (size_t)tl * T) * W2;
-            const uint32_t ne = min(T, len - tl * T), nfl = ne * W2;
-#pragma unroll
-            for (uint32_t r = 0; r < TILE_REGS; ++r) {
-                const uint32_t k = lane + 64 * r;
-                rg[r] = k < nfl ? so.rw[e0 + k] : 0.0f;
-            }
-            if (PRUNED) {
-#pragma unroll
-                for (uint32_t r = 0; r < TILE_REGS / 2; ++r) {
-                    const uint32_t k = lane + 64 * r;
-                    mk[r] = k < ne ? so.mask[base + (size_t)tl * T + k] : 0u;
-                }
-            }
-        };
-        auto commit = [&](uint32_t buf) {  // entry-major registers -> stream-major LDS
-#pragma unroll
-            for (uint32_t r = 0; r < TILE_REGS; ++r) {
-                const uint32_t k = lane + 64 * r;
-                if (k < T * W2) tile[buf * CHAIN_TILE_WORDS + (k % W2) * TP + k / W2] = rg[r];
-            }
-            if (PRUNED) {
-#pragma unroll
-                for (uint32_t r = 0; r < TILE_REGS / 2; ++r) mtile[buf * (TILE_FLOATS / 2) + lane + 64 * r] = mk[r];
-            }
-        };
-        auto step = [&](float delta, uint32_t m) {
-            float dd = d.zero;
-            if (SIGNED) dd = acc > 0.0f ? d.pos : (acc < 0.0f ? d.neg : d.zero);
-            const float nv = rp_maxf(acc * dd + delta, fl);
-            if (PRUNED) acc = (isreg && !((m >> a) & 1u)) ? acc : nv;
-            else acc = nv;
-        };
-        issue(0);
-        commit(0);
-        __builtin_amdgcn_wave_barrier();
-        for (uint32_t tl = 0; tl < ntiles; ++tl) {
-            const uint32_t buf = tl & 1u;
-            const bool more = tl + 1 < ntiles;
-            if (more) issue(tl + 1);
-            const uint32_t n = min(T, len - tl * T);
-            const float* row = tile + buf * CHAIN_TILE_WORDS + (chain ? lane : 0u) * TP;
-            const uint32_t* mrow = mtile + buf * (TILE_FLOATS / 2);
-            if (chain) {
-                const uint32_t n16 = n & ~15u;
-                uint32_t i = 0;
-                if (n16) {
-                    float4 c0 = *reinterpret_cast<const float4*>(row + 0), c1 = *reinterpret_cast<const float4*>(row + 4);
-                    float4 c2 = *reinterpret_cast<const float4*>(row + 8), c3 = *reinterpret_cast<const float4*>(row + 12);
-                    for (; i < n16; i += 16) {
-                        float4 x0 = c0, x1 = c1, x2 = c2, x3 = c3;
-                        if (i + 16 < n16) {  // the next 16 entries travel from LDS while these 16 are chained
-                            c0 = *reinterpret_cast<const float4*>(row + i + 16);
-                            c1 = *reinterpret_cast<const float4*>(row + i + 20);
-                            c2 = *reinterpret_cast<const float4*>(row + i + 24);
-                            c3 = *reinterpret_cast<const float4*>(row + i + 28);
-                        }
-                        uint32_t m[16];
-#pragma unroll
-                        for (uint32_t q = 0; q < 16; ++q) m[q] = PRUNED ? mrow[i + q] : 0xffffffffu;
-                        step(x0.x, m[0]); step(x0.y, m[1]); step(x0.z, m[2]); step(x0.w, m[3]);
-                        step(x1.x, m[4]); step(x1.y, m[5]); step(x1.z, m[6]); step(x1.w, m[7]);
-                        step(x2.x, m[8]); step(x2.y, m[9]); step(x2.z, m[10]); step(x2.w, m[11]);
-                        step(x3.x, m[12]); step(x3.y, m[13]); step(x3.z, m[14]); step(x3.w, m[15]);
-                    }
-                }
-                for (; i < n; ++i) step(row[i], PRUNED ? mrow[i] : 0xffffffffu);
-            }
-            if (more) commit(buf ^ 1u);
-            __builtin_amdgcn_wave_barrier();
-        }
-        if (chain) {
-            if (isreg) t.regret[cell] = acc;
-            else t.weight[cell] = acc;
-        }
-    } else {
-        // Welford mean with the pre-increment visit count (solver.rs:174-192): ev += (payoff - ev) / (n + 1).
-        // The divisor sequence is known in advance, so the whole wave precomputes b = (float)(n+1) and the
-        // correctly rounded 1/b per entry; the serial chain then needs mul + 2 fma per division
-        // (rp_div_by_recip1) and each quotient carries an exact off-path proof that it equals IEEE a / b.
-        const bool chain = lane < nact;
-        const size_t cell = (size_t)info * A + lane;
-        float ev = 0.0f;
-        uint32_t visits = 0;
-        if (chain) {
-            ev = t.payoff[cell];
-            visits = t.visits[cell];
-        }
-        const uint32_t v0 = __shfl(visits, 0, 64);
-        const float ev0 = __shfl(ev, 0, 64);
-        // every edge of an infoset is always visited together, so all its (payoff, visits) cells hold the same
-        // value and ONE chain serves them; anything else (a hand-made import) takes the plain path below
-        const bool uniform = __all(!chain || (visits == v0 && rp_f2u(ev) == rp_f2u(ev0)));
-        float* hist = ptile + 6 * PTILE;  // [PTILE] ev after each touch of the current tile
-        if (uniform) ev = ev0;
-        const float ev_start = ev;
-        if (uniform) {
-            const uint32_t ntiles = (len + PTILE - 1) / PTILE;
-            float rg[PTILE / 64];
-            auto issue = [&](uint32_t tl) {
-                const uint32_t n = min(PTILE, len - tl * PTILE);
-#pragma unroll
-                for (uint32_t r = 0; r < PTILE / 64; ++r) {
-                    const uint32_t k = lane + 64 * r;
-                    rg[r] = k < n ? so.payoff[base + (size_t)tl * PTILE + k] : 0.0f;
-                }
-            };
-            auto commit = [&](uint32_t tl, uint32_t buf) {
-                float* pt = ptile + buf * 3 * PTILE;
-#pragma unroll
-                for (uint32_t r = 0; r < PTILE / 64; ++r) {
-                    const uint32_t k = lane + 64 * r;
-                    const float b = (float)(v0 + tl * PTILE + k + 1u);  // (n + 1) as f32 (solver.rs:179)
-                    pt[k] = rg[r];
-                    pt[PTILE + k] = 1.0f / b;
-                    pt[2 * PTILE + k] = b;
-                }
-            };
-            issue(0);
-            commit(0, 0);
-            __builtin_amdgcn_wave_barrier();
-            for (uint32_t tl = 0; tl < ntiles; ++tl) {
-                const uint32_t buf = tl & 1u;
-                const bool more = tl + 1 < ntiles;
-                if (more) issue(tl + 1);
-                const uint32_t n = min(PTILE, len - tl * PTILE);
-                const float* pt = ptile + buf * 3 * PTILE;
-#ifndef RP_EXPERIMENT_SKIP_PAYOFF
-                // (1) the serial chain: 5 VALU ops per touch (sub, mul, fma, fma, add); lane 0 logs ev after each touch
-                const float ev_tile = ev;
-                {
-                    auto fast = [&](float pv, float rv, float bv) {
-                        const float s = pv - ev;
-                        const float q0 = s * rv;
-                        const float e0 = fmaf(-bv, q0, s);
-                        ev += fmaf(e0, rv, q0);
-                        return ev;
-                    };
-                    const uint32_t n4 = n & ~3u;
-                    uint32_t i = 0;
-                    for (; i < n4; i += 4) {
-                        const float4 pv = *reinterpret_cast<const float4*>(pt + i);
-                        const float4 rv = *reinterpret_cast<const float4*>(pt + PTILE + i);
-                        const float4 bv = *reinterpret_cast<const float4*>(pt + 2 * PTILE + i);
-                        float4 h;
-                        h.x = fast(pv.x, rv.x, bv.x); h.y = fast(pv.y, rv.y, bv.y);
-                        h.z = fast(pv.z, rv.z, bv.z); h.w = fast(pv.w, rv.w, bv.w);
-                        if (lane == 0) *reinterpret_cast<float4*>(hist + i) = h;
-                    }
-                    for (; i < n; ++i) {
-                        const float e = fast(pt[i], pt[PTILE + i], pt[2 * PTILE + i]);
-                        if (lane == 0) hist[i] = e;
-                    }
-                }
-                __builtin_amdgcn_wave_barrier();
-                // (2) the proof, lane-parallel and off the chain: every touch's quotient is re-derived from the logged
-                //     ev and checked with the exact-residual criterion of rp_div_by_recip1 (== IEEE s / b when proven)
-                bool bad = false;
-                for (uint32_t k = lane; k < n; k += 64) {
-                    const float prev = k ? hist[k - 1] : ev_tile;
-                    int proven;
-                    const float q = rp_div_by_recip1(pt[k] - prev, pt[2 * PTILE + k], pt[PTILE + k], &proven);
-                    bad |= !proven || (prev + q != hist[k]);
-                }
-                if (__any(bad)) {  // essentially never: redo this tile with IEEE divisions
-                    ev = ev_tile;
-                    for (uint32_t k = 0; k < n; ++k) ev += (pt[k] - ev) / pt[2 * PTILE + k];
-                }
-                __builtin_amdgcn_wave_barrier();
-#endif
-                if (more) commit(tl + 1, buf ^ 1u);
-                __builtin_amdgcn_wave_barrier();
-            }
-        }
-        if (chain) {
-            if (!uniform) {  // edges of one infoset with different visit counts (only after a hand-made import)
-                ev = ev_start;
-                uint32_t v = visits;
-                for (uint32_t i = 0; i < len; ++i) {
-                    ev += (so.payoff[base + i] - ev) / (float)(v + 1u);
-                    v += 1u;
-                }
-            }
-            t.payoff[cell] = ev;
-            t.visits[cell] = visits + len;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Composed update (include/rp_mi355x.h rp_compose_block; oracle: ora_mccfr_step_local): the serial chain of the
-// ordered mode is replaced by a two-level composition of per-cell maps F(x) = max(a x + b, m).
-//   k_block_maps  one workgroup per (infoset, block of T consecutive Decisions): sequential composition inside the
-//                 block, all blocks of all infosets in parallel
-//   k_combine2    (infoset, part) workgroups: block maps -> group maps -> Cell / InfoSum blob, or straight into the tables
-// ------------------------------------------------------------------------------------------------
-// Map / map_compose live in mccfr_kernels.hpp
-// block = the Decisions of infoset blockIdx.y produced by chunk blockIdx.x (RP_COMPOSE_CHUNK == CH_TREES trees):
-// in the sorted layout a contiguous group.  Large games (per-infoset slot map); small games fuse the sort away, below.
-template <bool PRUNED>
-__global__ __launch_bounds__(128) void k_block_maps(DevGame g, DevSorted so, StepParams p, Map* bmaps, float* bpsum,
-                                                    uint32_t* bcnt, uint32_t nblk_max) {
-    __shared__ __attribute__((aligned(16))) float tile[TILE_FLOATS + 2 * RP_MAX_ACTIONS * TILE_PAD];
-    __shared__ uint32_t mtile[TILE_FLOATS / 2];
-    __shared__ __attribute__((aligned(16))) float ptile[TILE_FLOATS / 2];
-    const uint32_t info = blockIdx.y, blk = blockIdx.x;
-    if (g.info_player[info] != p.walker) return;
-    const uint32_t A = g.A, nact = g.info_actions[info], W2 = 2 * A;
-    const uint32_t T = compose_block(A);  // touches per LDS tile
-    const uint32_t n = so.counts[(size_t)info * so.n_chunks + blk];
-    const uint32_t TP = T + TILE_PAD;
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const size_t base = seg_base(so, info) + so.offs[(size_t)info * so.n_chunks + blk];
-    const float NEG_INF = rp_u2f(0xff800000u);
-    const bool isreg = lane < A;
-    const uint32_t a = lane % A;
-    const bool chain = lane < W2 && a < nact;
-    const float tf = (float)p.epoch;
-    const float fl = isreg ? regret_floor_of(p.R, p.regret_min) : RP_EPSILON;
-    const float d = isreg ? (p.R == RP_REGRET_LINEAR ? tf / (tf + 1.0f) : 1.0f) : (p.W == RP_WEIGHT_EXPONENTIAL ? 0.9999f : 1.0f);
-    float ma = 1.0f, mb = 0.0f, mm = NEG_INF, psum = 0.0f;
-    uint32_t cnt = 0;
-    for (uint32_t t0 = 0; t0 < n; t0 += T) {  // the chain runs through the block tile by tile
-        const uint32_t m = min(T, n - t0);
-        if (wave == 0) {
-            const size_t e0 = (base + t0) * W2;
-            const uint32_t nfl = m * W2;
-            float lr[TILE_FLOATS / 64];
-#pragma unroll
-            for (uint32_t q = 0; q < TILE_FLOATS / 64; ++q) {
-                const uint32_t k = lane + 64 * q;
-                lr[q] = k < nfl ? so.rw[e0 + k] : 0.0f;
-            }
-#pragma unroll
-            for (uint32_t q = 0; q < TILE_FLOATS / 64; ++q) {
-                const uint32_t k = lane + 64 * q;
-                if (k < nfl) tile[(k % W2) * TP + k / W2] = lr[q];
-            }
-            if (PRUNED)
-                for (uint32_t k = lane; k < m; k += 64) mtile[k] = so.mask[base + t0 + k];
-        } else {
-            for (uint32_t k = lane; k < m; k += 64) ptile[k] = so.payoff[base + t0 + k];
-        }
-        __syncthreads();
-        if (wave == 0 && chain) {
-            const float* row = tile + lane * TP;
-            for (uint32_t i = 0; i < m; ++i) {
-                const float delta = row[i];
-                const bool skip = PRUNED && isreg && !((mtile[i] >> a) & 1u);
-                // first touch of the block: (d, delta, floor); then a <- a d, b <- b d + delta, m <- max(m d + delta, floor)
-                const float na = cnt ? ma * d : d;
-                const float nb = cnt ? mb * d + delta : delta;
-                const float nm = cnt ? rp_maxf(mm * d + delta, fl) : fl;
-                ma = skip ? ma : na;
-                mb = skip ? mb : nb;
-                mm = skip ? mm : nm;
-                cnt += skip ? 0u : 1u;
-            }
-        }
-        if (wave == 1 && lane == 0)
-            for (uint32_t i = 0; i < m; ++i) psum += ptile[i];
-        __syncthreads();
-    }
-    const size_t slot = (size_t)info * nblk_max + blk;
-    if (wave == 0 && lane < W2) bmaps[slot * W2 + lane] = Map{ma, mb, mm, chain ? cnt : 0u};
-    if (wave == 1 && lane == 0) {
-        bpsum[slot] = psum;
-        bcnt[slot] = n;
-    }
-}
-
-// Small games: block maps straight from the lane-interleaved Decisions of one chunk — no sorted copy in HBM at all.
-// One thread per tree.  The chunk's Decisions get their place in per-infoset, tree-ordered lists (LDS bitmap + prefix
-// popcount, as k_compact_small); then, cell by cell, every thread drops its trees' values at those places in an LDS
-// array (global reads coalesced over trees) and one thread per infoset composes its list sequentially out of LDS.
-template <bool PRUNED, uint32_t PASSES>
-__global__ __launch_bounds__(CH_THREADS) void k_chunk_maps(DevGame g, DevDecisions dc, StepParams p, Map* bmaps, float* bpsum,
-                                                           uint32_t* bcnt, uint32_t nblk_max) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t cm_lds[];
-    __shared__ uint32_t wave_tot[CH_THREADS / 64];
-    const uint32_t NI = g.n_infos, A = g.A, W2 = 2 * A, chunk = blockIdx.x, tid = threadIdx.x, MD = dc.maxdec;
-    uint32_t* bits = cm_lds;                                              // [NI][SM_WORDS]
-    uint32_t* lcount = bits + NI * SM_WORDS;                              // [NI]
-    uint32_t* lbase = lcount + NI;                                        // [NI]
-    float* vals = reinterpret_cast<float*>(lbase + NI);                   // [MD * CH_TREES] one cell's values, list order
-    uint16_t* pre = reinterpret_cast<uint16_t*>(vals + MD * CH_TREES);    // [NI][SM_WORDS]
-    uint16_t* posl = pre + NI * SM_WORDS;                                 // [MD][CH_TREES] list position of (slot, tree)
-    uint16_t* lmask = posl + MD * CH_TREES;                               // [MD * CH_TREES] expanded-edge masks (PRUNED)
-    chunk_bitmap(dc, NI, chunk, p.batch, bits);
-    for (uint32_t info = tid; info < NI; info += CH_THREADS) {
-        uint32_t run = 0;
-        for (uint32_t w = 0; w < SM_WORDS; ++w) {
-            pre[info * SM_WORDS + w] = (uint16_t)run;
-            run += __popc(bits[info * SM_WORDS + w]);
-        }
-        lcount[info] = run;
-    }
-    __syncthreads();
-    lds_exscan(lcount, lbase, NI, wave_tot);
-    const uint32_t lt = tid, tree = chunk * CH_TREES + lt;  // CH_TREES == CH_THREADS: one tree per thread
-    const uint32_t nd = tree < p.batch ? dc.ndec[tree] : 0u;
-    for (uint32_t slot = 0; slot < nd; ++slot) {
-        const uint32_t info = dc.info[slot * dc.stride + tree];
-        const uint32_t rank = pre[info * SM_WORDS + (lt >> 5)] + __popc(bits[info * SM_WORDS + (lt >> 5)] & ((1u << (lt & 31u)) - 1u));
-        const uint32_t pos = lbase[info] + rank;
-        posl[slot * CH_TREES + lt] = (uint16_t)pos;
-        if (PRUNED) lmask[pos] = (uint16_t)dc.mask[slot * dc.stride + tree];
-    }
-    const float NEG_INF = rp_u2f(0xff800000u);
-    const float tf = (float)p.epoch;
-    // chain phase: thread t owns infosets t, t + 256, ... (PASSES = 1 when the game has at most 256 infosets)
-    uint32_t my_nact[PASSES], my_n[PASSES], my_base[PASSES];
-#pragma unroll
-    for (uint32_t q = 0; q < PASSES; ++q) {
-        const uint32_t info = tid + q * CH_THREADS;
-        const bool mine = info < NI && g.info_player[info < NI ? info : 0u] == p.walker;
-        my_nact[q] = mine ? g.info_actions[info] : 0u;  // 0: not this walker's infoset
-        my_n[q] = mine ? lcount[info] : 0u;
-        my_base[q] = mine ? lbase[info] : 0u;
-    }
-    for (uint32_t c = 0; c <= W2; ++c) {  // regret cells, weight cells, then the payoff sum
-        const bool isreg = c < A, ispay = c == W2;
-        const uint32_t a = c % A;
-        __syncthreads();  // the previous cell's chains are done with `vals`
-        for (uint32_t slot = 0; slot < nd; ++slot) {
-            float v;
-            if (ispay) v = dc.payoff[slot * dc.stride + tree];
-            else if (isreg) v = dc.regret[(slot * A + a) * dc.stride + tree];
-            else {
-                const float sg = dc.policy[(slot * A + a) * dc.stride + tree];
-                v = p.W == RP_WEIGHT_LINEAR ? sg * tf : (p.W == RP_WEIGHT_QUADRATIC ? sg * tf * tf : sg);
-            }
-            vals[posl[slot * CH_TREES + lt]] = v;
-        }
-        __syncthreads();
-#pragma unroll
-        for (uint32_t q = 0; q < PASSES; ++q) {
-            const uint32_t info = tid + q * CH_THREADS;
-            if (!my_nact[q]) continue;
-            const uint32_t n = my_n[q], base = my_base[q];
-            const size_t slot_out = (size_t)info * nblk_max + chunk;
-            if (ispay) {  // payoff sum of the block, left fold from 0.0f
-                float sum = 0.0f;
-                for (uint32_t e = 0; e < n; ++e) sum += vals[base + e];
-                bpsum[slot_out] = sum;
-                bcnt[slot_out] = n;
-                continue;
-            }
-            const bool chain = a < my_nact[q];
-            const float fl = isreg ? regret_floor_of(p.R, p.regret_min) : RP_EPSILON;
-            const float d = isreg ? (p.R == RP_REGRET_LINEAR ? tf / (tf + 1.0f) : 1.0f) : (p.W == RP_WEIGHT_EXPONENTIAL ? 0.9999f : 1.0f);
-            float ma = 1.0f, mb = 0.0f, mm = NEG_INF;
-            uint32_t cnt = 0;
-            if (chain) {
-                for (uint32_t e = 0; e < n; ++e) {
-                    const float delta = vals[base + e];
-                    const bool skip = PRUNED && isreg && !((lmask[base + e] >> a) & 1u);
-                    // first touch of the block: (d, delta, floor); then a <- a d, b <- b d + delta, m <- max(m d + delta, floor)
-                    const float na = cnt ? ma * d : d;
-                    const float nb = cnt ? mb * d + delta : delta;
-                    const float nm = cnt ? rp_maxf(mm * d + delta, fl) : fl;
-                    ma = skip ? ma : na;
-                    mb = skip ? mb : nb;
-                    mm = skip ? mm : nm;
-                    cnt += skip ? 0u : 1u;
-                }
-            }
-            bmaps[slot_out * W2 + c] = Map{ma, mb, mm, chain ? cnt : 0u};
-        }
-    }
-}
-
-}  // namespace rp
-#include "traverse_static.hpp"
-namespace rp {
-
-// The two-level fold of the block maps (include/rp_mi355x.h RP_FOLD_GROUP: the block maps of a cell composed sequentially
-// inside groups of RP_FOLD_GROUP consecutive blocks, the group maps then in group order), spread over (infoset, part)
-// workgroups, and — APPLY — the rest of the step with it.
-//   stage 1  a part owns CB2_GPW(2A) consecutive groups: its block maps are one contiguous run of HBM, copied to LDS by all
-//            256 threads at once (one round trip instead of a chain of eight per thread), then thread (group, cell) composes
-//            its RP_FOLD_GROUP maps out of LDS in block order; the group maps go to HBM with agent-scope stores;
-//   stage 2  the LAST part of an infoset to finish (arrival counter; which one is timing, what it computes is not) folds the
-//            infoset's group maps in group order into the summary cell maps, payoff sum and count;
-//   APPLY    single-GPU step: that workgroup also applies the summary to the infoset's table row (k_fold with world = 1)
-//            and refreshes the row of the per-infoset tables the next traversal reads (k_prepare_infos): one launch
-//            instead of three.  Otherwise it writes the summary blob (rp_mccfr_step_local).
-// Cross-workgroup data is a few KB per infoset: agent-scope (sc1) stores + s_waitcnt before the arrival, agent-scope
-// loads after it.  (A release FENCE at agent scope writes back a whole XCD's L2: tried on the block maps, 4x slower.)
-// This hand-over is written against the gfx942 / gfx950 memory system, not against the portable memory model: relaxed agent-scope
-// stores are sc1 write-through stores that `s_waitcnt vmcnt(0)` waits for (no separate store counter), relaxed agent-scope loads
-// bypass the XCD's non-coherent lines.  On any other target the arrival counter would need release / acquire semantics:
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__)
-#error "k_combine2's cross-workgroup hand-over relies on gfx942/gfx950 store counting and sc1 semantics: use an acq_rel arrival counter on other targets"
-#endif
-__device__ __forceinline__ uint32_t ld_agent(const uint32_t* q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_agent(uint32_t* q, uint32_t v) { __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ Map ld_map(const Map* m) {
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(m);
-    return Map{rp_u2f(ld_agent(w)), rp_u2f(ld_agent(w + 1)), rp_u2f(ld_agent(w + 2)), ld_agent(w + 3)};
-}
-__device__ __forceinline__ void st_map(Map* m, const Map& v) {
-    uint32_t* w = reinterpret_cast<uint32_t*>(m);
-    st_agent(w, rp_f2u(v.a));
-    st_agent(w + 1, rp_f2u(v.b));
-    st_agent(w + 2, rp_f2u(v.m));
-    st_agent(w + 3, v.n);
-}
-__host__ __device__ inline uint32_t cb2_gpw(uint32_t W2) { return 32u / W2 ? 32u / W2 : 1u; }  // groups per part: a 32 KB tile
-struct FoldScratch {
-    Map* gmaps;      // [n_infos][ngrp_max][2A]
-    float* gpsum;    // [n_infos][ngrp_max]
-    uint32_t* gcnt;  // [n_infos][ngrp_max]
-    uint32_t* done;  // [n_infos] parts finished
-    uint32_t ngrp_max;
-};
-template <bool APPLY>
-__global__ __launch_bounds__(256) void k_combine2(DevGame g, DevTables t, DevInfoTab it, StepParams p, const Map* bmaps, const float* bpsum,
-                                                  const uint32_t* bcnt, uint32_t nblk_max, FoldScratch fs, Cell* cells, InfoSum* sums) {
-    extern __shared__ __attribute__((aligned(16))) uint4 cb_lds[];
-    __shared__ uint32_t role, sh_len;
-    __shared__ float sh_ps;
-    const uint32_t info = blockIdx.x, part = blockIdx.y, tid = threadIdx.x;
-    const uint32_t A = g.A, W2 = 2 * A, GPW = cb2_gpw(W2);
-    const Map ident{1.0f, 0.0f, rp_u2f(0xff800000u), 0u};
-    if (g.info_player[info] != p.walker) {  // not this walker's infoset: nothing happened to it
-        if (!APPLY && part == 0) {
-            if (tid < W2) {
-                Cell* cl = &cells[(size_t)info * A + tid % A];
-                if (tid < A) { cl->ra = ident.a; cl->rb = ident.b; cl->rm = ident.m; cl->rn = 0u; }
-                else { cl->wa = ident.a; cl->wb = ident.b; cl->wm = ident.m; cl->wn = 0u; }
-            } else if (tid == W2) {
-                sums[info] = InfoSum{0u, 0.0f};
-            }
-        }
-        return;
-    }
-    const uint32_t nb = (p.batch + RP_COMPOSE_CHUNK - 1) / RP_COMPOSE_CHUNK;  // one block per chunk of trees
-    const uint32_t ngrp = (nb + RP_FOLD_GROUP - 1) / RP_FOLD_GROUP, nparts = (ngrp + GPW - 1) / GPW;
-    if (part >= nparts) return;
-    const uint32_t g0 = part * GPW, b_lo = g0 * RP_FOLD_GROUP, b_hi = min(nb, (g0 + GPW) * RP_FOLD_GROUP), count = b_hi - b_lo;
-    uint4* tile = cb_lds;                                                                // [GPW * 64][W2] block maps
-    float* ps_t = reinterpret_cast<float*>(tile + (size_t)GPW * RP_FOLD_GROUP * W2);     // [GPW * 64]
-    uint32_t* cn_t = reinterpret_cast<uint32_t*>(ps_t + GPW * RP_FOLD_GROUP);            // [GPW * 64]
-    {
-        const uint4* src = reinterpret_cast<const uint4*>(bmaps + ((size_t)info * nblk_max + b_lo) * W2);
-        for (uint32_t e = tid; e < count * W2; e += 256u) tile[e] = src[e];
-        for (uint32_t e = tid; e < count; e += 256u) {
-            ps_t[e] = bpsum[(size_t)info * nblk_max + b_lo + e];
-            cn_t[e] = bcnt[(size_t)info * nblk_max + b_lo + e];
-        }
-    }
-    __syncthreads();
-    if (tid < GPW * W2) {
-        const uint32_t s = tid / W2, c = tid % W2, grp = g0 + s;
-        if (grp < ngrp) {
-            const uint32_t lo = s * RP_FOLD_GROUP, hi = min(count, lo + RP_FOLD_GROUP);
-            Map m = ident;
-            for (uint32_t b0 = lo; b0 < hi; b0 += 8u) {  // eight LDS reads in flight ahead of the dependent chain
-                uint4 v[8];
-#pragma unroll
-                for (uint32_t q = 0; q < 8u; ++q) v[q] = tile[min(b0 + q, hi - 1u) * W2 + c];
-#pragma unroll
-                for (uint32_t q = 0; q < 8u; ++q)
-                    if (b0 + q < hi) m = map_compose(m, Map{rp_u2f(v[q].x), rp_u2f(v[q].y), rp_u2f(v[q].z), v[q].w});
-            }
-            st_map(&fs.gmaps[((size_t)info * fs.ngrp_max + grp) * W2 + c], m);
-        }
-    } else if (tid < GPW * W2 + GPW) {
-        const uint32_t s = tid - GPW * W2, grp = g0 + s;
-        if (grp < ngrp) {
-            const uint32_t lo = s * RP_FOLD_GROUP, hi = min(count, lo + RP_FOLD_GROUP);
-            float gp = 0.0f;
-            uint32_t gc = 0;
-            for (uint32_t b = lo; b < hi; ++b) {
-                gp += ps_t[b];
-                gc += cn_t[b];
-            }
-            st_agent(reinterpret_cast<uint32_t*>(fs.gpsum) + (size_t)info * fs.ngrp_max + grp, rp_f2u(gp));
-            st_agent(fs.gcnt + (size_t)info * fs.ngrp_max + grp, gc);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the group maps are in memory before this part counts itself in
-    __syncthreads();
-    if (tid == 0) role = atomicAdd(&fs.done[info], 1u) == nparts - 1u ? 1u : 0u;
-    __syncthreads();
-    if (!role) return;
-    if (tid == 0) fs.done[info] = 0;  // for the next launch
-    // the infoset's group maps: into LDS by all threads at once (one round trip), then folded in group order
-    Map tot = ident;
-    float ps = 0.0f;
-    uint32_t len = 0;
-    const uint32_t TILE_G = GPW * RP_FOLD_GROUP;
-    const uint32_t* gm = reinterpret_cast<const uint32_t*>(fs.gmaps + (size_t)info * fs.ngrp_max * W2);
-    for (uint32_t k0 = 0; k0 < ngrp; k0 += TILE_G) {
-        const uint32_t n = min(TILE_G, ngrp - k0);
-        __syncthreads();
-        for (uint32_t e = tid; e < n * W2; e += 256u) {
-            const uint32_t* w = gm + ((size_t)k0 * W2 + e) * 4u;
-            tile[e] = make_uint4(ld_agent(w), ld_agent(w + 1), ld_agent(w + 2), ld_agent(w + 3));
-        }
-        for (uint32_t e = tid; e < n; e += 256u) {
-            ps_t[e] = rp_u2f(ld_agent(reinterpret_cast<const uint32_t*>(fs.gpsum) + (size_t)info * fs.ngrp_max + k0 + e));
-            cn_t[e] = ld_agent(fs.gcnt + (size_t)info * fs.ngrp_max + k0 + e);
-        }
-        __syncthreads();
-        if (tid < W2) {
-            for (uint32_t k0b = 0; k0b < n; k0b += 8u) {
-                uint4 v[8];
-#pragma unroll
-                for (uint32_t q = 0; q < 8u; ++q) v[q] = tile[min(k0b + q, n - 1u) * W2 + tid];
-#pragma unroll
-                for (uint32_t q = 0; q < 8u; ++q)
-                    if (k0b + q < n) tot = map_compose(tot, Map{rp_u2f(v[q].x), rp_u2f(v[q].y), rp_u2f(v[q].z), v[q].w});
-            }
-        } else if (tid == W2) {
-            for (uint32_t k = 0; k < n; ++k) {
-                ps += ps_t[k];
-                len += cn_t[k];
-            }
-        }
-    }
-    if (tid == W2) {
-        sh_ps = ps;
-        sh_len = len;
-    }
-    if (!APPLY) {
-        if (tid < W2) {
-            Cell* cl = &cells[(size_t)info * A + tid % A];
-            if (tid < A) { cl->ra = tot.a; cl->rb = tot.b; cl->rm = tot.m; cl->rn = tot.n; }
-            else { cl->wa = tot.a; cl->wb = tot.b; cl->wm = tot.m; cl->wn = tot.n; }
-        }
-        __syncthreads();
-        if (tid == 0) sums[info] = InfoSum{sh_len, sh_ps};
-        return;
-    }
-    // k_fold, world = 1, for this infoset's row
-    __syncthreads();
-    const uint32_t nact = g.info_actions[info];
-    if (tid < W2 && tid % A < nact) {
-        const uint32_t cell = info * A + tid % A;
-        if (tid < A) {
-            float r = t.regret[cell];
-            if (tot.n) r = rp_maxf(tot.a * r + tot.b, tot.m);
-            t.regret[cell] = r;
-            float ev = t.payoff[cell];
-            uint32_t visits = t.visits[cell];
-            if (sh_len) {
-                const uint32_t n2 = visits + sh_len;
-                ev = ev + (sh_ps - (float)sh_len * ev) / (float)n2;
-                visits = n2;
-            }
-            t.payoff[cell] = ev;
-            t.visits[cell] = visits;
-        } else {
-            float w = t.weight[cell];
-            if (tot.n) w = rp_maxf(tot.a * w + tot.b, tot.m);
-            t.weight[cell] = w;
-        }
-    }
-    __syncthreads();  // workgroup scope: the row just written is what prepare_one reads
-    if (tid == 0) prepare_one(g, t, p, it, info);
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_fold: the receiving side of the multi-GPU exchange (oracle: ora_mccfr_step_apply)
-// ------------------------------------------------------------------------------------------------
-// one thread per table cell; `blob` holds `world` summaries back to back: [cells][sums]
-__global__ void k_fold(DevGame g, DevTables t, const unsigned char* blob, size_t blob_stride, uint32_t world) {
-    const uint32_t cell = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t ncell = g.n_infos * g.A;
-    if (cell >= ncell) return;
-    const uint32_t info = cell / g.A, a = cell % g.A;
-    if (a >= g.info_actions[info]) return;
-    float r = t.regret[cell], w = t.weight[cell], ev = t.payoff[cell];
-    uint32_t visits = t.visits[cell];
-    for (uint32_t rk = 0; rk < world; ++rk) {
-        const unsigned char* b = blob + (size_t)rk * blob_stride;
-        const Cell c = reinterpret_cast<const Cell*>(b)[cell];
-        const InfoSum s = reinterpret_cast<const InfoSum*>(b + (size_t)ncell * sizeof(Cell))[info];
-        if (c.rn) r = rp_maxf(c.ra * r + c.rb, c.rm);
-        if (c.wn) w = rp_maxf(c.wa * w + c.wb, c.wm);
-        if (s.count) {
-            const uint32_t n2 = visits + s.count;
-            ev = ev + (s.psum - (float)s.count * ev) / (float)n2;
-            visits = n2;
-        }
-    }
-    t.regret[cell] = r;
-    t.weight[cell] = w;
-    t.payoff[cell] = ev;
-    t.visits[cell] = visits;
-}
-
-// the exchange window (rp_mccfr_window_local): acc <- step o acc per table cell — the maps of consecutive local
-// steps composed in step order, touch counts, payoff sums and visit counts added (oracle: ora_mccfr_window_accumulate)
-__global__ void k_accumulate(DevGame g, unsigned char* acc, const unsigned char* step, uint32_t first) {
-    const uint32_t cell = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t ncell = g.n_infos * g.A;
-    if (cell >= ncell) return;
-    const Cell s = reinterpret_cast<const Cell*>(step)[cell];
-    Cell* ac = reinterpret_cast<Cell*>(acc) + cell;
-    if (first) {
-        *ac = s;
-    } else {
-        const Cell a = *ac;
-        const Map r = map_compose(Map{a.ra, a.rb, a.rm, a.rn}, Map{s.ra, s.rb, s.rm, s.rn});
-        const Map w = map_compose(Map{a.wa, a.wb, a.wm, a.wn}, Map{s.wa, s.wb, s.wm, s.wn});
-        *ac = Cell{r.a, r.b, r.m, w.a, w.b, w.m, r.n, w.n};
-    }
-    if (cell % g.A == 0) {
-        const uint32_t info = cell / g.A;
-        const InfoSum si = reinterpret_cast<const InfoSum*>(step + (size_t)ncell * sizeof(Cell))[info];
-        InfoSum* ai = reinterpret_cast<InfoSum*>(acc + (size_t)ncell * sizeof(Cell)) + info;
-        if (first) *ai = si;
-        else *ai = InfoSum{ai->count + si.count, ai->psum + si.psum};
-    }
-}
-
-}  // namespace rp
 
 // =================================================================================================
 // host side
@@ -1709,7 +117,7 @@ int set_device(const rp_mccfr* h) {
     return RP_OK;
 }
 
-size_t chain_lds_bytes(uint32_t A) { (void)A; return (size_t)CHAIN_LDS_WORDS * 4; }
+size_t chain_lds_bytes() { return (size_t)CHAIN_LDS_WORDS * 4; }
 
 size_t summary_bytes_of(const rp_mccfr* h) {
     return (size_t)h->tbl.n_infos * h->tbl.max_actions * sizeof(Cell) + (size_t)h->tbl.n_infos * sizeof(InfoSum);
@@ -1881,6 +289,36 @@ void clock_drain(KernelClock& c) {
     }
     c.pending.clear();
 }
+void clock_drain_all(rp_mccfr* h) {
+    for (KernelClock* c : {&h->clk_traverse, &h->clk_compact, &h->clk_update}) clock_drain(*c);
+}
+
+// run-time flags -> template arguments: f(std::bool_constant<a>{}, std::bool_constant<b>{})
+template <class F>
+void with_bool(bool a, F&& f) {
+    if (a) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <class F>
+void with_bools(bool a, bool b, F&& f) {
+    with_bool(a, [&](auto ta) { with_bool(b, [&](auto tb) { f(ta, tb); }); });
+}
+
+// rp_mccfr::static_skel -> the skeleton type: f(KuhnSkel{}) or f(LeducSkel{}); and the instantiations of the skeleton kernels:
+// f(G{}, std::integral_constant<int, walker>{}, std::bool_constant<pruned>{}, std::bool_constant<ref>{})
+template <class F>
+void with_skeleton(int static_skel, F&& f) {
+    if (static_skel == 1) f(KuhnSkel{});
+    else if (static_skel == 2) f(LeducSkel{});  // 0: the game matches no skeleton, nothing to instantiate
+}
+template <class F>
+void with_static_traversal(int static_skel, uint32_t walker, bool pruned, bool ref, F&& f) {
+    with_skeleton(static_skel, [&](auto gt) {
+        with_bool(walker == 0, [&](auto w0) {
+            with_bools(pruned, ref, [&](auto pr, auto rf) { f(gt, std::integral_constant<int, decltype(w0)::value ? 0 : 1>{}, pr, rf); });
+        });
+    });
+}
 
 // Does the game's state table match skeleton G node for node, for EVERY chance outcome?  (traverse_static.hpp)  Also: an
 // infoset belongs to one skeleton node only, so a sampled tree meets each walker infoset at most once (a span of the
@@ -2006,31 +444,18 @@ int launch_traverse(rp_mccfr* h, const StepParams& p) {
     if (h->static_skel) {
         launch_prepare(h, p);
         const dim3 grid((h->batch + 255) / 256), block(256);
-        const bool pr = p.S != RP_SAMPLING_EXTERNAL, rf = p.ref_info != nullptr;
-#define LAUNCH_STATIC(G, WK)                                                                                                   \
-    do {                                                                                                                       \
-        if (pr && rf) hipLaunchKernelGGL((k_traverse_static<G, WK, true, true>), grid, block, 0, h->stream, h->g, h->itab, h->dc, p);    \
-        else if (pr) hipLaunchKernelGGL((k_traverse_static<G, WK, true, false>), grid, block, 0, h->stream, h->g, h->itab, h->dc, p);   \
-        else if (rf) hipLaunchKernelGGL((k_traverse_static<G, WK, false, true>), grid, block, 0, h->stream, h->g, h->itab, h->dc, p);   \
-        else hipLaunchKernelGGL((k_traverse_static<G, WK, false, false>), grid, block, 0, h->stream, h->g, h->itab, h->dc, p);          \
-    } while (0)
-        if (h->static_skel == 1) {
-            if (p.walker == 0) LAUNCH_STATIC(KuhnSkel, 0);
-            else LAUNCH_STATIC(KuhnSkel, 1);
-        } else {
-            if (p.walker == 0) LAUNCH_STATIC(LeducSkel, 0);
-            else LAUNCH_STATIC(LeducSkel, 1);
-        }
-#undef LAUNCH_STATIC
+        with_static_traversal(h->static_skel, p.walker, p.S != RP_SAMPLING_EXTERNAL, p.ref_info != nullptr, [&](auto gt, auto wk, auto pr, auto rf) {
+            hipLaunchKernelGGL((k_traverse_static<decltype(gt), decltype(wk)::value, decltype(pr)::value, decltype(rf)::value>), grid, block, 0,
+                               h->stream, h->g, h->itab, h->dc, p);
+        });
     } else if (h->use_lds_traverse) {
         launch_prepare(h, p);
         const size_t lds = traverse_lds_bytes(h);
         const dim3 grid((h->batch + 63) / 64), block(64);
-#define LAUNCH_TRAVERSE(TV) \
-    hipLaunchKernelGGL((k_traverse_lds<TV>), grid, block, lds, h->stream, h->g, h->itab, h->dc, p, h->sc.maxn, h->sc.maxs, h->maxint)
-        if (h->tbl.max_actions <= 4) LAUNCH_TRAVERSE(true);
-        else LAUNCH_TRAVERSE(false);
-#undef LAUNCH_TRAVERSE
+        with_bool(h->tbl.max_actions <= 4, [&](auto tv) {
+            hipLaunchKernelGGL((k_traverse_lds<decltype(tv)::value>), grid, block, lds, h->stream, h->g, h->itab, h->dc, p, h->sc.maxn, h->sc.maxs,
+                               h->maxint);
+        });
     } else {
         launch_prepare_ref(h, p);
         const uint32_t threads = 256, blocks = (h->batch + threads - 1) / threads;
@@ -2063,15 +488,14 @@ int launch_sort(rp_mccfr* h, const StepParams& p) {
 }
 
 int launch_chain(rp_mccfr* h, const StepParams& p) {
-    const size_t lds = chain_lds_bytes(h->tbl.max_actions);
+    const size_t lds = chain_lds_bytes();
     const bool sgn = h->R == RP_REGRET_DISCOUNTED || h->R == RP_REGRET_ASYMMETRIC;
     const bool prn = h->S != RP_SAMPLING_EXTERNAL;
     const dim3 grid(h->tbl.n_infos), block(128);
     clock_begin(h, h->clk_update);
-    if (sgn && prn) hipLaunchKernelGGL((k_chain<true, true>), grid, block, lds, h->stream, h->g, h->t, h->so, p);
-    else if (sgn) hipLaunchKernelGGL((k_chain<true, false>), grid, block, lds, h->stream, h->g, h->t, h->so, p);
-    else if (prn) hipLaunchKernelGGL((k_chain<false, true>), grid, block, lds, h->stream, h->g, h->t, h->so, p);
-    else hipLaunchKernelGGL((k_chain<false, false>), grid, block, lds, h->stream, h->g, h->t, h->so, p);
+    with_bools(sgn, prn, [&](auto sg, auto pr) {
+        hipLaunchKernelGGL((k_chain<decltype(sg)::value, decltype(pr)::value>), grid, block, lds, h->stream, h->g, h->t, h->so, p);
+    });
     clock_end(h, h->clk_update);
     HIP_TRY(hipGetLastError());
     return RP_OK;
@@ -2115,44 +539,25 @@ int launch_summarize(rp_mccfr* h, const StepParams& p, void* blob_dev, bool fuse
         clock_begin(h, h->clk_traverse);
         launch_prepare(h, p);
         const size_t lds = traverse_maps_lds_bytes(h);
-#define LAUNCH_FUSED_AS(G, WK, PR, RF)                                                                                                  \
-    hipLaunchKernelGGL((k_traverse_maps_static<G, WK, PR, RF>), dim3(nblk), dim3(256), lds, h->stream, h->g, h->itab, p, bmaps, bpsum, \
-                       bcnt, nblk_max, h->maxdec, h->cell_pad)
-#define LAUNCH_FUSED(G, WK)                                    \
-    do {                                                       \
-        const bool rf = p.ref_info != nullptr;                 \
-        if (pruned && rf) LAUNCH_FUSED_AS(G, WK, true, true);  \
-        else if (pruned) LAUNCH_FUSED_AS(G, WK, true, false);  \
-        else if (rf) LAUNCH_FUSED_AS(G, WK, false, true);      \
-        else LAUNCH_FUSED_AS(G, WK, false, false);             \
-    } while (0)
-        if (h->static_skel == 1) {
-            if (p.walker == 0) LAUNCH_FUSED(KuhnSkel, 0);
-            else LAUNCH_FUSED(KuhnSkel, 1);
-        } else {
-            if (p.walker == 0) LAUNCH_FUSED(LeducSkel, 0);
-            else LAUNCH_FUSED(LeducSkel, 1);
-        }
-#undef LAUNCH_FUSED
-#undef LAUNCH_FUSED_AS
+        with_static_traversal(h->static_skel, p.walker, pruned, p.ref_info != nullptr, [&](auto gt, auto wk, auto pr, auto rf) {
+            hipLaunchKernelGGL((k_traverse_maps_static<decltype(gt), decltype(wk)::value, decltype(pr)::value, decltype(rf)::value>), dim3(nblk),
+                               dim3(256), lds, h->stream, h->g, h->itab, p, bmaps, bpsum, bcnt, nblk_max, h->maxdec, h->cell_pad);
+        });
         clock_end(h, h->clk_traverse);
     }
     clock_begin(h, h->clk_update);
     if (fused) {
     } else if (!h->dc.slotmap) {
         const size_t lds = chunk_maps_lds_bytes(h);
-#define LAUNCH_CHUNK_MAPS(PR, PS) \
-    hipLaunchKernelGGL((k_chunk_maps<PR, PS>), dim3(nblk), dim3(CH_THREADS), lds, h->stream, h->g, h->dc, p, bmaps, bpsum, bcnt, nblk_max)
-        const bool one = h->tbl.n_infos <= CH_THREADS;
-        if (pruned && one) LAUNCH_CHUNK_MAPS(true, 1);
-        else if (pruned) LAUNCH_CHUNK_MAPS(true, CM_PASSES);
-        else if (one) LAUNCH_CHUNK_MAPS(false, 1);
-        else LAUNCH_CHUNK_MAPS(false, CM_PASSES);
-#undef LAUNCH_CHUNK_MAPS
-    } else if (pruned) {
-        hipLaunchKernelGGL((k_block_maps<true>), dim3(nblk, h->tbl.n_infos), dim3(128), 0, h->stream, h->g, h->so, p, bmaps, bpsum, bcnt, nblk_max);
+        with_bools(pruned, h->tbl.n_infos <= CH_THREADS, [&](auto pr, auto one) {
+            hipLaunchKernelGGL((k_chunk_maps<decltype(pr)::value, decltype(one)::value ? 1u : CM_PASSES>), dim3(nblk), dim3(CH_THREADS), lds,
+                               h->stream, h->g, h->dc, p, bmaps, bpsum, bcnt, nblk_max);
+        });
     } else {
-        hipLaunchKernelGGL((k_block_maps<false>), dim3(nblk, h->tbl.n_infos), dim3(128), 0, h->stream, h->g, h->so, p, bmaps, bpsum, bcnt, nblk_max);
+        with_bool(pruned, [&](auto pr) {
+            hipLaunchKernelGGL((k_block_maps<decltype(pr)::value>), dim3(nblk, h->tbl.n_infos), dim3(128), 0, h->stream, h->g, h->so, p, bmaps,
+                               bpsum, bcnt, nblk_max);
+        });
     }
     {
         const uint32_t W2 = 2 * A, GPW = cb2_gpw(W2);
@@ -2310,17 +715,17 @@ int rp_mccfr_create(const rp_game_table* game, rp_regret_kind r, rp_weight_kind 
     CREATE_TRY(hipMalloc(&h->d_children, h->children.size() * 4));
     CREATE_TRY(hipMemcpy(h->d_children, h->children.data(), h->children.size() * 4, hipMemcpyHostToDevice));
     // child records: one load on arrival at a node instead of children[] -> states[] -> payoffs[]
-    std::vector<uint4> kids(h->children.size());
-    for (size_t c = 0; c < h->children.size(); ++c) {
-        const uint32_t sid = h->children[c];
+    const std::function<uint4(uint32_t)> rec_of = [&](uint32_t sid) {
         uint4 r = packed[sid];
         r.w = sid;
         if (game->states[sid].n_children == 0 && game->n_players == 2) {
             r.y = rp_f2u(h->payoffs[(size_t)game->states[sid].offset * 2 + 0]);
             r.z = rp_f2u(h->payoffs[(size_t)game->states[sid].offset * 2 + 1]);
         }
-        kids[c] = r;
-    }
+        return r;
+    };
+    std::vector<uint4> kids(h->children.size());
+    for (size_t c = 0; c < h->children.size(); ++c) kids[c] = rec_of(h->children[c]);
     CREATE_TRY(hipMalloc(&h->d_kids, std::max<size_t>(kids.size(), 1) * sizeof(uint4)));
     CREATE_TRY(hipMemcpy(h->d_kids, kids.data(), kids.size() * sizeof(uint4), hipMemcpyHostToDevice));
     CREATE_TRY(hipMalloc(&h->d_payoffs, h->payoffs.size() * 4));
@@ -2374,30 +779,23 @@ int rp_mccfr_create(const rp_game_table* game, rp_regret_kind r, rp_weight_kind 
         rp_mccfr_destroy(h);
         return rp::fail(RP_ERR_CAPACITY, "rp_mccfr_create: more than 254 walker infosets per tree");
     }
-    if (chain_lds_bytes(game->max_actions) > 64 * 1024) {
+    if (chain_lds_bytes() > 64 * 1024) {
         rp_mccfr_destroy(h);
-        return rp::fail(RP_ERR_CAPACITY, "rp_mccfr_create: chain tiles need %zu B of LDS", chain_lds_bytes(game->max_actions));
+        return rp::fail(RP_ERR_CAPACITY, "rp_mccfr_create: chain tiles need %zu B of LDS", chain_lds_bytes());
     }
     h->use_lds_traverse = traverse_fits_lds(h) && getenv("RP_MCCFR_HBM_SCRATCH") == nullptr;
     h->fuse_maps = getenv("RP_TRAV_UNFUSED") == nullptr;
     if (h->use_lds_traverse && getenv("RP_TRAV_GENERIC") == nullptr) {
-        if (skel_matches<KuhnSkel>(game, h->children)) h->static_skel = 1;
-        else if (skel_matches<LeducSkel>(game, h->children)) h->static_skel = 2;
+        for (int k = 1; k <= 2 && !h->static_skel; ++k)
+            with_skeleton(k, [&](auto gt) {
+                if (skel_matches<decltype(gt)>(game, h->children)) h->static_skel = k;
+            });
     }
     h->g.rows = nullptr;
     if (h->static_skel && getenv("RP_TRAV_NO_FLAT") == nullptr) {
-        const std::function<uint4(uint32_t)> rec_of = [&](uint32_t sid) {
-            uint4 r = packed[sid];
-            r.w = sid;
-            if (game->states[sid].n_children == 0 && game->n_players == 2) {
-                r.y = rp_f2u(h->payoffs[(size_t)game->states[sid].offset * 2 + 0]);
-                r.z = rp_f2u(h->payoffs[(size_t)game->states[sid].offset * 2 + 1]);
-            }
-            return r;
-        };
         std::vector<uint32_t> rows;
-        const bool ok = h->static_skel == 1 ? build_rows<KuhnSkel>(game, h->children, rec_of, rows, h->g.row_base, h->g.row_fan)
-                                            : build_rows<LeducSkel>(game, h->children, rec_of, rows, h->g.row_base, h->g.row_fan);
+        bool ok = false;
+        with_skeleton(h->static_skel, [&](auto gt) { ok = build_rows<decltype(gt)>(game, h->children, rec_of, rows, h->g.row_base, h->g.row_fan); });
         if (ok) {
             CREATE_TRY(hipMalloc(&h->d_rows, rows.size() * 4));
             CREATE_TRY(hipMemcpy(h->d_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
@@ -2422,9 +820,7 @@ int rp_mccfr_destroy(rp_mccfr* h) {
     if (!h) return RP_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    clock_drain(h->clk_traverse);
-    clock_drain(h->clk_compact);
-    clock_drain(h->clk_update);
+    clock_drain_all(h);
     void* ptrs[] = {h->d_info_streams, h->d_chance_streams, h->d_ref_mid, h->d_rows, h->d_states, h->d_children, h->d_kids, h->d_payoffs, h->d_info_actions, h->d_info_player, h->d_scratch,
                     h->d_dec, h->d_sorted, h->d_bmaps, h->d_itab, h->d_summary, h->d_window, h->d_counters, h->t.regret, h->t.weight, h->t.payoff,
                     h->t.visits};
@@ -2484,9 +880,7 @@ int rp_mccfr_sync(rp_mccfr* h) {
     int rc = set_device(h);
     if (rc) return rc;
     rc = check_device_errors(h);
-    clock_drain(h->clk_traverse);
-    clock_drain(h->clk_compact);
-    clock_drain(h->clk_update);
+    clock_drain_all(h);
     return rc;
 }
 
@@ -2857,9 +1251,7 @@ int rp_mccfr_profile(rp_mccfr* h, int enable) {
     if (!h) return rp::fail(RP_ERR_INVALID, "rp_mccfr_profile: NULL handle");
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    clock_drain(h->clk_traverse);
-    clock_drain(h->clk_compact);
-    clock_drain(h->clk_update);
+    clock_drain_all(h);
     h->profiling = enable != 0;
     h->clk_traverse.total_ms = h->clk_compact.total_ms = h->clk_update.total_ms = 0.0;
     h->clk_traverse.launches = h->clk_compact.launches = h->clk_update.launches = 0;
@@ -2891,9 +1283,7 @@ int rp_mccfr_kernel_time(rp_mccfr* h, const char* name, double* total_ms, uint64
     if (!h || !name) return rp::fail(RP_ERR_INVALID, "rp_mccfr_kernel_time: NULL argument");
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    clock_drain(h->clk_traverse);
-    clock_drain(h->clk_compact);
-    clock_drain(h->clk_update);
+    clock_drain_all(h);
     const KernelClock* c = nullptr;
     if (std::string(name) == "traverse") c = &h->clk_traverse;
     else if (std::string(name) == "compact") c = &h->clk_compact;

@@ -1,4 +1,5 @@
-// mccfr_kernels.hpp — device-side data layout shared by mccfr.hip's kernels and host code.
+// mccfr_kernels.hpp — device-side data layout shared by the MCCFR kernels (mccfr_traverse.hpp, mccfr_update.hpp, traverse_static.hpp,
+// sparse.hip) and mccfr.hip's host code, the per-cell map algebra of the composed update and the steps more than one kernel performs.
 #ifndef RP_MCCFR_KERNELS_HPP
 #define RP_MCCFR_KERNELS_HPP
 
@@ -127,6 +128,17 @@ struct InfoSum {
     float psum;
 };
 
+// the batch's Decisions sorted into one tree-id-ordered segment per infoset (k_count / k_scan / k_compact)
+struct DevSorted {
+    float* rw;         // [cap][2A]  per Decisions: regret delta a=0..A-1, then weight delta a=0..A-1
+    uint32_t* mask;    // [cap]      edges present in the regret vector
+    float* payoff;     // [cap]
+    uint32_t* counts;  // [n_infos][n_chunks]
+    uint32_t* offs;    // [n_infos][n_chunks]
+    uint32_t* total;   // [n_infos]  segment length
+    uint32_t n_chunks;
+};
+
 enum : uint32_t { PT_CHANCE = 0, PT_WALKER = 1, PT_OPP = 2, PT_NONE = 3 };
 enum : uint32_t { ERR_NODE_CAPACITY = 1u, ERR_STACK_CAPACITY = 2u, ERR_DEC_CAPACITY = 4u };
 
@@ -175,6 +187,19 @@ __host__ __device__ inline float regret_floor_of(int R, float regret_min) {
     return regret_min;
 }
 
+// WeightSchedule::accumulate's immediate term (policy/{linear,quadratic}.rs): sigma * t, sigma * t * t
+__device__ __forceinline__ float weight_delta(int W, float sigma, float tf) {
+    return W == RP_WEIGHT_LINEAR ? sigma * tf : (W == RP_WEIGHT_QUADRATIC ? sigma * tf * tf : sigma);
+}
+// per-cell constants of a composed chain: the sign-independent discount d and the floor of a regret or a weight cell
+struct ChainParams {
+    float d, fl;
+};
+__device__ __forceinline__ ChainParams chain_params(const StepParams& p, bool isreg, float tf) {
+    const float fl = isreg ? regret_floor_of(p.R, p.regret_min) : RP_EPSILON;
+    const float d = isreg ? (p.R == RP_REGRET_LINEAR ? tf / (tf + 1.0f) : 1.0f) : (p.W == RP_WEIGHT_EXPONENTIAL ? 0.9999f : 1.0f);
+    return ChainParams{d, fl};
+}
 
 struct Map {
     float a, b, m;
@@ -206,6 +231,55 @@ __device__ __forceinline__ void map_touch(Map& mp, float d, float delta, float f
         mp.m = rp_maxf(mp.m * d + delta, floor_v);
     }
     mp.n += 1;
+}
+// map_touch without a branch, for the chains that run in lock step: equals map_touch when `skip` is false and leaves the map
+// alone when it is true (a pruned edge is not touched at all: a touch would apply the discount)
+__device__ __forceinline__ void map_touch_unless(Map& mp, bool skip, float d, float delta, float floor_v) {
+    const float na = mp.n ? mp.a * d : d;
+    const float nb = mp.n ? mp.b * d + delta : delta;
+    const float nm = mp.n ? rp_maxf(mp.m * d + delta, floor_v) : floor_v;
+    mp.a = skip ? mp.a : na;
+    mp.b = skip ? mp.b : nb;
+    mp.m = skip ? mp.m : nm;
+    mp.n += skip ? 0u : 1u;
+}
+__device__ __forceinline__ Map map_identity() { return Map{1.0f, 0.0f, rp_u2f(0xff800000u), 0u}; }
+// F(x) = max(a x + b, m) of a map that holds at least one touch; map_apply: any map (no touch = the identity)
+__device__ __forceinline__ float map_eval(const Map& mp, float x) { return rp_maxf(mp.a * x + mp.b, mp.m); }
+__device__ __forceinline__ float map_apply(const Map& mp, float x) { return mp.n ? map_eval(mp, x) : x; }
+// a batch's (payoff sum, count) folded into a cell's (mean payoff, visits)
+__device__ __forceinline__ void fold_payoff(float& ev, uint32_t& visits, float psum, uint32_t count) {
+    if (count) {
+        const uint32_t n2 = visits + count;
+        ev = ev + (psum - (float)count * ev) / (float)n2;
+        visits = n2;
+    }
+}
+// the regret and the weight half of a Cell as maps
+__device__ __forceinline__ Map cell_regret(const Cell& c) { return Map{c.ra, c.rb, c.rm, c.rn}; }
+__device__ __forceinline__ Map cell_weight(const Cell& c) { return Map{c.wa, c.wb, c.wm, c.wn}; }
+__device__ __forceinline__ void cell_set_regret(Cell& c, const Map& mp) { c.ra = mp.a; c.rb = mp.b; c.rm = mp.m; c.rn = mp.n; }
+__device__ __forceinline__ void cell_set_weight(Cell& c, const Map& mp) { c.wa = mp.a; c.wb = mp.b; c.wm = mp.m; c.wn = mp.n; }
+
+// ------------------------------------------------------------------------------------------------
+// per-infoset, tree-ordered lists of one chunk of CH_TREES trees: an LDS bitmap [infoset][tree] marks the trees that produced
+// Decisions for the infoset; the place of a tree's Decisions in the infoset's list is a prefix popcount of that bitmap row
+// ------------------------------------------------------------------------------------------------
+#define CH_TREES 256u     // trees per compaction chunk == RP_COMPOSE_CHUNK (a block of the composed update)
+#define SM_WORDS (CH_TREES / 32u)
+static_assert(CH_TREES == RP_COMPOSE_CHUNK, "a block of the composed update is one compaction chunk of trees");
+// pre[info][w] = trees before word w that visited the infoset; returns the length of the infoset's list
+__device__ __forceinline__ uint32_t list_prefix(const uint32_t* bits, uint16_t* pre, uint32_t info) {
+    uint32_t run = 0;
+    for (uint32_t w = 0; w < SM_WORDS; ++w) {
+        pre[info * SM_WORDS + w] = (uint16_t)run;
+        run += __popc(bits[info * SM_WORDS + w]);
+    }
+    return run;
+}
+// place of local tree `lt` in the infoset's list
+__device__ __forceinline__ uint32_t list_rank(const uint32_t* bits, const uint16_t* pre, uint32_t info, uint32_t lt) {
+    return pre[info * SM_WORDS + (lt >> 5)] + __popc(bits[info * SM_WORDS + (lt >> 5)] & ((1u << (lt & 31u)) - 1u));
 }
 
 }  // namespace rp

@@ -1,0 +1,881 @@
+// mccfr_update.hpp — the update kernels of mccfr.hip (Solver::update_*, solver.rs:143-192): the stable counting sort of a batch's
+// Decisions (k_count / k_scan / k_compact, k_count_small / k_compact_small), the ordered chains (k_chain), the block maps of the
+// composed update (k_block_maps, k_chunk_maps), their two-level fold (k_combine2) and the multi-GPU exchange (k_fold, k_accumulate).
+#ifndef RP_MCCFR_UPDATE_HPP
+#define RP_MCCFR_UPDATE_HPP
+
+#include "mccfr_kernels.hpp"
+#include "mccfr_traverse.hpp"  // lane_of, DevInfoTab, prepare_one
+
+namespace rp {
+
+// ------------------------------------------------------------------------------------------------
+// Update pipeline (Solver::update_{regret,weight,payoff,visits}, solver.rs:96-105,143-192):
+//   k_count    per (infoset, 1024-tree chunk): how many trees of the chunk produced Decisions for it
+//   k_scan     per infoset: exclusive scan of the chunk counts -> offsets, segment length
+//   k_compact  scatter the Decisions into ONE tree-id-ordered segment per infoset (stable counting sort)
+//   k_chain    per infoset: stream the segment through LDS tiles and apply the touches sequentially,
+//              one lane per table cell (the reference's order-dependent semantics, bit for bit)
+// ------------------------------------------------------------------------------------------------
+// CH_TREES (trees per compaction chunk), SM_WORDS and DevSorted live in mccfr_kernels.hpp
+#define CH_THREADS 256u   // small-game kernels: one tree per thread
+#define SLOT_THREADS (CH_TREES / 4u)  // slot-map kernels: four slot-map bytes per thread
+
+__device__ __forceinline__ uint32_t chunk_slots(const DevDecisions& dc, uint32_t info, uint32_t t0, uint32_t batch) {
+    uint32_t slots = 0;
+    if (t0 + 4 <= batch) {
+        slots = *reinterpret_cast<const uint32_t*>(&dc.slotmap[(size_t)info * dc.stride + t0]);
+    } else {
+        for (uint32_t k = 0; k < 4; ++k)
+            if (t0 + k < batch) slots |= (uint32_t)dc.slotmap[(size_t)info * dc.stride + t0 + k] << (8 * k);
+    }
+    return slots;
+}
+__device__ __forceinline__ uint32_t nonzero_bytes(uint32_t v) {
+    return ((v & 0xffu) != 0) + ((v & 0xff00u) != 0) + ((v & 0xff0000u) != 0) + ((v & 0xff000000u) != 0);
+}
+// block-wide exclusive scan over the blockDim.x threads in thread order; returns (exclusive prefix, total)
+__device__ __forceinline__ uint32_t block_exscan(uint32_t v, uint32_t* wave_tot, uint32_t* total) {
+    const uint32_t tid = threadIdx.x;
+    uint32_t incl = v;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(incl, d, 64);
+        if ((int)(tid & 63) >= d) incl += o;
+    }
+    if ((tid & 63) == 63) wave_tot[tid >> 6] = incl;
+    __syncthreads();
+    uint32_t wbase = 0, tot = 0;
+    for (uint32_t w = 0; w < blockDim.x / 64; ++w) {
+        const uint32_t c = wave_tot[w];
+        if (w < (tid >> 6)) wbase += c;
+        tot += c;
+    }
+    __syncthreads();
+    *total = tot;
+    return wbase + incl - v;
+}
+
+__global__ __launch_bounds__(SLOT_THREADS) void k_count(DevGame g, DevDecisions dc, DevSorted so, StepParams p) {
+    __shared__ uint32_t wave_tot[CH_THREADS / 64];
+    const uint32_t info = blockIdx.y, chunk = blockIdx.x;
+    if (g.info_player[info] != p.walker) return;
+    const uint32_t t0 = chunk * CH_TREES + threadIdx.x * 4;
+    uint32_t cnt = nonzero_bytes(chunk_slots(dc, info, t0, p.batch));
+    for (int d = 32; d > 0; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+    if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t c = 0;
+        for (uint32_t w = 0; w < blockDim.x / 64; ++w) c += wave_tot[w];
+        so.counts[(size_t)info * so.n_chunks + chunk] = c;
+    }
+}
+
+__global__ __launch_bounds__(CH_THREADS) void k_scan(DevGame g, DevSorted so, StepParams p) {
+    __shared__ uint32_t wave_tot[CH_THREADS / 64];
+    const uint32_t info = blockIdx.x;
+    if (g.info_player[info] != p.walker) {
+        if (threadIdx.x == 0) so.total[info] = 0;
+        return;
+    }
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < so.n_chunks; base += CH_THREADS) {
+        const uint32_t c = base + threadIdx.x;
+        const uint32_t v = c < so.n_chunks ? so.counts[(size_t)info * so.n_chunks + c] : 0u;
+        uint32_t tot;
+        const uint32_t ex = block_exscan(v, wave_tot, &tot);
+        if (c < so.n_chunks) so.offs[(size_t)info * so.n_chunks + c] = carry + ex;
+        carry += tot;
+    }
+    if (threadIdx.x == 0) so.total[info] = carry;
+}
+
+__global__ __launch_bounds__(SLOT_THREADS) void k_compact(DevGame g, DevDecisions dc, DevSorted so, StepParams p) {
+    __shared__ uint32_t wave_tot[CH_THREADS / 64];
+    __shared__ uint32_t sh_base;
+    const uint32_t info = blockIdx.y, chunk = blockIdx.x;
+    if (g.info_player[info] != p.walker) return;
+    // segment base = sum of the lengths of all lower infosets
+    uint32_t part = 0;
+    for (uint32_t i = threadIdx.x; i < info; i += blockDim.x) part += so.total[i];
+    for (int d = 32; d > 0; d >>= 1) part += __shfl_xor(part, d, 64);
+    if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = part;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t b0 = so.offs[(size_t)info * so.n_chunks + chunk];
+        for (uint32_t w = 0; w < blockDim.x / 64; ++w) b0 += wave_tot[w];
+        sh_base = b0;
+    }
+    __syncthreads();
+    const uint32_t A = g.A, nact = g.info_actions[info];
+    const uint32_t t0 = chunk * CH_TREES + threadIdx.x * 4;
+    const uint32_t slots = chunk_slots(dc, info, t0, p.batch);
+    uint32_t tot;
+    uint32_t rank = block_exscan(nonzero_bytes(slots), wave_tot, &tot);
+    const float tf = (float)p.epoch;
+    for (uint32_t k = 0; k < 4; ++k) {
+        const uint32_t sl = (slots >> (8 * k)) & 0xffu;
+        if (!sl) continue;
+        const uint32_t tree = t0 + k, slot = sl - 1;
+        const size_t pos = (size_t)sh_base + rank;
+        for (uint32_t a = 0; a < A; ++a) {  // the scatter, as in k_compact_small: behind a shared call both kernels compile differently
+            float rd = 0.0f, wd = 0.0f;
+            if (a < nact) {
+                rd = dc.regret[(slot * A + a) * dc.stride + tree];
+                const float sg = dc.policy[(slot * A + a) * dc.stride + tree];
+                wd = weight_delta(p.W, sg, tf);
+            }
+            so.rw[pos * 2 * A + a] = rd;
+            so.rw[pos * 2 * A + A + a] = wd;
+        }
+        so.mask[pos] = dc.mask[slot * dc.stride + tree];
+        so.payoff[pos] = dc.payoff[slot * dc.stride + tree];
+        rank += 1;
+    }
+}
+
+// ---- games whose per-chunk bitmap fits in LDS (56 B per infoset): the same stable counting sort without the
+// per-infoset slot map in HBM --------
+// One workgroup per chunk of CH_TREES trees.  A tree's Decisions are marked in an LDS bitmap [infoset][tree]; the
+// rank of a Decisions inside its (chunk, infoset) bucket — its place in tree-id order — is a prefix popcount of that
+// bitmap row.  Every Decisions is read once; nothing is scanned per infoset.
+#define CM_PASSES 4u  // k_chunk_maps: infosets per thread; 4 * 256 infosets * 56 B is past its 64 KB LDS budget
+__device__ __forceinline__ void chunk_bitmap(const DevDecisions& dc, uint32_t n_infos, uint32_t chunk, uint32_t batch,
+                                             uint32_t* bits) {
+    for (uint32_t e = threadIdx.x; e < n_infos * SM_WORDS; e += CH_THREADS) bits[e] = 0;
+    __syncthreads();
+    for (uint32_t lt = threadIdx.x; lt < CH_TREES; lt += CH_THREADS) {
+        const uint32_t tree = chunk * CH_TREES + lt;  // coalesced over threads
+        if (tree >= batch) continue;
+        const uint32_t nd = dc.ndec[tree];
+        for (uint32_t slot = 0; slot < nd; ++slot)
+            atomicOr(&bits[dc.info[slot * dc.stride + tree] * SM_WORDS + (lt >> 5)], 1u << (lt & 31u));
+    }
+    __syncthreads();
+}
+// exclusive scan of in[0..n) into out[0..n) (both LDS), any n, by the whole workgroup
+__device__ __forceinline__ void lds_exscan(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* wave_tot) {
+    uint32_t carry = 0;
+    for (uint32_t b0 = 0; b0 < n; b0 += blockDim.x) {
+        const uint32_t i = b0 + threadIdx.x;
+        uint32_t tot;
+        const uint32_t ex = block_exscan(i < n ? in[i] : 0u, wave_tot, &tot);
+        if (i < n) out[i] = carry + ex;
+        carry += tot;
+    }
+    __syncthreads();
+}
+__global__ __launch_bounds__(CH_THREADS) void k_count_small(DevGame g, DevDecisions dc, DevSorted so, StepParams p) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t sm_lds[];
+    uint32_t* bits = sm_lds;  // [n_infos][SM_WORDS]
+    const uint32_t chunk = blockIdx.x;
+    chunk_bitmap(dc, g.n_infos, chunk, p.batch, bits);
+    for (uint32_t info = threadIdx.x; info < g.n_infos; info += CH_THREADS) {
+        uint32_t c = 0;
+        for (uint32_t w = 0; w < SM_WORDS; ++w) c += __popc(bits[info * SM_WORDS + w]);
+        so.counts[(size_t)info * so.n_chunks + chunk] = c;
+    }
+}
+__global__ __launch_bounds__(CH_THREADS) void k_compact_small(DevGame g, DevDecisions dc, DevSorted so, StepParams p) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t sm_lds[];
+    __shared__ uint32_t wave_tot[CH_THREADS / 64];
+    const uint32_t NI = g.n_infos;
+    uint32_t* bits = sm_lds;                                        // [NI][SM_WORDS]
+    uint32_t* base = bits + NI * SM_WORDS;                          // [NI] first position of the (chunk, infoset) bucket
+    uint32_t* tots = base + NI;                                     // [NI] segment lengths
+    uint16_t* pre = reinterpret_cast<uint16_t*>(tots + NI);         // [NI][SM_WORDS] trees before word w that visited the infoset
+    const uint32_t chunk = blockIdx.x;
+    chunk_bitmap(dc, g.n_infos, chunk, p.batch, bits);
+    for (uint32_t info = threadIdx.x; info < g.n_infos; info += CH_THREADS) {  // list_prefix; the row's count is not needed here
+        uint32_t run = 0;
+        for (uint32_t w = 0; w < SM_WORDS; ++w) {
+            pre[info * SM_WORDS + w] = (uint16_t)run;
+            run += __popc(bits[info * SM_WORDS + w]);
+        }
+    }
+    // bucket base = sum of the lengths of all lower infosets + this chunk's offset inside the infoset's segment
+    for (uint32_t info = threadIdx.x; info < NI; info += CH_THREADS) tots[info] = so.total[info];
+    __syncthreads();
+    lds_exscan(tots, base, NI, wave_tot);
+    for (uint32_t info = threadIdx.x; info < NI; info += CH_THREADS) base[info] += so.offs[(size_t)info * so.n_chunks + chunk];
+    __syncthreads();
+    const uint32_t A = g.A;
+    const float tf = (float)p.epoch;
+    for (uint32_t lt = threadIdx.x; lt < CH_TREES; lt += CH_THREADS) {
+        const uint32_t tree = chunk * CH_TREES + lt;
+        if (tree >= p.batch) continue;
+        const uint32_t nd = dc.ndec[tree];
+        for (uint32_t slot = 0; slot < nd; ++slot) {
+            const uint32_t info = dc.info[slot * dc.stride + tree];
+            const uint32_t nact = g.info_actions[info];
+            const size_t pos = (size_t)base[info] + list_rank(bits, pre, info, lt);
+            for (uint32_t a = 0; a < A; ++a) {  // the scatter of k_compact, kept equal to it
+                float rd = 0.0f, wd = 0.0f;
+                if (a < nact) {
+                    rd = dc.regret[(slot * A + a) * dc.stride + tree];
+                    const float sg = dc.policy[(slot * A + a) * dc.stride + tree];
+                    wd = weight_delta(p.W, sg, tf);
+                }
+                so.rw[pos * 2 * A + a] = rd;
+                so.rw[pos * 2 * A + A + a] = wd;
+            }
+            so.mask[pos] = dc.mask[slot * dc.stride + tree];
+            so.payoff[pos] = dc.payoff[slot * dc.stride + tree];
+        }
+    }
+}
+
+// per-epoch discount constants of a RegretSchedule (regret/{linear,discounted,asymmetric}.rs)
+struct Discount {
+    float pos, neg, zero;
+};
+__device__ __forceinline__ Discount regret_discount(int R, float t, float pow15, float pow05) {
+    Discount d{1.0f, 1.0f, 1.0f};
+    const float lin = t / (t + 1.0f);
+    if (R == RP_REGRET_LINEAR) d = Discount{lin, lin, lin};
+    else if (R == RP_REGRET_ASYMMETRIC) d = Discount{1.0f, lin, lin};
+    else if (R == RP_REGRET_DISCOUNTED) {
+        const float xp = pow15, xn = pow05, xz = t / 1.0f;
+        d = Discount{xp / (xp + 1.0f), xn / (xn + 1.0f), xz / (xz + 1.0f)};
+    }
+    return d;
+}
+__device__ __forceinline__ uint32_t seg_base(const DevSorted& so, uint32_t info) {
+    uint32_t part = 0;
+    for (uint32_t i = lane_of(); i < info; i += 64) part += so.total[i];
+    for (int d = 32; d > 0; d >>= 1) part += __shfl_xor(part, d, 64);
+    return part;
+}
+
+#define TILE_FLOATS 1024u  // regret/weight deltas per LDS tile (16 per lane)
+#define TILE_REGS (TILE_FLOATS / 64u)
+#define TILE_PAD 4u        // row padding of the stream-major tile (keeps 16-B alignment, staggers banks)
+#define PTILE 1024u        // payoffs per LDS tile
+
+// LDS carve of k_chain (bytes): regret/weight tiles, mask tiles, payoff / reciprocal / divisor tiles
+#define CHAIN_TILE_WORDS (TILE_FLOATS + 2u * RP_MAX_ACTIONS * TILE_PAD)
+#define CHAIN_LDS_WORDS (2u * CHAIN_TILE_WORDS + 2u * (TILE_FLOATS / 2u) + 7u * PTILE)
+
+// wave 0: regret + weight cells, universal op acc <- max(acc * d + delta, floor) (x * 1.0f is exact, so Summed /
+// Floored / Constant / Linear-weight schedules are the same instruction stream with d = 1).  wave 1: payoff + visits.
+// Tiles are double buffered: the global loads of tile t+1 are issued into registers BEFORE the chain over tile t
+// and committed to LDS after it, so HBM/L2 latency hides under the serial chain.  In LDS a tile is stream-major
+// ([cell][entry]) so each chain lane reads its own stream 4 entries at a time (ds_read_b128), 16 entries ahead.
+template <bool SIGNED, bool PRUNED>
+__global__ __launch_bounds__(128) void k_chain(DevGame g, DevTables t, DevSorted so, StepParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const uint32_t info = blockIdx.x;
+    if (g.info_player[info] != p.walker) return;
+    const uint32_t len = so.total[info];
+    if (len == 0) return;
+    const uint32_t A = g.A, nact = g.info_actions[info], W2 = 2 * A;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const size_t base = seg_base(so, info);
+    const float tf = (float)p.epoch;
+    float* tile = reinterpret_cast<float*>(smem);                                  // [2][CHAIN_TILE_WORDS]
+    uint32_t* mtile = reinterpret_cast<uint32_t*>(tile + 2 * CHAIN_TILE_WORDS);    // [2][TILE_FLOATS / 2]
+    float* ptile = reinterpret_cast<float*>(mtile + TILE_FLOATS);                  // [2][3][PTILE]: payoff, 1/b, b
+    if (wave == 0) {
+        const uint32_t T = (TILE_FLOATS / W2) & ~3u;  // Decisions per tile, multiple of 4
+        const uint32_t TP = T + TILE_PAD;             // row stride of the stream-major tile
+        const bool isreg = lane < A;
+        const uint32_t a = lane % A;
+        const bool chain = lane < W2 && a < nact;
+        const size_t cell = (size_t)info * A + a;
+        float acc = 0.0f, fl = RP_EPSILON;
+        Discount d{1.0f, 1.0f, 1.0f};
+        if (chain) {
+            if (isreg) {
+                acc = t.regret[cell];
+                fl = regret_floor_of(p.R, p.regret_min);
+                d = regret_discount(p.R, tf, p.pow15, p.pow05);
+            } else {
+                acc = t.weight[cell];
+                const float dw = p.W == RP_WEIGHT_EXPONENTIAL ? 0.9999f : 1.0f;
+                d = Discount{dw, dw, dw};
+            }
+        }
+        const uint32_t ntiles = (len + T - 1) / T;
+        float rg[TILE_REGS];
+        uint32_t mk[TILE_REGS / 2];
+        auto issue = [&](uint32_t tl) {
+            const size_t e0 = (base + (size_t)tl * T) * W2;
+            const uint32_t ne = min(T, len - tl * T), nfl = ne * W2;
+#pragma unroll
+            for (uint32_t r = 0; r < TILE_REGS; ++r) {
+                const uint32_t k = lane + 64 * r;
+                rg[r] = k < nfl ? so.rw[e0 + k] : 0.0f;
+            }
+            if (PRUNED) {
+#pragma unroll
+                for (uint32_t r = 0; r < TILE_REGS / 2; ++r) {
+                    const uint32_t k = lane + 64 * r;
+                    mk[r] = k < ne ? so.mask[base + (size_t)tl * T + k] : 0u;
+                }
+            }
+        };
+        auto commit = [&](uint32_t buf) {  // entry-major registers -> stream-major LDS
+#pragma unroll
+            for (uint32_t r = 0; r < TILE_REGS; ++r) {
+                const uint32_t k = lane + 64 * r;
+                if (k < T * W2) tile[buf * CHAIN_TILE_WORDS + (k % W2) * TP + k / W2] = rg[r];
+            }
+            if (PRUNED) {
+#pragma unroll
+                for (uint32_t r = 0; r < TILE_REGS / 2; ++r) mtile[buf * (TILE_FLOATS / 2) + lane + 64 * r] = mk[r];
+            }
+        };
+        auto step = [&](float delta, uint32_t m) {
+            float dd = d.zero;
+            if (SIGNED) dd = acc > 0.0f ? d.pos : (acc < 0.0f ? d.neg : d.zero);
+            const float nv = rp_maxf(acc * dd + delta, fl);
+            if (PRUNED) acc = (isreg && !((m >> a) & 1u)) ? acc : nv;
+            else acc = nv;
+        };
+        issue(0);
+        commit(0);
+        __builtin_amdgcn_wave_barrier();
+        for (uint32_t tl = 0; tl < ntiles; ++tl) {
+            const uint32_t buf = tl & 1u;
+            const bool more = tl + 1 < ntiles;
+            if (more) issue(tl + 1);
+            const uint32_t n = min(T, len - tl * T);
+            const float* row = tile + buf * CHAIN_TILE_WORDS + (chain ? lane : 0u) * TP;
+            const uint32_t* mrow = mtile + buf * (TILE_FLOATS / 2);
+            if (chain) {
+                const uint32_t n16 = n & ~15u;
+                uint32_t i = 0;
+                if (n16) {
+                    float4 c0 = *reinterpret_cast<const float4*>(row + 0), c1 = *reinterpret_cast<const float4*>(row + 4);
+                    float4 c2 = *reinterpret_cast<const float4*>(row + 8), c3 = *reinterpret_cast<const float4*>(row + 12);
+                    for (; i < n16; i += 16) {
+                        float4 x0 = c0, x1 = c1, x2 = c2, x3 = c3;
+                        if (i + 16 < n16) {  // the next 16 entries travel from LDS while these 16 are chained
+                            c0 = *reinterpret_cast<const float4*>(row + i + 16);
+                            c1 = *reinterpret_cast<const float4*>(row + i + 20);
+                            c2 = *reinterpret_cast<const float4*>(row + i + 24);
+                            c3 = *reinterpret_cast<const float4*>(row + i + 28);
+                        }
+                        uint32_t m[16];
+#pragma unroll
+                        for (uint32_t q = 0; q < 16; ++q) m[q] = PRUNED ? mrow[i + q] : 0xffffffffu;
+                        step(x0.x, m[0]); step(x0.y, m[1]); step(x0.z, m[2]); step(x0.w, m[3]);
+                        step(x1.x, m[4]); step(x1.y, m[5]); step(x1.z, m[6]); step(x1.w, m[7]);
+                        step(x2.x, m[8]); step(x2.y, m[9]); step(x2.z, m[10]); step(x2.w, m[11]);
+                        step(x3.x, m[12]); step(x3.y, m[13]); step(x3.z, m[14]); step(x3.w, m[15]);
+                    }
+                }
+                for (; i < n; ++i) step(row[i], PRUNED ? mrow[i] : 0xffffffffu);
+            }
+            if (more) commit(buf ^ 1u);
+            __builtin_amdgcn_wave_barrier();
+        }
+        if (chain) {
+            if (isreg) t.regret[cell] = acc;
+            else t.weight[cell] = acc;
+        }
+    } else {
+        // Welford mean with the pre-increment visit count (solver.rs:174-192): ev += (payoff - ev) / (n + 1).
+        // The divisor sequence is known in advance, so the whole wave precomputes b = (float)(n+1) and the
+        // correctly rounded 1/b per entry; the serial chain then needs mul + 2 fma per division
+        // (rp_div_by_recip1) and each quotient carries an exact off-path proof that it equals IEEE a / b.
+        const bool chain = lane < nact;
+        const size_t cell = (size_t)info * A + lane;
+        float ev = 0.0f;
+        uint32_t visits = 0;
+        if (chain) {
+            ev = t.payoff[cell];
+            visits = t.visits[cell];
+        }
+        const uint32_t v0 = __shfl(visits, 0, 64);
+        const float ev0 = __shfl(ev, 0, 64);
+        // every edge of an infoset is always visited together, so all its (payoff, visits) cells hold the same
+        // value and ONE chain serves them; anything else (a hand-made import) takes the plain path below
+        const bool uniform = __all(!chain || (visits == v0 && rp_f2u(ev) == rp_f2u(ev0)));
+        float* hist = ptile + 6 * PTILE;  // [PTILE] ev after each touch of the current tile
+        if (uniform) ev = ev0;
+        const float ev_start = ev;
+        if (uniform) {
+            const uint32_t ntiles = (len + PTILE - 1) / PTILE;
+            float rg[PTILE / 64];
+            auto issue = [&](uint32_t tl) {
+                const uint32_t n = min(PTILE, len - tl * PTILE);
+#pragma unroll
+                for (uint32_t r = 0; r < PTILE / 64; ++r) {
+                    const uint32_t k = lane + 64 * r;
+                    rg[r] = k < n ? so.payoff[base + (size_t)tl * PTILE + k] : 0.0f;
+                }
+            };
+            auto commit = [&](uint32_t tl, uint32_t buf) {
+                float* pt = ptile + buf * 3 * PTILE;
+#pragma unroll
+                for (uint32_t r = 0; r < PTILE / 64; ++r) {
+                    const uint32_t k = lane + 64 * r;
+                    const float b = (float)(v0 + tl * PTILE + k + 1u);  // (n + 1) as f32 (solver.rs:179)
+                    pt[k] = rg[r];
+                    pt[PTILE + k] = 1.0f / b;
+                    pt[2 * PTILE + k] = b;
+                }
+            };
+            issue(0);
+            commit(0, 0);
+            __builtin_amdgcn_wave_barrier();
+            for (uint32_t tl = 0; tl < ntiles; ++tl) {
+                const uint32_t buf = tl & 1u;
+                const bool more = tl + 1 < ntiles;
+                if (more) issue(tl + 1);
+                const uint32_t n = min(PTILE, len - tl * PTILE);
+                const float* pt = ptile + buf * 3 * PTILE;
+#ifndef RP_EXPERIMENT_SKIP_PAYOFF
+                // (1) the serial chain: 5 VALU ops per touch (sub, mul, fma, fma, add); lane 0 logs ev after each touch
+                const float ev_tile = ev;
+                {
+                    auto fast = [&](float pv, float rv, float bv) {
+                        const float s = pv - ev;
+                        const float q0 = s * rv;
+                        const float e0 = fmaf(-bv, q0, s);
+                        ev += fmaf(e0, rv, q0);
+                        return ev;
+                    };
+                    const uint32_t n4 = n & ~3u;
+                    uint32_t i = 0;
+                    for (; i < n4; i += 4) {
+                        const float4 pv = *reinterpret_cast<const float4*>(pt + i);
+                        const float4 rv = *reinterpret_cast<const float4*>(pt + PTILE + i);
+                        const float4 bv = *reinterpret_cast<const float4*>(pt + 2 * PTILE + i);
+                        float4 h;
+                        h.x = fast(pv.x, rv.x, bv.x); h.y = fast(pv.y, rv.y, bv.y);
+                        h.z = fast(pv.z, rv.z, bv.z); h.w = fast(pv.w, rv.w, bv.w);
+                        if (lane == 0) *reinterpret_cast<float4*>(hist + i) = h;
+                    }
+                    for (; i < n; ++i) {
+                        const float e = fast(pt[i], pt[PTILE + i], pt[2 * PTILE + i]);
+                        if (lane == 0) hist[i] = e;
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();
+                // (2) the proof, lane-parallel and off the chain: every touch's quotient is re-derived from the logged
+                //     ev and checked with the exact-residual criterion of rp_div_by_recip1 (== IEEE s / b when proven)
+                bool bad = false;
+                for (uint32_t k = lane; k < n; k += 64) {
+                    const float prev = k ? hist[k - 1] : ev_tile;
+                    int proven;
+                    const float q = rp_div_by_recip1(pt[k] - prev, pt[2 * PTILE + k], pt[PTILE + k], &proven);
+                    bad |= !proven || (prev + q != hist[k]);
+                }
+                if (__any(bad)) {  // essentially never: redo this tile with IEEE divisions
+                    ev = ev_tile;
+                    for (uint32_t k = 0; k < n; ++k) ev += (pt[k] - ev) / pt[2 * PTILE + k];
+                }
+                __builtin_amdgcn_wave_barrier();
+#endif
+                if (more) commit(tl + 1, buf ^ 1u);
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+        if (chain) {
+            if (!uniform) {  // edges of one infoset with different visit counts (only after a hand-made import)
+                ev = ev_start;
+                uint32_t v = visits;
+                for (uint32_t i = 0; i < len; ++i) {
+                    ev += (so.payoff[base + i] - ev) / (float)(v + 1u);
+                    v += 1u;
+                }
+            }
+            t.payoff[cell] = ev;
+            t.visits[cell] = visits + len;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Composed update (include/rp_mi355x.h rp_compose_block; oracle: ora_mccfr_step_local): the serial chain of the
+// ordered mode is replaced by a two-level composition of per-cell maps F(x) = max(a x + b, m).
+//   k_block_maps  one workgroup per (infoset, block of T consecutive Decisions): sequential composition inside the
+//                 block, all blocks of all infosets in parallel
+//   k_combine2    (infoset, part) workgroups: block maps -> group maps -> Cell / InfoSum blob, or straight into the tables
+// ------------------------------------------------------------------------------------------------
+// Map / map_compose live in mccfr_kernels.hpp
+// block = the Decisions of infoset blockIdx.y produced by chunk blockIdx.x (RP_COMPOSE_CHUNK == CH_TREES trees):
+// in the sorted layout a contiguous group.  Large games (per-infoset slot map); small games fuse the sort away, below.
+template <bool PRUNED>
+__global__ __launch_bounds__(128) void k_block_maps(DevGame g, DevSorted so, StepParams p, Map* bmaps, float* bpsum,
+                                                    uint32_t* bcnt, uint32_t nblk_max) {
+    __shared__ __attribute__((aligned(16))) float tile[TILE_FLOATS + 2 * RP_MAX_ACTIONS * TILE_PAD];
+    __shared__ uint32_t mtile[TILE_FLOATS / 2];
+    __shared__ __attribute__((aligned(16))) float ptile[TILE_FLOATS / 2];
+    const uint32_t info = blockIdx.y, blk = blockIdx.x;
+    if (g.info_player[info] != p.walker) return;
+    const uint32_t A = g.A, nact = g.info_actions[info], W2 = 2 * A;
+    const uint32_t T = compose_block(A);  // touches per LDS tile
+    const uint32_t n = so.counts[(size_t)info * so.n_chunks + blk];
+    const uint32_t TP = T + TILE_PAD;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const size_t base = seg_base(so, info) + so.offs[(size_t)info * so.n_chunks + blk];
+    const bool isreg = lane < A;
+    const uint32_t a = lane % A;
+    const bool chain = lane < W2 && a < nact;
+    const float tf = (float)p.epoch;
+    const ChainParams cp = chain_params(p, isreg, tf);
+    const float fl = cp.fl, d = cp.d;
+    Map mp{1.0f, 0.0f, rp_u2f(0xff800000u), 0u};
+    float psum = 0.0f;
+    for (uint32_t t0 = 0; t0 < n; t0 += T) {  // the chain runs through the block tile by tile
+        const uint32_t m = min(T, n - t0);
+        if (wave == 0) {
+            const size_t e0 = (base + t0) * W2;
+            const uint32_t nfl = m * W2;
+            float lr[TILE_FLOATS / 64];
+#pragma unroll
+            for (uint32_t q = 0; q < TILE_FLOATS / 64; ++q) {
+                const uint32_t k = lane + 64 * q;
+                lr[q] = k < nfl ? so.rw[e0 + k] : 0.0f;
+            }
+#pragma unroll
+            for (uint32_t q = 0; q < TILE_FLOATS / 64; ++q) {
+                const uint32_t k = lane + 64 * q;
+                if (k < nfl) tile[(k % W2) * TP + k / W2] = lr[q];
+            }
+            if (PRUNED)
+                for (uint32_t k = lane; k < m; k += 64) mtile[k] = so.mask[base + t0 + k];
+        } else {
+            for (uint32_t k = lane; k < m; k += 64) ptile[k] = so.payoff[base + t0 + k];
+        }
+        __syncthreads();
+        if (wave == 0 && chain) {
+            const float* row = tile + lane * TP;
+            for (uint32_t i = 0; i < m; ++i) {
+                const float delta = row[i];
+                const bool skip = PRUNED && isreg && !((mtile[i] >> a) & 1u);
+                // map_touch_unless(mp, skip, d, delta, fl), spelled out: behind a call the compiler schedules this loop differently
+                const float na = mp.n ? mp.a * d : d;
+                const float nb = mp.n ? mp.b * d + delta : delta;
+                const float nm = mp.n ? rp_maxf(mp.m * d + delta, fl) : fl;
+                mp.a = skip ? mp.a : na;
+                mp.b = skip ? mp.b : nb;
+                mp.m = skip ? mp.m : nm;
+                mp.n += skip ? 0u : 1u;
+            }
+        }
+        if (wave == 1 && lane == 0)
+            for (uint32_t i = 0; i < m; ++i) psum += ptile[i];
+        __syncthreads();
+    }
+    const size_t slot = (size_t)info * nblk_max + blk;
+    if (wave == 0 && lane < W2) bmaps[slot * W2 + lane] = Map{mp.a, mp.b, mp.m, chain ? mp.n : 0u};
+    if (wave == 1 && lane == 0) {
+        bpsum[slot] = psum;
+        bcnt[slot] = n;
+    }
+}
+
+// Small games: block maps straight from the lane-interleaved Decisions of one chunk — no sorted copy in HBM at all.
+// One thread per tree.  The chunk's Decisions get their place in per-infoset, tree-ordered lists (LDS bitmap + prefix
+// popcount, as k_compact_small); then, cell by cell, every thread drops its trees' values at those places in an LDS
+// array (global reads coalesced over trees) and one thread per infoset composes its list sequentially out of LDS.
+template <bool PRUNED, uint32_t PASSES>
+__global__ __launch_bounds__(CH_THREADS) void k_chunk_maps(DevGame g, DevDecisions dc, StepParams p, Map* bmaps, float* bpsum,
+                                                           uint32_t* bcnt, uint32_t nblk_max) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t cm_lds[];
+    __shared__ uint32_t wave_tot[CH_THREADS / 64];
+    const uint32_t NI = g.n_infos, A = g.A, W2 = 2 * A, chunk = blockIdx.x, tid = threadIdx.x, MD = dc.maxdec;
+    uint32_t* bits = cm_lds;                                              // [NI][SM_WORDS]
+    uint32_t* lcount = bits + NI * SM_WORDS;                              // [NI]
+    uint32_t* lbase = lcount + NI;                                        // [NI]
+    float* vals = reinterpret_cast<float*>(lbase + NI);                   // [MD * CH_TREES] one cell's values, list order
+    uint16_t* pre = reinterpret_cast<uint16_t*>(vals + MD * CH_TREES);    // [NI][SM_WORDS]
+    uint16_t* posl = pre + NI * SM_WORDS;                                 // [MD][CH_TREES] list position of (slot, tree)
+    uint16_t* lmask = posl + MD * CH_TREES;                               // [MD * CH_TREES] expanded-edge masks (PRUNED)
+    chunk_bitmap(dc, NI, chunk, p.batch, bits);
+    for (uint32_t info = tid; info < NI; info += CH_THREADS) lcount[info] = list_prefix(bits, pre, info);
+    __syncthreads();
+    lds_exscan(lcount, lbase, NI, wave_tot);
+    const uint32_t lt = tid, tree = chunk * CH_TREES + lt;  // CH_TREES == CH_THREADS: one tree per thread
+    const uint32_t nd = tree < p.batch ? dc.ndec[tree] : 0u;
+    for (uint32_t slot = 0; slot < nd; ++slot) {
+        const uint32_t info = dc.info[slot * dc.stride + tree];
+        const uint32_t pos = lbase[info] + list_rank(bits, pre, info, lt);
+        posl[slot * CH_TREES + lt] = (uint16_t)pos;
+        if (PRUNED) lmask[pos] = (uint16_t)dc.mask[slot * dc.stride + tree];
+    }
+    const float tf = (float)p.epoch;
+    // chain phase: thread t owns infosets t, t + 256, ... (PASSES = 1 when the game has at most 256 infosets)
+    uint32_t my_nact[PASSES], my_n[PASSES], my_base[PASSES];
+#pragma unroll
+    for (uint32_t q = 0; q < PASSES; ++q) {
+        const uint32_t info = tid + q * CH_THREADS;
+        const bool mine = info < NI && g.info_player[info < NI ? info : 0u] == p.walker;
+        my_nact[q] = mine ? g.info_actions[info] : 0u;  // 0: not this walker's infoset
+        my_n[q] = mine ? lcount[info] : 0u;
+        my_base[q] = mine ? lbase[info] : 0u;
+    }
+    for (uint32_t c = 0; c <= W2; ++c) {  // regret cells, weight cells, then the payoff sum
+        const bool isreg = c < A, ispay = c == W2;
+        const uint32_t a = c % A;
+        __syncthreads();  // the previous cell's chains are done with `vals`
+        for (uint32_t slot = 0; slot < nd; ++slot) {
+            float v;
+            if (ispay) v = dc.payoff[slot * dc.stride + tree];
+            else if (isreg) v = dc.regret[(slot * A + a) * dc.stride + tree];
+            else v = weight_delta(p.W, dc.policy[(slot * A + a) * dc.stride + tree], tf);
+            vals[posl[slot * CH_TREES + lt]] = v;
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t q = 0; q < PASSES; ++q) {
+            const uint32_t info = tid + q * CH_THREADS;
+            if (!my_nact[q]) continue;
+            const uint32_t n = my_n[q], base = my_base[q];
+            const size_t slot_out = (size_t)info * nblk_max + chunk;
+            if (ispay) {  // payoff sum of the block, left fold from 0.0f
+                float sum = 0.0f;
+                for (uint32_t e = 0; e < n; ++e) sum += vals[base + e];
+                bpsum[slot_out] = sum;
+                bcnt[slot_out] = n;
+                continue;
+            }
+            const bool chain = a < my_nact[q];
+            const ChainParams cp = chain_params(p, isreg, tf);
+            Map mp = map_identity();
+            if (chain)
+                for (uint32_t e = 0; e < n; ++e)
+                    map_touch_unless(mp, PRUNED && isreg && !((lmask[base + e] >> a) & 1u), cp.d, vals[base + e], cp.fl);
+            bmaps[slot_out * W2 + c] = mp;
+        }
+    }
+}
+
+// The two-level fold of the block maps (include/rp_mi355x.h RP_FOLD_GROUP: the block maps of a cell composed sequentially
+// inside groups of RP_FOLD_GROUP consecutive blocks, the group maps then in group order), spread over (infoset, part)
+// workgroups, and — APPLY — the rest of the step with it.
+//   stage 1  a part owns CB2_GPW(2A) consecutive groups: its block maps are one contiguous run of HBM, copied to LDS by all
+//            256 threads at once (one round trip instead of a chain of eight per thread), then thread (group, cell) composes
+//            its RP_FOLD_GROUP maps out of LDS in block order; the group maps go to HBM with agent-scope stores;
+//   stage 2  the LAST part of an infoset to finish (arrival counter; which one is timing, what it computes is not) folds the
+//            infoset's group maps in group order into the summary cell maps, payoff sum and count;
+//   APPLY    single-GPU step: that workgroup also applies the summary to the infoset's table row (k_fold with world = 1)
+//            and refreshes the row of the per-infoset tables the next traversal reads (k_prepare_infos): one launch
+//            instead of three.  Otherwise it writes the summary blob (rp_mccfr_step_local).
+// Cross-workgroup data is a few KB per infoset: agent-scope (sc1) stores + s_waitcnt before the arrival, agent-scope
+// loads after it.  (A release FENCE at agent scope writes back a whole XCD's L2: tried on the block maps, 4x slower.)
+// This hand-over is written against the gfx942 / gfx950 memory system, not against the portable memory model: relaxed agent-scope
+// stores are sc1 write-through stores that `s_waitcnt vmcnt(0)` waits for (no separate store counter), relaxed agent-scope loads
+// bypass the XCD's non-coherent lines.  On any other target the arrival counter would need release / acquire semantics:
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__)
+#error "k_combine2's cross-workgroup hand-over relies on gfx942/gfx950 store counting and sc1 semantics: use an acq_rel arrival counter on other targets"
+#endif
+__device__ __forceinline__ uint32_t ld_agent(const uint32_t* q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_agent(uint32_t* q, uint32_t v) { __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ Map ld_map(const Map* m) {
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(m);
+    return Map{rp_u2f(ld_agent(w)), rp_u2f(ld_agent(w + 1)), rp_u2f(ld_agent(w + 2)), ld_agent(w + 3)};
+}
+__device__ __forceinline__ void st_map(Map* m, const Map& v) {
+    uint32_t* w = reinterpret_cast<uint32_t*>(m);
+    st_agent(w, rp_f2u(v.a));
+    st_agent(w + 1, rp_f2u(v.b));
+    st_agent(w + 2, rp_f2u(v.m));
+    st_agent(w + 3, v.n);
+}
+__host__ __device__ inline uint32_t cb2_gpw(uint32_t W2) { return 32u / W2 ? 32u / W2 : 1u; }  // groups per part: a 32 KB tile
+struct FoldScratch {
+    Map* gmaps;      // [n_infos][ngrp_max][2A]
+    float* gpsum;    // [n_infos][ngrp_max]
+    uint32_t* gcnt;  // [n_infos][ngrp_max]
+    uint32_t* done;  // [n_infos] parts finished
+    uint32_t ngrp_max;
+};
+template <bool APPLY>
+__global__ __launch_bounds__(256) void k_combine2(DevGame g, DevTables t, DevInfoTab it, StepParams p, const Map* bmaps, const float* bpsum,
+                                                  const uint32_t* bcnt, uint32_t nblk_max, FoldScratch fs, Cell* cells, InfoSum* sums) {
+    extern __shared__ __attribute__((aligned(16))) uint4 cb_lds[];
+    __shared__ uint32_t role, sh_len;
+    __shared__ float sh_ps;
+    const uint32_t info = blockIdx.x, part = blockIdx.y, tid = threadIdx.x;
+    const uint32_t A = g.A, W2 = 2 * A, GPW = cb2_gpw(W2);
+    const Map ident = map_identity();
+    if (g.info_player[info] != p.walker) {  // not this walker's infoset: nothing happened to it
+        if (!APPLY && part == 0) {
+            if (tid < W2) {
+                Cell& cl = cells[(size_t)info * A + tid % A];
+                if (tid < A) cell_set_regret(cl, ident);
+                else cell_set_weight(cl, ident);
+            } else if (tid == W2) {
+                sums[info] = InfoSum{0u, 0.0f};
+            }
+        }
+        return;
+    }
+    const uint32_t nb = (p.batch + RP_COMPOSE_CHUNK - 1) / RP_COMPOSE_CHUNK;  // one block per chunk of trees
+    const uint32_t ngrp = (nb + RP_FOLD_GROUP - 1) / RP_FOLD_GROUP, nparts = (ngrp + GPW - 1) / GPW;
+    if (part >= nparts) return;
+    const uint32_t g0 = part * GPW, b_lo = g0 * RP_FOLD_GROUP, b_hi = min(nb, (g0 + GPW) * RP_FOLD_GROUP), count = b_hi - b_lo;
+    uint4* tile = cb_lds;                                                                // [GPW * 64][W2] block maps
+    float* ps_t = reinterpret_cast<float*>(tile + (size_t)GPW * RP_FOLD_GROUP * W2);     // [GPW * 64]
+    uint32_t* cn_t = reinterpret_cast<uint32_t*>(ps_t + GPW * RP_FOLD_GROUP);            // [GPW * 64]
+    {
+        const uint4* src = reinterpret_cast<const uint4*>(bmaps + ((size_t)info * nblk_max + b_lo) * W2);
+        for (uint32_t e = tid; e < count * W2; e += 256u) tile[e] = src[e];
+        for (uint32_t e = tid; e < count; e += 256u) {
+            ps_t[e] = bpsum[(size_t)info * nblk_max + b_lo + e];
+            cn_t[e] = bcnt[(size_t)info * nblk_max + b_lo + e];
+        }
+    }
+    __syncthreads();
+    if (tid < GPW * W2) {
+        const uint32_t s = tid / W2, c = tid % W2, grp = g0 + s;
+        if (grp < ngrp) {
+            const uint32_t lo = s * RP_FOLD_GROUP, hi = min(count, lo + RP_FOLD_GROUP);
+            Map m = ident;
+            for (uint32_t b0 = lo; b0 < hi; b0 += 8u) {  // eight LDS reads in flight ahead of the dependent chain
+                uint4 v[8];
+#pragma unroll
+                for (uint32_t q = 0; q < 8u; ++q) v[q] = tile[min(b0 + q, hi - 1u) * W2 + c];
+#pragma unroll
+                for (uint32_t q = 0; q < 8u; ++q)
+                    if (b0 + q < hi) m = map_compose(m, Map{rp_u2f(v[q].x), rp_u2f(v[q].y), rp_u2f(v[q].z), v[q].w});
+            }
+            st_map(&fs.gmaps[((size_t)info * fs.ngrp_max + grp) * W2 + c], m);
+        }
+    } else if (tid < GPW * W2 + GPW) {
+        const uint32_t s = tid - GPW * W2, grp = g0 + s;
+        if (grp < ngrp) {
+            const uint32_t lo = s * RP_FOLD_GROUP, hi = min(count, lo + RP_FOLD_GROUP);
+            float gp = 0.0f;
+            uint32_t gc = 0;
+            for (uint32_t b = lo; b < hi; ++b) {
+                gp += ps_t[b];
+                gc += cn_t[b];
+            }
+            st_agent(reinterpret_cast<uint32_t*>(fs.gpsum) + (size_t)info * fs.ngrp_max + grp, rp_f2u(gp));
+            st_agent(fs.gcnt + (size_t)info * fs.ngrp_max + grp, gc);
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the group maps are in memory before this part counts itself in
+    __syncthreads();
+    if (tid == 0) role = atomicAdd(&fs.done[info], 1u) == nparts - 1u ? 1u : 0u;
+    __syncthreads();
+    if (!role) return;
+    if (tid == 0) fs.done[info] = 0;  // for the next launch
+    // the infoset's group maps: into LDS by all threads at once (one round trip), then folded in group order
+    Map tot = ident;
+    float ps = 0.0f;
+    uint32_t len = 0;
+    const uint32_t TILE_G = GPW * RP_FOLD_GROUP;
+    const uint32_t* gm = reinterpret_cast<const uint32_t*>(fs.gmaps + (size_t)info * fs.ngrp_max * W2);
+    for (uint32_t k0 = 0; k0 < ngrp; k0 += TILE_G) {
+        const uint32_t n = min(TILE_G, ngrp - k0);
+        __syncthreads();
+        for (uint32_t e = tid; e < n * W2; e += 256u) {
+            const uint32_t* w = gm + ((size_t)k0 * W2 + e) * 4u;
+            tile[e] = make_uint4(ld_agent(w), ld_agent(w + 1), ld_agent(w + 2), ld_agent(w + 3));
+        }
+        for (uint32_t e = tid; e < n; e += 256u) {
+            ps_t[e] = rp_u2f(ld_agent(reinterpret_cast<const uint32_t*>(fs.gpsum) + (size_t)info * fs.ngrp_max + k0 + e));
+            cn_t[e] = ld_agent(fs.gcnt + (size_t)info * fs.ngrp_max + k0 + e);
+        }
+        __syncthreads();
+        if (tid < W2) {
+            for (uint32_t k0b = 0; k0b < n; k0b += 8u) {
+                uint4 v[8];
+#pragma unroll
+                for (uint32_t q = 0; q < 8u; ++q) v[q] = tile[min(k0b + q, n - 1u) * W2 + tid];
+#pragma unroll
+                for (uint32_t q = 0; q < 8u; ++q)
+                    if (k0b + q < n) tot = map_compose(tot, Map{rp_u2f(v[q].x), rp_u2f(v[q].y), rp_u2f(v[q].z), v[q].w});
+            }
+        } else if (tid == W2) {
+            for (uint32_t k = 0; k < n; ++k) {
+                ps += ps_t[k];
+                len += cn_t[k];
+            }
+        }
+    }
+    if (tid == W2) {
+        sh_ps = ps;
+        sh_len = len;
+    }
+    if (!APPLY) {
+        if (tid < W2) {
+            Cell& cl = cells[(size_t)info * A + tid % A];
+            if (tid < A) cell_set_regret(cl, tot);
+            else cell_set_weight(cl, tot);
+        }
+        __syncthreads();
+        if (tid == 0) sums[info] = InfoSum{sh_len, sh_ps};
+        return;
+    }
+    // k_fold, world = 1, for this infoset's row
+    __syncthreads();
+    const uint32_t nact = g.info_actions[info];
+    if (tid < W2 && tid % A < nact) {
+        const uint32_t cell = info * A + tid % A;
+        if (tid < A) {
+            t.regret[cell] = map_apply(tot, t.regret[cell]);
+            float ev = t.payoff[cell];
+            uint32_t visits = t.visits[cell];
+            fold_payoff(ev, visits, sh_ps, sh_len);
+            t.payoff[cell] = ev;
+            t.visits[cell] = visits;
+        } else {
+            t.weight[cell] = map_apply(tot, t.weight[cell]);
+        }
+    }
+    __syncthreads();  // workgroup scope: the row just written is what prepare_one reads
+    if (tid == 0) prepare_one(g, t, p, it, info);
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_fold: the receiving side of the multi-GPU exchange (oracle: ora_mccfr_step_apply)
+// ------------------------------------------------------------------------------------------------
+// one thread per table cell; `blob` holds `world` summaries back to back: [cells][sums]
+__global__ void k_fold(DevGame g, DevTables t, const unsigned char* blob, size_t blob_stride, uint32_t world) {
+    const uint32_t cell = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t ncell = g.n_infos * g.A;
+    if (cell >= ncell) return;
+    const uint32_t info = cell / g.A, a = cell % g.A;
+    if (a >= g.info_actions[info]) return;
+    float r = t.regret[cell], w = t.weight[cell], ev = t.payoff[cell];
+    uint32_t visits = t.visits[cell];
+    for (uint32_t rk = 0; rk < world; ++rk) {
+        const unsigned char* b = blob + (size_t)rk * blob_stride;
+        const Cell c = reinterpret_cast<const Cell*>(b)[cell];
+        const InfoSum s = reinterpret_cast<const InfoSum*>(b + (size_t)ncell * sizeof(Cell))[info];
+        if (c.rn) r = map_eval(cell_regret(c), r);  // map_apply, its test here: the Cell's fields are then loaded only when used
+        if (c.wn) w = map_eval(cell_weight(c), w);
+        fold_payoff(ev, visits, s.psum, s.count);
+    }
+    t.regret[cell] = r;
+    t.weight[cell] = w;
+    t.payoff[cell] = ev;
+    t.visits[cell] = visits;
+}
+
+// the exchange window (rp_mccfr_window_local): acc <- step o acc per table cell — the maps of consecutive local
+// steps composed in step order, touch counts, payoff sums and visit counts added (oracle: ora_mccfr_window_accumulate)
+__global__ void k_accumulate(DevGame g, unsigned char* acc, const unsigned char* step, uint32_t first) {
+    const uint32_t cell = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t ncell = g.n_infos * g.A;
+    if (cell >= ncell) return;
+    const Cell s = reinterpret_cast<const Cell*>(step)[cell];
+    Cell* ac = reinterpret_cast<Cell*>(acc) + cell;
+    if (first) {
+        *ac = s;
+    } else {
+        const Cell a = *ac;
+        const Map r = map_compose(cell_regret(a), cell_regret(s));
+        const Map w = map_compose(cell_weight(a), cell_weight(s));
+        *ac = Cell{r.a, r.b, r.m, w.a, w.b, w.m, r.n, w.n};
+    }
+    if (cell % g.A == 0) {
+        const uint32_t info = cell / g.A;
+        const InfoSum si = reinterpret_cast<const InfoSum*>(step + (size_t)ncell * sizeof(Cell))[info];
+        InfoSum* ai = reinterpret_cast<InfoSum*>(acc + (size_t)ncell * sizeof(Cell)) + info;
+        if (first) *ai = si;
+        else *ai = InfoSum{ai->count + si.count, ai->psum + si.psum};
+    }
+}
+
+}  // namespace rp
+
+#endif

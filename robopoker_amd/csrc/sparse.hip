@@ -330,12 +330,6 @@ __global__ __launch_bounds__(128) void k_apply_hot(SparseParams p, DevBatch b, S
     }
 }
 
-__device__ __forceinline__ float composed_wdelta(int W, float sigma, float tf) {
-    if (W == RP_WEIGHT_LINEAR) return sigma * tf;
-    if (W == RP_WEIGHT_QUADRATIC) return sigma * tf * tf;
-    return sigma;
-}
-
 // COMPOSED, first half: a row's touches -> one entry (oracle: ora_profile_summarize).  Blocks of RP_SPARSE_BLOCK
 // consecutive touches are composed sequentially — every (row, block) pair by its own 16-lane group, so a hot row's
 // thousands of touches spread over the chip — and the block records of a row are folded in block order.
@@ -570,7 +564,7 @@ __global__ __launch_bounds__(256) void k_block_maps_sparse(SparseParams p, DevBa
                 if (u >= m) break;
                 if (mine) {
                     if ((cur.ev_mask >> u) & 1u) map_touch(br, p.dr, cur.dv[u], p.floor_r);
-                    map_touch(bw, p.dw, composed_wdelta(p.W, cur.sv[u], p.tf), RP_EPSILON);
+                    map_touch(bw, p.dw, weight_delta(p.W, cur.sv[u], p.tf), RP_EPSILON);
                 }
                 bp += cur.pv[u];
             }

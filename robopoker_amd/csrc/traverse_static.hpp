@@ -22,6 +22,10 @@
 
 #include <type_traits>
 
+#include "mccfr_kernels.hpp"
+#include "mccfr_traverse.hpp"  // DevInfoTab, count_metrics, the draws
+#include "mccfr_update.hpp"    // lds_exscan: the fused kernel builds the block maps of its chunk
+
 namespace rp {
 
 enum : int { SK_CHANCE = 0, SK_P0 = 1, SK_P1 = 2, SK_TERMINAL = 3 };
@@ -463,17 +467,17 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
     __shared__ uint32_t cls_n[16], cls_at[16];
     const uint32_t NI = g.n_infos, chunk = blockIdx.x, lt = threadIdx.x;
     uint32_t* bits = tm_lds;
-    uint32_t* lcount = bits + NI * 8u;
+    uint32_t* lcount = bits + NI * SM_WORDS;
     uint32_t* lbase = lcount + NI;
     uint16_t* pre = reinterpret_cast<uint16_t*>(lbase + NI);
-    uint16_t* order = pre + NI * 8u;
+    uint16_t* order = pre + NI * SM_WORDS;
     float* vals = reinterpret_cast<float*>(order + NI + (NI & 1u));
     // places per cell.  The five chains of an infoset read vals[c L + base + e] in the same instruction: with L a multiple of 32 they
     // share a bank (a 5-way conflict at every step); lpad = 7 words moves the cells apart (measured round 4, profiles/r04_optin_ab.json:
     // pads 0 / 3 / 7 / 13 within 1 % of each other — the conflicts were not the limiter)
     const uint32_t L = maxdec * 256u + lpad;
     uint32_t* lmask = reinterpret_cast<uint32_t*>(vals + 5u * L);
-    for (uint32_t e = lt; e < NI * 8u; e += 256u) bits[e] = 0;
+    for (uint32_t e = lt; e < NI * SM_WORDS; e += 256u) bits[e] = 0;
     if (lt < 16u) cls_n[lt] = 0;
     __syncthreads();
     const uint32_t lane = chunk * 256u + lt;
@@ -483,16 +487,12 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
         [&](auto info_of, auto live_of) __attribute__((always_inline)) {
             sk_for<0, SkelOf<G>::S.n>([&](auto J) __attribute__((always_inline)) {
                 if constexpr (SkelOf<G>::S.kind[decltype(J)::value] == (W == 0 ? SK_P0 : SK_P1)) {
-                    if (live_of(J)) atomicOr(&bits[info_of(J) * 8u + (lt >> 5)], 1u << (lt & 31u));
+                    if (live_of(J)) atomicOr(&bits[info_of(J) * SM_WORDS + (lt >> 5)], 1u << (lt & 31u));
                 }
             });
             __syncthreads();
             for (uint32_t info = lt; info < NI; info += 256u) {
-                uint32_t run = 0;
-                for (uint32_t w = 0; w < 8u; ++w) {
-                    pre[info * 8u + w] = (uint16_t)run;
-                    run += __popc(bits[info * 8u + w]);
-                }
+                const uint32_t run = list_prefix(bits, pre, info);
                 lcount[info] = run;
                 atomicAdd(&cls_n[15u - (run ? 32u - (uint32_t)__builtin_clz(run) : 0u)], 1u);  // class 15 - bit length: long lists first
             }
@@ -513,12 +513,12 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
         };
     auto on_decision =
         [&](auto, uint32_t info, float g0, float g1, float s0, float s1, float payoff, uint32_t mask) __attribute__((always_inline)) {
-            const uint32_t pos = lbase[info] + pre[info * 8u + (lt >> 5)] + __popc(bits[info * 8u + (lt >> 5)] & ((1u << (lt & 31u)) - 1u));
+            const uint32_t pos = lbase[info] + list_rank(bits, pre, info, lt);
             if constexpr (PRUNED) lmask[pos] = mask;
             vals[pos] = g0;
             vals[L + pos] = g1;
-            vals[2u * L + pos] = p.W == RP_WEIGHT_LINEAR ? s0 * tf : (p.W == RP_WEIGHT_QUADRATIC ? s0 * tf * tf : s0);
-            vals[3u * L + pos] = p.W == RP_WEIGHT_LINEAR ? s1 * tf : (p.W == RP_WEIGHT_QUADRATIC ? s1 * tf * tf : s1);
+            vals[2u * L + pos] = weight_delta(p.W, s0, tf);
+            vals[3u * L + pos] = weight_delta(p.W, s1, tf);
             vals[4u * L + pos] = payoff;
             ndec += 1u;
         };
@@ -529,7 +529,6 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
     __syncthreads();
     // the chains: task = (cell c, infoset); cells 0,1 regret, 2,3 weight, 4 the payoff sum.  The payoff sums are handed out after all
     // the map chains, so that no wavefront mixes the two loops (measured round 4: 0.582 -> 0.562 ms per launch against task % 5)
-    const float NEG_INF = rp_u2f(0xff800000u);
     for (uint32_t task = lt; task < 5u * NI; task += 256u) {
         const uint32_t c = task < 4u * NI ? task & 3u : 4u;
         const uint32_t info = order[task < 4u * NI ? task >> 2 : task - 4u * NI];
@@ -545,23 +544,10 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
             continue;
         }
         const bool isreg = c < 2u;
-        const float fl = isreg ? regret_floor_of(p.R, p.regret_min) : RP_EPSILON;
-        const float d = isreg ? (p.R == RP_REGRET_LINEAR ? tf / (tf + 1.0f) : 1.0f) : (p.W == RP_WEIGHT_EXPONENTIAL ? 0.9999f : 1.0f);
-        float ma = 1.0f, mb = 0.0f, mm = NEG_INF;
-        uint32_t cnt = 0;
-        for (uint32_t e = 0; e < n; ++e) {
-            const float delta = v[e];
-            const bool skip = PRUNED && isreg && !((lmask[base + e] >> c) & 1u);
-            // first touch of the block: (d, delta, floor); then a <- a d, b <- b d + delta, m <- max(m d + delta, floor)
-            const float na = cnt ? ma * d : d;
-            const float nb = cnt ? mb * d + delta : delta;
-            const float nm = cnt ? rp_maxf(mm * d + delta, fl) : fl;
-            ma = skip ? ma : na;
-            mb = skip ? mb : nb;
-            mm = skip ? mm : nm;
-            cnt += skip ? 0u : 1u;
-        }
-        bmaps[slot_out * 4u + c] = Map{ma, mb, mm, cnt};
+        const ChainParams cp = chain_params(p, isreg, tf);
+        Map mp = map_identity();
+        for (uint32_t e = 0; e < n; ++e) map_touch_unless(mp, PRUNED && isreg && !((lmask[base + e] >> c) & 1u), cp.d, v[e], cp.fl);
+        bmaps[slot_out * 4u + c] = mp;
     }
     count_metrics(p, nn, ndec, 0u);
 }

@@ -224,7 +224,12 @@ def test_long_run_stays_bit_exact(gpu, mode, game, regret, weight, sampling):
 @pytest.mark.parametrize("mode", ["ordered", "composed"])
 @pytest.mark.parametrize("regret,weight,sampling", [("floored", "linear", "external"), ("linear", "quadratic", "pluribus")])
 def test_wide_leduc_takes_the_large_game_path_bit_exact(gpu, mode, regret, weight, sampling):
-    # 616 infosets (> 256): per-infoset slot map, k_count / k_compact, k_block_maps over (infoset, chunk) groups
+    # 616 infosets: more than one per thread of a chunk's workgroup, and at most CM_PASSES * 256 with the chunk's lists still inside
+    # the 64 KB LDS budget, so no slot map (alloc_batch_buffers).  The game matches the Leduc skeleton, so the traversal is
+    # k_traverse_static<LeducSkel, .>, not the fused kernel (more than 256 infosets).  The composed step builds the block maps with
+    # k_chunk_maps<., CM_PASSES> (four infosets per thread) and folds them with k_combine2<true>; the ordered step sorts with
+    # k_count_small / k_scan / k_compact_small and applies with k_chain.  The slot-map kernels (k_count / k_compact / k_block_maps)
+    # run in the two tests below, which set RP_MCCFR_SLOTMAP
     g = Game("leduc_wide")
     assert g.n_infos == 616
     hp = oracle.default_hyper()
@@ -261,6 +266,31 @@ def test_slotmap_sort_variant_for_large_games_is_identical(gpu, monkeypatch):
     ra, rb = a.export(), b.export()
     for f in ("visits", "regret", "weight", "payoff"):
         assert np.array_equal(ra[f].view(np.uint32), rb[f].view(np.uint32)), f
+
+
+@pytest.mark.parametrize("mode", ["ordered", "composed"])
+@pytest.mark.parametrize("regret,weight,sampling", [("floored", "linear", "external"), ("linear", "quadratic", "pluribus")])
+def test_wide_leduc_slotmap_path_equals_the_oracle(gpu, monkeypatch, mode, regret, weight, sampling):
+    # the slot-map path against the oracle itself, with and without pruned edges: k_count / k_scan / k_compact, then k_chain
+    # (ordered) or k_block_maps<PRUNED> + k_combine2 (composed).  Batch 300 = one full 256-tree chunk and a ragged one.
+    g = Game("leduc_wide")
+    hp = oracle.default_hyper()
+    hp.prune_warmup = 1
+    hp.prune_threshold = -0.5  # edges are pruned from the second step on (the oracle's node count drops by a seventh)
+    monkeypatch.setenv("RP_MCCFR_SLOTMAP", "1")
+    dev = Solver(g, regret, weight, sampling, batch=300, seed=41, hyper=hp)
+    monkeypatch.delenv("RP_MCCFR_SLOTMAP")
+    ora = oracle.OracleSolver(g, regret, weight, sampling, batch=300, seed=41, hyper=hp)
+    if mode == "composed":
+        dev.set_update_mode("composed")
+    for _ in range(3):
+        dev.step()
+        if mode == "composed":
+            ora.step_world(1)
+        else:
+            ora.step()
+    assert_tables_equal(dev.export(), ora.export())
+    assert dev.counters() == ora.counters()
 
 
 @pytest.mark.parametrize("batch", [1, 63, 64, 65, 1024, 1025, 5000])
