@@ -359,6 +359,11 @@ RP_API int rp_profile_set_epoch(rp_profile* h, uint64_t epoch);
 RP_API int rp_profile_get_rows(rp_profile* h, uint64_t n, const uint32_t* rows, rp_encounter* out);
 /* overwrite rows from the host (hydrate / resynchronisation): in[i*max_actions + a] -> (rows[i], action a) */
 RP_API int rp_profile_set_rows(rp_profile* h, uint64_t n, const uint32_t* rows, const rp_encounter* in);
+/* the three distributions of rp_nlhe_policy for n rows of this table, every pointer in DEVICE memory: rows_dev [n], n_actions_dev [n]
+ * (clamped to max_actions), policy_dev [n][max_actions] (zero from slot n_actions on; a row >= n_rows reads as no actions).  One
+ * launch queued on the profile's stream; rp_profile_sync waits. */
+RP_API int rp_profile_policy(rp_profile* h, rp_dist_kind kind, uint64_t n, const uint32_t* rows_dev, const uint8_t* n_actions_dev,
+                             float* policy_dev);
 RP_API int rp_profile_set_stream(rp_profile* h, void* hip_stream);
 /* multi-GPU: bytes of one summary entry (16 + 2*max_actions*16), and the two halves of a sharded step.
  * summarize: this rank's batch -> entries sorted by row in `entries_dev` (capacity >= batch->n entries);
@@ -428,6 +433,29 @@ RP_API int rp_nlhe_export(rp_nlhe* h, uint64_t cap, uint64_t* n, uint64_t* past,
 /* Hydrate (profile.rs:90-141): load Encounters by infoset; sets the epoch */
 RP_API int rp_nlhe_import(rp_nlhe* h, uint64_t n, const uint64_t* past, const uint32_t* present, const uint64_t* choices,
                           const rp_encounter* enc, uint64_t epoch);
+
+/* What the blueprint says, asked BY KEY (Brain::policy, parlor/src/players/brain.rs:45-55; Source::strategy / Source::memory,
+ * nlhe/src/source.rs:40-87): n infosets (past[i], present[i], choices[i]) against the device-resident table, read-only — nothing is
+ * inserted, epoch / counters / keys are unchanged, and no query can fail a later step.
+ * rp_nlhe_policy: RefProf::iterated_distribution / averaged_distribution (profile.rs:40-51) or CfrFlow::sampling_distribution
+ * (flow.rs:24-42, temperature / smoothing / curiosity of the handle's rp_hyper).  policy [n][9]; edges [n][9] (edge code of slot a);
+ * n_actions [n] = the consecutive non-zero 5-bit groups of `choices` from bit 0 (at most 9); found [n] (1: the infoset has a row).
+ * edges / n_actions / found may be NULL.  An infoset without a row reads as default regret, zero weight (book.rs:93-122); slots
+ * a >= n_actions are zero.  The arithmetic is rp_mccfr_policy's: f32, left folds in slot order, every operation rounded on its own.
+ * The _device forms take every pointer in DEVICE memory, queue one launch on the handle's stream (rp_nlhe_set_stream) and return:
+ * they are ordered after earlier steps and imports, rp_nlhe_sync waits.  The host forms stage, launch and synchronise.
+ * n = 0 is RP_OK without a launch. */
+RP_API int rp_nlhe_policy(rp_nlhe* h, rp_dist_kind kind, uint64_t n, const uint64_t* past, const uint32_t* present,
+                          const uint64_t* choices, float* policy, uint8_t* edges, uint8_t* n_actions, uint8_t* found);
+RP_API int rp_nlhe_policy_device(rp_nlhe* h, rp_dist_kind kind, uint64_t n, const uint64_t* past_dev, const uint32_t* present_dev,
+                                 const uint64_t* choices_dev, float* policy_dev, uint8_t* edges_dev, uint8_t* n_actions_dev,
+                                 uint8_t* found_dev);
+/* Source::memory (nlhe/src/source.rs:40-65): the 9 Encounters of each infoset, enc [n][9]; an absent infoset's are
+ * {weight 0, regret = the edge's default, payoff 0, visits 0}, slots a >= n_actions are zero */
+RP_API int rp_nlhe_memory(rp_nlhe* h, uint64_t n, const uint64_t* past, const uint32_t* present, const uint64_t* choices,
+                          rp_encounter* enc, uint8_t* n_actions, uint8_t* found);
+RP_API int rp_nlhe_memory_device(rp_nlhe* h, uint64_t n, const uint64_t* past_dev, const uint32_t* present_dev,
+                                 const uint64_t* choices_dev, rp_encounter* enc_dev, uint8_t* n_actions_dev, uint8_t* found_dev);
 
 /* Multi-GPU (BASELINE configs[3]): trees sharded by rank (rank r samples tree ids [r*B, (r+1)*B) of a world*B-tree epoch
  * against a replicated table).  step_local: this rank's traversal reduced to one composed entry per infoset touched

@@ -199,6 +199,7 @@ _SIGNATURES = {
     "rp_profile_epoch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rp_profile_set_epoch": (C.c_int, [C.c_void_p, C.c_uint64]),
     "rp_profile_get_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "rp_profile_policy": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rp_profile_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rp_profile_entry_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
     "rp_profile_summarize": (C.c_int, [C.c_void_p, C.POINTER(Decisions), C.c_void_p, C.POINTER(C.c_uint32)]),
@@ -291,6 +292,10 @@ _SIGNATURES = {
     "rp_nlhe_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "rp_nlhe_export": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rp_nlhe_import": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "rp_nlhe_policy": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64] + [C.c_void_p] * 7),
+    "rp_nlhe_policy_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64] + [C.c_void_p] * 7),
+    "rp_nlhe_memory": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6),
+    "rp_nlhe_memory_device": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6),
     "rp_nlhe_set_shard": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "rp_nlhe_entry_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
     "rp_nlhe_step_local": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "nlmc_level.hpp"
+#include "nlmc_query.hpp"
 #include "rp_internal.h"
 #include "sortscan.hpp"
 
@@ -930,6 +931,121 @@ int rp_nlhe_sync(rp_nlhe* h) {
         HIP_TRY(hipMemset(h->d_remap_err, 0, 4));
         return nl_capacity_error(err);
     }
+    return RP_OK;
+}
+
+}  // extern "C"
+
+// ---- the read side (nlmc_query.hpp): queries by NlheInfo key, read-only.  The _device forms queue one launch on the profile's
+// stream; the host forms stage through device scratch, call them and synchronise.
+namespace {
+uint32_t nlq_blocks(const rp_nlhe* h, uint64_t n, uint32_t per_block) {
+    return (uint32_t)std::min<uint64_t>((n + per_block - 1) / per_block, h->grid_cap);
+}
+// device scratch of one host-form query: the keys in, the answers out, all in one allocation
+struct NlqStage {
+    unsigned char* base = nullptr;
+    uint64_t *past = nullptr, *choices = nullptr;
+    uint32_t* present = nullptr;
+    unsigned char* main = nullptr;  // policy [n][9] f32 or enc [n][9]
+    uint8_t *edges = nullptr, *n_actions = nullptr, *found = nullptr;
+    ~NlqStage() {
+        if (base) (void)hipFree(base);
+    }
+};
+int nlq_stage(NlqStage& s, hipStream_t st, uint64_t n, size_t main_bytes, const uint64_t* past, const uint32_t* present, const uint64_t* choices) {
+    const size_t o_choices = n * 8, o_main = o_choices + n * 8, o_present = o_main + n * main_bytes, o_edges = o_present + n * 4,
+                 o_nact = o_edges + n * NLMC_A, o_found = o_nact + n;
+    HIP_TRY(hipMalloc(&s.base, o_found + n));
+    s.past = reinterpret_cast<uint64_t*>(s.base);
+    s.choices = reinterpret_cast<uint64_t*>(s.base + o_choices);
+    s.main = s.base + o_main;
+    s.present = reinterpret_cast<uint32_t*>(s.base + o_present);
+    s.edges = s.base + o_edges;
+    s.n_actions = s.base + o_nact;
+    s.found = s.base + o_found;
+    HIP_TRY(hipMemcpyAsync(s.past, past, n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s.choices, choices, n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s.present, present, n * 4, hipMemcpyHostToDevice, st));
+    return RP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rp_nlhe_policy_device(rp_nlhe* h, rp_dist_kind kind, uint64_t n, const uint64_t* past, const uint32_t* present, const uint64_t* choices,
+                          float* policy, uint8_t* edges, uint8_t* n_actions, uint8_t* found) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_policy: NULL handle");
+    if (kind != RP_DIST_ITERATED && kind != RP_DIST_AVERAGED && kind != RP_DIST_SAMPLING)
+        return rp::fail(RP_ERR_INVALID, "rp_nlhe_policy: unknown distribution kind %d", (int)kind);
+    if (n == 0) return RP_OK;
+    if (!past || !present || !choices || !policy) return rp::fail(RP_ERR_INVALID, "rp_nlhe_policy: NULL keys or NULL policy with n > 0");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    const NlQuery q{n, past, present, choices, edges, n_actions, found};
+    const DistParams hp{h->hp.temperature, h->hp.smoothing, h->hp.curiosity};
+    // RP_NLHE_QUERY_SHAPE=lane (read at every call, so that one table answers through both shapes alternately:
+    // scripts/nlhe_policy_rate.py): the one-lane-per-query kernel the shipped shape is measured against
+    const char* shape = getenv("RP_NLHE_QUERY_SHAPE");
+    if (shape && !strcmp(shape, "lane"))
+        hipLaunchKernelGGL(k_nl_policy_lane, dim3(nlq_blocks(h, n, NLQ_BLOCK)), dim3(NLQ_BLOCK), 0, st, h->tab, q, (int)kind, hp, policy);
+    else if (kind == RP_DIST_ITERATED)
+        hipLaunchKernelGGL(k_nl_policy_group<false>, dim3(nlq_blocks(h, n, NLQ_BLOCK / NLQ_GROUP)), dim3(NLQ_BLOCK), 0, st, h->tab, q, (int)kind, hp, policy);
+    else
+        hipLaunchKernelGGL(k_nl_policy_group<true>, dim3(nlq_blocks(h, n, NLQ_BLOCK / NLQ_GROUP)), dim3(NLQ_BLOCK), 0, st, h->tab, q, (int)kind, hp, policy);
+    HIP_TRY(hipGetLastError());
+    return RP_OK;
+}
+
+int rp_nlhe_policy(rp_nlhe* h, rp_dist_kind kind, uint64_t n, const uint64_t* past, const uint32_t* present, const uint64_t* choices,
+                   float* policy, uint8_t* edges, uint8_t* n_actions, uint8_t* found) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_policy: NULL handle");
+    if (kind != RP_DIST_ITERATED && kind != RP_DIST_AVERAGED && kind != RP_DIST_SAMPLING)
+        return rp::fail(RP_ERR_INVALID, "rp_nlhe_policy: unknown distribution kind %d", (int)kind);
+    if (n == 0) return RP_OK;
+    if (!past || !present || !choices || !policy) return rp::fail(RP_ERR_INVALID, "rp_nlhe_policy: NULL keys or NULL policy with n > 0");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    NlqStage s;
+    int rc = nlq_stage(s, st, n, NLMC_A * sizeof(float), past, present, choices);
+    if (rc) return rc;
+    if ((rc = rp_nlhe_policy_device(h, kind, n, s.past, s.present, s.choices, reinterpret_cast<float*>(s.main), s.edges, s.n_actions, s.found)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(policy, s.main, n * NLMC_A * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (edges) HIP_TRY(hipMemcpyAsync(edges, s.edges, n * NLMC_A, hipMemcpyDeviceToHost, st));
+    if (n_actions) HIP_TRY(hipMemcpyAsync(n_actions, s.n_actions, n, hipMemcpyDeviceToHost, st));
+    if (found) HIP_TRY(hipMemcpyAsync(found, s.found, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RP_OK;
+}
+
+int rp_nlhe_memory_device(rp_nlhe* h, uint64_t n, const uint64_t* past, const uint32_t* present, const uint64_t* choices, rp_encounter* enc,
+                          uint8_t* n_actions, uint8_t* found) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_memory: NULL handle");
+    if (n == 0) return RP_OK;
+    if (!past || !present || !choices || !enc) return rp::fail(RP_ERR_INVALID, "rp_nlhe_memory: NULL keys or NULL enc with n > 0");
+    HIP_TRY(hipSetDevice(h->device));
+    const NlQuery q{n, past, present, choices, nullptr, n_actions, found};
+    hipLaunchKernelGGL(k_nl_memory, dim3(nlq_blocks(h, n, NLQ_BLOCK / NLQ_MGROUP)), dim3(NLQ_BLOCK), 0, rp::profile_stream(h->prof), h->tab, q, enc);
+    HIP_TRY(hipGetLastError());
+    return RP_OK;
+}
+
+int rp_nlhe_memory(rp_nlhe* h, uint64_t n, const uint64_t* past, const uint32_t* present, const uint64_t* choices, rp_encounter* enc,
+                   uint8_t* n_actions, uint8_t* found) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_memory: NULL handle");
+    if (n == 0) return RP_OK;
+    if (!past || !present || !choices || !enc) return rp::fail(RP_ERR_INVALID, "rp_nlhe_memory: NULL keys or NULL enc with n > 0");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    NlqStage s;
+    int rc = nlq_stage(s, st, n, NLMC_A * sizeof(rp_encounter), past, present, choices);
+    if (rc) return rc;
+    if ((rc = rp_nlhe_memory_device(h, n, s.past, s.present, s.choices, reinterpret_cast<rp_encounter*>(s.main), s.n_actions, s.found))) return rc;
+    HIP_TRY(hipMemcpyAsync(enc, s.main, n * NLMC_A * sizeof(rp_encounter), hipMemcpyDeviceToHost, st));
+    if (n_actions) HIP_TRY(hipMemcpyAsync(n_actions, s.n_actions, n, hipMemcpyDeviceToHost, st));
+    if (found) HIP_TRY(hipMemcpyAsync(found, s.found, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return RP_OK;
 }
 

@@ -16,6 +16,7 @@
 
 #include "sortscan.hpp"
 #include "mccfr_kernels.hpp"
+#include "policy_dist.hpp"
 
 namespace rp {
 
@@ -800,6 +801,23 @@ __global__ void k_gather_rows(const float* tab, uint32_t A, const uint32_t* rows
     out[e].visits = reinterpret_cast<const uint32_t*>(row)[3 * A + a];
 }
 
+// rp_profile_policy: one lane per queried row (a row is 16 * max_actions bytes; only its regrets or its weights are read)
+__global__ __launch_bounds__(256) void k_row_policy(const float* tab, uint64_t n_rows, uint32_t A, int kind, DistParams hp, const uint32_t* rows,
+                                                    const uint8_t* n_actions, uint64_t n, float* policy) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) {
+        const uint32_t row = rows[i];
+        const uint32_t na = row < n_rows ? min((uint32_t)n_actions[i], A) : 0u;
+        const float* src = tab + (size_t)(row < n_rows ? row : 0u) * 4u * A + (kind == (int)RP_DIST_ITERATED ? 0u : A);
+        float v[RP_MAX_ACTIONS], out[RP_MAX_ACTIONS];
+#pragma unroll
+        for (uint32_t a = 0; a < RP_MAX_ACTIONS; ++a) v[a] = a < na ? src[a] : 0.0f;
+        policy_distribution<RP_MAX_ACTIONS>(kind, hp, v, na, out);
+#pragma unroll
+        for (uint32_t a = 0; a < RP_MAX_ACTIONS; ++a)
+            if (a < A) policy[i * A + a] = out[a];
+    }
+}
+
 struct SpClock {
     double total_ms = 0.0;
     uint64_t launches = 0;
@@ -1207,6 +1225,20 @@ int rp_profile_set_rows(rp_profile* h, uint64_t n, const uint32_t* rows, const r
         }
         HIP_TRY(hipMemcpy(h->tab + (size_t)rows[i] * 4u * h->A, row.data(), row.size() * 4, hipMemcpyHostToDevice));
     }
+    return RP_OK;
+}
+
+int rp_profile_policy(rp_profile* h, rp_dist_kind kind, uint64_t n, const uint32_t* rows_dev, const uint8_t* n_actions_dev, float* policy_dev) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_profile_policy: null handle");
+    if (kind != RP_DIST_ITERATED && kind != RP_DIST_AVERAGED && kind != RP_DIST_SAMPLING)
+        return rp::fail(RP_ERR_INVALID, "rp_profile_policy: unknown distribution kind %d", (int)kind);
+    if (n == 0) return RP_OK;
+    if (!rows_dev || !n_actions_dev || !policy_dev) return rp::fail(RP_ERR_INVALID, "rp_profile_policy: null argument with n > 0");
+    HIP_TRY(hipSetDevice(h->device));
+    const DistParams hp{h->hp.temperature, h->hp.smoothing, h->hp.curiosity};
+    hipLaunchKernelGGL(k_row_policy, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 16384)), dim3(256), 0, h->stream, h->tab, h->n_rows, h->A,
+                       (int)kind, hp, rows_dev, n_actions_dev, n, policy_dev);
+    HIP_TRY(hipGetLastError());
     return RP_OK;
 }
 

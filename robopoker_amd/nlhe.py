@@ -174,6 +174,61 @@ class NlheSolver:
         enc = np.ascontiguousarray(enc, dtype=ENC_DTYPE)
         _lib.check(self._lib.rp_nlhe_import(self._h, past.size, _p(past), _p(present), _p(choices), _p(enc), epoch))
 
+    # ---- the read side: what the blueprint says about infosets given BY KEY (include/rp_mi355x.h rp_nlhe_policy / rp_nlhe_memory) ----
+    def _keys(self, past, present, choices):
+        """-> (on_device, past, present, choices): torch device tensors go to the _device forms, anything else through numpy to the host forms"""
+        if isinstance(past, torch.Tensor):
+            ks = [t.contiguous() for t in (past, present, choices)]
+            assert all(isinstance(t, torch.Tensor) and t.is_cuda for t in ks), "keys: three device tensors or three host arrays"
+            assert ks[0].element_size() == 8 and ks[1].element_size() == 4 and ks[2].element_size() == 8  # torch spells u64 / u32 as int64 / int32
+            assert ks[0].numel() == ks[1].numel() == ks[2].numel()
+            return True, *ks
+        ks = (np.ascontiguousarray(past, np.uint64), np.ascontiguousarray(present, np.uint32), np.ascontiguousarray(choices, np.uint64))
+        assert ks[0].size == ks[1].size == ks[2].size
+        return False, *ks
+
+    def policy(self, past, present, choices, kind="averaged"):
+        """``Brain::policy`` / ``Source::strategy`` for n infosets: dict(policy float32[n,9], edges uint8[n,9], n_actions uint8[n],
+        found bool[n]); kind: "iterated", "averaged", "sampling".  Read-only.  Device tensors in -> device tensors out, queued on the
+        solver's stream (``sync()`` waits); numpy in -> numpy out."""
+        dev, past, present, choices = self._keys(past, present, choices)
+        if dev:
+            n, d = past.numel(), past.device
+            out = dict(policy=torch.empty((n, A), dtype=torch.float32, device=d), edges=torch.empty((n, A), dtype=torch.uint8, device=d),
+                       n_actions=torch.empty(n, dtype=torch.uint8, device=d), found=torch.empty(n, dtype=torch.uint8, device=d))
+            torch.cuda.current_stream(d).synchronize()  # whatever produced the keys on torch's stream has finished
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if n else None
+            _lib.check(self._lib.rp_nlhe_policy_device(self._h, _lib.DIST[kind], n, ptr(past), ptr(present), ptr(choices), ptr(out["policy"]),
+                                                       ptr(out["edges"]), ptr(out["n_actions"]), ptr(out["found"])))
+            self._query_keys = (past, present, choices)  # the queued launch reads them
+            out["found"] = out["found"].view(torch.bool)
+            return out
+        n = past.size
+        out = dict(policy=np.zeros((n, A), np.float32), edges=np.zeros((n, A), np.uint8), n_actions=np.zeros(n, np.uint8),
+                   found=np.zeros(n, np.uint8))
+        _lib.check(self._lib.rp_nlhe_policy(self._h, _lib.DIST[kind], n, _p(past), _p(present), _p(choices), _p(out["policy"]),
+                                            _p(out["edges"]), _p(out["n_actions"]), _p(out["found"])))
+        out["found"] = out["found"].view(np.bool_)
+        return out
+
+    def memory(self, past, present, choices):
+        """``Source::memory`` for n infosets: (enc ENC_DTYPE[n,9], n_actions uint8[n], found bool[n]).  Device tensors in -> enc is a device
+        tensor uint8[n,9,16] (``.cpu().numpy().view(ENC_DTYPE)[..., 0]``), queued on the solver's stream."""
+        dev, past, present, choices = self._keys(past, present, choices)
+        if dev:
+            n, d = past.numel(), past.device
+            enc = torch.empty((n, A, ENC_DTYPE.itemsize), dtype=torch.uint8, device=d)
+            nact, found = torch.empty(n, dtype=torch.uint8, device=d), torch.empty(n, dtype=torch.uint8, device=d)
+            torch.cuda.current_stream(d).synchronize()
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if n else None
+            _lib.check(self._lib.rp_nlhe_memory_device(self._h, n, ptr(past), ptr(present), ptr(choices), ptr(enc), ptr(nact), ptr(found)))
+            self._query_keys = (past, present, choices)
+            return enc, nact, found.view(torch.bool)
+        n = past.size
+        enc, nact, found = np.zeros((n, A), dtype=ENC_DTYPE), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        _lib.check(self._lib.rp_nlhe_memory(self._h, n, _p(past), _p(present), _p(choices), _p(enc), _p(nact), _p(found)))
+        return enc, nact, found.view(np.bool_)
+
 
 
 def playouts(n_players: int, n_games: int, seed: int, max_steps: int = 200, device: int = 0):

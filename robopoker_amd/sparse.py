@@ -79,6 +79,32 @@ class SparseProfile:
         _lib.check(self._lib.rp_profile_get_rows(self._h, rows.size, rows.ctypes.data, out.ctypes.data))
         return out
 
+    def set_rows(self, rows, enc):
+        """overwrite rows from the host: enc structured [len(rows)][A] of (weight, regret, payoff, visits)"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        enc = np.ascontiguousarray(enc, dtype=[("weight", "<f4"), ("regret", "<f4"), ("payoff", "<f4"), ("visits", "<u4")])
+        assert enc.shape == (rows.size, self.A)
+        _lib.check(self._lib.rp_profile_set_rows(self._h, rows.size, rows.ctypes.data, enc.ctypes.data))
+
+    def policy(self, rows, n_actions, kind="averaged") -> torch.Tensor:
+        """iterated / averaged / sampling distribution of the given rows (include/rp_mi355x.h rp_profile_policy): device tensor
+        float32[n][A], zero from slot n_actions[i] on.  rows / n_actions: device tensors (int32 / uint8) or host arrays (uploaded);
+        queued on the profile's stream, ``sync()`` waits."""
+        dev = torch.device("cuda", self.device)
+        if not isinstance(rows, torch.Tensor):
+            rows = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.uint32).view(np.int32)).to(dev)
+        if not isinstance(n_actions, torch.Tensor):
+            n_actions = torch.from_numpy(np.ascontiguousarray(n_actions, dtype=np.uint8)).to(dev)
+        rows, n_actions = rows.contiguous(), n_actions.contiguous()
+        assert rows.element_size() == 4 and n_actions.element_size() == 1 and rows.numel() == n_actions.numel()
+        n = rows.numel()
+        out = torch.empty((n, self.A), dtype=torch.float32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()  # the uploads above ran on torch's stream
+        _lib.check(self._lib.rp_profile_policy(self._h, _lib.DIST[kind], n, rows.data_ptr() if n else None,
+                                               n_actions.data_ptr() if n else None, out.data_ptr() if n else None))
+        self._query_keys = (rows, n_actions)  # the queued launch reads them
+        return out
+
     def set_stream(self, ptr):
         _lib.check(self._lib.rp_profile_set_stream(self._h, ptr))
 

@@ -5,6 +5,7 @@
       -> the four isomorphism -> abstraction Lookup tables (nlhe/src/encoder.rs:30-36)
       -> NlheSolver(tables=...) = Flagship<LinearRegret, LinearWeight, PluribusSampling> for a fixed number of steps
       -> NlheProfile::rows streamed to a blueprint file (COPY format) -> Hydrate into a fresh solver
+      -> the hydrated solver answers policy queries by key for every exported infoset (rp_nlhe_policy)
       -> the next batch of both solvers is identical (every key, mask and the regret / policy bits).
 
 usage: full_blueprint.py [batch] [steps] [cap_log2]      -> one JSON object on stdout (stage times in seconds)"""
@@ -68,6 +69,14 @@ b = NlheSolver(cap_log2=cap, regret="linear", weight="linear", batch=batch, seed
 b.load(*back, epoch=a.epoch)
 out["hydrate_s"] = time.perf_counter() - t0
 os.remove(path)
+# the hydrated blueprint asked by key for every infoset the trained solver exported: the answers are the trained table's own
+t0 = time.perf_counter()
+asked = b.policy(exp[0], exp[1], exp[2], kind="averaged")
+out["policy_query_s"] = time.perf_counter() - t0
+out["policy_queries"] = int(exp[0].size)
+out["policy_queries_all_found"] = bool(asked["found"].all())
+out["policy_queries_equal_trained_table"] = bool(np.array_equal(asked["policy"].view(np.uint32),
+                                                               a.policy(exp[0], exp[1], exp[2], kind="averaged")["policy"].view(np.uint32)))
 da, db = a.batch(), b.batch()
 same = da["n"] == db["n"]
 for f in ("tree", "past", "present", "choices", "n_actions", "expanded"):
