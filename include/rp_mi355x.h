@@ -457,6 +457,77 @@ RP_API int rp_nlhe_memory(rp_nlhe* h, uint64_t n, const uint64_t* past, const ui
 RP_API int rp_nlhe_memory_device(rp_nlhe* h, uint64_t n, const uint64_t* past_dev, const uint32_t* present_dev,
                                  const uint64_t* choices_dev, rp_encounter* enc_dev, uint8_t* n_actions_dev, uint8_t* found_dev);
 
+/* Ranges: what the blueprint says about every hole a seat could hold, given what the other seat has seen (Nlhe::reach,
+ * opponent_reaches, opponent_range, opponent_observations, signalled_observations, signalled_reaches, normalize:
+ * nlhe/src/solver.rs:137-260).  One recall is the edge-level content of a Witness (kicker/src/witness.rs:36-44) after
+ * Recall::history(); translating actions to edges is the caller's.  Read-only exactly as the key queries above: nothing is inserted,
+ * epoch / counters / keys are unchanged, no query can fail a later step.  One workgroup per recall (csrc/nlmc_range.hpp).
+ *
+ * CANDIDATES, in HandIterator order (deuce/src/hand_iter.rs: ascending numeric value of the two-bit mask), count[r] of them.
+ *   `board` = the union of draws[0 .. k), k = the larger of the number of Draw edges in the history (at most 3) and the street the
+ *   replay ends on (the replay can deal a street no Draw edge names, see REPLAY).
+ *   RP_REACH_OPPONENT  Observation::opponents (deuce/src/observation.rs:122-126): every mask disjoint from hole | board; the subject
+ *                      (whose policy is multiplied) is the seat opposite `pov` and holds the candidate.
+ *   RP_REACH_SIGNALLED signalled_reaches (solver.rs:227-240): every mask disjoint from board — hero's own cards are NOT removed;
+ *                      the subject is `pov`, holding the candidate; the other seat's stub hole is inert.
+ * REACH = 1.0f * p_1 * p_2 ..., multiplied left to right in f32, one rounding per multiply (Iterator::product, solver.rs:145-152);
+ *   one factor per replay node whose turn, read BEFORE the edge is applied, is the subject (encoder.rs:72-84); an empty product
+ *   is 1.0f.  The factor is averaged_distribution(info).density(edge): RP_DIST_AVERAGED's arithmetic as rp_nlhe_policy has it (an
+ *   absent infoset reads as zero weights; the total is the left fold over all slots of the infoset), 0.0f when the edge is not
+ *   among the infoset's choices.
+ * REPLAY = CfrEncoder::replay over NlheGame::apply (nlhe/src/game.rs:50-70) from Game::from_start(dealer, stacks), with one
+ *   deviation: where the reference's reveal() deals random cards, the recall's draws are dealt (street s deals draws[s]).  Corners
+ *   as the reference has them: at a terminal state the remaining edges change nothing and contribute nothing; a choice edge met at a
+ *   chance node first deals the pending streets (that node's turn was chance: no factor); a Draw edge met at a choice node leaves
+ *   the game unchanged, is still appended to the path, and contributes factor 0 when the actor is the subject.
+ * KEY of a node = resume(past, game) (nlhe/src/encoder.rs:59-67, info.rs:125-139): every edge so far is collected into a Path, which
+ *   keeps only the FIRST 12 (kicker/src/path.rs:169-181, MAX_PATH_EDGES); the key's `past` is the trailing choice edges of that
+ *   12-edge path, `choices` = game.choices(aggression of the same path), `present` = the bucket of (candidate, the game's board at
+ *   that node).  From the 13th edge on the path no longer grows: that is the reference's behaviour for long histories and is
+ *   reproduced, not repaired.
+ * NORMALIZE (solver.rs:254-260): total = the f32 sum in candidate order, every reach divided by it; a total equal to zero (either
+ *   sign) leaves the stream untouched.  normalize = 0: opponent_reaches / signalled_reaches; != 0: the two *_observations.
+ * RANGE (rp_nlhe_opponent_range = opponent_range's Posterior<NlheSecret>): candidates and reaches of RP_REACH_OPPONENT; the bucket is
+ *   abstraction(candidate, board); mass[r][b] = the f32 sum of the reaches of bucket index b in candidate order (Posterior::add,
+ *   mccfr/src/strategy/posterior.rs:47-50), seen[r][b] = 1 where some candidate has that bucket (an entry of the map, mass 0.0 included).
+ * STATUS per recall, rp_recall_status.  A malformed recall yields count 0, zero outputs and its status; the call is still RP_OK and
+ *   the other recalls of the batch are answered.  No input causes an out-of-bounds access.
+ * Outputs: count [n]; holes [n][RP_NLHE_MAX_HOLES] the candidates' masks; reach [n][RP_NLHE_MAX_HOLES]; status [n]; entries past
+ * count[r] are zero; holes and status may be NULL.  mass [n][256] f32, seen [n][256].  The _device forms take every pointer in
+ * DEVICE memory, queue one launch on the handle's stream and return, ordered exactly like rp_nlhe_policy_device; the host forms
+ * stage, launch and synchronise.  n_recalls = 0 is RP_OK without a launch. */
+#define RP_NLHE_MAX_HISTORY 48u
+#define RP_NLHE_MAX_HOLES 1326u
+typedef struct rp_nlhe_recall {
+    uint64_t hole;       /* the point-of-view seat's two cards: bit c = card c, as everywhere in this library */
+    uint64_t draws[3];   /* flop (3 bits), turn (1), river (1): the cards each Draw deals, in street order; 0 where not dealt */
+    int16_t stacks[2];   /* 0,0 = the reference's STACK (200); otherwise both positive */
+    uint8_t pov;         /* Witness::turn(): seat 0 or 1 */
+    uint8_t dealer;      /* 0 in analysis mode */
+    uint8_t n_edges;     /* <= RP_NLHE_MAX_HISTORY */
+    uint8_t reserved;    /* 0 */
+    uint8_t edges[RP_NLHE_MAX_HISTORY]; /* edge codes (Draw = 1 ...: kicker/src/edge.rs:101-120), Draw edges included */
+} rp_nlhe_recall;
+typedef enum { RP_REACH_OPPONENT = 0, RP_REACH_SIGNALLED = 1 } rp_reach_kind;
+typedef enum {
+    RP_RECALL_OK = 0,
+    RP_RECALL_EDGE = 1,    /* an edge code that is no edge (0 or above 19) */
+    RP_RECALL_ILLEGAL = 2, /* a snapped action the rules refuse (Game::is_allowed) */
+    RP_RECALL_LENGTH = 3,  /* n_edges above RP_NLHE_MAX_HISTORY */
+    RP_RECALL_CARDS = 4,   /* hole not two cards; draws with wrong popcounts, overlapping each other or the hole, or out of street order */
+    RP_RECALL_DRAW = 5,    /* a Draw (an edge, or a street the replay deals itself) that needs cards the recall does not carry */
+    RP_RECALL_SEAT = 6,    /* pov > 1, dealer > 1, reserved != 0, or stacks neither 0,0 nor both positive */
+    RP_RECALL_LOOKUP = 7   /* lookup-table encoder only: an observation the tables do not hold (the reference panics) */
+} rp_recall_status;
+RP_API int rp_nlhe_reaches(rp_nlhe* h, rp_reach_kind kind, int normalize, uint64_t n_recalls, const rp_nlhe_recall* recalls,
+                           uint32_t* count, uint64_t* holes, float* reach, uint8_t* status);
+RP_API int rp_nlhe_reaches_device(rp_nlhe* h, rp_reach_kind kind, int normalize, uint64_t n_recalls, const rp_nlhe_recall* recalls_dev,
+                                  uint32_t* count_dev, uint64_t* holes_dev, float* reach_dev, uint8_t* status_dev);
+RP_API int rp_nlhe_opponent_range(rp_nlhe* h, uint64_t n_recalls, const rp_nlhe_recall* recalls, float* mass, uint8_t* seen,
+                                  uint8_t* status);
+RP_API int rp_nlhe_opponent_range_device(rp_nlhe* h, uint64_t n_recalls, const rp_nlhe_recall* recalls_dev, float* mass_dev,
+                                         uint8_t* seen_dev, uint8_t* status_dev);
+
 /* Multi-GPU (BASELINE configs[3]): trees sharded by rank (rank r samples tree ids [r*B, (r+1)*B) of a world*B-tree epoch
  * against a replicated table).  step_local: this rank's traversal reduced to one composed entry per infoset touched
  * (rp_profile_summarize's records, entry_bytes each, at most max_entries) plus the infoset KEY of every entry — each

@@ -31,6 +31,9 @@ GAME = {"kuhn": 0, "leduc": 1, "rps": 2, "leduc_wide": 3}
 DIST = {"iterated": 0, "averaged": 1, "sampling": 2}
 METRIC = {"sinkhorn": 0, "variation": 1}
 UPDATE = {"ordered": 0, "composed": 1}
+REACH = {"opponent": 0, "signalled": 1}  # rp_reach_kind
+RP_NLHE_MAX_HISTORY = 48
+RP_NLHE_MAX_HOLES = 1326
 
 
 class Hyper(C.Structure):
@@ -48,6 +51,12 @@ class Hyper(C.Structure):
 
 class Encounter(C.Structure):
     _fields_ = [("weight", C.c_float), ("regret", C.c_float), ("payoff", C.c_float), ("visits", C.c_uint32)]
+
+
+class NlheRecall(C.Structure):
+    """rp_nlhe_recall: what one seat has seen, at edge level (88 bytes)"""
+    _fields_ = [("hole", C.c_uint64), ("draws", C.c_uint64 * 3), ("stacks", C.c_int16 * 2), ("pov", C.c_uint8), ("dealer", C.c_uint8),
+                ("n_edges", C.c_uint8), ("reserved", C.c_uint8), ("edges", C.c_uint8 * 48)]
 
 
 class State(C.Structure):
@@ -296,6 +305,10 @@ _SIGNATURES = {
     "rp_nlhe_policy_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64] + [C.c_void_p] * 7),
     "rp_nlhe_memory": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6),
     "rp_nlhe_memory_device": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6),
+    "rp_nlhe_reaches": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint64] + [C.c_void_p] * 5),
+    "rp_nlhe_reaches_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint64] + [C.c_void_p] * 5),
+    "rp_nlhe_opponent_range": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
+    "rp_nlhe_opponent_range_device": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
     "rp_nlhe_set_shard": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "rp_nlhe_entry_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
     "rp_nlhe_step_local": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),

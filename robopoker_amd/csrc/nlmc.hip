@@ -33,6 +33,7 @@
 
 #include "nlmc_level.hpp"
 #include "nlmc_query.hpp"
+#include "nlmc_range.hpp"
 #include "rp_internal.h"
 #include "sortscan.hpp"
 
@@ -1045,6 +1046,109 @@ int rp_nlhe_memory(rp_nlhe* h, uint64_t n, const uint64_t* past, const uint32_t*
     HIP_TRY(hipMemcpyAsync(enc, s.main, n * NLMC_A * sizeof(rp_encounter), hipMemcpyDeviceToHost, st));
     if (n_actions) HIP_TRY(hipMemcpyAsync(n_actions, s.n_actions, n, hipMemcpyDeviceToHost, st));
     if (found) HIP_TRY(hipMemcpyAsync(found, s.found, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RP_OK;
+}
+
+}  // extern "C"
+
+// ---- ranges (nlmc_range.hpp): one workgroup per recall, at most NR_CHUNK recalls per launch
+namespace {
+constexpr uint64_t NR_CHUNK = 1ull << 20;
+int nr_launch(rp_nlhe* h, int kind, int normalize, uint64_t n, const rp_nlhe_recall* recalls, uint32_t* count, uint64_t* holes, float* reach,
+              float* mass, uint8_t* seen, uint8_t* status) {
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    for (uint64_t at = 0; at < n; at += NR_CHUNK) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(NR_CHUNK, n - at);
+        NrArgs q{};
+        q.recalls = recalls + at;
+        q.kind = kind;
+        q.normalize = normalize;
+        q.count = count ? count + at : nullptr;
+        q.holes = holes ? holes + at * RP_NLHE_MAX_HOLES : nullptr;
+        q.reach = reach ? reach + at * RP_NLHE_MAX_HOLES : nullptr;
+        q.mass = mass ? mass + at * 256u : nullptr;
+        q.seen = seen ? seen + at * 256u : nullptr;
+        q.status = status ? status + at : nullptr;
+        hipLaunchKernelGGL(k_nl_range, dim3(m), dim3(NR_BLOCK), 0, st, h->tab, h->prm, q);
+        HIP_TRY(hipGetLastError());
+    }
+    return RP_OK;
+}
+// device scratch of a host-form range query, freed on every way out
+struct NrStage {
+    unsigned char* base = nullptr;
+    ~NrStage() {
+        if (base) (void)hipFree(base);
+    }
+};
+}  // namespace
+
+extern "C" {
+
+int rp_nlhe_reaches_device(rp_nlhe* h, rp_reach_kind kind, int normalize, uint64_t n, const rp_nlhe_recall* recalls, uint32_t* count,
+                           uint64_t* holes, float* reach, uint8_t* status) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_reaches: NULL handle");
+    if (kind != RP_REACH_OPPONENT && kind != RP_REACH_SIGNALLED) return rp::fail(RP_ERR_INVALID, "rp_nlhe_reaches: unknown reach kind %d", (int)kind);
+    if (n == 0) return RP_OK;
+    if (!recalls || !count || !reach) return rp::fail(RP_ERR_INVALID, "rp_nlhe_reaches: NULL recalls, count or reach with n_recalls > 0");
+    return nr_launch(h, (int)kind, normalize ? 1 : 0, n, recalls, count, holes, reach, nullptr, nullptr, status);
+}
+
+int rp_nlhe_reaches(rp_nlhe* h, rp_reach_kind kind, int normalize, uint64_t n, const rp_nlhe_recall* recalls, uint32_t* count, uint64_t* holes,
+                    float* reach, uint8_t* status) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_reaches: NULL handle");
+    if (kind != RP_REACH_OPPONENT && kind != RP_REACH_SIGNALLED) return rp::fail(RP_ERR_INVALID, "rp_nlhe_reaches: unknown reach kind %d", (int)kind);
+    if (n == 0) return RP_OK;
+    if (!recalls || !count || !reach) return rp::fail(RP_ERR_INVALID, "rp_nlhe_reaches: NULL recalls, count or reach with n_recalls > 0");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    // holes | recalls (8-byte aligned) | reach | count | status
+    const size_t b_holes = holes ? n * RP_NLHE_MAX_HOLES * 8 : 0, o_rec = b_holes, o_reach = o_rec + n * sizeof(rp_nlhe_recall),
+                 o_count = o_reach + n * RP_NLHE_MAX_HOLES * 4, o_status = o_count + n * 4;
+    NrStage s;
+    HIP_TRY(hipMalloc(&s.base, o_status + n));
+    rp_nlhe_recall* d_rec = reinterpret_cast<rp_nlhe_recall*>(s.base + o_rec);
+    uint64_t* d_holes = holes ? reinterpret_cast<uint64_t*>(s.base) : nullptr;
+    float* d_reach = reinterpret_cast<float*>(s.base + o_reach);
+    uint32_t* d_count = reinterpret_cast<uint32_t*>(s.base + o_count);
+    uint8_t* d_status = s.base + o_status;
+    HIP_TRY(hipMemcpyAsync(d_rec, recalls, n * sizeof(rp_nlhe_recall), hipMemcpyHostToDevice, st));
+    int rc = nr_launch(h, (int)kind, normalize ? 1 : 0, n, d_rec, d_count, d_holes, d_reach, nullptr, nullptr, d_status);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(reach, d_reach, n * RP_NLHE_MAX_HOLES * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(count, d_count, n * 4, hipMemcpyDeviceToHost, st));
+    if (holes) HIP_TRY(hipMemcpyAsync(holes, d_holes, b_holes, hipMemcpyDeviceToHost, st));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RP_OK;
+}
+
+int rp_nlhe_opponent_range_device(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, float* mass, uint8_t* seen, uint8_t* status) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_opponent_range: NULL handle");
+    if (n == 0) return RP_OK;
+    if (!recalls || !mass || !seen) return rp::fail(RP_ERR_INVALID, "rp_nlhe_opponent_range: NULL recalls, mass or seen with n_recalls > 0");
+    return nr_launch(h, (int)RP_REACH_OPPONENT, 0, n, recalls, nullptr, nullptr, nullptr, mass, seen, status);
+}
+
+int rp_nlhe_opponent_range(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, float* mass, uint8_t* seen, uint8_t* status) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_opponent_range: NULL handle");
+    if (n == 0) return RP_OK;
+    if (!recalls || !mass || !seen) return rp::fail(RP_ERR_INVALID, "rp_nlhe_opponent_range: NULL recalls, mass or seen with n_recalls > 0");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    const size_t o_mass = n * sizeof(rp_nlhe_recall), o_seen = o_mass + n * 256u * 4, o_status = o_seen + n * 256u;
+    NrStage s;
+    HIP_TRY(hipMalloc(&s.base, o_status + n));
+    rp_nlhe_recall* d_rec = reinterpret_cast<rp_nlhe_recall*>(s.base);
+    float* d_mass = reinterpret_cast<float*>(s.base + o_mass);
+    HIP_TRY(hipMemcpyAsync(d_rec, recalls, n * sizeof(rp_nlhe_recall), hipMemcpyHostToDevice, st));
+    int rc = nr_launch(h, (int)RP_REACH_OPPONENT, 0, n, d_rec, nullptr, nullptr, nullptr, d_mass, s.base + o_seen, s.base + o_status);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(mass, d_mass, n * 256u * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(seen, s.base + o_seen, n * 256u, hipMemcpyDeviceToHost, st));
+    if (status) HIP_TRY(hipMemcpyAsync(status, s.base + o_status, n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return RP_OK;
 }

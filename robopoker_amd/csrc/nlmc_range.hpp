@@ -1,0 +1,289 @@
+// nlmc_range.hpp — ranges from the NLHE blueprint: the reach of every hole one seat could hold, given what the other seat has seen
+// (rp_nlhe_reaches), and its projection onto abstraction buckets (rp_nlhe_opponent_range).  Read-only, like nlmc_query.hpp.
+//
+// Reference: Nlhe::reach / opponent_reaches / opponent_range / opponent_observations / signalled_observations / signalled_reaches /
+// normalize (nlhe/src/solver.rs:137-260) over CfrEncoder::replay (mccfr/src/strategy/encoder.rs:72-84), NlheGame::apply
+// (nlhe/src/game.rs:50-70), NlheEncoder::resume (nlhe/src/encoder.rs:59-67), NlheInfo::from((Path, Abstraction, Path))
+// (nlhe/src/info.rs:125-139), Path::from_iter (kicker/src/path.rs:169-181), Posterior::add (mccfr/src/strategy/posterior.rs:47-50).
+// The rules are stated in include/rp_mi355x.h above rp_nlhe_reaches.
+//
+// The factorisation.  The reference replays one perfect-information game per candidate hole.  With the board cards given, nothing
+// PUBLIC in that replay depends on the candidate: turns, chips, the 12-edge path, `past` and `choices` of every node are the same
+// for all of them, and the only thing that differs is the bucket of (candidate, board of the node's street) — at most four
+// values.  So one workgroup answers one recall in three phases:
+//   A  lane 0 validates the recall and replays it ONCE with the engine (nlhe_engine.hpp), leaving in LDS the list of the subject's
+//      nodes (past, choices, street, slot of the edge taken or NR_NONE), the board of every street and the cards still free;
+//   B  the lanes stride over the candidates.  Candidate j is the j-th pair of free cards by (high card, low card), which is
+//      HandIterator's order (ascending mask) with the taken cards already left out: no compaction pass.  Per candidate: one
+//      nl_bucket per street that has a subject node, then per node the home slot and the row's weights loaded together, nlq_find,
+//      the averaged fold over all nch slots, ONE divide (the slot of the edge taken) and the multiply;
+//   C  reaches: the total is one lane's f32 fold in candidate order, then every lane divides its own entries;
+//      range:   lane b owns bucket b and scans (bucket, reach) of all candidates in order — every lane reads the same LDS address
+//               in the same iteration (a broadcast), and each sum is the reference's left fold.
+// No atomic and no store touches the table; nlq_find runs divergent and holds no wave collective.
+#ifndef RP_NLMC_RANGE_HPP
+#define RP_NLMC_RANGE_HPP
+
+#include "nlmc_query.hpp"
+
+namespace rp {
+
+#define NR_BLOCK 256u
+#define NR_NONE 0xffu  // the edge taken is not among the node's choices: factor 0
+static_assert(RP_NLHE_MAX_HOLES == 52u * 51u / 2u, "two cards of 52");
+static_assert(sizeof(rp_nlhe_recall) == 88, "rp_nlhe_recall is 88 bytes (INTEGRATION.md mirrors it)");
+
+struct NrArgs {
+    const rp_nlhe_recall* recalls;
+    int kind, normalize;
+    // reaches (mass == NULL): count [n], holes [n][1326] (may be NULL), reach [n][1326]
+    uint32_t* count;
+    uint64_t* holes;
+    float* reach;
+    // range (mass != NULL): mass [n][256], seen [n][256]
+    float* mass;
+    uint8_t* seen;
+    uint8_t* status;  // may be NULL
+};
+
+struct NrNode {
+    uint64_t past, choices;
+    uint8_t street, slot, nch, pad;
+};
+
+// Phase A: validation and the public replay.  Returns the status; on RP_RECALL_OK the node list, boards and free cards are set.
+struct NrPublic {
+    NrNode node[RP_NLHE_MAX_HISTORY];
+    uint64_t board[4];   // the board a node of street s sees: draws[0 .. s)
+    uint64_t head;       // the board the candidates are disjoint from, and the range's buckets are taken on
+    uint32_t n_nodes, streets, head_street, n_free, count, status, lookup_miss;
+    float total;
+    uint8_t free_card[52];
+};
+
+__device__ __forceinline__ uint32_t nr_replay(const rp_nlhe_recall& rc, int kind, NrPublic& pub) {
+    if (rc.n_edges > RP_NLHE_MAX_HISTORY) return RP_RECALL_LENGTH;
+    if (rc.pov > 1u || rc.dealer > 1u || rc.reserved != 0u) return RP_RECALL_SEAT;
+    const bool std_stacks = rc.stacks[0] == 0 && rc.stacks[1] == 0;
+    if (!std_stacks && (rc.stacks[0] <= 0 || rc.stacks[1] <= 0)) return RP_RECALL_SEAT;
+    if ((rc.hole & ~HAND_MASK) != 0 || __popcll(rc.hole) != 2) return RP_RECALL_CARDS;
+    uint64_t gone = rc.hole;
+    for (uint32_t s = 0; s < 3u; ++s) {
+        const uint64_t d = rc.draws[s];
+        if (d == 0) continue;
+        if ((d & ~HAND_MASK) != 0 || __popcll(d) != (s == 0 ? 3 : 1) || (d & gone) != 0) return RP_RECALL_CARDS;
+        if (s > 0 && rc.draws[s - 1] == 0) return RP_RECALL_CARDS;  // a street without the one before it
+        gone |= d;
+    }
+    uint32_t n_draw_edges = 0;
+    for (uint32_t i = 0; i < rc.n_edges; ++i) {
+        const uint32_t e = rc.edges[i];
+        if (e < NE_DRAW || e >= NE_RAISE0 + 10u) return RP_RECALL_EDGE;
+        n_draw_edges += e == NE_DRAW ? 1u : 0u;
+    }
+    const int subject = kind == (int)RP_REACH_OPPONENT ? 1 - (int)rc.pov : (int)rc.pov;
+
+    // Game::from_start(dealer, stacks) (kicker game.rs:80-85); the seats hold no cards: nothing public depends on them, and the
+    // recall's own cards were checked against each other above
+    G2 g;
+    g.n = 2;
+    g.dealer = (int)rc.dealer;
+    g.ticker = 0;
+    g.pot = 0;
+    g.board = 0;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        g.state[i] = NL_BETTING;
+        g.stack[i] = std_stacks ? 200 : (int)rc.stacks[i];
+        g.stake[i] = g.spent[i] = 0;
+        g.cards[i] = 0;
+    }
+    for (int b = 0; b < 2; ++b) g.force_act(NlAction{NA_BLIND, g.to_post(), 0});
+
+    // the first 12 edges as resume() sees them: the trailing choice edges and their aggression
+    uint64_t tail = 0;
+    uint32_t tail_len = 0, aggr = 0, n_nodes = 0, streets = 0;
+    for (uint32_t i = 0; i < rc.n_edges; ++i) {
+        const uint32_t e = rc.edges[i];
+        const int turn = g.turn();
+        if (turn == subject) {
+            const NlView v = nl_view(g);
+            uint64_t choices;
+            const uint32_t nch = nl_choices_path(v, (int)aggr, &choices);
+            uint32_t slot = NR_NONE;
+            for (uint32_t a = 0; a < nch; ++a)
+                if (((choices >> (5u * a)) & 31ull) == e) slot = a;
+            NrNode& nd = pub.node[n_nodes++];
+            nd.past = tail;
+            nd.choices = choices;
+            nd.street = (uint8_t)v.street;
+            nd.slot = (uint8_t)slot;
+            nd.nch = (uint8_t)nch;
+            nd.pad = 0;
+            streets |= 1u << v.street;
+        }
+        if (i < 12u) {  // MAX_PATH_EDGES: Path::from_iter takes the first 12 edges and drops the rest
+            if (e == NE_DRAW) {
+                tail = 0;
+                tail_len = aggr = 0;
+            } else {
+                tail |= (uint64_t)e << (5u * tail_len++);
+                aggr += (e == NE_SHOVE || e >= NE_OPEN0) ? 1u : 0u;
+            }
+        }
+        // NlheGame::apply
+        if (turn == NT_TERMINAL) continue;
+        if (e != NE_DRAW) {
+            while (g.turn() == NT_CHANCE) {  // the pending streets, from the recall's draws where the reference deals at random
+                const uint64_t d = rc.draws[g.street()];
+                if (d == 0) return RP_RECALL_DRAW;
+                g.force_act(NlAction{NA_DRAW, 0, d});
+            }
+            if (g.turn() == NT_TERMINAL) continue;
+        } else {
+            if (g.turn() != NT_CHANCE) continue;
+            const uint64_t d = rc.draws[g.street()];
+            if (d == 0) return RP_RECALL_DRAW;
+            g.force_act(NlAction{NA_DRAW, 0, d});
+            continue;
+        }
+        const NlAction a = nl_action_v(nl_view(g), e);
+        if (!g.allowed(a)) return RP_RECALL_ILLEGAL;
+        g.force_act(a);
+    }
+    // the board: the streets the history's Draw edges dealt, and any the replay dealt on its own
+    const uint32_t dealt = max(min(n_draw_edges, 3u), (uint32_t)g.street());
+    uint64_t b = 0;
+    pub.board[0] = 0;
+    for (uint32_t s = 0; s < 3u; ++s) {
+        if (s < dealt) {
+            if (rc.draws[s] == 0) return RP_RECALL_DRAW;
+            b |= rc.draws[s];
+        }
+        pub.board[s + 1] = b;  // for s >= dealt: never read (no node of that street)
+    }
+    pub.head = pub.board[dealt];
+    pub.head_street = dealt;
+    pub.n_nodes = n_nodes;
+    pub.streets = streets;
+    const uint64_t taken = pub.head | (kind == (int)RP_REACH_OPPONENT ? rc.hole : 0ull);
+    uint32_t n_free = 0;
+    for (uint32_t c = 0; c < 52u; ++c)
+        if (!((taken >> c) & 1ull)) pub.free_card[n_free++] = (uint8_t)c;
+    pub.n_free = n_free;
+    pub.count = n_free * (n_free - 1u) / 2u;
+    return RP_RECALL_OK;
+}
+
+// candidate j -> (hi, lo) with j = hi (hi - 1) / 2 + lo, lo < hi: the pairs of free cards by high card, then low card
+__device__ __forceinline__ void nr_pair(uint32_t j, uint32_t* hi, uint32_t* lo) {
+    uint32_t h = (uint32_t)((1.0f + sqrtf(1.0f + 8.0f * (float)j)) * 0.5f);
+    while (h * (h - 1u) / 2u > j) h -= 1u;
+    while ((h + 1u) * h / 2u <= j) h += 1u;
+    *hi = h;
+    *lo = j - h * (h - 1u) / 2u;
+}
+
+// one factor: averaged_distribution(info).density(edge) for the infoset (nd.past, present, nd.choices) — the fold of
+// policy_distribution<>(RP_DIST_AVERAGED) over all nch slots, and the one quotient that is asked for
+__device__ __forceinline__ float nr_factor(const NlTable& t, const NrNode& nd, uint32_t present) {
+    const uint32_t home = (uint32_t)nl_key_hash(nd.past, nd.choices, present) & t.mask;
+    const uint4* sl = reinterpret_cast<const uint4*>(t.slots + home);
+    const uint4 lo = sl[0], hi = sl[1];
+    // the weights are floats 9..17 of the row: pieces 2..4 hold floats 8..19
+    const float4* rw = reinterpret_cast<const float4*>(t.rows + (size_t)home * 4u * NLMC_A);
+    float4 p0 = rw[2], p1 = rw[3], p2 = rw[4];
+    uint32_t row;
+    const bool found = nlq_find(t, nd.past, nd.choices, present, home, lo, hi, &row);
+    if (found && row != home) {
+        const float4* rr = reinterpret_cast<const float4*>(t.rows + (size_t)row * 4u * NLMC_A);
+        p0 = rr[2], p1 = rr[3], p2 = rr[4];
+    }
+    const float w[NLMC_A] = {p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w, p2.x, p2.y};
+    float sum = 0.0f, mine = 0.0f;
+#pragma unroll
+    for (uint32_t a = 0; a < NLMC_A; ++a) {
+        const float v = rp_maxf(found ? w[a] : 0.0f, RP_EPSILON);
+        if (a < nd.nch) sum += v;
+        mine = a == nd.slot ? v : mine;
+    }
+    return nd.slot == NR_NONE ? 0.0f : mine / sum;
+}
+
+__global__ __launch_bounds__(NR_BLOCK) void k_nl_range(NlTable t, NlParams p, NrArgs q) {
+    __shared__ NrPublic pub;
+    __shared__ float s_reach[RP_NLHE_MAX_HOLES];
+    __shared__ uint8_t s_bucket[RP_NLHE_MAX_HOLES];
+    const uint32_t r = blockIdx.x, tid = threadIdx.x;
+    const bool range = q.mass != nullptr;
+
+    if (tid == 0) {
+        pub.status = nr_replay(q.recalls[r], q.kind, pub);
+        pub.lookup_miss = 0;
+    }
+    __syncthreads();
+    uint32_t err = 0;
+    if (pub.status == RP_RECALL_OK) {
+        const uint32_t count = pub.count, streets = pub.streets, n_nodes = pub.n_nodes;
+        for (uint32_t j = tid; j < count; j += NR_BLOCK) {
+            uint32_t hi, lo;
+            nr_pair(j, &hi, &lo);
+            const uint64_t hole = (1ull << pub.free_card[hi]) | (1ull << pub.free_card[lo]);
+            uint32_t bucket[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                if ((streets >> s) & 1u) bucket[s] = nl_bucket(p, s, hole, pub.board[s], &err);
+            float reach = 1.0f;
+            for (uint32_t k = 0; k < n_nodes; ++k) {
+                const NrNode nd = pub.node[k];
+                const uint32_t present = nd.street == 0 ? bucket[0] : (nd.street == 1 ? bucket[1] : (nd.street == 2 ? bucket[2] : bucket[3]));
+                reach *= nr_factor(t, nd, present);
+            }
+            s_reach[j] = reach;
+            if (range) s_bucket[j] = (uint8_t)nl_bucket(p, (int)pub.head_street, hole, pub.head, &err);
+            else if (q.holes) q.holes[(size_t)r * RP_NLHE_MAX_HOLES + j] = hole;
+        }
+    }
+    // a hole the encoder's tables do not know (the reference panics): the recall is answered as malformed.  Every lane that saw
+    // one stores the same value; the barrier orders the stores before the read
+    if (err) pub.lookup_miss = 1;
+    __syncthreads();
+    const uint32_t status = pub.status != RP_RECALL_OK ? pub.status : (pub.lookup_miss ? (uint32_t)RP_RECALL_LOOKUP : (uint32_t)RP_RECALL_OK);
+    const uint32_t count = status == RP_RECALL_OK ? pub.count : 0u;
+    if (tid == 0 && q.status) q.status[r] = (uint8_t)status;
+
+    if (range) {
+        // lane b = bucket b: Posterior::add in candidate order
+        float m = 0.0f;
+        uint32_t any = 0;
+        for (uint32_t j = 0; j < count; ++j) {
+            const bool mine = s_bucket[j] == tid;
+            m = mine ? m + s_reach[j] : m;
+            any |= mine ? 1u : 0u;
+        }
+        q.mass[(size_t)r * 256u + tid] = m;
+        q.seen[(size_t)r * 256u + tid] = (uint8_t)any;
+        return;
+    }
+    if (q.normalize) {
+        if (tid == 0) {
+            float total = 0.0f;
+            for (uint32_t j = 0; j < count; ++j) total += s_reach[j];
+            pub.total = total;
+        }
+        __syncthreads();
+    }
+    const float total = q.normalize ? pub.total : 0.0f;
+    if (tid == 0) q.count[r] = count;
+    for (uint32_t j = tid; j < RP_NLHE_MAX_HOLES; j += NR_BLOCK) {
+        float v = j < count ? s_reach[j] : 0.0f;
+        if (j < count && total != 0.0f) v = v / total;  // a zero total (either sign) leaves the stream untouched
+        q.reach[(size_t)r * RP_NLHE_MAX_HOLES + j] = v;
+        if (q.holes && j >= count) q.holes[(size_t)r * RP_NLHE_MAX_HOLES + j] = 0ull;
+    }
+}
+static_assert(NR_BLOCK == 256u, "k_nl_range: one lane per bucket of the range");
+
+}  // namespace rp
+
+#endif

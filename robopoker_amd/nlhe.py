@@ -13,8 +13,41 @@ A = 9  # widest NLHE infoset (pokerkit/src/lib.rs:130-133)
 ENC_DTYPE = np.dtype([("weight", "<f4"), ("regret", "<f4"), ("payoff", "<f4"), ("visits", "<u4")])
 
 
+MAX_HISTORY, MAX_HOLES, BUCKETS = _lib.RP_NLHE_MAX_HISTORY, _lib.RP_NLHE_MAX_HOLES, 256
+RECALL_DTYPE = np.dtype([("hole", "<u8"), ("draws", "<u8", (3,)), ("stacks", "<i2", (2,)), ("pov", "u1"), ("dealer", "u1"),
+                         ("n_edges", "u1"), ("reserved", "u1"), ("edges", "u1", (MAX_HISTORY,))])  # rp_nlhe_recall, 88 bytes
+assert RECALL_DTYPE.itemsize == C.sizeof(_lib.NlheRecall) == 88
+
+
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+class Recall:
+    """What one seat has seen, at edge level: a ``Witness`` (crates/kicker/src/witness.rs:36-44) after ``Recall::history()``.
+    ``hole``: pov's two cards as a mask (bit c = card c); ``draws``: up to three masks (flop, turn, river) in street order;
+    ``edges``: edge codes, Draw edges (1) included; ``stacks`` (0, 0) = the reference's STACK.  Nothing is checked here: a
+    malformed recall is answered with its status by the queries."""
+
+    def __init__(self, pov, hole, draws=(), edges=(), stacks=(0, 0), dealer=0):
+        self.pov, self.hole, self.draws, self.edges, self.stacks, self.dealer = pov, hole, tuple(draws), tuple(edges), tuple(stacks), dealer
+
+    @staticmethod
+    def pack(recalls) -> np.ndarray:
+        """-> RECALL_DTYPE[n]; a history longer than the cap keeps its first 48 edges and its true length clipped to 255 (status LENGTH)"""
+        if isinstance(recalls, np.ndarray) and recalls.dtype == RECALL_DTYPE:
+            return np.ascontiguousarray(recalls)
+        if isinstance(recalls, Recall):
+            recalls = [recalls]
+        out = np.zeros(len(recalls), RECALL_DTYPE)
+        for i, r in enumerate(recalls):
+            out[i]["hole"] = r.hole
+            out[i]["draws"][: len(r.draws)] = r.draws
+            out[i]["stacks"] = r.stacks
+            out[i]["pov"], out[i]["dealer"], out[i]["n_edges"] = r.pov, r.dealer, min(len(r.edges), 255)
+            k = min(len(r.edges), MAX_HISTORY)
+            out[i]["edges"][:k] = r.edges[:k]
+        return out
 
 
 class NlheSolver:
@@ -228,6 +261,69 @@ class NlheSolver:
         enc, nact, found = np.zeros((n, A), dtype=ENC_DTYPE), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
         _lib.check(self._lib.rp_nlhe_memory(self._h, n, _p(past), _p(present), _p(choices), _p(enc), _p(nact), _p(found)))
         return enc, nact, found.view(np.bool_)
+
+    # ---- ranges (include/rp_mi355x.h rp_nlhe_reaches / rp_nlhe_opponent_range): the blueprint's reach of every hole a seat could hold ----
+    def reaches_raw(self, recalls, kind="opponent", normalize=False):
+        """the untrimmed arrays of rp_nlhe_reaches: dict(count uint32[n], holes uint64[n,1326], reach float32[n,1326], status uint8[n])"""
+        rec = Recall.pack(recalls)
+        n = rec.size
+        out = dict(count=np.zeros(n, np.uint32), holes=np.zeros((n, MAX_HOLES), np.uint64), reach=np.zeros((n, MAX_HOLES), np.float32),
+                   status=np.zeros(n, np.uint8))
+        _lib.check(self._lib.rp_nlhe_reaches(self._h, _lib.REACH[kind], 1 if normalize else 0, n, _p(rec), _p(out["count"]), _p(out["holes"]),
+                                             _p(out["reach"]), _p(out["status"])))
+        return out
+
+    def reaches(self, recalls, kind="opponent", normalize=False):
+        """``opponent_reaches`` / ``signalled_reaches`` (nlhe/src/solver.rs:162-169,227-240) for n recalls: a list of
+        (holes uint64[count], reach float32[count], status) in ``HandIterator`` order; status != 0 (malformed recall): empty arrays."""
+        raw = self.reaches_raw(recalls, kind, normalize)
+        return [(raw["holes"][i, :c].copy(), raw["reach"][i, :c].copy(), int(raw["status"][i])) for i, c in enumerate(raw["count"])]
+
+    def opponent_observations(self, recalls):
+        """``Nlhe::opponent_observations`` (solver.rs:206-208): the villain's holes with reaches normalised to sum to 1"""
+        return self.reaches(recalls, "opponent", True)
+
+    def signalled_observations(self, recalls):
+        """``Nlhe::signalled_observations`` (solver.rs:221-223): what hero's own line says about hero's hole"""
+        return self.reaches(recalls, "signalled", True)
+
+    def opponent_range(self, recalls):
+        """``Nlhe::opponent_range`` (solver.rs:192-197), the Posterior over abstraction buckets of the board's street:
+        (mass float32[n,256], seen bool[n,256], status uint8[n])"""
+        rec = Recall.pack(recalls)
+        n = rec.size
+        mass, seen, status = np.zeros((n, BUCKETS), np.float32), np.zeros((n, BUCKETS), np.uint8), np.zeros(n, np.uint8)
+        _lib.check(self._lib.rp_nlhe_opponent_range(self._h, n, _p(rec), _p(mass), _p(seen), _p(status)))
+        return mass, seen.view(np.bool_), status
+
+    def reaches_device(self, recalls_dev, kind="opponent", normalize=False):
+        """rp_nlhe_reaches_device: ``recalls_dev`` a device uint8 tensor [n, 88] (``torch.from_numpy(Recall.pack(..).view(np.uint8))``);
+        -> dict of device tensors (count int32[n], holes int64[n,1326], reach float32[n,1326], status uint8[n]), queued on the
+        solver's stream (``sync()`` waits)"""
+        rec = recalls_dev.contiguous()
+        assert rec.is_cuda and rec.element_size() == 1 and rec.numel() % RECALL_DTYPE.itemsize == 0
+        n, d = rec.numel() // RECALL_DTYPE.itemsize, rec.device
+        out = dict(count=torch.empty(n, dtype=torch.int32, device=d), holes=torch.empty((n, MAX_HOLES), dtype=torch.int64, device=d),
+                   reach=torch.empty((n, MAX_HOLES), dtype=torch.float32, device=d), status=torch.empty(n, dtype=torch.uint8, device=d))
+        torch.cuda.current_stream(d).synchronize()
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if n else None
+        _lib.check(self._lib.rp_nlhe_reaches_device(self._h, _lib.REACH[kind], 1 if normalize else 0, n, ptr(rec), ptr(out["count"]),
+                                                    ptr(out["holes"]), ptr(out["reach"]), ptr(out["status"])))
+        self._query_keys = (rec,)  # the queued launch reads them
+        return out
+
+    def opponent_range_device(self, recalls_dev):
+        """rp_nlhe_opponent_range_device: -> device tensors (mass float32[n,256], seen uint8[n,256], status uint8[n])"""
+        rec = recalls_dev.contiguous()
+        assert rec.is_cuda and rec.element_size() == 1 and rec.numel() % RECALL_DTYPE.itemsize == 0
+        n, d = rec.numel() // RECALL_DTYPE.itemsize, rec.device
+        mass = torch.empty((n, BUCKETS), dtype=torch.float32, device=d)
+        seen, status = torch.empty((n, BUCKETS), dtype=torch.uint8, device=d), torch.empty(n, dtype=torch.uint8, device=d)
+        torch.cuda.current_stream(d).synchronize()
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if n else None
+        _lib.check(self._lib.rp_nlhe_opponent_range_device(self._h, n, ptr(rec), ptr(mass), ptr(seen), ptr(status)))
+        self._query_keys = (rec,)
+        return mass, seen, status
 
 
 

@@ -1,0 +1,312 @@
+"""Ranges from the device-resident blueprint: rp_nlhe_reaches (opponent / signalled, raw and normalised) and rp_nlhe_opponent_range,
+host and _device forms, against the naive per-candidate model of tests/nlhe_range_model.py (pinned by
+tests/test_nlhe_range_model.py).  Bit patterns only: there is no tolerance.
+
+One batch mixes every case the replay has: the root, flop histories from either seat, a river history longer than the 12 edges a
+Path keeps, a fold with edges after it, a choice edge at a chance node and a Draw edge at a choice node, a recall none of whose
+infosets has a row, and two malformed recalls between valid ones.  The table has 2^10 slots and holds about half of the ~1 800
+infosets the model asks for (chosen by a hash of the key; never more than 960), which leaves found, absent, off-home-slot and
+all-zero-weight infosets in every recall but the absent one.  Each of these is asserted to occur."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import nlhe_policy_model as PM
+import nlhe_range_model as RM
+import oracle_nlhe as ON
+from robopoker_amd import _lib
+from robopoker_amd.nlhe import A, ENC_DTYPE, MAX_HOLES, NlheSolver, Recall
+
+pytestmark = pytest.mark.gpu
+
+CAP_LOG2 = 10
+SLOTS = 1 << CAP_LOG2
+WEIGHTS = np.array([0.0, 1e-39, 1.0, 1e12], np.float32)  # 1e-39 is subnormal: below RP_EPSILON
+OPEN2, OPEN3, POT, HALF = ON.Open(2), ON.Open(3), ON.RaiseOdds(1, 1), ON.RaiseOdds(1, 2)
+DRAW, FOLD, CHECK, CALL = ON.E_DRAW, ON.E_FOLD, ON.E_CHECK, ON.E_CALL
+
+
+def cards(*cs):
+    return sum(1 << c for c in cs)
+
+
+HOLE, FLOP, TURN, RIVER = cards(51, 50), cards(3, 17, 30), cards(44), cards(9)
+LONG = [OPEN2, POT, CALL, DRAW, CHECK, CHECK, DRAW, CHECK, CHECK, DRAW, CHECK, POT, POT, POT, CALL]  # 15 edges, the river from edge 10 on
+# (name, kind, recall); the absent recall comes first: its keys are never loaded, whoever else asks for them
+CASES = [
+    ("absent", "opponent", Recall(1, cards(0, 1), [cards(20, 21, 22)], [OPEN3, CALL, DRAW, CHECK, CHECK])),
+    ("root", "opponent", Recall(0, HOLE)),
+    ("root", "signalled", Recall(0, HOLE)),
+    ("flop pov 0", "opponent", Recall(0, HOLE, [FLOP], [OPEN2, CALL, DRAW, CHECK, HALF, CALL])),
+    ("bad edge", "opponent", Recall(0, HOLE, [FLOP], [OPEN2, CALL, DRAW, 25])),
+    ("flop pov 1", "opponent", Recall(1, HOLE, [FLOP], [OPEN2, CALL, DRAW, CHECK, HALF, CALL])),
+    ("river", "signalled", Recall(0, HOLE, [FLOP, TURN, RIVER], LONG)),
+    ("hole on the flop", "opponent", Recall(0, cards(3, 50), [FLOP], [OPEN2, CALL, DRAW, CHECK])),
+    ("fold", "opponent", Recall(0, HOLE, [FLOP], [OPEN2, FOLD, CHECK, CALL, DRAW])),
+    ("corners", "signalled", Recall(0, HOLE, [FLOP, TURN], [OPEN2, CALL, CHECK, DRAW, CHECK, DRAW, CHECK], stacks=(150, 90))),
+    ("corners", "opponent", Recall(0, HOLE, [FLOP, TURN], [OPEN2, CALL, CHECK, DRAW, CHECK, DRAW, CHECK], stacks=(150, 90))),
+]
+STATUS = {"bad edge": RM.EDGE, "hole on the flop": RM.CARDS}
+
+
+class Rows:
+    """the blueprint the model reads, decided key by key as the model asks: about half of the keys get a row of corner weights
+    (garbage beyond the infoset's actions), the others — and every key the absent recall asked for — have none"""
+
+    def __init__(self):
+        self.loaded, self.never, self.forbid, self.n_rows = {}, set(), False, 0
+
+    def get(self, key):
+        if self.forbid:
+            self.never.add(key)
+        if key in self.never:
+            return None
+        if key not in self.loaded:
+            h = PM.key_hash(key[0] ^ 0x5EED, key[2], key[1])
+            w = None
+            if h % 2 == 0 and self.n_rows < SLOTS - 64:
+                self.n_rows += 1
+                w = WEIGHTS[[(h >> (8 + 2 * a)) & 3 for a in range(A)]].copy()
+                if (h >> 40) % 8 == 0:
+                    w[:] = 0.0  # a row whose weights are all zero: the same uniform policy as an absent one
+                w[PM.nch(key[2]):] = 7.0
+            self.loaded[key] = w
+        return self.loaded[key]
+
+    def table(self):
+        keys = [k for k, w in self.loaded.items() if w is not None]
+        enc = np.zeros((len(keys), A), dtype=ENC_DTYPE)
+        enc["weight"] = np.stack([self.loaded[k] for k in keys])
+        enc["regret"], enc["payoff"], enc["visits"] = -3.0, 2.5, 11
+        return (np.array([k[0] for k in keys], np.uint64), np.array([k[1] for k in keys], np.uint32),
+                np.array([k[2] for k in keys], np.uint64), enc)
+
+
+class Model:
+    """the model's answers for CASES, computed once per module"""
+
+    def __init__(self):
+        self.rows, self.used, self.raw = Rows(), {}, []
+        for i, (name, kind, r) in enumerate(CASES):
+            self.rows.forbid = name == "absent"
+            self.used[i] = []
+            self.raw.append(RM.reaches(r, kind, self.rows, used=self.used[i]))
+        self.rows.forbid = False
+        self.normed = [(st, holes, RM.normalized(reach)) for st, holes, reach in self.raw]
+        self.range = [RM.opponent_range(r, self.rows, stream=self.raw[i]) if kind == "opponent" else None for i, (_, kind, r) in enumerate(CASES)]
+        self.table = self.rows.table()
+
+    def solver(self, rows=None):
+        """rows: load the first `rows` infosets only (room for a training step in the 1 024 slots)"""
+        s = NlheSolver(cap_log2=CAP_LOG2, batch=1, seed=1)
+        s.load(*(x[:rows] for x in self.table), epoch=3)
+        return s
+
+
+@pytest.fixture(scope="module")
+def model():
+    return Model()
+
+
+def bits(x):
+    return np.ascontiguousarray(x).view(np.uint32)
+
+
+def placement(past, present, choices):
+    """slot and home slot of every key after rp_nlhe_import into an empty table (insertion in order, linear probing)"""
+    taken, slot, home = set(), [], []
+    for p, q, c in zip(past, present, choices):
+        h = PM.key_hash(p, c, q) & (SLOTS - 1)
+        s = h
+        while s in taken:
+            s = (s + 1) & (SLOTS - 1)
+        taken.add(s)
+        slot.append(s)
+        home.append(h)
+    return np.array(slot), np.array(home)
+
+
+def as_map(past, present, choices, enc):
+    return {(int(p), int(q), int(c)): enc[i].tobytes() for i, (p, q, c) in enumerate(zip(past, present, choices))}
+
+
+def by_kind(kind):
+    return [i for i, c in enumerate(CASES) if c[1] == kind]
+
+
+def check_stream(got, want, what):
+    """got: one recall's (count, holes[1326], reach[1326], status); want: the model's (status, holes, reach)"""
+    count, holes, reach, status = got
+    assert status == want[0] and count == want[1].size, what
+    assert np.array_equal(holes[:count], want[1]) and not holes[count:].any(), what
+    assert np.array_equal(bits(reach[:count]), bits(want[2])) and not bits(reach[count:]).any(), what
+
+
+def test_every_case_occurs(model):
+    m = model
+    past, present, choices, enc = m.table
+    assert SLOTS // 2 < past.size < SLOTS
+    slot, home = placement(past, present, choices)
+    off_home = {(int(p), int(q), int(c)) for p, q, c, s, h in zip(past, present, choices, slot, home) if s != h}
+    everything = [u for i in m.used for u in m.used[i]]
+    assert any(found and key in off_home for key, found, _ in everything), "no factor is read off its home slot"
+    assert any(found for _, found, _ in everything) and any(not found for _, found, _ in everything)
+    assert any(found and not m.rows.loaded[key][: PM.nch(key[2])].any() for key, found, _ in everything), "no all-zero row"
+    names = [c[0] for c in CASES]
+    absent = m.used[names.index("absent")]
+    assert absent and not any(found for _, found, _ in absent)
+    # uniform factors: two nodes of the absent recall's subject, call among 5 then check among 6 choices of zero weight
+    assert len({int(b) for b in bits(m.raw[names.index("absent")][2])}) <= 2
+    corners = m.used[[i for i, c in enumerate(CASES) if c[:2] == ("corners", "signalled")][0]]
+    assert any(not live for _, _, live in corners) and not m.raw[[i for i, c in enumerate(CASES) if c[:2] == ("corners", "signalled")][0]][2].any()
+    # the 12-edge rule changes a key: at edge 13 of the river history the model's `past` is not the river's edges before it
+    river = CASES[names.index("river")][2]
+    key = m.used[names.index("river")][5][0]  # seat 0's sixth and last node of the first candidate
+    assert ON.path_unpack(key[0]) == list(river.edges[10:12]) != list(river.edges[10:13])
+    for i, (name, _, _) in enumerate(CASES):
+        assert m.raw[i][0] == STATUS.get(name, RM.OK), name
+    assert m.raw[names.index("fold")][1].size == 1081  # the Draw edge after the fold still puts the flop on the board
+    assert [m.raw[i][1].size for i in (1, 2)] == [1225, 1326]
+
+
+def test_reaches_host_forms(gpu, model):
+    m = model
+    s = m.solver()
+    before = (s.export(), s.epoch, s.counters())
+    for kind in ("opponent", "signalled"):
+        pick = by_kind(kind)
+        raw = s.reaches_raw([CASES[i][2] for i in pick], kind)
+        for j, i in enumerate(pick):
+            check_stream((raw["count"][j], raw["holes"][j], raw["reach"][j], raw["status"][j]), m.raw[i], CASES[i][:2])
+        trimmed = s.reaches([CASES[i][2] for i in pick], kind)
+        assert all(h.size == r.size == m.raw[i][1].size and st == m.raw[i][0] for (h, r, st), i in zip(trimmed, pick))
+    # normalised: a stream with mass, and the all-zero stream that is left untouched
+    for i, want in enumerate(m.normed):
+        if CASES[i][0] in ("corners", "flop pov 0", "river"):
+            fn = s.opponent_observations if CASES[i][1] == "opponent" else s.signalled_observations
+            holes, reach, status = fn(CASES[i][2])[0]
+            assert status == RM.OK and np.array_equal(holes, want[1]) and np.array_equal(bits(reach), bits(want[2])), CASES[i][:2]
+    zero = [w for w, c in zip(m.normed, CASES) if c[:2] == ("corners", "signalled")][0]
+    assert zero[2].size and not bits(zero[2]).any()
+    # read-only
+    after = (s.export(), s.epoch, s.counters())
+    assert all(np.array_equal(x, y) for x, y in zip(before[0][:3], after[0][:3])) and before[0][3].tobytes() == after[0][3].tobytes()
+    assert before[1:] == after[1:] == (3, (0, 0, m.table[0].size))
+
+
+def test_opponent_range(gpu, model):
+    m = model
+    s = m.solver()
+    pick = by_kind("opponent")
+    mass, seen, status = s.opponent_range([CASES[i][2] for i in pick])
+    for j, i in enumerate(pick):
+        want = m.range[i]
+        assert status[j] == want[0], CASES[i][0]
+        assert np.array_equal(bits(mass[j]), bits(want[1])) and np.array_equal(seen[j], want[2]), CASES[i][0]
+    ok = [j for j, i in enumerate(pick) if m.range[i][0] == RM.OK]
+    assert all(seen[j].any() for j in ok) and not any(seen[j].any() or mass[j].any() for j in range(len(pick)) if j not in ok)
+    assert 0 < seen[pick.index(1)].sum() <= 169 and not seen[pick.index(1)][169:].any()  # the root: preflop buckets of the hash encoder
+
+
+def test_device_forms_equal_the_host_forms(gpu, model):
+    m = model
+    s = m.solver()
+    for kind, normalize in (("opponent", False), ("signalled", True)):
+        recalls = [CASES[i][2] for i in by_kind(kind)]
+        host = s.reaches_raw(recalls, kind, normalize)
+        dev_in = torch.from_numpy(Recall.pack(recalls).view(np.uint8).copy()).to("cuda")
+        dev = s.reaches_device(dev_in, kind, normalize)
+        s.sync()
+        assert all(t.is_cuda for t in dev.values())
+        assert np.array_equal(dev["count"].cpu().numpy().view(np.uint32), host["count"])
+        assert np.array_equal(dev["holes"].cpu().numpy().view(np.uint64), host["holes"])
+        assert np.array_equal(bits(dev["reach"].cpu().numpy()), bits(host["reach"]))
+        assert np.array_equal(dev["status"].cpu().numpy(), host["status"])
+    recalls = [CASES[i][2] for i in by_kind("opponent")]
+    host = s.opponent_range(recalls)
+    mass, seen, status = s.opponent_range_device(torch.from_numpy(Recall.pack(recalls).view(np.uint8).copy()).to("cuda"))
+    s.sync()
+    assert np.array_equal(bits(mass.cpu().numpy()), bits(host[0])) and np.array_equal(seen.cpu().numpy().view(np.bool_), host[1])
+    assert np.array_equal(status.cpu().numpy(), host[2])
+
+
+def test_a_queried_table_steps_like_one_never_queried(gpu, model):
+    m = model
+    s, twin = m.solver(rows=256), m.solver(rows=256)
+    recalls = [c[2] for c in CASES]
+    s.reaches_raw(recalls, "opponent")
+    s.reaches_raw(recalls, "signalled", True)
+    s.opponent_range(recalls)
+    s.step()
+    twin.step()
+    # as maps by key: a step inserts from many lanes at once, so which slot a new infoset lands in differs from run to run
+    am, bm = as_map(*s.export()), as_map(*twin.export())
+    assert am.keys() == bm.keys() and len(am) > 256 and all(am[k] == bm[k] for k in am)
+    assert (s.epoch, s.counters()) == (twin.epoch, twin.counters()) and s.epoch == 4
+
+
+def hash_buckets(obs, street):
+    """the hash encoder's bucket index of canonical observations (nl_bucket, encoder 0) for a whole isomorphism list"""
+    m = np.uint64
+    z = obs.astype(np.int64).view(np.uint64) ^ m((0x51ED270B5 * (street + 1)) & PM.M64)
+    z ^= z >> m(30)
+    z *= m(0xBF58476D1CE4E5B9)
+    z ^= z >> m(27)
+    z *= m(0x94D049BB133111EB)
+    z ^= z >> m(31)
+    return (z % m((169, 256, 256, 101)[street])).astype(np.uint8)
+
+
+def test_lookup_table_encoder(gpu, model):
+    # the encoder over rp_lookup tables: with the hash encoder's buckets in them it answers as the hash encoder does; the turn and river
+    # tables here hold the isomorphisms of the first 16 pockets only, so a recall that needs a turn bucket meets a hole they do not know
+    from robopoker_amd import deuce
+
+    m = model
+    tables = []
+    for street, (name, pockets) in enumerate((("pref", 1326), ("flop", 1326), ("turn", 16), ("rive", 16))):
+        obs = deuce.isomorphisms(name, 0, pockets)
+        tables.append(deuce.Lookup(name, obs, torch.from_numpy(hash_buckets(obs.cpu().numpy(), street)).to("cuda")))
+    s = NlheSolver(cap_log2=CAP_LOG2, batch=1, seed=1, tables=tables)
+    s.load(*m.table, epoch=3)
+    names = [c[0] for c in CASES]
+    pick = [names.index("root"), names.index("flop pov 0"), names.index("flop pov 1"), [i for i, c in enumerate(CASES) if c[:2] == ("corners", "opponent")][0]]
+    raw = s.reaches_raw([CASES[i][2] for i in pick], "opponent")
+    mass, seen, status = s.opponent_range([CASES[i][2] for i in pick])
+    for j, i in enumerate(pick[:3]):
+        check_stream((raw["count"][j], raw["holes"][j], raw["reach"][j], raw["status"][j]), m.raw[i], CASES[i][:2])
+        assert status[j] == RM.OK and np.array_equal(bits(mass[j]), bits(m.range[i][1])) and np.array_equal(seen[j], m.range[i][2])
+    assert raw["status"][3] == status[3] == RM.LOOKUP and raw["count"][3] == 0
+    assert not raw["reach"][3].any() and not raw["holes"][3].any() and not mass[3].any() and not seen[3].any()
+    s.close()
+    for t in tables:
+        t.close()
+
+
+def test_arguments(gpu):
+    lib = _lib.load()
+    s = NlheSolver(cap_log2=CAP_LOG2, batch=4, seed=2)
+    rec = Recall.pack([Recall(0, HOLE)])
+    count, reach = np.zeros(1, np.uint32), np.zeros((1, MAX_HOLES), np.float32)
+    mass, seen = np.zeros((1, 256), np.float32), np.zeros((1, 256), np.uint8)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    assert lib.rp_nlhe_reaches(s._h, 2, 0, 1, p(rec), p(count), None, p(reach), None) == _lib.RP_ERR_INVALID
+    assert b"kind" in lib.rp_last_error()
+    assert lib.rp_nlhe_reaches(s._h, 0, 0, 1, None, p(count), None, p(reach), None) == _lib.RP_ERR_INVALID
+    assert lib.rp_nlhe_reaches(s._h, 0, 0, 1, p(rec), p(count), None, None, None) == _lib.RP_ERR_INVALID
+    assert lib.rp_nlhe_opponent_range(s._h, 1, p(rec), None, p(seen), None) == _lib.RP_ERR_INVALID
+    for fn in (lib.rp_nlhe_reaches, lib.rp_nlhe_reaches_device):
+        assert fn(s._h, 0, 0, 0, None, None, None, None, None) == _lib.RP_OK
+    for fn in (lib.rp_nlhe_opponent_range, lib.rp_nlhe_opponent_range_device):
+        assert fn(s._h, 0, None, None, None, None) == _lib.RP_OK
+    # holes and status may be NULL; an empty table answers the root with ones
+    assert lib.rp_nlhe_reaches(s._h, 0, 0, 1, p(rec), p(count), None, p(reach), None) == _lib.RP_OK
+    assert count[0] == 1225 and np.array_equal(bits(reach[0, :1225]), bits(np.ones(1225, np.float32))) and not reach[0, 1225:].any()
+    assert lib.rp_nlhe_opponent_range(s._h, 1, p(rec), p(mass), p(seen), None) == _lib.RP_OK and 0 < seen.sum() <= 169
+    # a history longer than the cap is a status, not an error; the handle still steps
+    long = Recall(0, HOLE, [FLOP], [CHECK] * 60)
+    assert s.reaches(long)[0][2] == RM.LENGTH and s.opponent_range(long)[2][0] == RM.LENGTH
+    s.step()
+    assert s.epoch == 1 and s.counters()[2] > 0
