@@ -9,6 +9,14 @@
 // over it, every lane executes the same instruction stream (no divergence, no LDS, no stack), all per-node state sits in
 // registers with static indices, and the loads of independent sub-trees overlap.
 //
+// A lane does not evaluate the whole skeleton, though.  What can never be live in the same tree is evaluated once (the
+// packed-row variant; "mutually exclusive sub-trees" below): two sub-trees of the same shape below two edges of an OPPONENT
+// node — the opponent samples one action — share one instance, built and valued for whichever the opponent's pick selects
+// (Leduc: round 2 after check-check with round 2 after check-raise-call for walker 0, with round 2 after raise-call for
+// walker 1: 29 of the 38 nodes are evaluated), and the two terminal children of an opponent node (fold / call) share one
+// division.  Dead nodes are still masked out of the sums, and every live node sees the operations it saw unmerged, in the same
+// order: the tables stay bit-identical (tests/test_gpu_mccfr_exclusive.py).  The child-record variant merges nothing.
+//
 // Same arithmetic as k_traverse_lds, operation for operation (TreeBuilder::build builder.rs:74-87,141-161 in pop-last
 // order = pre-order with children in DESCENDING edge order; CfrFlow::dfs / recursed_value / ancestor_reach
 // flow.rs:64-87,166-216): the Decisions are bit-identical (tests/test_gpu_mccfr.py::test_static_skeleton_equals_generic).
@@ -189,12 +197,118 @@ constexpr bool sk_child_terminal(int s, int e) {
     return false;
 }
 
+// ---- mutually exclusive sub-trees ---------------------------------------------------------------------------------------
+// An opponent node samples exactly ONE action under every sampling scheme (pruning only removes further nodes), so two
+// sub-trees whose lowest common ancestor is an opponent node of this walker are never live in the same tree.  Where two such
+// sub-trees hang below chance nodes lo < hi, have the same shape (kinds, parents, edges) and the same row layout, the packed-row
+// traversal evaluates ONE instance of them, at hi's place, for whichever the opponent's pick at the common ancestor selects:
+// lo keeps only what its parent's row says about it (state id, fan-out) and its own liveness.
+struct ExclPair {
+    int lo = -1, hi = -1;  // the two chance nodes; -1: this skeleton / walker has no such pair
+    int anc = -1;          // their lowest common ancestor, an opponent node
+    int edge_lo = 0;       // anc's edge towards lo: pick[anc] == edge_lo selects lo, anything else hi
+};
+constexpr int sk_lca(const Skeleton& S, int a, int b) {  // pre-order: a is b's ancestor (or b) iff a <= b <= end[a]
+    while (!(a <= b && b <= S.end[a])) a = S.parent[a];
+    return a;
+}
+// the k-th opponent edge on the way from node n up to the root, as 2 * (opponent node) + edge; -1: there are fewer
+constexpr int sk_outer_edge(const Skeleton& S, int opp, int n, int k) {
+    for (; S.parent[n] >= 0; n = S.parent[n])
+        if (S.kind[S.parent[n]] == opp && k-- == 0) return S.parent[n] * 2 + S.edge[n];
+    return -1;
+}
+constexpr bool sk_same_shape(const Skeleton& S, const RowLayout& R, int x, int y) {
+    if (S.end[x] - x != S.end[y] - y || R.group[x] != R.group[y]) return false;
+    for (int i = 0; i <= S.end[x] - x; ++i) {
+        if (S.kind[x + i] != S.kind[y + i]) return false;
+        if (i && (S.parent[x + i] - x != S.parent[y + i] - y || S.edge[x + i] != S.edge[y + i])) return false;
+        if (i && (R.word[x + i] != R.word[y + i] || R.word2[x + i] != R.word2[y + i])) return false;
+        if (S.kind[x + i] == SK_CHANCE && (R.words[x + i] != R.words[y + i] || R.stride[x + i] != R.stride[y + i])) return false;
+    }
+    return true;
+}
+constexpr ExclPair sk_exclusive_pair(const Skeleton& S, const RowLayout& R, int walker) {
+    const int wk = walker == 0 ? SK_P0 : SK_P1, opp = walker == 0 ? SK_P1 : SK_P0;
+    ExclPair best;
+    bool best_even = false;
+    for (int x = 0; x < S.n; ++x) {
+        if (S.kind[x] != SK_CHANCE) continue;
+        for (int y = S.end[x] + 1; y < S.n; ++y) {
+            if (S.kind[y] != SK_CHANCE) continue;
+            const int a = sk_lca(S, x, y);
+            if (S.kind[a] != opp || !sk_same_shape(S, R, x, y)) continue;
+            // the merged instance hands its Decisions over at hi's place: ascending node order survives iff no walker node
+            // between the two sub-trees can be live together with lo
+            bool ordered = true;
+            for (int n = S.end[x] + 1; n < y; ++n)
+                if (S.kind[n] == wk && S.kind[sk_lca(S, x, n)] != opp) ordered = false;
+            if (!ordered) continue;
+            // prefer partners with equally many opponent edges above them (ancestor_reach: no padding factor)
+            int kx = 0, ky = 0;
+            while (sk_outer_edge(S, opp, x, kx) >= 0) ++kx;
+            while (sk_outer_edge(S, opp, y, ky) >= 0) ++ky;
+            if (best.lo >= 0 && (best_even || kx != ky)) continue;
+            int c = x;
+            while (S.parent[c] != a) c = S.parent[c];
+            best.lo = x;
+            best.hi = y;
+            best.anc = a;
+            best.edge_lo = S.edge[c];
+            best_even = kx == ky;
+        }
+    }
+    return best;
+}
+// MERGE = false: nothing is merged (the child-record variant, the unmerged cross-check)
+template <class G, int W, bool MERGE>
+struct SkelExcl {
+    using SK = SkelOf<G>;
+    static constexpr ExclPair X = MERGE ? sk_exclusive_pair(SK::S, SK::R, W) : ExclPair{};
+    static constexpr int LO = X.lo, HI = X.hi, SHIFT = X.hi - X.lo;
+    static constexpr bool in_lo(int n) { return LO >= 0 && LO <= n && n <= SK::S.end[LO]; }
+    static constexpr bool in_hi(int n) { return HI >= 0 && HI <= n && n <= SK::S.end[HI]; }
+    static constexpr bool skipped(int n) { return in_lo(n) && n != LO; }  // never built: its partner in hi's sub-tree stands for it
+    static constexpr int at(int n) { return in_lo(n) ? n + SHIFT : n; }   // where the traversal keeps what it knows of node n
+    static constexpr bool both_below(int j) { return LO >= 0 && j < LO && HI <= SK::S.end[j]; }
+};
+// an opponent node whose children are all terminal: only the sampled child can be live, one division serves the pair
+template <class G>
+constexpr bool sk_leaf_pair(int s) {
+    int kids = 0;
+    for (int c = 0; c < SkelOf<G>::S.n; ++c)
+        if (SkelOf<G>::S.parent[c] == s) {
+            if (SkelOf<G>::S.kind[c] != SK_TERMINAL) return false;
+            ++kids;
+        }
+    return kids == 2;
+}
+template <class G>
+constexpr int sk_child(int s, int e) {
+    for (int c = 0; c < SkelOf<G>::S.n; ++c)
+        if (SkelOf<G>::S.parent[c] == s && SkelOf<G>::S.edge[c] == e) return c;
+    return -1;
+}
+
 static_assert(SkelOf<KuhnSkel>::S.n == 11, "Kuhn: two deals, four decision nodes, five terminals");
 static_assert(SkelOf<LeducSkel>::S.n == 38, "Leduc: two deals, 4 + 3 x 4 decision nodes, three board draws, 2 + 3 x 5 terminals");
 static_assert(SkelOf<LeducSkel>::S.end[0] == 37 && SkelOf<LeducSkel>::S.kind[2] == SK_P0, "pre-order, the first decision is P0's");
 static_assert(SkelOf<LeducSkel>::R.words[0] == 2 && SkelOf<LeducSkel>::R.words[1] == 14 && SkelOf<LeducSkel>::R.stride[1] == 16,
               "Leduc: the second deal alone below the first; round 1 = 4 infosets, 3 board deals, 2 folds in a 64-byte row");
 static_assert(SkelOf<KuhnSkel>::R.words[1] == 14 && SkelOf<KuhnSkel>::R.stride[1] == 16, "Kuhn: 4 infosets, 5 terminals");
+
+static_assert(SkelExcl<LeducSkel, 0, true>::LO == 17 && SkelExcl<LeducSkel, 0, true>::HI == 28 && SkelExcl<LeducSkel, 0, true>::X.anc == 15 &&
+                  SkelExcl<LeducSkel, 0, true>::X.edge_lo == 1,
+              "Leduc, walker 0: CHECKED is the opponent's, so round 2 after check-raise-call and round 2 after check-check never meet");
+static_assert(SkelExcl<LeducSkel, 1, true>::LO == 4 && SkelExcl<LeducSkel, 1, true>::HI == 28 && SkelExcl<LeducSkel, 1, true>::X.anc == 2 &&
+                  SkelExcl<LeducSkel, 1, true>::X.edge_lo == 1,
+              "Leduc, walker 1: OPEN is the opponent's; round 2 after raise-call pairs with the one after check-check (one opponent edge each)");
+static_assert(SkelExcl<KuhnSkel, 0, true>::LO < 0 && SkelExcl<KuhnSkel, 1, true>::LO < 0, "Kuhn: one deal, nothing to pair");
+static_assert(SkelExcl<LeducSkel, 0, false>::LO < 0 && !SkelExcl<LeducSkel, 0, false>::skipped(20) && SkelExcl<LeducSkel, 0, false>::at(20) == 20,
+              "unmerged: every node stands for itself");
+static_assert(sk_leaf_pair<LeducSkel>(6) && sk_leaf_pair<LeducSkel>(10) && !sk_leaf_pair<LeducSkel>(3) && sk_leaf_pair<KuhnSkel>(3) &&
+                  sk_leaf_pair<KuhnSkel>(7),
+              "fold / call below a raise: RAISED', CHECKRAISED' and Kuhn's Bet, CheckBet");
 
 // compile-time loops: f(std::integral_constant<int, I>) for I = LO .. HI-1, ascending / descending
 template <int I, int HI, class F>
@@ -225,6 +339,7 @@ template <class G, int W, bool PRUNED, bool REF, bool ROWS, class OnBuilt, class
 __device__ __forceinline__ uint32_t static_traverse(const DevGame& g, const DevInfoTab& it, const StepParams& p, uint64_t tree_id,
                                                     bool present, OnBuilt&& on_built, OnDecision&& on_decision) {
     using SK = SkelOf<G>;
+    using EX = SkelExcl<G, W, ROWS>;  // the packed-row variant merges the exclusive pair and the leaf pairs; the child-record one nothing
     constexpr int N = SK::S.n;
     constexpr int K_WALKER = W == 0 ? SK_P0 : SK_P1;
     constexpr int K_OPP = W == 0 ? SK_P1 : SK_P0;
@@ -237,6 +352,8 @@ __device__ __forceinline__ uint32_t static_traverse(const DevGame& g, const DevI
     uint32_t pick[N];              // chance: the sampled outcome; opponent: the sampled action; walker (PRUNED): the surviving edges
     bool live[N];
     float sg0[N], sg1[N], q0[N], q1[N];   // (sigma, q) of a player node's two edges
+    // the exclusive pair: the opponent's pick selects lo, and the two chance nodes' own liveness (live[hi] becomes the merged one)
+    bool sel_lo = false, live_lo = false, live_hi = false;
     // every draw of this tree: rp_node_hash(seed, epoch, tree, key) with the (seed, epoch, tree) part hashed once
     const uint64_t th = rp_node_hash_tree(rp_node_hash_step(p.seed, p.epoch), tree_id);
     const char* const irows = reinterpret_cast<const char*>(it.row2);
@@ -248,6 +365,7 @@ __device__ __forceinline__ uint32_t static_traverse(const DevGame& g, const DevI
     sk_for<0, N>([&](auto I) __attribute__((always_inline)) {
         constexpr int s = I;
         constexpr int par = SK::S.parent[s];
+        if constexpr (EX::skipped(s)) return;  // inside lo: its partner inside hi is built for both
         if constexpr (par >= 0) {
             if constexpr (!ROWS) {
                 uint32_t k = (uint32_t)SK::S.edge[s];
@@ -261,11 +379,16 @@ __device__ __forceinline__ uint32_t static_traverse(const DevGame& g, const DevI
             } else if constexpr (SK::S.kind[par] == SK_CHANCE) {  // the first node of par's group: the whole row, by slices
                 constexpr int c = par;
                 constexpr int up = SK::R.group[c];
-                if constexpr (up >= 0) ridx[c] = ridx[up] * g.row_fan[c] + pick[c];
+                if constexpr (up >= 0) ridx[c] = ridx[up] * nout[c] + pick[c];
                 else ridx[c] = pick[c];
                 // one scalar base, one 32-bit lane offset, the slices at immediate offsets
-                const char* const row = reinterpret_cast<const char*>(g.rows + g.row_base[c]);
-                const uint32_t off = ridx[c] * (uint32_t)(SK::R.stride[c] * 4);
+                const char* row = reinterpret_cast<const char*>(g.rows + g.row_base[c]);
+                uint32_t off = ridx[c] * (uint32_t)(SK::R.stride[c] * 4);
+                if constexpr (EX::in_hi(c)) {  // the selected alternative's table (same layout: sk_same_shape)
+                    row = reinterpret_cast<const char*>(g.rows);
+                    const uint32_t base_lo = g.row_base[c - EX::SHIFT], base_hi = g.row_base[c];
+                    off += (sel_lo ? base_lo : base_hi) * 16u;
+                }
                 constexpr int NS = (SK::R.words[c] + 3) / 4;
                 uint32_t w[NS * 4];
                 sk_for<0, NS>([&](auto K) __attribute__((always_inline)) {
@@ -287,6 +410,10 @@ __device__ __forceinline__ uint32_t static_traverse(const DevGame& g, const DevI
                             rw[m] = w[SK::R.word[m]];
                             if constexpr (REF) ry[m] = w[SK::R.word2[m]];
                             nout[m] = g.row_fan[m];
+                            if constexpr (EX::in_hi(c)) {
+                                const uint32_t fan_lo = g.row_fan[m - EX::SHIFT];
+                                nout[m] = sel_lo ? fan_lo : nout[m];
+                            }
                         } else {
                             ry[m] = w[SK::R.word[m]];
                         }
@@ -296,6 +423,21 @@ __device__ __forceinline__ uint32_t static_traverse(const DevGame& g, const DevI
             if constexpr (SK::S.kind[par] == K_OPP) live[s] = live[par] && pick[par] == (uint32_t)SK::S.edge[s];
             else if constexpr (PRUNED && SK::S.kind[par] == K_WALKER) live[s] = live[par] && ((pick[par] >> SK::S.edge[s]) & 1u);
             else live[s] = live[par];
+        }
+        if constexpr (s == EX::LO) return;  // drawn at hi, if it is the selected one
+        if constexpr (s == EX::HI) {  // from here on hi stands for the alternative the opponent's pick leads to (both dead: either)
+            sel_lo = pick[EX::X.anc] == (uint32_t)EX::X.edge_lo;
+            // (selects between values, never between array elements: the arrays must stay in registers)
+            live_lo = live[EX::LO];
+            live_hi = live[s];
+            const uint32_t key_lo = rw[EX::LO], key_hi = rw[s], fan_lo = nout[EX::LO], fan_hi = nout[s];
+            rw[s] = sel_lo ? key_lo : key_hi;
+            nout[s] = sel_lo ? fan_lo : fan_hi;
+            if constexpr (REF) {
+                const uint32_t ci_lo = ry[EX::LO], ci_hi = ry[s];
+                ry[s] = sel_lo ? ci_lo : ci_hi;
+            }
+            live[s] = sel_lo ? live_lo : live_hi;
         }
         if constexpr (SK::S.kind[s] == SK_CHANCE) {  // SamplingScheme::sample at a chance node: uniform (external.rs:41-64)
             // ry = chance_info (read under REF only); 0: the root deal (thread RNG in the reference)
@@ -333,48 +475,90 @@ __device__ __forceinline__ uint32_t static_traverse(const DevGame& g, const DevI
     });
 
     // ---- Tree::partition + CfrFlow::dfs per walker decision node (tree.rs:88-98, flow.rs:64-87) ---------------------
+    // A node of lo's sub-tree is counted, listed and valued through its partner in hi's: at most one of the two is live.
     uint32_t nn = 0;
-    sk_for<0, N>([&](auto I) __attribute__((always_inline)) { nn += live[decltype(I)::value] ? 1u : 0u; });
-    on_built([&](auto I) __attribute__((always_inline)) { return ry[decltype(I)::value]; },
-             [&](auto I) __attribute__((always_inline)) { return live[decltype(I)::value]; });
+    sk_for<0, N>([&](auto I) __attribute__((always_inline)) {
+        if constexpr (!EX::in_lo(decltype(I)::value)) nn += live[decltype(I)::value] ? 1u : 0u;
+    });
+    on_built([&](auto I) __attribute__((always_inline)) { return ry[EX::at(decltype(I)::value)]; },
+             [&](auto I) __attribute__((always_inline)) { return EX::in_lo(decltype(I)::value) ? false : live[decltype(I)::value]; });
     sk_for<0, N>([&](auto J) __attribute__((always_inline)) {
         constexpr int j = J;
-        if constexpr (SK::S.kind[j] == K_WALKER) {
+        if constexpr (SK::S.kind[j] == K_WALKER && !EX::in_lo(j)) {
             constexpr int E = SK::S.end[j];
+            // both alternatives below j: their reach products come down both paths, the merged instance is entered at hi with the
+            // selected pair and its sum goes up to lo's parent under lo's liveness, to hi's under hi's.  Only one of them below
+            // j (or j inside hi): j live means that one is the selected one.
+            constexpr bool BOTH = EX::both_below(j);
             float rel[N], smp[N], acc[N], tv[2] = {0.0f, 0.0f};
+            float rel_lo = 1.0f, smp_lo = 1.0f;
             // top-down over the sub-tree: reach products from j's children (flow.rs:195-212); a leaf hands its value to its
             // parent right here, an internal node starts its sum at 0 (the two-children argument of k_traverse_lds)
             sk_for<j + 1, E + 1>([&](auto Nn) __attribute__((always_inline)) {
                 constexpr int n = Nn;
                 constexpr int par = SK::S.parent[n];
                 constexpr int e = SK::S.edge[n];
+                // where node n and its parent keep their state.  A node of lo's sub-tree reads and writes its partner's slots in
+                // hi's: for a root on lo's path (not BOTH) hi's slots hold the lo alternative whenever the root is live, so the
+                // sweep runs over lo's nodes with hi's storage.  lo's own parent lies outside the pair and stands for itself.
+                constexpr int an = EX::at(n), ap = n == EX::LO ? par : EX::at(par);
+                if constexpr (BOTH && EX::skipped(n)) return;
                 float r = 1.0f, sm = 1.0f;
+                if constexpr (ROWS && SK::S.kind[n] == SK_TERMINAL && SK::S.kind[par] == K_OPP && sk_leaf_pair<G>(par)) {
+                    // the opponent's two terminal children: the unsampled one is dead, so the sampled one's r / sm * payoff is the
+                    // only value that enters the parent's sum — computed with the edge's factors selected, added once
+                    if constexpr (e == 1) {
+                        const bool e1 = pick[ap] != 0u;
+                        const float s_0 = sg0[ap], s_1 = sg1[ap], q_0 = q0[ap], q_1 = q1[ap];
+                        constexpr int sib = EX::at(sk_child<G>(par, 0));
+                        const uint32_t p_0 = pay[sib], p_1 = pay[an];
+                        r = rel[ap] * (e1 ? s_1 : s_0);
+                        sm = smp[ap] * (e1 ? q_1 : q_0);
+                        const float v = r / sm * rp_u2f(e1 ? p_1 : p_0);
+                        acc[ap] = live[ap] ? acc[ap] + v : acc[ap];
+                    }
+                    return;
+                }
                 if constexpr (par != j) {
-                    r = rel[par];
-                    sm = smp[par];
-                    if constexpr (SK::S.kind[par] == K_WALKER) r = r * (e ? sg1[par] : sg0[par]);
+                    r = rel[ap];
+                    sm = smp[ap];
+                    if constexpr (SK::S.kind[par] == K_WALKER) r = r * (e ? sg1[ap] : sg0[ap]);
                     if constexpr (SK::S.kind[par] == K_OPP) {
-                        r = r * (e ? sg1[par] : sg0[par]);
-                        sm = sm * (e ? q1[par] : q0[par]);
+                        r = r * (e ? sg1[ap] : sg0[ap]);
+                        sm = sm * (e ? q1[ap] : q0[ap]);
                     }
                 }
+                if constexpr (BOTH && n == EX::LO) {  // kept for hi
+                    rel_lo = r;
+                    smp_lo = sm;
+                    return;
+                }
+                if constexpr (BOTH && n == EX::HI) {
+                    r = sel_lo ? rel_lo : r;
+                    sm = sel_lo ? smp_lo : sm;
+                }
                 if constexpr (SK::S.kind[n] == SK_TERMINAL) {
-                    const float v = r / sm * rp_u2f(pay[n]);
+                    const float v = r / sm * rp_u2f(pay[an]);
                     if constexpr (par == j) tv[e] = v;
-                    else acc[par] = live[n] ? acc[par] + v : acc[par];
+                    else acc[ap] = live[an] ? acc[ap] + v : acc[ap];
                 } else {
-                    rel[n] = r;
-                    smp[n] = sm;
-                    acc[n] = 0.0f;
+                    rel[an] = r;
+                    smp[an] = sm;
+                    acc[an] = 0.0f;
                 }
             });
             // bottom-up: the internal nodes' sums, descending node index (node.rs:103-107)
             sk_for_down<E, j + 1>([&](auto Nn) __attribute__((always_inline)) {
                 constexpr int n = Nn;
                 constexpr int par = SK::S.parent[n];
+                constexpr int an = EX::at(n), ap = n == EX::LO ? par : EX::at(par);  // as in the sweep above
+                if constexpr (BOTH && EX::skipped(n)) return;  // summed when hi's sub-tree came by
                 if constexpr (SK::S.kind[n] != SK_TERMINAL) {
-                    if constexpr (par == j) tv[SK::S.edge[n]] = acc[n];
-                    else acc[par] = live[n] ? acc[par] + acc[n] : acc[par];
+                    bool lv = live[an];
+                    if constexpr (n == EX::LO) lv = live_lo;
+                    if constexpr (n == EX::HI) lv = live_hi;
+                    if constexpr (par == j) tv[SK::S.edge[n]] = acc[an];
+                    else acc[ap] = lv ? acc[ap] + acc[an] : acc[ap];
                 }
             });
             // ancestor_reach (flow.rs:166-174): the opponent's edges on the way up
@@ -383,7 +567,7 @@ __device__ __forceinline__ uint32_t static_traverse(const DevGame& g, const DevI
                 // ancestors of j in the order j, parent(j), ...: node index DESCENDS along the chain, so visit candidates from
                 // j downwards and keep those on the chain
                 constexpr int n = j - decltype(Q)::value;
-                if constexpr (n > 0) {
+                if constexpr (n > 0 && !(EX::in_hi(j) && n <= EX::HI)) {
                     // is n on the parent chain of j (n == j or an ancestor)?  pre-order: n <= j <= end[n]
                     if constexpr (n <= j && j <= SK::S.end[n]) {
                         constexpr int par = SK::S.parent[n];
@@ -394,6 +578,27 @@ __device__ __forceinline__ uint32_t static_traverse(const DevGame& g, const DevI
                     }
                 }
             });
+            if constexpr (EX::in_hi(j)) {
+                // j inside the merged instance: from hi upwards the chain is the selected alternative's, edge by edge in the same
+                // order; the shorter chain is padded with the factor 1 (exact)
+                sk_for<0, N>([&](auto Q) __attribute__((always_inline)) {
+                    constexpr int fl = sk_outer_edge(SK::S, K_OPP, EX::LO, decltype(Q)::value);
+                    constexpr int fh = sk_outer_edge(SK::S, K_OPP, EX::HI, decltype(Q)::value);
+                    if constexpr (fl >= 0 || fh >= 0) {
+                        float cl = 1.0f, ql = 1.0f, ch = 1.0f, qh = 1.0f;
+                        if constexpr (fl >= 0) {
+                            cl = (fl & 1) ? sg1[fl >> 1] : sg0[fl >> 1];
+                            ql = (fl & 1) ? q1[fl >> 1] : q0[fl >> 1];
+                        }
+                        if constexpr (fh >= 0) {
+                            ch = (fh & 1) ? sg1[fh >> 1] : sg0[fh >> 1];
+                            qh = (fh & 1) ? q1[fh >> 1] : q0[fh >> 1];
+                        }
+                        cf = cf * (sel_lo ? cl : ch);
+                        sm_ = sm_ * (sel_lo ? ql : qh);
+                    }
+                });
+            }
             const float reach = cf / sm_;
             const float u0 = reach * tv[0], u1 = reach * tv[1];
             if constexpr (!PRUNED) {
