@@ -513,7 +513,7 @@ typedef enum {
     RP_RECALL_OK = 0,
     RP_RECALL_EDGE = 1,    /* an edge code that is no edge (0 or above 19) */
     RP_RECALL_ILLEGAL = 2, /* a snapped action the rules refuse (Game::is_allowed) */
-    RP_RECALL_LENGTH = 3,  /* n_edges above RP_NLHE_MAX_HISTORY */
+    RP_RECALL_LENGTH = 3,  /* n_edges above RP_NLHE_MAX_HISTORY (a frontier: or n_prefix above RP_NLHE_MAX_PREFIX) */
     RP_RECALL_CARDS = 4,   /* hole not two cards; draws with wrong popcounts, overlapping each other or the hole, or out of street order */
     RP_RECALL_DRAW = 5,    /* a Draw (an edge, or a street the replay deals itself) that needs cards the recall does not carry */
     RP_RECALL_SEAT = 6,    /* pov > 1, dealer > 1, reserved != 0, or stacks neither 0,0 nor both positive */
@@ -527,6 +527,72 @@ RP_API int rp_nlhe_opponent_range(rp_nlhe* h, uint64_t n_recalls, const rp_nlhe_
                                   uint8_t* status);
 RP_API int rp_nlhe_opponent_range_device(rp_nlhe* h, uint64_t n_recalls, const rp_nlhe_recall* recalls_dev, float* mass_dev,
                                          uint8_t* seen_dev, uint8_t* status_dev);
+
+/* Frontier payoffs: what the blueprint says a depth-limited leaf is worth (DepthSampler::payoffs, nlhe/src/solver.rs:39-67, called at
+ * every frontier leaf the depth solver builds: subgame/src/depth/encoder.rs:96-98, subgame/src/encoder.rs:102-104).  For each of
+ * the RP_NLHE_FRONTIER_LEAVES x RP_NLHE_FRONTIER_LEAVES pairs (k, j) of continuation strategies, `rollouts` games are played from
+ * the frontier state to the end with NlheEncoder::biased_rollout (nlhe/src/encoder.rs:70-147) and their utilities averaged.  Read-only
+ * exactly as the key queries above: nothing is inserted, epoch / counters / keys are unchanged, no query can fail a later step.
+ * One workgroup per frontier (csrc/nlmc_frontier.hpp).
+ *
+ * FRONTIER STATE `game` = the state after `edges` has been replayed from Game::from_start(dealer, stacks) by the ranges' REPLAY rule,
+ *   with the frontier's own draws and both seats holding their cards (holes[s] is seat s's).  RP_RECALL_DRAW where a street is needed
+ *   and not carried.  `game` may be a chance node (the reference's case), a choice node, or terminal.
+ * PREFIX.  The reference passes payoffs() the SOLVER's construction prefix (solver.rs:97-101: the current street's descents of the
+ *   recall the solver was built from), not the path to the leaf: it is the same for every leaf of one solver.  So `prefix` is an
+ *   input of its own, independent of `edges`, and the story of a rollout starts from it (Story::from(prefix), encoder.rs:91).  A
+ *   Path keeps only its first 12 edges, so a longer prefix could never matter: n_prefix > 12 is RP_RECALL_LENGTH.
+ * ROLLOUT = encoder.rs:89-115 over plain Game::apply: at a chance node ONE street is dealt (game.reveal()), at a choice node the edge
+ *   sampled below is applied as game.apply(game.snap(game.actionize(edge))); every step pushes its edge (Draw, or the sampled edge)
+ *   onto the story; a terminal node ends the rollout.
+ * KEY at a decision = resume(story edges, game) (encoder.rs:59-67), the ranges' KEY rule applied to the story: the first 12 edges
+ *   of prefix ++ rollout edges are the path, `past` its trailing choice edges, `choices` = game.choices(aggression of that path),
+ *   `present` = the bucket of (the actor's hole, the board).  From the 13th story edge on the path is frozen; reproduced, not repaired.
+ * POLICY = RP_DIST_AVERAGED in rp_nlhe_policy's arithmetic; an absent infoset, or a row of zero weights, is uniform.
+ * SAMPLE_BIASED (encoder.rs:121-146), f32, one rounding per operation: w_a = p_a * m_a with m_a = bias when the actor's continuation
+ *   is 1 and the edge is Fold, 2 and the edge is Check or Call, 3 and the edge is Open, Raise or Shove, and 1.0f otherwise
+ *   (continuation 0 biases nothing); the actor's continuation is k for seat `internal`, j for the other seat.  total = the left fold
+ *   of w from 0; threshold = u * total; the running sum starts from 0 and the first slot with threshold < sum wins, the last slot
+ *   if there is none.
+ * VALUE = (float)(reward - spent) of seat `internal` at the terminal state (Settlement::won, kicker/src/settlement.rs:30-32);
+ *   payoffs[i][k][j] = the f32 left fold over r, divided by (float)rollouts.
+ * RANDOM NUMBERS.  The reference uses the thread RNG here (rand::random, Deck::deal): there is nothing of the reference's to
+ *   reproduce, and the library's counter contract is used (the one rp_nlhe_playouts has).  rollout_id = ((first_id + i) * 16 + 4 k + j)
+ *   * rollouts + r, wrapping; draw c of a rollout is rp_node_hash(seed, 0, rollout_id, c), c counting from 0 in consumption order.  A
+ *   chance step consumes one draw per card — rp_pick_uniform over the popcount of the deck picks the pick-th lowest card, which is
+ *   then removed: 3 cards to the flop, then 1 and 1 — a decision one draw, u = rp_u01.  The deck is the 52 cards minus both holes and
+ *   the board.  A frontier's answer depends on seed, first_id + i and its own record only, never on the batch around it.
+ * TERMINATION.  The step loop of a rollout is bounded by a constant derived from the rules (chips are finite, every raise commits
+ *   some: csrc/nlmc_frontier.hpp).  A rollout that reaches the bound, or a snapped action the rules refuse, gives the frontier the
+ *   status RP_RECALL_ILLEGAL instead of a hang.
+ * STATUS per frontier, rp_recall_status, by the ranges' rules: n_edges above RP_NLHE_MAX_HISTORY or n_prefix above 12 LENGTH;
+ *   internal > 1, dealer > 1, reserved != 0 or bad stacks SEAT; a hole that is not two cards, or cards shared between the holes and
+ *   the draws, CARDS; an edge code outside 1..19 in `edges` or `prefix` EDGE.  A malformed frontier yields zero outputs and its
+ *   status; the call is still RP_OK and the rest of the batch is answered.  No input causes an out-of-bounds access or an unbounded loop.
+ * Arguments: rollouts = 0 is treated as 1 (FrontierHyperParams::rollouts, subgame/src/depth/hyperparams.rs:29-31); rollouts > 4096,
+ *   or a bias that is not finite and positive, is RP_ERR_INVALID.  payoffs [n][4][4]; won [n][16][rollouts] the utility of every
+ *   rollout (may be NULL); status [n] (may be NULL).  The _device form takes every pointer in DEVICE memory, queues one launch on the
+ *   handle's stream and returns, ordered exactly like rp_nlhe_policy_device; the host form stages, launches and synchronises.
+ *   n = 0 is RP_OK without a launch. */
+#define RP_NLHE_FRONTIER_LEAVES 4u
+#define RP_NLHE_MAX_PREFIX 12u
+typedef struct rp_nlhe_frontier {
+    uint64_t holes[2];   /* the cards of seat 0 and seat 1 */
+    uint64_t draws[3];   /* as in rp_nlhe_recall */
+    int16_t stacks[2];   /* as in rp_nlhe_recall */
+    uint8_t internal;    /* the seat whose utility is reported: 0 or 1 */
+    uint8_t dealer;      /* as in rp_nlhe_recall */
+    uint8_t n_edges;     /* <= RP_NLHE_MAX_HISTORY */
+    uint8_t n_prefix;    /* <= RP_NLHE_MAX_PREFIX */
+    uint8_t edges[RP_NLHE_MAX_HISTORY]; /* the history from Game::from_start to the frontier state, Draw edges included */
+    uint8_t prefix[RP_NLHE_MAX_PREFIX]; /* the solver's construction prefix: the story starts from it; independent of `edges` */
+    uint8_t reserved[4]; /* 0 */
+} rp_nlhe_frontier;      /* 112 bytes */
+RP_API int rp_nlhe_frontier_payoffs(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* frontiers, float bias, uint32_t rollouts,
+                                    uint64_t seed, uint64_t first_id, float* payoffs, int16_t* won, uint8_t* status);
+RP_API int rp_nlhe_frontier_payoffs_device(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* frontiers_dev, float bias,
+                                           uint32_t rollouts, uint64_t seed, uint64_t first_id, float* payoffs_dev, int16_t* won_dev,
+                                           uint8_t* status_dev);
 
 /* Multi-GPU (BASELINE configs[3]): trees sharded by rank (rank r samples tree ids [r*B, (r+1)*B) of a world*B-tree epoch
  * against a replicated table).  step_local: this rank's traversal reduced to one composed entry per infoset touched

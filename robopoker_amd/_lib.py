@@ -34,6 +34,8 @@ UPDATE = {"ordered": 0, "composed": 1}
 REACH = {"opponent": 0, "signalled": 1}  # rp_reach_kind
 RP_NLHE_MAX_HISTORY = 48
 RP_NLHE_MAX_HOLES = 1326
+RP_NLHE_FRONTIER_LEAVES = 4
+RP_NLHE_MAX_PREFIX = 12
 
 
 class Hyper(C.Structure):
@@ -57,6 +59,13 @@ class NlheRecall(C.Structure):
     """rp_nlhe_recall: what one seat has seen, at edge level (88 bytes)"""
     _fields_ = [("hole", C.c_uint64), ("draws", C.c_uint64 * 3), ("stacks", C.c_int16 * 2), ("pov", C.c_uint8), ("dealer", C.c_uint8),
                 ("n_edges", C.c_uint8), ("reserved", C.c_uint8), ("edges", C.c_uint8 * 48)]
+
+
+class NlheFrontier(C.Structure):
+    """rp_nlhe_frontier: a depth-limited leaf — both holes, the history to it and the solver's prefix (112 bytes)"""
+    _fields_ = [("holes", C.c_uint64 * 2), ("draws", C.c_uint64 * 3), ("stacks", C.c_int16 * 2), ("internal", C.c_uint8),
+                ("dealer", C.c_uint8), ("n_edges", C.c_uint8), ("n_prefix", C.c_uint8), ("edges", C.c_uint8 * 48),
+                ("prefix", C.c_uint8 * 12), ("reserved", C.c_uint8 * 4)]
 
 
 class State(C.Structure):
@@ -309,6 +318,9 @@ _SIGNATURES = {
     "rp_nlhe_reaches_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint64] + [C.c_void_p] * 5),
     "rp_nlhe_opponent_range": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
     "rp_nlhe_opponent_range_device": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
+    "rp_nlhe_frontier_payoffs": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_float, C.c_uint32, C.c_uint64, C.c_uint64] + [C.c_void_p] * 3),
+    "rp_nlhe_frontier_payoffs_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_float, C.c_uint32, C.c_uint64, C.c_uint64]
+                                        + [C.c_void_p] * 3),
     "rp_nlhe_set_shard": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "rp_nlhe_entry_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
     "rp_nlhe_step_local": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),

@@ -31,6 +31,7 @@
 #include <string>
 #include <vector>
 
+#include "nlmc_frontier.hpp"
 #include "nlmc_level.hpp"
 #include "nlmc_query.hpp"
 #include "nlmc_range.hpp"
@@ -1148,6 +1149,72 @@ int rp_nlhe_opponent_range(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(mass, d_mass, n * 256u * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(seen, s.base + o_seen, n * 256u, hipMemcpyDeviceToHost, st));
+    if (status) HIP_TRY(hipMemcpyAsync(status, s.base + o_status, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RP_OK;
+}
+
+}  // extern "C"
+
+// ---- frontier payoffs (nlmc_frontier.hpp): one workgroup per frontier, at most NR_CHUNK frontiers per launch
+namespace {
+// rollouts = 0 is 1; the arguments a call is refused for
+int nf_check(const char* name, rp_nlhe* h, float bias, uint32_t* rollouts) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "%s: NULL handle", name);
+    if (!(bias > 0.0f) || std::isinf(bias)) return rp::fail(RP_ERR_INVALID, "%s: bias must be finite and positive", name);
+    if (*rollouts > 4096u) return rp::fail(RP_ERR_INVALID, "%s: rollouts %u above 4096", name, *rollouts);
+    if (*rollouts == 0u) *rollouts = 1u;
+    return RP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rp_nlhe_frontier_payoffs_device(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* frontiers, float bias, uint32_t rollouts, uint64_t seed,
+                                    uint64_t first_id, float* payoffs, int16_t* won, uint8_t* status) {
+    int rc = nf_check("rp_nlhe_frontier_payoffs", h, bias, &rollouts);
+    if (rc) return rc;
+    if (n == 0) return RP_OK;
+    if (!frontiers || !payoffs) return rp::fail(RP_ERR_INVALID, "rp_nlhe_frontier_payoffs: NULL frontiers or payoffs with n > 0");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    for (uint64_t at = 0; at < n; at += NR_CHUNK) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(NR_CHUNK, n - at);
+        NfArgs q{};
+        q.frontiers = frontiers + at;
+        q.bias = bias;
+        q.rollouts = rollouts;
+        q.step_hash = rp_node_hash_step(seed, 0);
+        q.first_id = first_id + at;
+        q.payoffs = payoffs + at * NF_CELLS;
+        q.won = won ? won + at * NF_CELLS * rollouts : nullptr;
+        q.status = status ? status + at : nullptr;
+        hipLaunchKernelGGL(k_nl_frontier, dim3(m), dim3(NF_BLOCK), 0, st, h->tab, h->prm, q);
+        HIP_TRY(hipGetLastError());
+    }
+    return RP_OK;
+}
+
+int rp_nlhe_frontier_payoffs(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* frontiers, float bias, uint32_t rollouts, uint64_t seed,
+                             uint64_t first_id, float* payoffs, int16_t* won, uint8_t* status) {
+    int rc = nf_check("rp_nlhe_frontier_payoffs", h, bias, &rollouts);
+    if (rc) return rc;
+    if (n == 0) return RP_OK;
+    if (!frontiers || !payoffs) return rp::fail(RP_ERR_INVALID, "rp_nlhe_frontier_payoffs: NULL frontiers or payoffs with n > 0");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    // frontiers (8-byte aligned) | payoffs | won | status
+    const size_t b_won = won ? n * NF_CELLS * rollouts * sizeof(int16_t) : 0, o_pay = n * sizeof(rp_nlhe_frontier),
+                 o_won = o_pay + n * NF_CELLS * sizeof(float), o_status = o_won + b_won;
+    NrStage s;
+    HIP_TRY(hipMalloc(&s.base, o_status + n));
+    rp_nlhe_frontier* d_fr = reinterpret_cast<rp_nlhe_frontier*>(s.base);
+    float* d_pay = reinterpret_cast<float*>(s.base + o_pay);
+    int16_t* d_won = won ? reinterpret_cast<int16_t*>(s.base + o_won) : nullptr;
+    HIP_TRY(hipMemcpyAsync(d_fr, frontiers, n * sizeof(rp_nlhe_frontier), hipMemcpyHostToDevice, st));
+    if ((rc = rp_nlhe_frontier_payoffs_device(h, n, d_fr, bias, rollouts, seed, first_id, d_pay, d_won, s.base + o_status))) return rc;
+    HIP_TRY(hipMemcpyAsync(payoffs, d_pay, n * NF_CELLS * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (won) HIP_TRY(hipMemcpyAsync(won, d_won, b_won, hipMemcpyDeviceToHost, st));
     if (status) HIP_TRY(hipMemcpyAsync(status, s.base + o_status, n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return RP_OK;

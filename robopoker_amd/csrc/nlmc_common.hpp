@@ -191,27 +191,31 @@ __device__ __forceinline__ void nl_load_row(const float* rows, uint32_t row, boo
     }
 }
 
+// the pick-th lowest card of the deck (pick < its popcount) as a mask: a popcount search (a loop clearing `pick` bits runs up to 51
+// rounds)
+__device__ __forceinline__ uint64_t nl_nth_card(uint64_t deck, uint32_t pick) {
+    uint32_t k = pick, w = (uint32_t)deck, base = 0;
+    const uint32_t plo = (uint32_t)__popc(w);
+    if (k >= plo) {
+        k -= plo;
+        w = (uint32_t)(deck >> 32);
+        base = 32;
+    }
+#pragma unroll
+    for (uint32_t half = 16; half >= 1; half >>= 1) {
+        const uint32_t c = (uint32_t)__popc(w & ((1u << half) - 1u));
+        const bool up = k >= c;
+        k -= up ? c : 0u;
+        w = up ? w >> half : w & ((1u << half) - 1u);
+        base += up ? half : 0u;
+    }
+    return 1ull << base;
+}
 __device__ __forceinline__ uint64_t nl_draw(uint64_t deck, int k, const NlParams& p, uint64_t tree, uint64_t key) {  // tree = its id in the epoch
     uint64_t out = 0;
     for (int c = 0; c < k; ++c) {
         const uint32_t pick = rp_pick_uniform(rp_node_hash_draw(p.step_hash, tree, key + (uint64_t)c), (uint32_t)__popcll(deck));
-        // the pick-th lowest card of the deck: a popcount search (a loop clearing `pick` bits runs up to 51 rounds)
-        uint32_t k = pick, w = (uint32_t)deck, base = 0;
-        const uint32_t plo = (uint32_t)__popc(w);
-        if (k >= plo) {
-            k -= plo;
-            w = (uint32_t)(deck >> 32);
-            base = 32;
-        }
-#pragma unroll
-        for (uint32_t half = 16; half >= 1; half >>= 1) {
-            const uint32_t c = (uint32_t)__popc(w & ((1u << half) - 1u));
-            const bool up = k >= c;
-            k -= up ? c : 0u;
-            w = up ? w >> half : w & ((1u << half) - 1u);
-            base += up ? half : 0u;
-        }
-        const uint64_t card = 1ull << base;
+        const uint64_t card = nl_nth_card(deck, pick);
         out |= card;
         deck &= ~card;
     }

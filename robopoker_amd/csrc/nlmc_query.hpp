@@ -59,6 +59,26 @@ __device__ __forceinline__ bool nlq_find(const NlTable& t, uint64_t past, uint64
     return false;
 }
 
+// The nine weights of an infoset's row, and whether it has one.  The home slot and the home row's weights are loaded together, the
+// row again only when the key was found further down its probe chain.  w is the row's bytes as stored (slots past the infoset's
+// actions included); an absent infoset leaves the home row's in it: read `found` first.
+__device__ __forceinline__ bool nlq_row_weights(const NlTable& t, uint64_t past, uint64_t choices, uint32_t present, float* w) {
+    const uint32_t home = (uint32_t)nl_key_hash(past, choices, present) & t.mask;
+    const uint4* sl = reinterpret_cast<const uint4*>(t.slots + home);
+    const uint4 lo = sl[0], hi = sl[1];
+    // the weights are floats 9..17 of the row: pieces 2..4 hold floats 8..19
+    const float4* rw = reinterpret_cast<const float4*>(t.rows + (size_t)home * 4u * NLMC_A);
+    float4 p0 = rw[2], p1 = rw[3], p2 = rw[4];
+    uint32_t row;
+    const bool found = nlq_find(t, past, choices, present, home, lo, hi, &row);
+    if (found && row != home) {
+        const float4* rr = reinterpret_cast<const float4*>(t.rows + (size_t)row * 4u * NLMC_A);
+        p0 = rr[2], p1 = rr[3], p2 = rr[4];
+    }
+    w[0] = p0.y, w[1] = p0.z, w[2] = p0.w, w[3] = p1.x, w[4] = p1.y, w[5] = p1.z, w[6] = p1.w, w[7] = p2.x, w[8] = p2.y;
+    return found;
+}
+
 struct NlQuery {
     uint64_t n;
     const uint64_t* past;

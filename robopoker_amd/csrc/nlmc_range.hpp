@@ -25,6 +25,7 @@
 #define RP_NLMC_RANGE_HPP
 
 #include "nlmc_query.hpp"
+#include "nlmc_replay.hpp"
 
 namespace rp {
 
@@ -63,58 +64,35 @@ struct NrPublic {
 
 __device__ __forceinline__ uint32_t nr_replay(const rp_nlhe_recall& rc, int kind, NrPublic& pub) {
     if (rc.n_edges > RP_NLHE_MAX_HISTORY) return RP_RECALL_LENGTH;
-    if (rc.pov > 1u || rc.dealer > 1u || rc.reserved != 0u) return RP_RECALL_SEAT;
-    const bool std_stacks = rc.stacks[0] == 0 && rc.stacks[1] == 0;
-    if (!std_stacks && (rc.stacks[0] <= 0 || rc.stacks[1] <= 0)) return RP_RECALL_SEAT;
-    if ((rc.hole & ~HAND_MASK) != 0 || __popcll(rc.hole) != 2) return RP_RECALL_CARDS;
-    uint64_t gone = rc.hole;
-    for (uint32_t s = 0; s < 3u; ++s) {
-        const uint64_t d = rc.draws[s];
-        if (d == 0) continue;
-        if ((d & ~HAND_MASK) != 0 || __popcll(d) != (s == 0 ? 3 : 1) || (d & gone) != 0) return RP_RECALL_CARDS;
-        if (s > 0 && rc.draws[s - 1] == 0) return RP_RECALL_CARDS;  // a street without the one before it
-        gone |= d;
-    }
+    // the checks, from_start, the 12-edge path and apply are nlmc_replay.hpp's: one definition for every query that replays
+    uint32_t st = nrp_check_seats(rc.pov, rc.dealer, rc.reserved, rc.stacks);
+    if (st != RP_RECALL_OK) return st;
+    uint64_t gone = 0;
+    if ((st = nrp_check_hole(rc.hole, &gone)) != RP_RECALL_OK) return st;
+    if ((st = nrp_check_draws(rc.draws, gone)) != RP_RECALL_OK) return st;
     uint32_t n_draw_edges = 0;
-    for (uint32_t i = 0; i < rc.n_edges; ++i) {
-        const uint32_t e = rc.edges[i];
-        if (e < NE_DRAW || e >= NE_RAISE0 + 10u) return RP_RECALL_EDGE;
-        n_draw_edges += e == NE_DRAW ? 1u : 0u;
-    }
+    if ((st = nrp_check_edges(rc.edges, rc.n_edges, &n_draw_edges)) != RP_RECALL_OK) return st;
     const int subject = kind == (int)RP_REACH_OPPONENT ? 1 - (int)rc.pov : (int)rc.pov;
 
-    // Game::from_start(dealer, stacks) (kicker game.rs:80-85); the seats hold no cards: nothing public depends on them, and the
-    // recall's own cards were checked against each other above
+    // the seats hold no cards: nothing public depends on them, and the recall's own cards were checked against each other above
     G2 g;
-    g.n = 2;
-    g.dealer = (int)rc.dealer;
-    g.ticker = 0;
-    g.pot = 0;
-    g.board = 0;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        g.state[i] = NL_BETTING;
-        g.stack[i] = std_stacks ? 200 : (int)rc.stacks[i];
-        g.stake[i] = g.spent[i] = 0;
-        g.cards[i] = 0;
-    }
-    for (int b = 0; b < 2; ++b) g.force_act(NlAction{NA_BLIND, g.to_post(), 0});
+    nrp_from_start(g, rc.dealer, rc.stacks, 0ull, 0ull);
 
     // the first 12 edges as resume() sees them: the trailing choice edges and their aggression
-    uint64_t tail = 0;
-    uint32_t tail_len = 0, aggr = 0, n_nodes = 0, streets = 0;
+    NrpPath path;
+    path.clear();
+    uint32_t n_nodes = 0, streets = 0;
     for (uint32_t i = 0; i < rc.n_edges; ++i) {
         const uint32_t e = rc.edges[i];
-        const int turn = g.turn();
-        if (turn == subject) {
+        if (g.turn() == subject) {
             const NlView v = nl_view(g);
             uint64_t choices;
-            const uint32_t nch = nl_choices_path(v, (int)aggr, &choices);
+            const uint32_t nch = nl_choices_path(v, (int)path.aggr, &choices);
             uint32_t slot = NR_NONE;
             for (uint32_t a = 0; a < nch; ++a)
                 if (((choices >> (5u * a)) & 31ull) == e) slot = a;
             NrNode& nd = pub.node[n_nodes++];
-            nd.past = tail;
+            nd.past = path.tail;
             nd.choices = choices;
             nd.street = (uint8_t)v.street;
             nd.slot = (uint8_t)slot;
@@ -122,34 +100,8 @@ __device__ __forceinline__ uint32_t nr_replay(const rp_nlhe_recall& rc, int kind
             nd.pad = 0;
             streets |= 1u << v.street;
         }
-        if (i < 12u) {  // MAX_PATH_EDGES: Path::from_iter takes the first 12 edges and drops the rest
-            if (e == NE_DRAW) {
-                tail = 0;
-                tail_len = aggr = 0;
-            } else {
-                tail |= (uint64_t)e << (5u * tail_len++);
-                aggr += (e == NE_SHOVE || e >= NE_OPEN0) ? 1u : 0u;
-            }
-        }
-        // NlheGame::apply
-        if (turn == NT_TERMINAL) continue;
-        if (e != NE_DRAW) {
-            while (g.turn() == NT_CHANCE) {  // the pending streets, from the recall's draws where the reference deals at random
-                const uint64_t d = rc.draws[g.street()];
-                if (d == 0) return RP_RECALL_DRAW;
-                g.force_act(NlAction{NA_DRAW, 0, d});
-            }
-            if (g.turn() == NT_TERMINAL) continue;
-        } else {
-            if (g.turn() != NT_CHANCE) continue;
-            const uint64_t d = rc.draws[g.street()];
-            if (d == 0) return RP_RECALL_DRAW;
-            g.force_act(NlAction{NA_DRAW, 0, d});
-            continue;
-        }
-        const NlAction a = nl_action_v(nl_view(g), e);
-        if (!g.allowed(a)) return RP_RECALL_ILLEGAL;
-        g.force_act(a);
+        path.push(e);
+        if ((st = nrp_apply(g, e, rc.draws)) != RP_RECALL_OK) return st;
     }
     // the board: the streets the history's Draw edges dealt, and any the replay dealt on its own
     const uint32_t dealt = max(min(n_draw_edges, 3u), (uint32_t)g.street());
@@ -187,19 +139,8 @@ __device__ __forceinline__ void nr_pair(uint32_t j, uint32_t* hi, uint32_t* lo) 
 // one factor: averaged_distribution(info).density(edge) for the infoset (nd.past, present, nd.choices) — the fold of
 // policy_distribution<>(RP_DIST_AVERAGED) over all nch slots, and the one quotient that is asked for
 __device__ __forceinline__ float nr_factor(const NlTable& t, const NrNode& nd, uint32_t present) {
-    const uint32_t home = (uint32_t)nl_key_hash(nd.past, nd.choices, present) & t.mask;
-    const uint4* sl = reinterpret_cast<const uint4*>(t.slots + home);
-    const uint4 lo = sl[0], hi = sl[1];
-    // the weights are floats 9..17 of the row: pieces 2..4 hold floats 8..19
-    const float4* rw = reinterpret_cast<const float4*>(t.rows + (size_t)home * 4u * NLMC_A);
-    float4 p0 = rw[2], p1 = rw[3], p2 = rw[4];
-    uint32_t row;
-    const bool found = nlq_find(t, nd.past, nd.choices, present, home, lo, hi, &row);
-    if (found && row != home) {
-        const float4* rr = reinterpret_cast<const float4*>(t.rows + (size_t)row * 4u * NLMC_A);
-        p0 = rr[2], p1 = rr[3], p2 = rr[4];
-    }
-    const float w[NLMC_A] = {p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w, p2.x, p2.y};
+    float w[NLMC_A];
+    const bool found = nlq_row_weights(t, nd.past, nd.choices, present, w);
     float sum = 0.0f, mine = 0.0f;
 #pragma unroll
     for (uint32_t a = 0; a < NLMC_A; ++a) {

@@ -17,6 +17,11 @@ MAX_HISTORY, MAX_HOLES, BUCKETS = _lib.RP_NLHE_MAX_HISTORY, _lib.RP_NLHE_MAX_HOL
 RECALL_DTYPE = np.dtype([("hole", "<u8"), ("draws", "<u8", (3,)), ("stacks", "<i2", (2,)), ("pov", "u1"), ("dealer", "u1"),
                          ("n_edges", "u1"), ("reserved", "u1"), ("edges", "u1", (MAX_HISTORY,))])  # rp_nlhe_recall, 88 bytes
 assert RECALL_DTYPE.itemsize == C.sizeof(_lib.NlheRecall) == 88
+LEAVES, MAX_PREFIX, MAX_ROLLOUTS = _lib.RP_NLHE_FRONTIER_LEAVES, _lib.RP_NLHE_MAX_PREFIX, 4096
+FRONTIER_DTYPE = np.dtype([("holes", "<u8", (2,)), ("draws", "<u8", (3,)), ("stacks", "<i2", (2,)), ("internal", "u1"), ("dealer", "u1"),
+                           ("n_edges", "u1"), ("n_prefix", "u1"), ("edges", "u1", (MAX_HISTORY,)), ("prefix", "u1", (MAX_PREFIX,)),
+                           ("reserved", "u1", (4,))])  # rp_nlhe_frontier, 112 bytes
+assert FRONTIER_DTYPE.itemsize == C.sizeof(_lib.NlheFrontier) == 112
 
 
 def _p(a):
@@ -47,6 +52,37 @@ class Recall:
             out[i]["pov"], out[i]["dealer"], out[i]["n_edges"] = r.pov, r.dealer, min(len(r.edges), 255)
             k = min(len(r.edges), MAX_HISTORY)
             out[i]["edges"][:k] = r.edges[:k]
+        return out
+
+
+class Frontier:
+    """A depth-limited leaf (``DepthSampler::payoffs``, crates/nlhe/src/solver.rs:51-66): ``holes`` the two-card masks of seat 0 and
+    seat 1; ``internal`` the seat whose utility is reported; ``draws`` / ``edges`` / ``stacks`` / ``dealer`` as in ``Recall`` — the
+    history from ``Game::from_start`` to the frontier state; ``prefix``: the solver's construction prefix (edge codes), the start of
+    every rollout's story, independent of ``edges``.  Nothing is checked here: a malformed frontier is answered with its status."""
+
+    def __init__(self, holes, internal=0, draws=(), edges=(), prefix=(), stacks=(0, 0), dealer=0):
+        self.holes, self.internal, self.draws, self.edges = tuple(holes), internal, tuple(draws), tuple(edges)
+        self.prefix, self.stacks, self.dealer = tuple(prefix), tuple(stacks), dealer
+
+    @staticmethod
+    def pack(frontiers) -> np.ndarray:
+        """-> FRONTIER_DTYPE[n]; edges / prefix longer than their caps keep their first entries and their true length clipped to 255
+        (status LENGTH)"""
+        if isinstance(frontiers, np.ndarray) and frontiers.dtype == FRONTIER_DTYPE:
+            return np.ascontiguousarray(frontiers)
+        if isinstance(frontiers, Frontier):
+            frontiers = [frontiers]
+        out = np.zeros(len(frontiers), FRONTIER_DTYPE)
+        for i, f in enumerate(frontiers):
+            out[i]["holes"] = f.holes
+            out[i]["draws"][: len(f.draws)] = f.draws
+            out[i]["stacks"] = f.stacks
+            out[i]["internal"], out[i]["dealer"] = f.internal, f.dealer
+            out[i]["n_edges"], out[i]["n_prefix"] = min(len(f.edges), 255), min(len(f.prefix), 255)
+            k, m = min(len(f.edges), MAX_HISTORY), min(len(f.prefix), MAX_PREFIX)
+            out[i]["edges"][:k] = f.edges[:k]
+            out[i]["prefix"][:m] = f.prefix[:m]
         return out
 
 
@@ -325,6 +361,36 @@ class NlheSolver:
         self._query_keys = (rec,)
         return mass, seen, status
 
+    # ---- frontier payoffs (include/rp_mi355x.h rp_nlhe_frontier_payoffs): biased continuation rollouts from depth-limited leaves ----
+    def frontier_payoffs(self, frontiers, bias=5.0, rollouts=16, seed=0, first_id=0, return_won=False):
+        """``DepthSampler::payoffs`` for n frontiers: (payoffs float32[n,4,4], status uint8[n]), payoffs[i,k,j] = the mean utility of
+        seat ``internal`` when it continues with strategy k and the other seat with j (0 blueprint, 1 fold-, 2 call-, 3 raise-biased).
+        ``return_won``: also won int16[n,16,rollouts], every rollout's utility.  Rollout r of cell (k, j) of frontier i draws from
+        the counter stream ((first_id + i) * 16 + 4 k + j) * rollouts + r of ``seed``: a batch split into calls with matching
+        ``first_id`` answers the same bits.  Read-only."""
+        fr = Frontier.pack(frontiers)
+        n, r = fr.size, max(int(rollouts), 1)
+        pay, status = np.zeros((n, LEAVES, LEAVES), np.float32), np.zeros(n, np.uint8)
+        won = np.zeros((n, LEAVES * LEAVES, min(r, MAX_ROLLOUTS)), np.int16) if return_won else None
+        _lib.check(self._lib.rp_nlhe_frontier_payoffs(self._h, n, _p(fr), bias, int(rollouts), seed, first_id, _p(pay), _p(won), _p(status)))
+        return (pay, status, won) if return_won else (pay, status)
+
+    def frontier_payoffs_device(self, frontiers_dev, bias=5.0, rollouts=16, seed=0, first_id=0, return_won=False):
+        """rp_nlhe_frontier_payoffs_device: ``frontiers_dev`` a device uint8 tensor [n, 112]
+        (``torch.from_numpy(Frontier.pack(..).view(np.uint8))``); -> device tensors (payoffs float32[n,4,4], status uint8[n]) and, with
+        ``return_won``, won int16[n,16,rollouts], queued on the solver's stream (``sync()`` waits)"""
+        fr = frontiers_dev.contiguous()
+        assert fr.is_cuda and fr.element_size() == 1 and fr.numel() % FRONTIER_DTYPE.itemsize == 0
+        n, d, r = fr.numel() // FRONTIER_DTYPE.itemsize, fr.device, max(int(rollouts), 1)
+        pay = torch.empty((n, LEAVES, LEAVES), dtype=torch.float32, device=d)
+        status = torch.empty(n, dtype=torch.uint8, device=d)
+        won = torch.empty((n, LEAVES * LEAVES, min(r, MAX_ROLLOUTS)), dtype=torch.int16, device=d) if return_won else None
+        torch.cuda.current_stream(d).synchronize()
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if n and t is not None else None
+        _lib.check(self._lib.rp_nlhe_frontier_payoffs_device(self._h, n, ptr(fr), bias, int(rollouts), seed, first_id, ptr(pay), ptr(won),
+                                                             ptr(status)))
+        self._query_keys = (fr,)  # the queued launch reads them
+        return (pay, status, won) if return_won else (pay, status)
 
 
 def playouts(n_players: int, n_games: int, seed: int, max_steps: int = 200, device: int = 0):
