@@ -243,6 +243,18 @@ __device__ __forceinline__ void map_touch_unless(Map& mp, bool skip, float d, fl
     mp.m = skip ? mp.m : nm;
     mp.n += skip ? 0u : 1u;
 }
+// map_touch_unless for a discount of exactly 1.0f (Summed / Floored regret, Constant / Linear / Quadratic weight: chain_params):
+// the same expressions without the `* d`.  x * 1.0f == x for every float, -0 and +-inf included, so the bits are those of
+// map_touch_unless(mp, skip, 1.0f, delta, floor_v).
+__device__ __forceinline__ void map_touch_unit_unless(Map& mp, bool skip, float delta, float floor_v) {
+    const float na = mp.n ? mp.a : 1.0f;
+    const float nb = mp.n ? mp.b + delta : delta;
+    const float nm = mp.n ? rp_maxf(mp.m + delta, floor_v) : floor_v;
+    mp.a = skip ? mp.a : na;
+    mp.b = skip ? mp.b : nb;
+    mp.m = skip ? mp.m : nm;
+    mp.n += skip ? 0u : 1u;
+}
 __device__ __forceinline__ Map map_identity() { return Map{1.0f, 0.0f, rp_u2f(0xff800000u), 0u}; }
 // F(x) = max(a x + b, m) of a map that holds at least one touch; map_apply: any map (no touch = the identity)
 __device__ __forceinline__ float map_eval(const Map& mp, float x) { return rp_maxf(mp.a * x + mp.b, mp.m); }

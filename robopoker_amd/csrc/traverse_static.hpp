@@ -661,7 +661,7 @@ __global__ __launch_bounds__(256) void k_traverse_static(DevGame g, DevInfoTab i
 // A chain is sequential and as long as its list (a root infoset meets a third of the chunk's trees, a river infoset a few):
 // the (infoset, cell) tasks are handed out in descending order of list length (a counting sort by log2 class), so the 64
 // chains of a wave have similar lengths instead of every wave waiting for one long chain.
-// LDS (dynamic): bits u32[NI][8] | lcount u32[NI] | lbase u32[NI] | pre u16[NI][8] | order u16[NI + (NI & 1)] | vals f32[5][maxdec * 256]
+// LDS (dynamic): bits u32[NI][8] | lcount u32[NI] | lbase u32[NI] | pre u16[NI][8] | order u16[NI + (NI & 1)] | vals f32[5][maxdec * 256 + lpad]
 //                | (PRUNED) lmask u32[maxdec * 256]: the expanded edges of every list entry — a regret cell skips the entries
 //                  whose edge was pruned (no touch at all: a touch would apply the discount), as k_chunk_maps<true> does
 template <class G, int W, bool PRUNED, bool REF>
@@ -732,27 +732,56 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
     const uint32_t nn = g.rows ? static_traverse<G, W, PRUNED, REF, true>(g, it, p, tree_id, present, on_built, on_decision)
                                : static_traverse<G, W, PRUNED, REF, false>(g, it, p, tree_id, present, on_built, on_decision);
     __syncthreads();
-    // the chains: task = (cell c, infoset); cells 0,1 regret, 2,3 weight, 4 the payoff sum.  The payoff sums are handed out after all
-    // the map chains, so that no wavefront mixes the two loops (measured round 4: 0.582 -> 0.562 ms per launch against task % 5)
-    for (uint32_t task = lt; task < 5u * NI; task += 256u) {
-        const uint32_t c = task < 4u * NI ? task & 3u : 4u;
-        const uint32_t info = order[task < 4u * NI ? task >> 2 : task - 4u * NI];
-        if (g.info_player[info] != p.walker) continue;
-        const uint32_t n = lcount[info], base = lbase[info];
-        const size_t slot_out = (size_t)info * nblk_max + chunk;
-        const float* v = vals + (size_t)c * L + base;
-        if (c == 4u) {  // payoff sum of the block, left fold from 0.0f
-            float sum = 0.0f;
-            for (uint32_t e = 0; e < n; ++e) sum += v[e];
-            bpsum[slot_out] = sum;
-            bcnt[slot_out] = n;
-            continue;
+    // the chains of an infoset's list: two regret cells, two weight cells, the payoff sum.  Both discounts are uniform over the grid:
+    // branched on once, around the whole phase
+    const ChainParams cpr = chain_params(p, true, tf), cpw = chain_params(p, false, tf);
+    if (cpr.d == 1.0f && cpw.d == 1.0f) {
+        // unit discounts (Summed / Floored regret with Constant / Linear / Quadratic weight): five lanes per infoset — regret 0, 1,
+        // weight 0, 1, payoff — 12 infosets per wavefront in `order`, all lanes in ONE loop without the multiplications.  The payoff
+        // lane runs the same touch with the floor -inf and takes no pruned-edge skip: its b is v[0] + v[1] + ... in list order.  A
+        // payoff is produced as 0.0f + ev and is never -0, so v[0] == 0.0f + v[0] and b equals the left fold from 0.0f bit for bit;
+        // the final 0.0f + b gives the empty list its 0.0f (b of the identity).  Its m is ignored.
+        const uint32_t ln = lt & 63u, sub = ln / 5u, c = ln - 5u * sub;
+        const float fl = c < 2u ? cpr.fl : (c < 4u ? cpw.fl : rp_u2f(0xff800000u));
+        for (uint32_t i = (lt >> 6) * 12u + sub; ln < 60u && i < NI; i += 4u * 12u) {
+            const uint32_t info = order[i];
+            if (g.info_player[info] != p.walker) continue;
+            const uint32_t n = lcount[info], base = lbase[info];
+            const size_t slot_out = (size_t)info * nblk_max + chunk;
+            const float* v = vals + (size_t)c * L + base;
+            Map mp = map_identity();
+            for (uint32_t e = 0; e < n; ++e) map_touch_unit_unless(mp, PRUNED && c < 2u && !((lmask[base + e] >> c) & 1u), v[e], fl);
+            if (c < 4u) {
+                bmaps[slot_out * 4u + c] = mp;
+            } else {
+                bpsum[slot_out] = 0.0f + mp.b;
+                bcnt[slot_out] = n;
+            }
         }
-        const bool isreg = c < 2u;
-        const ChainParams cp = chain_params(p, isreg, tf);
-        Map mp = map_identity();
-        for (uint32_t e = 0; e < n; ++e) map_touch_unless(mp, PRUNED && isreg && !((lmask[base + e] >> c) & 1u), cp.d, v[e], cp.fl);
-        bmaps[slot_out * 4u + c] = mp;
+    } else {
+        // any other discount: task = (cell c, infoset); cells 0,1 regret, 2,3 weight, 4 the payoff sum.  The payoff sums are handed out
+        // after all the map chains, so that no wavefront mixes the two loops (measured round 4: 0.582 -> 0.562 ms per launch against
+        // task % 5)
+        for (uint32_t task = lt; task < 5u * NI; task += 256u) {
+            const uint32_t c = task < 4u * NI ? task & 3u : 4u;
+            const uint32_t info = order[task < 4u * NI ? task >> 2 : task - 4u * NI];
+            if (g.info_player[info] != p.walker) continue;
+            const uint32_t n = lcount[info], base = lbase[info];
+            const size_t slot_out = (size_t)info * nblk_max + chunk;
+            const float* v = vals + (size_t)c * L + base;
+            if (c == 4u) {  // payoff sum of the block, left fold from 0.0f
+                float sum = 0.0f;
+                for (uint32_t e = 0; e < n; ++e) sum += v[e];
+                bpsum[slot_out] = sum;
+                bcnt[slot_out] = n;
+                continue;
+            }
+            const bool isreg = c < 2u;
+            const ChainParams cp = isreg ? cpr : cpw;
+            Map mp = map_identity();
+            for (uint32_t e = 0; e < n; ++e) map_touch_unless(mp, PRUNED && isreg && !((lmask[base + e] >> c) & 1u), cp.d, v[e], cp.fl);
+            bmaps[slot_out * 4u + c] = mp;
+        }
     }
     count_metrics(p, nn, ndec, 0u);
 }
