@@ -594,6 +594,71 @@ RP_API int rp_nlhe_frontier_payoffs_device(rp_nlhe* h, uint64_t n, const rp_nlhe
                                            uint32_t rollouts, uint64_t seed, uint64_t first_id, float* payoffs_dev, int16_t* won_dev,
                                            uint8_t* status_dev);
 
+/* Subgame worlds: the opponent's range cut into quantile worlds, and opponent holes dealt from a world (Nlhe::setup,
+ * nlhe/src/solver.rs:129-136 = opponent_range(recall).partition(); the Belief<NlheSecret, 4> it yields is used on every iteration of
+ * SubGameSolver::step / WorldSolver::new, subgame/src/solver.rs:94-100,149-153, world/solver.rs:49-50,66-72: a world is drawn from
+ * belief.weights() and NlheEncoder::restrict, nlhe/src/encoder.rs:148-186, rejection-samples an opponent hole of that world).  The
+ * outputs of rp_nlhe_restrict are what rp_nlhe_frontier.holes[external] wants.  Read-only exactly as the key queries above: nothing is
+ * inserted, epoch / counters / keys are unchanged, no query can fail a later step.  One workgroup per recall (csrc/nlmc_world.hpp).
+ *
+ * PARTITION (Partition::partition::<4> for Posterior<NlheSecret>, subgame/src/world/partition.rs:26-52) of mass[256], seen[256].
+ *   The entries are the buckets b with seen[b] != 0 in ascending b (the BTreeMap's order: an Abstraction is street << 8 | index and a
+ *   recall has one street).  total = the f32 left fold of the entries' masses in that order.  total <= 0 (no entry at all included):
+ *   every entry gets world 0 and weights = {0.25f, 0.25f, 0.25f, 0.25f}.  Otherwise the entries are sorted by mass, descending and
+ *   stable — equal masses keep ascending b (sort_by with partial_cmp) — segment = total / 4.0f, index = 0, bucket = accumulated =
+ *   0.0f, and for each entry in sorted order: bucket += m; accumulated += m; world[b] = index; then, if accumulated >= segment *
+ *   (float)(index + 1) && index < 3: weights[index] = bucket / total; index += 1; bucket = 0.0f — an `if`, not a `while`: at most one
+ *   advance per entry.  After the loop weights[index] = bucket / total.  A world never reached keeps weight 0.0f.  Every operation is
+ *   rounded on its own, in f32.  world[b] = RP_WORLD_NONE where seen[b] == 0.  The range's masses are finite and >= +0; for the
+ *   stand-alone entry an input outside that is unspecified in value, but no input causes an out-of-bounds access or an unbounded loop.
+ * BELIEF of a recall = PARTITION applied to rp_nlhe_opponent_range's mass / seen of that recall: the same candidates
+ *   (RP_REACH_OPPONENT, HandIterator order), the same REPLAY / KEY / REACH, the same statuses, RP_RECALL_LOOKUP exactly as there.
+ *   hole_world[j] = world[bucket(candidate j, head board)]; entries past count are RP_WORLD_NONE.  A malformed recall is the empty
+ *   row: every world RP_WORLD_NONE, weights 0.25f.
+ * RESTRICT (NlheEncoder::restrict).  Recall r's deals d = 0 .. deals are answered each on its own:
+ *   deal_id = (first_id + r) * deals + d, wrapping; draw c of a deal is rp_node_hash(seed, 1, deal_id, c) (epoch 1: the frontier's
+ *   stream uses epoch 0).
+ *   World.  A request 0..3 is that world.  A request RP_WORLD_NONE (or worlds == NULL) draws it: x = rp_u01(draw 0) * (the left fold
+ *   of weights from 0.0f); the first world whose running f32 sum exceeds x wins (x < sum); if there is none — it cannot happen with
+ *   u < 1, and is stated so that the rule is total — the highest world of non-zero weight, world 0 if every weight is zero.  Draw 0
+ *   belongs to the world whether or not it is used.  A request in 4..254 is a malformed deal: hole 0, world_out RP_WORLD_NONE,
+ *   attempts 0.
+ *   Attempt a uses draws 1 + 2a and 2 + 2a.  The free cards are the 52 cards minus pov's hole and the head board (Observation::
+ *   opponents' set, which equals deck | external's cards of encoder.rs:165).  First card: the rp_pick_uniform(h, n_free)-th lowest
+ *   free card; second card: the rp_pick_uniform(h', n_free - 1)-th lowest of the rest.  The attempt is accepted iff hole_world[that
+ *   hole] == world (Belief::remember; its empty-members clause cannot occur, a valid recall has candidates).
+ *   The answer is the hole of the first accepted attempt a in [0, RP_NLHE_MAX_REJECTIONS), attempts = a; if there is none, the hole
+ *   of attempt a = RP_NLHE_MAX_REJECTIONS whatever its world, attempts = RP_NLHE_MAX_REJECTIONS (the reference's fallback to an
+ *   unconstrained hole).  world_out = the world asked for or drawn.  How the kernel finds the first accepted attempt is its own
+ *   business (a world without a member goes straight to the fallback); the sequential rule defines the answer.
+ *   RANDOM NUMBERS.  The reference uses the thread RNG here (Deck::from(available).hole(), and the caller's draw of the world): there
+ *   is nothing of the reference's to reproduce, and the library's counter contract is used, as the frontier payoffs do.  Cards are
+ *   picked as the frontier picks them — the pick-th lowest card, uniform — not by a bit-for-bit restatement of Deck::draw's loop
+ *   (deuce/src/deck.rs:33-48): both are uniform over the ordered pairs of distinct free cards.
+ *   A recall's answer depends on seed, first_id + r, deals and its own record only, never on the batch around it.  A malformed
+ *   recall yields zero holes, RP_WORLD_NONE, zero attempts and its status; the call is still RP_OK.
+ * Arguments: world [n][256] u8, weights [n][4] f32, hole_world [n][RP_NLHE_MAX_HOLES] u8 (may be NULL), status [n] (may be NULL);
+ *   worlds [n][deals] u8 (may be NULL: every world is drawn), holes [n][deals] u64, world_out [n][deals] u8 (may be NULL), attempts
+ *   [n][deals] u16 (may be NULL).  n = 0 or deals = 0 is RP_OK without a launch; deals > 4096, or a NULL required pointer, is
+ *   RP_ERR_INVALID.  The _device forms take every pointer in DEVICE memory, queue one launch on the handle's stream and return,
+ *   ordered exactly like rp_nlhe_policy_device; the host forms stage, launch and synchronise. */
+#define RP_NLHE_WORLDS 4u             /* pokerkit::N_WORLDS */
+#define RP_NLHE_MAX_REJECTIONS 10000u /* encoder.rs:162 */
+#define RP_WORLD_NONE 0xffu           /* a bucket / hole that is no member; in a request: "draw the world" */
+RP_API int rp_nlhe_partition(rp_nlhe* h, uint64_t n, const float* mass, const uint8_t* seen, uint8_t* world, float* weights);
+RP_API int rp_nlhe_partition_device(rp_nlhe* h, uint64_t n, const float* mass_dev, const uint8_t* seen_dev, uint8_t* world_dev,
+                                    float* weights_dev);
+RP_API int rp_nlhe_belief(rp_nlhe* h, uint64_t n_recalls, const rp_nlhe_recall* recalls, uint8_t* world, float* weights,
+                          uint8_t* hole_world, uint8_t* status);
+RP_API int rp_nlhe_belief_device(rp_nlhe* h, uint64_t n_recalls, const rp_nlhe_recall* recalls_dev, uint8_t* world_dev,
+                                 float* weights_dev, uint8_t* hole_world_dev, uint8_t* status_dev);
+RP_API int rp_nlhe_restrict(rp_nlhe* h, uint64_t n_recalls, const rp_nlhe_recall* recalls, uint32_t deals, const uint8_t* worlds,
+                            uint64_t seed, uint64_t first_id, uint64_t* holes, uint8_t* world_out, uint16_t* attempts,
+                            uint8_t* status);
+RP_API int rp_nlhe_restrict_device(rp_nlhe* h, uint64_t n_recalls, const rp_nlhe_recall* recalls_dev, uint32_t deals,
+                                   const uint8_t* worlds_dev, uint64_t seed, uint64_t first_id, uint64_t* holes_dev,
+                                   uint8_t* world_out_dev, uint16_t* attempts_dev, uint8_t* status_dev);
+
 /* Multi-GPU (BASELINE configs[3]): trees sharded by rank (rank r samples tree ids [r*B, (r+1)*B) of a world*B-tree epoch
  * against a replicated table).  step_local: this rank's traversal reduced to one composed entry per infoset touched
  * (rp_profile_summarize's records, entry_bytes each, at most max_entries) plus the infoset KEY of every entry — each

@@ -36,6 +36,9 @@ RP_NLHE_MAX_HISTORY = 48
 RP_NLHE_MAX_HOLES = 1326
 RP_NLHE_FRONTIER_LEAVES = 4
 RP_NLHE_MAX_PREFIX = 12
+RP_NLHE_WORLDS = 4
+RP_NLHE_MAX_REJECTIONS = 10000
+RP_WORLD_NONE = 0xFF
 
 
 class Hyper(C.Structure):
@@ -321,6 +324,13 @@ _SIGNATURES = {
     "rp_nlhe_frontier_payoffs": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_float, C.c_uint32, C.c_uint64, C.c_uint64] + [C.c_void_p] * 3),
     "rp_nlhe_frontier_payoffs_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_float, C.c_uint32, C.c_uint64, C.c_uint64]
                                         + [C.c_void_p] * 3),
+    "rp_nlhe_partition": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
+    "rp_nlhe_partition_device": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
+    "rp_nlhe_belief": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5),
+    "rp_nlhe_belief_device": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5),
+    "rp_nlhe_restrict": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64] + [C.c_void_p] * 4),
+    "rp_nlhe_restrict_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64]
+                                + [C.c_void_p] * 4),
     "rp_nlhe_set_shard": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "rp_nlhe_entry_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
     "rp_nlhe_step_local": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),

@@ -35,6 +35,7 @@
 #include "nlmc_level.hpp"
 #include "nlmc_query.hpp"
 #include "nlmc_range.hpp"
+#include "nlmc_world.hpp"
 #include "rp_internal.h"
 #include "sortscan.hpp"
 
@@ -1215,6 +1216,147 @@ int rp_nlhe_frontier_payoffs(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* fro
     if ((rc = rp_nlhe_frontier_payoffs_device(h, n, d_fr, bias, rollouts, seed, first_id, d_pay, d_won, s.base + o_status))) return rc;
     HIP_TRY(hipMemcpyAsync(payoffs, d_pay, n * NF_CELLS * sizeof(float), hipMemcpyDeviceToHost, st));
     if (won) HIP_TRY(hipMemcpyAsync(won, d_won, b_won, hipMemcpyDeviceToHost, st));
+    if (status) HIP_TRY(hipMemcpyAsync(status, s.base + o_status, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RP_OK;
+}
+
+}  // extern "C"
+
+// ---- subgame worlds (nlmc_world.hpp): one workgroup per recall (partition: per row), at most NR_CHUNK per launch
+namespace {
+constexpr uint32_t NW_MAX_DEALS = 4096u;
+// belief (deals == 0) and restrict (deals > 0) are one kernel: every pointer in device memory
+int nw_launch(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, uint8_t* world, float* weights, uint8_t* hole_world, uint32_t deals,
+              const uint8_t* worlds, uint64_t seed, uint64_t first_id, uint64_t* holes, uint8_t* world_out, uint16_t* attempts, uint8_t* status) {
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    for (uint64_t at = 0; at < n; at += NR_CHUNK) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(NR_CHUNK, n - at);
+        NwArgs q{};
+        q.recalls = recalls + at;
+        q.world = world ? world + at * 256u : nullptr;
+        q.weights = weights ? weights + at * RP_NLHE_WORLDS : nullptr;
+        q.hole_world = hole_world ? hole_world + at * RP_NLHE_MAX_HOLES : nullptr;
+        q.deals = deals;
+        q.worlds = worlds ? worlds + at * deals : nullptr;
+        q.step_hash = rp_node_hash_step(seed, 1);
+        q.first_id = first_id + at;
+        q.holes = holes ? holes + at * deals : nullptr;
+        q.world_out = world_out ? world_out + at * deals : nullptr;
+        q.attempts = attempts ? attempts + at * deals : nullptr;
+        q.status = status ? status + at : nullptr;
+        hipLaunchKernelGGL(k_nl_world, dim3(m), dim3(NW_BLOCK), 0, st, h->tab, h->prm, q);
+        HIP_TRY(hipGetLastError());
+    }
+    return RP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rp_nlhe_partition_device(rp_nlhe* h, uint64_t n, const float* mass, const uint8_t* seen, uint8_t* world, float* weights) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_partition: NULL handle");
+    if (n == 0) return RP_OK;
+    if (!mass || !seen || !world || !weights) return rp::fail(RP_ERR_INVALID, "rp_nlhe_partition: NULL mass, seen, world or weights with n > 0");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    for (uint64_t at = 0; at < n; at += NR_CHUNK) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(NR_CHUNK, n - at);
+        hipLaunchKernelGGL(k_nl_partition, dim3(m), dim3(NW_BLOCK), 0, st, mass + at * 256u, seen + at * 256u, world + at * 256u,
+                           weights + at * RP_NLHE_WORLDS);
+        HIP_TRY(hipGetLastError());
+    }
+    return RP_OK;
+}
+
+int rp_nlhe_partition(rp_nlhe* h, uint64_t n, const float* mass, const uint8_t* seen, uint8_t* world, float* weights) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_partition: NULL handle");
+    if (n == 0) return RP_OK;
+    if (!mass || !seen || !world || !weights) return rp::fail(RP_ERR_INVALID, "rp_nlhe_partition: NULL mass, seen, world or weights with n > 0");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    // mass | weights | seen | world
+    const size_t o_weights = n * 256u * 4, o_seen = o_weights + n * RP_NLHE_WORLDS * 4, o_world = o_seen + n * 256u;
+    NrStage s;
+    HIP_TRY(hipMalloc(&s.base, o_world + n * 256u));
+    float* d_mass = reinterpret_cast<float*>(s.base);
+    float* d_weights = reinterpret_cast<float*>(s.base + o_weights);
+    HIP_TRY(hipMemcpyAsync(d_mass, mass, n * 256u * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s.base + o_seen, seen, n * 256u, hipMemcpyHostToDevice, st));
+    int rc = rp_nlhe_partition_device(h, n, d_mass, s.base + o_seen, s.base + o_world, d_weights);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(world, s.base + o_world, n * 256u, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(weights, d_weights, n * RP_NLHE_WORLDS * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RP_OK;
+}
+
+int rp_nlhe_belief_device(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, uint8_t* world, float* weights, uint8_t* hole_world,
+                          uint8_t* status) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_belief: NULL handle");
+    if (n == 0) return RP_OK;
+    if (!recalls || !world || !weights) return rp::fail(RP_ERR_INVALID, "rp_nlhe_belief: NULL recalls, world or weights with n_recalls > 0");
+    return nw_launch(h, n, recalls, world, weights, hole_world, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, status);
+}
+
+int rp_nlhe_belief(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, uint8_t* world, float* weights, uint8_t* hole_world, uint8_t* status) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_belief: NULL handle");
+    if (n == 0) return RP_OK;
+    if (!recalls || !world || !weights) return rp::fail(RP_ERR_INVALID, "rp_nlhe_belief: NULL recalls, world or weights with n_recalls > 0");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    // recalls (8-byte aligned) | weights | world | hole_world | status
+    const size_t b_hw = hole_world ? n * RP_NLHE_MAX_HOLES : 0, o_weights = n * sizeof(rp_nlhe_recall), o_world = o_weights + n * RP_NLHE_WORLDS * 4,
+                 o_hw = o_world + n * 256u, o_status = o_hw + b_hw;
+    NrStage s;
+    HIP_TRY(hipMalloc(&s.base, o_status + n));
+    rp_nlhe_recall* d_rec = reinterpret_cast<rp_nlhe_recall*>(s.base);
+    float* d_weights = reinterpret_cast<float*>(s.base + o_weights);
+    HIP_TRY(hipMemcpyAsync(d_rec, recalls, n * sizeof(rp_nlhe_recall), hipMemcpyHostToDevice, st));
+    int rc = rp_nlhe_belief_device(h, n, d_rec, s.base + o_world, d_weights, hole_world ? s.base + o_hw : nullptr, s.base + o_status);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(world, s.base + o_world, n * 256u, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(weights, d_weights, n * RP_NLHE_WORLDS * 4, hipMemcpyDeviceToHost, st));
+    if (hole_world) HIP_TRY(hipMemcpyAsync(hole_world, s.base + o_hw, b_hw, hipMemcpyDeviceToHost, st));
+    if (status) HIP_TRY(hipMemcpyAsync(status, s.base + o_status, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RP_OK;
+}
+
+int rp_nlhe_restrict_device(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, uint32_t deals, const uint8_t* worlds, uint64_t seed,
+                            uint64_t first_id, uint64_t* holes, uint8_t* world_out, uint16_t* attempts, uint8_t* status) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_restrict: NULL handle");
+    if (deals > NW_MAX_DEALS) return rp::fail(RP_ERR_INVALID, "rp_nlhe_restrict: deals %u above %u", deals, NW_MAX_DEALS);
+    if (n == 0 || deals == 0) return RP_OK;
+    if (!recalls || !holes) return rp::fail(RP_ERR_INVALID, "rp_nlhe_restrict: NULL recalls or holes with n_recalls > 0");
+    return nw_launch(h, n, recalls, nullptr, nullptr, nullptr, deals, worlds, seed, first_id, holes, world_out, attempts, status);
+}
+
+int rp_nlhe_restrict(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, uint32_t deals, const uint8_t* worlds, uint64_t seed, uint64_t first_id,
+                     uint64_t* holes, uint8_t* world_out, uint16_t* attempts, uint8_t* status) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_restrict: NULL handle");
+    if (deals > NW_MAX_DEALS) return rp::fail(RP_ERR_INVALID, "rp_nlhe_restrict: deals %u above %u", deals, NW_MAX_DEALS);
+    if (n == 0 || deals == 0) return RP_OK;
+    if (!recalls || !holes) return rp::fail(RP_ERR_INVALID, "rp_nlhe_restrict: NULL recalls or holes with n_recalls > 0");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    // holes | recalls (8-byte aligned) | attempts | worlds | world_out | status
+    const size_t nd = n * deals, o_rec = nd * 8, o_att = o_rec + n * sizeof(rp_nlhe_recall), o_worlds = o_att + nd * 2, o_out = o_worlds + nd,
+                 o_status = o_out + nd;
+    NrStage s;
+    HIP_TRY(hipMalloc(&s.base, o_status + n));
+    uint64_t* d_holes = reinterpret_cast<uint64_t*>(s.base);
+    rp_nlhe_recall* d_rec = reinterpret_cast<rp_nlhe_recall*>(s.base + o_rec);
+    uint16_t* d_att = reinterpret_cast<uint16_t*>(s.base + o_att);
+    HIP_TRY(hipMemcpyAsync(d_rec, recalls, n * sizeof(rp_nlhe_recall), hipMemcpyHostToDevice, st));
+    if (worlds) HIP_TRY(hipMemcpyAsync(s.base + o_worlds, worlds, nd, hipMemcpyHostToDevice, st));
+    int rc = rp_nlhe_restrict_device(h, n, d_rec, deals, worlds ? s.base + o_worlds : nullptr, seed, first_id, d_holes, s.base + o_out, d_att,
+                                     s.base + o_status);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(holes, d_holes, nd * 8, hipMemcpyDeviceToHost, st));
+    if (world_out) HIP_TRY(hipMemcpyAsync(world_out, s.base + o_out, nd, hipMemcpyDeviceToHost, st));
+    if (attempts) HIP_TRY(hipMemcpyAsync(attempts, d_att, nd * 2, hipMemcpyDeviceToHost, st));
     if (status) HIP_TRY(hipMemcpyAsync(status, s.base + o_status, n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return RP_OK;

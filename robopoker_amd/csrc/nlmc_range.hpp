@@ -151,6 +151,63 @@ __device__ __forceinline__ float nr_factor(const NlTable& t, const NrNode& nd, u
     return nd.slot == NR_NONE ? 0.0f : mine / sum;
 }
 
+// Phase B: the lanes stride over the candidates of a recall whose replay succeeded.  s_reach[j] = the reach of candidate j; with
+// `range`, s_bucket[j] = its bucket on the head board, otherwise its mask goes to holes_row (may be NULL).  *err: nl_bucket's.
+__device__ __forceinline__ void nr_candidates(const NlTable& t, const NlParams& p, const NrPublic& pub, bool range, float* s_reach, uint8_t* s_bucket,
+                                              uint64_t* holes_row, uint32_t tid, uint32_t* err) {
+    const uint32_t count = pub.count, streets = pub.streets, n_nodes = pub.n_nodes;
+    for (uint32_t j = tid; j < count; j += NR_BLOCK) {
+        uint32_t hi, lo;
+        nr_pair(j, &hi, &lo);
+        const uint64_t hole = (1ull << pub.free_card[hi]) | (1ull << pub.free_card[lo]);
+        uint32_t bucket[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            if ((streets >> s) & 1u) bucket[s] = nl_bucket(p, s, hole, pub.board[s], err);
+        float reach = 1.0f;
+        for (uint32_t k = 0; k < n_nodes; ++k) {
+            const NrNode nd = pub.node[k];
+            const uint32_t present = nd.street == 0 ? bucket[0] : (nd.street == 1 ? bucket[1] : (nd.street == 2 ? bucket[2] : bucket[3]));
+            reach *= nr_factor(t, nd, present);
+        }
+        s_reach[j] = reach;
+        if (range) s_bucket[j] = (uint8_t)nl_bucket(p, (int)pub.head_street, hole, pub.head, err);
+        else if (holes_row) holes_row[j] = hole;
+    }
+}
+
+// Phases A and B of one recall, by the whole workgroup (it holds two barriers): returns the recall's status, the same in every lane;
+// on RP_RECALL_OK pub, s_reach and (range) s_bucket are set for pub.count candidates.
+__device__ __forceinline__ uint32_t nr_recall(const NlTable& t, const NlParams& p, const rp_nlhe_recall& rc, int kind, bool range, NrPublic& pub,
+                                              float* s_reach, uint8_t* s_bucket, uint64_t* holes_row, uint32_t tid) {
+    if (tid == 0) {
+        pub.status = nr_replay(rc, kind, pub);
+        pub.lookup_miss = 0;
+    }
+    __syncthreads();
+    uint32_t err = 0;
+    if (pub.status == RP_RECALL_OK) nr_candidates(t, p, pub, range, s_reach, s_bucket, holes_row, tid, &err);
+    // a hole the encoder's tables do not know (the reference panics): the recall is answered as malformed.  Every lane that saw
+    // one stores the same value; the barrier orders the stores before the read
+    if (err) pub.lookup_miss = 1;
+    __syncthreads();
+    return pub.status != RP_RECALL_OK ? pub.status : (pub.lookup_miss ? (uint32_t)RP_RECALL_LOOKUP : (uint32_t)RP_RECALL_OK);
+}
+
+// Phase C of a range: lane b = bucket b, Posterior::add in candidate order — every lane reads the same LDS address in the same
+// iteration (a broadcast), and each sum is the reference's left fold
+__device__ __forceinline__ void nr_bucket_mass(const float* s_reach, const uint8_t* s_bucket, uint32_t count, uint32_t tid, float* mass, uint32_t* seen) {
+    float m = 0.0f;
+    uint32_t any = 0;
+    for (uint32_t j = 0; j < count; ++j) {
+        const bool mine = s_bucket[j] == tid;
+        m = mine ? m + s_reach[j] : m;
+        any |= mine ? 1u : 0u;
+    }
+    *mass = m;
+    *seen = any;
+}
+
 __global__ __launch_bounds__(NR_BLOCK) void k_nl_range(NlTable t, NlParams p, NrArgs q) {
     __shared__ NrPublic pub;
     __shared__ float s_reach[RP_NLHE_MAX_HOLES];
@@ -158,50 +215,15 @@ __global__ __launch_bounds__(NR_BLOCK) void k_nl_range(NlTable t, NlParams p, Nr
     const uint32_t r = blockIdx.x, tid = threadIdx.x;
     const bool range = q.mass != nullptr;
 
-    if (tid == 0) {
-        pub.status = nr_replay(q.recalls[r], q.kind, pub);
-        pub.lookup_miss = 0;
-    }
-    __syncthreads();
-    uint32_t err = 0;
-    if (pub.status == RP_RECALL_OK) {
-        const uint32_t count = pub.count, streets = pub.streets, n_nodes = pub.n_nodes;
-        for (uint32_t j = tid; j < count; j += NR_BLOCK) {
-            uint32_t hi, lo;
-            nr_pair(j, &hi, &lo);
-            const uint64_t hole = (1ull << pub.free_card[hi]) | (1ull << pub.free_card[lo]);
-            uint32_t bucket[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                if ((streets >> s) & 1u) bucket[s] = nl_bucket(p, s, hole, pub.board[s], &err);
-            float reach = 1.0f;
-            for (uint32_t k = 0; k < n_nodes; ++k) {
-                const NrNode nd = pub.node[k];
-                const uint32_t present = nd.street == 0 ? bucket[0] : (nd.street == 1 ? bucket[1] : (nd.street == 2 ? bucket[2] : bucket[3]));
-                reach *= nr_factor(t, nd, present);
-            }
-            s_reach[j] = reach;
-            if (range) s_bucket[j] = (uint8_t)nl_bucket(p, (int)pub.head_street, hole, pub.head, &err);
-            else if (q.holes) q.holes[(size_t)r * RP_NLHE_MAX_HOLES + j] = hole;
-        }
-    }
-    // a hole the encoder's tables do not know (the reference panics): the recall is answered as malformed.  Every lane that saw
-    // one stores the same value; the barrier orders the stores before the read
-    if (err) pub.lookup_miss = 1;
-    __syncthreads();
-    const uint32_t status = pub.status != RP_RECALL_OK ? pub.status : (pub.lookup_miss ? (uint32_t)RP_RECALL_LOOKUP : (uint32_t)RP_RECALL_OK);
+    const uint32_t status = nr_recall(t, p, q.recalls[r], q.kind, range, pub, s_reach, s_bucket,
+                                      q.holes ? q.holes + (size_t)r * RP_NLHE_MAX_HOLES : nullptr, tid);
     const uint32_t count = status == RP_RECALL_OK ? pub.count : 0u;
     if (tid == 0 && q.status) q.status[r] = (uint8_t)status;
 
     if (range) {
-        // lane b = bucket b: Posterior::add in candidate order
-        float m = 0.0f;
-        uint32_t any = 0;
-        for (uint32_t j = 0; j < count; ++j) {
-            const bool mine = s_bucket[j] == tid;
-            m = mine ? m + s_reach[j] : m;
-            any |= mine ? 1u : 0u;
-        }
+        float m;
+        uint32_t any;
+        nr_bucket_mass(s_reach, s_bucket, count, tid, &m, &any);
         q.mass[(size_t)r * 256u + tid] = m;
         q.seen[(size_t)r * 256u + tid] = (uint8_t)any;
         return;

@@ -22,6 +22,7 @@ FRONTIER_DTYPE = np.dtype([("holes", "<u8", (2,)), ("draws", "<u8", (3,)), ("sta
                            ("n_edges", "u1"), ("n_prefix", "u1"), ("edges", "u1", (MAX_HISTORY,)), ("prefix", "u1", (MAX_PREFIX,)),
                            ("reserved", "u1", (4,))])  # rp_nlhe_frontier, 112 bytes
 assert FRONTIER_DTYPE.itemsize == C.sizeof(_lib.NlheFrontier) == 112
+WORLDS, MAX_REJECTIONS, WORLD_NONE, MAX_DEALS = _lib.RP_NLHE_WORLDS, _lib.RP_NLHE_MAX_REJECTIONS, _lib.RP_WORLD_NONE, 4096
 
 
 def _p(a):
@@ -391,6 +392,92 @@ class NlheSolver:
                                                              ptr(status)))
         self._query_keys = (fr,)  # the queued launch reads them
         return (pay, status, won) if return_won else (pay, status)
+
+    # ---- subgame worlds (include/rp_mi355x.h rp_nlhe_partition / rp_nlhe_belief / rp_nlhe_restrict): the opponent's range in quantile worlds ----
+    def partition(self, mass, seen):
+        """``Posterior::partition::<4>`` for n rows of (mass float32[n,256], seen bool[n,256]), as ``opponent_range`` returns them:
+        (world uint8[n,256], weights float32[n,4]); world 0 holds the buckets of highest mass, WORLD_NONE marks a bucket that is no entry"""
+        mass = np.ascontiguousarray(mass, np.float32).reshape(-1, BUCKETS)
+        seen = np.ascontiguousarray(np.asarray(seen) != 0, np.uint8).reshape(-1, BUCKETS)
+        n = mass.shape[0]
+        assert seen.shape[0] == n
+        world, weights = np.zeros((n, BUCKETS), np.uint8), np.zeros((n, WORLDS), np.float32)
+        _lib.check(self._lib.rp_nlhe_partition(self._h, n, _p(mass), _p(seen), _p(world), _p(weights)))
+        return world, weights
+
+    def partition_device(self, mass_dev, seen_dev):
+        """rp_nlhe_partition_device: device tensors (mass float32[n,256], seen uint8[n,256]), as ``opponent_range_device`` returns them ->
+        device tensors (world uint8[n,256], weights float32[n,4]), queued on the solver's stream (``sync()`` waits)"""
+        mass, seen = mass_dev.contiguous(), seen_dev.contiguous()
+        assert mass.is_cuda and seen.is_cuda and mass.dtype == torch.float32 and seen.element_size() == 1
+        assert mass.numel() % BUCKETS == 0 and seen.numel() == mass.numel()
+        n, d = mass.numel() // BUCKETS, mass.device
+        world, weights = torch.empty((n, BUCKETS), dtype=torch.uint8, device=d), torch.empty((n, WORLDS), dtype=torch.float32, device=d)
+        torch.cuda.current_stream(d).synchronize()
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if n else None
+        _lib.check(self._lib.rp_nlhe_partition_device(self._h, n, ptr(mass), ptr(seen), ptr(world), ptr(weights)))
+        self._query_keys = (mass, seen)  # the queued launch reads them
+        return world, weights
+
+    def belief(self, recalls):
+        """``Nlhe::setup`` (solver.rs:129-136) = ``opponent_range(recall).partition()`` for n recalls: dict(world uint8[n,256],
+        weights float32[n,4], hole_world uint8[n,1326] — the world of every candidate hole in ``HandIterator`` order, WORLD_NONE past
+        the recall's count — and status uint8[n])"""
+        rec = Recall.pack(recalls)
+        n = rec.size
+        out = dict(world=np.zeros((n, BUCKETS), np.uint8), weights=np.zeros((n, WORLDS), np.float32),
+                   hole_world=np.zeros((n, MAX_HOLES), np.uint8), status=np.zeros(n, np.uint8))
+        _lib.check(self._lib.rp_nlhe_belief(self._h, n, _p(rec), _p(out["world"]), _p(out["weights"]), _p(out["hole_world"]), _p(out["status"])))
+        return out
+
+    def belief_device(self, recalls_dev):
+        """rp_nlhe_belief_device: ``recalls_dev`` as for ``reaches_device`` -> dict of device tensors as ``belief`` returns them"""
+        rec = recalls_dev.contiguous()
+        assert rec.is_cuda and rec.element_size() == 1 and rec.numel() % RECALL_DTYPE.itemsize == 0
+        n, d = rec.numel() // RECALL_DTYPE.itemsize, rec.device
+        out = dict(world=torch.empty((n, BUCKETS), dtype=torch.uint8, device=d), weights=torch.empty((n, WORLDS), dtype=torch.float32, device=d),
+                   hole_world=torch.empty((n, MAX_HOLES), dtype=torch.uint8, device=d), status=torch.empty(n, dtype=torch.uint8, device=d))
+        torch.cuda.current_stream(d).synchronize()
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if n else None
+        _lib.check(self._lib.rp_nlhe_belief_device(self._h, n, ptr(rec), ptr(out["world"]), ptr(out["weights"]), ptr(out["hole_world"]),
+                                                   ptr(out["status"])))
+        self._query_keys = (rec,)
+        return out
+
+    def restrict(self, recalls, deals=1, worlds=None, seed=0, first_id=0):
+        """``NlheEncoder::restrict`` for n recalls, ``deals`` opponent holes each: dict(holes uint64[n,deals], world uint8[n,deals] — the
+        world asked for or drawn — attempts uint16[n,deals] (MAX_REJECTIONS: the unconstrained fallback) and status uint8[n]).
+        ``worlds``: None (every world is drawn from the belief's weights) or uint8[n,deals] of 0..3 / WORLD_NONE (draw).  Deal d of
+        recall r draws from the counter stream (first_id + r) * deals + d of ``seed`` (epoch 1): a batch split into calls with
+        matching ``first_id`` answers the same holes.  Read-only."""
+        rec = Recall.pack(recalls)
+        n, deals = rec.size, int(deals)
+        w = None if worlds is None else np.ascontiguousarray(worlds, np.uint8).reshape(n, deals)
+        out = dict(holes=np.zeros((n, deals), np.uint64), world=np.zeros((n, deals), np.uint8), attempts=np.zeros((n, deals), np.uint16),
+                   status=np.zeros(n, np.uint8))
+        _lib.check(self._lib.rp_nlhe_restrict(self._h, n, _p(rec), deals, _p(w), seed, first_id, _p(out["holes"]), _p(out["world"]),
+                                              _p(out["attempts"]), _p(out["status"])))
+        return out
+
+    def restrict_device(self, recalls_dev, deals=1, worlds_dev=None, seed=0, first_id=0):
+        """rp_nlhe_restrict_device: ``recalls_dev`` as for ``reaches_device``, ``worlds_dev`` None or a device uint8 tensor [n, deals] ->
+        dict of device tensors (holes int64[n,deals], world uint8[n,deals], attempts int16[n,deals], status uint8[n]), queued on the
+        solver's stream (``sync()`` waits)"""
+        rec = recalls_dev.contiguous()
+        assert rec.is_cuda and rec.element_size() == 1 and rec.numel() % RECALL_DTYPE.itemsize == 0
+        n, d, deals = rec.numel() // RECALL_DTYPE.itemsize, rec.device, int(deals)
+        w = None
+        if worlds_dev is not None:
+            w = worlds_dev.contiguous()
+            assert w.is_cuda and w.element_size() == 1 and w.numel() == n * deals
+        out = dict(holes=torch.empty((n, deals), dtype=torch.int64, device=d), world=torch.empty((n, deals), dtype=torch.uint8, device=d),
+                   attempts=torch.empty((n, deals), dtype=torch.int16, device=d), status=torch.empty(n, dtype=torch.uint8, device=d))
+        torch.cuda.current_stream(d).synchronize()
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if n and deals and t is not None else None
+        _lib.check(self._lib.rp_nlhe_restrict_device(self._h, n, ptr(rec), deals, ptr(w), seed, first_id, ptr(out["holes"]), ptr(out["world"]),
+                                                     ptr(out["attempts"]), ptr(out["status"])))
+        self._query_keys = (rec, w)
+        return out
 
 
 def playouts(n_players: int, n_games: int, seed: int, max_steps: int = 200, device: int = 0):
