@@ -659,6 +659,132 @@ RP_API int rp_nlhe_restrict_device(rp_nlhe* h, uint64_t n_recalls, const rp_nlhe
                                    const uint8_t* worlds_dev, uint64_t seed, uint64_t first_id, uint64_t* holes_dev,
                                    uint8_t* world_out_dev, uint16_t* attempts_dev, uint8_t* status_dev);
 
+/* Depth-limited re-solve: DepthSolver::step x iterations and Harvest::harvest (subgame/src/depth/solver.rs:76-123), the solver
+ * Nlhe::adapt_leaf builds (nlhe/src/solver.rs:97-102) and Solved::run drives (parlor/src/players/solved.rs:39-64).  One small tree
+ * per iteration from the entry state, the local profile beside it, every frontier's rollouts in the same launch; many solves per call.
+ * Read-only exactly as the queries above: nothing is inserted, epoch / counters / keys are unchanged, no solve can fail a later step.
+ * One workgroup per solve (csrc/nlmc_depth.hpp).
+ *
+ * ENTRY = an rp_nlhe_frontier, validated and replayed by the frontier's rules with the frontier's statuses: `game` = the entry state,
+ *   `internal` = the seat the solve is for (recall.turn()), `prefix` = the solver's construction prefix (the reference passes the
+ *   trailing choice edges of the history, subgame_descents).  Both holes are required and distinct: the reference's `wipe` state
+ *   (both seats holding the hero's cards, kicker/src/witness.rs:219-221) cannot be dealt from one deck and is RP_RECALL_CARDS here.
+ * ORIGIN.  DepthGame::at_frontier (depth/game.rs:73-77) needs inner.depth() > origin at a chance node, and NlheGame::depth() is the
+ *   street (nlhe/src/game.rs:72-74).  DepthSolver::new sets origin = the entry's street, so under adapt_leaf the chance node that closes
+ *   the entry street (whose board is still the entry street's) is NOT a frontier: it is a leaf (depth/encoder.rs:109-110) valued by
+ *   stored payoffs, and no rollout is played.  That is reproduced, not repaired, and origin is an input: origin[i] = the entry's street
+ *   (or RP_NLHE_DEPTH_ORIGIN_ENTRY, or origin == NULL for the whole batch) is adapt_leaf bit for bit; origin[i] = street - 1 puts the
+ *   4 x 4 continuation game at the next street boundary.  Any other value outside -1 .. 3 is RP_RECALL_SEAT.
+ * PROFILE = DepthProfile over DepthView over this handle's table (depth/profile.rs, depth/view.rs), t = 0 at the start of a solve.  An
+ *   infoset is (kind, past, present, choices), kind 0 Game / 1 Pick.  A local row shadows the blueprint.  Absent, cum_weight and
+ *   cum_regret read max(blueprint, EPSILON), cum_payoff and cum_visits the blueprint's value; an infoset the blueprint does not hold
+ *   reads as rp_nlhe_memory reads it (default regrets, zero weight, payoff, visits).  Pick edges read 0.25f, EPSILON, 0.0f, 0.  The
+ *   first write of an edge creates it from warmstart (mccfr/src/strategy/profile.rs:94-104): weight = ((p * k) * (k + 1.0f)) / 2.0f
+ *   with k = `prior` and p = RP_DIST_AVERAGED of the blueprint row, regret = blueprint regret * (k / (float)max(epoch, 1)), payoff 0,
+ *   visits 0; Pick edges from Encounter::default() (all zero).  regret() = max(cum_regret, EPSILON), weight() likewise.  The
+ *   warmstart's regret is stated for completeness and is unobservable: an edge is first written by update_regret (every slot of an
+ *   updated infoset has a child at its head), which reads cum_regret before the edge exists and overwrites the warmstart's value.
+ * ITERATION t = 0 .. iterations: walker = seat t % 2; one tree; the Decisions of every infoset whose head's turn is the walker, all
+ *   computed on the profile as it stands, then applied in ascending head-node order; t += 1.
+ * TREE = TreeBuilder with ExternalSampling over DepthEncoder (mccfr/src/solver/builder.rs, sample/external.rs, depth/encoder.rs).
+ *   Node 0 is the entry state.  A node's branches are pushed in slot order onto one stack and the stack's top is grown next, so nodes
+ *   are numbered in depth-first order, a node's LAST slot first; a node's edges are walked newest first (petgraph), which is slot
+ *   order.  Branches of a node, by what it is:
+ *     a chance node with street > origin (a FRONTIER; they are numbered f = 0, 1, .. in node order): the four Pick(k) edges, leading
+ *       to Internal(k) nodes.  The node itself stays the chance node it was grown as (depth/encoder.rs:95-101 turns a copy into the
+ *       Frontier phase), so ExternalSampling keeps ONE of the four, uniformly (`randomly`), its info is never read and internal's
+ *       continuation is not learnt.
+ *     an Internal(k) node (turn = the seat opposite `internal`): the four Pick(j) edges to External(k, j) nodes, which are terminal
+ *       with payoff payoffs[k][j] for `internal`, -payoffs[k][j] for the other seat.  Its infoset is Pick(key of the chance node):
+ *       past = the trailing choice edges of the 12-edge path, present = the bucket of the ticker's seat (sweat() at a chance node,
+ *       kicker/src/game.rs:180-185, 656-658), choices = the one-edge Path [Draw] (game.choices at a chance node); four slots, slot c
+ *       = continuation c.
+ *     any other chance node, a terminal node: none (a leaf).
+ *     a decision node: one per edge of its infoset's choices, the state after game.apply(game.snap(game.actionize(edge))).  Its
+ *       infoset is Game(KEY), KEY = resume(prefix ++ the game edges from the entry, game) by the frontier's KEY rule (first 12 edges).
+ *   Of a node whose turn is the walker every branch is kept; of any other decision or Internal node one, by the weighted draw.
+ * DRAWS.  h(node) = rp_node_hash(seed, 2, (first_id + i) * RP_NLHE_DEPTH_MAX_ITERATIONS + t, the node's number), wrapping — epoch 2:
+ *   the frontier's stream is epoch 0, the worlds' epoch 1; a function of seed, first_id + i, t and the node only.  Frontier node:
+ *   rp_pick_uniform(h, 4).  Weighted draw (sample/external.rs:41-64 as the blueprint traversal draws it): w_a = max(q_a, EPSILON)
+ *   with q = RP_DIST_SAMPLING of weight() under the handle's rp_hyper; total = the left fold of w; u = rp_u01(h) * total; the pick
+ *   starts at slot 0 and moves on while the running sum up to and including it is <= u and a slot is left.
+ * FRONTIER PAYOFFS of frontier f of tree t are, bit for bit, rp_nlhe_frontier_payoffs' answer for the record {holes, draws, stacks,
+ *   internal, dealer, edges = the entry's edges ++ the game edges to the node, prefix} with the call's seed, bias and rollouts and
+ *   first_id + i = ((first_id + i) * RP_NLHE_DEPTH_MAX_ITERATIONS + t) * RP_NLHE_DEPTH_MAX_FRONTIERS + f (wrapping).  So a
+ *   T-iteration solve is the first T iterations of a longer one, and a batch split over calls with matching first_id answers the same.
+ *   A frontier's status other than OK is the solve's; more than RP_NLHE_DEPTH_MAX_FRONTIERS frontiers in one tree is
+ *   RP_DEPTH_FRONTIERS, a history past RP_NLHE_MAX_HISTORY RP_RECALL_LENGTH.
+ * VALUES = CfrFlow::dfs (mccfr/src/strategy/flow.rs:64-86) per infoset, f32, one rounding per operation, every sum a left fold from
+ *   0.0f in slot order.  rd = the fold of regret() over the head's choices.  For each node `root` of the span in node order:
+ *     reach = cf / sm, both folded from 1.0f up the ancestors of root, nearest first, over the edges whose parent's turn is neither
+ *       chance nor the walker: cf *= regret(edge) / (the parent's rd), sm *= the parent's q(edge);
+ *     v_a = reach * recursed_value(child a, 1.0f, 1.0f) for each child; ev = the fold of (regret(a) / rd) * v_a; payoff += ev;
+ *     delta_a += v_a - ev (from 0.0f).
+ *   recursed_value(node, rr, sr) = (rr / sr) * terminal_value(node) at a node without children, else the fold over its children of
+ *     recursed_value(child, rr' , sr'): rr' = rr * regret(edge) / rd unless the node is chance, sr' = sr * q(edge) where the node
+ *     is neither chance nor the walker's.  terminal_value (nash.rs:66-79) for hero = root's turn: at a terminal state game.payoff(hero)
+ *     = (float)(reward - spent), or +-payoffs[k][j] at an External node; at a chance leaf cum_payoff(info, first choice) of the nearest
+ *     ancestor that is not chance — a stored payoff, from the local row if there is one, else the blueprint's.
+ *   policy = RP_DIST_ITERATED of regret() (iterated_distribution).
+ * UPDATE (mccfr/src/solver/solver.rs:143-192) of one infoset, edge by edge: regret = max(cum_regret + delta, -inf) (SummedRegret);
+ *   weight = max(cum_weight + policy * (float)t, EPSILON) (LinearWeight, epoch t); payoff += (payoff_of_the_infoset - payoff) /
+ *   (float)(cum_visits + 1); visits += 1 — in that order, so on an infoset's first update cum_regret is still max(blueprint,
+ *   EPSILON) while cum_weight, payoff and visits are already the warmstart's.
+ * RESULT = Harvest at Game(KEY of the entry state): the key, n_actions, refined = iterated_distribution, visits = cum_visits, regret =
+ *   the fold of max(cum_regret, 0.0f); n_actions = 0 and a zero key where the entry state is chance or terminal (a valid solve).
+ *   sum_regret = (the fold of max(regret, 0.0f) over the local rows in exported order, slots ascending) / (float)max(t, 1) — the
+ *   reference folds a HashMap in no stated order.  Counters: nodes, infosets (updated), frontiers and rollouts (16 x rollouts each)
+ *   over all iterations.  rows[i][..]: the local profile, sorted ascending by (kind, past, present, choices); n_rows is the true count
+ *   even where it exceeds rows_cap.  A solve that fails yields a zero result (and no rows) with its status; the call is still RP_OK
+ *   and the rest of the batch is answered.
+ * BOUNDS.  Every loop is bounded; a tree of more than RP_NLHE_DEPTH_MAX_NODES nodes (or more than its share of distinct infosets or
+ *   pending branches) ends the solve with RP_DEPTH_NODES, a local profile of more than RP_NLHE_DEPTH_MAX_ROWS rows with RP_DEPTH_ROWS.
+ *   The first 64 rows of a solve live in LDS, the rest in a region of device memory the handle keeps for the call (168 bytes x 448 rows
+ *   per solve of a launch, at most 4 096 solves per launch; allocated on first use, grown on demand, freed with the handle).
+ * Arguments: NULL args, iterations outside 1 .. RP_NLHE_DEPTH_MAX_ITERATIONS, rollouts > 4096 (0 reads as 1), a bias or prior that is
+ *   not finite and positive, or reserved != 0 is RP_ERR_INVALID whatever else is passed (args are checked first, without a device);
+ *   then n = 0 is RP_OK without a launch; then a NULL handle, entries or results, or rows == NULL with rows_cap > 0, is RP_ERR_INVALID.  The _device form takes every array in DEVICE memory, queues its launches on
+ *   the handle's stream and returns, ordered exactly like rp_nlhe_policy_device; the host form stages, launches and synchronises. */
+#define RP_NLHE_DEPTH_MAX_ITERATIONS 4096u
+#define RP_NLHE_DEPTH_MAX_FRONTIERS 32u
+#define RP_NLHE_DEPTH_MAX_NODES 384u
+#define RP_NLHE_DEPTH_MAX_ROWS 512u
+#define RP_NLHE_DEPTH_ORIGIN_ENTRY 127 /* origin[i]: the entry's street */
+enum { RP_DEPTH_NODES = 8, RP_DEPTH_ROWS = 9, RP_DEPTH_FRONTIERS = 10 }; /* statuses after RP_RECALL_LOOKUP */
+typedef struct rp_nlhe_depth_args { /* one per call */
+    uint32_t iterations; /* 1 .. RP_NLHE_DEPTH_MAX_ITERATIONS */
+    uint32_t rollouts;   /* as rp_nlhe_frontier_payoffs: 0 reads as 1, > 4096 invalid */
+    float bias;          /* finite, > 0 */
+    float prior;         /* WarmstartHyperParams::prior_strength as f32: finite, > 0 */
+    uint64_t seed, first_id;
+    uint32_t rows_cap;   /* local-profile rows exported per solve; 0 = none */
+    uint32_t reserved;   /* 0 */
+} rp_nlhe_depth_args;    /* 40 bytes */
+typedef struct rp_nlhe_depth_result {
+    uint64_t past, choices; /* the key of the entry state's infoset */
+    uint32_t present;
+    uint8_t n_actions, status, pad[2];
+    float refined[9];
+    uint32_t visits[9];
+    float regret, sum_regret;
+    uint32_t iterations, n_rows;
+    uint64_t nodes, infosets, frontiers, rollouts;
+} rp_nlhe_depth_result;  /* 144 bytes */
+typedef struct rp_nlhe_depth_row {
+    uint8_t kind, n_actions, pad[2]; /* kind 0 Game, 1 Pick */
+    uint32_t present;
+    uint64_t past, choices;
+    rp_encounter enc[9];             /* zero from n_actions on */
+} rp_nlhe_depth_row;     /* 168 bytes */
+/* bias 5, rollouts 16 (FrontierHyperParams::default), prior 2^14 (WarmstartHyperParams::default), 1 iteration, no rows */
+RP_API void rp_nlhe_depth_args_default(rp_nlhe_depth_args* out);
+RP_API int rp_nlhe_depth_solve(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* entries, const int8_t* origin,
+                               const rp_nlhe_depth_args* args, rp_nlhe_depth_result* results,
+                               rp_nlhe_depth_row* rows /* [n][rows_cap] or NULL */);
+RP_API int rp_nlhe_depth_solve_device(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* entries_dev, const int8_t* origin_dev,
+                                      const rp_nlhe_depth_args* args /* host */, rp_nlhe_depth_result* results_dev,
+                                      rp_nlhe_depth_row* rows_dev);
+
 /* Multi-GPU (BASELINE configs[3]): trees sharded by rank (rank r samples tree ids [r*B, (r+1)*B) of a world*B-tree epoch
  * against a replicated table).  step_local: this rank's traversal reduced to one composed entry per infoset touched
  * (rp_profile_summarize's records, entry_bytes each, at most max_entries) plus the infoset KEY of every entry — each

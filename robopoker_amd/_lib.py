@@ -39,6 +39,12 @@ RP_NLHE_MAX_PREFIX = 12
 RP_NLHE_WORLDS = 4
 RP_NLHE_MAX_REJECTIONS = 10000
 RP_WORLD_NONE = 0xFF
+RP_NLHE_DEPTH_MAX_ITERATIONS = 4096
+RP_NLHE_DEPTH_MAX_FRONTIERS = 32
+RP_NLHE_DEPTH_MAX_NODES = 384
+RP_NLHE_DEPTH_MAX_ROWS = 512
+RP_NLHE_DEPTH_ORIGIN_ENTRY = 127
+RP_DEPTH_NODES, RP_DEPTH_ROWS, RP_DEPTH_FRONTIERS = 8, 9, 10
 
 
 class Hyper(C.Structure):
@@ -69,6 +75,26 @@ class NlheFrontier(C.Structure):
     _fields_ = [("holes", C.c_uint64 * 2), ("draws", C.c_uint64 * 3), ("stacks", C.c_int16 * 2), ("internal", C.c_uint8),
                 ("dealer", C.c_uint8), ("n_edges", C.c_uint8), ("n_prefix", C.c_uint8), ("edges", C.c_uint8 * 48),
                 ("prefix", C.c_uint8 * 12), ("reserved", C.c_uint8 * 4)]
+
+
+class NlheDepthArgs(C.Structure):
+    """rp_nlhe_depth_args: one per call (40 bytes)"""
+    _fields_ = [("iterations", C.c_uint32), ("rollouts", C.c_uint32), ("bias", C.c_float), ("prior", C.c_float), ("seed", C.c_uint64),
+                ("first_id", C.c_uint64), ("rows_cap", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class NlheDepthResult(C.Structure):
+    """rp_nlhe_depth_result: the Harvest of one solve and its counters (144 bytes)"""
+    _fields_ = [("past", C.c_uint64), ("choices", C.c_uint64), ("present", C.c_uint32), ("n_actions", C.c_uint8), ("status", C.c_uint8),
+                ("pad", C.c_uint8 * 2), ("refined", C.c_float * 9), ("visits", C.c_uint32 * 9), ("regret", C.c_float),
+                ("sum_regret", C.c_float), ("iterations", C.c_uint32), ("n_rows", C.c_uint32), ("nodes", C.c_uint64),
+                ("infosets", C.c_uint64), ("frontiers", C.c_uint64), ("rollouts", C.c_uint64)]
+
+
+class NlheDepthRow(C.Structure):
+    """rp_nlhe_depth_row: one row of a solve's local profile (168 bytes)"""
+    _fields_ = [("kind", C.c_uint8), ("n_actions", C.c_uint8), ("pad", C.c_uint8 * 2), ("present", C.c_uint32), ("past", C.c_uint64),
+                ("choices", C.c_uint64), ("enc", Encounter * 9)]
 
 
 class State(C.Structure):
@@ -324,6 +350,9 @@ _SIGNATURES = {
     "rp_nlhe_frontier_payoffs": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_float, C.c_uint32, C.c_uint64, C.c_uint64] + [C.c_void_p] * 3),
     "rp_nlhe_frontier_payoffs_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_float, C.c_uint32, C.c_uint64, C.c_uint64]
                                         + [C.c_void_p] * 3),
+    "rp_nlhe_depth_args_default": (None, [C.POINTER(NlheDepthArgs)]),
+    "rp_nlhe_depth_solve": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(NlheDepthArgs), C.c_void_p, C.c_void_p]),
+    "rp_nlhe_depth_solve_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(NlheDepthArgs), C.c_void_p, C.c_void_p]),
     "rp_nlhe_partition": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
     "rp_nlhe_partition_device": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
     "rp_nlhe_belief": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5),

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "nlmc_frontier.hpp"
+#include "nlmc_depth.hpp"
 #include "nlmc_level.hpp"
 #include "nlmc_query.hpp"
 #include "nlmc_range.hpp"
@@ -115,6 +116,8 @@ struct rp_nlhe {
     bool tree_mode_off = false;  // a tree outgrew its region once: the handle stays on the batch-wide path
     uint32_t* ex_k_parked = nullptr;  // rp_nlhe_set_exact(h, 0) on a large-batch handle: lv.ex_k while the exact evaluation is off
     uint32_t chunks = 1;  // passes per batch (RP_NLHE_CHUNKS; doubled when a pass runs out of nodes)
+    void* depth_rows = nullptr;  // rp_nlhe_depth_solve: the overflow rows of a launch's solves (grow-only)
+    size_t depth_rows_bytes = 0;
     uint32_t grid_cap = 16384;  // workgroups of the grid-stride kernels (measured: 1024 -14 %, 4096 -4 %)
 };
 
@@ -564,7 +567,7 @@ int rp_nlhe_destroy(rp_nlhe* h) {
     }
     for (void* p : h->allocs) (void)hipFree(p);
     if (h->post) (void)hipHostFree(h->post);
-    for (void* p : {h->x_keys, h->x_counts, h->x_all, h->x_packed})
+    for (void* p : {h->x_keys, h->x_counts, h->x_all, h->x_packed, h->depth_rows})
         if (p) (void)hipFree(p);
     delete h;
     return RP_OK;
@@ -1217,6 +1220,109 @@ int rp_nlhe_frontier_payoffs(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* fro
     HIP_TRY(hipMemcpyAsync(payoffs, d_pay, n * NF_CELLS * sizeof(float), hipMemcpyDeviceToHost, st));
     if (won) HIP_TRY(hipMemcpyAsync(won, d_won, b_won, hipMemcpyDeviceToHost, st));
     if (status) HIP_TRY(hipMemcpyAsync(status, s.base + o_status, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RP_OK;
+}
+
+}  // extern "C"
+
+// ---- depth-limited re-solve (nlmc_depth.hpp): one workgroup per solve, at most ND_CHUNK solves per launch
+namespace {
+// the arguments a call is refused for, before anything else is looked at (so that they can be checked without a device)
+constexpr uint64_t ND_CHUNK = 4096;  // solves per launch: what the overflow region is sized for
+int nd_check(const rp_nlhe_depth_args* a, uint32_t* rollouts) {
+    if (!a) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: NULL args");
+    if (a->iterations < 1u || a->iterations > RP_NLHE_DEPTH_MAX_ITERATIONS)
+        return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: iterations %u outside 1 .. %u", a->iterations, RP_NLHE_DEPTH_MAX_ITERATIONS);
+    if (a->rollouts > 4096u) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: rollouts %u above 4096", a->rollouts);
+    if (!(a->bias > 0.0f) || std::isinf(a->bias)) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: bias must be finite and positive");
+    if (!(a->prior > 0.0f) || std::isinf(a->prior)) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: prior must be finite and positive");
+    if (a->reserved != 0u) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: reserved must be 0");
+    *rollouts = a->rollouts == 0u ? 1u : a->rollouts;
+    return RP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void rp_nlhe_depth_args_default(rp_nlhe_depth_args* out) {
+    if (!out) return;
+    *out = rp_nlhe_depth_args{};
+    out->iterations = 1;
+    out->rollouts = 16;          // FrontierHyperParams::default
+    out->bias = 5.0f;
+    out->prior = 16384.0f;       // WarmstartHyperParams::default: 1 << 14
+}
+
+int rp_nlhe_depth_solve_device(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* entries, const int8_t* origin, const rp_nlhe_depth_args* args,
+                               rp_nlhe_depth_result* results, rp_nlhe_depth_row* rows) {
+    uint32_t rollouts = 0;
+    int rc = nd_check(args, &rollouts);
+    if (rc) return rc;
+    if (n == 0) return RP_OK;
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: NULL handle");
+    if (!entries || !results) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: NULL entries or results with n > 0");
+    if (args->rows_cap > 0u && !rows) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: NULL rows with rows_cap > 0");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    // the overflow rows of one launch's solves: launches of one call follow each other on the stream and share the region
+    const uint64_t chunk = std::min<uint64_t>(ND_CHUNK, n);
+    const size_t need = (size_t)chunk * ND_ROWS_OVF * sizeof(NdRow);
+    if (need > h->depth_rows_bytes) {
+        HIP_TRY(hipStreamSynchronize(st));  // an earlier call's launch may still write the old region
+        if (h->depth_rows) HIP_TRY(hipFree(h->depth_rows));
+        h->depth_rows = nullptr;
+        h->depth_rows_bytes = 0;
+        HIP_TRY(hipMalloc(&h->depth_rows, need));
+        h->depth_rows_bytes = need;
+    }
+    for (uint64_t at = 0; at < n; at += ND_CHUNK) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(ND_CHUNK, n - at);
+        NdArgs q{};
+        q.entries = entries + at;
+        q.origin = origin ? origin + at : nullptr;
+        q.iterations = args->iterations;
+        q.rollouts = rollouts;
+        q.rows_cap = rows ? args->rows_cap : 0u;
+        q.bias = args->bias;
+        q.prior = args->prior;
+        q.step_hash_rollout = rp_node_hash_step(args->seed, 0);
+        q.step_hash_tree = rp_node_hash_step(args->seed, 2);
+        q.first_id = args->first_id + at;
+        q.overflow = static_cast<NdRow*>(h->depth_rows);
+        q.results = results + at;
+        q.rows = rows ? rows + at * args->rows_cap : nullptr;
+        hipLaunchKernelGGL(k_nl_depth, dim3(m), dim3(ND_BLOCK), 0, st, h->tab, h->prm, q);
+        HIP_TRY(hipGetLastError());
+    }
+    return RP_OK;
+}
+
+int rp_nlhe_depth_solve(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* entries, const int8_t* origin, const rp_nlhe_depth_args* args,
+                        rp_nlhe_depth_result* results, rp_nlhe_depth_row* rows) {
+    uint32_t rollouts = 0;
+    int rc = nd_check(args, &rollouts);
+    if (rc) return rc;
+    if (n == 0) return RP_OK;
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: NULL handle");
+    if (!entries || !results) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: NULL entries or results with n > 0");
+    if (args->rows_cap > 0u && !rows) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: NULL rows with rows_cap > 0");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    // entries (8-byte aligned) | results | rows | origin
+    const size_t b_rows = n * args->rows_cap * sizeof(rp_nlhe_depth_row), o_res = n * sizeof(rp_nlhe_frontier),
+                 o_rows = o_res + n * sizeof(rp_nlhe_depth_result), o_origin = o_rows + b_rows;
+    NrStage s;
+    HIP_TRY(hipMalloc(&s.base, o_origin + n));
+    rp_nlhe_frontier* d_en = reinterpret_cast<rp_nlhe_frontier*>(s.base);
+    rp_nlhe_depth_result* d_res = reinterpret_cast<rp_nlhe_depth_result*>(s.base + o_res);
+    rp_nlhe_depth_row* d_rows = args->rows_cap ? reinterpret_cast<rp_nlhe_depth_row*>(s.base + o_rows) : nullptr;
+    int8_t* d_origin = origin ? reinterpret_cast<int8_t*>(s.base + o_origin) : nullptr;
+    HIP_TRY(hipMemcpyAsync(d_en, entries, n * sizeof(rp_nlhe_frontier), hipMemcpyHostToDevice, st));
+    if (origin) HIP_TRY(hipMemcpyAsync(d_origin, origin, n, hipMemcpyHostToDevice, st));
+    if ((rc = rp_nlhe_depth_solve_device(h, n, d_en, d_origin, args, d_res, d_rows))) return rc;
+    HIP_TRY(hipMemcpyAsync(results, d_res, n * sizeof(rp_nlhe_depth_result), hipMemcpyDeviceToHost, st));
+    if (d_rows) HIP_TRY(hipMemcpyAsync(rows, d_rows, b_rows, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return RP_OK;
 }

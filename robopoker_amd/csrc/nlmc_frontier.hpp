@@ -56,7 +56,7 @@ struct NfArgs {
 struct NfPublic {
     G2 game;       // the frontier state, both seats holding their cards
     NrpPath path;  // the prefix as a key reads it
-    uint32_t status, internal, lookup_miss, stuck;
+    uint32_t status, internal;
 };
 
 // Phase A: validation and the replay.  Returns the status; on RP_RECALL_OK the game and the prefix path are set.
@@ -158,37 +158,35 @@ __device__ __forceinline__ int nf_rollout(const NlTable& t, const NlParams& p, G
     return 0;
 }
 
-__global__ __launch_bounds__(NF_BLOCK) void k_nl_frontier(NlTable t, NlParams p, NfArgs q) {
-    __shared__ NfPublic pub;
-    __shared__ int16_t s_won[NF_CELLS * NF_CHUNK];
-    const uint32_t i = blockIdx.x, tid = threadIdx.x, rollouts = q.rollouts;
+// What the status of a frontier needs beside its replay: set by any lane of the workgroup, read after a barrier
+struct NfFlags {
+    uint32_t lookup_miss, stuck;
+};
 
-    if (tid == 0) {
-        pub.status = nf_replay(q.frontiers[i], pub);
-        pub.lookup_miss = pub.stuck = 0;
-    }
-    __syncthreads();
-    const bool valid = pub.status == RP_RECALL_OK;
+// Phases B and C for one frontier state by the whole workgroup (NF_BLOCK lanes, every lane calls it: the barriers inside are
+// reached uniformly): the 16 x rollouts games of stream `id`, folded per cell.  Lane c < 16 returns the f32 sum of cell c over r
+// ascending (the caller divides); `valid` = false plays nothing.  Shared by k_nl_frontier and the depth solver (nlmc_depth.hpp),
+// which hands in the state of a tree's frontier node.  s_won: NF_CELLS * NF_CHUNK values of LDS; won: global, may be NULL.
+__device__ __forceinline__ float nf_cells(const NlTable& t, const NlParams& p, bool valid, const G2& game, const NrpPath& path, int internal, float bias,
+                                          uint32_t rollouts, uint64_t step_hash, uint64_t id, int16_t* s_won, int16_t* won, NfFlags* flags) {
+    const uint32_t tid = threadIdx.x;
     float sum = 0.0f;  // lanes 0..15: the cell's running sum
     for (uint32_t r0 = 0; r0 < rollouts; r0 += NF_CHUNK) {
         const uint32_t rc = min(NF_CHUNK, rollouts - r0);
         uint32_t err = 0;
         bool stuck = false;
         if (valid) {
-            const G2 game = pub.game;
-            const NrpPath path = pub.path;
-            const int internal = (int)pub.internal;
             for (uint32_t x = tid; x < NF_CELLS * rc; x += NF_BLOCK) {
                 const uint32_t cell = x / rc, r = r0 + x % rc;
-                const uint64_t id = ((q.first_id + i) * NF_CELLS + cell) * rollouts + r;  // wrapping
-                const int won = nf_rollout(t, p, game, path, internal, cell >> 2, cell & 3u, q.bias, rp_node_hash_tree(q.step_hash, id), &err, &stuck);
-                s_won[x] = (int16_t)won;
-                if (q.won) q.won[((size_t)i * NF_CELLS + cell) * rollouts + r] = (int16_t)won;
+                const uint64_t rid = (id * NF_CELLS + cell) * rollouts + r;  // wrapping
+                const int w = nf_rollout(t, p, game, path, internal, cell >> 2, cell & 3u, bias, rp_node_hash_tree(step_hash, rid), &err, &stuck);
+                s_won[x] = (int16_t)w;
+                if (won) won[(size_t)cell * rollouts + r] = (int16_t)w;
             }
         }
         // every lane that saw one stores the same value; the barrier orders the stores before the read
-        if (err) pub.lookup_miss = 1;
-        if (stuck) pub.stuck = 1;
+        if (err) flags->lookup_miss = 1;
+        if (stuck) flags->stuck = 1;
         __syncthreads();
         // Phase C.  The reference sums a cell's utilities left to right in f32; this is that fold, r ascending.  The order is in
         // fact immaterial wherever |won| x rollouts <= 2^24 — with the reference's 200-chip stacks |won| <= 200 and rollouts <= 4 096,
@@ -197,8 +195,27 @@ __global__ __launch_bounds__(NF_BLOCK) void k_nl_frontier(NlTable t, NlParams p,
             for (uint32_t x = 0; x < rc; ++x) sum += (float)s_won[tid * rc + x];
         __syncthreads();
     }
+    return sum;
+}
+
+__global__ __launch_bounds__(NF_BLOCK) void k_nl_frontier(NlTable t, NlParams p, NfArgs q) {
+    __shared__ NfPublic pub;
+    __shared__ NfFlags flags;
+    __shared__ int16_t s_won[NF_CELLS * NF_CHUNK];
+    const uint32_t i = blockIdx.x, tid = threadIdx.x, rollouts = q.rollouts;
+
+    if (tid == 0) {
+        pub.status = nf_replay(q.frontiers[i], pub);
+        flags.lookup_miss = flags.stuck = 0;
+    }
+    __syncthreads();
+    const bool valid = pub.status == RP_RECALL_OK;
+    const G2 game = pub.game;
+    const NrpPath path = pub.path;
+    const float sum = nf_cells(t, p, valid, game, path, (int)pub.internal, q.bias, rollouts, q.step_hash, q.first_id + i, s_won,
+                               q.won ? q.won + (size_t)i * NF_CELLS * rollouts : nullptr, &flags);
     // a hole the encoder's tables do not know (the reference panics) or a rollout that could not go on: answered as malformed
-    const uint32_t status = !valid ? pub.status : (pub.lookup_miss ? (uint32_t)RP_RECALL_LOOKUP : (pub.stuck ? (uint32_t)RP_RECALL_ILLEGAL : (uint32_t)RP_RECALL_OK));
+    const uint32_t status = !valid ? pub.status : (flags.lookup_miss ? (uint32_t)RP_RECALL_LOOKUP : (flags.stuck ? (uint32_t)RP_RECALL_ILLEGAL : (uint32_t)RP_RECALL_OK));
     if (tid < NF_CELLS) q.payoffs[(size_t)i * NF_CELLS + tid] = status == RP_RECALL_OK ? sum / (float)rollouts : 0.0f;
     if (tid == 0 && q.status) q.status[i] = (uint8_t)status;
     if (status != RP_RECALL_OK && q.won)

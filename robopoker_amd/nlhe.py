@@ -22,6 +22,14 @@ FRONTIER_DTYPE = np.dtype([("holes", "<u8", (2,)), ("draws", "<u8", (3,)), ("sta
                            ("n_edges", "u1"), ("n_prefix", "u1"), ("edges", "u1", (MAX_HISTORY,)), ("prefix", "u1", (MAX_PREFIX,)),
                            ("reserved", "u1", (4,))])  # rp_nlhe_frontier, 112 bytes
 assert FRONTIER_DTYPE.itemsize == C.sizeof(_lib.NlheFrontier) == 112
+DEPTH_RESULT_DTYPE = np.dtype([("past", "<u8"), ("choices", "<u8"), ("present", "<u4"), ("n_actions", "u1"), ("status", "u1"), ("pad", "u1", (2,)),
+                               ("refined", "<f4", (A,)), ("visits", "<u4", (A,)), ("regret", "<f4"), ("sum_regret", "<f4"),
+                               ("iterations", "<u4"), ("n_rows", "<u4"), ("nodes", "<u8"), ("infosets", "<u8"), ("frontiers", "<u8"),
+                               ("rollouts", "<u8")])  # rp_nlhe_depth_result, 144 bytes
+DEPTH_ROW_DTYPE = np.dtype([("kind", "u1"), ("n_actions", "u1"), ("pad", "u1", (2,)), ("present", "<u4"), ("past", "<u8"), ("choices", "<u8"),
+                            ("enc", ENC_DTYPE, (A,))])  # rp_nlhe_depth_row, 168 bytes
+assert DEPTH_RESULT_DTYPE.itemsize == C.sizeof(_lib.NlheDepthResult) == 144 and DEPTH_ROW_DTYPE.itemsize == C.sizeof(_lib.NlheDepthRow) == 168
+ORIGIN_ENTRY = _lib.RP_NLHE_DEPTH_ORIGIN_ENTRY
 WORLDS, MAX_REJECTIONS, WORLD_NONE, MAX_DEALS = _lib.RP_NLHE_WORLDS, _lib.RP_NLHE_MAX_REJECTIONS, _lib.RP_WORLD_NONE, 4096
 
 
@@ -392,6 +400,82 @@ class NlheSolver:
                                                              ptr(status)))
         self._query_keys = (fr,)  # the queued launch reads them
         return (pay, status, won) if return_won else (pay, status)
+
+    # ---- depth-limited re-solve (include/rp_mi355x.h rp_nlhe_depth_solve): DepthSolver steps and harvest, many solves per launch ----
+    def _depth_args(self, iterations, rollouts, bias, prior, seed, first_id, rows_cap):
+        a = _lib.NlheDepthArgs()
+        self._lib.rp_nlhe_depth_args_default(C.byref(a))
+        a.iterations, a.seed, a.first_id, a.rows_cap = int(iterations), seed, first_id, int(rows_cap)
+        if rollouts is not None:
+            a.rollouts = int(rollouts)
+        if bias is not None:
+            a.bias = bias
+        if prior is not None:
+            a.prior = prior
+        return a
+
+    @staticmethod
+    def depth_entries(entries) -> np.ndarray:
+        """-> FRONTIER_DTYPE[n]; an entry given as a ``Frontier`` without a prefix gets the reference's (``subgame_descents``: the
+        trailing choice edges of its history)"""
+        if isinstance(entries, Frontier):
+            entries = [entries]
+        if isinstance(entries, (list, tuple)):
+            filled = []
+            for f in entries:
+                if not f.prefix:
+                    tail = []
+                    for e in reversed(f.edges):
+                        if e == 1:  # Draw
+                            break
+                        tail.append(e)
+                    f = Frontier(f.holes, f.internal, f.draws, f.edges, tail[::-1], f.stacks, f.dealer)
+                filled.append(f)
+            entries = filled
+        return Frontier.pack(entries)
+
+    @staticmethod
+    def _origin(origin, n):
+        if origin is None:
+            return None
+        o = np.full(n, origin, np.int8) if np.isscalar(origin) else np.array([ORIGIN_ENTRY if x is None else x for x in origin], np.int8)
+        assert o.size == n
+        return o
+
+    def depth_solve(self, entries, origin=None, iterations=1, rollouts=None, bias=None, prior=None, seed=0, first_id=0, rows_cap=0):
+        """``DepthSolver`` for n entries (``Frontier`` records: ``internal`` the seat solved for, ``edges`` the history to the entry
+        state, ``prefix`` the construction prefix, derived where empty): ``iterations`` steps each, then the ``Harvest`` at the entry
+        state.  ``origin``: None = every entry's own street, which is ``adapt_leaf`` as written (chance leaves valued by stored
+        payoffs, no rollouts); an int or one per entry (None = that entry's street) = the depth beyond which a chance node is a
+        frontier, ``street - 1`` for the 4 x 4 continuation game at the next street boundary.  -> (results DEPTH_RESULT_DTYPE[n],
+        rows DEPTH_ROW_DTYPE[n, rows_cap]): ``refined`` the iterated distribution over the entry infoset's choices, ``rows`` the
+        solve's local profile sorted by (kind, past, present, choices).  Solve i draws from the streams of ``first_id + i`` under
+        ``seed``: a batch split into calls with matching ``first_id`` answers the same bits.  Read-only."""
+        en = self.depth_entries(entries)
+        n = en.size
+        a = self._depth_args(iterations, rollouts, bias, prior, seed, first_id, rows_cap)
+        o = self._origin(origin, n)
+        res, rows = np.zeros(n, DEPTH_RESULT_DTYPE), np.zeros((n, int(rows_cap)), DEPTH_ROW_DTYPE)
+        _lib.check(self._lib.rp_nlhe_depth_solve(self._h, n, _p(en), _p(o), C.byref(a), _p(res), _p(rows) if rows_cap else None))
+        return res, rows
+
+    def depth_solve_device(self, entries_dev, origin_dev=None, iterations=1, rollouts=None, bias=None, prior=None, seed=0, first_id=0,
+                           rows_cap=0):
+        """rp_nlhe_depth_solve_device: ``entries_dev`` a device uint8 tensor [n, 112], ``origin_dev`` a device int8 tensor [n] or None;
+        -> device uint8 tensors (results [n, 144], rows [n, rows_cap, 168]) queued on the solver's stream (``sync()`` waits); view
+        them with DEPTH_RESULT_DTYPE / DEPTH_ROW_DTYPE on the host"""
+        en = entries_dev.contiguous()
+        assert en.is_cuda and en.element_size() == 1 and en.numel() % FRONTIER_DTYPE.itemsize == 0
+        n, d = en.numel() // FRONTIER_DTYPE.itemsize, en.device
+        assert origin_dev is None or (origin_dev.is_cuda and origin_dev.dtype == torch.int8 and origin_dev.numel() == n)
+        a = self._depth_args(iterations, rollouts, bias, prior, seed, first_id, rows_cap)
+        res = torch.empty((n, DEPTH_RESULT_DTYPE.itemsize), dtype=torch.uint8, device=d)
+        rows = torch.empty((n, int(rows_cap), DEPTH_ROW_DTYPE.itemsize), dtype=torch.uint8, device=d)
+        torch.cuda.current_stream(d).synchronize()
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if n and t is not None and t.numel() else None
+        _lib.check(self._lib.rp_nlhe_depth_solve_device(self._h, n, ptr(en), ptr(origin_dev), C.byref(a), ptr(res), ptr(rows)))
+        self._query_keys = (en, origin_dev)  # the queued launch reads them
+        return res, rows
 
     # ---- subgame worlds (include/rp_mi355x.h rp_nlhe_partition / rp_nlhe_belief / rp_nlhe_restrict): the opponent's range in quantile worlds ----
     def partition(self, mass, seen):
