@@ -785,6 +785,119 @@ RP_API int rp_nlhe_depth_solve_device(rp_nlhe* h, uint64_t n, const rp_nlhe_fron
                                       const rp_nlhe_depth_args* args /* host */, rp_nlhe_depth_result* results_dev,
                                       rp_nlhe_depth_row* rows_dev);
 
+/* Safe subgame re-solve: SubGameSolver::step x iterations and Harvest::harvest (subgame/src/solver.rs:146-229), the solver
+ * Nlhe::adapt_full builds (nlhe/src/solver.rs:121-127), and — see ADAPT_SAFE — the one adapt_safe builds.  Many solves per call, one
+ * workgroup per solve (csrc/nlmc_subgame.hpp), read-only exactly as the depth solve.  Everything the depth solve's block above states
+ * holds here word for word — ENTRY's replay and statuses, TREE, DRAWS, FRONTIER PAYOFFS, VALUES, UPDATE, the counters — except for
+ * the deltas below.
+ *
+ * WHERE THE TREE ENDS.  SubGameSolver::new passes origin = None (solver.rs:47-49), so DepthGame::at_frontier is false at every node
+ *   (depth/game.rs:73-77) and SubGameEncoder::branches gives a chance or terminal node no branch (encoder.rs:115-116; WorldEncoder the
+ *   same, world/encoder.rs:100-107).  The tree of adapt_full and of adapt_safe is therefore the rest of the ENTRY STREET, its chance
+ *   leaves valued by stored payoffs — the depth block's adapt_leaf situation — whatever the reference's own comments say about trees
+ *   "to the terminals" (nlhe/src/solver.rs:103-107, world/solver.rs:1-8).  Reproduced, not repaired.
+ * ORIGIN, per solve.  RP_NLHE_SUBGAME_ORIGIN_NONE (or origin == NULL for the whole batch) is adapt_full as written: no node is a
+ *   frontier, no rollout is played, `rollouts` and `bias` are not read.  A value in -1 .. 3 is SubGameSolver::with_origin: a chance
+ *   node with street > origin is a FRONTIER exactly as in the depth block.  Anything else is RP_RECALL_SEAT.
+ * ENTRY.  Only holes[internal] is read and validated; holes[1 - internal] may hold anything.  The draws are checked against
+ *   internal's hole alone.  `internal` is the seat the solve is for, the seat opposite is dealt anew before every tree.
+ * BELIEF, per solve, an input: hole_world[RP_NLHE_MAX_HOLES] u8 and weights[4] f32 exactly as rp_nlhe_belief(_device) writes them for
+ *   the recall {pov = internal, hole = holes[internal], draws, edges, stacks, dealer}.  The free cards are the 52 minus internal's
+ *   hole and the entry state's board, in ascending order; the candidate index of a hole is hi (hi - 1) / 2 + lo over the positions
+ *   (hi > lo) of its cards among them; count = n_free (n_free - 1) / 2.  The belief is data: a hole_world byte in 4 .. 254, and any byte
+ *   at or past count, reads as RP_WORLD_NONE.  A weight that is negative, NaN or infinite makes the solve RP_RECALL_CARDS (a belief
+ *   that could not have been dealt from; no closer status exists).  All weights zero is legal: every iteration draws world 0.
+ * DEAL of iteration t = deal d = t of recall first_id + i under rp_nlhe_restrict's rules with deals = RP_NLHE_DEPTH_MAX_ITERATIONS and
+ *   no world requested: deal_id = (first_id + i) * RP_NLHE_DEPTH_MAX_ITERATIONS + t on epoch 1, World, Attempt, the fallback at
+ *   RP_NLHE_MAX_REJECTIONS and RANDOM NUMBERS unchanged.  So rp_nlhe_restrict(deals = 4096) on that recall answers every deal of a
+ *   solve, a T-iteration solve is the first T iterations of a longer one, and a split batch answers the same.  The hole dealt is the
+ *   other seat's cards for the whole of tree t: its `present` buckets, the showdowns, and holes[1 - internal] of the record FRONTIER
+ *   PAYOFFS names.  (SubGameSolver::build's construction-time deal is discarded by the first step and is not reproduced.)
+ *   The workgroup finds the first accepted attempt with all 256 lanes (lane l tries l, l + 256, ..; the minimum accepted index wins
+ *   after each round); a world none of whose candidates belongs to it goes straight to the fallback.
+ * PROFILE = WorldProfile over DepthView (world/profile.rs, depth/view.rs).  An infoset is (world, kind, past, present, choices): every
+ *   infoset of tree t carries world_t (WorldInfo, world/info.rs; subgame/src/encoder.rs:46-57).  A local row shadows the blueprint for
+ *   its world only; a read that misses falls to the blueprint by the UNTAGGED key with the depth block's max(., EPSILON) rules
+ *   (profile.rs:120-146); the first write warm-starts from the untagged blueprint row (profile.rs:67-109 through DepthView::warmstart).
+ *   depth/view.rs was read for anything else: it forwards t, sum_regret, walker and the three sampling parameters to the blueprint
+ *   and overrides nothing further, so the depth block's PROFILE rules with the tag added are the whole of it.  A chance leaf's stored
+ *   payoff reads the local row of that world, else the blueprint.
+ * RESULT = Harvest (solver.rs:184-229) at Game(KEY of the entry state); the entry state's cards are the last iteration's (only its
+ *   `present` can depend on them, and only where the seat to act is not `internal`).  p_w = iterated_distribution at world w — from the
+ *   local row of that world, else from max(blueprint, EPSILON).
+ *     refined[a] = the f32 fold from 0.0f over w = 0 .. 3 of p_w[a] / 4.0f; Pick edges do not occur at a Game infoset.
+ *     visits[a]  = the wrapping u32 sum over w of cum_visits.
+ *     regret     = ONE f32 fold from 0.0f of max(cum_regret, 0.0f), edges outer, worlds inner.  The edges come from the keys of a
+ *       BTreeMap<Edge, _>, i.e. in kicker::Edge's derived order (edge.rs:18-27): Fold < Check < Call < Open(n) ascending < Raise(Odds)
+ *       by the pair (n, d) < Shove.  That is NOT slot order — slots run raises (grid order), Shove, Call, Fold, Check (game.rs:253-283)
+ *       — and Odds compare as pairs, not as ratios: (1,1) (1,2) (1,3) (1,4) (2,1) (2,3) (3,1) (3,2) (3,4) (5,4).  refined and visits are
+ *       per edge and are reported by slot.
+ *     sum_regret as in the depth block, over the exported row order.  drawn[w] = the iterations dealt from world w (they sum to
+ *       `iterations`), attempts = the sum of the deals' attempts, fallbacks = the deals that took the fallback.
+ *   rows[i][..]: the local profile sorted ascending by (world, kind, past, present, choices).  deals[i][t], t < deals_cap: the deal of
+ *   iteration t {hole, world, attempts}; zero past the iterations done.  A solve that fails yields a zero result, no rows and no deals.
+ * ADAPT_SAFE.  WorldSolver (world/solver.rs) over NlheEncoder / NlheProfile was read against SubGameSolver with origin = None:
+ *   WorldEncoder builds the same keys (prefix edges ++ path into NlheEncoder::resume) and stops at the same nodes (NlheGame keeps the
+ *   default is_frontier() = false); WorldProfile<NlheProfile> reads and warm-starts exactly what WorldProfile<DepthView<..>> does for
+ *   Game edges, and without a frontier there is no Pick edge; step and harvest are the same text.  So adapt_safe IS the
+ *   RP_NLHE_SUBGAME_ORIGIN_NONE answer bit for bit and needs no field of its own.
+ * BOUNDS.  As the depth block, with a local profile of up to RP_NLHE_SUBGAME_MAX_ROWS rows (RP_DEPTH_ROWS beyond): the tag splits the
+ *   infosets of both seats by world.  The first 64 rows live in LDS, the rest in a region of this entry point's own (168 bytes x 1 984
+ *   rows per solve of a launch, at most 1 024 solves per launch).  The deal's loop is bounded by RP_NLHE_MAX_REJECTIONS.  No input
+ *   causes an out-of-bounds access or an unbounded loop.
+ * Arguments: as the depth solve — args first, without a device (NULL args, iterations outside 1 .. RP_NLHE_DEPTH_MAX_ITERATIONS,
+ *   rollouts > 4096, a bias or prior not finite and positive, reserved != 0: RP_ERR_INVALID); then n = 0 is RP_OK without a launch;
+ *   then a NULL handle, entries, hole_world, weights or results, rows == NULL with rows_cap > 0 or deals == NULL with deals_cap > 0, is
+ *   RP_ERR_INVALID.  The _device form takes every array in DEVICE memory and queues its launches on the handle's stream, so the
+ *   outputs of rp_nlhe_belief_device feed it without a host copy. */
+#define RP_NLHE_SUBGAME_MAX_ROWS 2048u
+#define RP_NLHE_SUBGAME_ORIGIN_NONE 126 /* origin[i]: no frontier (adapt_full / adapt_safe as written) */
+typedef struct rp_nlhe_subgame_args { /* one per call */
+    uint32_t iterations; /* 1 .. RP_NLHE_DEPTH_MAX_ITERATIONS */
+    uint32_t rollouts;   /* as rp_nlhe_depth_args */
+    float bias;          /* finite, > 0 */
+    float prior;         /* finite, > 0 */
+    uint64_t seed, first_id;
+    uint32_t rows_cap;   /* local-profile rows exported per solve; 0 = none */
+    uint32_t deals_cap;  /* deals traced per solve; 0 = none */
+    uint32_t reserved[2]; /* 0 */
+} rp_nlhe_subgame_args;  /* 48 bytes */
+typedef struct rp_nlhe_subgame_result {
+    uint64_t past, choices; /* the key of the entry state's infoset */
+    uint32_t present;
+    uint8_t n_actions, status, pad[2];
+    float refined[9];
+    uint32_t visits[9];
+    float regret, sum_regret;
+    uint32_t iterations, n_rows;
+    uint64_t nodes, infosets, frontiers, rollouts;
+    uint32_t drawn[4];      /* iterations dealt from each world */
+    uint64_t attempts;      /* summed over the deals */
+    uint32_t fallbacks, pad2;
+} rp_nlhe_subgame_result; /* 176 bytes */
+typedef struct rp_nlhe_subgame_row {
+    uint8_t kind, n_actions, world, pad; /* kind 0 Game, 1 Pick */
+    uint32_t present;
+    uint64_t past, choices;
+    rp_encounter enc[9];                 /* zero from n_actions on */
+} rp_nlhe_subgame_row;    /* 168 bytes */
+typedef struct rp_nlhe_subgame_deal {
+    uint64_t hole;
+    uint8_t world, pad;
+    uint16_t attempts;
+    uint32_t pad2;
+} rp_nlhe_subgame_deal;   /* 16 bytes */
+/* rp_nlhe_depth_args_default's values; no rows, no deals */
+RP_API void rp_nlhe_subgame_args_default(rp_nlhe_subgame_args* out);
+RP_API int rp_nlhe_subgame_solve(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* entries, const uint8_t* hole_world /* [n][1326] */,
+                                 const float* weights /* [n][4] */, const int8_t* origin, const rp_nlhe_subgame_args* args,
+                                 rp_nlhe_subgame_result* results, rp_nlhe_subgame_row* rows /* [n][rows_cap] or NULL */,
+                                 rp_nlhe_subgame_deal* deals /* [n][deals_cap] or NULL */);
+RP_API int rp_nlhe_subgame_solve_device(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* entries_dev, const uint8_t* hole_world_dev,
+                                        const float* weights_dev, const int8_t* origin_dev,
+                                        const rp_nlhe_subgame_args* args /* host */, rp_nlhe_subgame_result* results_dev,
+                                        rp_nlhe_subgame_row* rows_dev, rp_nlhe_subgame_deal* deals_dev);
+
 /* Multi-GPU (BASELINE configs[3]): trees sharded by rank (rank r samples tree ids [r*B, (r+1)*B) of a world*B-tree epoch
  * against a replicated table).  step_local: this rank's traversal reduced to one composed entry per infoset touched
  * (rp_profile_summarize's records, entry_bytes each, at most max_entries) plus the infoset KEY of every entry — each

@@ -45,6 +45,8 @@ RP_NLHE_DEPTH_MAX_NODES = 384
 RP_NLHE_DEPTH_MAX_ROWS = 512
 RP_NLHE_DEPTH_ORIGIN_ENTRY = 127
 RP_DEPTH_NODES, RP_DEPTH_ROWS, RP_DEPTH_FRONTIERS = 8, 9, 10
+RP_NLHE_SUBGAME_MAX_ROWS = 2048
+RP_NLHE_SUBGAME_ORIGIN_NONE = 126
 
 
 class Hyper(C.Structure):
@@ -89,6 +91,28 @@ class NlheDepthResult(C.Structure):
                 ("pad", C.c_uint8 * 2), ("refined", C.c_float * 9), ("visits", C.c_uint32 * 9), ("regret", C.c_float),
                 ("sum_regret", C.c_float), ("iterations", C.c_uint32), ("n_rows", C.c_uint32), ("nodes", C.c_uint64),
                 ("infosets", C.c_uint64), ("frontiers", C.c_uint64), ("rollouts", C.c_uint64)]
+
+
+class NlheSubgameArgs(C.Structure):
+    """rp_nlhe_subgame_args: one per call (48 bytes)"""
+    _fields_ = [("iterations", C.c_uint32), ("rollouts", C.c_uint32), ("bias", C.c_float), ("prior", C.c_float), ("seed", C.c_uint64),
+                ("first_id", C.c_uint64), ("rows_cap", C.c_uint32), ("deals_cap", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class NlheSubgameResult(C.Structure):
+    """rp_nlhe_subgame_result: the Harvest of one solve over the four worlds, its counters and its deals' (176 bytes)"""
+    _fields_ = NlheDepthResult._fields_ + [("drawn", C.c_uint32 * 4), ("attempts", C.c_uint64), ("fallbacks", C.c_uint32), ("pad2", C.c_uint32)]
+
+
+class NlheSubgameRow(C.Structure):
+    """rp_nlhe_subgame_row: one row of a solve's world-tagged local profile (168 bytes)"""
+    _fields_ = [("kind", C.c_uint8), ("n_actions", C.c_uint8), ("world", C.c_uint8), ("pad", C.c_uint8), ("present", C.c_uint32),
+                ("past", C.c_uint64), ("choices", C.c_uint64), ("enc", Encounter * 9)]
+
+
+class NlheSubgameDeal(C.Structure):
+    """rp_nlhe_subgame_deal: the deal of one iteration (16 bytes)"""
+    _fields_ = [("hole", C.c_uint64), ("world", C.c_uint8), ("pad", C.c_uint8), ("attempts", C.c_uint16), ("pad2", C.c_uint32)]
 
 
 class NlheDepthRow(C.Structure):
@@ -353,6 +377,9 @@ _SIGNATURES = {
     "rp_nlhe_depth_args_default": (None, [C.POINTER(NlheDepthArgs)]),
     "rp_nlhe_depth_solve": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(NlheDepthArgs), C.c_void_p, C.c_void_p]),
     "rp_nlhe_depth_solve_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(NlheDepthArgs), C.c_void_p, C.c_void_p]),
+    "rp_nlhe_subgame_args_default": (None, [C.POINTER(NlheSubgameArgs)]),
+    "rp_nlhe_subgame_solve": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4 + [C.POINTER(NlheSubgameArgs)] + [C.c_void_p] * 3),
+    "rp_nlhe_subgame_solve_device": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4 + [C.POINTER(NlheSubgameArgs)] + [C.c_void_p] * 3),
     "rp_nlhe_partition": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
     "rp_nlhe_partition_device": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
     "rp_nlhe_belief": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5),

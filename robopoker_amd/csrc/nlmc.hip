@@ -37,6 +37,7 @@
 #include "nlmc_query.hpp"
 #include "nlmc_range.hpp"
 #include "nlmc_world.hpp"
+#include "nlmc_subgame.hpp"
 #include "rp_internal.h"
 #include "sortscan.hpp"
 
@@ -118,6 +119,8 @@ struct rp_nlhe {
     uint32_t chunks = 1;  // passes per batch (RP_NLHE_CHUNKS; doubled when a pass runs out of nodes)
     void* depth_rows = nullptr;  // rp_nlhe_depth_solve: the overflow rows of a launch's solves (grow-only)
     size_t depth_rows_bytes = 0;
+    void* subgame_rows = nullptr;  // rp_nlhe_subgame_solve: likewise, its own region
+    size_t subgame_rows_bytes = 0;
     uint32_t grid_cap = 16384;  // workgroups of the grid-stride kernels (measured: 1024 -14 %, 4096 -4 %)
 };
 
@@ -567,7 +570,7 @@ int rp_nlhe_destroy(rp_nlhe* h) {
     }
     for (void* p : h->allocs) (void)hipFree(p);
     if (h->post) (void)hipHostFree(h->post);
-    for (void* p : {h->x_keys, h->x_counts, h->x_all, h->x_packed, h->depth_rows})
+    for (void* p : {h->x_keys, h->x_counts, h->x_all, h->x_packed, h->depth_rows, h->subgame_rows})
         if (p) (void)hipFree(p);
     delete h;
     return RP_OK;
@@ -1482,3 +1485,123 @@ extern "C" RP_API int rp_nl_tree_rec(uint32_t* out, uint32_t trees) {
     return RP_OK;
 }
 #endif
+
+// ---- safe subgame re-solve (nlmc_subgame.hpp): one workgroup per solve, at most NS_CHUNK solves per launch
+namespace {
+constexpr uint64_t NS_CHUNK = 1024;  // solves per launch: what the overflow region is sized for
+int ns_check(const rp_nlhe_subgame_args* a, uint32_t* rollouts) {
+    if (!a) return rp::fail(RP_ERR_INVALID, "rp_nlhe_subgame_solve: NULL args");
+    if (a->iterations < 1u || a->iterations > RP_NLHE_DEPTH_MAX_ITERATIONS)
+        return rp::fail(RP_ERR_INVALID, "rp_nlhe_subgame_solve: iterations %u outside 1 .. %u", a->iterations, RP_NLHE_DEPTH_MAX_ITERATIONS);
+    if (a->rollouts > 4096u) return rp::fail(RP_ERR_INVALID, "rp_nlhe_subgame_solve: rollouts %u above 4096", a->rollouts);
+    if (!(a->bias > 0.0f) || std::isinf(a->bias)) return rp::fail(RP_ERR_INVALID, "rp_nlhe_subgame_solve: bias must be finite and positive");
+    if (!(a->prior > 0.0f) || std::isinf(a->prior)) return rp::fail(RP_ERR_INVALID, "rp_nlhe_subgame_solve: prior must be finite and positive");
+    if (a->reserved[0] != 0u || a->reserved[1] != 0u) return rp::fail(RP_ERR_INVALID, "rp_nlhe_subgame_solve: reserved must be 0");
+    *rollouts = a->rollouts == 0u ? 1u : a->rollouts;
+    return RP_OK;
+}
+int ns_pointers(rp_nlhe* h, const void* entries, const void* hole_world, const void* weights, const rp_nlhe_subgame_args* args, const void* results,
+                const void* rows, const void* deals) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_subgame_solve: NULL handle");
+    if (!entries || !hole_world || !weights || !results)
+        return rp::fail(RP_ERR_INVALID, "rp_nlhe_subgame_solve: NULL entries, hole_world, weights or results with n > 0");
+    if (args->rows_cap > 0u && !rows) return rp::fail(RP_ERR_INVALID, "rp_nlhe_subgame_solve: NULL rows with rows_cap > 0");
+    if (args->deals_cap > 0u && !deals) return rp::fail(RP_ERR_INVALID, "rp_nlhe_subgame_solve: NULL deals with deals_cap > 0");
+    return RP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void rp_nlhe_subgame_args_default(rp_nlhe_subgame_args* out) {
+    if (!out) return;
+    *out = rp_nlhe_subgame_args{};
+    out->iterations = 1;
+    out->rollouts = 16;     // FrontierHyperParams::default
+    out->bias = 5.0f;
+    out->prior = 16384.0f;  // WarmstartHyperParams::default: 1 << 14
+}
+
+int rp_nlhe_subgame_solve_device(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* entries, const uint8_t* hole_world, const float* weights,
+                                 const int8_t* origin, const rp_nlhe_subgame_args* args, rp_nlhe_subgame_result* results, rp_nlhe_subgame_row* rows,
+                                 rp_nlhe_subgame_deal* deals) {
+    uint32_t rollouts = 0;
+    int rc = ns_check(args, &rollouts);
+    if (rc) return rc;
+    if (n == 0) return RP_OK;
+    if ((rc = ns_pointers(h, entries, hole_world, weights, args, results, rows, deals))) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    // the overflow rows of one launch's solves: launches of one call follow each other on the stream and share the region
+    const uint64_t chunk = std::min<uint64_t>(NS_CHUNK, n);
+    const size_t need = (size_t)chunk * NS_ROWS_OVF * sizeof(NdRow);
+    if (need > h->subgame_rows_bytes) {
+        HIP_TRY(hipStreamSynchronize(st));  // an earlier call's launch may still write the old region
+        if (h->subgame_rows) HIP_TRY(hipFree(h->subgame_rows));
+        h->subgame_rows = nullptr;
+        h->subgame_rows_bytes = 0;
+        HIP_TRY(hipMalloc(&h->subgame_rows, need));
+        h->subgame_rows_bytes = need;
+    }
+    for (uint64_t at = 0; at < n; at += NS_CHUNK) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(NS_CHUNK, n - at);
+        NsArgs q{};
+        q.entries = entries + at;
+        q.hole_world = hole_world + at * RP_NLHE_MAX_HOLES;
+        q.weights = weights + at * RP_NLHE_WORLDS;
+        q.origin = origin ? origin + at : nullptr;
+        q.iterations = args->iterations;
+        q.rollouts = rollouts;
+        q.rows_cap = rows ? args->rows_cap : 0u;
+        q.deals_cap = deals ? args->deals_cap : 0u;
+        q.bias = args->bias;
+        q.prior = args->prior;
+        q.step_hash_rollout = rp_node_hash_step(args->seed, 0);
+        q.step_hash_deal = rp_node_hash_step(args->seed, 1);
+        q.step_hash_tree = rp_node_hash_step(args->seed, 2);
+        q.first_id = args->first_id + at;
+        q.overflow = static_cast<NdRow*>(h->subgame_rows);
+        q.results = results + at;
+        q.rows = q.rows_cap ? rows + at * args->rows_cap : nullptr;
+        q.deals = q.deals_cap ? deals + at * args->deals_cap : nullptr;
+        hipLaunchKernelGGL(k_nl_subgame, dim3(m), dim3(NS_BLOCK), 0, st, h->tab, h->prm, q);
+        HIP_TRY(hipGetLastError());
+    }
+    return RP_OK;
+}
+
+int rp_nlhe_subgame_solve(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* entries, const uint8_t* hole_world, const float* weights, const int8_t* origin,
+                          const rp_nlhe_subgame_args* args, rp_nlhe_subgame_result* results, rp_nlhe_subgame_row* rows, rp_nlhe_subgame_deal* deals) {
+    uint32_t rollouts = 0;
+    int rc = ns_check(args, &rollouts);
+    if (rc) return rc;
+    if (n == 0) return RP_OK;
+    if ((rc = ns_pointers(h, entries, hole_world, weights, args, results, rows, deals))) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    // entries (8-byte aligned) | results | rows | deals | weights | hole_world | origin
+    const size_t b_rows = n * args->rows_cap * sizeof(rp_nlhe_subgame_row), b_deals = n * args->deals_cap * sizeof(rp_nlhe_subgame_deal),
+                 o_res = n * sizeof(rp_nlhe_frontier), o_rows = o_res + n * sizeof(rp_nlhe_subgame_result), o_deals = o_rows + b_rows,
+                 o_weights = o_deals + b_deals, o_hw = o_weights + n * RP_NLHE_WORLDS * sizeof(float), o_origin = o_hw + n * RP_NLHE_MAX_HOLES;
+    NrStage s;
+    HIP_TRY(hipMalloc(&s.base, o_origin + n));
+    rp_nlhe_frontier* d_en = reinterpret_cast<rp_nlhe_frontier*>(s.base);
+    rp_nlhe_subgame_result* d_res = reinterpret_cast<rp_nlhe_subgame_result*>(s.base + o_res);
+    rp_nlhe_subgame_row* d_rows = args->rows_cap ? reinterpret_cast<rp_nlhe_subgame_row*>(s.base + o_rows) : nullptr;
+    rp_nlhe_subgame_deal* d_deals = args->deals_cap ? reinterpret_cast<rp_nlhe_subgame_deal*>(s.base + o_deals) : nullptr;
+    float* d_weights = reinterpret_cast<float*>(s.base + o_weights);
+    uint8_t* d_hw = reinterpret_cast<uint8_t*>(s.base + o_hw);
+    int8_t* d_origin = origin ? reinterpret_cast<int8_t*>(s.base + o_origin) : nullptr;
+    HIP_TRY(hipMemcpyAsync(d_en, entries, n * sizeof(rp_nlhe_frontier), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_weights, weights, n * RP_NLHE_WORLDS * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_hw, hole_world, n * RP_NLHE_MAX_HOLES, hipMemcpyHostToDevice, st));
+    if (origin) HIP_TRY(hipMemcpyAsync(d_origin, origin, n, hipMemcpyHostToDevice, st));
+    if ((rc = rp_nlhe_subgame_solve_device(h, n, d_en, d_hw, d_weights, d_origin, args, d_res, d_rows, d_deals))) return rc;
+    HIP_TRY(hipMemcpyAsync(results, d_res, n * sizeof(rp_nlhe_subgame_result), hipMemcpyDeviceToHost, st));
+    if (d_rows) HIP_TRY(hipMemcpyAsync(rows, d_rows, b_rows, hipMemcpyDeviceToHost, st));
+    if (d_deals) HIP_TRY(hipMemcpyAsync(deals, d_deals, b_deals, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RP_OK;
+}
+
+}  // extern "C"

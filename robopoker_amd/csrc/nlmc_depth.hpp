@@ -41,6 +41,7 @@ namespace rp {
 #define ND_INFOS 96u   // distinct infosets with children in one tree
 #define ND_TODO 256u   // pending branches
 #define ND_NONE 0xffffu
+#define ND_PRESENT_BITS 29u  // present is street << 8 | index; bits 29-30 of a local key are free for a tag, bit 31 is the kind
 static_assert(sizeof(rp_nlhe_depth_args) == 40 && sizeof(rp_nlhe_depth_result) == 144 && sizeof(rp_nlhe_depth_row) == 168, "INTEGRATION.md mirrors them");
 static_assert(NF_CELLS * NF_CHUNK * sizeof(int16_t) >= 3u * ND_NODES * sizeof(float), "the sweeps' three floats per node live in the rollouts' buffer");
 
@@ -99,13 +100,17 @@ struct NdRow {  // a local row: 168 bytes
     uint32_t v[NLMC_A];
 };
 // A solve's local profile: the first ND_ROWS_LDS rows in LDS, later ones in the solve's overflow region; `hash` (LDS) holds 32 bits of
-// every row's key so that a lookup scans LDS and touches a row only to confirm
-struct NdRows {
+// every row's key so that a lookup scans LDS and touches a row only to confirm.  H: how many of the 32 bits are kept (the subgame
+// solve, whose profile is four times as deep, keeps 16)
+template <class H>
+struct NdRowsT {
+    typedef H hash_t;
     NdRow* lds;
     NdRow* ovf;
-    uint32_t* hash;
+    H* hash;
     __device__ __forceinline__ NdRow& at(uint32_t i) const { return i < ND_ROWS_LDS ? lds[i] : ovf[i - ND_ROWS_LDS]; }
 };
+typedef NdRowsT<uint32_t> NdRows;
 struct NdShared {
     NfPublic pub;
     NfFlags flags;
@@ -180,8 +185,9 @@ __device__ __forceinline__ bool nd_blueprint(const NlTable& t, uint64_t past, ui
 __device__ __forceinline__ uint32_t nd_row_hash(uint64_t past, uint64_t choices, uint32_t present_kind) {
     return (uint32_t)(nl_key_hash(past, choices, present_kind) >> 32);
 }
-__device__ __forceinline__ int nd_find_row(const NdRows& rows, uint32_t n, uint64_t past, uint64_t choices, uint32_t present_kind) {
-    const uint32_t h = nd_row_hash(past, choices, present_kind);
+template <class R>
+__device__ __forceinline__ int nd_find_row(const R& rows, uint32_t n, uint64_t past, uint64_t choices, uint32_t present_kind) {
+    const typename R::hash_t h = (typename R::hash_t)nd_row_hash(past, choices, present_kind);
     for (uint32_t i = 0; i < n; ++i) {
         if (rows.hash[i] != h) continue;
         const NdRow& r = rows.at(i);
@@ -191,9 +197,12 @@ __device__ __forceinline__ int nd_find_row(const NdRows& rows, uint32_t n, uint6
 }
 
 // the entry of an infoset in this tree's table: found by key or made from the profile as it stands.  ND_NONE: the table is full.
-__device__ __forceinline__ uint32_t nd_info_of(const NlTable& t, NdShared& sh, NdInfo* infos, const NdRows& rows, uint64_t past, uint64_t choices,
-                                               uint32_t present, uint32_t kind, uint32_t nch, uint32_t node) {
-    const uint32_t pk = present | (kind << 31);
+// tag: bits above `present` that belong to the LOCAL key only (the subgame solve's world, nlmc_subgame.hpp); the blueprint is asked
+// without them
+template <class R>
+__device__ __forceinline__ uint32_t nd_info_of(const NlTable& t, NdShared& sh, NdInfo* infos, const R& rows, uint64_t past, uint64_t choices,
+                                               uint32_t present, uint32_t kind, uint32_t nch, uint32_t node, uint32_t tag = 0u) {
+    const uint32_t pk = present | tag | (kind << 31);
     for (uint32_t i = 0; i < sh.n_infos; ++i)
         if (infos[i].past == past && infos[i].choices == choices && infos[i].present_kind == pk) return i;
     if (sh.n_infos >= ND_INFOS) return ND_NONE;
@@ -251,9 +260,10 @@ __device__ __forceinline__ uint32_t nd_weighted(const NlParams& p, const NdInfo&
 
 // One node: TreeBuilder::next's grow + branches + sample.  `g`, `path`: the node's state; the branches kept go onto the stack in slot
 // order.  Returns a status.
-__device__ __forceinline__ uint32_t nd_grow(const NlTable& t, const NlParams& p, NdShared& sh, NdNode* nodes, NdInfo* infos, const NdRows& rows, const G2& g,
+template <class R>
+__device__ __forceinline__ uint32_t nd_grow(const NlTable& t, const NlParams& p, NdShared& sh, NdNode* nodes, NdInfo* infos, const R& rows, const G2& g,
                                             const NrpPath& path, uint32_t parent, uint32_t slot, uint32_t phase, uint32_t k, uint32_t j,
-                                            uint32_t depth, uint32_t walker, uint64_t tree_hash) {
+                                            uint32_t depth, uint32_t walker, uint64_t tree_hash, uint32_t tag = 0u) {
     if (sh.n_nodes >= ND_NODES) return RP_DEPTH_NODES;
     const uint32_t idx = sh.n_nodes++;
     NdNode& n = nodes[idx];
@@ -300,7 +310,7 @@ __device__ __forceinline__ uint32_t nd_grow(const NlTable& t, const NlParams& p,
         }
         const uint32_t present = nl_bucket(p, g.street(), seat ? g.cards[1] : g.cards[0], g.board, &err);
         if (err) return RP_RECALL_LOOKUP;
-        const uint32_t e = nd_info_of(t, sh, infos, rows, path.tail, choices, present, kind, nch, idx);
+        const uint32_t e = nd_info_of(t, sh, infos, rows, path.tail, choices, present, kind, nch, idx, tag);
         if (e == ND_NONE) return RP_DEPTH_NODES;
         n.info = (uint16_t)e;
         if (infos[e].head != idx) {  // a later node of the span
@@ -322,11 +332,12 @@ __device__ __forceinline__ uint32_t nd_grow(const NlTable& t, const NlParams& p,
 }
 
 // Phase A: the tree of iteration sh.t.  Returns a status.
-__device__ __forceinline__ uint32_t nd_build(const NlTable& t, const NlParams& p, NdShared& sh, NdNode* nodes, NdInfo* infos, const NdRows& rows,
-                                             uint32_t walker, uint64_t tree_hash) {
+template <class R>
+__device__ __forceinline__ uint32_t nd_build(const NlTable& t, const NlParams& p, NdShared& sh, NdNode* nodes, NdInfo* infos, const R& rows,
+                                             uint32_t walker, uint64_t tree_hash, uint32_t tag = 0u) {
     sh.n_nodes = sh.n_infos = sh.n_frontiers = sh.n_todo = 0;
     const G2 entry = sh.pub.game;
-    uint32_t st = nd_grow(t, p, sh, nodes, infos, rows, entry, sh.pub.path, ND_NONE, 0, NDP_DELEGATE, 0, 0, 0, walker, tree_hash);
+    uint32_t st = nd_grow(t, p, sh, nodes, infos, rows, entry, sh.pub.path, ND_NONE, 0, NDP_DELEGATE, 0, 0, 0, walker, tree_hash, tag);
     while (st == RP_RECALL_OK && sh.n_todo > 0) {
         const uint32_t leaf = sh.todo[--sh.n_todo], parent = leaf & 0xffffu, slot = leaf >> 16;
         const NdNode& pn = nodes[parent];
@@ -350,7 +361,7 @@ __device__ __forceinline__ uint32_t nd_build(const NlTable& t, const NlParams& p
             path.push(e);
             depth += 1u;
         }
-        st = nd_grow(t, p, sh, nodes, infos, rows, g, path, parent, slot, phase, k, j, depth, walker, tree_hash);
+        st = nd_grow(t, p, sh, nodes, infos, rows, g, path, parent, slot, phase, k, j, depth, walker, tree_hash, tag);
     }
     // the last descendant of every node: a subtree is the run of node numbers [node, last]
     for (uint32_t x = sh.n_nodes; st == RP_RECALL_OK && x-- > 1u;) {
@@ -379,7 +390,9 @@ __device__ __forceinline__ float nd_terminal(const NdShared& sh, const NdNode* n
 }
 
 // CfrFlow::dfs for the infoset `e` + Solver::update_*: Phase C for one infoset.  rr / sr / val: three floats per node.  Returns a status.
-__device__ __forceinline__ uint32_t nd_update(const NlTable& t, NdShared& sh, const NdNode* nodes, const NdInfo* infos, const NdRows& rows,
+// ROWS: the cap of the local profile; TAGGED: present_kind carries a tag above ND_PRESENT_BITS that the blueprint's key does not have.
+template <uint32_t ROWS = ND_ROWS, bool TAGGED = false, class R>
+__device__ __forceinline__ uint32_t nd_update(const NlTable& t, NdShared& sh, const NdNode* nodes, const NdInfo* infos, const R& rows,
                                               uint32_t ei, uint32_t walker, float prior, float* rr, float* sr, float* val) {
     const NdInfo& e = infos[ei];
     const uint32_t nch = e.nch;
@@ -436,9 +449,9 @@ __device__ __forceinline__ uint32_t nd_update(const NlTable& t, NdShared& sh, co
     const float tf = (float)sh.t;
     int ri = e.row;
     if (ri < 0) {
-        if (sh.n_rows >= ND_ROWS) return RP_DEPTH_ROWS;
+        if (sh.n_rows >= ROWS) return RP_DEPTH_ROWS;
         ri = (int)sh.n_rows++;
-        rows.hash[ri] = nd_row_hash(e.past, e.choices, e.present_kind);
+        rows.hash[ri] = (typename R::hash_t)nd_row_hash(e.past, e.choices, e.present_kind);
         NdRow& row = rows.at(ri);
         row.past = e.past;
         row.choices = e.choices;
@@ -447,7 +460,7 @@ __device__ __forceinline__ uint32_t nd_update(const NlTable& t, NdShared& sh, co
         for (uint32_t a = 0; a < NLMC_A; ++a) ws[a] = 0.0f;  // a Pick edge: Encounter::default()
         if ((e.present_kind >> 31) == 0u) {                   // warmstart: the blueprint's averaged policy scaled by k (k + 1) / 2
             float *br = sh.tmp[4], *bw = sh.tmp[5], *avg = sh.tmp[6];
-            nd_blueprint(t, e.past, e.choices, e.present_kind, br, bw, nullptr, nullptr);
+            nd_blueprint(t, e.past, e.choices, TAGGED ? e.present_kind & ((1u << ND_PRESENT_BITS) - 1u) : e.present_kind, br, bw, nullptr, nullptr);
             policy_distribution<NLMC_A>((int)RP_DIST_AVERAGED, none, bw, nch, avg);
             for (uint32_t a = 0; a < nch; ++a) ws[a] = ((avg[a] * prior) * (prior + 1.0f)) / 2.0f;
         }

@@ -30,6 +30,14 @@ DEPTH_ROW_DTYPE = np.dtype([("kind", "u1"), ("n_actions", "u1"), ("pad", "u1", (
                             ("enc", ENC_DTYPE, (A,))])  # rp_nlhe_depth_row, 168 bytes
 assert DEPTH_RESULT_DTYPE.itemsize == C.sizeof(_lib.NlheDepthResult) == 144 and DEPTH_ROW_DTYPE.itemsize == C.sizeof(_lib.NlheDepthRow) == 168
 ORIGIN_ENTRY = _lib.RP_NLHE_DEPTH_ORIGIN_ENTRY
+SUBGAME_RESULT_DTYPE = np.dtype(DEPTH_RESULT_DTYPE.descr + [("drawn", "<u4", (4,)), ("attempts", "<u8"), ("fallbacks", "<u4"),
+                                                            ("pad2", "<u4")])  # rp_nlhe_subgame_result, 176 bytes
+SUBGAME_ROW_DTYPE = np.dtype([("kind", "u1"), ("n_actions", "u1"), ("world", "u1"), ("pad", "u1"), ("present", "<u4"), ("past", "<u8"),
+                              ("choices", "<u8"), ("enc", ENC_DTYPE, (A,))])  # rp_nlhe_subgame_row, 168 bytes
+SUBGAME_DEAL_DTYPE = np.dtype([("hole", "<u8"), ("world", "u1"), ("pad", "u1"), ("attempts", "<u2"), ("pad2", "<u4")])  # rp_nlhe_subgame_deal
+assert SUBGAME_RESULT_DTYPE.itemsize == C.sizeof(_lib.NlheSubgameResult) == 176 and SUBGAME_ROW_DTYPE.itemsize == C.sizeof(_lib.NlheSubgameRow) == 168
+assert SUBGAME_DEAL_DTYPE.itemsize == C.sizeof(_lib.NlheSubgameDeal) == 16 and C.sizeof(_lib.NlheSubgameArgs) == 48
+ORIGIN_NONE = _lib.RP_NLHE_SUBGAME_ORIGIN_NONE
 WORLDS, MAX_REJECTIONS, WORLD_NONE, MAX_DEALS = _lib.RP_NLHE_WORLDS, _lib.RP_NLHE_MAX_REJECTIONS, _lib.RP_WORLD_NONE, 4096
 
 
@@ -476,6 +484,87 @@ class NlheSolver:
         _lib.check(self._lib.rp_nlhe_depth_solve_device(self._h, n, ptr(en), ptr(origin_dev), C.byref(a), ptr(res), ptr(rows)))
         self._query_keys = (en, origin_dev)  # the queued launch reads them
         return res, rows
+
+    # ---- safe subgame re-solve (include/rp_mi355x.h rp_nlhe_subgame_solve): SubGameSolver steps and harvest, many solves per launch ----
+    def _subgame_args(self, iterations, rollouts, bias, prior, seed, first_id, rows_cap, deals_cap):
+        a = _lib.NlheSubgameArgs()
+        self._lib.rp_nlhe_subgame_args_default(C.byref(a))
+        a.iterations, a.seed, a.first_id, a.rows_cap, a.deals_cap = int(iterations), seed, first_id, int(rows_cap), int(deals_cap)
+        if rollouts is not None:
+            a.rollouts = int(rollouts)
+        if bias is not None:
+            a.bias = bias
+        if prior is not None:
+            a.prior = prior
+        return a
+
+    @staticmethod
+    def subgame_recalls(entries) -> np.ndarray:
+        """-> RECALL_DTYPE[n]: the recall whose belief a subgame solve of each entry wants — ``internal``'s point of view of the
+        entry's history (``belief(subgame_recalls(entries))`` yields ``hole_world`` / ``weights`` for ``subgame_solve``)"""
+        en = NlheSolver.depth_entries(entries)
+        rec = np.zeros(en.size, RECALL_DTYPE)
+        for i, f in enumerate(en):
+            rec[i]["hole"] = f["holes"][min(int(f["internal"]), 1)]
+            for k in ("draws", "stacks", "dealer", "n_edges", "edges"):
+                rec[i][k] = f[k]
+            rec[i]["pov"] = f["internal"]
+        return rec
+
+    @staticmethod
+    def _subgame_origin(origin, n):
+        if origin is None:
+            return None
+        o = np.full(n, origin, np.int8) if np.isscalar(origin) else np.array([ORIGIN_NONE if x is None else x for x in origin], np.int8)
+        assert o.size == n
+        return o
+
+    def subgame_solve(self, entries, beliefs, origin=None, iterations=1, rollouts=None, bias=None, prior=None, seed=0, first_id=0, rows_cap=0,
+                      deals_cap=0):
+        """``SubGameSolver`` (``adapt_full``; ``adapt_safe`` answers the same) for n entries as ``depth_solve`` takes them, except that
+        the hole of the seat opposite ``internal`` is not read: before every iteration that seat is dealt a hole from a world drawn
+        from the belief (``NlheEncoder::restrict``, deal ``t`` of ``restrict(.., deals=4096)`` for the same ``seed`` / ``first_id``),
+        and every infoset of that iteration's tree is tagged with the world.  ``beliefs``: (hole_world uint8[n,1326], weights
+        float32[n,4]) or the dict ``belief()`` returns.  ``origin``: None (or None per entry) = no frontier, the solver as written — the
+        tree is the rest of the entry street, chance leaves valued by stored payoffs; an int in -1 .. 3 = ``with_origin``.
+        -> (results SUBGAME_RESULT_DTYPE[n], rows SUBGAME_ROW_DTYPE[n, rows_cap] sorted by (world, kind, past, present, choices),
+        deals SUBGAME_DEAL_DTYPE[n, deals_cap]): ``refined`` averages the four worlds' iterated distributions.  Read-only."""
+        en = self.depth_entries(entries)
+        n = en.size
+        if isinstance(beliefs, dict):
+            beliefs = (beliefs["hole_world"], beliefs["weights"])
+        hw = np.ascontiguousarray(beliefs[0], np.uint8).reshape(n, MAX_HOLES)
+        wt = np.ascontiguousarray(beliefs[1], np.float32).reshape(n, WORLDS)
+        a = self._subgame_args(iterations, rollouts, bias, prior, seed, first_id, rows_cap, deals_cap)
+        o = self._subgame_origin(origin, n)
+        res, rows = np.zeros(n, SUBGAME_RESULT_DTYPE), np.zeros((n, int(rows_cap)), SUBGAME_ROW_DTYPE)
+        deals = np.zeros((n, int(deals_cap)), SUBGAME_DEAL_DTYPE)
+        _lib.check(self._lib.rp_nlhe_subgame_solve(self._h, n, _p(en), _p(hw), _p(wt), _p(o), C.byref(a), _p(res), _p(rows) if rows_cap else None,
+                                                   _p(deals) if deals_cap else None))
+        return res, rows, deals
+
+    def subgame_solve_device(self, entries_dev, hole_world_dev, weights_dev, origin_dev=None, iterations=1, rollouts=None, bias=None, prior=None,
+                             seed=0, first_id=0, rows_cap=0, deals_cap=0):
+        """rp_nlhe_subgame_solve_device: ``entries_dev`` a device uint8 tensor [n, 112]; ``hole_world_dev`` uint8 [n, 1326] and
+        ``weights_dev`` float32 [n, 4] as ``belief_device`` returns them (no host copy in between); ``origin_dev`` a device int8
+        tensor [n] or None; -> device uint8 tensors (results [n, 176], rows [n, rows_cap, 168], deals [n, deals_cap, 16]) queued on the
+        solver's stream (``sync()`` waits); view them with the SUBGAME_*_DTYPEs on the host"""
+        en, hw, wt = entries_dev.contiguous(), hole_world_dev.contiguous(), weights_dev.contiguous()
+        assert en.is_cuda and en.element_size() == 1 and en.numel() % FRONTIER_DTYPE.itemsize == 0
+        n, d = en.numel() // FRONTIER_DTYPE.itemsize, en.device
+        assert hw.is_cuda and hw.element_size() == 1 and hw.numel() == n * MAX_HOLES
+        assert wt.is_cuda and wt.dtype == torch.float32 and wt.numel() == n * WORLDS
+        assert origin_dev is None or (origin_dev.is_cuda and origin_dev.dtype == torch.int8 and origin_dev.numel() == n)
+        a = self._subgame_args(iterations, rollouts, bias, prior, seed, first_id, rows_cap, deals_cap)
+        res = torch.empty((n, SUBGAME_RESULT_DTYPE.itemsize), dtype=torch.uint8, device=d)
+        rows = torch.empty((n, int(rows_cap), SUBGAME_ROW_DTYPE.itemsize), dtype=torch.uint8, device=d)
+        deals = torch.empty((n, int(deals_cap), SUBGAME_DEAL_DTYPE.itemsize), dtype=torch.uint8, device=d)
+        torch.cuda.current_stream(d).synchronize()
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if n and t is not None and t.numel() else None
+        _lib.check(self._lib.rp_nlhe_subgame_solve_device(self._h, n, ptr(en), ptr(hw), ptr(wt), ptr(origin_dev), C.byref(a), ptr(res), ptr(rows),
+                                                          ptr(deals)))
+        self._query_keys = (en, hw, wt, origin_dev)  # the queued launch reads them
+        return res, rows, deals
 
     # ---- subgame worlds (include/rp_mi355x.h rp_nlhe_partition / rp_nlhe_belief / rp_nlhe_restrict): the opponent's range in quantile worlds ----
     def partition(self, mass, seen):
