@@ -73,6 +73,7 @@ struct rp_mccfr {
     void* d_payoffs = nullptr;
     void* d_info_actions = nullptr;
     void* d_info_player = nullptr;
+    void* d_info_rank = nullptr;  // DevGame::info_rank, then DevGame::rank_info
     void* d_scratch = nullptr;
     void* d_dec = nullptr;
     void* d_summary = nullptr;
@@ -226,14 +227,13 @@ int alloc_batch_buffers(rp_mccfr* h, uint32_t batch) {
     so.counts = sw; sw += nic;
     so.offs = sw; sw += nic;
     so.total = sw;
-    // per-(infoset, block) maps of the composed update
+    // per-block rows of the composed update's maps (bmap_index): one walker's infosets at a time, so sized by the larger player
     if (h->d_bmaps) HIP_TRY(hipFree(h->d_bmaps));
     h->d_bmaps = nullptr;
     const size_t nblk_max = (stride + RP_COMPOSE_CHUNK - 1) / RP_COMPOSE_CHUNK;
     // ... followed by the group maps and the arrival counters of k_combine2
     const size_t ngrp_max = (nblk_max + RP_FOLD_GROUP - 1) / RP_FOLD_GROUP;
-    const size_t per_slot = 2 * A * sizeof(Map) + sizeof(float) + sizeof(uint32_t);
-    const size_t bytes = (size_t)h->tbl.n_infos * (nblk_max + ngrp_max) * per_slot + (size_t)h->tbl.n_infos * sizeof(uint32_t);
+    const size_t bytes = bmap_index((uint32_t)(nblk_max + ngrp_max), 0, 0, h->g.rank_max, 2 * A) * sizeof(Map) + (size_t)h->tbl.n_infos * sizeof(uint32_t);
     HIP_TRY(hipMalloc(&h->d_bmaps, bytes));
     HIP_TRY(hipMemset(h->d_bmaps, 0, bytes));
     HIP_TRY(hipDeviceSynchronize());  // the memset runs on the null stream; the solver's stream is non-blocking (rp_mccfr_set_batch)
@@ -518,6 +518,7 @@ size_t traverse_maps_lds_bytes(const rp_mccfr* h) {
     const size_t masks = h->S != RP_SAMPLING_EXTERNAL ? (size_t)h->maxdec * 256 * 4 : 0;  // the expanded edges of every list entry
     return (NI * 8 + 2 * NI) * 4 + NI * 8 * 2 + (NI + (NI & 1)) * 2 + (size_t)5 * (h->maxdec * 256 + h->cell_pad) * 4 + masks;
 }
+static_assert(CH_THREADS <= 256u, "k_traverse_maps_static packs (infoset, rank of the infoset) into the 16 bits of an `order` entry");
 bool traverse_maps_fused(const rp_mccfr* h) {
     return h->static_skel && !h->dc.slotmap && h->tbl.n_infos <= CH_THREADS &&
            traverse_maps_lds_bytes(h) <= 64 * 1024 && h->fuse_maps;
@@ -530,10 +531,7 @@ int launch_summarize(rp_mccfr* h, const StepParams& p, void* blob_dev, bool fuse
     InfoSum* sums = reinterpret_cast<InfoSum*>(blob + (size_t)h->tbl.n_infos * h->tbl.max_actions * sizeof(Cell));
     const uint32_t A = h->tbl.max_actions;
     const uint32_t nblk_max = chunks_of(h->dc.stride), nblk = chunks_of(h->batch);
-    const size_t slots = (size_t)h->tbl.n_infos * nblk_max;
     Map* bmaps = reinterpret_cast<Map*>(h->d_bmaps);
-    float* bpsum = reinterpret_cast<float*>(bmaps + slots * 2 * A);
-    uint32_t* bcnt = reinterpret_cast<uint32_t*>(bpsum + slots);
     const bool pruned = h->S != RP_SAMPLING_EXTERNAL;
     if (fused) {
         clock_begin(h, h->clk_traverse);
@@ -541,7 +539,7 @@ int launch_summarize(rp_mccfr* h, const StepParams& p, void* blob_dev, bool fuse
         const size_t lds = traverse_maps_lds_bytes(h);
         with_static_traversal(h->static_skel, p.walker, pruned, p.ref_info != nullptr, [&](auto gt, auto wk, auto pr, auto rf) {
             hipLaunchKernelGGL((k_traverse_maps_static<decltype(gt), decltype(wk)::value, decltype(pr)::value, decltype(rf)::value>), dim3(nblk),
-                               dim3(256), lds, h->stream, h->g, h->itab, p, bmaps, bpsum, bcnt, nblk_max, h->maxdec, h->cell_pad);
+                               dim3(256), lds, h->stream, h->g, h->itab, p, bmaps, h->maxdec, h->cell_pad);
         });
         clock_end(h, h->clk_traverse);
     }
@@ -551,32 +549,26 @@ int launch_summarize(rp_mccfr* h, const StepParams& p, void* blob_dev, bool fuse
         const size_t lds = chunk_maps_lds_bytes(h);
         with_bools(pruned, h->tbl.n_infos <= CH_THREADS, [&](auto pr, auto one) {
             hipLaunchKernelGGL((k_chunk_maps<decltype(pr)::value, decltype(one)::value ? 1u : CM_PASSES>), dim3(nblk), dim3(CH_THREADS), lds,
-                               h->stream, h->g, h->dc, p, bmaps, bpsum, bcnt, nblk_max);
+                               h->stream, h->g, h->dc, p, bmaps);
         });
     } else {
         with_bool(pruned, [&](auto pr) {
-            hipLaunchKernelGGL((k_block_maps<decltype(pr)::value>), dim3(nblk, h->tbl.n_infos), dim3(128), 0, h->stream, h->g, h->so, p, bmaps,
-                               bpsum, bcnt, nblk_max);
+            hipLaunchKernelGGL((k_block_maps<decltype(pr)::value>), dim3(nblk, h->tbl.n_infos), dim3(128), 0, h->stream, h->g, h->so, p, bmaps);
         });
     }
     {
-        const uint32_t W2 = 2 * A, GPW = cb2_gpw(W2);
-        const size_t ngrp_max = (nblk_max + RP_FOLD_GROUP - 1) / RP_FOLD_GROUP, gslots = (size_t)h->tbl.n_infos * ngrp_max;
+        const uint32_t W2 = 2 * A, nr = h->g.rank_count[p.walker];
+        const uint32_t ngrp_max = (nblk_max + RP_FOLD_GROUP - 1) / RP_FOLD_GROUP, ngrp = (nblk + RP_FOLD_GROUP - 1) / RP_FOLD_GROUP;
         FoldScratch fs;
-        fs.gmaps = reinterpret_cast<Map*>(bcnt + slots);
-        fs.gpsum = reinterpret_cast<float*>(fs.gmaps + gslots * W2);
-        fs.gcnt = reinterpret_cast<uint32_t*>(fs.gpsum + gslots);
-        fs.done = fs.gcnt + gslots;
-        fs.ngrp_max = (uint32_t)ngrp_max;
-        const uint32_t ngrp = (nblk + RP_FOLD_GROUP - 1) / RP_FOLD_GROUP, nparts = (ngrp + GPW - 1) / GPW;
-        const size_t lds = (size_t)GPW * RP_FOLD_GROUP * (W2 * 16 + 8);
-        const dim3 grid(h->tbl.n_infos, std::max(nparts, 1u));
+        fs.gmaps = bmaps + bmap_index(nblk_max, 0, 0, h->g.rank_max, W2);
+        fs.done = reinterpret_cast<uint32_t*>(bmaps + bmap_index(nblk_max + ngrp_max, 0, 0, h->g.rank_max, W2));
+        const dim3 grid(std::max(ngrp, 1u), cb2_tiles(nr, W2));
         if (apply) {
-            hipLaunchKernelGGL((k_combine2<true>), grid, dim3(256), lds, h->stream, h->g, h->t, h->itab, p, bmaps, bpsum, bcnt, nblk_max, fs, cells, sums);
+            hipLaunchKernelGGL((k_combine2<true>), grid, dim3(CB2_THREADS), 0, h->stream, h->g, h->t, h->itab, p, bmaps, nr, fs, cells, sums);
             h->tables_version += 1;  // the kernel refreshes the rows of the per-infoset tables it changes
             if (h->itab_version + 1 == h->tables_version) h->itab_version = h->tables_version;
         } else {
-            hipLaunchKernelGGL((k_combine2<false>), grid, dim3(256), lds, h->stream, h->g, h->t, h->itab, p, bmaps, bpsum, bcnt, nblk_max, fs, cells, sums);
+            hipLaunchKernelGGL((k_combine2<false>), grid, dim3(CB2_THREADS), 0, h->stream, h->g, h->t, h->itab, p, bmaps, nr, fs, cells, sums);
         }
     }
     clock_end(h, h->clk_update);
@@ -742,6 +734,27 @@ int rp_mccfr_create(const rp_game_table* game, rp_regret_kind r, rp_weight_kind 
     h->g.payoffs = reinterpret_cast<const float*>(h->d_payoffs);
     h->g.info_actions = reinterpret_cast<const uint8_t*>(h->d_info_actions);
     h->g.info_player = reinterpret_cast<const uint8_t*>(h->d_info_player);
+    {
+        // an infoset's rank among its player's infosets and the way back (bmap_index: block maps compacted by walker)
+        std::vector<uint32_t> rank(game->n_infos), count(8, 0u);
+        const auto owned = [&](uint32_t i) { return h->info_player[i] < game->n_players; };  // rp_game_table_check: at most 8 players
+        for (uint32_t i = 0; i < game->n_infos; ++i) rank[i] = owned(i) ? count[h->info_player[i]]++ : 0u;
+        uint32_t rank_max = 1;
+        for (uint32_t w = 0; w < 8; ++w) {
+            h->g.rank_count[w] = count[w];
+            rank_max = std::max(rank_max, count[w]);
+        }
+        h->g.rank_max = rank_max;
+        std::vector<uint32_t> tab((size_t)game->n_infos + (size_t)game->n_players * rank_max, 0u);
+        for (uint32_t i = 0; i < game->n_infos; ++i) {
+            tab[i] = rank[i];
+            if (owned(i)) tab[(size_t)game->n_infos + (size_t)h->info_player[i] * rank_max + rank[i]] = i;
+        }
+        CREATE_TRY(hipMalloc(&h->d_info_rank, tab.size() * 4));
+        CREATE_TRY(hipMemcpy(h->d_info_rank, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+        h->g.info_rank = reinterpret_cast<const uint32_t*>(h->d_info_rank);
+        h->g.rank_info = h->g.info_rank + game->n_infos;
+    }
     h->g.n_players = game->n_players;
     h->g.n_infos = game->n_infos;
     h->g.A = game->max_actions;
@@ -821,7 +834,7 @@ int rp_mccfr_destroy(rp_mccfr* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     clock_drain_all(h);
-    void* ptrs[] = {h->d_info_streams, h->d_chance_streams, h->d_ref_mid, h->d_rows, h->d_states, h->d_children, h->d_kids, h->d_payoffs, h->d_info_actions, h->d_info_player, h->d_scratch,
+    void* ptrs[] = {h->d_info_streams, h->d_chance_streams, h->d_ref_mid, h->d_rows, h->d_states, h->d_children, h->d_kids, h->d_payoffs, h->d_info_actions, h->d_info_player, h->d_info_rank, h->d_scratch,
                     h->d_dec, h->d_sorted, h->d_bmaps, h->d_itab, h->d_summary, h->d_window, h->d_counters, h->t.regret, h->t.weight, h->t.payoff,
                     h->t.visits};
     for (void* p : ptrs)

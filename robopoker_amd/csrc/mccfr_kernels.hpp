@@ -21,6 +21,12 @@ struct DevGame {
     const float* payoffs;         // [n_terminals][n_players]
     const uint8_t* info_actions;  // [n_infos]
     const uint8_t* info_player;   // [n_infos]
+    // infoset ids are in discovery order, so the players' infosets interleave: an infoset's rank among its player's infosets, the way
+    // back, and the per-player counts (the block maps of the composed update are compacted by walker: bmap_index)
+    const uint32_t* info_rank;    // [n_infos]
+    const uint32_t* rank_info;    // [n_players][rank_max]
+    uint32_t rank_count[8];       // infosets of player w (rp_game_table: at most 8 players)
+    uint32_t rank_max;            // the largest of them, at least 1
     uint32_t n_players;
     uint32_t n_infos;
     uint32_t A;                   // table row stride (max_actions)
@@ -205,11 +211,19 @@ struct Map {
     float a, b, m;
     uint32_t n;
 };
+// The block maps of the composed update, and the group maps of their fold (k_combine2), are chunk-major and compacted by walker:
+// row `blk` (a block = one chunk of RP_COMPOSE_CHUNK trees; a group = RP_FOLD_GROUP blocks) holds, for every infoset of the walker
+// in rank order, 2A + 1 slots of 16 bytes: the cell maps (regret a = 0..A-1, then weight) and one slot {., payoff sum, ., count} with
+// the sum in Map::b and the count in Map::n.  A chunk's writer fills one contiguous row; the fold reads lane = (rank, slot)
+// and meets consecutive 16-byte words.  Every writer and the reader index through this function.
+__host__ __device__ inline size_t bmap_index(uint32_t blk, uint32_t rank, uint32_t slot, uint32_t rank_max, uint32_t W2) {
+    return ((size_t)blk * rank_max + rank) * (W2 + 1u) + slot;
+}
 // touches per LDS tile of the block-map chains
 __host__ __device__ inline uint32_t compose_block(uint32_t max_actions) { return (1024u / (2u * max_actions)) & ~3u; }
-__device__ __forceinline__ Map map_compose(const Map& first, const Map& second) {  // `first` is applied first
-    if (second.n == 0) return first;
-    if (first.n == 0) return second;
+// the composition of two maps that both hold a touch; `first` is applied first.  The one spelling of the algebra: map_compose and
+// map_compose_select only decide when it applies
+__device__ __forceinline__ Map map_compose_touched(const Map& first, const Map& second) {
     Map r;
     r.a = second.a * first.a;
     r.b = second.a * first.b + second.b;
@@ -217,6 +231,18 @@ __device__ __forceinline__ Map map_compose(const Map& first, const Map& second) 
     r.m = rp_maxf(t, second.m);
     r.n = first.n + second.n;
     return r;
+}
+__device__ __forceinline__ Map map_compose(const Map& first, const Map& second) {  // `first` is applied first
+    if (second.n == 0) return first;
+    if (first.n == 0) return second;
+    return map_compose_touched(first, second);
+}
+// map_compose without a branch, for the folds whose lanes run in lock step (k_combine2): the general case computed whether needed or
+// not, then selected, so the bits are those of map_compose(first, second).  r.n == first.n + second.n in all three cases.
+__device__ __forceinline__ Map map_compose_select(const Map& first, const Map& second) {
+    const Map r = map_compose_touched(first, second);
+    const bool keep = second.n == 0, take = first.n == 0;
+    return Map{keep ? first.a : (take ? second.a : r.a), keep ? first.b : (take ? second.b : r.b), keep ? first.m : (take ? second.m : r.m), r.n};
 }
 
 // first touch of an empty map sets (d, delta, floor); later touches compose one step (oracle: map_touch)
@@ -256,6 +282,8 @@ __device__ __forceinline__ void map_touch_unit_unless(Map& mp, bool skip, float 
     mp.n += skip ? 0u : 1u;
 }
 __device__ __forceinline__ Map map_identity() { return Map{1.0f, 0.0f, rp_u2f(0xff800000u), 0u}; }
+// the payoff slot of a block-map row (bmap_index): only b and n are read
+__device__ __forceinline__ Map map_sum_slot(float psum, uint32_t count) { return Map{1.0f, psum, rp_u2f(0xff800000u), count}; }
 // F(x) = max(a x + b, m) of a map that holds at least one touch; map_apply: any map (no touch = the identity)
 __device__ __forceinline__ float map_eval(const Map& mp, float x) { return rp_maxf(mp.a * x + mp.b, mp.m); }
 __device__ __forceinline__ float map_apply(const Map& mp, float x) { return mp.n ? map_eval(mp, x) : x; }

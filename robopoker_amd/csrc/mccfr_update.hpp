@@ -493,14 +493,13 @@ __global__ __launch_bounds__(128) void k_chain(DevGame g, DevTables t, DevSorted
 // ordered mode is replaced by a two-level composition of per-cell maps F(x) = max(a x + b, m).
 //   k_block_maps  one workgroup per (infoset, block of T consecutive Decisions): sequential composition inside the
 //                 block, all blocks of all infosets in parallel
-//   k_combine2    (infoset, part) workgroups: block maps -> group maps -> Cell / InfoSum blob, or straight into the tables
+//   k_combine2    (group, infoset tile) workgroups: block maps -> group maps -> Cell / InfoSum blob, or straight into the tables
 // ------------------------------------------------------------------------------------------------
 // Map / map_compose live in mccfr_kernels.hpp
 // block = the Decisions of infoset blockIdx.y produced by chunk blockIdx.x (RP_COMPOSE_CHUNK == CH_TREES trees):
 // in the sorted layout a contiguous group.  Large games (per-infoset slot map); small games fuse the sort away, below.
 template <bool PRUNED>
-__global__ __launch_bounds__(128) void k_block_maps(DevGame g, DevSorted so, StepParams p, Map* bmaps, float* bpsum,
-                                                    uint32_t* bcnt, uint32_t nblk_max) {
+__global__ __launch_bounds__(128) void k_block_maps(DevGame g, DevSorted so, StepParams p, Map* bmaps) {
     __shared__ __attribute__((aligned(16))) float tile[TILE_FLOATS + 2 * RP_MAX_ACTIONS * TILE_PAD];
     __shared__ uint32_t mtile[TILE_FLOATS / 2];
     __shared__ __attribute__((aligned(16))) float ptile[TILE_FLOATS / 2];
@@ -561,12 +560,9 @@ __global__ __launch_bounds__(128) void k_block_maps(DevGame g, DevSorted so, Ste
             for (uint32_t i = 0; i < m; ++i) psum += ptile[i];
         __syncthreads();
     }
-    const size_t slot = (size_t)info * nblk_max + blk;
-    if (wave == 0 && lane < W2) bmaps[slot * W2 + lane] = Map{mp.a, mp.b, mp.m, chain ? mp.n : 0u};
-    if (wave == 1 && lane == 0) {
-        bpsum[slot] = psum;
-        bcnt[slot] = n;
-    }
+    const size_t out = bmap_index(blk, g.info_rank[info], 0u, g.rank_max, W2);
+    if (wave == 0 && lane < W2) bmaps[out + lane] = Map{mp.a, mp.b, mp.m, chain ? mp.n : 0u};
+    if (wave == 1 && lane == 0) bmaps[out + W2] = map_sum_slot(psum, n);
 }
 
 // Small games: block maps straight from the lane-interleaved Decisions of one chunk — no sorted copy in HBM at all.
@@ -574,8 +570,7 @@ __global__ __launch_bounds__(128) void k_block_maps(DevGame g, DevSorted so, Ste
 // popcount, as k_compact_small); then, cell by cell, every thread drops its trees' values at those places in an LDS
 // array (global reads coalesced over trees) and one thread per infoset composes its list sequentially out of LDS.
 template <bool PRUNED, uint32_t PASSES>
-__global__ __launch_bounds__(CH_THREADS) void k_chunk_maps(DevGame g, DevDecisions dc, StepParams p, Map* bmaps, float* bpsum,
-                                                           uint32_t* bcnt, uint32_t nblk_max) {
+__global__ __launch_bounds__(CH_THREADS) void k_chunk_maps(DevGame g, DevDecisions dc, StepParams p, Map* bmaps) {
     extern __shared__ __attribute__((aligned(16))) uint32_t cm_lds[];
     __shared__ uint32_t wave_tot[CH_THREADS / 64];
     const uint32_t NI = g.n_infos, A = g.A, W2 = 2 * A, chunk = blockIdx.x, tid = threadIdx.x, MD = dc.maxdec;
@@ -626,12 +621,11 @@ __global__ __launch_bounds__(CH_THREADS) void k_chunk_maps(DevGame g, DevDecisio
             const uint32_t info = tid + q * CH_THREADS;
             if (!my_nact[q]) continue;
             const uint32_t n = my_n[q], base = my_base[q];
-            const size_t slot_out = (size_t)info * nblk_max + chunk;
+            const size_t out = bmap_index(chunk, g.info_rank[info], c, g.rank_max, W2);
             if (ispay) {  // payoff sum of the block, left fold from 0.0f
                 float sum = 0.0f;
                 for (uint32_t e = 0; e < n; ++e) sum += vals[base + e];
-                bpsum[slot_out] = sum;
-                bcnt[slot_out] = n;
+                bmaps[out] = map_sum_slot(sum, n);
                 continue;
             }
             const bool chain = a < my_nact[q];
@@ -640,23 +634,25 @@ __global__ __launch_bounds__(CH_THREADS) void k_chunk_maps(DevGame g, DevDecisio
             if (chain)
                 for (uint32_t e = 0; e < n; ++e)
                     map_touch_unless(mp, PRUNED && isreg && !((lmask[base + e] >> a) & 1u), cp.d, vals[base + e], cp.fl);
-            bmaps[slot_out * W2 + c] = mp;
+            bmaps[out] = mp;
         }
     }
 }
 
 // The two-level fold of the block maps (include/rp_mi355x.h RP_FOLD_GROUP: the block maps of a cell composed sequentially
-// inside groups of RP_FOLD_GROUP consecutive blocks, the group maps then in group order), spread over (infoset, part)
-// workgroups, and — APPLY — the rest of the step with it.
-//   stage 1  a part owns CB2_GPW(2A) consecutive groups: its block maps are one contiguous run of HBM, copied to LDS by all
-//            256 threads at once (one round trip instead of a chain of eight per thread), then thread (group, cell) composes
-//            its RP_FOLD_GROUP maps out of LDS in block order; the group maps go to HBM with agent-scope stores;
-//   stage 2  the LAST part of an infoset to finish (arrival counter; which one is timing, what it computes is not) folds the
-//            infoset's group maps in group order into the summary cell maps, payoff sum and count;
-//   APPLY    single-GPU step: that workgroup also applies the summary to the infoset's table row (k_fold with world = 1)
-//            and refreshes the row of the per-infoset tables the next traversal reads (k_prepare_infos): one launch
+// inside groups of RP_FOLD_GROUP consecutive blocks, the group maps then in group order), spread over (group, infoset tile)
+// workgroups, and — APPLY — the rest of the step with it.  The block maps are chunk-major (bmap_index), so nothing is transposed:
+//   tiles    the walker's infosets in rank order, cut into the fewest runs of at most 256 / (2A + 1) whole infosets, balanced
+//            (Leduc: 2 tiles of 30); lane = (infoset of the tile, slot), slot 2A the payoff sum and count;
+//   stage 1  a lane walks the blocks of its group in block order: one 16-byte load per step, a wavefront's loads one contiguous
+//            run; the loads do not depend on the chain and stay CB2_DEPTH ahead of it.  The group maps go to HBM with
+//            agent-scope stores, laid out as the block maps are;
+//   stage 2  the LAST group of a tile to finish (arrival counter; which one is timing, what it computes is not) folds the
+//            tile's group maps in group order, same lanes, into the summary cell maps, payoff sum and count;
+//   APPLY    single-GPU step: that workgroup also applies the summary to its infosets' table rows (k_fold with world = 1)
+//            and refreshes their rows of the per-infoset tables the next traversal reads (k_prepare_infos): one launch
 //            instead of three.  Otherwise it writes the summary blob (rp_mccfr_step_local).
-// Cross-workgroup data is a few KB per infoset: agent-scope (sc1) stores + s_waitcnt before the arrival, agent-scope
+// Cross-workgroup data is a few KB per group: agent-scope (sc1) stores + s_waitcnt before the arrival, agent-scope
 // loads after it.  (A release FENCE at agent scope writes back a whole XCD's L2: tried on the block maps, 4x slower.)
 // This hand-over is written against the gfx942 / gfx950 memory system, not against the portable memory model: relaxed agent-scope
 // stores are sc1 write-through stores that `s_waitcnt vmcnt(0)` waits for (no separate store counter), relaxed agent-scope loads
@@ -664,12 +660,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_chunk_maps(DevGame g, DevDecisio
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__)
 #error "k_combine2's cross-workgroup hand-over relies on gfx942/gfx950 store counting and sc1 semantics: use an acq_rel arrival counter on other targets"
 #endif
-__device__ __forceinline__ uint32_t ld_agent(const uint32_t* q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_agent(uint32_t* q, uint32_t v) { __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ Map ld_map(const Map* m) {
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(m);
-    return Map{rp_u2f(ld_agent(w)), rp_u2f(ld_agent(w + 1)), rp_u2f(ld_agent(w + 2)), ld_agent(w + 3)};
-}
 __device__ __forceinline__ void st_map(Map* m, const Map& v) {
     uint32_t* w = reinterpret_cast<uint32_t*>(m);
     st_agent(w, rp_f2u(v.a));
@@ -677,152 +668,159 @@ __device__ __forceinline__ void st_map(Map* m, const Map& v) {
     st_agent(w + 2, rp_f2u(v.m));
     st_agent(w + 3, v.n);
 }
-__host__ __device__ inline uint32_t cb2_gpw(uint32_t W2) { return 32u / W2 ? 32u / W2 : 1u; }  // groups per part: a 32 KB tile
+#ifndef CB2_DEPTH
+#define CB2_DEPTH 8u   // block maps per batch of a stage-1 chain: one batch composes while the loads of the next are in flight
+#endif
+#ifndef CB2_DEPTH2
+#define CB2_DEPTH2 8u   // the same for the group maps of stage 2, two 8-byte agent-scope loads each: its one workgroup per tile is the
+                       // serial tail of the launch, but deeper batches cost the registers that keep four workgroups on a CU
+#endif
+#define CB2_THREADS 256u
+static_assert(2u * RP_MAX_ACTIONS + 1u <= CB2_THREADS, "a tile of k_combine2 holds at least one whole infoset");
+// infosets per tile at most, and the number of tiles of a player with nr infosets
+__host__ __device__ inline uint32_t cb2_tile_infos(uint32_t W2) { return CB2_THREADS / (W2 + 1u); }
+__host__ __device__ inline uint32_t cb2_tiles(uint32_t nr, uint32_t W2) { return nr ? (nr + cb2_tile_infos(W2) - 1u) / cb2_tile_infos(W2) : 1u; }
 struct FoldScratch {
-    Map* gmaps;      // [n_infos][ngrp_max][2A]
-    float* gpsum;    // [n_infos][ngrp_max]
-    uint32_t* gcnt;  // [n_infos][ngrp_max]
-    uint32_t* done;  // [n_infos] parts finished
-    uint32_t ngrp_max;
+    Map* gmaps;      // [group][rank][2A + 1]: bmap_index
+    uint32_t* done;  // [tile] groups finished
 };
+// one lane's left fold, from the identity, of the n >= 1 slots load(0), load(1), ... : cell maps composed, or — sum — payoff sums
+// and counts added from 0.0f / 0.  The loads do not depend on the chain: two batches of D, the loads of one in flight while the
+// other is folded; the clamp keeps the loads of a ragged last batch inside the run.
+template <uint32_t D, class Load>
+__device__ __forceinline__ Map fold_slots(uint32_t n, bool sum, Load load) {
+    Map m = map_identity();
+    uint4 va[D], vb[D];
+    auto issue = [&](uint4* v, uint32_t k0) __attribute__((always_inline)) {
+#pragma unroll
+        for (uint32_t q = 0; q < D; ++q) v[q] = load(min(k0 + q, n - 1u));
+    };
+    auto fold = [&](const uint4* v, uint32_t k0) __attribute__((always_inline)) {
+#pragma unroll
+        for (uint32_t q = 0; q < D; ++q) {
+            const Map s{rp_u2f(v[q].x), rp_u2f(v[q].y), rp_u2f(v[q].z), v[q].w};
+            // the payoff lane runs the compose too and keeps nothing of it but the lock step: its a and m are never read
+            const Map c = map_compose_select(m, s);
+            const bool on = k0 + q < n;
+            m.a = on ? c.a : m.a;
+            m.b = on ? (sum ? m.b + s.b : c.b) : m.b;
+            m.m = on ? c.m : m.m;
+            m.n = on ? m.n + s.n : m.n;
+        }
+    };
+    // every load below is issued unconditionally on its path and consumed on the same path: no loaded value is merged with an
+    // older one at a join, where the copy would wait for the loads just issued
+    uint32_t k0 = 0;
+    issue(va, 0u);
+    // (sched_barrier: the scheduler otherwise sinks a batch's loads below the fold they are meant to overlap)
+    for (; k0 + 2u * D < n; k0 += 2u * D) {
+        issue(vb, k0 + D);
+        __builtin_amdgcn_sched_barrier(0);
+        fold(va, k0);
+        __builtin_amdgcn_sched_barrier(0);
+        issue(va, k0 + 2u * D);
+        __builtin_amdgcn_sched_barrier(0);
+        fold(vb, k0 + D);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if (k0 + D < n) {
+        issue(vb, k0 + D);
+        __builtin_amdgcn_sched_barrier(0);
+        fold(va, k0);
+        fold(vb, k0 + D);
+    } else {
+        fold(va, k0);
+    }
+    return m;
+}
 template <bool APPLY>
-__global__ __launch_bounds__(256) void k_combine2(DevGame g, DevTables t, DevInfoTab it, StepParams p, const Map* bmaps, const float* bpsum,
-                                                  const uint32_t* bcnt, uint32_t nblk_max, FoldScratch fs, Cell* cells, InfoSum* sums) {
-    extern __shared__ __attribute__((aligned(16))) uint4 cb_lds[];
-    __shared__ uint32_t role, sh_len;
-    __shared__ float sh_ps;
-    const uint32_t info = blockIdx.x, part = blockIdx.y, tid = threadIdx.x;
-    const uint32_t A = g.A, W2 = 2 * A, GPW = cb2_gpw(W2);
-    const Map ident = map_identity();
-    if (g.info_player[info] != p.walker) {  // not this walker's infoset: nothing happened to it
-        if (!APPLY && part == 0) {
-            if (tid < W2) {
-                Cell& cl = cells[(size_t)info * A + tid % A];
-                if (tid < A) cell_set_regret(cl, ident);
-                else cell_set_weight(cl, ident);
-            } else if (tid == W2) {
+__global__ __launch_bounds__(CB2_THREADS) void k_combine2(DevGame g, DevTables t, DevInfoTab it, StepParams p, const Map* bmaps, uint32_t nr,
+                                                          FoldScratch fs, Cell* cells, InfoSum* sums) {
+    __shared__ uint32_t role;
+    __shared__ float sh_ps[CB2_THREADS / 3u];
+    __shared__ uint32_t sh_len[CB2_THREADS / 3u];
+    const uint32_t grp = blockIdx.x, tile = blockIdx.y, tid = threadIdx.x;
+    const uint32_t A = g.A, W2 = 2 * A, SL = W2 + 1u;
+    if (!APPLY && grp == 0 && tile == 0) {  // not this walker's infosets: nothing happened to them
+        const Map ident = map_identity();
+        for (uint32_t e = tid; e < g.n_infos * SL; e += CB2_THREADS) {
+            const uint32_t info = e / SL, slot = e - info * SL;
+            if (g.info_player[info] == p.walker) continue;
+            if (slot == W2) {
                 sums[info] = InfoSum{0u, 0.0f};
+            } else {
+                Cell& cl = cells[(size_t)info * A + slot % A];
+                if (slot < A) cell_set_regret(cl, ident);
+                else cell_set_weight(cl, ident);
             }
         }
-        return;
     }
     const uint32_t nb = (p.batch + RP_COMPOSE_CHUNK - 1) / RP_COMPOSE_CHUNK;  // one block per chunk of trees
-    const uint32_t ngrp = (nb + RP_FOLD_GROUP - 1) / RP_FOLD_GROUP, nparts = (ngrp + GPW - 1) / GPW;
-    if (part >= nparts) return;
-    const uint32_t g0 = part * GPW, b_lo = g0 * RP_FOLD_GROUP, b_hi = min(nb, (g0 + GPW) * RP_FOLD_GROUP), count = b_hi - b_lo;
-    uint4* tile = cb_lds;                                                                // [GPW * 64][W2] block maps
-    float* ps_t = reinterpret_cast<float*>(tile + (size_t)GPW * RP_FOLD_GROUP * W2);     // [GPW * 64]
-    uint32_t* cn_t = reinterpret_cast<uint32_t*>(ps_t + GPW * RP_FOLD_GROUP);            // [GPW * 64]
-    {
-        const uint4* src = reinterpret_cast<const uint4*>(bmaps + ((size_t)info * nblk_max + b_lo) * W2);
-        for (uint32_t e = tid; e < count * W2; e += 256u) tile[e] = src[e];
-        for (uint32_t e = tid; e < count; e += 256u) {
-            ps_t[e] = bpsum[(size_t)info * nblk_max + b_lo + e];
-            cn_t[e] = bcnt[(size_t)info * nblk_max + b_lo + e];
-        }
+    const uint32_t ngrp = (nb + RP_FOLD_GROUP - 1) / RP_FOLD_GROUP;
+    if (grp >= ngrp) return;
+    const uint32_t ntiles = cb2_tiles(nr, W2);
+    const uint32_t r_lo = (uint32_t)((uint64_t)tile * nr / ntiles), r_hi = (uint32_t)((uint64_t)(tile + 1u) * nr / ntiles);
+    const uint32_t li = tid / SL, slot = tid - li * SL, rank = r_lo + li;
+    const bool active = rank < r_hi, sum = slot == W2;
+    const size_t row = (size_t)g.rank_max * SL;  // 16-byte words from a block's (group's) row to the next
+    if (active) {
+        const uint32_t b_lo = grp * RP_FOLD_GROUP, n = min(nb, b_lo + RP_FOLD_GROUP) - b_lo;
+        const uint4* src = reinterpret_cast<const uint4*>(bmaps) + bmap_index(b_lo, rank, slot, g.rank_max, W2);
+        const Map m = fold_slots<CB2_DEPTH>(n, sum, [&](uint32_t k) { return src[(size_t)k * row]; });
+        st_map(&fs.gmaps[bmap_index(grp, rank, slot, g.rank_max, W2)], m);
     }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the group maps are in memory before this group counts itself in
     __syncthreads();
-    if (tid < GPW * W2) {
-        const uint32_t s = tid / W2, c = tid % W2, grp = g0 + s;
-        if (grp < ngrp) {
-            const uint32_t lo = s * RP_FOLD_GROUP, hi = min(count, lo + RP_FOLD_GROUP);
-            Map m = ident;
-            for (uint32_t b0 = lo; b0 < hi; b0 += 8u) {  // eight LDS reads in flight ahead of the dependent chain
-                uint4 v[8];
-#pragma unroll
-                for (uint32_t q = 0; q < 8u; ++q) v[q] = tile[min(b0 + q, hi - 1u) * W2 + c];
-#pragma unroll
-                for (uint32_t q = 0; q < 8u; ++q)
-                    if (b0 + q < hi) m = map_compose(m, Map{rp_u2f(v[q].x), rp_u2f(v[q].y), rp_u2f(v[q].z), v[q].w});
-            }
-            st_map(&fs.gmaps[((size_t)info * fs.ngrp_max + grp) * W2 + c], m);
-        }
-    } else if (tid < GPW * W2 + GPW) {
-        const uint32_t s = tid - GPW * W2, grp = g0 + s;
-        if (grp < ngrp) {
-            const uint32_t lo = s * RP_FOLD_GROUP, hi = min(count, lo + RP_FOLD_GROUP);
-            float gp = 0.0f;
-            uint32_t gc = 0;
-            for (uint32_t b = lo; b < hi; ++b) {
-                gp += ps_t[b];
-                gc += cn_t[b];
-            }
-            st_agent(reinterpret_cast<uint32_t*>(fs.gpsum) + (size_t)info * fs.ngrp_max + grp, rp_f2u(gp));
-            st_agent(fs.gcnt + (size_t)info * fs.ngrp_max + grp, gc);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the group maps are in memory before this part counts itself in
-    __syncthreads();
-    if (tid == 0) role = atomicAdd(&fs.done[info], 1u) == nparts - 1u ? 1u : 0u;
+    if (tid == 0) role = atomicAdd(&fs.done[tile], 1u) == ngrp - 1u ? 1u : 0u;
     __syncthreads();
     if (!role) return;
-    if (tid == 0) fs.done[info] = 0;  // for the next launch
-    // the infoset's group maps: into LDS by all threads at once (one round trip), then folded in group order
-    Map tot = ident;
-    float ps = 0.0f;
-    uint32_t len = 0;
-    const uint32_t TILE_G = GPW * RP_FOLD_GROUP;
-    const uint32_t* gm = reinterpret_cast<const uint32_t*>(fs.gmaps + (size_t)info * fs.ngrp_max * W2);
-    for (uint32_t k0 = 0; k0 < ngrp; k0 += TILE_G) {
-        const uint32_t n = min(TILE_G, ngrp - k0);
-        __syncthreads();
-        for (uint32_t e = tid; e < n * W2; e += 256u) {
-            const uint32_t* w = gm + ((size_t)k0 * W2 + e) * 4u;
-            tile[e] = make_uint4(ld_agent(w), ld_agent(w + 1), ld_agent(w + 2), ld_agent(w + 3));
-        }
-        for (uint32_t e = tid; e < n; e += 256u) {
-            ps_t[e] = rp_u2f(ld_agent(reinterpret_cast<const uint32_t*>(fs.gpsum) + (size_t)info * fs.ngrp_max + k0 + e));
-            cn_t[e] = ld_agent(fs.gcnt + (size_t)info * fs.ngrp_max + k0 + e);
-        }
-        __syncthreads();
-        if (tid < W2) {
-            for (uint32_t k0b = 0; k0b < n; k0b += 8u) {
-                uint4 v[8];
-#pragma unroll
-                for (uint32_t q = 0; q < 8u; ++q) v[q] = tile[min(k0b + q, n - 1u) * W2 + tid];
-#pragma unroll
-                for (uint32_t q = 0; q < 8u; ++q)
-                    if (k0b + q < n) tot = map_compose(tot, Map{rp_u2f(v[q].x), rp_u2f(v[q].y), rp_u2f(v[q].z), v[q].w});
-            }
-        } else if (tid == W2) {
-            for (uint32_t k = 0; k < n; ++k) {
-                ps += ps_t[k];
-                len += cn_t[k];
-            }
-        }
-    }
-    if (tid == W2) {
-        sh_ps = ps;
-        sh_len = len;
+    if (tid == 0) fs.done[tile] = 0;  // for the next launch
+    // the tile's group maps, folded in group order
+    Map tot = map_identity();
+    uint32_t info = 0;
+    if (active) {
+        const uint64_t* gm = reinterpret_cast<const uint64_t*>(fs.gmaps + bmap_index(0u, rank, slot, g.rank_max, W2));
+        tot = fold_slots<CB2_DEPTH2>(ngrp, sum, [&](uint32_t k) {
+            const uint64_t* w = gm + (size_t)k * row * 2u;
+            const uint64_t lo = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint64_t hi = __hip_atomic_load(w + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+        });
+        info = g.rank_info[(size_t)p.walker * g.rank_max + rank];
     }
     if (!APPLY) {
-        if (tid < W2) {
-            Cell& cl = cells[(size_t)info * A + tid % A];
-            if (tid < A) cell_set_regret(cl, tot);
-            else cell_set_weight(cl, tot);
+        if (active) {
+            if (sum) {
+                sums[info] = InfoSum{tot.n, tot.b};
+            } else {
+                Cell& cl = cells[(size_t)info * A + slot % A];
+                if (slot < A) cell_set_regret(cl, tot);
+                else cell_set_weight(cl, tot);
+            }
         }
-        __syncthreads();
-        if (tid == 0) sums[info] = InfoSum{sh_len, sh_ps};
         return;
     }
-    // k_fold, world = 1, for this infoset's row
+    // k_fold, world = 1, for the rows of this tile's infosets
+    if (active && sum) {
+        sh_ps[li] = tot.b;
+        sh_len[li] = tot.n;
+    }
     __syncthreads();
-    const uint32_t nact = g.info_actions[info];
-    if (tid < W2 && tid % A < nact) {
-        const uint32_t cell = info * A + tid % A;
-        if (tid < A) {
+    if (active && !sum && slot % A < g.info_actions[info]) {
+        const uint32_t cell = info * A + slot % A;
+        if (slot < A) {
             t.regret[cell] = map_apply(tot, t.regret[cell]);
             float ev = t.payoff[cell];
             uint32_t visits = t.visits[cell];
-            fold_payoff(ev, visits, sh_ps, sh_len);
+            fold_payoff(ev, visits, sh_ps[li], sh_len[li]);
             t.payoff[cell] = ev;
             t.visits[cell] = visits;
         } else {
             t.weight[cell] = map_apply(tot, t.weight[cell]);
         }
     }
-    __syncthreads();  // workgroup scope: the row just written is what prepare_one reads
-    if (tid == 0) prepare_one(g, t, p, it, info);
+    __syncthreads();  // workgroup scope: the rows just written are what prepare_one reads
+    if (active && slot == 0) prepare_one(g, t, p, it, info);
 }
 
 // ------------------------------------------------------------------------------------------------

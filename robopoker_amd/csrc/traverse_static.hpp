@@ -657,7 +657,7 @@ __global__ __launch_bounds__(256) void k_traverse_static(DevGame g, DevInfoTab i
 // update") happens here on the values as they are produced: the lists' places are known once the trees are sampled
 // (on_built), each Decisions drops its five values (two regret deltas, two weight deltas, the payoff) at its place in LDS,
 // and the chains of ALL cells run side by side, one thread per (infoset, cell).  Same lists, same order, same operations
-// as k_chunk_maps: bmaps / bpsum / bcnt are bit-identical (tests/test_gpu_mccfr.py).
+// as k_chunk_maps: the chunk's row of block maps (bmap_index) is bit-identical (tests/test_gpu_mccfr.py).
 // A chain is sequential and as long as its list (a root infoset meets a third of the chunk's trees, a river infoset a few):
 // the (infoset, cell) tasks are handed out in descending order of list length (a counting sort by log2 class), so the 64
 // chains of a wave have similar lengths instead of every wave waiting for one long chain.
@@ -665,8 +665,8 @@ __global__ __launch_bounds__(256) void k_traverse_static(DevGame g, DevInfoTab i
 //                | (PRUNED) lmask u32[maxdec * 256]: the expanded edges of every list entry — a regret cell skips the entries
 //                  whose edge was pruned (no touch at all: a touch would apply the discount), as k_chunk_maps<true> does
 template <class G, int W, bool PRUNED, bool REF>
-__global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevInfoTab it, StepParams p, Map* bmaps, float* bpsum,
-                                                              uint32_t* bcnt, uint32_t nblk_max, uint32_t maxdec, uint32_t lpad) {
+__global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevInfoTab it, StepParams p, Map* bmaps,
+                                                              uint32_t maxdec, uint32_t lpad) {
     extern __shared__ __attribute__((aligned(16))) uint32_t tm_lds[];
     __shared__ uint32_t wave_tot[4];
     __shared__ uint32_t cls_n[16], cls_at[16];
@@ -713,7 +713,9 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
             __syncthreads();
             for (uint32_t info = lt; info < NI; info += 256u) {
                 const uint32_t run = lcount[info];
-                order[atomicAdd(&cls_at[15u - (run ? 32u - (uint32_t)__builtin_clz(run) : 0u)], 1u)] = (uint16_t)info;
+                // the infoset and, fetched now and not in the chain phase, its rank among its player's infosets (bmap_index) share the
+                // entry, 8 bits each: the launch is made for at most CH_THREADS infosets (traverse_maps_fused)
+                order[atomicAdd(&cls_at[15u - (run ? 32u - (uint32_t)__builtin_clz(run) : 0u)], 1u)] = (uint16_t)(info | g.info_rank[info] << 8);
             }
         };
     auto on_decision =
@@ -744,19 +746,14 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
         const uint32_t ln = lt & 63u, sub = ln / 5u, c = ln - 5u * sub;
         const float fl = c < 2u ? cpr.fl : (c < 4u ? cpw.fl : rp_u2f(0xff800000u));
         for (uint32_t i = (lt >> 6) * 12u + sub; ln < 60u && i < NI; i += 4u * 12u) {
-            const uint32_t info = order[i];
+            const uint32_t info = order[i] & 255u, rank = order[i] >> 8;
             if (g.info_player[info] != p.walker) continue;
             const uint32_t n = lcount[info], base = lbase[info];
-            const size_t slot_out = (size_t)info * nblk_max + chunk;
             const float* v = vals + (size_t)c * L + base;
             Map mp = map_identity();
             for (uint32_t e = 0; e < n; ++e) map_touch_unit_unless(mp, PRUNED && c < 2u && !((lmask[base + e] >> c) & 1u), v[e], fl);
-            if (c < 4u) {
-                bmaps[slot_out * 4u + c] = mp;
-            } else {
-                bpsum[slot_out] = 0.0f + mp.b;
-                bcnt[slot_out] = n;
-            }
+            if (c == 4u) mp.b = 0.0f + mp.b;  // the payoff slot {., sum, ., count}: no entry is skipped, so mp.n == n
+            bmaps[bmap_index(chunk, rank, c, g.rank_max, 4u)] = mp;
         }
     } else {
         // any other discount: task = (cell c, infoset); cells 0,1 regret, 2,3 weight, 4 the payoff sum.  The payoff sums are handed out
@@ -764,23 +761,22 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
         // task % 5)
         for (uint32_t task = lt; task < 5u * NI; task += 256u) {
             const uint32_t c = task < 4u * NI ? task & 3u : 4u;
-            const uint32_t info = order[task < 4u * NI ? task >> 2 : task - 4u * NI];
+            const uint32_t oi = order[task < 4u * NI ? task >> 2 : task - 4u * NI], info = oi & 255u, rank = oi >> 8;
             if (g.info_player[info] != p.walker) continue;
             const uint32_t n = lcount[info], base = lbase[info];
-            const size_t slot_out = (size_t)info * nblk_max + chunk;
+            const size_t out = bmap_index(chunk, rank, c, g.rank_max, 4u);
             const float* v = vals + (size_t)c * L + base;
             if (c == 4u) {  // payoff sum of the block, left fold from 0.0f
                 float sum = 0.0f;
                 for (uint32_t e = 0; e < n; ++e) sum += v[e];
-                bpsum[slot_out] = sum;
-                bcnt[slot_out] = n;
+                bmaps[out] = map_sum_slot(sum, n);
                 continue;
             }
             const bool isreg = c < 2u;
             const ChainParams cp = isreg ? cpr : cpw;
             Map mp = map_identity();
             for (uint32_t e = 0; e < n; ++e) map_touch_unless(mp, PRUNED && isreg && !((lmask[base + e] >> c) & 1u), cp.d, v[e], cp.fl);
-            bmaps[slot_out * 4u + c] = mp;
+            bmaps[out] = mp;
         }
     }
     count_metrics(p, nn, ndec, 0u);
