@@ -945,37 +945,120 @@ int rp_nlhe_sync(rp_nlhe* h) {
 
 }  // extern "C"
 
-// ---- the read side (nlmc_query.hpp): queries by NlheInfo key, read-only.  The _device forms queue one launch on the profile's
-// stream; the host forms stage through device scratch, call them and synchronise.
+#ifdef NL_TREE_PROF  // diagnostic build only (scripts/r6_nltree_prof.sh): k_nl_tree's phase clocks
+extern "C" RP_API int rp_nl_tree_prof(uint64_t* out16, int reset) {
+    unsigned long long z[16] = {0};
+    if (out16) HIP_TRY(hipMemcpyFromSymbol(out16, HIP_SYMBOL(rp::g_nl_prof), sizeof(z)));
+    if (reset) HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(rp::g_nl_prof), z, sizeof(z)));
+    return RP_OK;
+}
+extern "C" RP_API int rp_nl_tree_rec(uint32_t* out, uint32_t trees) {
+    HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(rp::g_nl_rec), (size_t)std::min<uint32_t>(trees, 2048u) * 16u * 4u));
+    return RP_OK;
+}
+#endif
+
+// ---- the read side: read-only entry points in pairs.  The _device form takes every array in device memory and queues its launches
+// on the profile's stream; the host form stages the same arrays through one device allocation (Stage), calls the _device form and
+// synchronises.  The two forms of a pair share ONE check of their arguments: the refusals of include/rp_mi355x.h in its order, made
+// before a device is touched, naming the un-suffixed function; RP_OK from a check with n == 0 is the call's answer.  Every entry
+// point that may need more than one launch runs nl_chunks, whatever its chunk size.
 namespace {
+// device scratch of one host-form call.  The host form names its arrays — in(p, count): copied to the device, out(p, count): copied
+// back from it; a NULL array (an optional argument left out) or an empty one is no bytes and stays, or becomes, NULL — then up()
+// makes the ONE allocation, queues the uploads and points every named p at its device copy (16-byte aligned each), so that the
+// _device form is called with the host form's own arguments; down() queues the downloads and synchronises.  The allocation is freed
+// on every way out, a refusal after a launch was queued included: hipFree waits for the device.
+struct Stage {
+    struct Part {
+        void* p;  // the caller's pointer variable, whatever it points to
+        void* host;
+        size_t bytes, at;
+        bool in;
+    };
+    int device;
+    hipStream_t st;
+    std::vector<Part> parts;
+    size_t bytes = 0;
+    unsigned char* base = nullptr;
+    explicit Stage(const rp_nlhe* h) : device(h->device), st(rp::profile_stream(h->prof)) {}
+    Stage(const Stage&) = delete;
+    ~Stage() {
+        if (base) (void)hipFree(base);
+    }
+    template <typename T>
+    Stage& add(T*& p, size_t count, bool in) {
+        parts.push_back(Part{(void*)&p, (void*)p, p ? count * sizeof(T) : 0, bytes, in});
+        bytes += (parts.back().bytes + 15) & ~(size_t)15;
+        return *this;
+    }
+    template <typename T>
+    Stage& in(const T*& p, size_t count) {
+        return add(p, count, true);
+    }
+    template <typename T>
+    Stage& out(T*& p, size_t count) {
+        return add(p, count, false);
+    }
+    int up() {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipMalloc(&base, bytes));
+        for (const Part& p : parts) {
+            void* dev = p.bytes ? base + p.at : nullptr;
+            memcpy(p.p, &dev, sizeof(dev));
+            if (p.in && p.bytes) HIP_TRY(hipMemcpyAsync(base + p.at, p.host, p.bytes, hipMemcpyHostToDevice, st));
+        }
+        return RP_OK;
+    }
+    int down() {
+        for (const Part& p : parts)
+            if (!p.in && p.bytes) HIP_TRY(hipMemcpyAsync(p.host, base + p.at, p.bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return RP_OK;
+    }
+};
+// items at .. at + m of n, at most `chunk` per launch: f(at, m) queues one launch
+template <typename F>
+int nl_chunks(uint64_t n, uint64_t chunk, F f) {
+    for (uint64_t at = 0; at < n; at += chunk) {
+        f(at, (uint32_t)std::min<uint64_t>(chunk, n - at));
+        HIP_TRY(hipGetLastError());
+    }
+    return RP_OK;
+}
+// an optional array from its item i on
+template <typename T>
+T* nl_at(T* p, uint64_t i) {
+    return p ? p + i : nullptr;
+}
+// a grow-only region of the handle that queued launches write: an earlier call's launch may still write the old one
+int nl_grow(void*& region, size_t& bytes, size_t need, hipStream_t st) {
+    if (need <= bytes) return RP_OK;
+    HIP_TRY(hipStreamSynchronize(st));
+    if (region) HIP_TRY(hipFree(region));
+    region = nullptr;
+    bytes = 0;
+    HIP_TRY(hipMalloc(&region, need));
+    bytes = need;
+    return RP_OK;
+}
+
+// ---- queries by NlheInfo key (nlmc_query.hpp): one launch
 uint32_t nlq_blocks(const rp_nlhe* h, uint64_t n, uint32_t per_block) {
     return (uint32_t)std::min<uint64_t>((n + per_block - 1) / per_block, h->grid_cap);
 }
-// device scratch of one host-form query: the keys in, the answers out, all in one allocation
-struct NlqStage {
-    unsigned char* base = nullptr;
-    uint64_t *past = nullptr, *choices = nullptr;
-    uint32_t* present = nullptr;
-    unsigned char* main = nullptr;  // policy [n][9] f32 or enc [n][9]
-    uint8_t *edges = nullptr, *n_actions = nullptr, *found = nullptr;
-    ~NlqStage() {
-        if (base) (void)hipFree(base);
-    }
-};
-int nlq_stage(NlqStage& s, hipStream_t st, uint64_t n, size_t main_bytes, const uint64_t* past, const uint32_t* present, const uint64_t* choices) {
-    const size_t o_choices = n * 8, o_main = o_choices + n * 8, o_present = o_main + n * main_bytes, o_edges = o_present + n * 4,
-                 o_nact = o_edges + n * NLMC_A, o_found = o_nact + n;
-    HIP_TRY(hipMalloc(&s.base, o_found + n));
-    s.past = reinterpret_cast<uint64_t*>(s.base);
-    s.choices = reinterpret_cast<uint64_t*>(s.base + o_choices);
-    s.main = s.base + o_main;
-    s.present = reinterpret_cast<uint32_t*>(s.base + o_present);
-    s.edges = s.base + o_edges;
-    s.n_actions = s.base + o_nact;
-    s.found = s.base + o_found;
-    HIP_TRY(hipMemcpyAsync(s.past, past, n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s.choices, choices, n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s.present, present, n * 4, hipMemcpyHostToDevice, st));
+int nlq_policy_check(const rp_nlhe* h, rp_dist_kind kind, uint64_t n, const void* past, const void* present, const void* choices, const void* policy) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_policy: NULL handle");
+    if (kind != RP_DIST_ITERATED && kind != RP_DIST_AVERAGED && kind != RP_DIST_SAMPLING)
+        return rp::fail(RP_ERR_INVALID, "rp_nlhe_policy: unknown distribution kind %d", (int)kind);
+    if (n == 0) return RP_OK;
+    if (!past || !present || !choices || !policy) return rp::fail(RP_ERR_INVALID, "rp_nlhe_policy: NULL keys or NULL policy with n > 0");
+    return RP_OK;
+}
+int nlq_memory_check(const rp_nlhe* h, uint64_t n, const void* past, const void* present, const void* choices, const void* enc) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_memory: NULL handle");
+    if (n == 0) return RP_OK;
+    if (!past || !present || !choices || !enc) return rp::fail(RP_ERR_INVALID, "rp_nlhe_memory: NULL keys or NULL enc with n > 0");
     return RP_OK;
 }
 }  // namespace
@@ -984,11 +1067,8 @@ extern "C" {
 
 int rp_nlhe_policy_device(rp_nlhe* h, rp_dist_kind kind, uint64_t n, const uint64_t* past, const uint32_t* present, const uint64_t* choices,
                           float* policy, uint8_t* edges, uint8_t* n_actions, uint8_t* found) {
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_policy: NULL handle");
-    if (kind != RP_DIST_ITERATED && kind != RP_DIST_AVERAGED && kind != RP_DIST_SAMPLING)
-        return rp::fail(RP_ERR_INVALID, "rp_nlhe_policy: unknown distribution kind %d", (int)kind);
-    if (n == 0) return RP_OK;
-    if (!past || !present || !choices || !policy) return rp::fail(RP_ERR_INVALID, "rp_nlhe_policy: NULL keys or NULL policy with n > 0");
+    int rc = nlq_policy_check(h, kind, n, past, present, choices, policy);
+    if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = rp::profile_stream(h->prof);
     const NlQuery q{n, past, present, choices, edges, n_actions, found};
@@ -1008,31 +1088,18 @@ int rp_nlhe_policy_device(rp_nlhe* h, rp_dist_kind kind, uint64_t n, const uint6
 
 int rp_nlhe_policy(rp_nlhe* h, rp_dist_kind kind, uint64_t n, const uint64_t* past, const uint32_t* present, const uint64_t* choices,
                    float* policy, uint8_t* edges, uint8_t* n_actions, uint8_t* found) {
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_policy: NULL handle");
-    if (kind != RP_DIST_ITERATED && kind != RP_DIST_AVERAGED && kind != RP_DIST_SAMPLING)
-        return rp::fail(RP_ERR_INVALID, "rp_nlhe_policy: unknown distribution kind %d", (int)kind);
-    if (n == 0) return RP_OK;
-    if (!past || !present || !choices || !policy) return rp::fail(RP_ERR_INVALID, "rp_nlhe_policy: NULL keys or NULL policy with n > 0");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = rp::profile_stream(h->prof);
-    NlqStage s;
-    int rc = nlq_stage(s, st, n, NLMC_A * sizeof(float), past, present, choices);
-    if (rc) return rc;
-    if ((rc = rp_nlhe_policy_device(h, kind, n, s.past, s.present, s.choices, reinterpret_cast<float*>(s.main), s.edges, s.n_actions, s.found)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(policy, s.main, n * NLMC_A * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (edges) HIP_TRY(hipMemcpyAsync(edges, s.edges, n * NLMC_A, hipMemcpyDeviceToHost, st));
-    if (n_actions) HIP_TRY(hipMemcpyAsync(n_actions, s.n_actions, n, hipMemcpyDeviceToHost, st));
-    if (found) HIP_TRY(hipMemcpyAsync(found, s.found, n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RP_OK;
+    int rc = nlq_policy_check(h, kind, n, past, present, choices, policy);
+    if (rc || n == 0) return rc;
+    Stage s(h);
+    s.in(past, n).in(present, n).in(choices, n).out(policy, n * NLMC_A).out(edges, n * NLMC_A).out(n_actions, n).out(found, n);
+    if ((rc = s.up()) || (rc = rp_nlhe_policy_device(h, kind, n, past, present, choices, policy, edges, n_actions, found))) return rc;
+    return s.down();
 }
 
 int rp_nlhe_memory_device(rp_nlhe* h, uint64_t n, const uint64_t* past, const uint32_t* present, const uint64_t* choices, rp_encounter* enc,
                           uint8_t* n_actions, uint8_t* found) {
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_memory: NULL handle");
-    if (n == 0) return RP_OK;
-    if (!past || !present || !choices || !enc) return rp::fail(RP_ERR_INVALID, "rp_nlhe_memory: NULL keys or NULL enc with n > 0");
+    int rc = nlq_memory_check(h, n, past, present, choices, enc);
+    if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(h->device));
     const NlQuery q{n, past, present, choices, nullptr, n_actions, found};
     hipLaunchKernelGGL(k_nl_memory, dim3(nlq_blocks(h, n, NLQ_BLOCK / NLQ_MGROUP)), dim3(NLQ_BLOCK), 0, rp::profile_stream(h->prof), h->tab, q, enc);
@@ -1042,20 +1109,12 @@ int rp_nlhe_memory_device(rp_nlhe* h, uint64_t n, const uint64_t* past, const ui
 
 int rp_nlhe_memory(rp_nlhe* h, uint64_t n, const uint64_t* past, const uint32_t* present, const uint64_t* choices, rp_encounter* enc,
                    uint8_t* n_actions, uint8_t* found) {
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_memory: NULL handle");
-    if (n == 0) return RP_OK;
-    if (!past || !present || !choices || !enc) return rp::fail(RP_ERR_INVALID, "rp_nlhe_memory: NULL keys or NULL enc with n > 0");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = rp::profile_stream(h->prof);
-    NlqStage s;
-    int rc = nlq_stage(s, st, n, NLMC_A * sizeof(rp_encounter), past, present, choices);
-    if (rc) return rc;
-    if ((rc = rp_nlhe_memory_device(h, n, s.past, s.present, s.choices, reinterpret_cast<rp_encounter*>(s.main), s.n_actions, s.found))) return rc;
-    HIP_TRY(hipMemcpyAsync(enc, s.main, n * NLMC_A * sizeof(rp_encounter), hipMemcpyDeviceToHost, st));
-    if (n_actions) HIP_TRY(hipMemcpyAsync(n_actions, s.n_actions, n, hipMemcpyDeviceToHost, st));
-    if (found) HIP_TRY(hipMemcpyAsync(found, s.found, n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RP_OK;
+    int rc = nlq_memory_check(h, n, past, present, choices, enc);
+    if (rc || n == 0) return rc;
+    Stage s(h);
+    s.in(past, n).in(present, n).in(choices, n).out(enc, n * NLMC_A).out(n_actions, n).out(found, n);
+    if ((rc = s.up()) || (rc = rp_nlhe_memory_device(h, n, past, present, choices, enc, n_actions, found))) return rc;
+    return s.down();
 }
 
 }  // extern "C"
@@ -1067,110 +1126,81 @@ int nr_launch(rp_nlhe* h, int kind, int normalize, uint64_t n, const rp_nlhe_rec
               float* mass, uint8_t* seen, uint8_t* status) {
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = rp::profile_stream(h->prof);
-    for (uint64_t at = 0; at < n; at += NR_CHUNK) {
-        const uint32_t m = (uint32_t)std::min<uint64_t>(NR_CHUNK, n - at);
+    return nl_chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
         NrArgs q{};
         q.recalls = recalls + at;
         q.kind = kind;
         q.normalize = normalize;
-        q.count = count ? count + at : nullptr;
-        q.holes = holes ? holes + at * RP_NLHE_MAX_HOLES : nullptr;
-        q.reach = reach ? reach + at * RP_NLHE_MAX_HOLES : nullptr;
-        q.mass = mass ? mass + at * 256u : nullptr;
-        q.seen = seen ? seen + at * 256u : nullptr;
-        q.status = status ? status + at : nullptr;
+        q.count = nl_at(count, at);
+        q.holes = nl_at(holes, at * RP_NLHE_MAX_HOLES);
+        q.reach = nl_at(reach, at * RP_NLHE_MAX_HOLES);
+        q.mass = nl_at(mass, at * 256u);
+        q.seen = nl_at(seen, at * 256u);
+        q.status = nl_at(status, at);
         hipLaunchKernelGGL(k_nl_range, dim3(m), dim3(NR_BLOCK), 0, st, h->tab, h->prm, q);
-        HIP_TRY(hipGetLastError());
-    }
+    });
+}
+int nr_reaches_check(const rp_nlhe* h, rp_reach_kind kind, uint64_t n, const void* recalls, const void* count, const void* reach) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_reaches: NULL handle");
+    if (kind != RP_REACH_OPPONENT && kind != RP_REACH_SIGNALLED) return rp::fail(RP_ERR_INVALID, "rp_nlhe_reaches: unknown reach kind %d", (int)kind);
+    if (n == 0) return RP_OK;
+    if (!recalls || !count || !reach) return rp::fail(RP_ERR_INVALID, "rp_nlhe_reaches: NULL recalls, count or reach with n_recalls > 0");
     return RP_OK;
 }
-// device scratch of a host-form range query, freed on every way out
-struct NrStage {
-    unsigned char* base = nullptr;
-    ~NrStage() {
-        if (base) (void)hipFree(base);
-    }
-};
+int nr_range_check(const rp_nlhe* h, uint64_t n, const void* recalls, const void* mass, const void* seen) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_opponent_range: NULL handle");
+    if (n == 0) return RP_OK;
+    if (!recalls || !mass || !seen) return rp::fail(RP_ERR_INVALID, "rp_nlhe_opponent_range: NULL recalls, mass or seen with n_recalls > 0");
+    return RP_OK;
+}
 }  // namespace
 
 extern "C" {
 
 int rp_nlhe_reaches_device(rp_nlhe* h, rp_reach_kind kind, int normalize, uint64_t n, const rp_nlhe_recall* recalls, uint32_t* count,
                            uint64_t* holes, float* reach, uint8_t* status) {
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_reaches: NULL handle");
-    if (kind != RP_REACH_OPPONENT && kind != RP_REACH_SIGNALLED) return rp::fail(RP_ERR_INVALID, "rp_nlhe_reaches: unknown reach kind %d", (int)kind);
-    if (n == 0) return RP_OK;
-    if (!recalls || !count || !reach) return rp::fail(RP_ERR_INVALID, "rp_nlhe_reaches: NULL recalls, count or reach with n_recalls > 0");
+    int rc = nr_reaches_check(h, kind, n, recalls, count, reach);
+    if (rc || n == 0) return rc;
     return nr_launch(h, (int)kind, normalize ? 1 : 0, n, recalls, count, holes, reach, nullptr, nullptr, status);
 }
 
 int rp_nlhe_reaches(rp_nlhe* h, rp_reach_kind kind, int normalize, uint64_t n, const rp_nlhe_recall* recalls, uint32_t* count, uint64_t* holes,
                     float* reach, uint8_t* status) {
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_reaches: NULL handle");
-    if (kind != RP_REACH_OPPONENT && kind != RP_REACH_SIGNALLED) return rp::fail(RP_ERR_INVALID, "rp_nlhe_reaches: unknown reach kind %d", (int)kind);
-    if (n == 0) return RP_OK;
-    if (!recalls || !count || !reach) return rp::fail(RP_ERR_INVALID, "rp_nlhe_reaches: NULL recalls, count or reach with n_recalls > 0");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = rp::profile_stream(h->prof);
-    // holes | recalls (8-byte aligned) | reach | count | status
-    const size_t b_holes = holes ? n * RP_NLHE_MAX_HOLES * 8 : 0, o_rec = b_holes, o_reach = o_rec + n * sizeof(rp_nlhe_recall),
-                 o_count = o_reach + n * RP_NLHE_MAX_HOLES * 4, o_status = o_count + n * 4;
-    NrStage s;
-    HIP_TRY(hipMalloc(&s.base, o_status + n));
-    rp_nlhe_recall* d_rec = reinterpret_cast<rp_nlhe_recall*>(s.base + o_rec);
-    uint64_t* d_holes = holes ? reinterpret_cast<uint64_t*>(s.base) : nullptr;
-    float* d_reach = reinterpret_cast<float*>(s.base + o_reach);
-    uint32_t* d_count = reinterpret_cast<uint32_t*>(s.base + o_count);
-    uint8_t* d_status = s.base + o_status;
-    HIP_TRY(hipMemcpyAsync(d_rec, recalls, n * sizeof(rp_nlhe_recall), hipMemcpyHostToDevice, st));
-    int rc = nr_launch(h, (int)kind, normalize ? 1 : 0, n, d_rec, d_count, d_holes, d_reach, nullptr, nullptr, d_status);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(reach, d_reach, n * RP_NLHE_MAX_HOLES * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(count, d_count, n * 4, hipMemcpyDeviceToHost, st));
-    if (holes) HIP_TRY(hipMemcpyAsync(holes, d_holes, b_holes, hipMemcpyDeviceToHost, st));
-    if (status) HIP_TRY(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RP_OK;
+    int rc = nr_reaches_check(h, kind, n, recalls, count, reach);
+    if (rc || n == 0) return rc;
+    Stage s(h);
+    s.in(recalls, n).out(holes, n * RP_NLHE_MAX_HOLES).out(reach, n * RP_NLHE_MAX_HOLES).out(count, n).out(status, n);
+    if ((rc = s.up()) || (rc = rp_nlhe_reaches_device(h, kind, normalize, n, recalls, count, holes, reach, status))) return rc;
+    return s.down();
 }
 
 int rp_nlhe_opponent_range_device(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, float* mass, uint8_t* seen, uint8_t* status) {
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_opponent_range: NULL handle");
-    if (n == 0) return RP_OK;
-    if (!recalls || !mass || !seen) return rp::fail(RP_ERR_INVALID, "rp_nlhe_opponent_range: NULL recalls, mass or seen with n_recalls > 0");
+    int rc = nr_range_check(h, n, recalls, mass, seen);
+    if (rc || n == 0) return rc;
     return nr_launch(h, (int)RP_REACH_OPPONENT, 0, n, recalls, nullptr, nullptr, nullptr, mass, seen, status);
 }
 
 int rp_nlhe_opponent_range(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, float* mass, uint8_t* seen, uint8_t* status) {
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_opponent_range: NULL handle");
-    if (n == 0) return RP_OK;
-    if (!recalls || !mass || !seen) return rp::fail(RP_ERR_INVALID, "rp_nlhe_opponent_range: NULL recalls, mass or seen with n_recalls > 0");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = rp::profile_stream(h->prof);
-    const size_t o_mass = n * sizeof(rp_nlhe_recall), o_seen = o_mass + n * 256u * 4, o_status = o_seen + n * 256u;
-    NrStage s;
-    HIP_TRY(hipMalloc(&s.base, o_status + n));
-    rp_nlhe_recall* d_rec = reinterpret_cast<rp_nlhe_recall*>(s.base);
-    float* d_mass = reinterpret_cast<float*>(s.base + o_mass);
-    HIP_TRY(hipMemcpyAsync(d_rec, recalls, n * sizeof(rp_nlhe_recall), hipMemcpyHostToDevice, st));
-    int rc = nr_launch(h, (int)RP_REACH_OPPONENT, 0, n, d_rec, nullptr, nullptr, nullptr, d_mass, s.base + o_seen, s.base + o_status);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(mass, d_mass, n * 256u * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(seen, s.base + o_seen, n * 256u, hipMemcpyDeviceToHost, st));
-    if (status) HIP_TRY(hipMemcpyAsync(status, s.base + o_status, n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RP_OK;
+    int rc = nr_range_check(h, n, recalls, mass, seen);
+    if (rc || n == 0) return rc;
+    Stage s(h);
+    s.in(recalls, n).out(mass, n * 256u).out(seen, n * 256u).out(status, n);
+    if ((rc = s.up()) || (rc = rp_nlhe_opponent_range_device(h, n, recalls, mass, seen, status))) return rc;
+    return s.down();
 }
 
 }  // extern "C"
 
 // ---- frontier payoffs (nlmc_frontier.hpp): one workgroup per frontier, at most NR_CHUNK frontiers per launch
 namespace {
-// rollouts = 0 is 1; the arguments a call is refused for
-int nf_check(const char* name, rp_nlhe* h, float bias, uint32_t* rollouts) {
-    if (!h) return rp::fail(RP_ERR_INVALID, "%s: NULL handle", name);
-    if (!(bias > 0.0f) || std::isinf(bias)) return rp::fail(RP_ERR_INVALID, "%s: bias must be finite and positive", name);
-    if (*rollouts > 4096u) return rp::fail(RP_ERR_INVALID, "%s: rollouts %u above 4096", name, *rollouts);
+// rollouts = 0 is 1
+int nf_check(const rp_nlhe* h, uint64_t n, const void* frontiers, float bias, uint32_t* rollouts, const void* payoffs) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_frontier_payoffs: NULL handle");
+    if (!(bias > 0.0f) || std::isinf(bias)) return rp::fail(RP_ERR_INVALID, "rp_nlhe_frontier_payoffs: bias must be finite and positive");
+    if (*rollouts > 4096u) return rp::fail(RP_ERR_INVALID, "rp_nlhe_frontier_payoffs: rollouts %u above 4096", *rollouts);
     if (*rollouts == 0u) *rollouts = 1u;
+    if (n == 0) return RP_OK;
+    if (!frontiers || !payoffs) return rp::fail(RP_ERR_INVALID, "rp_nlhe_frontier_payoffs: NULL frontiers or payoffs with n > 0");
     return RP_OK;
 }
 }  // namespace
@@ -1179,14 +1209,11 @@ extern "C" {
 
 int rp_nlhe_frontier_payoffs_device(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* frontiers, float bias, uint32_t rollouts, uint64_t seed,
                                     uint64_t first_id, float* payoffs, int16_t* won, uint8_t* status) {
-    int rc = nf_check("rp_nlhe_frontier_payoffs", h, bias, &rollouts);
-    if (rc) return rc;
-    if (n == 0) return RP_OK;
-    if (!frontiers || !payoffs) return rp::fail(RP_ERR_INVALID, "rp_nlhe_frontier_payoffs: NULL frontiers or payoffs with n > 0");
+    int rc = nf_check(h, n, frontiers, bias, &rollouts, payoffs);
+    if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = rp::profile_stream(h->prof);
-    for (uint64_t at = 0; at < n; at += NR_CHUNK) {
-        const uint32_t m = (uint32_t)std::min<uint64_t>(NR_CHUNK, n - at);
+    return nl_chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
         NfArgs q{};
         q.frontiers = frontiers + at;
         q.bias = bias;
@@ -1194,54 +1221,51 @@ int rp_nlhe_frontier_payoffs_device(rp_nlhe* h, uint64_t n, const rp_nlhe_fronti
         q.step_hash = rp_node_hash_step(seed, 0);
         q.first_id = first_id + at;
         q.payoffs = payoffs + at * NF_CELLS;
-        q.won = won ? won + at * NF_CELLS * rollouts : nullptr;
-        q.status = status ? status + at : nullptr;
+        q.won = nl_at(won, at * NF_CELLS * rollouts);
+        q.status = nl_at(status, at);
         hipLaunchKernelGGL(k_nl_frontier, dim3(m), dim3(NF_BLOCK), 0, st, h->tab, h->prm, q);
-        HIP_TRY(hipGetLastError());
-    }
-    return RP_OK;
+    });
 }
 
 int rp_nlhe_frontier_payoffs(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* frontiers, float bias, uint32_t rollouts, uint64_t seed,
                              uint64_t first_id, float* payoffs, int16_t* won, uint8_t* status) {
-    int rc = nf_check("rp_nlhe_frontier_payoffs", h, bias, &rollouts);
-    if (rc) return rc;
-    if (n == 0) return RP_OK;
-    if (!frontiers || !payoffs) return rp::fail(RP_ERR_INVALID, "rp_nlhe_frontier_payoffs: NULL frontiers or payoffs with n > 0");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = rp::profile_stream(h->prof);
-    // frontiers (8-byte aligned) | payoffs | won | status
-    const size_t b_won = won ? n * NF_CELLS * rollouts * sizeof(int16_t) : 0, o_pay = n * sizeof(rp_nlhe_frontier),
-                 o_won = o_pay + n * NF_CELLS * sizeof(float), o_status = o_won + b_won;
-    NrStage s;
-    HIP_TRY(hipMalloc(&s.base, o_status + n));
-    rp_nlhe_frontier* d_fr = reinterpret_cast<rp_nlhe_frontier*>(s.base);
-    float* d_pay = reinterpret_cast<float*>(s.base + o_pay);
-    int16_t* d_won = won ? reinterpret_cast<int16_t*>(s.base + o_won) : nullptr;
-    HIP_TRY(hipMemcpyAsync(d_fr, frontiers, n * sizeof(rp_nlhe_frontier), hipMemcpyHostToDevice, st));
-    if ((rc = rp_nlhe_frontier_payoffs_device(h, n, d_fr, bias, rollouts, seed, first_id, d_pay, d_won, s.base + o_status))) return rc;
-    HIP_TRY(hipMemcpyAsync(payoffs, d_pay, n * NF_CELLS * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (won) HIP_TRY(hipMemcpyAsync(won, d_won, b_won, hipMemcpyDeviceToHost, st));
-    if (status) HIP_TRY(hipMemcpyAsync(status, s.base + o_status, n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RP_OK;
+    int rc = nf_check(h, n, frontiers, bias, &rollouts, payoffs);
+    if (rc || n == 0) return rc;
+    Stage s(h);
+    s.in(frontiers, n).out(payoffs, n * NF_CELLS).out(won, n * NF_CELLS * rollouts).out(status, n);
+    if ((rc = s.up()) || (rc = rp_nlhe_frontier_payoffs_device(h, n, frontiers, bias, rollouts, seed, first_id, payoffs, won, status))) return rc;
+    return s.down();
 }
 
 }  // extern "C"
 
 // ---- depth-limited re-solve (nlmc_depth.hpp): one workgroup per solve, at most ND_CHUNK solves per launch
 namespace {
-// the arguments a call is refused for, before anything else is looked at (so that they can be checked without a device)
 constexpr uint64_t ND_CHUNK = 4096;  // solves per launch: what the overflow region is sized for
-int nd_check(const rp_nlhe_depth_args* a, uint32_t* rollouts) {
-    if (!a) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: NULL args");
+// the fields the depth and the subgame args share: refused before anything else is looked at (so that they can be checked without a
+// device); rollouts = 0 is 1
+template <typename Args>
+int nd_args_check(const char* name, const Args* a, uint32_t* rollouts) {
+    if (!a) return rp::fail(RP_ERR_INVALID, "%s: NULL args", name);
     if (a->iterations < 1u || a->iterations > RP_NLHE_DEPTH_MAX_ITERATIONS)
-        return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: iterations %u outside 1 .. %u", a->iterations, RP_NLHE_DEPTH_MAX_ITERATIONS);
-    if (a->rollouts > 4096u) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: rollouts %u above 4096", a->rollouts);
-    if (!(a->bias > 0.0f) || std::isinf(a->bias)) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: bias must be finite and positive");
-    if (!(a->prior > 0.0f) || std::isinf(a->prior)) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: prior must be finite and positive");
-    if (a->reserved != 0u) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: reserved must be 0");
+        return rp::fail(RP_ERR_INVALID, "%s: iterations %u outside 1 .. %u", name, a->iterations, RP_NLHE_DEPTH_MAX_ITERATIONS);
+    if (a->rollouts > 4096u) return rp::fail(RP_ERR_INVALID, "%s: rollouts %u above 4096", name, a->rollouts);
+    if (!(a->bias > 0.0f) || std::isinf(a->bias)) return rp::fail(RP_ERR_INVALID, "%s: bias must be finite and positive", name);
+    if (!(a->prior > 0.0f) || std::isinf(a->prior)) return rp::fail(RP_ERR_INVALID, "%s: prior must be finite and positive", name);
+    uint32_t reserved[2] = {0u, 0u};  // one word in the depth args, two in the subgame args
+    static_assert(sizeof(Args::reserved) <= sizeof(reserved), "the reserved words of an args struct");
+    memcpy(reserved, &a->reserved, sizeof(Args::reserved));
+    if (reserved[0] != 0u || reserved[1] != 0u) return rp::fail(RP_ERR_INVALID, "%s: reserved must be 0", name);
     *rollouts = a->rollouts == 0u ? 1u : a->rollouts;
+    return RP_OK;
+}
+int nd_check(const rp_nlhe* h, uint64_t n, const void* entries, const rp_nlhe_depth_args* args, const void* results, const void* rows,
+             uint32_t* rollouts) {
+    int rc = nd_args_check("rp_nlhe_depth_solve", args, rollouts);
+    if (rc || n == 0) return rc;
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: NULL handle");
+    if (!entries || !results) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: NULL entries or results with n > 0");
+    if (args->rows_cap > 0u && !rows) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: NULL rows with rows_cap > 0");
     return RP_OK;
 }
 }  // namespace
@@ -1260,30 +1284,17 @@ void rp_nlhe_depth_args_default(rp_nlhe_depth_args* out) {
 int rp_nlhe_depth_solve_device(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* entries, const int8_t* origin, const rp_nlhe_depth_args* args,
                                rp_nlhe_depth_result* results, rp_nlhe_depth_row* rows) {
     uint32_t rollouts = 0;
-    int rc = nd_check(args, &rollouts);
-    if (rc) return rc;
-    if (n == 0) return RP_OK;
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: NULL handle");
-    if (!entries || !results) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: NULL entries or results with n > 0");
-    if (args->rows_cap > 0u && !rows) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: NULL rows with rows_cap > 0");
+    int rc = nd_check(h, n, entries, args, results, rows, &rollouts);
+    if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = rp::profile_stream(h->prof);
     // the overflow rows of one launch's solves: launches of one call follow each other on the stream and share the region
-    const uint64_t chunk = std::min<uint64_t>(ND_CHUNK, n);
-    const size_t need = (size_t)chunk * ND_ROWS_OVF * sizeof(NdRow);
-    if (need > h->depth_rows_bytes) {
-        HIP_TRY(hipStreamSynchronize(st));  // an earlier call's launch may still write the old region
-        if (h->depth_rows) HIP_TRY(hipFree(h->depth_rows));
-        h->depth_rows = nullptr;
-        h->depth_rows_bytes = 0;
-        HIP_TRY(hipMalloc(&h->depth_rows, need));
-        h->depth_rows_bytes = need;
-    }
-    for (uint64_t at = 0; at < n; at += ND_CHUNK) {
-        const uint32_t m = (uint32_t)std::min<uint64_t>(ND_CHUNK, n - at);
+    const size_t need = (size_t)std::min<uint64_t>(ND_CHUNK, n) * ND_ROWS_OVF * sizeof(NdRow);
+    if ((rc = nl_grow(h->depth_rows, h->depth_rows_bytes, need, st))) return rc;
+    return nl_chunks(n, ND_CHUNK, [&](uint64_t at, uint32_t m) {
         NdArgs q{};
         q.entries = entries + at;
-        q.origin = origin ? origin + at : nullptr;
+        q.origin = nl_at(origin, at);
         q.iterations = args->iterations;
         q.rollouts = rollouts;
         q.rows_cap = rows ? args->rows_cap : 0u;
@@ -1294,40 +1305,20 @@ int rp_nlhe_depth_solve_device(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* e
         q.first_id = args->first_id + at;
         q.overflow = static_cast<NdRow*>(h->depth_rows);
         q.results = results + at;
-        q.rows = rows ? rows + at * args->rows_cap : nullptr;
+        q.rows = nl_at(rows, at * args->rows_cap);
         hipLaunchKernelGGL(k_nl_depth, dim3(m), dim3(ND_BLOCK), 0, st, h->tab, h->prm, q);
-        HIP_TRY(hipGetLastError());
-    }
-    return RP_OK;
+    });
 }
 
 int rp_nlhe_depth_solve(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* entries, const int8_t* origin, const rp_nlhe_depth_args* args,
                         rp_nlhe_depth_result* results, rp_nlhe_depth_row* rows) {
     uint32_t rollouts = 0;
-    int rc = nd_check(args, &rollouts);
-    if (rc) return rc;
-    if (n == 0) return RP_OK;
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: NULL handle");
-    if (!entries || !results) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: NULL entries or results with n > 0");
-    if (args->rows_cap > 0u && !rows) return rp::fail(RP_ERR_INVALID, "rp_nlhe_depth_solve: NULL rows with rows_cap > 0");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = rp::profile_stream(h->prof);
-    // entries (8-byte aligned) | results | rows | origin
-    const size_t b_rows = n * args->rows_cap * sizeof(rp_nlhe_depth_row), o_res = n * sizeof(rp_nlhe_frontier),
-                 o_rows = o_res + n * sizeof(rp_nlhe_depth_result), o_origin = o_rows + b_rows;
-    NrStage s;
-    HIP_TRY(hipMalloc(&s.base, o_origin + n));
-    rp_nlhe_frontier* d_en = reinterpret_cast<rp_nlhe_frontier*>(s.base);
-    rp_nlhe_depth_result* d_res = reinterpret_cast<rp_nlhe_depth_result*>(s.base + o_res);
-    rp_nlhe_depth_row* d_rows = args->rows_cap ? reinterpret_cast<rp_nlhe_depth_row*>(s.base + o_rows) : nullptr;
-    int8_t* d_origin = origin ? reinterpret_cast<int8_t*>(s.base + o_origin) : nullptr;
-    HIP_TRY(hipMemcpyAsync(d_en, entries, n * sizeof(rp_nlhe_frontier), hipMemcpyHostToDevice, st));
-    if (origin) HIP_TRY(hipMemcpyAsync(d_origin, origin, n, hipMemcpyHostToDevice, st));
-    if ((rc = rp_nlhe_depth_solve_device(h, n, d_en, d_origin, args, d_res, d_rows))) return rc;
-    HIP_TRY(hipMemcpyAsync(results, d_res, n * sizeof(rp_nlhe_depth_result), hipMemcpyDeviceToHost, st));
-    if (d_rows) HIP_TRY(hipMemcpyAsync(rows, d_rows, b_rows, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RP_OK;
+    int rc = nd_check(h, n, entries, args, results, rows, &rollouts);
+    if (rc || n == 0) return rc;
+    Stage s(h);
+    s.in(entries, n).in(origin, n).out(results, n).out(rows, n * args->rows_cap);
+    if ((rc = s.up()) || (rc = rp_nlhe_depth_solve_device(h, n, entries, origin, args, results, rows))) return rc;
+    return s.down();
 }
 
 }  // extern "C"
@@ -1340,24 +1331,41 @@ int nw_launch(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, uint8_t* wo
               const uint8_t* worlds, uint64_t seed, uint64_t first_id, uint64_t* holes, uint8_t* world_out, uint16_t* attempts, uint8_t* status) {
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = rp::profile_stream(h->prof);
-    for (uint64_t at = 0; at < n; at += NR_CHUNK) {
-        const uint32_t m = (uint32_t)std::min<uint64_t>(NR_CHUNK, n - at);
+    return nl_chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
         NwArgs q{};
         q.recalls = recalls + at;
-        q.world = world ? world + at * 256u : nullptr;
-        q.weights = weights ? weights + at * RP_NLHE_WORLDS : nullptr;
-        q.hole_world = hole_world ? hole_world + at * RP_NLHE_MAX_HOLES : nullptr;
+        q.world = nl_at(world, at * 256u);
+        q.weights = nl_at(weights, at * RP_NLHE_WORLDS);
+        q.hole_world = nl_at(hole_world, at * RP_NLHE_MAX_HOLES);
         q.deals = deals;
-        q.worlds = worlds ? worlds + at * deals : nullptr;
+        q.worlds = nl_at(worlds, at * deals);
         q.step_hash = rp_node_hash_step(seed, 1);
         q.first_id = first_id + at;
-        q.holes = holes ? holes + at * deals : nullptr;
-        q.world_out = world_out ? world_out + at * deals : nullptr;
-        q.attempts = attempts ? attempts + at * deals : nullptr;
-        q.status = status ? status + at : nullptr;
+        q.holes = nl_at(holes, at * deals);
+        q.world_out = nl_at(world_out, at * deals);
+        q.attempts = nl_at(attempts, at * deals);
+        q.status = nl_at(status, at);
         hipLaunchKernelGGL(k_nl_world, dim3(m), dim3(NW_BLOCK), 0, st, h->tab, h->prm, q);
-        HIP_TRY(hipGetLastError());
-    }
+    });
+}
+int nw_partition_check(const rp_nlhe* h, uint64_t n, const void* mass, const void* seen, const void* world, const void* weights) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_partition: NULL handle");
+    if (n == 0) return RP_OK;
+    if (!mass || !seen || !world || !weights) return rp::fail(RP_ERR_INVALID, "rp_nlhe_partition: NULL mass, seen, world or weights with n > 0");
+    return RP_OK;
+}
+int nw_belief_check(const rp_nlhe* h, uint64_t n, const void* recalls, const void* world, const void* weights) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_belief: NULL handle");
+    if (n == 0) return RP_OK;
+    if (!recalls || !world || !weights) return rp::fail(RP_ERR_INVALID, "rp_nlhe_belief: NULL recalls, world or weights with n_recalls > 0");
+    return RP_OK;
+}
+// RP_OK with n == 0 or deals == 0 is the call's answer
+int nw_restrict_check(const rp_nlhe* h, uint64_t n, const void* recalls, uint32_t deals, const void* holes) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_restrict: NULL handle");
+    if (deals > NW_MAX_DEALS) return rp::fail(RP_ERR_INVALID, "rp_nlhe_restrict: deals %u above %u", deals, NW_MAX_DEALS);
+    if (n == 0 || deals == 0) return RP_OK;
+    if (!recalls || !holes) return rp::fail(RP_ERR_INVALID, "rp_nlhe_restrict: NULL recalls or holes with n_recalls > 0");
     return RP_OK;
 }
 }  // namespace
@@ -1365,143 +1373,67 @@ int nw_launch(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, uint8_t* wo
 extern "C" {
 
 int rp_nlhe_partition_device(rp_nlhe* h, uint64_t n, const float* mass, const uint8_t* seen, uint8_t* world, float* weights) {
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_partition: NULL handle");
-    if (n == 0) return RP_OK;
-    if (!mass || !seen || !world || !weights) return rp::fail(RP_ERR_INVALID, "rp_nlhe_partition: NULL mass, seen, world or weights with n > 0");
+    int rc = nw_partition_check(h, n, mass, seen, world, weights);
+    if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = rp::profile_stream(h->prof);
-    for (uint64_t at = 0; at < n; at += NR_CHUNK) {
-        const uint32_t m = (uint32_t)std::min<uint64_t>(NR_CHUNK, n - at);
+    return nl_chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
         hipLaunchKernelGGL(k_nl_partition, dim3(m), dim3(NW_BLOCK), 0, st, mass + at * 256u, seen + at * 256u, world + at * 256u,
                            weights + at * RP_NLHE_WORLDS);
-        HIP_TRY(hipGetLastError());
-    }
-    return RP_OK;
+    });
 }
 
 int rp_nlhe_partition(rp_nlhe* h, uint64_t n, const float* mass, const uint8_t* seen, uint8_t* world, float* weights) {
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_partition: NULL handle");
-    if (n == 0) return RP_OK;
-    if (!mass || !seen || !world || !weights) return rp::fail(RP_ERR_INVALID, "rp_nlhe_partition: NULL mass, seen, world or weights with n > 0");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = rp::profile_stream(h->prof);
-    // mass | weights | seen | world
-    const size_t o_weights = n * 256u * 4, o_seen = o_weights + n * RP_NLHE_WORLDS * 4, o_world = o_seen + n * 256u;
-    NrStage s;
-    HIP_TRY(hipMalloc(&s.base, o_world + n * 256u));
-    float* d_mass = reinterpret_cast<float*>(s.base);
-    float* d_weights = reinterpret_cast<float*>(s.base + o_weights);
-    HIP_TRY(hipMemcpyAsync(d_mass, mass, n * 256u * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s.base + o_seen, seen, n * 256u, hipMemcpyHostToDevice, st));
-    int rc = rp_nlhe_partition_device(h, n, d_mass, s.base + o_seen, s.base + o_world, d_weights);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(world, s.base + o_world, n * 256u, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(weights, d_weights, n * RP_NLHE_WORLDS * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RP_OK;
+    int rc = nw_partition_check(h, n, mass, seen, world, weights);
+    if (rc || n == 0) return rc;
+    Stage s(h);
+    s.in(mass, n * 256u).in(seen, n * 256u).out(world, n * 256u).out(weights, n * RP_NLHE_WORLDS);
+    if ((rc = s.up()) || (rc = rp_nlhe_partition_device(h, n, mass, seen, world, weights))) return rc;
+    return s.down();
 }
 
 int rp_nlhe_belief_device(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, uint8_t* world, float* weights, uint8_t* hole_world,
                           uint8_t* status) {
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_belief: NULL handle");
-    if (n == 0) return RP_OK;
-    if (!recalls || !world || !weights) return rp::fail(RP_ERR_INVALID, "rp_nlhe_belief: NULL recalls, world or weights with n_recalls > 0");
+    int rc = nw_belief_check(h, n, recalls, world, weights);
+    if (rc || n == 0) return rc;
     return nw_launch(h, n, recalls, world, weights, hole_world, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, status);
 }
 
 int rp_nlhe_belief(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, uint8_t* world, float* weights, uint8_t* hole_world, uint8_t* status) {
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_belief: NULL handle");
-    if (n == 0) return RP_OK;
-    if (!recalls || !world || !weights) return rp::fail(RP_ERR_INVALID, "rp_nlhe_belief: NULL recalls, world or weights with n_recalls > 0");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = rp::profile_stream(h->prof);
-    // recalls (8-byte aligned) | weights | world | hole_world | status
-    const size_t b_hw = hole_world ? n * RP_NLHE_MAX_HOLES : 0, o_weights = n * sizeof(rp_nlhe_recall), o_world = o_weights + n * RP_NLHE_WORLDS * 4,
-                 o_hw = o_world + n * 256u, o_status = o_hw + b_hw;
-    NrStage s;
-    HIP_TRY(hipMalloc(&s.base, o_status + n));
-    rp_nlhe_recall* d_rec = reinterpret_cast<rp_nlhe_recall*>(s.base);
-    float* d_weights = reinterpret_cast<float*>(s.base + o_weights);
-    HIP_TRY(hipMemcpyAsync(d_rec, recalls, n * sizeof(rp_nlhe_recall), hipMemcpyHostToDevice, st));
-    int rc = rp_nlhe_belief_device(h, n, d_rec, s.base + o_world, d_weights, hole_world ? s.base + o_hw : nullptr, s.base + o_status);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(world, s.base + o_world, n * 256u, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(weights, d_weights, n * RP_NLHE_WORLDS * 4, hipMemcpyDeviceToHost, st));
-    if (hole_world) HIP_TRY(hipMemcpyAsync(hole_world, s.base + o_hw, b_hw, hipMemcpyDeviceToHost, st));
-    if (status) HIP_TRY(hipMemcpyAsync(status, s.base + o_status, n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RP_OK;
+    int rc = nw_belief_check(h, n, recalls, world, weights);
+    if (rc || n == 0) return rc;
+    Stage s(h);
+    s.in(recalls, n).out(world, n * 256u).out(weights, n * RP_NLHE_WORLDS).out(hole_world, n * RP_NLHE_MAX_HOLES).out(status, n);
+    if ((rc = s.up()) || (rc = rp_nlhe_belief_device(h, n, recalls, world, weights, hole_world, status))) return rc;
+    return s.down();
 }
 
 int rp_nlhe_restrict_device(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, uint32_t deals, const uint8_t* worlds, uint64_t seed,
                             uint64_t first_id, uint64_t* holes, uint8_t* world_out, uint16_t* attempts, uint8_t* status) {
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_restrict: NULL handle");
-    if (deals > NW_MAX_DEALS) return rp::fail(RP_ERR_INVALID, "rp_nlhe_restrict: deals %u above %u", deals, NW_MAX_DEALS);
-    if (n == 0 || deals == 0) return RP_OK;
-    if (!recalls || !holes) return rp::fail(RP_ERR_INVALID, "rp_nlhe_restrict: NULL recalls or holes with n_recalls > 0");
+    int rc = nw_restrict_check(h, n, recalls, deals, holes);
+    if (rc || n == 0 || deals == 0) return rc;
     return nw_launch(h, n, recalls, nullptr, nullptr, nullptr, deals, worlds, seed, first_id, holes, world_out, attempts, status);
 }
 
 int rp_nlhe_restrict(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, uint32_t deals, const uint8_t* worlds, uint64_t seed, uint64_t first_id,
                      uint64_t* holes, uint8_t* world_out, uint16_t* attempts, uint8_t* status) {
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_restrict: NULL handle");
-    if (deals > NW_MAX_DEALS) return rp::fail(RP_ERR_INVALID, "rp_nlhe_restrict: deals %u above %u", deals, NW_MAX_DEALS);
-    if (n == 0 || deals == 0) return RP_OK;
-    if (!recalls || !holes) return rp::fail(RP_ERR_INVALID, "rp_nlhe_restrict: NULL recalls or holes with n_recalls > 0");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = rp::profile_stream(h->prof);
-    // holes | recalls (8-byte aligned) | attempts | worlds | world_out | status
-    const size_t nd = n * deals, o_rec = nd * 8, o_att = o_rec + n * sizeof(rp_nlhe_recall), o_worlds = o_att + nd * 2, o_out = o_worlds + nd,
-                 o_status = o_out + nd;
-    NrStage s;
-    HIP_TRY(hipMalloc(&s.base, o_status + n));
-    uint64_t* d_holes = reinterpret_cast<uint64_t*>(s.base);
-    rp_nlhe_recall* d_rec = reinterpret_cast<rp_nlhe_recall*>(s.base + o_rec);
-    uint16_t* d_att = reinterpret_cast<uint16_t*>(s.base + o_att);
-    HIP_TRY(hipMemcpyAsync(d_rec, recalls, n * sizeof(rp_nlhe_recall), hipMemcpyHostToDevice, st));
-    if (worlds) HIP_TRY(hipMemcpyAsync(s.base + o_worlds, worlds, nd, hipMemcpyHostToDevice, st));
-    int rc = rp_nlhe_restrict_device(h, n, d_rec, deals, worlds ? s.base + o_worlds : nullptr, seed, first_id, d_holes, s.base + o_out, d_att,
-                                     s.base + o_status);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(holes, d_holes, nd * 8, hipMemcpyDeviceToHost, st));
-    if (world_out) HIP_TRY(hipMemcpyAsync(world_out, s.base + o_out, nd, hipMemcpyDeviceToHost, st));
-    if (attempts) HIP_TRY(hipMemcpyAsync(attempts, d_att, nd * 2, hipMemcpyDeviceToHost, st));
-    if (status) HIP_TRY(hipMemcpyAsync(status, s.base + o_status, n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RP_OK;
+    int rc = nw_restrict_check(h, n, recalls, deals, holes);
+    if (rc || n == 0 || deals == 0) return rc;
+    Stage s(h);
+    s.in(recalls, n).in(worlds, n * deals).out(holes, n * deals).out(world_out, n * deals).out(attempts, n * deals).out(status, n);
+    if ((rc = s.up()) || (rc = rp_nlhe_restrict_device(h, n, recalls, deals, worlds, seed, first_id, holes, world_out, attempts, status))) return rc;
+    return s.down();
 }
 
 }  // extern "C"
 
-#ifdef NL_TREE_PROF  // diagnostic build only (scripts/r6_nltree_prof.sh): k_nl_tree's phase clocks
-extern "C" RP_API int rp_nl_tree_prof(uint64_t* out16, int reset) {
-    unsigned long long z[16] = {0};
-    if (out16) HIP_TRY(hipMemcpyFromSymbol(out16, HIP_SYMBOL(rp::g_nl_prof), sizeof(z)));
-    if (reset) HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(rp::g_nl_prof), z, sizeof(z)));
-    return RP_OK;
-}
-extern "C" RP_API int rp_nl_tree_rec(uint32_t* out, uint32_t trees) {
-    HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(rp::g_nl_rec), (size_t)std::min<uint32_t>(trees, 2048u) * 16u * 4u));
-    return RP_OK;
-}
-#endif
-
 // ---- safe subgame re-solve (nlmc_subgame.hpp): one workgroup per solve, at most NS_CHUNK solves per launch
 namespace {
 constexpr uint64_t NS_CHUNK = 1024;  // solves per launch: what the overflow region is sized for
-int ns_check(const rp_nlhe_subgame_args* a, uint32_t* rollouts) {
-    if (!a) return rp::fail(RP_ERR_INVALID, "rp_nlhe_subgame_solve: NULL args");
-    if (a->iterations < 1u || a->iterations > RP_NLHE_DEPTH_MAX_ITERATIONS)
-        return rp::fail(RP_ERR_INVALID, "rp_nlhe_subgame_solve: iterations %u outside 1 .. %u", a->iterations, RP_NLHE_DEPTH_MAX_ITERATIONS);
-    if (a->rollouts > 4096u) return rp::fail(RP_ERR_INVALID, "rp_nlhe_subgame_solve: rollouts %u above 4096", a->rollouts);
-    if (!(a->bias > 0.0f) || std::isinf(a->bias)) return rp::fail(RP_ERR_INVALID, "rp_nlhe_subgame_solve: bias must be finite and positive");
-    if (!(a->prior > 0.0f) || std::isinf(a->prior)) return rp::fail(RP_ERR_INVALID, "rp_nlhe_subgame_solve: prior must be finite and positive");
-    if (a->reserved[0] != 0u || a->reserved[1] != 0u) return rp::fail(RP_ERR_INVALID, "rp_nlhe_subgame_solve: reserved must be 0");
-    *rollouts = a->rollouts == 0u ? 1u : a->rollouts;
-    return RP_OK;
-}
-int ns_pointers(rp_nlhe* h, const void* entries, const void* hole_world, const void* weights, const rp_nlhe_subgame_args* args, const void* results,
-                const void* rows, const void* deals) {
+int ns_check(const rp_nlhe* h, uint64_t n, const void* entries, const void* hole_world, const void* weights, const rp_nlhe_subgame_args* args,
+             const void* results, const void* rows, const void* deals, uint32_t* rollouts) {
+    int rc = nd_args_check("rp_nlhe_subgame_solve", args, rollouts);
+    if (rc || n == 0) return rc;
     if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_subgame_solve: NULL handle");
     if (!entries || !hole_world || !weights || !results)
         return rp::fail(RP_ERR_INVALID, "rp_nlhe_subgame_solve: NULL entries, hole_world, weights or results with n > 0");
@@ -1526,30 +1458,19 @@ int rp_nlhe_subgame_solve_device(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier*
                                  const int8_t* origin, const rp_nlhe_subgame_args* args, rp_nlhe_subgame_result* results, rp_nlhe_subgame_row* rows,
                                  rp_nlhe_subgame_deal* deals) {
     uint32_t rollouts = 0;
-    int rc = ns_check(args, &rollouts);
-    if (rc) return rc;
-    if (n == 0) return RP_OK;
-    if ((rc = ns_pointers(h, entries, hole_world, weights, args, results, rows, deals))) return rc;
+    int rc = ns_check(h, n, entries, hole_world, weights, args, results, rows, deals, &rollouts);
+    if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = rp::profile_stream(h->prof);
     // the overflow rows of one launch's solves: launches of one call follow each other on the stream and share the region
-    const uint64_t chunk = std::min<uint64_t>(NS_CHUNK, n);
-    const size_t need = (size_t)chunk * NS_ROWS_OVF * sizeof(NdRow);
-    if (need > h->subgame_rows_bytes) {
-        HIP_TRY(hipStreamSynchronize(st));  // an earlier call's launch may still write the old region
-        if (h->subgame_rows) HIP_TRY(hipFree(h->subgame_rows));
-        h->subgame_rows = nullptr;
-        h->subgame_rows_bytes = 0;
-        HIP_TRY(hipMalloc(&h->subgame_rows, need));
-        h->subgame_rows_bytes = need;
-    }
-    for (uint64_t at = 0; at < n; at += NS_CHUNK) {
-        const uint32_t m = (uint32_t)std::min<uint64_t>(NS_CHUNK, n - at);
+    const size_t need = (size_t)std::min<uint64_t>(NS_CHUNK, n) * NS_ROWS_OVF * sizeof(NdRow);
+    if ((rc = nl_grow(h->subgame_rows, h->subgame_rows_bytes, need, st))) return rc;
+    return nl_chunks(n, NS_CHUNK, [&](uint64_t at, uint32_t m) {
         NsArgs q{};
         q.entries = entries + at;
         q.hole_world = hole_world + at * RP_NLHE_MAX_HOLES;
         q.weights = weights + at * RP_NLHE_WORLDS;
-        q.origin = origin ? origin + at : nullptr;
+        q.origin = nl_at(origin, at);
         q.iterations = args->iterations;
         q.rollouts = rollouts;
         q.rows_cap = rows ? args->rows_cap : 0u;
@@ -1565,43 +1486,19 @@ int rp_nlhe_subgame_solve_device(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier*
         q.rows = q.rows_cap ? rows + at * args->rows_cap : nullptr;
         q.deals = q.deals_cap ? deals + at * args->deals_cap : nullptr;
         hipLaunchKernelGGL(k_nl_subgame, dim3(m), dim3(NS_BLOCK), 0, st, h->tab, h->prm, q);
-        HIP_TRY(hipGetLastError());
-    }
-    return RP_OK;
+    });
 }
 
 int rp_nlhe_subgame_solve(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* entries, const uint8_t* hole_world, const float* weights, const int8_t* origin,
                           const rp_nlhe_subgame_args* args, rp_nlhe_subgame_result* results, rp_nlhe_subgame_row* rows, rp_nlhe_subgame_deal* deals) {
     uint32_t rollouts = 0;
-    int rc = ns_check(args, &rollouts);
-    if (rc) return rc;
-    if (n == 0) return RP_OK;
-    if ((rc = ns_pointers(h, entries, hole_world, weights, args, results, rows, deals))) return rc;
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = rp::profile_stream(h->prof);
-    // entries (8-byte aligned) | results | rows | deals | weights | hole_world | origin
-    const size_t b_rows = n * args->rows_cap * sizeof(rp_nlhe_subgame_row), b_deals = n * args->deals_cap * sizeof(rp_nlhe_subgame_deal),
-                 o_res = n * sizeof(rp_nlhe_frontier), o_rows = o_res + n * sizeof(rp_nlhe_subgame_result), o_deals = o_rows + b_rows,
-                 o_weights = o_deals + b_deals, o_hw = o_weights + n * RP_NLHE_WORLDS * sizeof(float), o_origin = o_hw + n * RP_NLHE_MAX_HOLES;
-    NrStage s;
-    HIP_TRY(hipMalloc(&s.base, o_origin + n));
-    rp_nlhe_frontier* d_en = reinterpret_cast<rp_nlhe_frontier*>(s.base);
-    rp_nlhe_subgame_result* d_res = reinterpret_cast<rp_nlhe_subgame_result*>(s.base + o_res);
-    rp_nlhe_subgame_row* d_rows = args->rows_cap ? reinterpret_cast<rp_nlhe_subgame_row*>(s.base + o_rows) : nullptr;
-    rp_nlhe_subgame_deal* d_deals = args->deals_cap ? reinterpret_cast<rp_nlhe_subgame_deal*>(s.base + o_deals) : nullptr;
-    float* d_weights = reinterpret_cast<float*>(s.base + o_weights);
-    uint8_t* d_hw = reinterpret_cast<uint8_t*>(s.base + o_hw);
-    int8_t* d_origin = origin ? reinterpret_cast<int8_t*>(s.base + o_origin) : nullptr;
-    HIP_TRY(hipMemcpyAsync(d_en, entries, n * sizeof(rp_nlhe_frontier), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_weights, weights, n * RP_NLHE_WORLDS * sizeof(float), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_hw, hole_world, n * RP_NLHE_MAX_HOLES, hipMemcpyHostToDevice, st));
-    if (origin) HIP_TRY(hipMemcpyAsync(d_origin, origin, n, hipMemcpyHostToDevice, st));
-    if ((rc = rp_nlhe_subgame_solve_device(h, n, d_en, d_hw, d_weights, d_origin, args, d_res, d_rows, d_deals))) return rc;
-    HIP_TRY(hipMemcpyAsync(results, d_res, n * sizeof(rp_nlhe_subgame_result), hipMemcpyDeviceToHost, st));
-    if (d_rows) HIP_TRY(hipMemcpyAsync(rows, d_rows, b_rows, hipMemcpyDeviceToHost, st));
-    if (d_deals) HIP_TRY(hipMemcpyAsync(deals, d_deals, b_deals, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RP_OK;
+    int rc = ns_check(h, n, entries, hole_world, weights, args, results, rows, deals, &rollouts);
+    if (rc || n == 0) return rc;
+    Stage s(h);
+    s.in(entries, n).in(hole_world, n * RP_NLHE_MAX_HOLES).in(weights, n * RP_NLHE_WORLDS).in(origin, n);
+    s.out(results, n).out(rows, n * args->rows_cap).out(deals, n * args->deals_cap);
+    if ((rc = s.up()) || (rc = rp_nlhe_subgame_solve_device(h, n, entries, hole_world, weights, origin, args, results, rows, deals))) return rc;
+    return s.down();
 }
 
 }  // extern "C"

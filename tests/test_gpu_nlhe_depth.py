@@ -199,6 +199,40 @@ def test_device_form_splits_repeats_and_reads_only(gpu, model):
     assert s.epoch == EPOCH + 1
 
 
+ND_CHUNK = 4096  # solves per launch: ND_CHUNK of robopoker_amd/csrc/nlmc.hip
+
+
+@pytest.mark.parametrize("rows_cap", [0, 4])
+def test_a_batch_past_one_launch_equals_its_split(gpu, model, rows_cap):
+    """ND_CHUNK + 1 solves take a second launch: every pointer and first_id move on by ND_CHUNK.  One call equals, byte for byte, the
+    first ND_CHUNK solves and the last one asked for in calls of their own with matching first_id, in the host and the device form."""
+    s = model.solver()
+    n = ND_CHUNK + 1
+    # the cases cycled so that the second launch's only solve is one with frontiers and rows
+    pick = (np.arange(n) - ND_CHUNK + NAMES.index("flop, next street")) % len(CASES)
+    en, og = NlheSolver.depth_entries(entries())[pick], NlheSolver._origin(origins(), len(CASES))[pick]
+    parts = ((slice(0, n), FIRST_ID), (slice(0, ND_CHUNK), FIRST_ID), (slice(ND_CHUNK, n), FIRST_ID + ND_CHUNK))
+    host = [s.depth_solve(en[at], og[at], 1, 1, BIAS, PRIOR, SEED, fid, rows_cap) for at, fid in parts]
+    en_dev, og_dev = torch.from_numpy(en.view(np.uint8).reshape(n, -1).copy()).to("cuda"), torch.from_numpy(og).to("cuda")
+    dev = [s.depth_solve_device(en_dev[at], og_dev[at], 1, 1, BIAS, PRIOR, SEED, fid, rows_cap) for at, fid in parts]
+    s.sync()
+    assert all(t.is_cuda for pair in dev for t in pair)
+    back = lambda t, dtype, *shape: np.frombuffer(t.cpu().numpy().tobytes(), dtype).reshape(shape)
+    dev = [(back(r, DEPTH_RESULT_DTYPE, len(r)), back(w, DEPTH_ROW_DTYPE, len(r), rows_cap)) for r, w in dev]
+    for form, (whole, head, tail) in (("host", host), ("device", dev)):
+        assert whole[0].shape == (n,) and whole[1].shape == (n, rows_cap), form
+        for f in DEPTH_RESULT_DTYPE.names:
+            assert np.concatenate([head[0][f], tail[0][f]]).tobytes() == whole[0][f].tobytes(), (form, f)
+        assert np.concatenate([head[0], tail[0]]).tobytes() == whole[0].tobytes(), form
+        assert np.concatenate([head[1], tail[1]]).tobytes() == whole[1].tobytes(), form
+    assert dev[0][0].tobytes() == host[0][0].tobytes() and dev[0][1].tobytes() == host[0][1].tobytes()
+    # the last solve is a real one, and its id is what it draws from: under the first solve's id it samples another tree
+    last = host[0][0][-1]
+    assert last["status"] == FM.OK and last["nodes"] > 1 and last["frontiers"] > 0 and last["n_rows"] > 0
+    assert rows_cap == 0 or host[0][1][-1].view(np.uint8).any()
+    assert s.depth_solve(en[ND_CHUNK:], og[ND_CHUNK:], 1, 1, BIAS, PRIOR, SEED, FIRST_ID, rows_cap)[0].tobytes() != host[2][0].tobytes()
+
+
 def test_one_frontier_equals_the_frontier_entry_point(gpu, model):
     """the payoffs the model took for one frontier of a tree are rp_nlhe_frontier_payoffs' for the stated record and id"""
     m = model

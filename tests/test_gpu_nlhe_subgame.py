@@ -266,6 +266,44 @@ def test_splits_repeats_and_reads_only(gpu, model):
     assert s.epoch == EPOCH + 1
 
 
+NS_CHUNK = 1024  # solves per launch: NS_CHUNK of robopoker_amd/csrc/nlmc.hip
+
+
+def test_a_batch_past_one_launch_equals_its_split(gpu, model):
+    """NS_CHUNK + 1 solves take a second launch: every pointer and first_id move on by NS_CHUNK.  One call equals, byte for byte, the
+    first NS_CHUNK solves and the last one asked for in calls of their own with matching first_id, in the host and the device form;
+    the beliefs are rp_nlhe_belief_device's over the cycled recalls."""
+    s = model.solver()
+    n, rows_cap, deals_cap = NS_CHUNK + 1, 4, 2
+    cases = [c for c in CASES if c[0] in ("river, seat 1", "flop", "flop, origin 0", "preflop", "no other hole", "chance")]
+    # the cases cycled so that the second launch's only solve is one with frontiers and rows
+    pick = (np.arange(n) - NS_CHUNK + [c[0] for c in cases].index("flop, origin 0")) % len(cases)
+    en, og = NlheSolver.depth_entries(entries(cases))[pick], NlheSolver._subgame_origin(origins(cases), len(cases))[pick]
+    bel = s.belief_device(torch.from_numpy(NlheSolver.subgame_recalls(en).view(np.uint8).copy()).to("cuda"))
+    en_dev, og_dev = torch.from_numpy(en.view(np.uint8).reshape(n, -1).copy()).to("cuda"), torch.from_numpy(og).to("cuda")
+    parts = ((slice(0, n), FIRST_ID), (slice(0, NS_CHUNK), FIRST_ID), (slice(NS_CHUNK, n), FIRST_ID + NS_CHUNK))
+    dev = [s.subgame_solve_device(en_dev[at], bel["hole_world"][at], bel["weights"][at], og_dev[at], 1, 1, BIAS, PRIOR, SEED, fid, rows_cap, deals_cap)
+           for at, fid in parts]
+    s.sync()
+    assert all(t.is_cuda for part in dev for t in part) and not bel["status"].cpu().numpy().any()
+    back = lambda t, dtype, *shape: np.frombuffer(t.cpu().numpy().tobytes(), dtype).reshape(shape)
+    dev = [(back(r, SUBGAME_RESULT_DTYPE, len(r)), back(w, SUBGAME_ROW_DTYPE, len(r), rows_cap), back(d, SUBGAME_DEAL_DTYPE, len(r), deals_cap))
+           for r, w, d in dev]
+    hw, wt = bel["hole_world"].cpu().numpy(), bel["weights"].cpu().numpy()
+    host = [s.subgame_solve(en[at], (hw[at], wt[at]), og[at], 1, 1, BIAS, PRIOR, SEED, fid, rows_cap, deals_cap) for at, fid in parts]
+    for form, (whole, head, tail) in (("host", host), ("device", dev)):
+        assert whole[0].shape == (n,) and whole[1].shape == (n, rows_cap) and whole[2].shape == (n, deals_cap), form
+        for f in SUBGAME_RESULT_DTYPE.names:
+            assert np.concatenate([head[0][f], tail[0][f]]).tobytes() == whole[0][f].tobytes(), (form, f)
+        assert all(np.concatenate([a, b]).tobytes() == w.tobytes() for a, b, w in zip(head, tail, whole)), form
+    assert all(d.tobytes() == h.tobytes() for d, h in zip(dev[0], host[0]))
+    # the last solve is a real one, and its id is what it draws from: under the first solve's id it is dealt another hole
+    last = host[0][0][-1]
+    assert last["status"] == FM.OK and last["nodes"] > 1 and last["frontiers"] > 0 and last["n_rows"] > 0 and host[0][2][-1]["hole"][0] != 0
+    wrong = s.subgame_solve(en[NS_CHUNK:], (hw[NS_CHUNK:], wt[NS_CHUNK:]), og[NS_CHUNK:], 1, 1, BIAS, PRIOR, SEED, FIRST_ID, rows_cap, deals_cap)
+    assert wrong[2].tobytes() != host[2][2].tobytes()
+
+
 def test_one_frontier_equals_the_frontier_entry_point(gpu, model):
     """the payoffs the model took for one frontier of a tree are rp_nlhe_frontier_payoffs' for the record that carries THAT
     ITERATION's hole for the other seat, and the stated id"""
