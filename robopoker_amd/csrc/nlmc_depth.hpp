@@ -25,6 +25,8 @@
 // The local profile keeps its first ND_ROWS_LDS rows in LDS and the rest in the solve's overflow region of device memory (NdRows); 32
 // bits of every key stay in LDS for the lookups.  After the last iteration the lanes rank the rows by key (one lane per row), lane 0
 // folds sum_regret and writes the result; the rows leave one lane per row.
+// Everything but the kernel's own skeleton is a function the subgame solve calls too (nlmc_subgame.hpp): a float fold, the frontier
+// id or the status rule changed here changes both.
 #ifndef RP_NLMC_DEPTH_HPP
 #define RP_NLMC_DEPTH_HPP
 
@@ -118,7 +120,6 @@ struct NdShared {
     int origin;
     uint64_t c_nodes, c_infosets, c_frontiers;
     uint16_t fnode[ND_FRONTIERS];
-    uint16_t rank[ND_ROWS];
     uint32_t todo[ND_TODO];  // parent | slot << 16
     float pay[ND_FRONTIERS][NF_CELLS];
     // lane 0's vectors over the slots of one infoset: indexed by a run-time slot, they would live in scratch memory as locals
@@ -495,12 +496,177 @@ __device__ __forceinline__ bool nd_row_less(const NdRow& a, const NdRow& b) {  /
     return a.choices < b.choices;
 }
 
+// ---- what the two solves share beside the tree: k_nl_depth below and k_nl_subgame (nlmc_subgame.hpp) call these ----
+
+// sh.origin of solve i.  `none`: the caller's constant for "no origin given", read as `none_is`; any other value outside -1 .. 3 is
+// RP_RECALL_SEAT
+__device__ __forceinline__ uint32_t nd_origin(const int8_t* origin, uint32_t i, int none, int none_is, int* out) {
+    const int o = origin ? (int)origin[i] : none;
+    *out = o == none ? none_is : o;
+    return o != none && (o < -1 || o > 3) ? (uint32_t)RP_RECALL_SEAT : (uint32_t)RP_RECALL_OK;
+}
+
+// lane 0 before the first iteration: the status of the entry, an empty profile, the counters at zero
+__device__ __forceinline__ void nd_begin(NdShared& sh, uint32_t st) {
+    sh.status = st;
+    sh.flags.lookup_miss = sh.flags.stuck = 0;
+    sh.n_rows = sh.t = 0;
+    sh.c_nodes = sh.c_infosets = sh.c_frontiers = 0;
+}
+
+// Phase B: the payoffs of every frontier of the tree into sh.pay, and the status.  Called by all ND_BLOCK lanes under uniform control
+// flow: the barriers of nf_cells and the one here are reached by every lane, and what decides the trip count (sh.n_frontiers,
+// sh.status) is read after a barrier.  entry: the solve's record, for the length of its history; id, it: the solve's and the iteration's.
+// The length and the tree's number are taken anew for every frontier: held across nf_cells they cost k_nl_subgame 36 more scalar
+// spills and 1 - 3 % of its time.
+__device__ __forceinline__ void nd_frontiers(const NlTable& t, const NlParams& p, NdShared& sh, const NdNode* nodes, const rp_nlhe_frontier& entry,
+                                             uint64_t id, uint32_t it, float bias, uint32_t rollouts, uint64_t step_hash, int16_t* s_won) {
+    const uint32_t tid = threadIdx.x, n_frontiers = sh.n_frontiers;
+    for (uint32_t f = 0; f < n_frontiers; ++f) {
+        const NdNode& fn = nodes[sh.fnode[f]];
+        const bool fits = (uint32_t)entry.n_edges + fn.depth <= RP_NLHE_MAX_HISTORY;
+        G2 g;
+        nd_unpack(fn, sh.pub.game, g);
+        const NrpPath path = sh.pub.path;  // payoffs(&self.prefix, ..): a rollout's story starts from the PREFIX, not from the node's path
+        const uint64_t fid = (id * RP_NLHE_DEPTH_MAX_ITERATIONS + it) * RP_NLHE_DEPTH_MAX_FRONTIERS + f;
+        const float sum = nf_cells(t, p, fits, g, path, (int)sh.pub.internal, bias, rollouts, step_hash, fid, s_won, nullptr, &sh.flags);
+        if (tid < NF_CELLS) sh.pay[f][tid] = sum / (float)rollouts;
+        if (tid == 0 && sh.status == RP_RECALL_OK)  // the first frontier that fails gives the status
+            sh.status = !fits ? (uint32_t)RP_RECALL_LENGTH
+                              : (sh.flags.lookup_miss ? (uint32_t)RP_RECALL_LOOKUP : (sh.flags.stuck ? (uint32_t)RP_RECALL_ILLEGAL : (uint32_t)RP_RECALL_OK));
+        __syncthreads();
+        if (sh.status != RP_RECALL_OK) break;
+    }
+}
+
+// Phase C, lane 0 only: the update of every infoset of iteration `it`'s walker, in entry order, then the counters.  buf: the sweeps'
+// 3 x ND_NODES floats.  ROWS, TAGGED: nd_update's.
+template <uint32_t ROWS, bool TAGGED, class R>
+__device__ __forceinline__ void nd_updates(const NlTable& t, NdShared& sh, const NdNode* nodes, const NdInfo* infos, const R& rows, uint32_t it,
+                                           float prior, float* buf) {
+    const uint32_t walker = it & 1u;
+    uint32_t st = RP_RECALL_OK, updated = 0;
+    for (uint32_t e = 0; e < sh.n_infos && st == RP_RECALL_OK; ++e) {
+        if (nd_turn(nodes[infos[e].head].meta) != walker) continue;  // record_infosets
+        st = nd_update<ROWS, TAGGED>(t, sh, nodes, infos, rows, e, walker, prior, buf, buf + ND_NODES, buf + 2u * ND_NODES);
+        updated += 1u;
+    }
+    sh.status = st;
+    sh.c_nodes += sh.n_nodes;
+    sh.c_infosets += updated;
+    sh.c_frontiers += sh.n_frontiers;
+    sh.t = it + 1u;
+}
+
+// the rows ranked by key, one lane per row: keys are distinct, so the ranks are a permutation.  rank[x]: the row of rank x (LDS).  No
+// barrier inside; the caller's follows.
+template <bool (*LESS)(const NdRow&, const NdRow&), class R>
+__device__ __forceinline__ void nd_rank(const R& rows, uint32_t n_rows, uint16_t* rank) {
+    for (uint32_t a = threadIdx.x; a < n_rows; a += ND_BLOCK) {
+        const NdRow& ra = rows.at(a);
+        uint32_t below = 0;
+        for (uint32_t b = 0; b < n_rows; ++b) below += LESS(rows.at(b), ra) ? 1u : 0u;
+        rank[below] = (uint16_t)a;
+    }
+}
+
+// lane 0: the result cleared, its status, and of a solve that went well the fields the two results share — sum_regret folded in
+// ranked order, slots ascending, and the counters.  OUT: written in place, a local copy's arrays would be indexed at run time.
+// Returns whether the solve went well.
+template <class OUT, class R>
+__device__ __forceinline__ bool nd_result_head(OUT& out, const NdShared& sh, const R& rows, const uint16_t* rank, uint32_t rollouts) {
+    out = OUT{};
+    out.status = (uint8_t)sh.status;
+    if (sh.status != RP_RECALL_OK) return false;
+    const uint32_t n_rows = sh.n_rows;
+    float total = 0.0f;
+    for (uint32_t x = 0; x < n_rows; ++x) {
+        const NdRow& row = rows.at(rank[x]);
+        for (uint32_t a = 0; a < row.nch; ++a) total += rp_maxf(row.r[a], 0.0f);
+    }
+    out.sum_regret = total / (float)(sh.t > 1u ? sh.t : 1u);
+    out.iterations = sh.t;
+    out.n_rows = n_rows;
+    out.nodes = sh.c_nodes;
+    out.infosets = sh.c_infosets;
+    out.frontiers = sh.c_frontiers;
+    out.rollouts = sh.c_frontiers * NF_CELLS * rollouts;
+    return true;
+}
+
+// the infoset of the entry state, whose turn it is (turn >= 0): DepthInfo::Game(info).  err: nl_bucket's
+struct NdEntry {
+    uint64_t choices;
+    uint32_t nch, present, err;
+};
+__device__ __forceinline__ NdEntry nd_entry(const NlParams& p, const G2& g, int turn, const NrpPath& path) {
+    NdEntry e;
+    e.err = 0;
+    e.nch = nl_choices_path(nl_view(g), (int)path.aggr, &e.choices);
+    e.present = nl_bucket(p, g.street(), turn ? g.cards[1] : g.cards[0], g.board, &e.err);
+    return e;
+}
+// cum_regret r[] and visits v[] of the entry infoset as the harvest reads them: from the local row of key (past, choices, present | tag)
+// if there is one, else from the blueprint's row of the untagged key with max(r, RP_EPSILON).  w, pp: NLMC_A floats each for the rest
+// of the blueprint's answer
+template <class R>
+__device__ __forceinline__ void nd_entry_row(const NlTable& t, const R& rows, uint32_t n_rows, uint64_t past, const NdEntry& e, uint32_t tag, float* r,
+                                             uint32_t* v, float* w, float* pp) {
+    const int ri = nd_find_row(rows, n_rows, past, e.choices, e.present | tag);
+    if (ri >= 0) {
+        for (uint32_t a = 0; a < NLMC_A; ++a) {
+            r[a] = rows.at(ri).r[a];
+            v[a] = rows.at(ri).v[a];
+        }
+    } else {
+        nd_blueprint(t, past, e.choices, e.present, r, w, pp, v);
+        for (uint32_t a = 0; a < NLMC_A; ++a) r[a] = rp_maxf(r[a], RP_EPSILON);
+    }
+}
+// lane 0: the entry infoset's key and regret into the result; a bucket the tables do not know makes the whole result its status
+template <class OUT>
+__device__ __forceinline__ void nd_result_entry(OUT& out, NdShared& sh, const NdEntry& e, float regret) {
+    out.regret = regret;
+    out.past = sh.pub.path.tail;
+    out.choices = e.choices;
+    out.present = e.present;
+    out.n_actions = (uint8_t)e.nch;
+    if (e.err) {
+        out = OUT{};
+        out.status = (uint8_t)RP_RECALL_LOOKUP;
+        sh.status = RP_RECALL_LOOKUP;
+    }
+}
+
+// the export of one solve's rows in ranked order, one lane per row; rows from n_rows on (all rows of a failed solve: n_rows = 0) are
+// zero.  The two row structs differ in one byte: the world of a subgame row, padding (and a tag of 0) in a depth row.
+__device__ __forceinline__ void nd_set_world(rp_nlhe_depth_row&, uint32_t) {}
+__device__ __forceinline__ void nd_set_world(rp_nlhe_subgame_row& o, uint32_t world) { o.world = (uint8_t)world; }
+template <class ROW, class R>
+__device__ __forceinline__ void nd_export(ROW* out /* [rows_cap] */, uint32_t rows_cap, uint32_t n_rows, const R& rows, const uint16_t* rank) {
+    for (uint32_t x = threadIdx.x; x < rows_cap; x += ND_BLOCK) {
+        ROW& o = out[x];
+        o = ROW{};
+        if (x < n_rows) {
+            const NdRow& row = rows.at(rank[x]);
+            o.kind = (uint8_t)(row.present_kind >> 31);
+            o.n_actions = (uint8_t)row.nch;
+            nd_set_world(o, (row.present_kind >> ND_PRESENT_BITS) & 3u);
+            o.present = row.present_kind & ((1u << ND_PRESENT_BITS) - 1u);
+            o.past = row.past;
+            o.choices = row.choices;
+            for (uint32_t a = 0; a < row.nch; ++a) o.enc[a] = rp_encounter{row.w[a], row.r[a], row.p[a], row.v[a]};
+        }
+    }
+}
+
 __global__ __launch_bounds__(ND_BLOCK) void k_nl_depth(NlTable t, NlParams p, NdArgs q) {
     __shared__ NdShared sh;
     __shared__ NdNode nodes[ND_NODES];
     __shared__ NdInfo infos[ND_INFOS];
     __shared__ NdRow rows_lds[ND_ROWS_LDS];
     __shared__ uint32_t row_hash[ND_ROWS];
+    __shared__ uint16_t s_rank[ND_ROWS];
     const NdRows rows{rows_lds, q.overflow + (size_t)blockIdx.x * ND_ROWS_OVF, row_hash};
     __shared__ float s_buf[NF_CELLS * NF_CHUNK / 2u];  // the rollouts' int16 buffer; between rollouts the sweeps' floats
     int16_t* s_won = reinterpret_cast<int16_t*>(s_buf);
@@ -508,150 +674,46 @@ __global__ __launch_bounds__(ND_BLOCK) void k_nl_depth(NlTable t, NlParams p, Nd
     const uint64_t id = q.first_id + i;  // wrapping
 
     if (tid == 0) {
-        const rp_nlhe_frontier& fr = q.entries[i];
-        uint32_t st = nf_replay(fr, sh.pub);
-        if (st == RP_RECALL_OK) {
-            const int o = q.origin ? (int)q.origin[i] : (int)RP_NLHE_DEPTH_ORIGIN_ENTRY;
-            sh.origin = o == (int)RP_NLHE_DEPTH_ORIGIN_ENTRY ? sh.pub.game.street() : o;
-            if (o != (int)RP_NLHE_DEPTH_ORIGIN_ENTRY && (o < -1 || o > 3)) st = RP_RECALL_SEAT;
-        }
-        sh.status = st;
-        sh.flags.lookup_miss = sh.flags.stuck = 0;
-        sh.n_rows = sh.t = 0;
-        sh.c_nodes = sh.c_infosets = sh.c_frontiers = 0;
+        uint32_t st = nf_replay(q.entries[i], sh.pub, true);
+        if (st == RP_RECALL_OK) st = nd_origin(q.origin, i, (int)RP_NLHE_DEPTH_ORIGIN_ENTRY, sh.pub.game.street(), &sh.origin);
+        nd_begin(sh, st);
     }
     __syncthreads();
     for (uint32_t it = 0; it < q.iterations; ++it) {
         if (sh.status != RP_RECALL_OK) break;  // uniform: read after a barrier, written before the next
-        const uint32_t walker = it & 1u;
         __syncthreads();
-        if (tid == 0) sh.status = nd_build(t, p, sh, nodes, infos, rows, walker, rp_node_hash_tree(q.step_hash_tree, id * RP_NLHE_DEPTH_MAX_ITERATIONS + it));
+        if (tid == 0) sh.status = nd_build(t, p, sh, nodes, infos, rows, it & 1u, rp_node_hash_tree(q.step_hash_tree, id * RP_NLHE_DEPTH_MAX_ITERATIONS + it));
         __syncthreads();
         if (sh.status != RP_RECALL_OK) break;
-        // Phase B
-        const uint32_t n_frontiers = sh.n_frontiers;
-        for (uint32_t f = 0; f < n_frontiers; ++f) {
-            const NdNode& fn = nodes[sh.fnode[f]];
-            const bool fits = (uint32_t)q.entries[i].n_edges + fn.depth <= RP_NLHE_MAX_HISTORY;
-            G2 g;
-            nd_unpack(fn, sh.pub.game, g);
-            const NrpPath path = sh.pub.path;  // payoffs(&self.prefix, ..): a rollout's story starts from the PREFIX, not from the node's path
-            const uint64_t fid = (id * RP_NLHE_DEPTH_MAX_ITERATIONS + it) * RP_NLHE_DEPTH_MAX_FRONTIERS + f;
-            const float sum = nf_cells(t, p, fits, g, path, (int)sh.pub.internal, q.bias, q.rollouts, q.step_hash_rollout, fid, s_won, nullptr, &sh.flags);
-            if (tid < NF_CELLS) sh.pay[f][tid] = sum / (float)q.rollouts;
-            if (tid == 0 && sh.status == RP_RECALL_OK)  // the first frontier that fails gives the status
-                sh.status = !fits ? (uint32_t)RP_RECALL_LENGTH
-                                  : (sh.flags.lookup_miss ? (uint32_t)RP_RECALL_LOOKUP : (sh.flags.stuck ? (uint32_t)RP_RECALL_ILLEGAL : (uint32_t)RP_RECALL_OK));
-            __syncthreads();
-            if (sh.status != RP_RECALL_OK) break;
-        }
+        nd_frontiers(t, p, sh, nodes, q.entries[i], id, it, q.bias, q.rollouts, q.step_hash_rollout, s_won);
         if (sh.status != RP_RECALL_OK) break;
-        // Phase C
-        if (tid == 0) {
-            float* rr = s_buf;
-            uint32_t st = RP_RECALL_OK, updated = 0;
-            for (uint32_t e = 0; e < sh.n_infos && st == RP_RECALL_OK; ++e) {
-                if (nd_turn(nodes[infos[e].head].meta) != walker) continue;  // record_infosets
-                st = nd_update(t, sh, nodes, infos, rows, e, walker, q.prior, rr, rr + ND_NODES, rr + 2u * ND_NODES);
-                updated += 1u;
-            }
-            sh.status = st;
-            sh.c_nodes += sh.n_nodes;
-            sh.c_infosets += updated;
-            sh.c_frontiers += sh.n_frontiers;
-            sh.t = it + 1u;
-        }
+        if (tid == 0) nd_updates<ND_ROWS, false>(t, sh, nodes, infos, rows, it, q.prior, s_buf);
         __syncthreads();
     }
     __syncthreads();
-    // the rows ranked by key, one lane per row: keys are distinct, so the ranks are a permutation
-    if (sh.status == RP_RECALL_OK) {
-        const uint32_t n_rows = sh.n_rows;
-        for (uint32_t a = tid; a < n_rows; a += ND_BLOCK) {
-            const NdRow& ra = rows.at(a);
-            uint32_t rank = 0;
-            for (uint32_t b = 0; b < n_rows; ++b) rank += nd_row_less(rows.at(b), ra) ? 1u : 0u;
-            sh.rank[rank] = (uint16_t)a;
-        }
-    }
+    if (sh.status == RP_RECALL_OK) nd_rank<nd_row_less>(rows, sh.n_rows, s_rank);
     __syncthreads();
     // the harvest
-    if (tid == 0) {
-        rp_nlhe_depth_result& out = q.results[i];  // written in place: a local copy's arrays would be indexed at run time
-        out = rp_nlhe_depth_result{};
-        out.status = (uint8_t)sh.status;
-        if (sh.status == RP_RECALL_OK) {
-            // sum_regret folded in ranked order
-            const uint32_t n_rows = sh.n_rows;
-            float total = 0.0f;
-            for (uint32_t x = 0; x < n_rows; ++x) {
-                const NdRow& row = rows.at(sh.rank[x]);
-                for (uint32_t a = 0; a < row.nch; ++a) total += rp_maxf(row.r[a], 0.0f);
+    if (tid == 0 && nd_result_head(q.results[i], sh, rows, s_rank, q.rollouts)) {
+        rp_nlhe_depth_result& out = q.results[i];
+        const G2 g = sh.pub.game;
+        const int turn = g.turn();
+        if (turn >= 0) {  // Harvest at DepthInfo::Game(info of the entry state)
+            const NdEntry e = nd_entry(p, g, turn, sh.pub.path);
+            float* r = sh.tmp[0];
+            nd_entry_row(t, rows, sh.n_rows, sh.pub.path.tail, e, 0u, r, sh.tmpu, sh.tmp[1], sh.tmp[2]);
+            const DistParams none{1.0f, 0.0f, 0.0f};
+            policy_distribution<NLMC_A>((int)RP_DIST_ITERATED, none, r, e.nch, out.refined);
+            float regret = 0.0f;
+            for (uint32_t a = 0; a < e.nch; ++a) {
+                regret += rp_maxf(r[a], 0.0f);
+                out.visits[a] = sh.tmpu[a];
             }
-            out.sum_regret = total / (float)(sh.t > 1u ? sh.t : 1u);
-            out.iterations = sh.t;
-            out.n_rows = n_rows;
-            out.nodes = sh.c_nodes;
-            out.infosets = sh.c_infosets;
-            out.frontiers = sh.c_frontiers;
-            out.rollouts = sh.c_frontiers * NF_CELLS * q.rollouts;
-            const G2 g = sh.pub.game;
-            const int turn = g.turn();
-            if (turn >= 0) {  // Harvest at DepthInfo::Game(info of the entry state)
-                uint64_t choices;
-                uint32_t err = 0;
-                const uint32_t nch = nl_choices_path(nl_view(g), (int)sh.pub.path.aggr, &choices);
-                const uint32_t present = nl_bucket(p, g.street(), turn ? g.cards[1] : g.cards[0], g.board, &err);
-                float *r = sh.tmp[0], *w = sh.tmp[1];
-                uint32_t* v = sh.tmpu;
-                const int ri = nd_find_row(rows, n_rows, sh.pub.path.tail, choices, present);
-                if (ri >= 0) {
-                    for (uint32_t a = 0; a < NLMC_A; ++a) {
-                        r[a] = rows.at(ri).r[a];
-                        v[a] = rows.at(ri).v[a];
-                    }
-                } else {
-                    float* pp = sh.tmp[2];
-                    nd_blueprint(t, sh.pub.path.tail, choices, present, r, w, pp, v);
-                    for (uint32_t a = 0; a < NLMC_A; ++a) r[a] = rp_maxf(r[a], RP_EPSILON);
-                }
-                const DistParams none{1.0f, 0.0f, 0.0f};
-                policy_distribution<NLMC_A>((int)RP_DIST_ITERATED, none, r, nch, out.refined);
-                float regret = 0.0f;
-                for (uint32_t a = 0; a < nch; ++a) {
-                    regret += rp_maxf(r[a], 0.0f);
-                    out.visits[a] = v[a];
-                }
-                out.regret = regret;
-                out.past = sh.pub.path.tail;
-                out.choices = choices;
-                out.present = present;
-                out.n_actions = (uint8_t)nch;
-                if (err) {
-                    out = rp_nlhe_depth_result{};
-                    out.status = (uint8_t)RP_RECALL_LOOKUP;
-                    sh.status = RP_RECALL_LOOKUP;
-                }
-            }
+            nd_result_entry(out, sh, e, regret);
         }
     }
     __syncthreads();
-    if (q.rows) {
-        const uint32_t n_rows = sh.status == RP_RECALL_OK ? sh.n_rows : 0u;
-        for (uint32_t x = tid; x < q.rows_cap; x += ND_BLOCK) {
-            rp_nlhe_depth_row& o = q.rows[(size_t)i * q.rows_cap + x];
-            o = rp_nlhe_depth_row{};
-            if (x < n_rows) {
-                const NdRow& row = rows.at(sh.rank[x]);
-                o.kind = (uint8_t)(row.present_kind >> 31);
-                o.n_actions = (uint8_t)row.nch;
-                o.present = row.present_kind & 0x7fffffffu;
-                o.past = row.past;
-                o.choices = row.choices;
-                for (uint32_t a = 0; a < row.nch; ++a) o.enc[a] = rp_encounter{row.w[a], row.r[a], row.p[a], row.v[a]};
-            }
-        }
-    }
+    if (q.rows) nd_export(q.rows + (size_t)i * q.rows_cap, q.rows_cap, sh.status == RP_RECALL_OK ? sh.n_rows : 0u, rows, s_rank);
 }
 
 }  // namespace rp

@@ -59,20 +59,22 @@ struct NfPublic {
     uint32_t status, internal;
 };
 
-// Phase A: validation and the replay.  Returns the status; on RP_RECALL_OK the game and the prefix path are set.
-__device__ __forceinline__ uint32_t nf_replay(const rp_nlhe_frontier& fr, NfPublic& pub) {
+// Phase A: validation and the replay.  Returns the status; on RP_RECALL_OK the game and the prefix path are set.  `both`: the holes of
+// both seats are inputs; else only `internal`'s is, and the other seat holds nothing (the subgame solve deals it, nlmc_subgame.hpp).
+__device__ __forceinline__ uint32_t nf_replay(const rp_nlhe_frontier& fr, NfPublic& pub, bool both) {
     if (fr.n_edges > RP_NLHE_MAX_HISTORY || fr.n_prefix > RP_NLHE_MAX_PREFIX) return RP_RECALL_LENGTH;
     uint32_t st = nrp_check_seats(fr.internal, fr.dealer, (uint32_t)(fr.reserved[0] | fr.reserved[1] | fr.reserved[2] | fr.reserved[3]), fr.stacks);
     if (st != RP_RECALL_OK) return st;
     uint64_t gone = 0;
-    if ((st = nrp_check_hole(fr.holes[0], &gone)) != RP_RECALL_OK) return st;
-    if ((st = nrp_check_hole(fr.holes[1], &gone)) != RP_RECALL_OK) return st;
+    const uint64_t hole0 = both || fr.internal == 0 ? fr.holes[0] : 0ull, hole1 = both || fr.internal != 0 ? fr.holes[1] : 0ull;
+    if ((st = nrp_check_hole(both ? hole0 : hole0 | hole1, &gone)) != RP_RECALL_OK) return st;  // not both: the one hole there is
+    if (both && (st = nrp_check_hole(hole1, &gone)) != RP_RECALL_OK) return st;
     if ((st = nrp_check_draws(fr.draws, gone)) != RP_RECALL_OK) return st;
     uint32_t n_draw_edges = 0;
     if ((st = nrp_check_edges(fr.edges, fr.n_edges, &n_draw_edges)) != RP_RECALL_OK) return st;
     if ((st = nrp_check_edges(fr.prefix, fr.n_prefix, &n_draw_edges)) != RP_RECALL_OK) return st;
     G2 g;
-    nrp_from_start(g, fr.dealer, fr.stacks, fr.holes[0], fr.holes[1]);
+    nrp_from_start(g, fr.dealer, fr.stacks, hole0, hole1);
     for (uint32_t i = 0; i < fr.n_edges; ++i)
         if ((st = nrp_apply(g, fr.edges[i], fr.draws)) != RP_RECALL_OK) return st;
     NrpPath path;
@@ -205,7 +207,7 @@ __global__ __launch_bounds__(NF_BLOCK) void k_nl_frontier(NlTable t, NlParams p,
     const uint32_t i = blockIdx.x, tid = threadIdx.x, rollouts = q.rollouts;
 
     if (tid == 0) {
-        pub.status = nf_replay(q.frontiers[i], pub);
+        pub.status = nf_replay(q.frontiers[i], pub, true);
         flags.lookup_miss = flags.stuck = 0;
     }
     __syncthreads();

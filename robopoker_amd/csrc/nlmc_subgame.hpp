@@ -1,7 +1,8 @@
 // nlmc_subgame.hpp — the safe subgame re-solve (rp_nlhe_subgame_solve): `iterations` steps of SubGameSolver, each on one small tree
 // whose opponent was dealt for that iteration from a world of the belief, the world-tagged local profile beside them, the rollouts of
 // every frontier in the same launch, then the harvest over the four worlds.  Read-only with respect to the blueprint, like
-// nlmc_depth.hpp, of which this is the second kernel: the tree, the sweeps and the update are that file's nd_* functions.
+// nlmc_depth.hpp, of which this is the second kernel: the tree, the sweeps and the update, phases B and C, the ranking, the head of
+// the result, the read of the entry infoset and the row export are that file's nd_* functions, one copy for both kernels.
 //
 // Reference: SubGameSolver::step / harvest (subgame/src/solver.rs:146-229), SubGameEncoder (subgame/src/encoder.rs), WorldInfo
 // (world/info.rs), WorldProfile (world/profile.rs) over DepthView (depth/view.rs), NlheEncoder::restrict (nlhe/src/encoder.rs:148-186).
@@ -32,7 +33,6 @@ namespace rp {
 #define NS_ROWS RP_NLHE_SUBGAME_MAX_ROWS
 #define NS_ROWS_OVF (NS_ROWS - ND_ROWS_LDS)
 #define NS_TAG_SHIFT ND_PRESENT_BITS
-#define NS_PRESENT_MASK ((1u << NS_TAG_SHIFT) - 1u)
 #define NS_NEVER 4  // sh.origin of RP_NLHE_SUBGAME_ORIGIN_NONE: no street lies beyond it
 static_assert(NS_BLOCK == NW_BLOCK, "the attempt rounds are one lane per attempt");
 static_assert(sizeof(rp_nlhe_subgame_args) == 48 && sizeof(rp_nlhe_subgame_result) == 176 && sizeof(rp_nlhe_subgame_row) == 168 &&
@@ -68,31 +68,6 @@ struct NsShared {  // the belief and the deal of one solve
     uint8_t hole_world[RP_NLHE_MAX_HOLES];
 };
 
-// nf_replay for an entry whose hole of the seat opposite `internal` is no input: that seat holds nothing until the first deal
-__device__ __forceinline__ uint32_t ns_replay(const rp_nlhe_frontier& fr, NfPublic& pub) {
-    if (fr.n_edges > RP_NLHE_MAX_HISTORY || fr.n_prefix > RP_NLHE_MAX_PREFIX) return RP_RECALL_LENGTH;
-    uint32_t st = nrp_check_seats(fr.internal, fr.dealer, (uint32_t)(fr.reserved[0] | fr.reserved[1] | fr.reserved[2] | fr.reserved[3]), fr.stacks);
-    if (st != RP_RECALL_OK) return st;
-    uint64_t gone = 0;
-    const uint64_t hole = fr.holes[fr.internal];
-    if ((st = nrp_check_hole(hole, &gone)) != RP_RECALL_OK) return st;
-    if ((st = nrp_check_draws(fr.draws, gone)) != RP_RECALL_OK) return st;
-    uint32_t n_draw_edges = 0;
-    if ((st = nrp_check_edges(fr.edges, fr.n_edges, &n_draw_edges)) != RP_RECALL_OK) return st;
-    if ((st = nrp_check_edges(fr.prefix, fr.n_prefix, &n_draw_edges)) != RP_RECALL_OK) return st;
-    G2 g;
-    nrp_from_start(g, fr.dealer, fr.stacks, fr.internal == 0 ? hole : 0ull, fr.internal == 0 ? 0ull : hole);
-    for (uint32_t i = 0; i < fr.n_edges; ++i)
-        if ((st = nrp_apply(g, fr.edges[i], fr.draws)) != RP_RECALL_OK) return st;
-    NrpPath path;
-    path.clear();
-    for (uint32_t i = 0; i < fr.n_prefix; ++i) path.push(fr.prefix[i]);
-    pub.game = g;
-    pub.path = path;
-    pub.internal = fr.internal;
-    return RP_RECALL_OK;
-}
-
 // the place of an edge code in kicker::Edge's derived Ord (edge.rs:18-27): Draw < Fold < Check < Call < Open(n) < Raise(Odds(n, d)) <
 // Shove, Odds compared as the pair (n, d).  The raise codes 10 .. 19 are Odds::GRID in grid order — (1,4) (1,3) (1,2) (2,3) (3,4) (1,1)
 // (5,4) (3,2) (2,1) (3,1) — whose ranks as pairs are 3 2 1 5 8 0 9 7 4 6: one nibble each.  Codes outside 1 .. 19 do not occur.
@@ -125,13 +100,9 @@ __global__ __launch_bounds__(NS_BLOCK) void k_nl_subgame(NlTable t, NlParams p, 
     const uint64_t id = q.first_id + i;  // wrapping
 
     if (tid == 0) {
-        const rp_nlhe_frontier& fr = q.entries[i];
-        uint32_t st = ns_replay(fr, sh.pub);
-        if (st == RP_RECALL_OK) {
-            const int o = q.origin ? (int)q.origin[i] : (int)RP_NLHE_SUBGAME_ORIGIN_NONE;
-            sh.origin = o == (int)RP_NLHE_SUBGAME_ORIGIN_NONE ? NS_NEVER : o;
-            if (o != (int)RP_NLHE_SUBGAME_ORIGIN_NONE && (o < -1 || o > 3)) st = RP_RECALL_SEAT;
-        }
+        // the hole of the seat opposite `internal` is no input: that seat holds nothing until the first deal
+        uint32_t st = nf_replay(q.entries[i], sh.pub, false);
+        if (st == RP_RECALL_OK) st = nd_origin(q.origin, i, (int)RP_NLHE_SUBGAME_ORIGIN_NONE, NS_NEVER, &sh.origin);
         for (uint32_t w = 0; w < RP_NLHE_WORLDS; ++w) {
             const float x = q.weights[(size_t)i * RP_NLHE_WORLDS + w];
             if (st == RP_RECALL_OK && (!(x >= 0.0f) || x == INFINITY)) st = RP_RECALL_CARDS;  // a belief that is none
@@ -148,10 +119,7 @@ __global__ __launch_bounds__(NS_BLOCK) void k_nl_subgame(NlTable t, NlParams p, 
         sw.attempts = 0;
         sw.fallbacks = 0;
         sw.first = NW_NEVER;
-        sh.status = st;
-        sh.flags.lookup_miss = sh.flags.stuck = 0;
-        sh.n_rows = sh.t = 0;
-        sh.c_nodes = sh.c_infosets = sh.c_frontiers = 0;
+        nd_begin(sh, st);
     }
     __syncthreads();
     {  // the belief into LDS: a byte that is no world, or lies past the candidates, reads as RP_WORLD_NONE
@@ -166,7 +134,6 @@ __global__ __launch_bounds__(NS_BLOCK) void k_nl_subgame(NlTable t, NlParams p, 
     __syncthreads();
     for (uint32_t it = 0; it < q.iterations; ++it) {
         if (sh.status != RP_RECALL_OK) break;  // uniform: read after a barrier, written before the next
-        const uint32_t walker = it & 1u;
         __syncthreads();
         // Phase D: the deal of this iteration — deal `it` of recall `id` among RP_NLHE_DEPTH_MAX_ITERATIONS, rp_nlhe_restrict's rules
         if (tid == 0) {
@@ -211,146 +178,53 @@ __global__ __launch_bounds__(NS_BLOCK) void k_nl_subgame(NlTable t, NlParams p, 
                 q.deals[(size_t)i * q.deals_cap + it] = d;
             }
             // Phase A
-            sh.status = nd_build(t, p, sh, nodes, infos, rows, walker, rp_node_hash_tree(q.step_hash_tree, id * RP_NLHE_DEPTH_MAX_ITERATIONS + it),
+            sh.status = nd_build(t, p, sh, nodes, infos, rows, it & 1u, rp_node_hash_tree(q.step_hash_tree, id * RP_NLHE_DEPTH_MAX_ITERATIONS + it),
                                  world << NS_TAG_SHIFT);
         }
         __syncthreads();
         if (sh.status != RP_RECALL_OK) break;
-        // Phase B
-        const uint32_t n_frontiers = sh.n_frontiers;
-        for (uint32_t f = 0; f < n_frontiers; ++f) {
-            const NdNode& fn = nodes[sh.fnode[f]];
-            const bool fits = (uint32_t)q.entries[i].n_edges + fn.depth <= RP_NLHE_MAX_HISTORY;
-            G2 g;
-            nd_unpack(fn, sh.pub.game, g);
-            const NrpPath path = sh.pub.path;
-            const uint64_t fid = (id * RP_NLHE_DEPTH_MAX_ITERATIONS + it) * RP_NLHE_DEPTH_MAX_FRONTIERS + f;
-            const float sum = nf_cells(t, p, fits, g, path, (int)sh.pub.internal, q.bias, q.rollouts, q.step_hash_rollout, fid, s_won, nullptr, &sh.flags);
-            if (tid < NF_CELLS) sh.pay[f][tid] = sum / (float)q.rollouts;
-            if (tid == 0 && sh.status == RP_RECALL_OK)
-                sh.status = !fits ? (uint32_t)RP_RECALL_LENGTH
-                                  : (sh.flags.lookup_miss ? (uint32_t)RP_RECALL_LOOKUP : (sh.flags.stuck ? (uint32_t)RP_RECALL_ILLEGAL : (uint32_t)RP_RECALL_OK));
-            __syncthreads();
-            if (sh.status != RP_RECALL_OK) break;
-        }
+        nd_frontiers(t, p, sh, nodes, q.entries[i], id, it, q.bias, q.rollouts, q.step_hash_rollout, s_won);
         if (sh.status != RP_RECALL_OK) break;
-        // Phase C
-        if (tid == 0) {
-            float* rr = s_buf;
-            uint32_t st = RP_RECALL_OK, updated = 0;
-            for (uint32_t e = 0; e < sh.n_infos && st == RP_RECALL_OK; ++e) {
-                if (nd_turn(nodes[infos[e].head].meta) != walker) continue;
-                st = nd_update<NS_ROWS, true>(t, sh, nodes, infos, rows, e, walker, q.prior, rr, rr + ND_NODES, rr + 2u * ND_NODES);
-                updated += 1u;
-            }
-            sh.status = st;
-            sh.c_nodes += sh.n_nodes;
-            sh.c_infosets += updated;
-            sh.c_frontiers += sh.n_frontiers;
-            sh.t = it + 1u;
-        }
+        if (tid == 0) nd_updates<NS_ROWS, true>(t, sh, nodes, infos, rows, it, q.prior, s_buf);
         __syncthreads();
     }
     __syncthreads();
-    // the rows ranked by key, one lane per row: keys are distinct, so the ranks are a permutation
-    if (sh.status == RP_RECALL_OK) {
-        const uint32_t n_rows = sh.n_rows;
-        for (uint32_t a = tid; a < n_rows; a += NS_BLOCK) {
-            const NdRow& ra = rows.at(a);
-            uint32_t rank = 0;
-            for (uint32_t b = 0; b < n_rows; ++b) rank += ns_row_less(rows.at(b), ra) ? 1u : 0u;
-            s_rank[rank] = (uint16_t)a;
-        }
-    }
+    if (sh.status == RP_RECALL_OK) nd_rank<ns_row_less>(rows, sh.n_rows, s_rank);
     __syncthreads();
     // the harvest
-    if (tid == 0) {
+    if (tid == 0 && nd_result_head(q.results[i], sh, rows, s_rank, q.rollouts)) {
         rp_nlhe_subgame_result& out = q.results[i];
-        out = rp_nlhe_subgame_result{};
-        out.status = (uint8_t)sh.status;
-        if (sh.status == RP_RECALL_OK) {
-            const uint32_t n_rows = sh.n_rows;
-            float total = 0.0f;
-            for (uint32_t x = 0; x < n_rows; ++x) {
-                const NdRow& row = rows.at(s_rank[x]);
-                for (uint32_t a = 0; a < row.nch; ++a) total += rp_maxf(row.r[a], 0.0f);
-            }
-            out.sum_regret = total / (float)(sh.t > 1u ? sh.t : 1u);
-            out.iterations = sh.t;
-            out.n_rows = n_rows;
-            out.nodes = sh.c_nodes;
-            out.infosets = sh.c_infosets;
-            out.frontiers = sh.c_frontiers;
-            out.rollouts = sh.c_frontiers * NF_CELLS * q.rollouts;
-            for (uint32_t w = 0; w < RP_NLHE_WORLDS; ++w) out.drawn[w] = sw.drawn[w];
-            out.attempts = sw.attempts;
-            out.fallbacks = sw.fallbacks;
-            const G2 g = sh.pub.game;  // as the last iteration dealt it
-            const int turn = g.turn();
-            if (turn >= 0) {  // Harvest at WorldInfo(w, Game(info of the entry state)), w = 0 .. 3
-                uint64_t choices;
-                uint32_t err = 0;
-                const uint32_t nch = nl_choices_path(nl_view(g), (int)sh.pub.path.aggr, &choices);
-                const uint32_t present = nl_bucket(p, g.street(), turn ? g.cards[1] : g.cards[0], g.board, &err);
-                const DistParams none{1.0f, 0.0f, 0.0f};
-                float *policy = sh.tmp[4], *bw = sh.tmp[5], *bp = sh.tmp[6];
-                uint32_t* v = sh.tmpu;
-                for (uint32_t w = 0; w < RP_NLHE_WORLDS; ++w) {
-                    float* r = sh.tmp[w];  // kept for the regret fold
-                    const int ri = nd_find_row(rows, n_rows, sh.pub.path.tail, choices, present | (w << NS_TAG_SHIFT));
-                    if (ri >= 0) {
-                        for (uint32_t a = 0; a < NLMC_A; ++a) {
-                            r[a] = rows.at(ri).r[a];
-                            v[a] = rows.at(ri).v[a];
-                        }
-                    } else {
-                        nd_blueprint(t, sh.pub.path.tail, choices, present, r, bw, bp, v);
-                        for (uint32_t a = 0; a < NLMC_A; ++a) r[a] = rp_maxf(r[a], RP_EPSILON);
-                    }
-                    policy_distribution<NLMC_A>((int)RP_DIST_ITERATED, none, r, nch, policy);
-                    for (uint32_t a = 0; a < nch; ++a) {
-                        out.refined[a] += policy[a] / 4.0f;  // from the zero of the cleared result
-                        out.visits[a] += v[a];                // wrapping
-                    }
-                }
-                float regret = 0.0f;  // edges outer, in the BTreeMap's key order; worlds inner
-                for (uint32_t k = 0; k < NS_EDGE_ORDERS; ++k)
-                    for (uint32_t a = 0; a < nch; ++a) {
-                        if (ns_edge_order((uint32_t)(choices >> (5u * a)) & 31u) != k) continue;
-                        for (uint32_t w = 0; w < RP_NLHE_WORLDS; ++w) regret += rp_maxf(sh.tmp[w][a], 0.0f);
-                    }
-                out.regret = regret;
-                out.past = sh.pub.path.tail;
-                out.choices = choices;
-                out.present = present;
-                out.n_actions = (uint8_t)nch;
-                if (err) {
-                    out = rp_nlhe_subgame_result{};
-                    out.status = (uint8_t)RP_RECALL_LOOKUP;
-                    sh.status = RP_RECALL_LOOKUP;
+        for (uint32_t w = 0; w < RP_NLHE_WORLDS; ++w) out.drawn[w] = sw.drawn[w];
+        out.attempts = sw.attempts;
+        out.fallbacks = sw.fallbacks;
+        const G2 g = sh.pub.game;  // as the last iteration dealt it
+        const int turn = g.turn();
+        if (turn >= 0) {  // Harvest at WorldInfo(w, Game(info of the entry state)), w = 0 .. 3
+            const NdEntry e = nd_entry(p, g, turn, sh.pub.path);
+            const DistParams none{1.0f, 0.0f, 0.0f};
+            float* policy = sh.tmp[4];
+            uint32_t* v = sh.tmpu;
+            for (uint32_t w = 0; w < RP_NLHE_WORLDS; ++w) {
+                float* r = sh.tmp[w];  // kept for the regret fold
+                nd_entry_row(t, rows, sh.n_rows, sh.pub.path.tail, e, w << NS_TAG_SHIFT, r, v, sh.tmp[5], sh.tmp[6]);
+                policy_distribution<NLMC_A>((int)RP_DIST_ITERATED, none, r, e.nch, policy);
+                for (uint32_t a = 0; a < e.nch; ++a) {
+                    out.refined[a] += policy[a] / 4.0f;  // from the zero of the cleared result
+                    out.visits[a] += v[a];                // wrapping
                 }
             }
+            float regret = 0.0f;  // edges outer, in the BTreeMap's key order; worlds inner
+            for (uint32_t k = 0; k < NS_EDGE_ORDERS; ++k)
+                for (uint32_t a = 0; a < e.nch; ++a) {
+                    if (ns_edge_order((uint32_t)(e.choices >> (5u * a)) & 31u) != k) continue;
+                    for (uint32_t w = 0; w < RP_NLHE_WORLDS; ++w) regret += rp_maxf(sh.tmp[w][a], 0.0f);
+                }
+            nd_result_entry(out, sh, e, regret);
         }
     }
     __syncthreads();
     const bool ok = sh.status == RP_RECALL_OK;
-    if (q.rows) {
-        const uint32_t n_rows = ok ? sh.n_rows : 0u;
-        for (uint32_t x = tid; x < q.rows_cap; x += NS_BLOCK) {
-            rp_nlhe_subgame_row& o = q.rows[(size_t)i * q.rows_cap + x];
-            o = rp_nlhe_subgame_row{};
-            if (x < n_rows) {
-                const NdRow& row = rows.at(s_rank[x]);
-                o.kind = (uint8_t)(row.present_kind >> 31);
-                o.n_actions = (uint8_t)row.nch;
-                o.world = (uint8_t)((row.present_kind >> NS_TAG_SHIFT) & 3u);
-                o.present = row.present_kind & NS_PRESENT_MASK;
-                o.past = row.past;
-                o.choices = row.choices;
-                for (uint32_t a = 0; a < row.nch; ++a) o.enc[a] = rp_encounter{row.w[a], row.r[a], row.p[a], row.v[a]};
-            }
-        }
-    }
+    if (q.rows) nd_export(q.rows + (size_t)i * q.rows_cap, q.rows_cap, ok ? sh.n_rows : 0u, rows, s_rank);
     if (q.deals) {  // the deals of the iterations done; none of a solve that failed
         const uint32_t done = ok ? sh.t : 0u;
         for (uint32_t x = tid; x < q.deals_cap; x += NS_BLOCK)

@@ -45,6 +45,18 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _dptr(t, live):
+    """the address of a device tensor for a _device call; NULL where ``live`` is false (nothing to do) or there is no tensor"""
+    return C.c_void_p(t.data_ptr()) if live and t is not None else None
+
+
+def _records(t, dtype):
+    """a device uint8 tensor holding packed ``dtype`` records -> (the tensor contiguous, n, its device)"""
+    t = t.contiguous()
+    assert t.is_cuda and t.element_size() == 1 and t.numel() % dtype.itemsize == 0
+    return t, t.numel() // dtype.itemsize, t.device
+
+
 class Recall:
     """What one seat has seen, at edge level: a ``Witness`` (crates/kicker/src/witness.rs:36-44) after ``Recall::history()``.
     ``hole``: pov's two cards as a mask (bit c = card c); ``draws``: up to three masks (flop, turn, river) in street order;
@@ -273,6 +285,13 @@ class NlheSolver:
         assert ks[0].size == ks[1].size == ks[2].size
         return False, *ks
 
+    def _queue(self, fn, d, live, keys, *args):
+        """a _device call on the solver's stream: whatever produced the inputs on torch's current stream has finished first; tensors
+        among ``args`` go as addresses (``_dptr``); ``keys``, which the queued launch reads, stay referenced"""
+        torch.cuda.current_stream(d).synchronize()
+        _lib.check(fn(self._h, *[_dptr(a, live) if isinstance(a, torch.Tensor) else a for a in args]))
+        self._query_keys = keys
+
     def policy(self, past, present, choices, kind="averaged"):
         """``Brain::policy`` / ``Source::strategy`` for n infosets: dict(policy float32[n,9], edges uint8[n,9], n_actions uint8[n],
         found bool[n]); kind: "iterated", "averaged", "sampling".  Read-only.  Device tensors in -> device tensors out, queued on the
@@ -282,11 +301,8 @@ class NlheSolver:
             n, d = past.numel(), past.device
             out = dict(policy=torch.empty((n, A), dtype=torch.float32, device=d), edges=torch.empty((n, A), dtype=torch.uint8, device=d),
                        n_actions=torch.empty(n, dtype=torch.uint8, device=d), found=torch.empty(n, dtype=torch.uint8, device=d))
-            torch.cuda.current_stream(d).synchronize()  # whatever produced the keys on torch's stream has finished
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if n else None
-            _lib.check(self._lib.rp_nlhe_policy_device(self._h, _lib.DIST[kind], n, ptr(past), ptr(present), ptr(choices), ptr(out["policy"]),
-                                                       ptr(out["edges"]), ptr(out["n_actions"]), ptr(out["found"])))
-            self._query_keys = (past, present, choices)  # the queued launch reads them
+            self._queue(self._lib.rp_nlhe_policy_device, d, n, (past, present, choices), _lib.DIST[kind], n, past, present, choices,
+                        out["policy"], out["edges"], out["n_actions"], out["found"])
             out["found"] = out["found"].view(torch.bool)
             return out
         n = past.size
@@ -305,10 +321,7 @@ class NlheSolver:
             n, d = past.numel(), past.device
             enc = torch.empty((n, A, ENC_DTYPE.itemsize), dtype=torch.uint8, device=d)
             nact, found = torch.empty(n, dtype=torch.uint8, device=d), torch.empty(n, dtype=torch.uint8, device=d)
-            torch.cuda.current_stream(d).synchronize()
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if n else None
-            _lib.check(self._lib.rp_nlhe_memory_device(self._h, n, ptr(past), ptr(present), ptr(choices), ptr(enc), ptr(nact), ptr(found)))
-            self._query_keys = (past, present, choices)
+            self._queue(self._lib.rp_nlhe_memory_device, d, n, (past, present, choices), n, past, present, choices, enc, nact, found)
             return enc, nact, found.view(torch.bool)
         n = past.size
         enc, nact, found = np.zeros((n, A), dtype=ENC_DTYPE), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
@@ -353,29 +366,19 @@ class NlheSolver:
         """rp_nlhe_reaches_device: ``recalls_dev`` a device uint8 tensor [n, 88] (``torch.from_numpy(Recall.pack(..).view(np.uint8))``);
         -> dict of device tensors (count int32[n], holes int64[n,1326], reach float32[n,1326], status uint8[n]), queued on the
         solver's stream (``sync()`` waits)"""
-        rec = recalls_dev.contiguous()
-        assert rec.is_cuda and rec.element_size() == 1 and rec.numel() % RECALL_DTYPE.itemsize == 0
-        n, d = rec.numel() // RECALL_DTYPE.itemsize, rec.device
+        rec, n, d = _records(recalls_dev, RECALL_DTYPE)
         out = dict(count=torch.empty(n, dtype=torch.int32, device=d), holes=torch.empty((n, MAX_HOLES), dtype=torch.int64, device=d),
                    reach=torch.empty((n, MAX_HOLES), dtype=torch.float32, device=d), status=torch.empty(n, dtype=torch.uint8, device=d))
-        torch.cuda.current_stream(d).synchronize()
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if n else None
-        _lib.check(self._lib.rp_nlhe_reaches_device(self._h, _lib.REACH[kind], 1 if normalize else 0, n, ptr(rec), ptr(out["count"]),
-                                                    ptr(out["holes"]), ptr(out["reach"]), ptr(out["status"])))
-        self._query_keys = (rec,)  # the queued launch reads them
+        self._queue(self._lib.rp_nlhe_reaches_device, d, n, (rec,), _lib.REACH[kind], 1 if normalize else 0, n, rec, out["count"], out["holes"],
+                    out["reach"], out["status"])
         return out
 
     def opponent_range_device(self, recalls_dev):
         """rp_nlhe_opponent_range_device: -> device tensors (mass float32[n,256], seen uint8[n,256], status uint8[n])"""
-        rec = recalls_dev.contiguous()
-        assert rec.is_cuda and rec.element_size() == 1 and rec.numel() % RECALL_DTYPE.itemsize == 0
-        n, d = rec.numel() // RECALL_DTYPE.itemsize, rec.device
+        rec, n, d = _records(recalls_dev, RECALL_DTYPE)
         mass = torch.empty((n, BUCKETS), dtype=torch.float32, device=d)
         seen, status = torch.empty((n, BUCKETS), dtype=torch.uint8, device=d), torch.empty(n, dtype=torch.uint8, device=d)
-        torch.cuda.current_stream(d).synchronize()
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if n else None
-        _lib.check(self._lib.rp_nlhe_opponent_range_device(self._h, n, ptr(rec), ptr(mass), ptr(seen), ptr(status)))
-        self._query_keys = (rec,)
+        self._queue(self._lib.rp_nlhe_opponent_range_device, d, n, (rec,), n, rec, mass, seen, status)
         return mass, seen, status
 
     # ---- frontier payoffs (include/rp_mi355x.h rp_nlhe_frontier_payoffs): biased continuation rollouts from depth-limited leaves ----
@@ -396,24 +399,22 @@ class NlheSolver:
         """rp_nlhe_frontier_payoffs_device: ``frontiers_dev`` a device uint8 tensor [n, 112]
         (``torch.from_numpy(Frontier.pack(..).view(np.uint8))``); -> device tensors (payoffs float32[n,4,4], status uint8[n]) and, with
         ``return_won``, won int16[n,16,rollouts], queued on the solver's stream (``sync()`` waits)"""
-        fr = frontiers_dev.contiguous()
-        assert fr.is_cuda and fr.element_size() == 1 and fr.numel() % FRONTIER_DTYPE.itemsize == 0
-        n, d, r = fr.numel() // FRONTIER_DTYPE.itemsize, fr.device, max(int(rollouts), 1)
+        (fr, n, d), r = _records(frontiers_dev, FRONTIER_DTYPE), max(int(rollouts), 1)
         pay = torch.empty((n, LEAVES, LEAVES), dtype=torch.float32, device=d)
         status = torch.empty(n, dtype=torch.uint8, device=d)
         won = torch.empty((n, LEAVES * LEAVES, min(r, MAX_ROLLOUTS)), dtype=torch.int16, device=d) if return_won else None
-        torch.cuda.current_stream(d).synchronize()
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if n and t is not None else None
-        _lib.check(self._lib.rp_nlhe_frontier_payoffs_device(self._h, n, ptr(fr), bias, int(rollouts), seed, first_id, ptr(pay), ptr(won),
-                                                             ptr(status)))
-        self._query_keys = (fr,)  # the queued launch reads them
+        self._queue(self._lib.rp_nlhe_frontier_payoffs_device, d, n, (fr,), n, fr, bias, int(rollouts), seed, first_id, pay, won, status)
         return (pay, status, won) if return_won else (pay, status)
 
     # ---- depth-limited re-solve (include/rp_mi355x.h rp_nlhe_depth_solve): DepthSolver steps and harvest, many solves per launch ----
-    def _depth_args(self, iterations, rollouts, bias, prior, seed, first_id, rows_cap):
-        a = _lib.NlheDepthArgs()
-        self._lib.rp_nlhe_depth_args_default(C.byref(a))
+    @staticmethod
+    def _solve_args(struct, default_fn, iterations, rollouts, bias, prior, seed, first_id, rows_cap, deals_cap=None):
+        """rp_nlhe_depth_args / rp_nlhe_subgame_args (``deals_cap``): the library's defaults where an argument is None"""
+        a = struct()
+        default_fn(C.byref(a))
         a.iterations, a.seed, a.first_id, a.rows_cap = int(iterations), seed, first_id, int(rows_cap)
+        if deals_cap is not None:
+            a.deals_cap = int(deals_cap)
         if rollouts is not None:
             a.rollouts = int(rollouts)
         if bias is not None:
@@ -443,10 +444,11 @@ class NlheSolver:
         return Frontier.pack(entries)
 
     @staticmethod
-    def _origin(origin, n):
+    def _origin(origin, n, none_value=ORIGIN_ENTRY):
+        """-> int8[n] or None; ``none_value``: what a None among per-entry origins reads as (ORIGIN_ENTRY: depth, ORIGIN_NONE: subgame)"""
         if origin is None:
             return None
-        o = np.full(n, origin, np.int8) if np.isscalar(origin) else np.array([ORIGIN_ENTRY if x is None else x for x in origin], np.int8)
+        o = np.full(n, origin, np.int8) if np.isscalar(origin) else np.array([none_value if x is None else x for x in origin], np.int8)
         assert o.size == n
         return o
 
@@ -461,7 +463,7 @@ class NlheSolver:
         ``seed``: a batch split into calls with matching ``first_id`` answers the same bits.  Read-only."""
         en = self.depth_entries(entries)
         n = en.size
-        a = self._depth_args(iterations, rollouts, bias, prior, seed, first_id, rows_cap)
+        a = self._solve_args(_lib.NlheDepthArgs, self._lib.rp_nlhe_depth_args_default, iterations, rollouts, bias, prior, seed, first_id, rows_cap)
         o = self._origin(origin, n)
         res, rows = np.zeros(n, DEPTH_RESULT_DTYPE), np.zeros((n, int(rows_cap)), DEPTH_ROW_DTYPE)
         _lib.check(self._lib.rp_nlhe_depth_solve(self._h, n, _p(en), _p(o), C.byref(a), _p(res), _p(rows) if rows_cap else None))
@@ -472,32 +474,16 @@ class NlheSolver:
         """rp_nlhe_depth_solve_device: ``entries_dev`` a device uint8 tensor [n, 112], ``origin_dev`` a device int8 tensor [n] or None;
         -> device uint8 tensors (results [n, 144], rows [n, rows_cap, 168]) queued on the solver's stream (``sync()`` waits); view
         them with DEPTH_RESULT_DTYPE / DEPTH_ROW_DTYPE on the host"""
-        en = entries_dev.contiguous()
-        assert en.is_cuda and en.element_size() == 1 and en.numel() % FRONTIER_DTYPE.itemsize == 0
-        n, d = en.numel() // FRONTIER_DTYPE.itemsize, en.device
+        en, n, d = _records(entries_dev, FRONTIER_DTYPE)
         assert origin_dev is None or (origin_dev.is_cuda and origin_dev.dtype == torch.int8 and origin_dev.numel() == n)
-        a = self._depth_args(iterations, rollouts, bias, prior, seed, first_id, rows_cap)
+        a = self._solve_args(_lib.NlheDepthArgs, self._lib.rp_nlhe_depth_args_default, iterations, rollouts, bias, prior, seed, first_id, rows_cap)
         res = torch.empty((n, DEPTH_RESULT_DTYPE.itemsize), dtype=torch.uint8, device=d)
         rows = torch.empty((n, int(rows_cap), DEPTH_ROW_DTYPE.itemsize), dtype=torch.uint8, device=d)
-        torch.cuda.current_stream(d).synchronize()
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if n and t is not None and t.numel() else None
-        _lib.check(self._lib.rp_nlhe_depth_solve_device(self._h, n, ptr(en), ptr(origin_dev), C.byref(a), ptr(res), ptr(rows)))
-        self._query_keys = (en, origin_dev)  # the queued launch reads them
+        self._queue(self._lib.rp_nlhe_depth_solve_device, d, n, (en, origin_dev), n, en, origin_dev, C.byref(a), res,
+                    rows if int(rows_cap) else None)
         return res, rows
 
     # ---- safe subgame re-solve (include/rp_mi355x.h rp_nlhe_subgame_solve): SubGameSolver steps and harvest, many solves per launch ----
-    def _subgame_args(self, iterations, rollouts, bias, prior, seed, first_id, rows_cap, deals_cap):
-        a = _lib.NlheSubgameArgs()
-        self._lib.rp_nlhe_subgame_args_default(C.byref(a))
-        a.iterations, a.seed, a.first_id, a.rows_cap, a.deals_cap = int(iterations), seed, first_id, int(rows_cap), int(deals_cap)
-        if rollouts is not None:
-            a.rollouts = int(rollouts)
-        if bias is not None:
-            a.bias = bias
-        if prior is not None:
-            a.prior = prior
-        return a
-
     @staticmethod
     def subgame_recalls(entries) -> np.ndarray:
         """-> RECALL_DTYPE[n]: the recall whose belief a subgame solve of each entry wants — ``internal``'s point of view of the
@@ -510,14 +496,6 @@ class NlheSolver:
                 rec[i][k] = f[k]
             rec[i]["pov"] = f["internal"]
         return rec
-
-    @staticmethod
-    def _subgame_origin(origin, n):
-        if origin is None:
-            return None
-        o = np.full(n, origin, np.int8) if np.isscalar(origin) else np.array([ORIGIN_NONE if x is None else x for x in origin], np.int8)
-        assert o.size == n
-        return o
 
     def subgame_solve(self, entries, beliefs, origin=None, iterations=1, rollouts=None, bias=None, prior=None, seed=0, first_id=0, rows_cap=0,
                       deals_cap=0):
@@ -535,8 +513,9 @@ class NlheSolver:
             beliefs = (beliefs["hole_world"], beliefs["weights"])
         hw = np.ascontiguousarray(beliefs[0], np.uint8).reshape(n, MAX_HOLES)
         wt = np.ascontiguousarray(beliefs[1], np.float32).reshape(n, WORLDS)
-        a = self._subgame_args(iterations, rollouts, bias, prior, seed, first_id, rows_cap, deals_cap)
-        o = self._subgame_origin(origin, n)
+        a = self._solve_args(_lib.NlheSubgameArgs, self._lib.rp_nlhe_subgame_args_default, iterations, rollouts, bias, prior, seed, first_id,
+                             rows_cap, deals_cap)
+        o = self._origin(origin, n, ORIGIN_NONE)
         res, rows = np.zeros(n, SUBGAME_RESULT_DTYPE), np.zeros((n, int(rows_cap)), SUBGAME_ROW_DTYPE)
         deals = np.zeros((n, int(deals_cap)), SUBGAME_DEAL_DTYPE)
         _lib.check(self._lib.rp_nlhe_subgame_solve(self._h, n, _p(en), _p(hw), _p(wt), _p(o), C.byref(a), _p(res), _p(rows) if rows_cap else None,
@@ -549,21 +528,17 @@ class NlheSolver:
         ``weights_dev`` float32 [n, 4] as ``belief_device`` returns them (no host copy in between); ``origin_dev`` a device int8
         tensor [n] or None; -> device uint8 tensors (results [n, 176], rows [n, rows_cap, 168], deals [n, deals_cap, 16]) queued on the
         solver's stream (``sync()`` waits); view them with the SUBGAME_*_DTYPEs on the host"""
-        en, hw, wt = entries_dev.contiguous(), hole_world_dev.contiguous(), weights_dev.contiguous()
-        assert en.is_cuda and en.element_size() == 1 and en.numel() % FRONTIER_DTYPE.itemsize == 0
-        n, d = en.numel() // FRONTIER_DTYPE.itemsize, en.device
+        (en, n, d), hw, wt = _records(entries_dev, FRONTIER_DTYPE), hole_world_dev.contiguous(), weights_dev.contiguous()
         assert hw.is_cuda and hw.element_size() == 1 and hw.numel() == n * MAX_HOLES
         assert wt.is_cuda and wt.dtype == torch.float32 and wt.numel() == n * WORLDS
         assert origin_dev is None or (origin_dev.is_cuda and origin_dev.dtype == torch.int8 and origin_dev.numel() == n)
-        a = self._subgame_args(iterations, rollouts, bias, prior, seed, first_id, rows_cap, deals_cap)
+        a = self._solve_args(_lib.NlheSubgameArgs, self._lib.rp_nlhe_subgame_args_default, iterations, rollouts, bias, prior, seed, first_id,
+                             rows_cap, deals_cap)
         res = torch.empty((n, SUBGAME_RESULT_DTYPE.itemsize), dtype=torch.uint8, device=d)
         rows = torch.empty((n, int(rows_cap), SUBGAME_ROW_DTYPE.itemsize), dtype=torch.uint8, device=d)
         deals = torch.empty((n, int(deals_cap), SUBGAME_DEAL_DTYPE.itemsize), dtype=torch.uint8, device=d)
-        torch.cuda.current_stream(d).synchronize()
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if n and t is not None and t.numel() else None
-        _lib.check(self._lib.rp_nlhe_subgame_solve_device(self._h, n, ptr(en), ptr(hw), ptr(wt), ptr(origin_dev), C.byref(a), ptr(res), ptr(rows),
-                                                          ptr(deals)))
-        self._query_keys = (en, hw, wt, origin_dev)  # the queued launch reads them
+        self._queue(self._lib.rp_nlhe_subgame_solve_device, d, n, (en, hw, wt, origin_dev), n, en, hw, wt, origin_dev, C.byref(a), res,
+                    rows if int(rows_cap) else None, deals if int(deals_cap) else None)
         return res, rows, deals
 
     # ---- subgame worlds (include/rp_mi355x.h rp_nlhe_partition / rp_nlhe_belief / rp_nlhe_restrict): the opponent's range in quantile worlds ----
@@ -586,10 +561,7 @@ class NlheSolver:
         assert mass.numel() % BUCKETS == 0 and seen.numel() == mass.numel()
         n, d = mass.numel() // BUCKETS, mass.device
         world, weights = torch.empty((n, BUCKETS), dtype=torch.uint8, device=d), torch.empty((n, WORLDS), dtype=torch.float32, device=d)
-        torch.cuda.current_stream(d).synchronize()
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if n else None
-        _lib.check(self._lib.rp_nlhe_partition_device(self._h, n, ptr(mass), ptr(seen), ptr(world), ptr(weights)))
-        self._query_keys = (mass, seen)  # the queued launch reads them
+        self._queue(self._lib.rp_nlhe_partition_device, d, n, (mass, seen), n, mass, seen, world, weights)
         return world, weights
 
     def belief(self, recalls):
@@ -605,16 +577,10 @@ class NlheSolver:
 
     def belief_device(self, recalls_dev):
         """rp_nlhe_belief_device: ``recalls_dev`` as for ``reaches_device`` -> dict of device tensors as ``belief`` returns them"""
-        rec = recalls_dev.contiguous()
-        assert rec.is_cuda and rec.element_size() == 1 and rec.numel() % RECALL_DTYPE.itemsize == 0
-        n, d = rec.numel() // RECALL_DTYPE.itemsize, rec.device
+        rec, n, d = _records(recalls_dev, RECALL_DTYPE)
         out = dict(world=torch.empty((n, BUCKETS), dtype=torch.uint8, device=d), weights=torch.empty((n, WORLDS), dtype=torch.float32, device=d),
                    hole_world=torch.empty((n, MAX_HOLES), dtype=torch.uint8, device=d), status=torch.empty(n, dtype=torch.uint8, device=d))
-        torch.cuda.current_stream(d).synchronize()
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if n else None
-        _lib.check(self._lib.rp_nlhe_belief_device(self._h, n, ptr(rec), ptr(out["world"]), ptr(out["weights"]), ptr(out["hole_world"]),
-                                                   ptr(out["status"])))
-        self._query_keys = (rec,)
+        self._queue(self._lib.rp_nlhe_belief_device, d, n, (rec,), n, rec, out["world"], out["weights"], out["hole_world"], out["status"])
         return out
 
     def restrict(self, recalls, deals=1, worlds=None, seed=0, first_id=0):
@@ -636,20 +602,15 @@ class NlheSolver:
         """rp_nlhe_restrict_device: ``recalls_dev`` as for ``reaches_device``, ``worlds_dev`` None or a device uint8 tensor [n, deals] ->
         dict of device tensors (holes int64[n,deals], world uint8[n,deals], attempts int16[n,deals], status uint8[n]), queued on the
         solver's stream (``sync()`` waits)"""
-        rec = recalls_dev.contiguous()
-        assert rec.is_cuda and rec.element_size() == 1 and rec.numel() % RECALL_DTYPE.itemsize == 0
-        n, d, deals = rec.numel() // RECALL_DTYPE.itemsize, rec.device, int(deals)
+        (rec, n, d), deals = _records(recalls_dev, RECALL_DTYPE), int(deals)
         w = None
         if worlds_dev is not None:
             w = worlds_dev.contiguous()
             assert w.is_cuda and w.element_size() == 1 and w.numel() == n * deals
         out = dict(holes=torch.empty((n, deals), dtype=torch.int64, device=d), world=torch.empty((n, deals), dtype=torch.uint8, device=d),
                    attempts=torch.empty((n, deals), dtype=torch.int16, device=d), status=torch.empty(n, dtype=torch.uint8, device=d))
-        torch.cuda.current_stream(d).synchronize()
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if n and deals and t is not None else None
-        _lib.check(self._lib.rp_nlhe_restrict_device(self._h, n, ptr(rec), deals, ptr(w), seed, first_id, ptr(out["holes"]), ptr(out["world"]),
-                                                     ptr(out["attempts"]), ptr(out["status"])))
-        self._query_keys = (rec, w)
+        self._queue(self._lib.rp_nlhe_restrict_device, d, n and deals, (rec, w), n, rec, deals, w, seed, first_id, out["holes"], out["world"],
+                    out["attempts"], out["status"])
         return out
 
 

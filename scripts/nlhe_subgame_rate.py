@@ -10,8 +10,10 @@ beliefs come from rp_nlhe_belief_device once, before any timed window, and stay 
               timed from the call to rp_nlhe_sync.
   depth       rp_nlhe_depth_solve_device on the same entries (their own holes), iterations and rollouts: the entry's street against
               ORIGIN_NONE (neither has a frontier), street - 1 against street - 1.  `ratio` = subgame / depth, medians.
-  depth_parent  with --parent-lib: the same depth solve through the PARENT commit's library, loaded beside this one, over a copy of the
-              same table, in the same alternating runs at the largest batch: whether adding the second kernel changed the first.
+  depth_parent, subgame_parent  with --parent-lib: the same two solves through the PARENT commit's library, loaded beside this one, over a
+              copy of the same table, in the same alternating runs at every batch — this build, the parent, this build, the parent, so
+              that every timed call follows one over the other build's table.  `*_equals_parent_bytes`: the result bytes;
+              `*_within_parent_spread`: this build's median inside the parent's own min - max, the noise of the host clock.
 All are timed with a host clock, alternating, `--runs` runs each after a warm-up of every shape; median, min and max.
 `model_bits_equal`: the first entries solved for 2 iterations against tests/nlhe_subgame_model.py over the exported table and the
 device's belief — result, rows and deals.  For the whole run: mean attempts per deal, the share of fallbacks, the largest row count.
@@ -33,25 +35,11 @@ sys.path.insert(0, os.path.join(R, "scripts"))
 say = lambda m: print(m, file=sys.stderr, flush=True)  # noqa: E731
 
 # as hipcc -Rpass-analysis=kernel-resource-usage reports them for gfx950 (csrc/Makefile's flags)
-STATIC = {"k_nl_subgame": {"vgprs": 149, "agprs": 0, "sgprs": 104, "sgpr_spills": 77, "vgpr_spills": 0, "scratch_bytes_per_lane": 80,
-                           "lds_bytes_per_block": 62152, "occupancy_waves_per_simd": 2, "block": 256},
-          "k_nl_depth": {"vgprs": 147, "agprs": 0, "sgprs": 104, "sgpr_spills": 80, "vgpr_spills": 0, "scratch_bytes_per_lane": 80,
+STATIC = {"k_nl_subgame": {"vgprs": 148, "agprs": 0, "sgprs": 104, "sgpr_spills": 85, "vgpr_spills": 0, "scratch_bytes_per_lane": 80,
+                           "lds_bytes_per_block": 61128, "occupancy_waves_per_simd": 2, "block": 256},
+          "k_nl_depth": {"vgprs": 146, "agprs": 0, "sgprs": 104, "sgpr_spills": 80, "vgpr_spills": 0, "scratch_bytes_per_lane": 80,
                          "lds_bytes_per_block": 58640, "occupancy_waves_per_simd": 2, "block": 256}}
 SEED, ROLLOUTS, BIAS, PRIOR = 7, 16, 5.0, 16384.0
-
-
-class Table:
-    """the exported blueprint as the model reads it"""
-
-    def __init__(self, past, present, choices, enc):
-        self.rows = {(int(p), int(q), int(c)): enc[i] for i, (p, q, c) in enumerate(zip(past, present, choices))}
-
-    def enc(self, key):
-        return self.rows.get(key)
-
-    def get(self, key):
-        row = self.rows.get(key)
-        return None if row is None else row["weight"]
 
 
 def parent_solver(path, like, table, epoch, cap_log2, batch):
@@ -92,6 +80,7 @@ def main():
     import torch
 
     import nlhe_subgame_model as SM
+    from nlhe_solve_common import Table
     from nlhe_subgame_caps import flop_entries
     from robopoker_amd import _lib
     from robopoker_amd.nlhe import DEPTH_RESULT_DTYPE, SUBGAME_RESULT_DTYPE, NlheSolver
@@ -155,10 +144,10 @@ def main():
         per_batch = {}
         for iterations in [int(x) for x in args.iterations.split(",")]:
             for name, (og_sub, og_depth) in origin.items():
-                def subgame():
+                def subgame(solver=s):
                     t0 = time.perf_counter()
-                    ans = s.subgame_solve_device(en, hw, wt, og_sub, iterations, ROLLOUTS, BIAS, PRIOR, SEED, 0, 0, 0)
-                    s.sync()
+                    ans = solver.subgame_solve_device(en, hw, wt, og_sub, iterations, ROLLOUTS, BIAS, PRIOR, SEED, 0, 0, 0)
+                    solver.sync()
                     return time.perf_counter() - t0, ans
 
                 def depth(solver=s):
@@ -167,18 +156,23 @@ def main():
                     solver.sync()
                     return time.perf_counter() - t0, ans
 
-                with_parent = sp is not None and n == max(batches)
+                with_parent = sp is not None
                 _, got = subgame()  # warm-up, and what the solves did
                 _, got_depth = depth()
                 if with_parent:
                     _, got_parent = depth(sp)
                     same_as_parent = got_parent[0].cpu().numpy().tobytes() == got_depth[0].cpu().numpy().tobytes()
+                    subgame_same_as_parent = subgame(sp)[1][0].cpu().numpy().tobytes() == got[0].cpu().numpy().tobytes()
                 r = got[0].cpu().numpy().view(SUBGAME_RESULT_DTYPE).reshape(n)
                 rd = got_depth[0].cpu().numpy().view(DEPTH_RESULT_DTYPE).reshape(n)
                 ok = r["status"] == 0
-                ts, td, tp = [], [], []
+                ts, td, tp, tsp = [], [], [], []
                 for _ in range(args.runs):
+                    # the two builds hold a table each, and a call that follows one over its own table finds it cached: with the parent,
+                    # every timed call of either build follows one over the OTHER build's table
                     ts.append(subgame()[0])
+                    if with_parent:
+                        tsp.append(subgame(sp)[0])
                     td.append(depth()[0])
                     if with_parent:
                         tp.append(depth(sp)[0])
@@ -194,20 +188,27 @@ def main():
                          {int(k): int(v) for k, v in zip(*np.unique(rd["status"], return_counts=True))},
                          "attempts_per_deal": float(r["attempts"][ok].sum()) / max(done, 1), "fallbacks": int(r["fallbacks"][ok].sum()),
                          "drawn": [int(x) for x in r["drawn"][ok].sum(axis=0)]}
-                for key, tt in (("subgame", ts), ("depth", td)) + ((("depth_parent", tp),) if with_parent else ()):
+                for key, tt in (("subgame", ts), ("depth", td)) + ((("depth_parent", tp), ("subgame_parent", tsp)) if with_parent else ()):
                     entry[key] = {"seconds": tt, "median_s": float(np.median(tt)), "min_s": min(tt), "max_s": max(tt)}
                 entry["ratio"] = entry["subgame"]["median_s"] / entry["depth"]["median_s"]
                 entry["subgame"]["iterations_per_s"] = done / entry["subgame"]["median_s"]
                 if with_parent:
                     entry["depth_equals_parent_bytes"] = bool(same_as_parent)
                     entry["depth_over_parent"] = entry["depth"]["median_s"] / entry["depth_parent"]["median_s"]
+                    entry["subgame_equals_parent_bytes"] = bool(subgame_same_as_parent)
+                    entry["subgame_over_parent"] = entry["subgame"]["median_s"] / entry["subgame_parent"]["median_s"]
+                    for kind in ("depth", "subgame"):  # this build's median inside the parent's own spread of the same alternating runs
+                        own, par = entry[kind], entry[kind + "_parent"]
+                        entry[kind + "_within_parent_spread"] = bool(par["min_s"] <= own["median_s"] <= par["max_s"])
+                        entry[kind + "_above_parent_max"] = bool(own["median_s"] > par["max_s"])
                 per_batch[f"iterations_{iterations}_{name}"] = entry
                 say(f"batch {n}, {iterations} iterations, {name}: subgame {entry['subgame']['median_s'] * 1e3:.3f} ms [{min(ts) * 1e3:.3f}, "
                     f"{max(ts) * 1e3:.3f}], depth {entry['depth']['median_s'] * 1e3:.3f} ms [{min(td) * 1e3:.3f}, {max(td) * 1e3:.3f}], ratio "
                     f"{entry['ratio']:.2f}; {entry['solves_ok']} ok, statuses {statuses}, max rows {entry['max_rows']} (depth {entry['depth_max_rows']}), "
                     f"{entry['attempts_per_deal']:.2f} attempts per deal, {entry['fallbacks']} fallbacks"
                     + (f"; parent's depth {entry['depth_parent']['median_s'] * 1e3:.3f} ms [{min(tp) * 1e3:.3f}, {max(tp) * 1e3:.3f}], same bytes "
-                       f"{same_as_parent}" if with_parent else ""))
+                       f"{same_as_parent}; parent's subgame {entry['subgame_parent']['median_s'] * 1e3:.3f} ms [{min(tsp) * 1e3:.3f}, "
+                       f"{max(tsp) * 1e3:.3f}], same bytes {subgame_same_as_parent}" if with_parent else ""))
         out["results"][str(n)] = per_batch
     out["whole_run"] = {"deals": total_deals, "mean_attempts_per_deal": total_attempts / max(total_deals, 1),
                         "fallback_share": total_fallbacks / max(total_deals, 1), "largest_row_count": largest_rows,

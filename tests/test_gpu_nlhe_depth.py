@@ -14,6 +14,7 @@ import torch
 import nlhe_depth_model as DM
 import nlhe_rollout_model as FM
 import oracle_nlhe as ON
+from nlhe_solve_common import bits, cards
 from robopoker_amd import _lib
 from robopoker_amd.nlhe import DEPTH_RESULT_DTYPE, DEPTH_ROW_DTYPE, Frontier, NlheSolver
 
@@ -22,12 +23,6 @@ pytestmark = pytest.mark.gpu
 OPEN2, OPEN3, POT, HALF = ON.Open(2), ON.Open(3), ON.RaiseOdds(1, 1), ON.RaiseOdds(1, 2)
 DRAW, FOLD, CHECK, CALL, SHOVE = ON.E_DRAW, ON.E_FOLD, ON.E_CHECK, ON.E_CALL, ON.E_SHOVE
 BIAS, PRIOR, SEED, FIRST_ID, EPOCH, ROWS_CAP = 5.0, 64.0, 0x5EED, 1000, 3, 48
-
-
-def cards(*cs):
-    return sum(1 << c for c in cs)
-
-
 HOLES, FLOP, TURN, RIVER = (cards(51, 50), cards(12, 25)), cards(3, 17, 30), cards(44), cards(9)
 TO_THE_RIVER = [OPEN2, CALL, DRAW, CHECK, CHECK, DRAW, CHECK, CHECK, DRAW, CHECK, POT]  # 11 edges, seat 1 to answer a river bet
 TO_THE_FLOP = [OPEN2, CALL, DRAW]
@@ -90,10 +85,6 @@ class Model:
 @pytest.fixture(scope="module")
 def model():
     return Model()
-
-
-def bits(x):
-    return np.ascontiguousarray(x, np.float32).view(np.uint32)
 
 
 def entries():
@@ -366,3 +357,23 @@ def test_a_history_past_the_cap_is_a_status(gpu):
     res, rows = s.depth_solve([entry, entry, FLOP_NEXT], [0, None, 0], 2, 1, BIAS, PRIOR, SEED, FIRST_ID, ROWS_CAP)
     for i in range(3):
         assert_equal(res[i], rows[i], want[i], i)
+
+
+def test_the_rows_kept_are_the_first_in_rank_order(gpu):
+    """rows_cap below, at and above n_rows: the export keeps the first rows_cap rows of the ranking and pads with zero bytes, and the
+    result — sum_regret is folded over ALL rows in rank order — does not depend on how many rows leave"""
+    bp = DM.Blueprint()
+    want = DM.solve(FLOP_NEXT, 0, bp, 0, 2, rollouts=1, bp_epoch=EPOCH, bias=BIAS, prior=PRIOR, seed=SEED, first_id=FIRST_ID)
+    n_rows = want["n_rows"]
+    assert want["status"] == FM.OK and n_rows > 1
+    table = bp.table()
+    s = NlheSolver(cap_log2=(2 * table[0].size).bit_length() + 1, batch=1, seed=1)
+    s.load(*table, epoch=EPOCH)
+    results = []
+    for rows_cap in (1, n_rows, n_rows + 3):
+        res, rows = s.depth_solve(FLOP_NEXT, 0, 2, 1, BIAS, PRIOR, SEED, FIRST_ID, rows_cap)
+        assert rows.shape == (1, rows_cap)
+        assert_equal(res[0], rows[0], dict(want, rows=want["rows"][:rows_cap]), rows_cap)
+        assert not rows[0][n_rows:].view(np.uint8).any() and rows[0][:n_rows].view(np.uint8).reshape(min(rows_cap, n_rows), -1).any(axis=1).all()
+        results.append(res.tobytes())
+    assert results[0] == results[1] == results[2]

@@ -15,8 +15,9 @@ import nlhe_depth_model as DM
 import nlhe_rollout_model as FM
 import nlhe_subgame_model as SM
 import oracle_nlhe as ON
+from nlhe_solve_common import Table, bits, cards
 from robopoker_amd import _lib
-from robopoker_amd.nlhe import MAX_HOLES, SUBGAME_DEAL_DTYPE, SUBGAME_RESULT_DTYPE, SUBGAME_ROW_DTYPE, Frontier, NlheSolver
+from robopoker_amd.nlhe import MAX_HOLES, ORIGIN_NONE, SUBGAME_DEAL_DTYPE, SUBGAME_RESULT_DTYPE, SUBGAME_ROW_DTYPE, Frontier, NlheSolver
 
 pytestmark = pytest.mark.gpu
 
@@ -25,12 +26,6 @@ DRAW, FOLD, CHECK, CALL = ON.E_DRAW, ON.E_FOLD, ON.E_CHECK, ON.E_CALL
 BIAS, PRIOR, SEED, FIRST_ID, EPOCH, ROWS_CAP, DEALS_CAP = 5.0, 64.0, 0x5EED, 1000, 3, 176, 8
 F = np.float32
 NAN = float("nan")
-
-
-def cards(*cs):
-    return sum(1 << c for c in cs)
-
-
 HOLES, FLOP, TURN, RIVER = (cards(51, 50), cards(12, 25)), cards(3, 17, 30), cards(44), cards(9)
 TO_THE_RIVER = [OPEN2, CALL, DRAW, CHECK, CHECK, DRAW, CHECK, CHECK, DRAW, CHECK, POT]  # seat 1 to answer a river bet
 TO_THE_FLOP = [OPEN2, CALL, DRAW]
@@ -93,10 +88,6 @@ class Model:
 @pytest.fixture(scope="module")
 def model():
     return Model()
-
-
-def bits(x):
-    return np.ascontiguousarray(x, np.float32).view(np.uint32)
 
 
 def entries(cases=CASES):
@@ -194,7 +185,7 @@ def test_device_form_chained_from_the_belief(gpu, model):
     cases = [c for c in CASES if c[0] in ("river, seat 1", "flop", "flop, origin 0", "preflop", "no other hole", "chance")]
     en = NlheSolver.depth_entries(entries(cases))
     recalls = NlheSolver.subgame_recalls(en)
-    og = NlheSolver._subgame_origin(origins(cases), len(cases))
+    og = NlheSolver._origin(origins(cases), len(cases), ORIGIN_NONE)
     bel = s.belief_device(torch.from_numpy(recalls.view(np.uint8).copy()).to("cuda"))
     dev = s.subgame_solve_device(torch.from_numpy(en.view(np.uint8).copy()).to("cuda"), bel["hole_world"], bel["weights"],
                                  torch.from_numpy(og).to("cuda"), 8, 2, BIAS, PRIOR, SEED, FIRST_ID, ROWS_CAP, DEALS_CAP)
@@ -218,18 +209,37 @@ def test_device_form_chained_from_the_belief(gpu, model):
     assert_equal(two[0][i], two[1][i], two[2][i], want, "flop, origin 0, the device's belief")
 
 
-class Table:
-    """the exported blueprint as the model reads it"""
-
-    def __init__(self, past, present, choices, enc):
-        self.rows = {(int(p), int(q), int(c)): enc[i] for i, (p, q, c) in enumerate(zip(past, present, choices))}
-
-    def enc(self, key):
-        return self.rows.get(key)
-
-    def get(self, key):
-        row = self.rows.get(key)
-        return None if row is None else row["weight"]
+def test_a_history_past_the_cap_is_a_status(gpu, model):
+    """the depth test's 47-edge entry between two valid ones, under a belief of rp_nlhe_belief: its tree is built and dealt for, its
+    first frontier lies past RP_NLHE_MAX_HISTORY, so the solve ends with RP_RECALL_LENGTH — a zero result, zero rows, zero deals — and
+    its neighbours answer what the model does"""
+    m = model
+    s = m.solver()
+    # the record carries all three draws: the model deals through the recall's replay, which wants a card for every Draw edge it counts
+    # (up to three), while the entry state itself stays on the flop — a Draw edge met at a choice node changes nothing
+    long_entry = Frontier(HOLES, 0, [FLOP, TURN, RIVER], TO_THE_FLOP + [DRAW] * 44, prefix=[CHECK])
+    flop_next = Frontier(HOLES, 0, [FLOP], TO_THE_FLOP, prefix=[CHECK])
+    batch, rows_cap, deals_cap = [flop_next, long_entry, FLOP_ENTRY], 8, 2
+    assert DM.street(FM.frontier_game(long_entry)) == 1 and len(long_entry.edges) == 47
+    # the belief of the same seat, hole and flop three edges in: the candidate holes of the entry state
+    bel = s.belief(NlheSolver.subgame_recalls([flop_next, flop_next, FLOP_ENTRY]))
+    assert not bel["status"].any()
+    table, keep = Table(*s.export()), []
+    kw = dict(m.kw, rollouts=1)
+    want = [SM.solve(e, bel["hole_world"][i], bel["weights"][i], 0, table, i, 2, keep=keep if e is long_entry else None, **kw)
+            for i, e in enumerate(batch)]
+    # on the model first: the entry itself replays, iteration 0 deals and builds a tree, and a frontier of that tree is what fails
+    failed = keep[0]
+    assert [w["status"] for w in want] == [FM.OK, FM.LENGTH, FM.OK] and failed.profile.t == 0 and len(failed.deals) == 1
+    _, frontiers = failed.build(0)
+    assert frontiers and all(len(long_entry.edges) + len(f.story) > FM.RM.MAX_HISTORY for f in frontiers)
+    assert want[0]["frontiers"] > 0 and want[0]["n_rows"] > rows_cap and want[2]["n_rows"] > rows_cap
+    res, rows, deals = s.subgame_solve(batch, bel, 0, 2, 1, BIAS, PRIOR, SEED, FIRST_ID, rows_cap, deals_cap)
+    for i in range(3):
+        assert_equal(res[i], rows[i], deals[i], dict(want[i], rows=want[i]["rows"][:rows_cap]), i)
+    zero = np.zeros(1, SUBGAME_RESULT_DTYPE)
+    zero["status"] = FM.LENGTH
+    assert res[1].tobytes() == zero.tobytes() and not rows[1].view(np.uint8).any() and not deals[1].view(np.uint8).any()
 
 
 def test_splits_repeats_and_reads_only(gpu, model):
@@ -278,7 +288,7 @@ def test_a_batch_past_one_launch_equals_its_split(gpu, model):
     cases = [c for c in CASES if c[0] in ("river, seat 1", "flop", "flop, origin 0", "preflop", "no other hole", "chance")]
     # the cases cycled so that the second launch's only solve is one with frontiers and rows
     pick = (np.arange(n) - NS_CHUNK + [c[0] for c in cases].index("flop, origin 0")) % len(cases)
-    en, og = NlheSolver.depth_entries(entries(cases))[pick], NlheSolver._subgame_origin(origins(cases), len(cases))[pick]
+    en, og = NlheSolver.depth_entries(entries(cases))[pick], NlheSolver._origin(origins(cases), len(cases), ORIGIN_NONE)[pick]
     bel = s.belief_device(torch.from_numpy(NlheSolver.subgame_recalls(en).view(np.uint8).copy()).to("cuda"))
     en_dev, og_dev = torch.from_numpy(en.view(np.uint8).reshape(n, -1).copy()).to("cuda"), torch.from_numpy(og).to("cuda")
     parts = ((slice(0, n), FIRST_ID), (slice(0, NS_CHUNK), FIRST_ID), (slice(NS_CHUNK, n), FIRST_ID + NS_CHUNK))
