@@ -898,6 +898,95 @@ RP_API int rp_nlhe_subgame_solve_device(rp_nlhe* h, uint64_t n, const rp_nlhe_fr
                                         const rp_nlhe_subgame_args* args /* host */, rp_nlhe_subgame_result* results_dev,
                                         rp_nlhe_subgame_row* rows_dev, rp_nlhe_subgame_deal* deals_dev);
 
+/* AIVAT: blueprint control variates per played hand (Aivat::corrections / action_node_correction / chance_node_correction,
+ * arena/src/aivat.rs:63-229; strategy_ev / observed_ev, arena/src/correction.rs:4-22; the queries eval_policy / eval_abstraction /
+ * eval_chance_correction, arena/src/repository.rs:368-442) — the one consumer of the table's payoff column.  Heads-up.  One hand
+ * is the two holes, the board as dealt, the walker's stacks and dealer, the hero seat and the hand's CHOICE plays in order (no
+ * Blind, no Draw).  Read-only exactly as rp_nlhe_policy: nothing is inserted, epoch / counters / keys are unchanged, no query can
+ * fail a later step.  One wavefront per hand (csrc/nlmc_aivat.hpp).
+ *
+ * TWO GAMES advance together.
+ *   The WALKER (Replayer, arena/src/replay.rs:90-107) is Game::from_start(dealer, stacks) with both holes dealt; the real actions
+ *   are applied to it (try_apply).  The WITNESS game is that of Witness::try_arrange(Choice(seat), arrangement, [])
+ *   (kicker/src/witness.rs:193-213): stacks [STACK; 2] and dealer 0 WHATEVER THE HAND SAYS.  That difference is the reference's and
+ *   is reproduced, not repaired.  The arrangement is the seat's hole plus ALL the board cards the hand carries, so seen().street()
+ *   is the hand's last street from the first node on, and sprout (witness.rs:497-505) deals every pending street into the witness as
+ *   soon as its head is a chance node below that street.  The reference keeps one witness per seat; they differ only in seen(), so
+ *   one witness game serves both.
+ * PER PLAY, in this order:  if the walker is terminal, stop (the remaining plays are ignored: no error).  While the walker is at a
+ *   chance node: street s needs draws[s] (RP_RECALL_DRAW where it is 0); unless s is preflop, take the CHANCE correction; deal
+ *   draws[s] into the walker.  If the walker's turn is `seat`, take the ACTION correction with that seat's hole and ADD it to hero; if
+ *   it is the other seat, take it with the other hole and SUBTRACT it from villain.  Push the play onto the witness game (is_allowed,
+ *   else the hand is refused: RP_AIVAT_WITNESS where the walker would have accepted the play, RP_RECALL_ILLEGAL where it refuses it
+ *   as well), then sprout.  Apply the play to the walker (is_allowed, else RP_RECALL_ILLEGAL).  Streets the walker still has to
+ *   deal when the plays run out (an all-in and a call) are not visited.
+ * THREE AGGRESSION COUNTS, none of them another's:
+ *   history()  (kicker/src/recall.rs:81-100) turns the witness's actions, Draws included, into edges with
+ *              state.edgify(action, running.aggression()), where `running` is a Path of the edges so far: Path keeps its FIRST 12
+ *              edges (MAX_PATH_EDGES), so from the 13th edge of the hand on that depth no longer changes.
+ *   subgame()  (recall.rs:103-112) collects the history's edges since the last Draw into a Path: the FIRST 12 edges of the current
+ *              street.  It is the key's `past`, and its aggression() (the raises / shoves among those 12) is the depth of the key's
+ *              `choices` = witness head.choices(depth) (nlhe/src/info.rs:117-122); no choices where the head is no decision node.
+ *   aggression() (recall.rs:63-70) counts the Raise / Shove ACTIONS since the last Draw, without a cut: the depth the OBSERVED edge is
+ *              snapped with, on the WALKER: edge = walker.edgify(action, aggression()) (kicker/src/game.rs:754-766, 813-818: the grid
+ *              edge of (street, depth) closest in chips on the walker's pot, the first of equally close ones, Shove where the grid is
+ *              empty).
+ * ACTION CORRECTION (aivat.rs:197-229).  present = the bucket of (the seat's hole, board): board_mode 0, the reference, takes EVERY
+ *   board card the hand carries (the witness's seen()) — before the hand's last street that is a bucket of another street than the
+ *   node's, and finds no row; board_mode 1 takes the walker's board at the node, the evaluator one would want.  The infoset
+ *   (past, present, choices) is probed: no row, no slots, or Σ_slots weight <= 0 give None.  Otherwise total = Σ w,
+ *   ev = Σ (w / total) · payoff, observed = payoff[idx] with idx the first slot whose edge is the observed edge, or ev where no slot
+ *   is; the correction is ev - observed.  Slots are the infoset's n_actions; slots past them are never read into a result.
+ * CHANCE CORRECTION (aivat.rs:151-195, repository.rs:397-442), at the walker's flop -> turn and turn -> river nodes.  The deals are
+ *   the single cards outside hero | villain | board, ascending (HandIterator), 45 or 44.  The walker after a deal says who acts: the
+ *   hero seat gives sign +, the other seat sign - and ITS hole as the pocket, anything else None.  past and choices are the witness's
+ *   as above (it has sprouted already: past is empty).  Deal d's bucket is that of (pocket, board | d) on the next street; a bucket
+ *   without a row DROPS the deal (the inner join), baseline = (Σ_slots w · payoff) / (Σ_slots w) is NULL where Σ_slots w == 0.
+ *   avg = (float)((double)(Σ_deals baseline over the non-NULL joined deals) / (double)(number of joined deals, NULL ones included)),
+ *   NULL where no joined deal has a value; obs = the observed deal's baseline; either NULL gives None; the correction is
+ *   sign · (avg - obs).
+ * ARITHMETIC, fixed here where the reference and SQL leave it open: every Σ is an f32 left fold from 0.0f, one rounding per
+ *   operation (include/rp_math.h), Σ_slots in slot order, Σ_deals in deal order; w / total, (w / total) · v, w · v and the baseline's
+ *   quotient are single f32 operations; avg is the one float8 division above, rounded to f32 — this is the definition whatever
+ *   PostgreSQL does with real / bigint.  hero, villain and chance accumulate in f32 in play order; total = (hero + villain) + chance.
+ *   NaN payloads are not part of the contract.
+ * LOOKUP-TABLE ENCODER: an observation the tables do not hold drops that deal at a chance node (as the join does) and is None at an
+ *   action node (as eval_abstraction is); it is never RP_RECALL_LOOKUP here.
+ * STATUS per hand: rp_recall_status's values with their meanings, plus RP_AIVAT_WITNESS.  Checked before the replay, in this order:
+ *   n_plays above RP_AIVAT_MAX_PLAYS LENGTH; seat > 1, dealer > 1, board_mode > 1, stacks neither 0,0 (= STACK) nor both positive
+ *   SEAT; a hole that is not two cards, holes or draws that overlap, draws with wrong popcounts or out of street order CARDS; a kind
+ *   that is no rp_aivat_play EDGE.  Then the first refusal of the replay in the order above.  A refused hand yields zero outputs and
+ *   its status; the call is still RP_OK and the other hands are answered.  No input causes an out-of-bounds access.
+ * Outputs: hero, villain, chance, total [n] f32; n_action, n_chance [n] u8, the nodes that contributed a correction that is not
+ *   None; status [n]; n_action, n_chance and status may be NULL.  adjusted = won + total is the caller's (aivat.rs:33-42).
+ *   The _device form takes every pointer in DEVICE memory, queues its launches on the handle's stream and returns, ordered exactly
+ *   like rp_nlhe_policy_device; the host form stages, launches and synchronises.  n = 0 is RP_OK without a launch. */
+#define RP_AIVAT_MAX_PLAYS 48u
+typedef enum { RP_PLAY_FOLD = 1, RP_PLAY_CALL = 2, RP_PLAY_CHECK = 3, RP_PLAY_RAISE = 4, RP_PLAY_SHOVE = 5 } rp_aivat_play; /* action.rs:8-16 */
+enum { RP_AIVAT_WITNESS = 11 }; /* the default-stack witness game refuses a play the walker accepts; after RP_DEPTH_FRONTIERS */
+typedef struct rp_aivat_hand {
+    uint64_t hole[2];      /* seat 0, seat 1 */
+    uint64_t draws[3];     /* flop / turn / river as dealt; 0 where not dealt */
+    int16_t  stacks[2];    /* the walker's starting stacks, both positive (0,0 = STACK) */
+    int16_t  chips[RP_AIVAT_MAX_PLAYS]; /* Call / Raise / Shove: the chips the play adds; ignored for Fold / Check */
+    uint8_t  kind[RP_AIVAT_MAX_PLAYS];  /* rp_aivat_play; the choice plays only: no Blind, no Draw */
+    uint8_t  seat, dealer, n_plays, board_mode;
+} rp_aivat_hand;           /* 192 bytes */
+RP_API int rp_nlhe_aivat(rp_nlhe* h, uint64_t n, const rp_aivat_hand* hands, float* hero, float* villain, float* chance, float* total,
+                         uint8_t* n_action, uint8_t* n_chance, uint8_t* status);
+RP_API int rp_nlhe_aivat_device(rp_nlhe* h, uint64_t n, const rp_aivat_hand* hands_dev, float* hero_dev, float* villain_dev,
+                                float* chance_dev, float* total_dev, uint8_t* n_action_dev, uint8_t* n_chance_dev, uint8_t* status_dev);
+/* Aivat::summarize (aivat.rs:45-61) with ratio and erf of pokerkit/src/metrics.rs:102-119.  Host only, no handle, no device.
+ *   n_f = (float)n; won = Σ adjusted; mean = ratio(won, n_f); variance = ratio(Σ (x - mean)(x - mean), n_f);
+ *   stderr = ratio(sqrt(variance), sqrt(n_f)); raw = raw_stddev · raw_stddev; adj = (stderr · stderr) · n_f;
+ *   reduction = adj > 0 ? raw / adj : 1; pvalue = stderr > 0 ? 2 · erf(-|mean| / stderr) : 1; ratio(a, b) = b > 0 ? a / b : 0.
+ *   f32 left folds from 0.0f, every operation rounded on its own, sqrt correctly rounded, erf's exp through rp_glibc_expf
+ *   (include/rp_libm_glibc.h).  n = 0 is RP_OK (all ratios 0, reduction 1, pvalue 1); adjusted may then be NULL. */
+typedef struct rp_aivat_summary {
+    float won, mean, stderr_, reduction, pvalue;
+} rp_aivat_summary;
+RP_API int rp_aivat_summarize(uint64_t n, const float* adjusted, float raw_stddev, rp_aivat_summary* out);
+
 /* Multi-GPU (BASELINE configs[3]): trees sharded by rank (rank r samples tree ids [r*B, (r+1)*B) of a world*B-tree epoch
  * against a replicated table).  step_local: this rank's traversal reduced to one composed entry per infoset touched
  * (rp_profile_summarize's records, entry_bytes each, at most max_entries) plus the infoset KEY of every entry — each

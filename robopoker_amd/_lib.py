@@ -47,6 +47,9 @@ RP_NLHE_DEPTH_ORIGIN_ENTRY = 127
 RP_DEPTH_NODES, RP_DEPTH_ROWS, RP_DEPTH_FRONTIERS = 8, 9, 10
 RP_NLHE_SUBGAME_MAX_ROWS = 2048
 RP_NLHE_SUBGAME_ORIGIN_NONE = 126
+RP_AIVAT_MAX_PLAYS = 48
+RP_AIVAT_WITNESS = 11
+PLAY = {"fold": 1, "call": 2, "check": 3, "raise": 4, "shove": 5}  # rp_aivat_play
 
 
 class Hyper(C.Structure):
@@ -70,6 +73,17 @@ class NlheRecall(C.Structure):
     """rp_nlhe_recall: what one seat has seen, at edge level (88 bytes)"""
     _fields_ = [("hole", C.c_uint64), ("draws", C.c_uint64 * 3), ("stacks", C.c_int16 * 2), ("pov", C.c_uint8), ("dealer", C.c_uint8),
                 ("n_edges", C.c_uint8), ("reserved", C.c_uint8), ("edges", C.c_uint8 * 48)]
+
+
+class AivatHand(C.Structure):
+    """rp_aivat_hand: one played heads-up hand, action level (192 bytes)"""
+    _fields_ = [("hole", C.c_uint64 * 2), ("draws", C.c_uint64 * 3), ("stacks", C.c_int16 * 2), ("chips", C.c_int16 * 48),
+                ("kind", C.c_uint8 * 48), ("seat", C.c_uint8), ("dealer", C.c_uint8), ("n_plays", C.c_uint8), ("board_mode", C.c_uint8)]
+
+
+class AivatSummary(C.Structure):
+    """rp_aivat_summary: Aivat::summarize's figures"""
+    _fields_ = [("won", C.c_float), ("mean", C.c_float), ("stderr", C.c_float), ("reduction", C.c_float), ("pvalue", C.c_float)]
 
 
 class NlheFrontier(C.Structure):
@@ -380,6 +394,9 @@ _SIGNATURES = {
     "rp_nlhe_subgame_args_default": (None, [C.POINTER(NlheSubgameArgs)]),
     "rp_nlhe_subgame_solve": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4 + [C.POINTER(NlheSubgameArgs)] + [C.c_void_p] * 3),
     "rp_nlhe_subgame_solve_device": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4 + [C.POINTER(NlheSubgameArgs)] + [C.c_void_p] * 3),
+    "rp_nlhe_aivat": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 8),
+    "rp_nlhe_aivat_device": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 8),
+    "rp_aivat_summarize": (C.c_int, [C.c_uint64, C.c_void_p, C.c_float, C.POINTER(AivatSummary)]),
     "rp_nlhe_partition": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
     "rp_nlhe_partition_device": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
     "rp_nlhe_belief": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5),

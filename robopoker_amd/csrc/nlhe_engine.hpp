@@ -234,6 +234,26 @@ __device__ int nl_edge_chips(uint32_t e, int pot) {  // Edge::into_chips
     }
     return 0;
 }
+// GameN::edgify (game.rs:754-766) with snap_to_edge (:813-818): a Raise becomes the grid edge of (street, depth) whose chips are
+// closest to the action's — min_by_key keeps the FIRST of equally close edges — and Shove where that cell of the grid is empty
+template <class G>
+__device__ uint32_t nl_edgify(const G& g, const NlAction& a, int depth) {
+    switch (a.kind) {
+        case NA_FOLD: return NE_FOLD;
+        case NA_CHECK: return NE_CHECK;
+        case NA_DRAW: return NE_DRAW;
+        case NA_CALL: case NA_BLIND: return NE_CALL;
+        case NA_SHOVE: return NE_SHOVE;
+    }
+    uint32_t grid[6], best = NE_SHOVE;
+    const int n = nl_raise_edges(g.street(), depth, grid);
+    int best_gap = 0x7fffffff;
+    for (int i = 0; i < n; ++i) {
+        const int gap = abs(nl_edge_chips(grid[i], g.pot) - a.chips);
+        if (gap < best_gap) best = grid[i], best_gap = gap;
+    }
+    return best;
+}
 // GameN::choices (game.rs:724-739): legal()'s order — raise grid, shove, call, fold, check
 template <class G>
 __device__ int nl_choices(const G& g, int depth, uint32_t* out) {

@@ -38,6 +38,8 @@
 #include "nlmc_range.hpp"
 #include "nlmc_world.hpp"
 #include "nlmc_subgame.hpp"
+#include "nlmc_aivat.hpp"
+#include "../../include/rp_libm_glibc.h"
 #include "rp_internal.h"
 #include "sortscan.hpp"
 
@@ -1499,6 +1501,72 @@ int rp_nlhe_subgame_solve(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* entrie
     s.out(results, n).out(rows, n * args->rows_cap).out(deals, n * args->deals_cap);
     if ((rc = s.up()) || (rc = rp_nlhe_subgame_solve_device(h, n, entries, hole_world, weights, origin, args, results, rows, deals))) return rc;
     return s.down();
+}
+
+}  // extern "C"
+
+// ---- AIVAT (nlmc_aivat.hpp): one wavefront per hand, at most NR_CHUNK hands per launch
+namespace {
+int na_check(const rp_nlhe* h, uint64_t n, const void* hands, const void* hero, const void* villain, const void* chance, const void* total) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_aivat: NULL handle");
+    if (n == 0) return RP_OK;
+    if (!hands || !hero || !villain || !chance || !total)
+        return rp::fail(RP_ERR_INVALID, "rp_nlhe_aivat: NULL hands, hero, villain, chance or total with n > 0");
+    return RP_OK;
+}
+// ratio and erf of pokerkit/src/metrics.rs:102-119
+float na_ratio(float num, float den) { return den > 0.0f ? num / den : 0.0f; }
+float na_erf(float x) {
+    const float A = 0.2316419f, B = 0.3989423f, C = 0.3193815f, D = -0.3565638f, E = 1.781478f, F = -1.821256f, G = 1.330274f;
+    const float t = 1.0f / (1.0f + A * fabsf(x));
+    const float d = B * rp_glibc_expf(-x * x / 2.0f);
+    const float p = d * t * (C + t * (D + t * (E + t * (F + t * G))));
+    return x > 0.0f ? 1.0f - p : p;
+}
+}  // namespace
+
+extern "C" {
+
+int rp_nlhe_aivat_device(rp_nlhe* h, uint64_t n, const rp_aivat_hand* hands, float* hero, float* villain, float* chance, float* total,
+                         uint8_t* n_action, uint8_t* n_chance, uint8_t* status) {
+    int rc = na_check(h, n, hands, hero, villain, chance, total);
+    if (rc || n == 0) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    return nl_chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
+        const NaArgs q{hands + at, hero + at, villain + at, chance + at, total + at, nl_at(n_action, at), nl_at(n_chance, at), nl_at(status, at)};
+        hipLaunchKernelGGL(k_nl_aivat, dim3(m), dim3(NA_BLOCK), 0, st, h->tab, h->prm, q);
+    });
+}
+
+int rp_nlhe_aivat(rp_nlhe* h, uint64_t n, const rp_aivat_hand* hands, float* hero, float* villain, float* chance, float* total, uint8_t* n_action,
+                  uint8_t* n_chance, uint8_t* status) {
+    int rc = na_check(h, n, hands, hero, villain, chance, total);
+    if (rc || n == 0) return rc;
+    Stage s(h);
+    s.in(hands, n).out(hero, n).out(villain, n).out(chance, n).out(total, n).out(n_action, n).out(n_chance, n).out(status, n);
+    if ((rc = s.up()) || (rc = rp_nlhe_aivat_device(h, n, hands, hero, villain, chance, total, n_action, n_chance, status))) return rc;
+    return s.down();
+}
+
+int rp_aivat_summarize(uint64_t n, const float* adjusted, float raw_stddev, rp_aivat_summary* out) {
+    if (!out) return rp::fail(RP_ERR_INVALID, "rp_aivat_summarize: NULL out");
+    if (n > 0 && !adjusted) return rp::fail(RP_ERR_INVALID, "rp_aivat_summarize: NULL adjusted with n > 0");
+    const float nf = (float)n;
+    float won = 0.0f;
+    for (uint64_t i = 0; i < n; ++i) won = won + adjusted[i];
+    const float mean = na_ratio(won, nf);
+    float squares = 0.0f;
+    for (uint64_t i = 0; i < n; ++i) squares = squares + (adjusted[i] - mean) * (adjusted[i] - mean);
+    const float variance = na_ratio(squares, nf);
+    const float stderr_ = na_ratio(sqrtf(variance), sqrtf(nf));
+    const float raw = raw_stddev * raw_stddev, adj = stderr_ * stderr_ * nf;
+    out->won = won;
+    out->mean = mean;
+    out->stderr_ = stderr_;
+    out->reduction = adj > 0.0f ? raw / adj : 1.0f;
+    out->pvalue = stderr_ > 0.0f ? 2.0f * na_erf(-fabsf(mean) / stderr_) : 1.0f;
+    return RP_OK;
 }
 
 }  // extern "C"

@@ -59,23 +59,43 @@ __device__ __forceinline__ bool nlq_find(const NlTable& t, uint64_t past, uint64
     return false;
 }
 
-// The nine weights of an infoset's row, and whether it has one.  The home slot and the home row's weights are loaded together, the
-// row again only when the key was found further down its probe chain.  w is the row's bytes as stored (slots past the infoset's
-// actions included); an absent infoset leaves the home row's in it: read `found` first.
-__device__ __forceinline__ bool nlq_row_weights(const NlTable& t, uint64_t past, uint64_t choices, uint32_t present, float* w) {
+// 16-byte pieces FIRST .. FIRST + N of an infoset's row (a row is 9 pieces: regret[9] weight[9] payoff[9] visits[9]), and whether
+// it has one.  The home slot and the home row's pieces are loaded together, the row again only when the key was found further down
+// its probe chain.  pc is the row's bytes as stored (slots past the infoset's actions included); an absent infoset leaves the home
+// row's in it: read `found` first.
+template <uint32_t FIRST, uint32_t N>
+__device__ __forceinline__ bool nlq_row_pieces(const NlTable& t, uint64_t past, uint64_t choices, uint32_t present, float4* pc) {
+    static_assert(FIRST + N <= NLMC_A, "a row is 4 x 9 floats = 9 pieces");
     const uint32_t home = (uint32_t)nl_key_hash(past, choices, present) & t.mask;
     const uint4* sl = reinterpret_cast<const uint4*>(t.slots + home);
     const uint4 lo = sl[0], hi = sl[1];
-    // the weights are floats 9..17 of the row: pieces 2..4 hold floats 8..19
     const float4* rw = reinterpret_cast<const float4*>(t.rows + (size_t)home * 4u * NLMC_A);
-    float4 p0 = rw[2], p1 = rw[3], p2 = rw[4];
+#pragma unroll
+    for (uint32_t i = 0; i < N; ++i) pc[i] = rw[FIRST + i];
     uint32_t row;
     const bool found = nlq_find(t, past, choices, present, home, lo, hi, &row);
     if (found && row != home) {
         const float4* rr = reinterpret_cast<const float4*>(t.rows + (size_t)row * 4u * NLMC_A);
-        p0 = rr[2], p1 = rr[3], p2 = rr[4];
+#pragma unroll
+        for (uint32_t i = 0; i < N; ++i) pc[i] = rr[FIRST + i];
     }
-    w[0] = p0.y, w[1] = p0.z, w[2] = p0.w, w[3] = p1.x, w[4] = p1.y, w[5] = p1.z, w[6] = p1.w, w[7] = p2.x, w[8] = p2.y;
+    return found;
+}
+// The nine weights of an infoset's row: floats 9..17, pieces 2..4 hold floats 8..19
+__device__ __forceinline__ bool nlq_row_weights(const NlTable& t, uint64_t past, uint64_t choices, uint32_t present, float* w) {
+    float4 p[3];
+    const bool found = nlq_row_pieces<2, 3>(t, past, choices, present, p);
+    w[0] = p[0].y, w[1] = p[0].z, w[2] = p[0].w, w[3] = p[1].x, w[4] = p[1].y, w[5] = p[1].z, w[6] = p[1].w, w[7] = p[2].x, w[8] = p[2].y;
+    return found;
+}
+// The nine weights and the nine payoffs: floats 9..17 and 18..26, pieces 2..6 hold floats 8..27
+__device__ __forceinline__ bool nlq_row_weights_payoffs(const NlTable& t, uint64_t past, uint64_t choices, uint32_t present, float* w, float* v) {
+    float4 p[5];
+    const bool found = nlq_row_pieces<2, 5>(t, past, choices, present, p);
+    const float f[20] = {p[0].x, p[0].y, p[0].z, p[0].w, p[1].x, p[1].y, p[1].z, p[1].w, p[2].x, p[2].y,
+                         p[2].z, p[2].w, p[3].x, p[3].y, p[3].z, p[3].w, p[4].x, p[4].y, p[4].z, p[4].w};
+#pragma unroll
+    for (uint32_t a = 0; a < NLMC_A; ++a) w[a] = f[1u + a], v[a] = f[10u + a];
     return found;
 }
 

@@ -17,6 +17,10 @@ MAX_HISTORY, MAX_HOLES, BUCKETS = _lib.RP_NLHE_MAX_HISTORY, _lib.RP_NLHE_MAX_HOL
 RECALL_DTYPE = np.dtype([("hole", "<u8"), ("draws", "<u8", (3,)), ("stacks", "<i2", (2,)), ("pov", "u1"), ("dealer", "u1"),
                          ("n_edges", "u1"), ("reserved", "u1"), ("edges", "u1", (MAX_HISTORY,))])  # rp_nlhe_recall, 88 bytes
 assert RECALL_DTYPE.itemsize == C.sizeof(_lib.NlheRecall) == 88
+MAX_PLAYS = _lib.RP_AIVAT_MAX_PLAYS
+AIVAT_DTYPE = np.dtype([("hole", "<u8", (2,)), ("draws", "<u8", (3,)), ("stacks", "<i2", (2,)), ("chips", "<i2", (MAX_PLAYS,)),
+                        ("kind", "u1", (MAX_PLAYS,)), ("seat", "u1"), ("dealer", "u1"), ("n_plays", "u1"), ("board_mode", "u1")])  # rp_aivat_hand
+assert AIVAT_DTYPE.itemsize == C.sizeof(_lib.AivatHand) == 192
 LEAVES, MAX_PREFIX, MAX_ROLLOUTS = _lib.RP_NLHE_FRONTIER_LEAVES, _lib.RP_NLHE_MAX_PREFIX, 4096
 FRONTIER_DTYPE = np.dtype([("holes", "<u8", (2,)), ("draws", "<u8", (3,)), ("stacks", "<i2", (2,)), ("internal", "u1"), ("dealer", "u1"),
                            ("n_edges", "u1"), ("n_prefix", "u1"), ("edges", "u1", (MAX_HISTORY,)), ("prefix", "u1", (MAX_PREFIX,)),
@@ -81,6 +85,37 @@ class Recall:
             out[i]["pov"], out[i]["dealer"], out[i]["n_edges"] = r.pov, r.dealer, min(len(r.edges), 255)
             k = min(len(r.edges), MAX_HISTORY)
             out[i]["edges"][:k] = r.edges[:k]
+        return out
+
+
+class AivatHand:
+    """One played heads-up hand at ACTION level, as the AIVAT evaluator takes it (crates/arena/src/aivat.rs:63-93): ``holes`` the
+    two-card masks of seat 0 and seat 1; ``draws`` up to three masks (flop, turn, river) as dealt; ``plays`` the hand's choice plays
+    in order, each (kind, chips) with kind "fold" / "check" / "call" / "raise" / "shove" (or its rp_aivat_play code) and chips the
+    amount the play adds (ignored for fold and check); ``seat`` the hero; ``stacks`` / ``dealer`` the real hand's ((0, 0) = STACK);
+    ``board_mode`` 0: the reference's bucket at an action node (every board card the hand carries), 1: the board at the node.
+    Nothing is checked here: a malformed hand is answered with its status."""
+
+    def __init__(self, holes, draws=(), plays=(), seat=0, stacks=(0, 0), dealer=0, board_mode=0):
+        self.holes, self.draws, self.plays = tuple(holes), tuple(draws), tuple(plays)
+        self.seat, self.stacks, self.dealer, self.board_mode = seat, tuple(stacks), dealer, board_mode
+
+    @staticmethod
+    def pack(hands) -> np.ndarray:
+        """-> AIVAT_DTYPE[n]; plays past the cap keep their first 48 and their true number clipped to 255 (status LENGTH)"""
+        if isinstance(hands, np.ndarray) and hands.dtype == AIVAT_DTYPE:
+            return np.ascontiguousarray(hands)
+        if isinstance(hands, AivatHand):
+            hands = [hands]
+        out = np.zeros(len(hands), AIVAT_DTYPE)
+        for i, h in enumerate(hands):
+            out[i]["hole"] = h.holes
+            out[i]["draws"][: len(h.draws)] = h.draws
+            out[i]["stacks"] = h.stacks
+            out[i]["seat"], out[i]["dealer"], out[i]["board_mode"], out[i]["n_plays"] = h.seat, h.dealer, h.board_mode, min(len(h.plays), 255)
+            for j, (kind, chips) in enumerate(h.plays[:MAX_PLAYS]):
+                out[i]["kind"][j] = _lib.PLAY[kind] if isinstance(kind, str) else kind
+                out[i]["chips"][j] = chips
         return out
 
 
@@ -380,6 +415,37 @@ class NlheSolver:
         seen, status = torch.empty((n, BUCKETS), dtype=torch.uint8, device=d), torch.empty(n, dtype=torch.uint8, device=d)
         self._queue(self._lib.rp_nlhe_opponent_range_device, d, n, (rec,), n, rec, mass, seen, status)
         return mass, seen, status
+
+    # ---- AIVAT (include/rp_mi355x.h rp_nlhe_aivat): the blueprint's control variates of played hands ----
+    def aivat(self, hands):
+        """``Aivat::corrections`` (crates/arena/src/aivat.rs:63-145) for n hands: dict(hero, villain, chance, total float32[n],
+        n_action, n_chance, status uint8[n]); ``won + total`` is the hand's adjusted value.  Read-only."""
+        hd = AivatHand.pack(hands)
+        n = hd.size
+        out = {k: np.zeros(n, np.float32) for k in ("hero", "villain", "chance", "total")}
+        out.update({k: np.zeros(n, np.uint8) for k in ("n_action", "n_chance", "status")})
+        _lib.check(self._lib.rp_nlhe_aivat(self._h, n, _p(hd), *[_p(out[k]) for k in ("hero", "villain", "chance", "total", "n_action",
+                                                                                    "n_chance", "status")]))
+        return out
+
+    def aivat_device(self, hands_dev):
+        """rp_nlhe_aivat_device: ``hands_dev`` a device uint8 tensor [n, 192] (``torch.from_numpy(AivatHand.pack(..).view(np.uint8))``);
+        -> the same dict of device tensors, queued on the solver's stream (``sync()`` waits)"""
+        hd, n, d = _records(hands_dev, AIVAT_DTYPE)
+        out = {k: torch.empty(n, dtype=torch.float32, device=d) for k in ("hero", "villain", "chance", "total")}
+        out.update({k: torch.empty(n, dtype=torch.uint8, device=d) for k in ("n_action", "n_chance", "status")})
+        self._queue(self._lib.rp_nlhe_aivat_device, d, n, (hd,), n, hd, *[out[k] for k in ("hero", "villain", "chance", "total", "n_action",
+                                                                                          "n_chance", "status")])
+        return out
+
+    @staticmethod
+    def aivat_summarize(adjusted, raw_stddev):
+        """``Aivat::summarize`` (aivat.rs:45-61) over the adjusted values of a match: dict(won, mean, stderr, reduction, pvalue) as
+        float32; ``raw_stddev``: the standard deviation of the raw winnings.  Host arithmetic, no device."""
+        x = np.ascontiguousarray(adjusted, np.float32).ravel()
+        s = _lib.AivatSummary()
+        _lib.check(_lib.load().rp_aivat_summarize(x.size, _p(x), float(raw_stddev), C.byref(s)))
+        return {k: np.float32(getattr(s, k)) for k in ("won", "mean", "stderr", "reduction", "pvalue")}
 
     # ---- frontier payoffs (include/rp_mi355x.h rp_nlhe_frontier_payoffs): biased continuation rollouts from depth-limited leaves ----
     def frontier_payoffs(self, frontiers, bias=5.0, rollouts=16, seed=0, first_id=0, return_won=False):
