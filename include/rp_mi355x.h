@@ -123,7 +123,9 @@ typedef struct rp_encounter {
 #define RP_NO_INFO 0xffffffffu
 typedef struct rp_state {
     uint8_t turn;       /* acting player 0..n_players-1, RP_TURN_CHANCE or RP_TURN_TERMINAL */
-    uint8_t n_children; /* branching factor (0 for terminals)                                */
+    uint8_t n_children; /* branching factor (0 for terminals), at most 16 (RP_MAX_ACTIONS) at player AND chance states: the
+                           traversals keep the taken edge in 4 bits.  A wider deal is split into two chance levels, as the
+                           built-in games deal their two private cards; rp_game_table_check answers RP_ERR_CAPACITY otherwise */
     uint16_t chance_info; /* chance states, reference-seed mode only: 1 + index of the node's info among rp_hash_streams.chance;
                              0 = this chance state has no counterpart in the reference's trees (the root deal, which the
                              reference takes from the thread RNG, kuhn/src/game.rs:115-123) and keeps the counter hash.
@@ -142,8 +144,9 @@ typedef struct rp_game_table {
     uint32_t n_terminals;  /* rows of payoffs[]                                     */
     uint32_t train_root;   /* CfrGame::root(): chance over deals -> first decision  */
     uint32_t exploit_root; /* CfrGame::exploitability_root()                        */
-    uint32_t max_depth;    /* longest root->leaf path (states)                      */
-    uint32_t max_tree_nodes; /* bound on nodes of one externally-sampled tree       */
+    uint32_t max_depth;    /* longest root->leaf path (states) from either root; may be overstated, never understated */
+    uint32_t max_tree_nodes; /* bound on nodes of one externally-sampled tree from train_root (walker states keep every
+                                child, all others one; maximum over the walkers); may be overstated, never understated */
     const rp_state* states;
     const uint32_t* children;
     const float* payoffs;          /* [n_terminals][n_players]                       */
@@ -164,7 +167,12 @@ RP_API int rp_game_destroy(rp_game* g);
  * or "Q|K|XRC|R" (Leduc: rank|board|round1|round2). Returns RP_ERR_INVALID when unknown. */
 RP_API int rp_game_info_id(const rp_game* g, const char* name, uint32_t* out);
 RP_API int rp_game_info_name(const rp_game* g, uint32_t info, char* buf, size_t cap);
-/* structural validation of a caller-built table (tree shape, offsets, perfect recall of ids) */
+/* Validation of a caller-built table, on the host; rp_mccfr_create runs it first.  RP_ERR_INVALID: NULL fields, n_players
+ * outside 1..8, max_actions outside 1..16, roots or offsets out of range, a child that does not follow its parent in states[],
+ * a player state whose infoset is out of range or disagrees with it in acting player or action count, max_depth or
+ * max_tree_nodes below what the table itself yields.  RP_ERR_CAPACITY: a state with more than 16 children (well formed, but
+ * the kernels cannot hold it).  NOT checked: perfect recall — that an infoset never occurs twice on one root-to-leaf path is
+ * the caller's to guarantee. */
 RP_API int rp_game_table_check(const rp_game_table* t);
 
 typedef struct rp_mccfr rp_mccfr;

@@ -465,6 +465,9 @@ static void apply_decision(ora_mccfr* h, const ora_decision* d) {
 ORA_API ora_mccfr* ora_mccfr_create(const rp_game_table* g, int R, int W, int S, uint32_t batch,
                                     const rp_hyper* hp, uint64_t seed) {
     if (!g || g->max_actions > ORA_MAXA) return NULL;
+    /* ora_node.kids[] has ORA_MAXA slots, for chance states too (rp_state.n_children, include/rp_mi355x.h) */
+    for (uint32_t s = 0; s < g->n_states; ++s)
+        if (g->states[s].n_children > ORA_MAXA) return NULL;
     ora_mccfr* h = (ora_mccfr*)calloc(1, sizeof(ora_mccfr));
     h->g = *g;
     h->states = (rp_state*)malloc(sizeof(rp_state) * g->n_states);

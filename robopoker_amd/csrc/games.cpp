@@ -12,7 +12,6 @@
 #include "rp_internal.h"
 
 #include <algorithm>
-#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -306,28 +305,41 @@ struct rp_game {
 
 namespace rp {
 
-// longest path and the largest externally-sampled tree (walker nodes expand all children,
-// other nodes exactly one), used to size per-tree scratch on the device
-static void tree_bounds(const rp_game_table& t, uint32_t root, uint32_t* depth, uint32_t* nodes) {
-    std::function<uint32_t(uint32_t)> dep = [&](uint32_t s) -> uint32_t {
-        const rp_state& st = t.states[s];
-        uint32_t d = 0;
-        for (uint32_t k = 0; k < st.n_children; ++k) d = std::max(d, dep(t.children[st.offset + k]));
-        return d + 1;
-    };
-    std::function<uint32_t(uint32_t, uint32_t)> cnt = [&](uint32_t s, uint32_t walker) -> uint32_t {
-        const rp_state& st = t.states[s];
-        uint32_t acc = 0;
-        for (uint32_t k = 0; k < st.n_children; ++k) {
-            uint32_t c = cnt(t.children[st.offset + k], walker);
-            acc = (st.turn == walker) ? acc + c : std::max(acc, c);
+// longest path and the largest externally-sampled tree (walker nodes expand all children, other nodes exactly one): sizes the
+// per-tree scratch on the device and decides which traversal kernel a game gets.  Children lie behind their parents, so one
+// backward sweep over the states from the last to `root` has every child's figures before its parent's.
+TableBounds table_bounds(const rp_game_table& t, uint32_t root) {
+    TableBounds best{};
+    const uint32_t n = t.n_states - root;
+    std::vector<uint32_t> dep(n), cnt(n), dec(n), stk(n), ins(n);
+    const auto sat = [](uint64_t v) { return (uint32_t)std::min<uint64_t>(v, 0xffffffffu); };
+    for (uint32_t w = 0; w < t.n_players; ++w) {
+        for (uint32_t s = t.n_states; s-- > root;) {
+            const rp_state& st = t.states[s];
+            const bool walker = st.turn == w;
+            uint64_t d = 0, c = 0, e = 0, i = 0, deepest = 0;
+            for (uint32_t k = 0; k < st.n_children; ++k) {
+                const uint32_t ch = t.children[st.offset + k] - root;
+                d = std::max<uint64_t>(d, dep[ch]);
+                c = walker ? c + cnt[ch] : std::max<uint64_t>(c, cnt[ch]);
+                e = walker ? e + dec[ch] : std::max<uint64_t>(e, dec[ch]);
+                i = walker ? i + ins[ch] : std::max<uint64_t>(i, ins[ch]);
+                deepest = std::max<uint64_t>(deepest, stk[ch]);
+            }
+            const uint32_t at = s - root;
+            dep[at] = sat(d + 1);
+            cnt[at] = sat(c + 1);
+            dec[at] = sat(e + (walker && st.n_children ? 1u : 0u));
+            ins[at] = st.n_children ? sat(i + 1) : 0u;
+            stk[at] = st.n_children ? sat((walker ? st.n_children : 1u) - 1u + std::max<uint64_t>(deepest, 1u)) : 0u;
         }
-        return acc + 1;
-    };
-    *depth = dep(root);
-    uint32_t n = 0;
-    for (uint32_t w = 0; w < t.n_players; ++w) n = std::max(n, cnt(root, w));
-    *nodes = n;
+        best.depth = dep[0];
+        best.nodes = std::max(best.nodes, cnt[0]);
+        best.decisions = std::max(best.decisions, dec[0]);
+        best.stack = std::max(best.stack, stk[0]);
+        best.internal = std::max(best.internal, ins[0]);
+    }
+    return best;
 }
 
 void finalize_view(rp_game* g, uint32_t train_root, uint32_t exploit_root) {
@@ -349,11 +361,9 @@ void finalize_view(rp_game* g, uint32_t train_root, uint32_t exploit_root) {
     v.info_actions = b.info_actions.data();
     v.info_player = b.info_player.data();
     v.default_regret = nullptr;
-    uint32_t d1, n1, d2, n2;
-    tree_bounds(v, train_root, &d1, &n1);
-    tree_bounds(v, exploit_root, &d2, &n2);
-    v.max_depth = std::max(d1, d2);
-    v.max_tree_nodes = n1;
+    const TableBounds train = table_bounds(v, train_root);
+    v.max_depth = std::max(train.depth, table_bounds(v, exploit_root).depth);
+    v.max_tree_nodes = train.nodes;
 }
 
 }  // namespace rp
@@ -446,6 +456,10 @@ int rp_game_table_check(const rp_game_table* t) {
         }
         if (st.n_children == 0 || (uint64_t)st.offset + st.n_children > t->n_children)
             return rp::fail(RP_ERR_INVALID, "table: bad child range");
+        // chance states too: the traversals keep the taken edge in 4 bits and draw into a 32-bit mask of expanded edges
+        if (st.n_children > RP_MAX_ACTIONS)
+            return rp::fail(RP_ERR_CAPACITY, "table: state %u has %u children, the limit is %u (split a wider deal into two chance levels)",
+                            s, (unsigned)st.n_children, RP_MAX_ACTIONS);
         for (uint32_t k = 0; k < st.n_children; ++k) {
             uint32_t c = t->children[st.offset + k];
             if (c >= t->n_states || c <= s) return rp::fail(RP_ERR_INVALID, "table: children must follow parents");
@@ -456,6 +470,15 @@ int rp_game_table_check(const rp_game_table* t) {
         if (t->info_actions[st.info] != st.n_children || t->info_player[st.info] != st.turn)
             return rp::fail(RP_ERR_INVALID, "table: infoset shape mismatch");
     }
+    // the declared bounds size the per-tree scratch and choose the traversal kernel: an understated one is refused here, not
+    // found on the device after a step.  Overstating is legal (it only costs scratch).
+    const rp::TableBounds train = rp::table_bounds(*t, t->train_root);
+    const uint32_t depth = std::max(train.depth, rp::table_bounds(*t, t->exploit_root).depth);
+    if (t->max_depth < depth)
+        return rp::fail(RP_ERR_INVALID, "table: max_depth %u is below the longest root-to-leaf path (%u states)", t->max_depth, depth);
+    if (t->max_tree_nodes < train.nodes)
+        return rp::fail(RP_ERR_INVALID, "table: max_tree_nodes %u is below the largest externally sampled tree (%u nodes)",
+                        t->max_tree_nodes, train.nodes);
     return RP_OK;
 }
 

@@ -126,45 +126,10 @@ size_t summary_bytes_of(const rp_mccfr* h) {
 
 // largest number of walker nodes / stack entries an externally sampled tree can have
 void sampled_tree_bounds(const rp_mccfr* h, uint32_t* maxdec, uint32_t* maxstack, uint32_t* maxint) {
-    const rp_game_table& t = h->tbl;
-    uint32_t best_dec = 1, best_stack = 1, best_int = 1;
-    for (uint32_t w = 0; w < t.n_players; ++w) {
-        std::function<uint32_t(uint32_t)> wn = [&](uint32_t s) -> uint32_t {
-            const rp_state& st = h->states[s];
-            uint32_t acc = 0;
-            for (uint32_t k = 0; k < st.n_children; ++k) {
-                uint32_t c = wn(h->children[st.offset + k]);
-                acc = st.turn == w ? acc + c : std::max(acc, c);
-            }
-            return acc + (st.turn == w && st.n_children ? 1u : 0u);
-        };
-        // pending leaves: at a walker node all children are pushed, one is popped and explored first
-        std::function<uint32_t(uint32_t)> stk = [&](uint32_t s) -> uint32_t {
-            const rp_state& st = h->states[s];
-            if (!st.n_children) return 0;
-            uint32_t deepest = 0;
-            for (uint32_t k = 0; k < st.n_children; ++k) deepest = std::max(deepest, stk(h->children[st.offset + k]));
-            uint32_t pushed = st.turn == w ? st.n_children : 1u;
-            return pushed - 1 + std::max(deepest, 1u);
-        };
-        // internal (expanded) nodes of a sampled tree
-        std::function<uint32_t(uint32_t)> ins = [&](uint32_t s) -> uint32_t {
-            const rp_state& st = h->states[s];
-            if (!st.n_children) return 0;
-            uint32_t acc = 0;
-            for (uint32_t k = 0; k < st.n_children; ++k) {
-                uint32_t c = ins(h->children[st.offset + k]);
-                acc = st.turn == w ? acc + c : std::max(acc, c);
-            }
-            return acc + 1;
-        };
-        best_int = std::max(best_int, ins(t.train_root));
-        best_dec = std::max(best_dec, wn(t.train_root));
-        best_stack = std::max(best_stack, stk(t.train_root));
-    }
-    *maxdec = best_dec;
-    *maxstack = best_stack + 1;
-    *maxint = best_int;
+    const rp::TableBounds b = rp::table_bounds(h->tbl, h->tbl.train_root);  // the sweep rp_game_table_check runs (games.cpp)
+    *maxdec = std::max(b.decisions, 1u);
+    *maxstack = std::max(b.stack, 1u) + 1;
+    *maxint = std::max(b.internal, 1u);
 }
 
 size_t chunk_maps_lds_bytes(const rp_mccfr* h);

@@ -23,6 +23,18 @@ int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 // Checkpoint's display line / Progress::format (metrics/checkpoint.rs:39-50, progress.rs:8-18)
 void format_progress(char* buf, size_t cap, uint64_t epoch, uint64_t nodes, uint64_t infos, double rate);
 
+// What one table says about the trees below `root` (games.cpp).  Walker states keep every child, all other states one
+// (external sampling); each sampled-tree figure is the maximum over the walkers 0..n_players-1, saturating at UINT32_MAX.
+// Needs children[] entries in range and behind their parents (rp_game_table_check verifies that first).
+struct TableBounds {
+    uint32_t depth;      // states on the longest root-to-leaf path
+    uint32_t nodes;      // nodes of the largest sampled tree
+    uint32_t decisions;  // walker nodes of a sampled tree
+    uint32_t stack;      // pending leaves of the traversal: a walker node pushes all children, one is popped and explored first
+    uint32_t internal;   // expanded (non-terminal) nodes of a sampled tree
+};
+TableBounds table_bounds(const rp_game_table& t, uint32_t root);
+
 }  // namespace rp
 
 // sparse.hip / deuce.hip: what nlmc.hip needs of the profile and of the encoder tables

@@ -42,6 +42,10 @@ SELECTION = [
                                 " or (test_elkan_iterations_bit_exact and sinkhorn-5-150) or test_equity_variation_bit_exact"
                                 " or test_empty_histogram_costs_zero or (test_layer_shape_corners_bit_exact and sinkhorn-65-130)"
                                 " or test_interval_decided_refresh_keeps_the_reference_state"),
+    # caller-built game tables (tests/game_tables.py): k_traverse_lds<false> with three players and with 16 actions + default_regret, the
+    # natural fall-through to k_traverse (depth 11), the smallest tree, and the exact counts of a 16-way chance draw
+    ("tests/test_gpu_mccfr_tables.py", "(test_catalogue_tables_bit_exact_vs_oracle and (three_players_a5 or widest_a16 or depth11 or two_states))"
+                                       " or test_16_way_chance_draws_on_the_device_are_the_restated_ones_exactly"),
 ]
 
 

@@ -1,7 +1,6 @@
 """The C oracle against INDEPENDENT restatements (tests/ref_numpy.py: float64 numpy written from the Rust sources) and
 against closed forms — a second pin next to the reference's own threshold tests.  The oracle and the HIP kernels share
 one author and one include/rp_math.h; these checks do not."""
-import itertools
 from fractions import Fraction
 
 import numpy as np
@@ -9,6 +8,7 @@ import pytest
 
 import oracle
 import ref_numpy as R
+from mccfr_hand import hand_decisions as _hand_decisions, node_hash as _node_hash, sampled_trees as _sampled_trees, u01 as _u01
 from lloyd_fixtures import flop_hist, flop_like_points, flop_metric, random_metric, smooth_metric, turn_like_points
 from robopoker_amd import Game
 
@@ -99,59 +99,6 @@ def test_distributions_match_the_float64_restatement():
         assert np.allclose(s.policy(info, "sampling"), R.sampling_f64(rows["weight"][info, :n]), rtol=2e-6, atol=1e-7)
 
 
-def _sampled_trees(g, walker):
-    """every externally-sampled tree of the game for `walker`: chance and opponent states keep ONE child (all
-    alternatives enumerated), walker states keep all (sample/external.rs:17-64).  A tree is a dict state -> kept children."""
-    t = g.table
-
-    def expand(state):
-        st = t.states[state]
-        if st.n_children == 0:
-            yield {}
-            return
-        kids = [t.children[st.offset + a] for a in range(st.n_children)]
-        if st.turn == walker:
-            for combo in itertools.product(*[list(expand(k)) for k in kids]):
-                tree = {state: list(enumerate(kids))}
-                for sub in combo:
-                    tree.update(sub)
-                yield tree
-        else:
-            for a, k in enumerate(kids):
-                for sub in expand(k):
-                    tree = {state: [(a, k)]}
-                    tree.update(sub)
-                    yield tree
-
-    return expand(t.train_root)
-
-
-def _hand_decisions(g, tree, walker):
-    """CfrFlow::dfs (flow.rs:64-87) for every walker infoset of one sampled tree at epoch 0 of a fresh profile: regret
-    matching is uniform and the sampling distribution is uniform, so an opponent edge carries sigma / q = 1 and a walker
-    edge sigma = 1/|choices| below the root (flow.rs:182-216); chance edges carry 1."""
-    t = g.table
-
-    def value(state):  # recursed_value with relative / sampling reach folded in (exact rationals)
-        st = t.states[state]
-        if st.n_children == 0:
-            return Fraction(t.payoffs[st.offset * t.n_players + walker]).limit_denominator(1 << 20)
-        kept = tree[state]
-        if st.turn == walker:
-            return sum(value(k) for _, k in kept) / st.n_children
-        return sum(value(k) for _, k in kept)  # one child; sigma / q = 1 (or chance: 1)
-
-    out = []
-    for state, kept in tree.items():
-        st = t.states[state]
-        if st.turn != walker:
-            continue
-        vals = [value(k) for _, k in kept]  # ancestor_reach = 1: every non-walker ancestor edge has sigma = q
-        ev = sum(vals) / len(vals)
-        out.append((st.info, tuple(float(v - ev) for v in vals), float(ev)))
-    return out
-
-
 @pytest.mark.parametrize("game", ["kuhn", "leduc"])
 def test_first_epoch_decisions_are_hand_traceable(game):
     # An independent enumeration (Python, exact rationals) of every tree external sampling can produce and of the
@@ -184,38 +131,6 @@ def test_first_epoch_decisions_are_hand_traceable(game):
 
 
 # ---- the pruning schemes' masks, from the table alone (sample/pruning.rs:44-66, pluribus.rs:72-101) -----------------------
-_M64 = (1 << 64) - 1
-
-
-def _mix64(z):
-    z ^= z >> 30
-    z = (z * 0xbf58476d1ce4e5b9) & _M64
-    z ^= z >> 27
-    z = (z * 0x94d049bb133111eb) & _M64
-    return z ^ (z >> 31)
-
-
-def _node_hash(seed, epoch, tree, key):  # include/rp_math.h rp_node_hash, restated on Python integers
-    h = _mix64((seed + 0x9e3779b97f4a7c15) & _M64)
-    h = _mix64(h ^ ((epoch * 0xd1342543de82ef95 + 0x632be59bd9b4e019) & _M64))
-    h = _mix64(h ^ ((tree * 0xaf251af3b0f025b5 + 0x2545f4914f6cdd1d) & _M64))
-    # the per-draw half: Murmur3's 32-bit finaliser over the low word and the folded key, the high word multiplied in
-    lo, hi, k = h & 0xffffffff, h >> 32, (key ^ (key >> 32)) & 0xffffffff
-    x = lo ^ k
-    x ^= x >> 16
-    x = (x * 0x85ebca6b) & 0xffffffff
-    x ^= x >> 13
-    x = (x * 0xc2b2ae35) & 0xffffffff
-    x ^= x >> 16
-    x = ((x ^ hi) * 0x9e3779b1) & 0xffffffff
-    x ^= x >> 15
-    return x << 32
-
-
-def _u01(h):  # rp_u01: the top 24 bits as a float in [0, 1)
-    return np.float32(h >> 40) * np.float32(5.9604644775390625e-8)
-
-
 @pytest.mark.parametrize("sampling", ["pluribus", "prunable"])
 def test_pruned_masks_follow_from_the_table(sampling):
     # Which walker edges a Decisions expanded is a pure function of (the infoset's accumulated regrets, the scheme's constants,
