@@ -484,8 +484,10 @@ size_t traverse_maps_lds_bytes(const rp_mccfr* h) {
     return (NI * 8 + 2 * NI) * 4 + NI * 8 * 2 + (NI + (NI & 1)) * 2 + (size_t)5 * (h->maxdec * 256 + h->cell_pad) * 4 + masks;
 }
 static_assert(CH_THREADS <= 256u, "k_traverse_maps_static packs (infoset, rank of the infoset) into the 16 bits of an `order` entry");
+// rank_max <= 64: one wavefront builds the chunk's lists, a lane per infoset of the walker (Kuhn 6, Leduc 60; a skeleton game with more
+// takes k_chunk_maps)
 bool traverse_maps_fused(const rp_mccfr* h) {
-    return h->static_skel && !h->dc.slotmap && h->tbl.n_infos <= CH_THREADS &&
+    return h->static_skel && !h->dc.slotmap && h->tbl.n_infos <= CH_THREADS && h->g.rank_max <= 64u &&
            traverse_maps_lds_bytes(h) <= 64 * 1024 && h->fuse_maps;
 }
 

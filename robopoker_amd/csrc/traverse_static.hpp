@@ -32,7 +32,6 @@
 
 #include "mccfr_kernels.hpp"
 #include "mccfr_traverse.hpp"  // DevInfoTab, count_metrics, the draws
-#include "mccfr_update.hpp"    // lds_exscan: the fused kernel builds the block maps of its chunk
 
 namespace rp {
 
@@ -660,7 +659,8 @@ __global__ __launch_bounds__(256) void k_traverse_static(DevGame g, DevInfoTab i
 // as k_chunk_maps: the chunk's row of block maps (bmap_index) is bit-identical (tests/test_gpu_mccfr.py).
 // A chain is sequential and as long as its list (a root infoset meets a third of the chunk's trees, a river infoset a few):
 // the (infoset, cell) tasks are handed out in descending order of list length (a counting sort by log2 class), so the 64
-// chains of a wave have similar lengths instead of every wave waiting for one long chain.
+// chains of a wave have similar lengths instead of every wave waiting for one long chain.  Only the walker's infosets have
+// lists: `order` holds those alone (rank_count[W] entries), and pre / lcount / lbase are written for them alone.
 // LDS (dynamic): bits u32[NI][8] | lcount u32[NI] | lbase u32[NI] | pre u16[NI][8] | order u16[NI + (NI & 1)] | vals f32[5][maxdec * 256 + lpad]
 //                | (PRUNED) lmask u32[maxdec * 256]: the expanded edges of every list entry — a regret cell skips the entries
 //                  whose edge was pruned (no touch at all: a touch would apply the discount), as k_chunk_maps<true> does
@@ -668,9 +668,12 @@ template <class G, int W, bool PRUNED, bool REF>
 __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevInfoTab it, StepParams p, Map* bmaps,
                                                               uint32_t maxdec, uint32_t lpad) {
     extern __shared__ __attribute__((aligned(16))) uint32_t tm_lds[];
-    __shared__ uint32_t wave_tot[4];
-    __shared__ uint32_t cls_n[16], cls_at[16];
+    static_assert(SM_WORDS == 8u, "a bitmap row is two 16-byte LDS reads, its prefix counts two 8-byte writes");
     const uint32_t NI = g.n_infos, chunk = blockIdx.x, lt = threadIdx.x;
+    // the lists are built by wavefront 0, lane r those of the walker's infoset of rank r (traverse_maps_fused: at most 64 ranks); the
+    // infoset is fetched here, long before its use
+    const uint32_t nr = g.rank_count[W];
+    const uint32_t my_info = lt < nr ? g.rank_info[(size_t)W * g.rank_max + lt] : 0u;
     uint32_t* bits = tm_lds;
     uint32_t* lcount = bits + NI * SM_WORDS;
     uint32_t* lbase = lcount + NI;
@@ -683,7 +686,6 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
     const uint32_t L = maxdec * 256u + lpad;
     uint32_t* lmask = reinterpret_cast<uint32_t*>(vals + 5u * L);
     for (uint32_t e = lt; e < NI * SM_WORDS; e += 256u) bits[e] = 0;
-    if (lt < 16u) cls_n[lt] = 0;
     __syncthreads();
     const uint32_t lane = chunk * 256u + lt;
     const float tf = (float)p.epoch;
@@ -696,27 +698,41 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
                 }
             });
             __syncthreads();
-            for (uint32_t info = lt; info < NI; info += 256u) {
-                const uint32_t run = list_prefix(bits, pre, info);
-                lcount[info] = run;
-                atomicAdd(&cls_n[15u - (run ? 32u - (uint32_t)__builtin_clz(run) : 0u)], 1u);  // class 15 - bit length: long lists first
-            }
-            __syncthreads();
-            lds_exscan(lcount, lbase, NI, wave_tot);
-            if (lt == 0) {
-                uint32_t at = 0;
-                for (uint32_t k = 0; k < 16u; ++k) {
-                    cls_at[k] = at;
-                    at += cls_n[k];
+            // wavefront 0, everything in registers: the prefix counts of the lane's bitmap row (list_prefix), the lists' bases by a
+            // scan across the lanes, the places in `order` by one ballot per length class.  The other wavefronts wait at the barrier
+            if (lt < 64u) {
+                const bool mine = lt < nr;
+                // the row in halves, each half's prefix counts stored before the next is read: the sampled tree is live in registers
+                uint2* const pw = reinterpret_cast<uint2*>(pre + my_info * SM_WORDS);
+                const uint4 lo = *reinterpret_cast<const uint4*>(bits + my_info * SM_WORDS);
+                const uint32_t p1 = __popc(lo.x), p2 = p1 + __popc(lo.y), p3 = p2 + __popc(lo.z), p4 = p3 + __popc(lo.w);
+                if (mine) pw[0] = make_uint2(p1 << 16, p2 | p3 << 16);
+                const uint4 hi = *reinterpret_cast<const uint4*>(bits + my_info * SM_WORDS + 4u);
+                const uint32_t p5 = p4 + __popc(hi.x), p6 = p5 + __popc(hi.y), p7 = p6 + __popc(hi.z);
+                if (mine) pw[1] = make_uint2(p4 | p5 << 16, p6 | p7 << 16);
+                const uint32_t run = mine ? p7 + __popc(hi.w) : 0u;
+                uint32_t incl = run;
+                for (int d = 1; d < 64; d <<= 1) {
+                    const uint32_t o = __shfl_up(incl, d, 64);
+                    if ((int)lt >= d) incl += o;
+                }
+                // long lists first: classes by bit length, 9 (a list of all CH_TREES trees) down to 0 (empty); ascending rank within one
+                const uint32_t len = run ? 32u - (uint32_t)__builtin_clz(run) : 0u;
+                uint32_t place = 0, at = 0;
+                for (uint32_t k = 10u; k-- > 0u;) {
+                    const unsigned long long m = __ballot(mine && len == k);
+                    if (len == k) place = at + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                    at += (uint32_t)__popcll(m);
+                }
+                if (mine) {
+                    lcount[my_info] = run;
+                    lbase[my_info] = incl - run;
+                    // the infoset and its rank among its player's infosets (bmap_index) share the entry, 8 bits each: the launch is
+                    // made for at most CH_THREADS infosets (traverse_maps_fused)
+                    order[place] = (uint16_t)(my_info | lt << 8);
                 }
             }
             __syncthreads();
-            for (uint32_t info = lt; info < NI; info += 256u) {
-                const uint32_t run = lcount[info];
-                // the infoset and, fetched now and not in the chain phase, its rank among its player's infosets (bmap_index) share the
-                // entry, 8 bits each: the launch is made for at most CH_THREADS infosets (traverse_maps_fused)
-                order[atomicAdd(&cls_at[15u - (run ? 32u - (uint32_t)__builtin_clz(run) : 0u)], 1u)] = (uint16_t)(info | g.info_rank[info] << 8);
-            }
         };
     auto on_decision =
         [&](auto, uint32_t info, float g0, float g1, float s0, float s1, float payoff, uint32_t mask) __attribute__((always_inline)) {
@@ -745,9 +761,8 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
         // the final 0.0f + b gives the empty list its 0.0f (b of the identity).  Its m is ignored.
         const uint32_t ln = lt & 63u, sub = ln / 5u, c = ln - 5u * sub;
         const float fl = c < 2u ? cpr.fl : (c < 4u ? cpw.fl : rp_u2f(0xff800000u));
-        for (uint32_t i = (lt >> 6) * 12u + sub; ln < 60u && i < NI; i += 4u * 12u) {
+        for (uint32_t i = (lt >> 6) * 12u + sub; ln < 60u && i < nr; i += 4u * 12u) {
             const uint32_t info = order[i] & 255u, rank = order[i] >> 8;
-            if (g.info_player[info] != p.walker) continue;
             const uint32_t n = lcount[info], base = lbase[info];
             const float* v = vals + (size_t)c * L + base;
             Map mp = map_identity();
@@ -759,10 +774,9 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
         // any other discount: task = (cell c, infoset); cells 0,1 regret, 2,3 weight, 4 the payoff sum.  The payoff sums are handed out
         // after all the map chains, so that no wavefront mixes the two loops (measured round 4: 0.582 -> 0.562 ms per launch against
         // task % 5)
-        for (uint32_t task = lt; task < 5u * NI; task += 256u) {
-            const uint32_t c = task < 4u * NI ? task & 3u : 4u;
-            const uint32_t oi = order[task < 4u * NI ? task >> 2 : task - 4u * NI], info = oi & 255u, rank = oi >> 8;
-            if (g.info_player[info] != p.walker) continue;
+        for (uint32_t task = lt; task < 5u * nr; task += 256u) {
+            const uint32_t c = task < 4u * nr ? task & 3u : 4u;
+            const uint32_t oi = order[task < 4u * nr ? task >> 2 : task - 4u * nr], info = oi & 255u, rank = oi >> 8;
             const uint32_t n = lcount[info], base = lbase[info];
             const size_t out = bmap_index(chunk, rank, c, g.rank_max, 4u);
             const float* v = vals + (size_t)c * L + base;
