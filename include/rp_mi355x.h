@@ -995,6 +995,92 @@ typedef struct rp_aivat_summary {
 } rp_aivat_summary;
 RP_API int rp_aivat_summarize(uint64_t n, const float* adjusted, float raw_stddev, rp_aivat_summary* out);
 
+/* MATCHES: batches of heads-up hands played on the device between two agents, each reading a device-resident blueprint — the
+ * producer of the hands rp_nlhe_aivat scores and of the winnings a bb/100 figure is made of.  Reference: the table of
+ * parlor/src/engine.rs:48-68, 268-320 seating parlor/src/players/{agent,brain,blueprint,dirac,fish}.rs; the statistics of
+ * spar/src/benchmark.rs:122-147.  One lane per hand (csrc/nlmc_match.hpp).  Seat s reads the table of handle hs; h1 == h0 or
+ * h1 == NULL: one table serves both seats.  Both handles live on one device and share one encoder (the same lookup tables, or
+ * both the hashed encoder).  Read-only on both tables exactly as rp_nlhe_policy: nothing is inserted, epoch / counters / keys are
+ * unchanged, a queried table steps like one never queried.
+ *
+ * IDS AND RANDOM NUMBERS.  The reference deals and samples from the thread RNG: there is nothing of it to reproduce, so the
+ *   library's counter contract (include/rp_math.h) is used, on two streams that never mix.  hand_id = first_id + i (wrapping);
+ *   deal_id = mirror ? hand_id >> 1 : hand_id.  Card c of a deal is rp_node_hash(seed, 0, deal_id, c), c = 0..8: seat 0's two
+ *   cards, seat 1's two, the flop's three, the turn, the river; each is rp_pick_uniform over the popcount of the remaining deck,
+ *   the pick-th lowest card, which is then removed (the frontier rollouts' rule).  With mirror and an odd hand_id the two holes are
+ *   swapped after dealing: hands 2m and 2m + 1 are one deal seen from both sides.  The board of a deal does not depend on the plays.
+ *   Decision d of a hand, d counting from 0 over both seats, reads rp_node_hash(seed, 1, hand_id, d) WHETHER ITS AGENT USES IT OR
+ *   NOT, so one seat's agent kind never shifts the other's draws.  A hand's outputs depend on seed, hand_id and the args only,
+ *   never on the batch around it: a batch split into calls with matching first_id answers the same bytes.
+ * THE GAME.  Game::from_start(dealer, stacks) with both holes; dealer 2 = hand_id & 1; stacks 0,0 = STACK.  At a chance node the
+ *   deal's street is applied; the run-out after an all-in and a call is dealt to the end.  draws[s] of the record is street s as
+ *   dealt, 0 for a street never reached.
+ * THE KEY AT A DECISION is that of Brain::policy on the engine's witness (engine.rs:48-68: Witness::initial_with the real buy-ins
+ *   and dealer, the actor's hole and the board dealt so far, the choice actions pushed) — the witness game IS the real game, so
+ *   one game is kept.  past = subgame(), choices = head.choices(subgame().aggression()), with the two 12-edge cuts stated above
+ *   rp_nlhe_aivat (history()'s running Path, subgame()'s Path); present = the bucket of (the actor's hole, the board at the node).
+ * AGENTS (rp_agent_kind).
+ *   RP_AGENT_BLUEPRINT (Agent<Blueprint>): RP_DIST_AVERAGED in rp_nlhe_policy's arithmetic, an absent row uniform; then sampled as
+ *     WeightedIndex over the BTreeMap<Edge, _>, i.e. in Edge's DERIVED Ord, not in slot order: Draw < Fold < Check < Call <
+ *     Open by chips < Raise by Odds' derived (numerator, denominator) tuple order < Shove (kicker/src/edge.rs:18-27,
+ *     odds.rs:10-11).  RP_EDGE_ORD_RANKS below is the rank of every edge code in that order.  total = the f32 left fold of the
+ *     probabilities from 0.0f in that order; threshold = rp_u01(draw) * total; the first edge with threshold < running sum (the
+ *     same fold) is played, the last edge if there is none.
+ *   RP_AGENT_DIRAC (Dirac<Blueprint>, nlhe::argmax, nlhe/src/strategy.rs:77-89): the LAST maximal edge in that same order
+ *     (Iterator::max_by with ties Equal keeps the later one).
+ *   RP_AGENT_FISH (fish.rs): reads no table.  Uniform, by rp_pick_uniform, over legal() in its own order (kicker/src/game.rs:
+ *     253-280: raise, shove, call, fold, check) with the shove removed; the raise is Game::raise(), the minimum.
+ *   A sampled edge becomes game.actionize(edge) (game.rs:741-751) on the real game.  Agent::sample's other arm (WeightedIndex
+ *   failing) cannot be reached with a floored distribution and is not built.  NaN weights are not part of the contract.
+ * A REFUSED PLAY.  snap = 0, the engine's rule (engine.rs:295-320): an action that is not is_allowed is rejected and the seat times
+ *   out into passive(); the play recorded and applied is passive(), and rejected[i] counts it, saturating at 255.  snap = 1: the
+ *   play is game.snap(game.actionize(edge)), as NlheGame::apply and the rollouts have it, and rejected stays 0; a snapped play the
+ *   rules still refuse gives the hand RP_RECALL_ILLEGAL as a rollout would (the reference panics).
+ * THE RECORD is an rp_aivat_hand rp_nlhe_aivat reads as it is: hole, draws, stacks (as given: 0,0 kept), dealer (the hand's, 0 or
+ *   1), seat = hero, board_mode (copied), the choice plays in order — kind, and chips for Call / Raise / Shove, 0 for Fold / Check —
+ *   n_plays, and zeros in the plays past n_plays.  won[i] = Settlement::won of seat `hero`, in chips.
+ * STATUS per hand: RP_RECALL_OK; RP_RECALL_LOOKUP where the lookup tables do not hold an observation a blueprint or dirac agent
+ *   asks for; RP_RECALL_LENGTH where the hand has more than RP_AIVAT_MAX_PLAYS plays — it is still played to its end, won and
+ *   rejected are valid and the record holds the first 48 plays with n_plays = 48; RP_RECALL_ILLEGAL for the refused snapped play
+ *   above, a decision without choices, or the step bound of the frontier rollouts (12 x 32 768 steps, the same derivation)
+ *   reached.  LOOKUP and ILLEGAL give zero outputs: an all-zero record, won 0, rejected 0.  No input causes an out-of-bounds
+ *   access or an unbounded loop.
+ * THE CALL.  RP_ERR_INVALID, and nothing per hand: NULL h0 or args, agent above RP_AGENT_FISH, dealer > 2, hero > 1, mirror, snap or
+ *   board_mode > 1, stacks neither 0,0 nor both positive, reserved != 0, handles on two devices or two encoders.  n = 0 is RP_OK
+ *   without a launch.  hands, won, rejected and status may each be NULL.  The _device form takes every output pointer in DEVICE
+ *   memory (args stay on the host), queues on h0's stream after an event recorded on h1's stream, and returns without
+ *   synchronising; the host form stages, launches and synchronises. */
+typedef enum { RP_AGENT_BLUEPRINT = 0, RP_AGENT_DIRAC = 1, RP_AGENT_FISH = 2 } rp_agent_kind;
+/* rank of edge code e (kicker/src/edge.rs:101-120: 1 Draw, 2 Fold, 3 Check, 4 Call, 5 Shove, 6..9 Open(2,3,4,5), 10..19
+ * Raise(1/4, 1/3, 1/2, 2/3, 3/4, 1/1, 5/4, 3/2, 2/1, 3/1)) in Edge's derived Ord; code 0 is no edge */
+#define RP_EDGE_ORD_RANKS {31, 0, 1, 2, 3, 18, 4, 5, 6, 7, 11, 10, 9, 13, 16, 8, 17, 15, 12, 14}
+typedef struct rp_nlhe_match_args {
+    uint64_t seed, first_id;
+    int16_t  stacks[2];     /* every hand starts from these; 0,0 = STACK; else both positive */
+    uint8_t  agent[2];      /* rp_agent_kind of seat 0 / seat 1 */
+    uint8_t  dealer;        /* 0, 1, or 2 = (hand id & 1) */
+    uint8_t  hero;          /* the seat `won` and the record's `seat` speak of */
+    uint8_t  mirror;        /* 1: hands 2m and 2m+1 are one deal with the holes swapped */
+    uint8_t  snap;          /* 0: the engine's rule for a refused play; 1: game.snap(...) */
+    uint8_t  board_mode;    /* copied into the records */
+    uint8_t  reserved[5];   /* 0 */
+} rp_nlhe_match_args;       /* 32 bytes */
+/* seed 0, first_id 0, stacks 0,0, both agents RP_AGENT_BLUEPRINT, dealer 2, hero 0, mirror 0, snap 0, board_mode 1 */
+RP_API void rp_nlhe_match_args_default(rp_nlhe_match_args* out);
+RP_API int rp_nlhe_match(rp_nlhe* h0, rp_nlhe* h1, uint64_t n, const rp_nlhe_match_args* args /* host */, rp_aivat_hand* hands,
+                         int16_t* won, uint8_t* rejected, uint8_t* status);
+RP_API int rp_nlhe_match_device(rp_nlhe* h0, rp_nlhe* h1, uint64_t n, const rp_nlhe_match_args* args /* host */,
+                                rp_aivat_hand* hands_dev, int16_t* won_dev, uint8_t* rejected_dev, uint8_t* status_dev);
+/* The bb/100 statistics of spar/src/benchmark.rs:122-147.  Host only, no handle, no device, f64 as the reference:
+ *   x_i = won[i] / (double)B_BLIND (2 chips); total_bb = Σ x, a left fold from 0.0; bb_per_100 = total_bb / n * 100;
+ *   mean = total_bb / n; stddev = sqrt(Σ (x - mean)(x - mean) / (n - 1)), 0 with n < 2;
+ *   confidence = 1.96 * stddev / sqrt(n) * 100, evaluated left to right.  n = 0: everything 0, won may then be NULL. */
+typedef struct rp_match_summary {
+    uint64_t hands;
+    double   total_bb, bb_per_100, stddev, confidence;
+} rp_match_summary;         /* 40 bytes */
+RP_API int rp_match_summarize(uint64_t n, const int16_t* won, rp_match_summary* out);
+
 /* Multi-GPU (BASELINE configs[3]): trees sharded by rank (rank r samples tree ids [r*B, (r+1)*B) of a world*B-tree epoch
  * against a replicated table).  step_local: this rank's traversal reduced to one composed entry per infoset touched
  * (rp_profile_summarize's records, entry_bytes each, at most max_entries) plus the infoset KEY of every entry — each

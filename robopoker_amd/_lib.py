@@ -50,6 +50,7 @@ RP_NLHE_SUBGAME_ORIGIN_NONE = 126
 RP_AIVAT_MAX_PLAYS = 48
 RP_AIVAT_WITNESS = 11
 PLAY = {"fold": 1, "call": 2, "check": 3, "raise": 4, "shove": 5}  # rp_aivat_play
+AGENT = {"blueprint": 0, "dirac": 1, "fish": 2}  # rp_agent_kind
 
 
 class Hyper(C.Structure):
@@ -84,6 +85,17 @@ class AivatHand(C.Structure):
 class AivatSummary(C.Structure):
     """rp_aivat_summary: Aivat::summarize's figures"""
     _fields_ = [("won", C.c_float), ("mean", C.c_float), ("stderr", C.c_float), ("reduction", C.c_float), ("pvalue", C.c_float)]
+
+
+class NlheMatchArgs(C.Structure):
+    """rp_nlhe_match_args: one per call (32 bytes)"""
+    _fields_ = [("seed", C.c_uint64), ("first_id", C.c_uint64), ("stacks", C.c_int16 * 2), ("agent", C.c_uint8 * 2), ("dealer", C.c_uint8),
+                ("hero", C.c_uint8), ("mirror", C.c_uint8), ("snap", C.c_uint8), ("board_mode", C.c_uint8), ("reserved", C.c_uint8 * 5)]
+
+
+class MatchSummary(C.Structure):
+    """rp_match_summary: the bb/100 figures of a series of winnings (40 bytes)"""
+    _fields_ = [("hands", C.c_uint64), ("total_bb", C.c_double), ("bb_per_100", C.c_double), ("stddev", C.c_double), ("confidence", C.c_double)]
 
 
 class NlheFrontier(C.Structure):
@@ -397,6 +409,10 @@ _SIGNATURES = {
     "rp_nlhe_aivat": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 8),
     "rp_nlhe_aivat_device": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 8),
     "rp_aivat_summarize": (C.c_int, [C.c_uint64, C.c_void_p, C.c_float, C.POINTER(AivatSummary)]),
+    "rp_nlhe_match_args_default": (None, [C.POINTER(NlheMatchArgs)]),
+    "rp_nlhe_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(NlheMatchArgs)] + [C.c_void_p] * 4),
+    "rp_nlhe_match_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(NlheMatchArgs)] + [C.c_void_p] * 4),
+    "rp_match_summarize": (C.c_int, [C.c_uint64, C.c_void_p, C.POINTER(MatchSummary)]),
     "rp_nlhe_partition": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
     "rp_nlhe_partition_device": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
     "rp_nlhe_belief": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5),

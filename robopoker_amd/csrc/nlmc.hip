@@ -39,6 +39,7 @@
 #include "nlmc_world.hpp"
 #include "nlmc_subgame.hpp"
 #include "nlmc_aivat.hpp"
+#include "nlmc_match.hpp"
 #include "../../include/rp_libm_glibc.h"
 #include "rp_internal.h"
 #include "sortscan.hpp"
@@ -1566,6 +1567,110 @@ int rp_aivat_summarize(uint64_t n, const float* adjusted, float raw_stddev, rp_a
     out->stderr_ = stderr_;
     out->reduction = adj > 0.0f ? raw / adj : 1.0f;
     out->pvalue = stderr_ > 0.0f ? 2.0f * na_erf(-fabsf(mean) / stderr_) : 1.0f;
+    return RP_OK;
+}
+
+}  // extern "C"
+
+// ---- matches (nlmc_match.hpp): one lane per hand, at most NR_CHUNK hands per launch
+namespace {
+int nm_check(const rp_nlhe* h0, const rp_nlhe* h1, const rp_nlhe_match_args* a) {
+    if (!h0) return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: NULL handle");
+    if (!a) return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: NULL args");
+    if (a->agent[0] > (uint8_t)RP_AGENT_FISH || a->agent[1] > (uint8_t)RP_AGENT_FISH)
+        return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: agent %u / %u is no rp_agent_kind", a->agent[0], a->agent[1]);
+    if (a->dealer > 2u) return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: dealer %u above 2", a->dealer);
+    if (a->hero > 1u) return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: hero %u above 1", a->hero);
+    if (a->mirror > 1u || a->snap > 1u || a->board_mode > 1u)
+        return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: mirror, snap and board_mode are 0 or 1");
+    const bool std_stacks = a->stacks[0] == 0 && a->stacks[1] == 0;
+    if (!std_stacks && (a->stacks[0] <= 0 || a->stacks[1] <= 0))
+        return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: stacks %d, %d are neither 0,0 nor both positive", a->stacks[0], a->stacks[1]);
+    for (uint8_t r : a->reserved)
+        if (r != 0u) return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: reserved must be 0");
+    if (h1 && h1 != h0) {
+        if (h1->device != h0->device) return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: the two handles are on devices %d and %d", h0->device, h1->device);
+        bool same = h1->prm.encoder == h0->prm.encoder;
+        for (int s = 0; s < 4 && same && h0->prm.encoder; ++s)
+            same = h1->prm.tkeys[s] == h0->prm.tkeys[s] && h1->prm.tabs[s] == h0->prm.tabs[s] && h1->prm.tn[s] == h0->prm.tn[s];
+        if (!same) return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: the two handles are built on different encoders");
+    }
+    return RP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void rp_nlhe_match_args_default(rp_nlhe_match_args* out) {
+    if (!out) return;
+    *out = rp_nlhe_match_args{};
+    out->dealer = 2;
+    out->board_mode = 1;
+}
+
+int rp_nlhe_match_device(rp_nlhe* h0, rp_nlhe* h1, uint64_t n, const rp_nlhe_match_args* args, rp_aivat_hand* hands, int16_t* won,
+                         uint8_t* rejected, uint8_t* status) {
+    int rc = nm_check(h0, h1, args);
+    if (rc || n == 0) return rc;
+    if (!h1) h1 = h0;
+    HIP_TRY(hipSetDevice(h0->device));
+    hipStream_t st = rp::profile_stream(h0->prof), st1 = rp::profile_stream(h1->prof);
+    if (st1 != st) {  // what h1's stream has queued for its table comes first
+        hipEvent_t ev;
+        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        hipError_t e = hipEventRecord(ev, st1);
+        if (e == hipSuccess) e = hipStreamWaitEvent(st, ev, 0);
+        (void)hipEventDestroy(ev);  // the wait already queued keeps what it needs
+        HIP_TRY(e);
+    }
+    return nl_chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
+        NmArgs q{};
+        q.deal_hash = rp_node_hash_step(args->seed, 0);
+        q.play_hash = rp_node_hash_step(args->seed, 1);
+        q.first_id = args->first_id + at;
+        q.n = m;
+        q.stacks[0] = args->stacks[0], q.stacks[1] = args->stacks[1];
+        q.agent[0] = args->agent[0], q.agent[1] = args->agent[1];
+        q.dealer = args->dealer, q.hero = args->hero, q.mirror = args->mirror, q.snap = args->snap, q.board_mode = args->board_mode;
+        q.hands = nl_at(hands, at);
+        q.won = nl_at(won, at);
+        q.rejected = nl_at(rejected, at);
+        q.status = nl_at(status, at);
+        hipLaunchKernelGGL(k_nl_match, dim3((m + NM_BLOCK - 1u) / NM_BLOCK), dim3(NM_BLOCK), 0, st, h0->tab, h1->tab, h0->prm, q);
+    });
+}
+
+int rp_nlhe_match(rp_nlhe* h0, rp_nlhe* h1, uint64_t n, const rp_nlhe_match_args* args, rp_aivat_hand* hands, int16_t* won, uint8_t* rejected,
+                  uint8_t* status) {
+    int rc = nm_check(h0, h1, args);
+    if (rc || n == 0) return rc;
+    Stage s(h0);
+    s.out(hands, n).out(won, n).out(rejected, n).out(status, n);
+    if ((rc = s.up()) || (rc = rp_nlhe_match_device(h0, h1, n, args, hands, won, rejected, status))) return rc;
+    return s.down();
+}
+
+int rp_match_summarize(uint64_t n, const int16_t* won, rp_match_summary* out) {
+    if (!out) return rp::fail(RP_ERR_INVALID, "rp_match_summarize: NULL out");
+    if (n > 0 && !won) return rp::fail(RP_ERR_INVALID, "rp_match_summarize: NULL won with n > 0");
+    *out = rp_match_summary{};
+    out->hands = n;
+    if (n == 0) return RP_OK;
+    const double nf = (double)n, bb = (double)NL_BBLIND;
+    double total = 0.0;
+    for (uint64_t i = 0; i < n; ++i) total = total + (double)won[i] / bb;
+    out->total_bb = total;
+    out->bb_per_100 = total / nf * 100.0;
+    if (n >= 2) {
+        const double mean = total / nf;
+        double squares = 0.0;
+        for (uint64_t i = 0; i < n; ++i) {
+            const double d = (double)won[i] / bb - mean;
+            squares = squares + d * d;
+        }
+        out->stddev = sqrt(squares / (double)(n - 1));
+    }
+    out->confidence = 1.96 * out->stddev / sqrt(nf) * 100.0;
     return RP_OK;
 }
 

@@ -39,20 +39,19 @@ struct NaArgs {
     uint8_t *n_action, *n_chance, *status;  // any may be NULL
 };
 
-// the witness game and what Recall derives from its actions
-struct NaWitness {
-    G2 g;
+// what Recall derives from a witness's actions, kept beside its game (shared with the match kernel, nlmc_match.hpp, whose
+// witness game is the real game)
+struct NaCounts {
     NrpPath run;                 // history()'s running Path: only its aggression is read
     uint64_t sub;                // subgame(): the street's first 12 edges, 5-bit fields
     uint32_t sub_len, sub_aggr;  // ... their number and the raises / shoves among them
     uint32_t act_aggr;           // Recall::aggression()
-    uint32_t streets;            // seen().street(): the streets the hand's draws carry
     __device__ __forceinline__ void street_begins() {
         sub = 0;
         sub_len = sub_aggr = act_aggr = 0;
     }
-    // try_push after can_push: the action joins the history as the edge history() gives it, then sprout()
-    __device__ __forceinline__ void push(const NlAction& a, const uint64_t* draws) {
+    // the action joins the history as the edge history() gives it on the game BEFORE the action
+    __device__ __forceinline__ void note(const G2& g, const NlAction& a) {
         const uint32_t e = nl_edgify(g, a, (int)run.aggr);
         run.push(e);
         if (sub_len < 12u) {
@@ -60,11 +59,25 @@ struct NaWitness {
             sub_aggr += (e == NE_SHOVE || e >= NE_OPEN0) ? 1u : 0u;
         }
         act_aggr += (a.kind == NA_RAISE || a.kind == NA_SHOVE) ? 1u : 0u;
+    }
+    // a street was dealt into the witness game
+    __device__ __forceinline__ void dealt() {
+        run.push(NE_DRAW);
+        street_begins();
+    }
+};
+
+// the witness game and what Recall derives from its actions
+struct NaWitness : NaCounts {
+    G2 g;
+    uint32_t streets;            // seen().street(): the streets the hand's draws carry
+    // try_push after can_push: the action joins the history as the edge history() gives it, then sprout()
+    __device__ __forceinline__ void push(const NlAction& a, const uint64_t* draws) {
+        note(g, a);
         g.force_act(a);
         while ((uint32_t)g.street() < streets && g.turn() == NT_CHANCE) {
             g.force_act(NlAction{NA_DRAW, 0, draws[g.street()]});
-            run.push(NE_DRAW);
-            street_begins();
+            dealt();
         }
     }
     // head().choices(subgame().aggression()); no choices where the head is no decision node

@@ -164,6 +164,7 @@ class NlheSolver:
             self.hp = _lib.Hyper()
             self._lib.rp_hyper_default(C.byref(self.hp))
         self.batch_size = batch
+        self.device = device
         self._tables = tables
         tab = None
         if tables is not None:
@@ -446,6 +447,49 @@ class NlheSolver:
         s = _lib.AivatSummary()
         _lib.check(_lib.load().rp_aivat_summarize(x.size, _p(x), float(raw_stddev), C.byref(s)))
         return {k: np.float32(getattr(s, k)) for k in ("won", "mean", "stderr", "reduction", "pvalue")}
+
+    # ---- matches (include/rp_mi355x.h rp_nlhe_match): hands played on the device between two agents, as AIVAT's records ----
+    @staticmethod
+    def _match_args(seed=0, first_id=0, stacks=(0, 0), agents=("blueprint", "blueprint"), dealer=2, hero=0, mirror=False, snap=False,
+                    board_mode=1):
+        """rp_nlhe_match_args; ``agents``: "blueprint" / "dirac" / "fish" (or rp_agent_kind codes) of seat 0 and seat 1"""
+        a = _lib.NlheMatchArgs()
+        _lib.load().rp_nlhe_match_args_default(C.byref(a))
+        a.seed, a.first_id, a.dealer, a.hero, a.mirror, a.snap, a.board_mode = seed, first_id, dealer, hero, int(mirror), int(snap), board_mode
+        a.stacks[0], a.stacks[1] = stacks
+        a.agent[0], a.agent[1] = (_lib.AGENT[k] if isinstance(k, str) else k for k in agents)
+        return a
+
+    def match(self, n, opponent=None, **args):
+        """n heads-up hands between seat 0 reading this solver's table and seat 1 reading ``opponent``'s (None: this one), the table of
+        ``parlor/src/engine.rs`` seating ``Agent<Blueprint>`` / ``Dirac`` / ``Fish``: dict(hands AIVAT_DTYPE[n], the records
+        ``aivat`` takes as they are; won int16[n], the hero's chips; rejected uint8[n]; status uint8[n]).  ``args``: seed, first_id,
+        stacks, agents, dealer (2 = alternating), hero, mirror, snap, board_mode.  Hand i draws from the counter streams of
+        ``first_id + i``: a batch split into calls with matching ``first_id`` answers the same bytes.  Read-only on both tables."""
+        a, n = self._match_args(**args), int(n)
+        out = dict(hands=np.zeros(n, AIVAT_DTYPE), won=np.zeros(n, np.int16), rejected=np.zeros(n, np.uint8), status=np.zeros(n, np.uint8))
+        _lib.check(self._lib.rp_nlhe_match(self._h, opponent._h if opponent is not None else None, n, C.byref(a), _p(out["hands"]),
+                                           _p(out["won"]), _p(out["rejected"]), _p(out["status"])))
+        return out
+
+    def match_device(self, n, opponent=None, **args):
+        """rp_nlhe_match_device: -> the same dict of device tensors (hands uint8[n, 192], which ``aivat_device`` takes as it is), queued
+        on the solver's stream after what ``opponent``'s stream holds (``sync()`` waits)"""
+        a, n, d = self._match_args(**args), int(n), torch.device("cuda", self.device)
+        out = dict(hands=torch.empty((n, AIVAT_DTYPE.itemsize), dtype=torch.uint8, device=d), won=torch.empty(n, dtype=torch.int16, device=d),
+                   rejected=torch.empty(n, dtype=torch.uint8, device=d), status=torch.empty(n, dtype=torch.uint8, device=d))
+        _lib.check(self._lib.rp_nlhe_match_device(self._h, opponent._h if opponent is not None else None, n, C.byref(a),
+                                                  *[_dptr(out[k], n) for k in ("hands", "won", "rejected", "status")]))
+        return out
+
+    @staticmethod
+    def match_summary(won):
+        """the bb/100 statistics of ``spar/src/benchmark.rs`` over the winnings of a match in chips: dict(hands, total_bb, bb_per_100,
+        stddev, confidence) as float64 (hands: int).  Host arithmetic, no device."""
+        x = np.ascontiguousarray(won, np.int16).ravel()
+        s = _lib.MatchSummary()
+        _lib.check(_lib.load().rp_match_summarize(x.size, _p(x), C.byref(s)))
+        return dict(hands=int(s.hands), **{k: np.float64(getattr(s, k)) for k in ("total_bb", "bb_per_100", "stddev", "confidence")})
 
     # ---- frontier payoffs (include/rp_mi355x.h rp_nlhe_frontier_payoffs): biased continuation rollouts from depth-limited leaves ----
     def frontier_payoffs(self, frontiers, bias=5.0, rollouts=16, seed=0, first_id=0, return_won=False):
