@@ -1081,6 +1081,96 @@ typedef struct rp_match_summary {
 } rp_match_summary;         /* 40 bytes */
 RP_API int rp_match_summarize(uint64_t n, const int16_t* won, rp_match_summary* out);
 
+/* SEARCH MATCHES: rp_nlhe_match in which a seat may re-solve every postflop decision — Agent<World<Blueprint>>,
+ * Agent<World<Depth<Blueprint>>> and their Dirac<..> forms (parlor/src/players/{brain,world,solved,dirac,agent}.rs) — on the device from
+ * the deal to the settlement, written as the same rp_aivat_hand records.  It answers "how many bb/100 does search buy over the
+ * blueprint".  Rounds of k_nl_search_advance / k_nl_search_compact / k_nl_world / k_nl_subgame (csrc/nlmc_search.hpp).
+ *
+ * EVERYTHING NOT ABOUT SEARCH IS rp_nlhe_match's CONTRACT, word for word: IDS AND RANDOM NUMBERS (the two counter streams of
+ *   match.seed, the deal and the mirror), THE GAME, THE KEY AT A DECISION, AGENTS (the three kinds, Edge's derived order), A REFUSED
+ *   PLAY, THE RECORD and the statuses.  Decision d of a hand reads rp_node_hash(match.seed, 1, hand_id, d) whatever its agent does
+ *   with it.  With search = {RP_SEARCH_NONE, RP_SEARCH_NONE} the four outputs are the bytes rp_nlhe_match writes.
+ * NO Depth<Blueprint>.  adapt_leaf solves from the witness's wipe state, in which both seats hold the hero's cards; the library
+ *   refuses that entry (RP_RECALL_CARDS: ENTRY above), and handing the solver the opponent's true hole would make the
+ *   agent clairvoyant.  World<Blueprint> (adapt_safe) and World<Depth<Blueprint>> (adapt_full) need no opponent hole and, by the
+ *   ADAPT_SAFE paragraph above, answer the same bits: RP_SEARCH_WORLD is both.
+ * A SEARCH SEAT.  search[s] = RP_SEARCH_WORLD with agent[s] = RP_AGENT_BLUEPRINT is Agent<World<..>>, with RP_AGENT_DIRAC
+ *   Agent<Dirac<World<..>>>, with RP_AGENT_FISH RP_ERR_INVALID.  Before the flop the seat reads its blueprint exactly as
+ *   rp_nlhe_match does (Brain::distrib, brain.rs:69-71).  At a postflop decision d of seat s, reading handle hs's table:
+ *   1 RECALL = {pov = s, hole = s's cards, draws = the streets dealt so far (0 beyond), stacks and dealer as the hand has them
+ *     (stacks as given: 0,0 kept), edges = the hand's whole history(): the edges the witness's counters are made of, Draws included}.
+ *   2 BELIEF AND SOLVE.  The belief is what rp_nlhe_belief answers for that recall on hs.  The entry is the rp_nlhe_frontier of
+ *     INTEGRATION.md's adapt_full: holes[s] only (the other 0), internal = s, draws, stacks, dealer and edges as the recall, prefix =
+ *     the history's trailing choice edges, first 12.  The solve is what rp_nlhe_subgame_solve answers for that one entry with that
+ *     belief, origin RP_NLHE_SUBGAME_ORIGIN_NONE (origin_mode 0, the reference as written) or the entry street - 1 (origin_mode 1),
+ *     the call's iterations, rollouts, bias and prior, seed = search_seed, and first_id = solve_id = hand_id * 256 + (d & 255),
+ *     wrapping — BIT FOR BIT: the search match answers what a caller composing the two public calls gets.
+ *   3 FALLBACK to the blueprint's policy (Solved's solve -> None arm), counted in unsolved[i] and coded in the step, the first of:
+ *     RP_SEARCH_FALLBACK_LENGTH (4) the history has more than RP_NLHE_MAX_HISTORY edges; RP_SEARCH_FALLBACK_CAP (5) the hand already
+ *     asked for RP_NLHE_SEARCH_MAX_SOLVES solves, both seats together — neither asks for a solve; then RP_SEARCH_FALLBACK_BELIEF (1)
+ *     the belief's status is not RP_RECALL_OK; RP_SEARCH_FALLBACK_SOLVE (2) the solve's status is not RP_RECALL_OK;
+ *     RP_SEARCH_FALLBACK_KEY (3) the result's (past, present, choices) is not the real decision's key — the entry is a replay of
+ *     edges and can part from the real chips after an off-grid play (the reference warns of this above subgame_descents).
+ *   4 BLEND (Solved::blend, solved.rs:133-152), per slot a of the infoset, f32, one rounding per operation, no contraction:
+ *     v = (float)visits[a]; w = v / (v + (float)visit_threshold); raw = w * refined[a] + (1.0f - w) * bp[a]; total = max(the left
+ *     fold of raw from 0.0f in Edge's derived order, RP_EPSILON); p[a] = raw / total.  bp is the match's RP_DIST_AVERAGED policy
+ *     (an absent row uniform).
+ *   5 CHOOSE from p by the blueprint agent's WeightedIndex rule in Edge order with the decision's draw, or by Dirac's last-maximal
+ *     rule; then actionize, then snap or the rejection rule, as rp_nlhe_match.
+ * ORDER INDEPENDENCE.  The pending solves of a round are compacted in an order that is the kernel's business; nothing a hand outputs
+ *   depends on it, on n, or on the batch around it: only the explicit solve_id identifies a solve.  A batch split into calls with
+ *   matching first_id answers the same bytes.
+ * OUTPUTS.  hands, won, rejected, status as rp_nlhe_match; searched[i] = the postflop decisions of search seats, saturating at 255;
+ *   unsolved[i] = those that fell back, likewise; both 0 for a hand without outputs.  steps[i][k], k < steps_cap: the hand's search
+ *   decisions in decision order — solve_id, the recall and the rp_nlhe_subgame_result as solved (both zero for fallbacks 4 and 5),
+ *   the belief's status, bp[9], p[9] (= bp after a fallback), seat, decision, the edge chosen from p, the fallback code — zero past
+ *   the hand's search decisions and zero for a hand without outputs.  Any output may be NULL.
+ * THE CALL.  The args are checked first, without a device and in this order: rp_nlhe_match's checks of `match`, search > 1, search
+ *   on a fish, origin_mode > 1, visit_threshold = 0, rp_nlhe_subgame_solve's checks of iterations / rollouts / bias / prior,
+ *   reserved0 != 0, steps == NULL with steps_cap > 0 — RP_ERR_INVALID; then n = 0 is RP_OK without a launch; then a NULL h0, or
+ *   handles on two devices or two encoders, RP_ERR_INVALID.  BOTH forms return when the match is finished: unlike
+ *   rp_nlhe_match_device, the _device form synchronises h0's stream — once per round, to read the round's count of solves — and only
+ *   keeps the outputs in DEVICE memory (args stay on the host).  Hands are played in chunks of 1 024, each chunk in at most
+ *   RP_NLHE_SEARCH_MAX_SOLVES + 2 rounds (every round but the last serves at least one solve of every unfinished hand; a chunk that
+ *   needs more is RP_ERR_HIP, not a spin).  SCRATCH is bounded independently of n by the chunk: about 2.4 KB per hand in flight plus
+ *   rp_nlhe_subgame_solve's overflow rows (168 bytes x 1 984 rows per solve of a launch), at most 345 MB; grow-only on h0, freed
+ *   with it.  Read-only on both tables exactly as rp_nlhe_policy. */
+typedef enum { RP_SEARCH_NONE = 0, RP_SEARCH_WORLD = 1 } rp_search_kind;
+typedef enum {
+    RP_SEARCH_SOLVED = 0, RP_SEARCH_FALLBACK_BELIEF = 1, RP_SEARCH_FALLBACK_SOLVE = 2, RP_SEARCH_FALLBACK_KEY = 3,
+    RP_SEARCH_FALLBACK_LENGTH = 4, RP_SEARCH_FALLBACK_CAP = 5
+} rp_search_fallback;
+#define RP_NLHE_SEARCH_MAX_SOLVES 48u /* per hand, both seats together */
+typedef struct rp_nlhe_search_args {
+    rp_nlhe_match_args match; /* every field with rp_nlhe_match's meaning and checks */
+    uint64_t search_seed;     /* the seed of every solve; never mixed with match.seed's two streams */
+    uint32_t iterations;      /* 1 .. RP_NLHE_DEPTH_MAX_ITERATIONS: stands in for the reference's 5 s deadline */
+    uint32_t rollouts;        /* as rp_nlhe_subgame_args */
+    float    bias, prior;     /* as rp_nlhe_subgame_args */
+    uint32_t visit_threshold; /* SubgameHyperParams::visit_threshold, >= 1 */
+    uint32_t steps_cap;       /* traced search decisions per hand, 0 = none */
+    uint8_t  search[2];       /* rp_search_kind of seat 0 / seat 1 */
+    uint8_t  origin_mode;     /* 0: RP_NLHE_SUBGAME_ORIGIN_NONE; 1: origin = the entry street - 1 */
+    uint8_t  reserved0[5];    /* 0 */
+} rp_nlhe_search_args;        /* 72 bytes */
+typedef struct rp_nlhe_search_step {
+    uint64_t solve_id;
+    rp_nlhe_recall recall;
+    rp_nlhe_subgame_result result;
+    float    bp[9], p[9];
+    uint32_t decision;        /* d, counting from 0 over both seats */
+    uint8_t  seat, edge, fallback /* rp_search_fallback */, belief_status;
+} rp_nlhe_search_step;        /* 352 bytes */
+/* rp_nlhe_match_args_default's match, no search seat, origin_mode 0, rp_nlhe_subgame_args_default's iterations / rollouts / bias /
+ * prior, visit_threshold 1 << 18, no trace, search_seed 0 */
+RP_API void rp_nlhe_search_args_default(rp_nlhe_search_args* out);
+RP_API int rp_nlhe_search_match(rp_nlhe* h0, rp_nlhe* h1, uint64_t n, const rp_nlhe_search_args* args /* host */, rp_aivat_hand* hands,
+                                int16_t* won, uint8_t* rejected, uint8_t* status, uint8_t* searched, uint8_t* unsolved,
+                                rp_nlhe_search_step* steps /* [n][steps_cap] or NULL */);
+RP_API int rp_nlhe_search_match_device(rp_nlhe* h0, rp_nlhe* h1, uint64_t n, const rp_nlhe_search_args* args /* host */,
+                                       rp_aivat_hand* hands_dev, int16_t* won_dev, uint8_t* rejected_dev, uint8_t* status_dev,
+                                       uint8_t* searched_dev, uint8_t* unsolved_dev, rp_nlhe_search_step* steps_dev);
+
 /* Multi-GPU (BASELINE configs[3]): trees sharded by rank (rank r samples tree ids [r*B, (r+1)*B) of a world*B-tree epoch
  * against a replicated table).  step_local: this rank's traversal reduced to one composed entry per infoset touched
  * (rp_profile_summarize's records, entry_bytes each, at most max_entries) plus the infoset KEY of every entry — each

@@ -51,6 +51,8 @@ RP_AIVAT_MAX_PLAYS = 48
 RP_AIVAT_WITNESS = 11
 PLAY = {"fold": 1, "call": 2, "check": 3, "raise": 4, "shove": 5}  # rp_aivat_play
 AGENT = {"blueprint": 0, "dirac": 1, "fish": 2}  # rp_agent_kind
+SEARCH = {"none": 0, "world": 1}  # rp_search_kind
+RP_NLHE_SEARCH_MAX_SOLVES = 48
 
 
 class Hyper(C.Structure):
@@ -93,6 +95,13 @@ class NlheMatchArgs(C.Structure):
                 ("hero", C.c_uint8), ("mirror", C.c_uint8), ("snap", C.c_uint8), ("board_mode", C.c_uint8), ("reserved", C.c_uint8 * 5)]
 
 
+class NlheSearchArgs(C.Structure):
+    """rp_nlhe_search_args: one per call (72 bytes)"""
+    _fields_ = [("match", NlheMatchArgs), ("search_seed", C.c_uint64), ("iterations", C.c_uint32), ("rollouts", C.c_uint32), ("bias", C.c_float),
+                ("prior", C.c_float), ("visit_threshold", C.c_uint32), ("steps_cap", C.c_uint32), ("search", C.c_uint8 * 2),
+                ("origin_mode", C.c_uint8), ("reserved0", C.c_uint8 * 5)]
+
+
 class MatchSummary(C.Structure):
     """rp_match_summary: the bb/100 figures of a series of winnings (40 bytes)"""
     _fields_ = [("hands", C.c_uint64), ("total_bb", C.c_double), ("bb_per_100", C.c_double), ("stddev", C.c_double), ("confidence", C.c_double)]
@@ -128,6 +137,12 @@ class NlheSubgameArgs(C.Structure):
 class NlheSubgameResult(C.Structure):
     """rp_nlhe_subgame_result: the Harvest of one solve over the four worlds, its counters and its deals' (176 bytes)"""
     _fields_ = NlheDepthResult._fields_ + [("drawn", C.c_uint32 * 4), ("attempts", C.c_uint64), ("fallbacks", C.c_uint32), ("pad2", C.c_uint32)]
+
+
+class NlheSearchStep(C.Structure):
+    """rp_nlhe_search_step: one traced search decision of a search match (352 bytes)"""
+    _fields_ = [("solve_id", C.c_uint64), ("recall", NlheRecall), ("result", NlheSubgameResult), ("bp", C.c_float * 9), ("p", C.c_float * 9),
+                ("decision", C.c_uint32), ("seat", C.c_uint8), ("edge", C.c_uint8), ("fallback", C.c_uint8), ("belief_status", C.c_uint8)]
 
 
 class NlheSubgameRow(C.Structure):
@@ -412,6 +427,9 @@ _SIGNATURES = {
     "rp_nlhe_match_args_default": (None, [C.POINTER(NlheMatchArgs)]),
     "rp_nlhe_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(NlheMatchArgs)] + [C.c_void_p] * 4),
     "rp_nlhe_match_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(NlheMatchArgs)] + [C.c_void_p] * 4),
+    "rp_nlhe_search_args_default": (None, [C.POINTER(NlheSearchArgs)]),
+    "rp_nlhe_search_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(NlheSearchArgs)] + [C.c_void_p] * 7),
+    "rp_nlhe_search_match_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(NlheSearchArgs)] + [C.c_void_p] * 7),
     "rp_match_summarize": (C.c_int, [C.c_uint64, C.c_void_p, C.POINTER(MatchSummary)]),
     "rp_nlhe_partition": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
     "rp_nlhe_partition_device": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),

@@ -40,6 +40,7 @@
 #include "nlmc_subgame.hpp"
 #include "nlmc_aivat.hpp"
 #include "nlmc_match.hpp"
+#include "nlmc_search.hpp"
 #include "../../include/rp_libm_glibc.h"
 #include "rp_internal.h"
 #include "sortscan.hpp"
@@ -124,6 +125,10 @@ struct rp_nlhe {
     size_t depth_rows_bytes = 0;
     void* subgame_rows = nullptr;  // rp_nlhe_subgame_solve: likewise, its own region
     size_t subgame_rows_bytes = 0;
+    void* search_scratch = nullptr;  // rp_nlhe_search_match: the hands in flight, the request lists and the solves' answers (grow-only)
+    size_t search_scratch_bytes = 0;
+    NsmPost* search_post = nullptr;      // pinned, mapped host memory: the round's counts of solves (k_nl_search_compact)
+    NsmPost* search_post_dev = nullptr;  // the same words as the device addresses them
     uint32_t grid_cap = 16384;  // workgroups of the grid-stride kernels (measured: 1024 -14 %, 4096 -4 %)
 };
 
@@ -573,7 +578,8 @@ int rp_nlhe_destroy(rp_nlhe* h) {
     }
     for (void* p : h->allocs) (void)hipFree(p);
     if (h->post) (void)hipHostFree(h->post);
-    for (void* p : {h->x_keys, h->x_counts, h->x_all, h->x_packed, h->depth_rows, h->subgame_rows})
+    if (h->search_post) (void)hipHostFree(h->search_post);
+    for (void* p : {h->x_keys, h->x_counts, h->x_all, h->x_packed, h->depth_rows, h->subgame_rows, h->search_scratch})
         if (p) (void)hipFree(p);
     delete h;
     return RP_OK;
@@ -1574,28 +1580,62 @@ int rp_aivat_summarize(uint64_t n, const float* adjusted, float raw_stddev, rp_a
 
 // ---- matches (nlmc_match.hpp): one lane per hand, at most NR_CHUNK hands per launch
 namespace {
-int nm_check(const rp_nlhe* h0, const rp_nlhe* h1, const rp_nlhe_match_args* a) {
-    if (!h0) return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: NULL handle");
-    if (!a) return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: NULL args");
+// the args alone, without a device; `name`: the un-suffixed function that refuses
+int nm_args_check(const char* name, const rp_nlhe_match_args* a) {
     if (a->agent[0] > (uint8_t)RP_AGENT_FISH || a->agent[1] > (uint8_t)RP_AGENT_FISH)
-        return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: agent %u / %u is no rp_agent_kind", a->agent[0], a->agent[1]);
-    if (a->dealer > 2u) return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: dealer %u above 2", a->dealer);
-    if (a->hero > 1u) return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: hero %u above 1", a->hero);
-    if (a->mirror > 1u || a->snap > 1u || a->board_mode > 1u)
-        return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: mirror, snap and board_mode are 0 or 1");
+        return rp::fail(RP_ERR_INVALID, "%s: agent %u / %u is no rp_agent_kind", name, a->agent[0], a->agent[1]);
+    if (a->dealer > 2u) return rp::fail(RP_ERR_INVALID, "%s: dealer %u above 2", name, a->dealer);
+    if (a->hero > 1u) return rp::fail(RP_ERR_INVALID, "%s: hero %u above 1", name, a->hero);
+    if (a->mirror > 1u || a->snap > 1u || a->board_mode > 1u) return rp::fail(RP_ERR_INVALID, "%s: mirror, snap and board_mode are 0 or 1", name);
     const bool std_stacks = a->stacks[0] == 0 && a->stacks[1] == 0;
     if (!std_stacks && (a->stacks[0] <= 0 || a->stacks[1] <= 0))
-        return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: stacks %d, %d are neither 0,0 nor both positive", a->stacks[0], a->stacks[1]);
+        return rp::fail(RP_ERR_INVALID, "%s: stacks %d, %d are neither 0,0 nor both positive", name, a->stacks[0], a->stacks[1]);
     for (uint8_t r : a->reserved)
-        if (r != 0u) return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: reserved must be 0");
+        if (r != 0u) return rp::fail(RP_ERR_INVALID, "%s: reserved must be 0", name);
+    return RP_OK;
+}
+// two handles play on one device and one encoder
+int nm_pair_check(const char* name, const rp_nlhe* h0, const rp_nlhe* h1) {
     if (h1 && h1 != h0) {
-        if (h1->device != h0->device) return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: the two handles are on devices %d and %d", h0->device, h1->device);
+        if (h1->device != h0->device) return rp::fail(RP_ERR_INVALID, "%s: the two handles are on devices %d and %d", name, h0->device, h1->device);
         bool same = h1->prm.encoder == h0->prm.encoder;
         for (int s = 0; s < 4 && same && h0->prm.encoder; ++s)
             same = h1->prm.tkeys[s] == h0->prm.tkeys[s] && h1->prm.tabs[s] == h0->prm.tabs[s] && h1->prm.tn[s] == h0->prm.tn[s];
-        if (!same) return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: the two handles are built on different encoders");
+        if (!same) return rp::fail(RP_ERR_INVALID, "%s: the two handles are built on different encoders", name);
     }
     return RP_OK;
+}
+int nm_check(const rp_nlhe* h0, const rp_nlhe* h1, const rp_nlhe_match_args* a) {
+    if (!h0) return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: NULL handle");
+    if (!a) return rp::fail(RP_ERR_INVALID, "rp_nlhe_match: NULL args");
+    int rc = nm_args_check("rp_nlhe_match", a);
+    return rc ? rc : nm_pair_check("rp_nlhe_match", h0, h1);
+}
+// what h1's stream has queued for its table comes before what is queued on st next
+int nm_after(hipStream_t st, hipStream_t st1) {
+    if (st1 == st) return RP_OK;
+    hipEvent_t ev;
+    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, st1);
+    if (e == hipSuccess) e = hipStreamWaitEvent(st, ev, 0);
+    (void)hipEventDestroy(ev);  // the wait already queued keeps what it needs
+    HIP_TRY(e);
+    return RP_OK;
+}
+NmArgs nm_args(const rp_nlhe_match_args* args, uint64_t at, uint32_t m, rp_aivat_hand* hands, int16_t* won, uint8_t* rejected, uint8_t* status) {
+    NmArgs q{};
+    q.deal_hash = rp_node_hash_step(args->seed, 0);
+    q.play_hash = rp_node_hash_step(args->seed, 1);
+    q.first_id = args->first_id + at;
+    q.n = m;
+    q.stacks[0] = args->stacks[0], q.stacks[1] = args->stacks[1];
+    q.agent[0] = args->agent[0], q.agent[1] = args->agent[1];
+    q.dealer = args->dealer, q.hero = args->hero, q.mirror = args->mirror, q.snap = args->snap, q.board_mode = args->board_mode;
+    q.hands = nl_at(hands, at);
+    q.won = nl_at(won, at);
+    q.rejected = nl_at(rejected, at);
+    q.status = nl_at(status, at);
+    return q;
 }
 }  // namespace
 
@@ -1615,27 +1655,9 @@ int rp_nlhe_match_device(rp_nlhe* h0, rp_nlhe* h1, uint64_t n, const rp_nlhe_mat
     if (!h1) h1 = h0;
     HIP_TRY(hipSetDevice(h0->device));
     hipStream_t st = rp::profile_stream(h0->prof), st1 = rp::profile_stream(h1->prof);
-    if (st1 != st) {  // what h1's stream has queued for its table comes first
-        hipEvent_t ev;
-        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        hipError_t e = hipEventRecord(ev, st1);
-        if (e == hipSuccess) e = hipStreamWaitEvent(st, ev, 0);
-        (void)hipEventDestroy(ev);  // the wait already queued keeps what it needs
-        HIP_TRY(e);
-    }
+    if ((rc = nm_after(st, st1))) return rc;
     return nl_chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
-        NmArgs q{};
-        q.deal_hash = rp_node_hash_step(args->seed, 0);
-        q.play_hash = rp_node_hash_step(args->seed, 1);
-        q.first_id = args->first_id + at;
-        q.n = m;
-        q.stacks[0] = args->stacks[0], q.stacks[1] = args->stacks[1];
-        q.agent[0] = args->agent[0], q.agent[1] = args->agent[1];
-        q.dealer = args->dealer, q.hero = args->hero, q.mirror = args->mirror, q.snap = args->snap, q.board_mode = args->board_mode;
-        q.hands = nl_at(hands, at);
-        q.won = nl_at(won, at);
-        q.rejected = nl_at(rejected, at);
-        q.status = nl_at(status, at);
+        const NmArgs q = nm_args(args, at, m, hands, won, rejected, status);
         hipLaunchKernelGGL(k_nl_match, dim3((m + NM_BLOCK - 1u) / NM_BLOCK), dim3(NM_BLOCK), 0, st, h0->tab, h1->tab, h0->prm, q);
     });
 }
@@ -1672,6 +1694,182 @@ int rp_match_summarize(uint64_t n, const int16_t* won, rp_match_summary* out) {
     }
     out->confidence = 1.96 * out->stddev / sqrt(nf) * 100.0;
     return RP_OK;
+}
+
+}  // extern "C"
+
+// ---- search matches (nlmc_search.hpp): NSM_CHUNK hands in flight, played in rounds; one synchronisation per round
+namespace {
+constexpr uint32_t NSM_MAX_ROUNDS = RP_NLHE_SEARCH_MAX_SOLVES + 2u;  // a hand parks once per solve, and ends in the round after its last
+int nsm_check(const rp_nlhe_search_args* a, const void* steps, uint32_t* rollouts) {
+    const char* name = "rp_nlhe_search_match";
+    if (!a) return rp::fail(RP_ERR_INVALID, "%s: NULL args", name);
+    int rc = nm_args_check(name, &a->match);
+    if (rc) return rc;
+    for (int s = 0; s < 2; ++s)  // both seats' kinds before either seat's fish, as the header orders them
+        if (a->search[s] > (uint8_t)RP_SEARCH_WORLD) return rp::fail(RP_ERR_INVALID, "%s: search %u of seat %d is no rp_search_kind", name, a->search[s], s);
+    for (int s = 0; s < 2; ++s)
+        if (a->search[s] != 0u && a->match.agent[s] == (uint8_t)RP_AGENT_FISH) return rp::fail(RP_ERR_INVALID, "%s: seat %d is a fish: it reads no table to search from", name, s);
+    if (a->origin_mode > 1u) return rp::fail(RP_ERR_INVALID, "%s: origin_mode %u above 1", name, a->origin_mode);
+    if (a->visit_threshold == 0u) return rp::fail(RP_ERR_INVALID, "%s: visit_threshold must be at least 1", name);
+    rp_nlhe_subgame_args sub{};
+    sub.iterations = a->iterations, sub.rollouts = a->rollouts, sub.bias = a->bias, sub.prior = a->prior;
+    if ((rc = nd_args_check(name, &sub, rollouts))) return rc;
+    for (uint8_t r : a->reserved0)
+        if (r != 0u) return rp::fail(RP_ERR_INVALID, "%s: reserved must be 0", name);
+    if (a->steps_cap > 0u && !steps) return rp::fail(RP_ERR_INVALID, "%s: NULL steps with steps_cap > 0", name);
+    return RP_OK;
+}
+// the grow-only scratch of a chunk, carved 16-byte aligned
+struct NsmScratch {
+    NsHand* hands;
+    NsmLists lists;
+    uint8_t* hole_world;
+    float* weights;
+    uint8_t* belief_status;
+    rp_nlhe_subgame_result* results;
+    size_t bytes;
+    explicit NsmScratch(unsigned char* base) {
+        size_t at = 0;
+        auto take = [&](size_t b) {
+            unsigned char* p = base ? base + at : nullptr;
+            at += (b + 15) & ~(size_t)15;
+            return p;
+        };
+        hands = reinterpret_cast<NsHand*>(take(sizeof(NsHand) * NSM_CHUNK));
+        lists.recalls = reinterpret_cast<rp_nlhe_recall*>(take(sizeof(rp_nlhe_recall) * NSM_CHUNK));
+        lists.entries = reinterpret_cast<rp_nlhe_frontier*>(take(sizeof(rp_nlhe_frontier) * NSM_CHUNK));
+        lists.ids = reinterpret_cast<uint64_t*>(take(sizeof(uint64_t) * NSM_CHUNK));
+        lists.origin = reinterpret_cast<int8_t*>(take(NSM_CHUNK));
+        hole_world = take((size_t)RP_NLHE_MAX_HOLES * NSM_CHUNK);
+        weights = reinterpret_cast<float*>(take(sizeof(float) * RP_NLHE_WORLDS * NSM_CHUNK));
+        belief_status = take(NSM_CHUNK);
+        results = reinterpret_cast<rp_nlhe_subgame_result*>(take(sizeof(rp_nlhe_subgame_result) * NSM_CHUNK));
+        bytes = at;
+    }
+};
+static_assert(NSM_CHUNK <= NS_CHUNK && NSM_CHUNK <= NR_CHUNK, "a round's solves of one seat are one launch of each kernel");
+}  // namespace
+
+extern "C" {
+
+void rp_nlhe_search_args_default(rp_nlhe_search_args* out) {
+    if (!out) return;
+    *out = rp_nlhe_search_args{};
+    rp_nlhe_match_args_default(&out->match);
+    rp_nlhe_subgame_args sub;
+    rp_nlhe_subgame_args_default(&sub);
+    out->iterations = sub.iterations, out->rollouts = sub.rollouts, out->bias = sub.bias, out->prior = sub.prior;
+    out->visit_threshold = 1u << 18;  // SubgameHyperParams::default
+}
+
+int rp_nlhe_search_match_device(rp_nlhe* h0, rp_nlhe* h1, uint64_t n, const rp_nlhe_search_args* args, rp_aivat_hand* hands, int16_t* won,
+                                uint8_t* rejected, uint8_t* status, uint8_t* searched, uint8_t* unsolved, rp_nlhe_search_step* steps) {
+    uint32_t rollouts = 0;
+    int rc = nsm_check(args, steps, &rollouts);
+    if (rc || n == 0) return rc;
+    if (!h0) return rp::fail(RP_ERR_INVALID, "rp_nlhe_search_match: NULL handle");
+    if ((rc = nm_pair_check("rp_nlhe_search_match", h0, h1))) return rc;
+    if (!h1) h1 = h0;
+    HIP_TRY(hipSetDevice(h0->device));
+    hipStream_t st = rp::profile_stream(h0->prof);
+    if ((rc = nm_after(st, rp::profile_stream(h1->prof)))) return rc;
+    if (!h0->search_post) {
+        void *hp_ = nullptr, *dp_ = nullptr;
+        if (hipHostMalloc(&hp_, sizeof(NsmPost), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+            hipHostGetDevicePointer(&dp_, hp_, 0) != hipSuccess) {
+            if (hp_) (void)hipHostFree(hp_);
+            return rp::fail(RP_ERR_HIP, "rp_nlhe_search_match: no pinned host memory for the rounds' counts");
+        }
+        memset(hp_, 0, sizeof(NsmPost));
+        h0->search_post = reinterpret_cast<NsmPost*>(hp_);
+        h0->search_post_dev = reinterpret_cast<NsmPost*>(dp_);
+    }
+    if ((rc = nl_grow(h0->search_scratch, h0->search_scratch_bytes, NsmScratch(nullptr).bytes, st))) return rc;
+    const NsmScratch sc(static_cast<unsigned char*>(h0->search_scratch));
+    const bool any_search = args->search[0] != 0u || args->search[1] != 0u;
+    if (any_search) {  // the overflow rows of one launch's solves, as rp_nlhe_subgame_solve_device sizes them
+        const size_t need = (size_t)std::min<uint64_t>(NSM_CHUNK, n) * NS_ROWS_OVF * sizeof(NdRow);
+        if ((rc = nl_grow(h0->subgame_rows, h0->subgame_rows_bytes, need, st))) return rc;
+    }
+    rp_nlhe* seat[2] = {h0, h1};
+    for (uint64_t at = 0; at < n; at += NSM_CHUNK) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(NSM_CHUNK, n - at);
+        NsmArgs q{};
+        q.match = nm_args(&args->match, at, m, hands, won, rejected, status);
+        q.search[0] = args->search[0], q.search[1] = args->search[1];
+        q.origin_mode = args->origin_mode;
+        q.visit_threshold = args->visit_threshold;
+        q.steps_cap = steps ? args->steps_cap : 0u;
+        q.hands = sc.hands;
+        q.searched = nl_at(searched, at);
+        q.unsolved = nl_at(unsolved, at);
+        q.steps = q.steps_cap ? steps + at * args->steps_cap : nullptr;
+        q.results = sc.results;
+        q.belief_status = sc.belief_status;
+        bool finished = false;
+        for (uint32_t round = 0; round < NSM_MAX_ROUNDS && !finished; ++round) {
+            q.first = round == 0u ? 1u : 0u;
+            hipLaunchKernelGGL(k_nl_search_advance, dim3((m + NM_BLOCK - 1u) / NM_BLOCK), dim3(NM_BLOCK), 0, st, h0->tab, h1->tab, h0->prm, q);
+            HIP_TRY(hipGetLastError());
+            if (!any_search) {  // no hand can park
+                finished = true;
+                break;
+            }
+            hipLaunchKernelGGL(k_nl_search_compact, dim3(1), dim3(NSM_SCAN), 0, st, sc.hands, m, sc.lists, h0->search_post_dev);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(st));  // the one wait of the round: how many solves it asks for
+            const uint32_t count[2] = {h0->search_post->count[0], h0->search_post->count[1]};
+            if (count[0] + count[1] > m) return rp::fail(RP_ERR_HIP, "rp_nlhe_search_match: %u + %u solves posted for %u hands", count[0], count[1], m);
+            if (count[0] + count[1] == 0u) {
+                finished = true;
+                break;
+            }
+            for (uint32_t s = 0, lo = 0; s < 2u; lo += count[s], ++s) {
+                if (count[s] == 0u) continue;
+                NwArgs w{};
+                w.recalls = sc.lists.recalls + lo;
+                w.weights = sc.weights + (size_t)lo * RP_NLHE_WORLDS;
+                w.hole_world = sc.hole_world + (size_t)lo * RP_NLHE_MAX_HOLES;
+                w.status = sc.belief_status + lo;
+                hipLaunchKernelGGL(k_nl_world, dim3(count[s]), dim3(NW_BLOCK), 0, st, seat[s]->tab, seat[s]->prm, w);
+                HIP_TRY(hipGetLastError());
+                NsArgs v{};
+                v.entries = sc.lists.entries + lo;
+                v.hole_world = w.hole_world;
+                v.weights = w.weights;
+                v.origin = args->origin_mode ? sc.lists.origin + lo : nullptr;
+                v.iterations = args->iterations;
+                v.rollouts = rollouts;
+                v.bias = args->bias;
+                v.prior = args->prior;
+                v.step_hash_rollout = rp_node_hash_step(args->search_seed, 0);
+                v.step_hash_deal = rp_node_hash_step(args->search_seed, 1);
+                v.step_hash_tree = rp_node_hash_step(args->search_seed, 2);
+                v.ids = sc.lists.ids + lo;
+                v.overflow = static_cast<NdRow*>(h0->subgame_rows);
+                v.results = sc.results + lo;
+                hipLaunchKernelGGL(k_nl_subgame, dim3(count[s]), dim3(NS_BLOCK), 0, st, seat[s]->tab, seat[s]->prm, v);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+        if (!finished) return rp::fail(RP_ERR_HIP, "rp_nlhe_search_match: hands still waiting for solves after %u rounds", NSM_MAX_ROUNDS);
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return RP_OK;
+}
+
+int rp_nlhe_search_match(rp_nlhe* h0, rp_nlhe* h1, uint64_t n, const rp_nlhe_search_args* args, rp_aivat_hand* hands, int16_t* won, uint8_t* rejected,
+                         uint8_t* status, uint8_t* searched, uint8_t* unsolved, rp_nlhe_search_step* steps) {
+    uint32_t rollouts = 0;
+    int rc = nsm_check(args, steps, &rollouts);
+    if (rc || n == 0) return rc;
+    if (!h0) return rp::fail(RP_ERR_INVALID, "rp_nlhe_search_match: NULL handle");
+    if ((rc = nm_pair_check("rp_nlhe_search_match", h0, h1))) return rc;
+    Stage s(h0);
+    s.out(hands, n).out(won, n).out(rejected, n).out(status, n).out(searched, n).out(unsolved, n).out(steps, n * args->steps_cap);
+    if ((rc = s.up()) || (rc = rp_nlhe_search_match_device(h0, h1, n, args, hands, won, rejected, status, searched, unsolved, steps))) return rc;
+    return s.down();
 }
 
 }  // extern "C"

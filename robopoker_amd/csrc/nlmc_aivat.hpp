@@ -50,8 +50,8 @@ struct NaCounts {
         sub = 0;
         sub_len = sub_aggr = act_aggr = 0;
     }
-    // the action joins the history as the edge history() gives it on the game BEFORE the action
-    __device__ __forceinline__ void note(const G2& g, const NlAction& a) {
+    // the action joins the history as the edge history() gives it on the game BEFORE the action; -> that edge
+    __device__ __forceinline__ uint32_t note(const G2& g, const NlAction& a) {
         const uint32_t e = nl_edgify(g, a, (int)run.aggr);
         run.push(e);
         if (sub_len < 12u) {
@@ -59,6 +59,7 @@ struct NaCounts {
             sub_aggr += (e == NE_SHOVE || e >= NE_OPEN0) ? 1u : 0u;
         }
         act_aggr += (a.kind == NA_RAISE || a.kind == NA_SHOVE) ? 1u : 0u;
+        return e;
     }
     // a street was dealt into the witness game
     __device__ __forceinline__ void dealt() {

@@ -148,54 +148,74 @@ __device__ __forceinline__ uint32_t nm_choose(const float* dist, uint64_t choice
     return edge;
 }
 
-__global__ __launch_bounds__(NM_BLOCK) void k_nl_match(NlTable t0, NlTable t1, NlParams p, NmArgs q) {
-    const uint32_t i = blockIdx.x * NM_BLOCK + threadIdx.x;
-    if (i >= q.n) return;
-    const uint64_t hand_id = q.first_id + i;
-    rp_aivat_hand* rec = q.hands ? q.hands + i : nullptr;
-    // the record starts as zeros: the plays past n_plays, and everything of a hand that ends without outputs
+// one hand between two of its steps: the game, the witness's counters, the nine cards and the counters of the loop.  k_nl_match keeps it
+// in registers from the deal to the settlement; the search match (nlmc_search.hpp) parks it in device memory at a search decision
+struct NmHand {
+    G2 g;
+    NaCounts w;
+    uint64_t hole0, hole1, flop, turn_card, river;
+    uint32_t status, n_plays, rejected, streets, decision, step, dealer;
+    int won;
+};
+
+// what a search seat adds to the loop (nlmc_search.hpp); here: nothing, and every call folds away
+struct NmNoSearch {
+    __device__ __forceinline__ bool seat(int) const { return false; }
+    __device__ __forceinline__ bool decide(const NmHand&, int, int, uint64_t, uint32_t, uint32_t, float*) { return true; }
+    __device__ __forceinline__ void chose(uint32_t) {}
+    __device__ __forceinline__ void edge(uint32_t) {}
+};
+
+// the record starts as zeros (the plays past n_plays, and everything of a hand that ends without outputs); the deal; the game
+__device__ __forceinline__ void nm_begin(NmHand& h, const NmArgs& q, uint64_t hand_id, rp_aivat_hand* rec) {
     if (rec) {
         uint4* z = reinterpret_cast<uint4*>(rec);
 #pragma unroll
         for (uint32_t k = 0; k < sizeof(rp_aivat_hand) / 16u; ++k) z[k] = make_uint4(0u, 0u, 0u, 0u);
     }
-
-    uint64_t hole0, hole1, flop, turn_card, river;
-    nm_deal(q.deal_hash, q.mirror ? hand_id >> 1 : hand_id, &hole0, &hole1, &flop, &turn_card, &river);
+    nm_deal(q.deal_hash, q.mirror ? hand_id >> 1 : hand_id, &h.hole0, &h.hole1, &h.flop, &h.turn_card, &h.river);
     if (q.mirror && (hand_id & 1ull)) {
-        const uint64_t x = hole0;
-        hole0 = hole1;
-        hole1 = x;
+        const uint64_t x = h.hole0;
+        h.hole0 = h.hole1;
+        h.hole1 = x;
     }
-    const uint32_t dealer = q.dealer == 2u ? (uint32_t)(hand_id & 1ull) : (uint32_t)q.dealer;
-    G2 g;
-    nrp_from_start(g, dealer, q.stacks, hole0, hole1);
-    NaCounts w;
-    w.run.clear();
-    w.street_begins();
+    h.dealer = q.dealer == 2u ? (uint32_t)(hand_id & 1ull) : (uint32_t)q.dealer;
+    nrp_from_start(h.g, h.dealer, q.stacks, h.hole0, h.hole1);
+    h.w.run.clear();
+    h.w.street_begins();
+    h.status = RP_RECALL_ILLEGAL;  // what the step bound leaves
+    h.n_plays = h.rejected = h.streets = h.decision = h.step = 0;
+    h.won = 0;
+}
 
+// the hand's loop, from where it stands to its end (true) or to a search decision that waits for its solve (false: nothing of the
+// decision is consumed, the same call takes it up again).  The one copy of the loop body: k_nl_match and k_nl_search_advance
+template <typename Search>
+__device__ __forceinline__ bool nm_play(NmHand& h, const NlTable& t0, const NlTable& t1, const NlParams& p, const NmArgs& q, uint64_t hand_id,
+                                        rp_aivat_hand* rec, Search& search) {
+    G2& g = h.g;
+    NaCounts& w = h.w;
     const uint64_t play_hash = rp_node_hash_tree(q.play_hash, hand_id);
     const DistParams none{1.0f, 0.0f, 0.0f};  // RP_DIST_AVERAGED reads no hyper-parameter
-    uint32_t status = RP_RECALL_ILLEGAL;      // what the step bound leaves
-    uint32_t n_plays = 0, rejected = 0, streets = 0, decision = 0, err = 0;
-    int won = 0;
-    for (uint32_t step = 0; step < NF_MAX_STEPS; ++step) {
+    uint32_t err = 0;
+    for (; h.step < NF_MAX_STEPS; ++h.step) {
         const int turn = g.turn();
         if (turn == NT_TERMINAL) {
             int reward[2];
             nl_settle(g, reward);
-            won = g.at(reward, (int)q.hero) - g.at(g.spent, (int)q.hero);  // Settlement::won
-            status = n_plays > RP_AIVAT_MAX_PLAYS ? (uint32_t)RP_RECALL_LENGTH : (uint32_t)RP_RECALL_OK;
+            h.won = g.at(reward, (int)q.hero) - g.at(g.spent, (int)q.hero);  // Settlement::won
+            h.status = h.n_plays > RP_AIVAT_MAX_PLAYS ? (uint32_t)RP_RECALL_LENGTH : (uint32_t)RP_RECALL_OK;
             break;
         }
         if (turn == NT_CHANCE) {
             const int s = g.street();
-            g.force_act(NlAction{NA_DRAW, 0, s == 0 ? flop : (s == 1 ? turn_card : river)});
+            g.force_act(NlAction{NA_DRAW, 0, s == 0 ? h.flop : (s == 1 ? h.turn_card : h.river)});
             w.dealt();
-            streets = (uint32_t)s + 1u;
+            search.edge(NE_DRAW);
+            h.streets = (uint32_t)s + 1u;
             continue;
         }
-        const uint64_t draw = rp_node_hash_key(play_hash, decision++);  // read whether the agent uses it or not
+        const uint64_t draw = rp_node_hash_key(play_hash, h.decision);  // read whether the agent uses it or not
         const uint32_t agent = turn ? q.agent[1] : q.agent[0];
         const NlView v = nl_view(g);
         NlAction act;
@@ -208,7 +228,7 @@ __global__ __launch_bounds__(NM_BLOCK) void k_nl_match(NlTable t0, NlTable t1, N
             const uint64_t c0 = g.cards[0], c1 = g.cards[1];
             const uint32_t present = nl_bucket(p, v.street, turn ? c1 : c0, g.board, &err);
             if (err) {
-                status = RP_RECALL_LOOKUP;
+                h.status = RP_RECALL_LOOKUP;
                 break;
             }
             NlTable t;  // the actor's table: both sets of pointers are kernel arguments, the actor selects
@@ -221,49 +241,71 @@ __global__ __launch_bounds__(NM_BLOCK) void k_nl_match(NlTable t0, NlTable t1, N
 #pragma unroll
             for (uint32_t a = 0; a < NLMC_A; ++a) wt[a] = found ? wt[a] : 0.0f;
             policy_distribution<NLMC_A>((int)RP_DIST_AVERAGED, none, wt, nch, dist);
-            act = nl_actionize(g, nm_choose(dist, choices, nch, agent == (uint32_t)RP_AGENT_DIRAC, draw), 0ull);
+            // a search seat past the flop: the blend of its solve's harvest and the blueprint takes dist's place
+            if (search.seat(turn) && v.street > 0 && !search.decide(h, turn, v.street, choices, nch, present, dist)) return false;
+            const uint32_t e = nm_choose(dist, choices, nch, agent == (uint32_t)RP_AGENT_DIRAC, draw);
+            search.chose(e);
+            act = nl_actionize(g, e, 0ull);
         }
+        h.decision += 1u;
         if (q.snap) {
             act = g.snap(act);
             if (!g.allowed(act)) break;
         } else if (!g.allowed(act)) {  // rejected; the seat times out into passive()
             act = g.passive();
-            rejected = min(rejected + 1u, 255u);
+            h.rejected = min(h.rejected + 1u, 255u);
         }
-        if (rec && n_plays < RP_AIVAT_MAX_PLAYS) {
-            rec->kind[n_plays] = (uint8_t)act.kind;
-            rec->chips[n_plays] = (int16_t)((act.kind == NA_FOLD || act.kind == NA_CHECK) ? 0 : act.chips);
+        if (rec && h.n_plays < RP_AIVAT_MAX_PLAYS) {
+            rec->kind[h.n_plays] = (uint8_t)act.kind;
+            rec->chips[h.n_plays] = (int16_t)((act.kind == NA_FOLD || act.kind == NA_CHECK) ? 0 : act.chips);
         }
-        n_plays += 1u;
-        w.note(g, act);
+        h.n_plays += 1u;
+        search.edge(w.note(g, act));
         g.force_act(act);
     }
+    return true;
+}
 
-    const bool outputs = status == RP_RECALL_OK || status == RP_RECALL_LENGTH;
+// the hand's outputs; -> whether it has any (a hand refused on the way leaves zeros)
+__device__ __forceinline__ bool nm_finish(const NmHand& h, const NmArgs& q, uint32_t i, rp_aivat_hand* rec) {
+    const bool outputs = h.status == RP_RECALL_OK || h.status == RP_RECALL_LENGTH;
     if (rec) {
         if (outputs) {
-            rec->hole[0] = hole0;
-            rec->hole[1] = hole1;
-            rec->draws[0] = streets > 0u ? flop : 0ull;
-            rec->draws[1] = streets > 1u ? turn_card : 0ull;
-            rec->draws[2] = streets > 2u ? river : 0ull;
+            rec->hole[0] = h.hole0;
+            rec->hole[1] = h.hole1;
+            rec->draws[0] = h.streets > 0u ? h.flop : 0ull;
+            rec->draws[1] = h.streets > 1u ? h.turn_card : 0ull;
+            rec->draws[2] = h.streets > 2u ? h.river : 0ull;
             rec->stacks[0] = q.stacks[0];
             rec->stacks[1] = q.stacks[1];
             rec->seat = q.hero;
-            rec->dealer = (uint8_t)dealer;
-            rec->n_plays = (uint8_t)min(n_plays, RP_AIVAT_MAX_PLAYS);
+            rec->dealer = (uint8_t)h.dealer;
+            rec->n_plays = (uint8_t)min(h.n_plays, RP_AIVAT_MAX_PLAYS);
             rec->board_mode = q.board_mode;
         } else {  // the plays made so far are taken back
-            const uint32_t made = min(n_plays, RP_AIVAT_MAX_PLAYS);
+            const uint32_t made = min(h.n_plays, RP_AIVAT_MAX_PLAYS);
             for (uint32_t k = 0; k < made; ++k) {
                 rec->kind[k] = 0;
                 rec->chips[k] = 0;
             }
         }
     }
-    if (q.won) q.won[i] = outputs ? (int16_t)won : (int16_t)0;
-    if (q.rejected) q.rejected[i] = outputs ? (uint8_t)rejected : (uint8_t)0;
-    if (q.status) q.status[i] = (uint8_t)status;
+    if (q.won) q.won[i] = outputs ? (int16_t)h.won : (int16_t)0;
+    if (q.rejected) q.rejected[i] = outputs ? (uint8_t)h.rejected : (uint8_t)0;
+    if (q.status) q.status[i] = (uint8_t)h.status;
+    return outputs;
+}
+
+__global__ __launch_bounds__(NM_BLOCK) void k_nl_match(NlTable t0, NlTable t1, NlParams p, NmArgs q) {
+    const uint32_t i = blockIdx.x * NM_BLOCK + threadIdx.x;
+    if (i >= q.n) return;
+    const uint64_t hand_id = q.first_id + i;
+    rp_aivat_hand* rec = q.hands ? q.hands + i : nullptr;
+    NmHand h;
+    NmNoSearch none;
+    nm_begin(h, q, hand_id, rec);
+    nm_play(h, t0, t1, p, q, hand_id, rec, none);
+    nm_finish(h, q, i, rec);
 }
 
 }  // namespace rp

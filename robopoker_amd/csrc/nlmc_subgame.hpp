@@ -52,6 +52,7 @@ struct NsArgs {
     uint64_t step_hash_deal;     // rp_node_hash_step(seed, 1): rp_nlhe_restrict's stream
     uint64_t step_hash_tree;     // rp_node_hash_step(seed, 2)
     uint64_t first_id;
+    const uint64_t* ids;  // [n] the id of every solve, or NULL (the public entry points): solve i is first_id + i
     NdRow* overflow;  // [n][NS_ROWS_OVF]
     rp_nlhe_subgame_result* results;
     rp_nlhe_subgame_row* rows;    // [n][rows_cap], may be NULL
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(NS_BLOCK) void k_nl_subgame(NlTable t, NlParams p, 
     int16_t* s_won = reinterpret_cast<int16_t*>(s_buf);
     uint16_t* s_rank = reinterpret_cast<uint16_t*>(s_buf);
     const uint32_t i = blockIdx.x, tid = threadIdx.x;
-    const uint64_t id = q.first_id + i;  // wrapping
+    const uint64_t id = q.ids ? q.ids[i] : q.first_id + i;  // wrapping
 
     if (tid == 0) {
         // the hole of the seat opposite `internal` is no input: that seat holds nothing until the first deal

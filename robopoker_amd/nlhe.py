@@ -42,6 +42,10 @@ SUBGAME_DEAL_DTYPE = np.dtype([("hole", "<u8"), ("world", "u1"), ("pad", "u1"), 
 assert SUBGAME_RESULT_DTYPE.itemsize == C.sizeof(_lib.NlheSubgameResult) == 176 and SUBGAME_ROW_DTYPE.itemsize == C.sizeof(_lib.NlheSubgameRow) == 168
 assert SUBGAME_DEAL_DTYPE.itemsize == C.sizeof(_lib.NlheSubgameDeal) == 16 and C.sizeof(_lib.NlheSubgameArgs) == 48
 ORIGIN_NONE = _lib.RP_NLHE_SUBGAME_ORIGIN_NONE
+SEARCH_STEP_DTYPE = np.dtype([("solve_id", "<u8"), ("recall", RECALL_DTYPE), ("result", SUBGAME_RESULT_DTYPE), ("bp", "<f4", (A,)), ("p", "<f4", (A,)),
+                              ("decision", "<u4"), ("seat", "u1"), ("edge", "u1"), ("fallback", "u1"),
+                              ("belief_status", "u1")])  # rp_nlhe_search_step, 352 bytes
+assert SEARCH_STEP_DTYPE.itemsize == C.sizeof(_lib.NlheSearchStep) == 352 and C.sizeof(_lib.NlheSearchArgs) == 72
 WORLDS, MAX_REJECTIONS, WORLD_NONE, MAX_DEALS = _lib.RP_NLHE_WORLDS, _lib.RP_NLHE_MAX_REJECTIONS, _lib.RP_WORLD_NONE, 4096
 
 
@@ -480,6 +484,56 @@ class NlheSolver:
                    rejected=torch.empty(n, dtype=torch.uint8, device=d), status=torch.empty(n, dtype=torch.uint8, device=d))
         _lib.check(self._lib.rp_nlhe_match_device(self._h, opponent._h if opponent is not None else None, n, C.byref(a),
                                                   *[_dptr(out[k], n) for k in ("hands", "won", "rejected", "status")]))
+        return out
+
+    # ---- search matches (include/rp_mi355x.h rp_nlhe_search_match): a seat may re-solve every postflop decision ----
+    @staticmethod
+    def _search_args(search=("none", "none"), origin_mode=0, iterations=None, rollouts=None, bias=None, prior=None, visit_threshold=None,
+                     steps_cap=0, search_seed=0, **match):
+        """rp_nlhe_search_args; ``search``: "none" / "world" (or rp_search_kind codes) of seat 0 and seat 1; the library's defaults where
+        an argument is None; everything else is ``_match_args``'s"""
+        a = _lib.NlheSearchArgs()
+        _lib.load().rp_nlhe_search_args_default(C.byref(a))
+        a.match = NlheSolver._match_args(**match)
+        a.search[0], a.search[1] = (_lib.SEARCH[k] if isinstance(k, str) else k for k in search)
+        a.origin_mode, a.steps_cap, a.search_seed = int(origin_mode), int(steps_cap), search_seed
+        for k, v in (("iterations", iterations), ("rollouts", rollouts), ("visit_threshold", visit_threshold)):
+            if v is not None:
+                setattr(a, k, int(v))
+        for k, v in (("bias", bias), ("prior", prior)):
+            if v is not None:
+                setattr(a, k, v)
+        return a
+
+    def search_match(self, n, opponent=None, **args):
+        """``match`` in which a seat may be a search agent (``Agent<World<Blueprint>>``, with "dirac" its Dirac form): at every postflop
+        decision the seat builds the opponent's range from its own table (``belief``), re-solves the rest of the street
+        (``subgame_solve`` with ``iterations``, ``rollouts``, ``bias``, ``prior``, ``search_seed`` and the id ``hand_id * 256 + decision``)
+        and plays the blend of the harvest and its blueprint by visit counts (``visit_threshold``).  ``args``: ``match``'s, plus search,
+        origin_mode (0: no frontier; 1: the entry street - 1), steps_cap (traced decisions per hand).  -> ``match``'s dict plus
+        searched uint8[n], unsolved uint8[n] (search decisions that fell back to the blueprint) and steps
+        SEARCH_STEP_DTYPE[n, steps_cap].  Read-only on both tables."""
+        a, n = self._search_args(**args), int(n)
+        out = dict(hands=np.zeros(n, AIVAT_DTYPE), won=np.zeros(n, np.int16), rejected=np.zeros(n, np.uint8), status=np.zeros(n, np.uint8),
+                   searched=np.zeros(n, np.uint8), unsolved=np.zeros(n, np.uint8))
+        steps = np.zeros((max(n, 1), a.steps_cap), SEARCH_STEP_DTYPE)  # a trace is asked for with an address, even for an empty batch
+        _lib.check(self._lib.rp_nlhe_search_match(self._h, opponent._h if opponent is not None else None, n, C.byref(a),
+                                                  *[_p(out[k]) for k in ("hands", "won", "rejected", "status", "searched", "unsolved")],
+                                                  _p(steps) if a.steps_cap else None))
+        out["steps"] = steps[:n]
+        return out
+
+    def search_match_device(self, n, opponent=None, **args):
+        """rp_nlhe_search_match_device: -> the same dict of device tensors (hands uint8[n, 192], steps uint8[n, steps_cap, 352]).  Unlike
+        ``match_device`` the call returns when the match is finished: it waits on the solver's stream once per round of solves"""
+        a, n, d = self._search_args(**args), int(n), torch.device("cuda", self.device)
+        out = dict(hands=torch.empty((n, AIVAT_DTYPE.itemsize), dtype=torch.uint8, device=d), won=torch.empty(n, dtype=torch.int16, device=d))
+        out.update({k: torch.empty(n, dtype=torch.uint8, device=d) for k in ("rejected", "status", "searched", "unsolved")})
+        steps = torch.empty((max(n, 1), a.steps_cap, SEARCH_STEP_DTYPE.itemsize), dtype=torch.uint8, device=d)  # an address even for n = 0
+        _lib.check(self._lib.rp_nlhe_search_match_device(self._h, opponent._h if opponent is not None else None, n, C.byref(a),
+                                                         *[_dptr(out[k], n) for k in ("hands", "won", "rejected", "status", "searched", "unsolved")],
+                                                         _dptr(steps, a.steps_cap)))
+        out["steps"] = steps[:n]
         return out
 
     @staticmethod
