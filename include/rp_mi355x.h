@@ -1111,6 +1111,10 @@ RP_API int rp_match_summarize(uint64_t n, const int16_t* won, rp_match_summary* 
  *     the belief's status is not RP_RECALL_OK; RP_SEARCH_FALLBACK_SOLVE (2) the solve's status is not RP_RECALL_OK;
  *     RP_SEARCH_FALLBACK_KEY (3) the result's (past, present, choices) is not the real decision's key — the entry is a replay of
  *     edges and can part from the real chips after an off-grid play (the reference warns of this above subgame_descents).
+ *     Codes 4 and 5 are guards no hand has been seen to reach: in 900 000 model hands between blueprint and Dirac seats, stacks up
+ *     to 32 767, a seat that could search met at most 21 edges of history and a hand at most 14 such decisions (pot-fraction raises
+ *     grow the pot geometrically and a street admits few); with a fish, whose minimum raises grow it linearly, 13 000 hands met at
+ *     most 18 and 7, and no bound is claimed (tests/test_nlhe_search_model.py, test_every_case_occurs).
  *   4 BLEND (Solved::blend, solved.rs:133-152), per slot a of the infoset, f32, one rounding per operation, no contraction:
  *     v = (float)visits[a]; w = v / (v + (float)visit_threshold); raw = w * refined[a] + (1.0f - w) * bp[a]; total = max(the left
  *     fold of raw from 0.0f in Edge's derived order, RP_EPSILON); p[a] = raw / total.  bp is the match's RP_DIST_AVERAGED policy
@@ -1120,6 +1124,11 @@ RP_API int rp_match_summarize(uint64_t n, const int16_t* won, rp_match_summary* 
  * ORDER INDEPENDENCE.  The pending solves of a round are compacted in an order that is the kernel's business; nothing a hand outputs
  *   depends on it, on n, or on the batch around it: only the explicit solve_id identifies a solve.  A batch split into calls with
  *   matching first_id answers the same bytes.
+ * PINNED WHILE THE POT FITS AN int16.  match.stacks are admitted up to 32 767 each, but the CPU models this call is tested against keep
+ *   chips in int16, as the reference does: at stacks of 24 000 and of 32 767 each their chips wrap in a solve's tree (a raise over a
+ *   shove leaves a negative stack, the next node offers no edge) and they refuse, RP_RECALL_ILLEGAL, solves that this library answers
+ *   RP_RECALL_OK and plays.  None of 360 model hands at stacks 600 to 16 384 differed.  Which side matches the reference where
+ *   stacks[0] + stacks[1] passes 32 767 is undecided; nothing is tested there.
  * OUTPUTS.  hands, won, rejected, status as rp_nlhe_match; searched[i] = the postflop decisions of search seats, saturating at 255;
  *   unsolved[i] = those that fell back, likewise; both 0 for a hand without outputs.  steps[i][k], k < steps_cap: the hand's search
  *   decisions in decision order — solve_id, the recall and the rp_nlhe_subgame_result as solved (both zero for fallbacks 4 and 5),

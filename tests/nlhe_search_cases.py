@@ -6,7 +6,11 @@ The blueprints are nlhe_match_cases.Rows — decided key by key as the model ask
 whole Encounter a solver warm-starts from and without that module's cap of 960 rows (a solve asks for every infoset of its tree; the
 table is sized from what was asked).  Seat 0 reads table 0, seat 1 table 1.  Batches are tiny — 9 hands, 2 or 3 iterations, one
 rollout, stacks (40, 25) so that the trees stay under RP_NLHE_DEPTH_MAX_NODES — and visit_threshold is 2, so that the blend moves the
-policy.  The seeds and first ids were found by search with the model; the CPU test asserts what the search was for."""
+policy.  The seeds and first ids were found by search with the model; the CPU test asserts what the search was for.  The model's
+answers take about 12 s to compute.
+
+No batch here holds RP_SEARCH_FALLBACK_SOLVE (a solve refused after a belief that was not): tests/test_gpu_nlhe_search_chunks.py pins
+it on lookup-table encoders; what a search on the hash encoder met is written in tests/test_nlhe_search_model.py::test_every_case_occurs."""
 import numpy as np
 
 import nlhe_depth_model as DM

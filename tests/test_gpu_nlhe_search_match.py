@@ -264,6 +264,42 @@ def test_a_hand_refused_after_a_search_decision_takes_its_steps_back(gpu, monkey
                     st["solve_id"], st["decision"], st["seat"], st["edge"], XM.BELIEF) and steps[k]["belief_status"] != MM.OK, (i, k)
                 n = len(st["bp"])
                 assert steps[k]["bp"][:n].tobytes() == np.array(st["bp"], np.float32).tobytes() and steps[k]["p"].tobytes() == steps[k]["bp"].tobytes()
+    # A trace shorter than the uncapped one.  steps_cap = 1: a refused hand takes back exactly its one record and writes nothing past
+    # it.  steps_cap = 0 with a trace address all the same: the hand has taken more search decisions than the cap (1 > 0), nothing of
+    # the trace is touched, searched and unsolved are zeroed.  The _device form on a trace allocated for one hand more, pre-filled:
+    # the extra row is untouched.  What stays unreached is the take-back's min(n_steps, steps_cap) with n_steps > steps_cap > 0: no
+    # hand of 12 000 ids is refused after TWO search decisions of seat 0 — seat 1 is refused at its first turn in between.
+    import ctypes as C
+    import itertools
+
+    from robopoker_amd import _lib
+    from robopoker_amd.nlhe import _dptr
+
+    d = torch.device("cuda", pair[0].device)
+    for (i, w, back), cap in itertools.product(zip(REFUSED_IDS, want, taken_back), (1, 0)):
+        a = NlheSolver._search_args(**dict(kw, first_id=i, steps_cap=cap))
+        steps = torch.full((2, 1, SEARCH_STEP_DTYPE.itemsize), 0xA5, dtype=torch.uint8, device=d)
+        counts = torch.full((2, 2), 0xA5, dtype=torch.uint8, device=d)  # searched, unsolved
+        torch.cuda.current_stream(d).synchronize()
+        _lib.check(_lib.load().rp_nlhe_search_match_device(pair[0]._h, pair[1]._h, 1, C.byref(a), None, None, None, None, _dptr(counts[0], 1),
+                                                           _dptr(counts[1], 1), _dptr(steps, 1)))
+        got, counts = steps.cpu().numpy(), counts.cpu().numpy()
+        assert (got[1] == 0xA5).all() and (counts[:, 1] == 0xA5).all(), i
+        first = got[0].reshape(-1).view(SEARCH_STEP_DTYPE)[0]
+        if back or w["status"] != MM.OK:
+            assert not counts[:, 0].any() and (not got[0].any() if cap else (got[0] == 0xA5).all()), (i, cap)
+            continue
+        assert tuple(counts[:, 0]) == (w["searched"], w["unsolved"]), i  # the uncapped counts
+        if cap == 0:
+            assert (got[0] == 0xA5).all(), i
+            continue
+        if not w["steps"]:
+            assert not got[0].any(), i
+            continue
+        st = w["steps"][0]
+        assert (first["solve_id"], first["decision"], first["seat"], first["edge"], first["fallback"]) == (
+            st["solve_id"], st["decision"], st["seat"], st["edge"], XM.BELIEF) and first["belief_status"] != MM.OK, i
+        assert first["bp"][: len(st["bp"])].tobytes() == np.array(st["bp"], np.float32).tobytes() and first["p"].tobytes() == first["bp"].tobytes()
     for s in pair:
         s.close()
     for t in tables:

@@ -5,6 +5,7 @@ import numpy as np
 import nlhe_match_model as MM
 import nlhe_search_cases as SC
 import nlhe_search_model as XM
+import nlhe_search_replay as RP
 from robopoker_amd import _lib
 
 F = np.float32
@@ -55,8 +56,34 @@ def test_every_case_occurs():
         assert [w["unsolved"] for w in hands] == [sum(s["fallback"] != XM.SOLVED for s in w["steps"]) for w in hands]
     # a solved decision on each postflop street
     assert {len(s["recall"].draws) for s in every if s["fallback"] == XM.SOLVED} == {1, 2, 3}
-    # the fallbacks the batches can reach; LENGTH and CAP need about fifty edges or solves in one hand and are in none
+    # The fallbacks the batches can reach.
+    # SOLVE (a solve refused after a belief that was not) is in none of these batches, which are played on the hash encoder: it is
+    # pinned on lookup-table encoders, against the replay model, by tests/test_gpu_nlhe_search_chunks.py
+    # (test_a_solve_refused_after_a_belief_that_was_not: RP_RECALL_LOOKUP from a frontier's rollout, origin_mode 1).  On the hash encoder
+    # no route was found.  Searched with the full model, both seats searching, 2 iterations, per solve (the counters add up over the
+    # two trees, the caps are per tree):
+    #   origin_mode 0 — 1 140 hands at stacks (0, 0) and 60 to 16 384: every solve RP_RECALL_OK; at most 104 nodes (RP_DEPTH_NODES: 384
+    #     a tree), 19 infosets (96 a tree), 19 rows (RP_DEPTH_ROWS: 2 048 a solve).
+    #   origin_mode 1 — 2 450 hands at (0, 0), 60 and 100: every solve RP_RECALL_OK; at most 205 nodes, 26 infosets, 26 rows and 22
+    #     frontiers (RP_DEPTH_FRONTIERS: 32 a tree; 22 is the largest seen in the 264 solves that were counted).
+    #   RP_DEPTH_ROWS by iterations — the first solve of 5 hands at 256 iterations: 419 to 708 rows of 2 048, in 2.2 to 3.9 s of
+    #     model time each; the rows flatten, and the 5 s a config may cost is used up long before the cap.
+    #   The raises a street admits bound the sampled tree well below every cap.
+    # At stacks 24 000 and 32 767 the MODEL refuses solves (RP_RECALL_ILLEGAL) that the library plays: in the oracle's int16 chips a
+    # raise over a shove wraps to a negative stack and the next node offers no edge.  The header states it (PINNED WHILE THE POT FITS
+    # AN int16); those hands pin nothing and are in no batch.
+    # LENGTH and CAP need 49 edges of history or 49 solves in one hand and are in none.  Searched with nlhe_match_model.play, no
+    # solves, seed 7, stacks (32 767, 32 767), (32 767, 3 000) and (0, 0), dealer alternating: 100 000 ids for each of blueprint v
+    # blueprint (snap off and on) and blueprint v dirac — 900 000 hands — met at most 21 edges at a postflop decision of a seat that
+    # could search and at most 14 such decisions in a hand; 13 000 hands with a fish on one seat (blueprint or dirac on the other,
+    # snap off and on) at most 18 and 7.  Pot-fraction raises grow the pot by a quarter at least, and a street admits few of them
+    # (the largest sampled tree above): between two table agents the history is bounded far below 49.  A fish raises the minimum,
+    # which grows the pot linearly — hands of 32 767 decisions and more were met at those stacks — so no bound is claimed against a
+    # fish; none of those hands had a search seat's postflop decision past 18 edges.
     assert {s["fallback"] for s in every} == {XM.SOLVED, XM.BELIEF, XM.KEY}
+    # the trace cap: hands of "both" and "deep" have three search decisions or more, so that a steps_cap of 1 and of one below the most
+    # end the trace before the hand (tests/test_gpu_nlhe_search_chunks.py)
+    assert all(max(len(w["steps"]) for w in m.want[name]) >= 3 for name in ("both", "deep"))
     fish = SC.config("world fish")[2]
     assert fish.agents[1] == MM.FISH and not fish.snap and any(s["fallback"] == XM.KEY for s in steps["world fish"])
     assert any(s["fallback"] == XM.BELIEF and s["belief_status"] != MM.OK for s in steps["world fish"])
@@ -81,6 +108,22 @@ def test_every_case_occurs():
             assert all(s["solve_id"] == (first + i) * 256 + s["decision"] for s in w["steps"])
     assert len({s["solve_id"] for s in steps["both"]}) == len(steps["both"])
     assert (1 << m.cap_log2) >= 2 * max(t[0].size for t in m.tables)
+
+
+def test_the_big_batch_fills_the_scan_in_its_first_round():
+    """what tests/test_gpu_nlhe_search_chunks.py's 1 089 hands are for, as far as it can be said without a solve: the first round of a
+    chunk asks for the first search decision of every hand that has one, and a hand gets there on its blueprint alone"""
+    big = RP.big_batch()
+    seat0, seat1 = big["first"]
+    assert seat0 > 256 and seat1 > 256  # every thread of the 256-thread scan holds a request; seat 1's list starts past seat 0's
+    assert seat0 + seat1 <= RP.CHUNK and RP.BIG_N == RP.CHUNK + 64 + 1 and big["args"].first_id == SC.config("both")[2].first_id
+    assert big["sargs"].steps_cap == RP.BIG_CAP < 3 and tuple(big["sargs"].search) == (XM.WORLD, XM.WORLD)
+    # the blueprints are nlhe_search_cases' with passive preflop rows added, none taken away or changed
+    for mine, theirs in zip(big["tables"], SC.model().tables):
+        n = theirs[0].size
+        assert mine[0].size > n and all(np.array_equal(a[:n], b) for a, b in zip(mine[:3], theirs[:3])) and mine[3][:n].tobytes() == theirs[3].tobytes()
+        assert len(set(zip(mine[0].tolist(), mine[1].tolist(), mine[2].tolist()))) == mine[0].size
+    assert (1 << big["cap_log2"]) >= 2 * max(t[0].size for t in big["tables"])
 
 
 def test_the_packed_steps_hold_the_models():
