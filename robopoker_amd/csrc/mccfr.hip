@@ -481,7 +481,7 @@ size_t chunk_maps_lds_bytes(const rp_mccfr* h) {
 size_t traverse_maps_lds_bytes(const rp_mccfr* h) {
     const size_t NI = h->tbl.n_infos;
     const size_t masks = h->S != RP_SAMPLING_EXTERNAL ? (size_t)h->maxdec * 256 * 4 : 0;  // the expanded edges of every list entry
-    return (NI * 8 + 2 * NI) * 4 + NI * 8 * 2 + (NI + (NI & 1)) * 2 + (size_t)5 * (h->maxdec * 256 + h->cell_pad) * 4 + masks;
+    return (NI * 8 + 2 * NI) * 4 + NI * 8 * 2 + (NI + (NI & 1)) * 2 + 2 * NI * 4 + (size_t)3 * (h->maxdec * 256 + h->cell_pad) * 4 + masks;
 }
 static_assert(CH_THREADS <= 256u, "k_traverse_maps_static packs (infoset, rank of the infoset) into the 16 bits of an `order` entry");
 // rank_max <= 64: one wavefront builds the chunk's lists, a lane per infoset of the walker (Kuhn 6, Leduc 60; a skeleton game with more

@@ -350,7 +350,11 @@ __device__ __forceinline__ uint32_t static_traverse(const DevGame& g, const DevI
     uint32_t ridx[N];              // chance: the row index of its group = the outcomes on the path, mixed radix, root first
     uint32_t pick[N];              // chance: the sampled outcome; opponent: the sampled action; walker (PRUNED): the surviving edges
     bool live[N];
-    float sg0[N], sg1[N], q0[N], q1[N];   // (sigma, q) of a player node's two edges
+    float sg0[N], sg1[N];  // walker: the sigmas of the node's two edges
+    // opponent: (sigma, q) of the SAMPLED edge alone.  The other edge leads to dead nodes only, and what a dead node computes is dropped
+    // by a select on live[], never by a multiplication (the sweeps, the leaf pairs; ancestor_reach is read under live[j], whose
+    // chain holds sampled edges only): the dead sub-tree carries the wrong factor and nothing reads it
+    float sgp[N], qp[N];
     // the exclusive pair: the opponent's pick selects lo, and the two chance nodes' own liveness (live[hi] becomes the merged one)
     bool sel_lo = false, live_lo = false, live_hi = false;
     // every draw of this tree: rp_node_hash(seed, epoch, tree, key) with the (seed, epoch, tree) part hashed once
@@ -445,17 +449,21 @@ __device__ __forceinline__ uint32_t static_traverse(const DevGame& g, const DevI
         } else if constexpr (SK::S.kind[s] == SK_P0 || SK::S.kind[s] == SK_P1) {
             const uint32_t info = ry[s];
             const char* const ir = irows + info * 32u;  // DevInfoTab::row2: {sigma0, sigma1, q0, q1, total, cum0, keep, 0}
-            const float4 f = *reinterpret_cast<const float4*>(ir);
-            sg0[s] = f.x;
-            sg1[s] = f.y;
-            q0[s] = f.z;
-            q1[s] = f.w;
             if constexpr (SK::S.kind[s] == K_OPP) {  // WeightedIndex over max(q, EPSILON): two actions = one threshold
+                const float4 f = *reinterpret_cast<const float4*>(ir);
                 const float2 tc = *reinterpret_cast<const float2*>(ir + 16);  // (total, cum[0])
                 const float x = REF ? rp_ref_draw_weight(rp_ref_seed_finish(&p.ref_info[info], tree_id), tc.x)
                                     : rp_u01(rp_node_hash_key(th, info)) * tc.x;
-                pick[s] = tc.y <= x ? 1u : 0u;
-            } else if constexpr (PRUNED) {  // SamplingScheme::sample at a walker node (d_sample_mask_tab, the same draw and masks)
+                const bool e1 = tc.y <= x;
+                pick[s] = e1 ? 1u : 0u;
+                sgp[s] = e1 ? f.y : f.x;
+                qp[s] = e1 ? f.w : f.z;
+            } else {  // a walker node's q take no part in anything
+                const float2 f = *reinterpret_cast<const float2*>(ir);
+                sg0[s] = f.x;
+                sg1[s] = f.y;
+            }
+            if constexpr (SK::S.kind[s] == K_WALKER && PRUNED) {  // SamplingScheme::sample at a walker node (d_sample_mask_tab: same draw, same masks)
                 uint32_t mask = 3u;
                 bool prune = true;
                 if (p.S == RP_SAMPLING_PLURIBUS)
@@ -505,14 +513,13 @@ __device__ __forceinline__ uint32_t static_traverse(const DevGame& g, const DevI
                 float r = 1.0f, sm = 1.0f;
                 if constexpr (ROWS && SK::S.kind[n] == SK_TERMINAL && SK::S.kind[par] == K_OPP && sk_leaf_pair<G>(par)) {
                     // the opponent's two terminal children: the unsampled one is dead, so the sampled one's r / sm * payoff is the
-                    // only value that enters the parent's sum — computed with the edge's factors selected, added once
+                    // only value that enters the parent's sum — computed with the sampled edge's factors and payoff, added once
                     if constexpr (e == 1) {
                         const bool e1 = pick[ap] != 0u;
-                        const float s_0 = sg0[ap], s_1 = sg1[ap], q_0 = q0[ap], q_1 = q1[ap];
                         constexpr int sib = EX::at(sk_child<G>(par, 0));
                         const uint32_t p_0 = pay[sib], p_1 = pay[an];
-                        r = rel[ap] * (e1 ? s_1 : s_0);
-                        sm = smp[ap] * (e1 ? q_1 : q_0);
+                        r = rel[ap] * sgp[ap];
+                        sm = smp[ap] * qp[ap];
                         const float v = r / sm * rp_u2f(e1 ? p_1 : p_0);
                         acc[ap] = live[ap] ? acc[ap] + v : acc[ap];
                     }
@@ -522,9 +529,9 @@ __device__ __forceinline__ uint32_t static_traverse(const DevGame& g, const DevI
                     r = rel[ap];
                     sm = smp[ap];
                     if constexpr (SK::S.kind[par] == K_WALKER) r = r * (e ? sg1[ap] : sg0[ap]);
-                    if constexpr (SK::S.kind[par] == K_OPP) {
-                        r = r * (e ? sg1[ap] : sg0[ap]);
-                        sm = sm * (e ? q1[ap] : q0[ap]);
+                    if constexpr (SK::S.kind[par] == K_OPP) {  // the sampled edge's: n is dead if it hangs below the other
+                        r = r * sgp[ap];
+                        sm = sm * qp[ap];
                     }
                 }
                 if constexpr (BOTH && n == EX::LO) {  // kept for hi
@@ -570,9 +577,9 @@ __device__ __forceinline__ uint32_t static_traverse(const DevGame& g, const DevI
                     // is n on the parent chain of j (n == j or an ancestor)?  pre-order: n <= j <= end[n]
                     if constexpr (n <= j && j <= SK::S.end[n]) {
                         constexpr int par = SK::S.parent[n];
-                        if constexpr (SK::S.kind[par] == K_OPP) {
-                            cf = cf * (SK::S.edge[n] ? sg1[par] : sg0[par]);
-                            sm_ = sm_ * (SK::S.edge[n] ? q1[par] : q0[par]);
+                        if constexpr (SK::S.kind[par] == K_OPP) {  // j live: its chain holds sampled edges only
+                            cf = cf * sgp[par];
+                            sm_ = sm_ * qp[par];
                         }
                     }
                 }
@@ -585,13 +592,14 @@ __device__ __forceinline__ uint32_t static_traverse(const DevGame& g, const DevI
                     constexpr int fh = sk_outer_edge(SK::S, K_OPP, EX::HI, decltype(Q)::value);
                     if constexpr (fl >= 0 || fh >= 0) {
                         float cl = 1.0f, ql = 1.0f, ch = 1.0f, qh = 1.0f;
+                        // j live: the selected alternative is live, and the edges above it are sampled ones
                         if constexpr (fl >= 0) {
-                            cl = (fl & 1) ? sg1[fl >> 1] : sg0[fl >> 1];
-                            ql = (fl & 1) ? q1[fl >> 1] : q0[fl >> 1];
+                            cl = sgp[fl >> 1];
+                            ql = qp[fl >> 1];
                         }
                         if constexpr (fh >= 0) {
-                            ch = (fh & 1) ? sg1[fh >> 1] : sg0[fh >> 1];
-                            qh = (fh & 1) ? q1[fh >> 1] : q0[fh >> 1];
+                            ch = sgp[fh >> 1];
+                            qh = qp[fh >> 1];
                         }
                         cf = cf * (sel_lo ? cl : ch);
                         sm_ = sm_ * (sel_lo ? ql : qh);
@@ -654,18 +662,26 @@ __global__ __launch_bounds__(256) void k_traverse_static(DevGame g, DevInfoTab i
 // reach HBM.  What k_chunk_maps does with the Decisions it reads back (per-infoset, tree-ordered lists by LDS bitmap +
 // prefix popcount; one sequential composition per (infoset, cell) from the identity: include/rp_mi355x.h "Composed
 // update") happens here on the values as they are produced: the lists' places are known once the trees are sampled
-// (on_built), each Decisions drops its five values (two regret deltas, two weight deltas, the payoff) at its place in LDS,
+// (on_built), each Decisions drops its three values (two regret deltas, the payoff) at its place in LDS — its two weight deltas
+// are the same for every entry of the infoset's list (the infoset's sigmas, the epoch): the first entry leaves the two sigmas in
+// `wsig`, and the chain's lane makes the delta of them once —
 // and the chains of ALL cells run side by side, one thread per (infoset, cell).  Same lists, same order, same operations
 // as k_chunk_maps: the chunk's row of block maps (bmap_index) is bit-identical (tests/test_gpu_mccfr.py).
 // A chain is sequential and as long as its list (a root infoset meets a third of the chunk's trees, a river infoset a few):
 // the (infoset, cell) tasks are handed out in descending order of list length (a counting sort by log2 class), so the 64
 // chains of a wave have similar lengths instead of every wave waiting for one long chain.  Only the walker's infosets have
 // lists: `order` holds those alone (rank_count[W] entries), and pre / lcount / lbase are written for them alone.
-// LDS (dynamic): bits u32[NI][8] | lcount u32[NI] | lbase u32[NI] | pre u16[NI][8] | order u16[NI + (NI & 1)] | vals f32[5][maxdec * 256 + lpad]
+// LDS (dynamic): bits u32[NI][8] | lcount u32[NI] | lbase u32[NI] | pre u16[NI][8] | order u16[NI + (NI & 1)] | wsig f32[NI][2]
+//                | vals f32[3][maxdec * 256 + lpad]
 //                | (PRUNED) lmask u32[maxdec * 256]: the expanded edges of every list entry — a regret cell skips the entries
 //                  whose edge was pruned (no touch at all: a touch would apply the discount), as k_chunk_maps<true> does
+// Workgroups per CU the registers are allocated for (__launch_bounds__).  With three value cells five workgroups fit in LDS (Leduc,
+// external sampling: 26 436 B each), and the kernel is a latency kernel: counter draws under external sampling take the 96 VGPRs of five
+// waves per SIMD, at the price of 14 - 20 spilled registers (60 - 84 B of scratch), and run 8 % faster for it than at four without scratch
+// (DESIGN.md §3 "Five workgroups per CU").  The pruned samplings and the reference draws spill hundreds of bytes at 128 already: four.
+constexpr int tm_workgroups(bool pruned, bool ref) { return (!pruned && !ref) ? 5 : 4; }
 template <class G, int W, bool PRUNED, bool REF>
-__global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevInfoTab it, StepParams p, Map* bmaps,
+__global__ __launch_bounds__(256, tm_workgroups(PRUNED, REF)) void k_traverse_maps_static(DevGame g, DevInfoTab it, StepParams p, Map* bmaps,
                                                               uint32_t maxdec, uint32_t lpad) {
     extern __shared__ __attribute__((aligned(16))) uint32_t tm_lds[];
     static_assert(SM_WORDS == 8u, "a bitmap row is two 16-byte LDS reads, its prefix counts two 8-byte writes");
@@ -679,16 +695,17 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
     uint32_t* lbase = lcount + NI;
     uint16_t* pre = reinterpret_cast<uint16_t*>(lbase + NI);
     uint16_t* order = pre + NI * SM_WORDS;
-    float* vals = reinterpret_cast<float*>(order + NI + (NI & 1u));
-    // places per cell.  The five chains of an infoset read vals[c L + base + e] in the same instruction: with L a multiple of 32 they
-    // share a bank (a 5-way conflict at every step); lpad = 7 words moves the cells apart (measured round 4, profiles/r04_optin_ab.json:
-    // pads 0 / 3 / 7 / 13 within 1 % of each other — the conflicts were not the limiter)
+    float* wsig = reinterpret_cast<float*>(order + NI + (NI & 1u));
+    float* vals = wsig + 2u * NI;
+    // places per cell.  The chains of an infoset read vals[k L + base + e], k = 0 .. 2, in the same instruction (a weight lane reads its
+    // regret neighbour's word: a broadcast): with L a multiple of 32 the three share a bank (a 3-way conflict at every step); lpad = 7
+    // words moves the cells apart (measured round 4 with five cells, profiles/r04_optin_ab.json: pads 0 / 3 / 7 / 13 within 1 % of
+    // each other — the conflicts were not the limiter)
     const uint32_t L = maxdec * 256u + lpad;
-    uint32_t* lmask = reinterpret_cast<uint32_t*>(vals + 5u * L);
+    uint32_t* lmask = reinterpret_cast<uint32_t*>(vals + 3u * L);
     for (uint32_t e = lt; e < NI * SM_WORDS; e += 256u) bits[e] = 0;
     __syncthreads();
     const uint32_t lane = chunk * 256u + lt;
-    const float tf = (float)p.epoch;
     uint32_t ndec = 0;
     auto on_built =
         [&](auto info_of, auto live_of) __attribute__((always_inline)) {
@@ -734,15 +751,19 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
             }
             __syncthreads();
         };
+    // the sigmas of a Decisions are row2[info].x/.y, the same two floats for every entry of the infoset's list: the first entry alone
+    // keeps them, for the weight chains
     auto on_decision =
         [&](auto, uint32_t info, float g0, float g1, float s0, float s1, float payoff, uint32_t mask) __attribute__((always_inline)) {
-            const uint32_t pos = lbase[info] + list_rank(bits, pre, info, lt);
+            const uint32_t at = list_rank(bits, pre, info, lt), pos = lbase[info] + at;
+            if (at == 0u) {
+                wsig[2u * info] = s0;
+                wsig[2u * info + 1u] = s1;
+            }
             if constexpr (PRUNED) lmask[pos] = mask;
             vals[pos] = g0;
             vals[L + pos] = g1;
-            vals[2u * L + pos] = weight_delta(p.W, s0, tf);
-            vals[3u * L + pos] = weight_delta(p.W, s1, tf);
-            vals[4u * L + pos] = payoff;
+            vals[2u * L + pos] = payoff;
             ndec += 1u;
         };
     const uint64_t tree_id = p.tree_base + lane;
@@ -751,7 +772,11 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
                                : static_traverse<G, W, PRUNED, REF, false>(g, it, p, tree_id, present, on_built, on_decision);
     __syncthreads();
     // the chains of an infoset's list: two regret cells, two weight cells, the payoff sum.  Both discounts are uniform over the grid:
-    // branched on once, around the whole phase
+    // branched on once, around the whole phase.  A weight cell's delta is the same for every entry of its list — weight_delta of the
+    // infoset's sigma, which every tree of the step read from row2[info], and of the epoch — so its lane computes it once, from the
+    // sigma the list's first entry left in wsig (an empty list leaves none, and touches nothing), and touches with the register: the
+    // operand, the operation and the order of per-entry values
+    const float tf = (float)p.epoch;
     const ChainParams cpr = chain_params(p, true, tf), cpw = chain_params(p, false, tf);
     if (cpr.d == 1.0f && cpw.d == 1.0f) {
         // unit discounts (Summed / Floored regret with Constant / Linear / Quadratic weight): five lanes per infoset — regret 0, 1,
@@ -761,12 +786,20 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
         // the final 0.0f + b gives the empty list its 0.0f (b of the identity).  Its m is ignored.
         const uint32_t ln = lt & 63u, sub = ln / 5u, c = ln - 5u * sub;
         const float fl = c < 2u ? cpr.fl : (c < 4u ? cpw.fl : rp_u2f(0xff800000u));
+        const bool isw = c == 2u || c == 3u;
+        const uint32_t cell = c == 4u ? 2u : c & 1u;  // a weight lane's reads land on its regret neighbour's word and are not used
         for (uint32_t i = (lt >> 6) * 12u + sub; ln < 60u && i < nr; i += 4u * 12u) {
             const uint32_t info = order[i] & 255u, rank = order[i] >> 8;
             const uint32_t n = lcount[info], base = lbase[info];
-            const float* v = vals + (size_t)c * L + base;
+            const float* v = vals + (size_t)cell * L + base;
+            const float wd = weight_delta(p.W, wsig[2u * info + (c & 1u)], tf);
+            // the entry's value or the lane's own delta, by bit masks: a select on the lane's kind is loop-invariant, the compiler
+            // splits the loop on it, and a wavefront with both kinds of lanes runs the two loops one after the other (measured: 6 % of
+            // the step, profiles/leduc_five_workgroups_before_after.json)
+            const uint32_t keep = isw ? 0u : ~0u, own = isw ? rp_f2u(wd) : 0u;
             Map mp = map_identity();
-            for (uint32_t e = 0; e < n; ++e) map_touch_unit_unless(mp, PRUNED && c < 2u && !((lmask[base + e] >> c) & 1u), v[e], fl);
+            for (uint32_t e = 0; e < n; ++e)
+                map_touch_unit_unless(mp, PRUNED && c < 2u && !((lmask[base + e] >> c) & 1u), rp_u2f((rp_f2u(v[e]) & keep) | own), fl);
             if (c == 4u) mp.b = 0.0f + mp.b;  // the payoff slot {., sum, ., count}: no entry is skipped, so mp.n == n
             bmaps[bmap_index(chunk, rank, c, g.rank_max, 4u)] = mp;
         }
@@ -779,8 +812,8 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
             const uint32_t oi = order[task < 4u * nr ? task >> 2 : task - 4u * nr], info = oi & 255u, rank = oi >> 8;
             const uint32_t n = lcount[info], base = lbase[info];
             const size_t out = bmap_index(chunk, rank, c, g.rank_max, 4u);
-            const float* v = vals + (size_t)c * L + base;
             if (c == 4u) {  // payoff sum of the block, left fold from 0.0f
+                const float* v = vals + (size_t)2u * L + base;
                 float sum = 0.0f;
                 for (uint32_t e = 0; e < n; ++e) sum += v[e];
                 bmaps[out] = map_sum_slot(sum, n);
@@ -788,8 +821,12 @@ __global__ __launch_bounds__(256, 4) void k_traverse_maps_static(DevGame g, DevI
             }
             const bool isreg = c < 2u;
             const ChainParams cp = isreg ? cpr : cpw;
+            const float* v = vals + (size_t)(c & 1u) * L + base;  // a weight task's reads land on its regret neighbour's word, unused
+            const float wd = weight_delta(p.W, wsig[2u * info + (c & 1u)], tf);
+            const uint32_t keep = isreg ? ~0u : 0u, own = isreg ? 0u : rp_f2u(wd);  // as in the unit-discount loop
             Map mp = map_identity();
-            for (uint32_t e = 0; e < n; ++e) map_touch_unless(mp, PRUNED && isreg && !((lmask[base + e] >> c) & 1u), cp.d, v[e], cp.fl);
+            for (uint32_t e = 0; e < n; ++e)
+                map_touch_unless(mp, PRUNED && isreg && !((lmask[base + e] >> c) & 1u), cp.d, rp_u2f((rp_f2u(v[e]) & keep) | own), cp.fl);
             bmaps[out] = mp;
         }
     }
