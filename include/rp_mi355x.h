@@ -1180,6 +1180,120 @@ RP_API int rp_nlhe_search_match_device(rp_nlhe* h0, rp_nlhe* h1, uint64_t n, con
                                        rp_aivat_hand* hands_dev, int16_t* won_dev, uint8_t* rejected_dev, uint8_t* status_dev,
                                        uint8_t* searched_dev, uint8_t* unsolved_dev, rp_nlhe_search_step* steps_dev);
 
+/* THE BLUEPRINT CENSUS: what the table says AS A WHOLE — TrainingAPI::stats, street_stats, saturation, cold and hot
+ * (crates/portal/src/training/api.rs:74-286) and StrategyAPI::grid_usage (crates/portal/src/strategy/api.rs:196-245), each a full scan
+ * of the blueprint table with a GROUP BY in the reference.  One read-only scan of the device-resident table fills one rp_census
+ * record (k_nl_census_scan / k_nl_census_fold, csrc/nlmc_census.hpp); pure host functions turn the record into the reference's
+ * response shapes, as rp_match_summarize does for matches.
+ * NAMES.  rp_nlhe_census (include/rp_mi355x_diag.h) is the profiled steps' node census and stays what it is: the scan is
+ *   rp_nlhe_table_census, its record rp_census, and the summaries' output types are rp_census_totals / _street / _peaks / _grid.
+ * A ROW of the SQL table is one (infoset, action a) pair, a < n_actions = the consecutive non-zero 5-bit groups of `choices`, at most
+ *   9, as everywhere in this header; its edge is the 5-bit code of group a, its street min(present >> 8, 4) — index 4 collects what the
+ *   reference prints as "unknown".  An infoset without actions has no row: it is in no count and in no list.
+ * THE RECORD.  cell[street][edge code] (code 0 stays empty), infosets[street] = COUNT(DISTINCT (past, present, choices)), epoch, slots
+ *   = the table's capacity, and two ranked lists of n_cold = n_hot = min(RP_NLHE_CENSUS_TOP, infosets) entries:
+ *   cold: value MIN(visits) over the infoset's actions, ascending; hot: value MAX(regret), ordered by MAX(ABS(regret)) descending;
+ *   ties in either by (past, present, choices) ascending as unsigned integers — total orders.  An entry carries past, choices, present,
+ *   edges = n_actions and its value: `visits` in the cold list (regret 0), `regret` in the hot list (visits 0); entries past n are zero.
+ *   Per cell: rows = COUNT(*); rated = rows whose decision total is not zero (the denominator of AVG, which skips NULLs); dominant =
+ *   rated rows with ratio > 0.5f; visits = the exact sum; ratio, weight, total, regret, payoff = double sums; five f32 and two u32
+ *   extremes.  A cell with rows == 0 is all zero.
+ * THE ARITHMETIC, bit for bit (tests/nlhe_census_model.py follows it with explicit loops):
+ *   Per infoset: dec_total = the f32 left fold of weight[0 .. n_actions) from 0.0f in action order (SUM(weight) OVER (PARTITION BY
+ *     past, present, choices)); per action ratio = weight[a] / dec_total in f32, one rounding.  With dec_total == 0.0f (either sign)
+ *     the row counts in rows, is not rated and adds nothing to ratio.  Row bytes at a >= n_actions reach no result.
+ *   Float sums: every term is converted to f64 (exact) and added in f64.  Within a SEGMENT of RP_NLHE_CENSUS_SEGMENT consecutive
+ *     slots: a left fold from +0.0 over the ready slots in ascending slot index and, within a slot, the actions in ascending a.  The
+ *     table's sum: the left fold from +0.0 of the segment sums in ascending segment index.  A table of at most 65 536 slots is one
+ *     plain left fold.  Two actions of one infoset with the same edge code (imported tables may hold such) both land in the cell,
+ *     in action order.  `total` adds dec_total once per row, rated or not.
+ *   Counts, visits, extremes and the lists do not depend on any order.  Extremes compare as values; the sign of a zero extreme is
+ *     unspecified.  NaN is outside the contract, as for every NLHE call.
+ * DEPARTURES FROM THE SQL.  Postgres accumulates SUM(real) in f32 in scan order, so weighted_freq and dec_total have no defined bits
+ *   in the reference: here weighted_freq = (float)(weight / total) of the f64 sums.  AVG(visits::float4) rounds every row to f32: here
+ *   the sum of visits is exact.  Postgres sorts NULL first under DESC: here a cell without a rated row sorts last in its street.
+ * THE CALLS.  NULL h or out is RP_ERR_INVALID before any device work.  rp_nlhe_table_census stages, launches and synchronises;
+ *   _device takes `out` in DEVICE memory, queues on the handle's stream — after every earlier step and import — and returns.  The scan
+ *   reads 32 bytes per slot and 144 bytes per READY slot and writes only its own scratch (about 21 KB per segment, grow-only on the
+ *   handle, freed with it) and the record, every byte of it: the table, epoch, counters and keys are unchanged.
+ * THE SUMMARIES.  Host only, no handle, no device.  Sums over cells are f64 left folds from +0.0 over street then code ascending,
+ *   averages one division in f64 and one cast to f32; a NULL argument is RP_ERR_INVALID.
+ *   rp_census_stats (ApiBlueprintStats): infosets, edges = rows, avg = sum / edges, extremes over the non-empty cells; avg_visits =
+ *     (float)((double)visits / edges); everything 0 with edges == 0.
+ *   rp_census_street_stats (ApiStreetStats): five entries, street 'P' 'F' 'T' 'R' '?', the same per street; a street without rows zero.
+ *   rp_census_saturation (ApiSaturation): max_weight, max_regret = MAX(ABS(regret)), max_payoff = MAX(ABS(payoff)), max_visits,
+ *     precision_f32 = FLT_MAX, weight_pct = max_weight / precision_f32 * 100.0f and regret_pct likewise, in f32 left to right.
+ *   rp_census_grid_usage (ApiGridUsage): the non-empty cells — avg_freq = (float)(ratio / rated), 0 with rated == 0; weighted_freq =
+ *     (float)(weight / total), 0 with total == 0; n_decisions_with_edge = rows; n_dominant — ordered by street ascending, then cells
+ *     with a rated row before those without, then avg_freq descending, then edge code ascending.  rows: room for 160; *n = written. */
+#if defined(__cplusplus)
+#define RP_STATIC_ASSERT(cond, name) static_assert(cond, #name)
+#else
+#define RP_STATIC_ASSERT(cond, name) _Static_assert(cond, #name)
+#endif
+#define RP_NLHE_CENSUS_TOP 64u
+#define RP_NLHE_CENSUS_SEGMENT 65536u
+#define RP_NLHE_CENSUS_STREETS 5u
+#define RP_NLHE_CENSUS_CODES 32u
+typedef struct rp_census_cell {
+    uint64_t rows, rated, dominant, visits;
+    double   ratio, weight, total, regret, payoff;
+    float    max_regret, min_regret, max_weight, max_payoff, min_payoff;
+    uint32_t max_visits, min_visits;
+    uint32_t reserved;      /* 0 */
+} rp_census_cell;           /* 104 bytes */
+typedef struct rp_census_entry {
+    uint64_t past, choices;
+    uint32_t present, edges;
+    uint32_t visits;        /* cold: MIN(visits) */
+    float    regret;        /* hot: MAX(regret) */
+} rp_census_entry;          /* 32 bytes */
+typedef struct rp_census {
+    rp_census_cell  cell[RP_NLHE_CENSUS_STREETS][RP_NLHE_CENSUS_CODES];
+    uint64_t        infosets[RP_NLHE_CENSUS_STREETS];
+    uint64_t        epoch, slots;
+    uint32_t        n_cold, n_hot;
+    rp_census_entry cold[RP_NLHE_CENSUS_TOP], hot[RP_NLHE_CENSUS_TOP];
+} rp_census;                /* 20800 bytes */
+typedef struct rp_census_totals {
+    uint64_t infosets, edges;
+    float    avg_regret, max_regret, min_regret, avg_weight, max_weight, avg_payoff, max_payoff, min_payoff, avg_visits;
+    uint32_t max_visits, min_visits;
+    uint32_t reserved;      /* 0 */
+} rp_census_totals;         /* 64 bytes */
+typedef struct rp_census_street {
+    uint64_t infosets, edges;
+    float    avg_regret, avg_weight, avg_payoff, avg_visits;
+    char     street;        /* 'P' 'F' 'T' 'R' '?' */
+    uint8_t  reserved[7];   /* 0 */
+} rp_census_street;         /* 40 bytes */
+typedef struct rp_census_peaks {
+    float    max_weight, max_regret, max_payoff;
+    uint32_t max_visits;
+    float    precision_f32, weight_pct, regret_pct;
+    uint32_t reserved;      /* 0 */
+} rp_census_peaks;          /* 32 bytes */
+typedef struct rp_census_grid {
+    uint64_t n_decisions_with_edge, n_dominant;
+    float    avg_freq, weighted_freq;
+    uint8_t  street, edge;  /* 0..4, the 5-bit edge code */
+    uint8_t  reserved[6];   /* 0 */
+} rp_census_grid;           /* 32 bytes */
+RP_STATIC_ASSERT(sizeof(rp_census_cell) == 104, rp_census_cell_is_104_bytes);
+RP_STATIC_ASSERT(sizeof(rp_census_entry) == 32, rp_census_entry_is_32_bytes);
+RP_STATIC_ASSERT(sizeof(rp_census) == 20800, rp_census_is_20800_bytes);
+RP_STATIC_ASSERT(sizeof(rp_census_totals) == 64, rp_census_totals_is_64_bytes);
+RP_STATIC_ASSERT(sizeof(rp_census_street) == 40, rp_census_street_is_40_bytes);
+RP_STATIC_ASSERT(sizeof(rp_census_peaks) == 32, rp_census_peaks_is_32_bytes);
+RP_STATIC_ASSERT(sizeof(rp_census_grid) == 32, rp_census_grid_is_32_bytes);
+#undef RP_STATIC_ASSERT /* this header's own: not part of the API */
+RP_API int rp_nlhe_table_census(rp_nlhe* h, rp_census* out);
+RP_API int rp_nlhe_table_census_device(rp_nlhe* h, rp_census* out_dev);
+RP_API int rp_census_stats(const rp_census* c, rp_census_totals* out);
+RP_API int rp_census_street_stats(const rp_census* c, rp_census_street* out /* [5] */);
+RP_API int rp_census_saturation(const rp_census* c, rp_census_peaks* out);
+RP_API int rp_census_grid_usage(const rp_census* c, rp_census_grid* rows /* [160] */, uint32_t* n);
+
 /* Multi-GPU (BASELINE configs[3]): trees sharded by rank (rank r samples tree ids [r*B, (r+1)*B) of a world*B-tree epoch
  * against a replicated table).  step_local: this rank's traversal reduced to one composed entry per infoset touched
  * (rp_profile_summarize's records, entry_bytes each, at most max_entries) plus the infoset KEY of every entry — each

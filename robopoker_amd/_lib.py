@@ -107,6 +107,55 @@ class MatchSummary(C.Structure):
     _fields_ = [("hands", C.c_uint64), ("total_bb", C.c_double), ("bb_per_100", C.c_double), ("stddev", C.c_double), ("confidence", C.c_double)]
 
 
+RP_NLHE_CENSUS_TOP, RP_NLHE_CENSUS_SEGMENT, RP_NLHE_CENSUS_STREETS, RP_NLHE_CENSUS_CODES = 64, 65536, 5, 32
+
+
+class CensusCell(C.Structure):
+    """rp_census_cell: one (street, edge code) cell of the blueprint census (104 bytes)"""
+    _fields_ = [("rows", C.c_uint64), ("rated", C.c_uint64), ("dominant", C.c_uint64), ("visits", C.c_uint64),
+                ("ratio", C.c_double), ("weight", C.c_double), ("total", C.c_double), ("regret", C.c_double), ("payoff", C.c_double),
+                ("max_regret", C.c_float), ("min_regret", C.c_float), ("max_weight", C.c_float), ("max_payoff", C.c_float),
+                ("min_payoff", C.c_float), ("max_visits", C.c_uint32), ("min_visits", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CensusEntry(C.Structure):
+    """rp_census_entry: one infoset of a ranked list (32 bytes)"""
+    _fields_ = [("past", C.c_uint64), ("choices", C.c_uint64), ("present", C.c_uint32), ("edges", C.c_uint32),
+                ("visits", C.c_uint32), ("regret", C.c_float)]
+
+
+class Census(C.Structure):
+    """rp_census: the record of one scan of the blueprint table (20 800 bytes)"""
+    _fields_ = [("cell", CensusCell * 32 * 5), ("infosets", C.c_uint64 * 5), ("epoch", C.c_uint64), ("slots", C.c_uint64),
+                ("n_cold", C.c_uint32), ("n_hot", C.c_uint32), ("cold", CensusEntry * 64), ("hot", CensusEntry * 64)]
+
+
+class CensusTotals(C.Structure):
+    """rp_census_totals: ApiBlueprintStats (64 bytes)"""
+    _fields_ = [("infosets", C.c_uint64), ("edges", C.c_uint64), ("avg_regret", C.c_float), ("max_regret", C.c_float),
+                ("min_regret", C.c_float), ("avg_weight", C.c_float), ("max_weight", C.c_float), ("avg_payoff", C.c_float),
+                ("max_payoff", C.c_float), ("min_payoff", C.c_float), ("avg_visits", C.c_float), ("max_visits", C.c_uint32),
+                ("min_visits", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CensusStreet(C.Structure):
+    """rp_census_street: ApiStreetStats (40 bytes)"""
+    _fields_ = [("infosets", C.c_uint64), ("edges", C.c_uint64), ("avg_regret", C.c_float), ("avg_weight", C.c_float),
+                ("avg_payoff", C.c_float), ("avg_visits", C.c_float), ("street", C.c_char), ("reserved", C.c_uint8 * 7)]
+
+
+class CensusPeaks(C.Structure):
+    """rp_census_peaks: ApiSaturation (32 bytes)"""
+    _fields_ = [("max_weight", C.c_float), ("max_regret", C.c_float), ("max_payoff", C.c_float), ("max_visits", C.c_uint32),
+                ("precision_f32", C.c_float), ("weight_pct", C.c_float), ("regret_pct", C.c_float), ("reserved", C.c_uint32)]
+
+
+class CensusGrid(C.Structure):
+    """rp_census_grid: ApiGridUsage (32 bytes)"""
+    _fields_ = [("n_decisions_with_edge", C.c_uint64), ("n_dominant", C.c_uint64), ("avg_freq", C.c_float), ("weighted_freq", C.c_float),
+                ("street", C.c_uint8), ("edge", C.c_uint8), ("reserved", C.c_uint8 * 6)]
+
+
 class NlheFrontier(C.Structure):
     """rp_nlhe_frontier: a depth-limited leaf — both holes, the history to it and the solver's prefix (112 bytes)"""
     _fields_ = [("holes", C.c_uint64 * 2), ("draws", C.c_uint64 * 3), ("stacks", C.c_int16 * 2), ("internal", C.c_uint8),
@@ -431,6 +480,12 @@ _SIGNATURES = {
     "rp_nlhe_search_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(NlheSearchArgs)] + [C.c_void_p] * 7),
     "rp_nlhe_search_match_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(NlheSearchArgs)] + [C.c_void_p] * 7),
     "rp_match_summarize": (C.c_int, [C.c_uint64, C.c_void_p, C.POINTER(MatchSummary)]),
+    "rp_nlhe_table_census": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rp_nlhe_table_census_device": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rp_census_stats": (C.c_int, [C.c_void_p, C.POINTER(CensusTotals)]),
+    "rp_census_street_stats": (C.c_int, [C.c_void_p, C.POINTER(CensusStreet)]),
+    "rp_census_saturation": (C.c_int, [C.c_void_p, C.POINTER(CensusPeaks)]),
+    "rp_census_grid_usage": (C.c_int, [C.c_void_p, C.POINTER(CensusGrid), C.POINTER(C.c_uint32)]),
     "rp_nlhe_partition": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
     "rp_nlhe_partition_device": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
     "rp_nlhe_belief": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5),

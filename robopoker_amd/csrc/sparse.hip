@@ -801,6 +801,13 @@ __global__ void k_gather_rows(const float* tab, uint32_t A, const uint32_t* rows
     out[e].visits = reinterpret_cast<const uint32_t*>(row)[3 * A + a];
 }
 
+// rp_profile_set_rows: packed[i][4A] (a row in the table's own layout) -> row rows[i]; the rows of a launch are distinct
+__global__ void k_scatter_rows(float* tab, uint32_t A4, const uint32_t* rows, uint64_t n, const float* packed) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * A4) return;
+    tab[(size_t)rows[e / A4] * A4 + (uint32_t)(e % A4)] = packed[e];
+}
+
 // rp_profile_policy: one lane per queried row (a row is 16 * max_actions bytes; only its regrets or its weights are read)
 __global__ __launch_bounds__(256) void k_row_policy(const float* tab, uint64_t n_rows, uint32_t A, int kind, DistParams hp, const uint32_t* rows,
                                                     const uint8_t* n_actions, uint64_t n, float* policy) {
@@ -1214,17 +1221,52 @@ int rp_profile_set_rows(rp_profile* h, uint64_t n, const uint32_t* rows, const r
         if (rows[i] >= h->n_rows) return rp::fail(RP_ERR_INVALID, "rp_profile_set_rows: row %u out of range", rows[i]);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    std::vector<float> row(4u * h->A);
-    for (uint64_t i = 0; i < n; ++i) {  // a resynchronisation path (tests, hydrate): one small copy per row
-        for (uint32_t a = 0; a < h->A; ++a) {
-            const rp_encounter& e = in[i * h->A + a];
-            row[a] = e.regret;
-            row[h->A + a] = e.weight;
-            row[2 * h->A + a] = e.payoff;
-            memcpy(&row[3 * h->A + a], &e.visits, 4);
-        }
-        HIP_TRY(hipMemcpy(h->tab + (size_t)rows[i] * 4u * h->A, row.data(), row.size() * 4, hipMemcpyHostToDevice));
+    // Rows packed in the table's layout on the host, SET_CHUNK at a time, and scattered by one launch per chunk (one copy per row
+    // until the blueprint census wanted half-full tables of 2^27 slots: 14 µs a row).  A row named more than once keeps its LAST
+    // Encounters, as the copies in order left it: the earlier ones are dropped here, so no two lanes write one row.
+    constexpr uint64_t SET_CHUNK = 1ull << 18;
+    const uint32_t A4 = 4u * h->A;
+    std::vector<bool> seen(h->n_rows, false);
+    std::vector<uint8_t> keep(n);
+    for (uint64_t i = n; i-- > 0;) {
+        keep[i] = seen[rows[i]] ? 0 : 1;
+        seen[rows[i]] = true;
     }
+    const uint64_t cap = std::min<uint64_t>(n, SET_CHUNK);
+    std::vector<float> packed(cap * A4);
+    std::vector<uint32_t> where(cap);
+    uint32_t* d_rows = nullptr;
+    float* d_packed = nullptr;
+    HIP_TRY(hipMalloc(&d_rows, cap * 4));
+    if (hipMalloc(&d_packed, cap * A4 * 4) != hipSuccess) {
+        (void)hipFree(d_rows);
+        return rp::fail(RP_ERR_HIP, "rp_profile_set_rows: no device memory for the staging rows");
+    }
+    hipError_t err = hipSuccess;
+    for (uint64_t i = 0; i < n && err == hipSuccess;) {
+        uint64_t m = 0;
+        for (; i < n && m < cap; ++i) {
+            if (!keep[i]) continue;
+            float* row = packed.data() + m * A4;
+            for (uint32_t a = 0; a < h->A; ++a) {
+                const rp_encounter& e = in[i * h->A + a];
+                row[a] = e.regret;
+                row[h->A + a] = e.weight;
+                row[2 * h->A + a] = e.payoff;
+                memcpy(&row[3 * h->A + a], &e.visits, 4);
+            }
+            where[m++] = rows[i];
+        }
+        if (m == 0) break;
+        if ((err = hipMemcpy(d_rows, where.data(), m * 4, hipMemcpyHostToDevice)) != hipSuccess) break;
+        if ((err = hipMemcpy(d_packed, packed.data(), m * A4 * 4, hipMemcpyHostToDevice)) != hipSuccess) break;
+        hipLaunchKernelGGL(k_scatter_rows, dim3((unsigned)((m * A4 + 255) / 256)), dim3(256), 0, h->stream, h->tab, A4, d_rows, m, d_packed);
+        if ((err = hipGetLastError()) != hipSuccess) break;
+        err = hipStreamSynchronize(h->stream);  // the staging vectors are filled again
+    }
+    (void)hipFree(d_rows);
+    (void)hipFree(d_packed);
+    if (err != hipSuccess) return rp::fail(RP_ERR_HIP, "rp_profile_set_rows: %s", hipGetErrorString(err));
     return RP_OK;
 }
 

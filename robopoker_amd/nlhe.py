@@ -46,6 +46,91 @@ SEARCH_STEP_DTYPE = np.dtype([("solve_id", "<u8"), ("recall", RECALL_DTYPE), ("r
                               ("decision", "<u4"), ("seat", "u1"), ("edge", "u1"), ("fallback", "u1"),
                               ("belief_status", "u1")])  # rp_nlhe_search_step, 352 bytes
 assert SEARCH_STEP_DTYPE.itemsize == C.sizeof(_lib.NlheSearchStep) == 352 and C.sizeof(_lib.NlheSearchArgs) == 72
+CENSUS_TOP, CENSUS_SEGMENT, CENSUS_STREETS, CENSUS_CODES = (_lib.RP_NLHE_CENSUS_TOP, _lib.RP_NLHE_CENSUS_SEGMENT, _lib.RP_NLHE_CENSUS_STREETS,
+                                                              _lib.RP_NLHE_CENSUS_CODES)
+CENSUS_CELL_DTYPE = np.dtype([("rows", "<u8"), ("rated", "<u8"), ("dominant", "<u8"), ("visits", "<u8"), ("ratio", "<f8"), ("weight", "<f8"),
+                              ("total", "<f8"), ("regret", "<f8"), ("payoff", "<f8"), ("max_regret", "<f4"), ("min_regret", "<f4"),
+                              ("max_weight", "<f4"), ("max_payoff", "<f4"), ("min_payoff", "<f4"), ("max_visits", "<u4"), ("min_visits", "<u4"),
+                              ("reserved", "<u4")])  # rp_census_cell, 104 bytes
+CENSUS_ENTRY_DTYPE = np.dtype([("past", "<u8"), ("choices", "<u8"), ("present", "<u4"), ("edges", "<u4"), ("visits", "<u4"),
+                               ("regret", "<f4")])  # rp_census_entry, 32 bytes
+CENSUS_DTYPE = np.dtype([("cell", CENSUS_CELL_DTYPE, (CENSUS_STREETS, CENSUS_CODES)), ("infosets", "<u8", (CENSUS_STREETS,)), ("epoch", "<u8"),
+                         ("slots", "<u8"), ("n_cold", "<u4"), ("n_hot", "<u4"), ("cold", CENSUS_ENTRY_DTYPE, (CENSUS_TOP,)),
+                         ("hot", CENSUS_ENTRY_DTYPE, (CENSUS_TOP,))])  # rp_census, 20 800 bytes
+assert CENSUS_CELL_DTYPE.itemsize == C.sizeof(_lib.CensusCell) == 104 and CENSUS_ENTRY_DTYPE.itemsize == C.sizeof(_lib.CensusEntry) == 32
+assert CENSUS_DTYPE.itemsize == C.sizeof(_lib.Census) == 20800
+# Edge's Display (kicker/src/edge.rs:229-241) by 5-bit edge code; code 0 is no edge, codes from 20 on name nothing
+EDGE_NAMES = ("", "?", "F", "O", "*", "!", "2bb", "3bb", "4bb", "5bb", "1:4", "1:3", "1:2", "2:3", "3:4", "1:1", "5:4", "3:2", "2:1", "3:1")
+STREET_NAMES = "PFTR?"
+
+
+def edge_name(code: int) -> str:
+    """``format!("{}", Edge::from(code))``; a code that is no edge reads "#<code>" """
+    return EDGE_NAMES[code] if 0 < code < len(EDGE_NAMES) else f"#{code}"
+
+
+def _census_ptr(census):
+    """a census record (``NlheSolver.table_census()``'s, or any CENSUS_DTYPE array of one item) as the summaries' argument"""
+    rec = np.ascontiguousarray(census, CENSUS_DTYPE).reshape(-1)
+    assert rec.size == 1, "one rp_census record"
+    return rec, _p(rec)
+
+
+def census_stats(census):
+    """``TrainingAPI::stats`` (ApiBlueprintStats) of a census record: dict(infosets, edges, avg_/max_/min_regret, avg_/max_weight,
+    avg_/max_/min_payoff, avg_/max_/min_visits); float32 where the reference's are.  Host arithmetic, no device."""
+    rec, ptr = _census_ptr(census)
+    s = _lib.CensusTotals()
+    _lib.check(_lib.load().rp_census_stats(ptr, C.byref(s)))
+    out = dict(infosets=int(s.infosets), edges=int(s.edges), max_visits=int(s.max_visits), min_visits=int(s.min_visits))
+    out.update({k: np.float32(getattr(s, k)) for k in ("avg_regret", "max_regret", "min_regret", "avg_weight", "max_weight", "avg_payoff",
+                                                       "max_payoff", "min_payoff", "avg_visits")})
+    return out
+
+
+def census_street_stats(census):
+    """``TrainingAPI::street_stats`` (ApiStreetStats): five dicts, street "P" "F" "T" "R" "?", a street without rows all zero"""
+    rec, ptr = _census_ptr(census)
+    s = (_lib.CensusStreet * CENSUS_STREETS)()
+    _lib.check(_lib.load().rp_census_street_stats(ptr, s))
+    return [dict(street=x.street.decode(), infosets=int(x.infosets), edges=int(x.edges),
+                 **{k: np.float32(getattr(x, k)) for k in ("avg_regret", "avg_weight", "avg_payoff", "avg_visits")}) for x in s]
+
+
+def census_saturation(census):
+    """``TrainingAPI::saturation`` (ApiSaturation): how close the table's largest magnitudes are to f32::MAX"""
+    rec, ptr = _census_ptr(census)
+    s = _lib.CensusPeaks()
+    _lib.check(_lib.load().rp_census_saturation(ptr, C.byref(s)))
+    return dict(max_visits=int(s.max_visits), **{k: np.float32(getattr(s, k)) for k in ("max_weight", "max_regret", "max_payoff", "precision_f32",
+                                                                                      "weight_pct", "regret_pct")})
+
+
+def census_grid_usage(census):
+    """``StrategyAPI::grid_usage`` (ApiGridUsage): one dict per non-empty (street, edge) cell — street, edge (``Edge``'s display), code,
+    avg_freq, weighted_freq, n_decisions_with_edge, n_dominant — by street, then avg_freq descending"""
+    rec, ptr = _census_ptr(census)
+    rows, n = (_lib.CensusGrid * (CENSUS_STREETS * CENSUS_CODES))(), C.c_uint32()
+    _lib.check(_lib.load().rp_census_grid_usage(ptr, rows, C.byref(n)))
+    return [dict(street=STREET_NAMES[r.street], edge=edge_name(r.edge), code=int(r.edge), avg_freq=np.float32(r.avg_freq),
+                 weighted_freq=np.float32(r.weighted_freq), n_decisions_with_edge=int(r.n_decisions_with_edge), n_dominant=int(r.n_dominant))
+            for r in rows[: n.value]]
+
+
+def census_cold(census, k=CENSUS_TOP):
+    """``TrainingAPI::cold(k)`` (ApiColdInfoset), k <= 64: the infosets with the fewest visits of their least visited action"""
+    rec = np.ascontiguousarray(census, CENSUS_DTYPE).reshape(-1)[0]
+    return [dict(past=int(e["past"]), present=int(e["present"]), choices=int(e["choices"]), visits=int(e["visits"]), edges=int(e["edges"]))
+            for e in rec["cold"][: min(int(k), int(rec["n_cold"]))]]
+
+
+def census_hot(census, k=CENSUS_TOP):
+    """``TrainingAPI::hot(k)`` (ApiHotInfoset), k <= 64: the infosets with the largest regret magnitude; max_regret = MAX(regret)"""
+    rec = np.ascontiguousarray(census, CENSUS_DTYPE).reshape(-1)[0]
+    return [dict(past=int(e["past"]), present=int(e["present"]), choices=int(e["choices"]), max_regret=np.float32(e["regret"]),
+                 edges=int(e["edges"])) for e in rec["hot"][: min(int(k), int(rec["n_hot"]))]]
+
+
 WORLDS, MAX_REJECTIONS, WORLD_NONE, MAX_DEALS = _lib.RP_NLHE_WORLDS, _lib.RP_NLHE_MAX_REJECTIONS, _lib.RP_WORLD_NONE, 4096
 
 
@@ -367,6 +452,24 @@ class NlheSolver:
         enc, nact, found = np.zeros((n, A), dtype=ENC_DTYPE), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
         _lib.check(self._lib.rp_nlhe_memory(self._h, n, _p(past), _p(present), _p(choices), _p(enc), _p(nact), _p(found)))
         return enc, nact, found.view(np.bool_)
+
+    # ---- the blueprint census (include/rp_mi355x.h rp_nlhe_table_census): what the table says as a whole ----
+    def table_census(self):
+        """one read-only scan of the table -> the rp_census record as a CENSUS_DTYPE scalar array (shape ()): cell[5][32], infosets[5],
+        epoch, slots, cold / hot lists.  ``census_stats`` / ``census_street_stats`` / ``census_saturation`` / ``census_grid_usage`` /
+        ``census_cold`` / ``census_hot`` read it.  (``census()`` is the profiled steps' node census.)"""
+        rec = np.zeros((), CENSUS_DTYPE)
+        _lib.check(self._lib.rp_nlhe_table_census(self._h, _p(rec)))
+        return rec
+
+    def table_census_device(self, out=None):
+        """the same record as a device tensor uint8[20800], queued on the solver's stream (``sync()`` waits;
+        ``.cpu().numpy().view(CENSUS_DTYPE)[0]``).  ``out``: a tensor to reuse."""
+        if out is None:
+            out = torch.empty(CENSUS_DTYPE.itemsize, dtype=torch.uint8, device=f"cuda:{self.device}")
+        assert out.is_cuda and out.is_contiguous() and out.element_size() * out.numel() == CENSUS_DTYPE.itemsize
+        self._queue(self._lib.rp_nlhe_table_census_device, out.device, True, None, out)
+        return out
 
     # ---- ranges (include/rp_mi355x.h rp_nlhe_reaches / rp_nlhe_opponent_range): the blueprint's reach of every hole a seat could hold ----
     def reaches_raw(self, recalls, kind="opponent", normalize=False):
