@@ -324,6 +324,10 @@ RP_API int rp_mccfr_traversal_variant(rp_mccfr* h, int* out);
  * outcomes) the traversal reads the game through; 0 when it follows the child records node by node instead (chance nodes of one
  * skeleton node with different numbers of outcomes, or RP_TRAV_NO_FLAT=1: the independent cross-check).  Same Decisions. */
 RP_API int rp_mccfr_traversal_rows_bytes(rp_mccfr* h, size_t* out);
+/* Composed update: how a step of the current batch size folds its group maps: 0 = in the launch that folds the block maps (the last
+ * workgroup of a tile), 1 = in a launch of its own, one workgroup per infoset (batches of many groups; RP_FOLD_SPLIT=1 / 0 at creation
+ * forces it always / never).  Same tables, counters and summary blobs. */
+RP_API int rp_mccfr_fold_variant(rp_mccfr* h, int* out);
 /* Which compile-time action skeleton a game table matches node for node, for every chance outcome (host only, no device
  * needed): 0 none (the generic traversal kernels), 1 Kuhn's, 2 Leduc's (any number of ranks). */
 RP_API int rp_game_skeleton(const rp_game_table* game, int* out);

@@ -106,6 +106,7 @@ struct rp_mccfr {
     uint64_t tables_version = 1, itab_version = 0;
     static constexpr uint32_t cell_pad = 7;  // words between the cells' value arrays in k_traverse_maps_static's LDS (bank spread)
     bool fuse_maps = true;  // composed update: traversal + block maps in one kernel when the game allows (RP_TRAV_UNFUSED=1: never)
+    uint32_t fold_split_groups = 0;  // composed update: batches of at least this many groups fold them in k_fold_groups (RP_FOLD_SPLIT=1 | 0: all | none)
     int static_skel = 0;  // 0: none (k_traverse_lds / k_traverse), 1: KuhnSkel, 2: LeducSkel (traverse_static.hpp)
     bool profiling = false;
     KernelClock clk_traverse, clk_compact, clk_update;
@@ -491,6 +492,14 @@ bool traverse_maps_fused(const rp_mccfr* h) {
            traverse_maps_lds_bytes(h) <= 64 * 1024 && h->fuse_maps;
 }
 
+// composed update: whether a batch's group maps are folded by a launch of their own (k_combine2<false, false> + k_fold_groups) or by the
+// last workgroup of each tile of k_combine2.  FOLD_SPLIT_GROUPS: DESIGN.md §3, "The group fold as a launch of its own"
+constexpr uint32_t FOLD_SPLIT_GROUPS = 128;
+bool fold_split(const rp_mccfr* h, uint32_t batch) {
+    const uint32_t ngrp = (chunks_of(batch) + RP_FOLD_GROUP - 1) / RP_FOLD_GROUP;
+    return ngrp >= h->fold_split_groups;
+}
+
 // apply = true: the summary is applied to the tables by the fold itself (single-GPU step), `blob_dev` is not written
 int launch_summarize(rp_mccfr* h, const StepParams& p, void* blob_dev, bool fused = false, bool apply = false) {
     unsigned char* blob = reinterpret_cast<unsigned char*>(blob_dev);
@@ -529,13 +538,18 @@ int launch_summarize(rp_mccfr* h, const StepParams& p, void* blob_dev, bool fuse
         FoldScratch fs;
         fs.gmaps = bmaps + bmap_index(nblk_max, 0, 0, h->g.rank_max, W2);
         fs.done = reinterpret_cast<uint32_t*>(bmaps + bmap_index(nblk_max + ngrp_max, 0, 0, h->g.rank_max, W2));
-        const dim3 grid(std::max(ngrp, 1u), cb2_tiles(nr, W2));
+        const dim3 grid(std::max(ngrp, 1u), cb2_tiles(nr, W2)), fold_grid(std::max(nr, 1u));
+        // few groups: the last workgroup of a tile folds them in the same launch; many: a launch of its own, a workgroup per infoset
+        const bool split = fold_split(h, h->batch);
+        if (split) hipLaunchKernelGGL((k_combine2<false, false>), grid, dim3(CB2_THREADS), 0, h->stream, h->g, h->t, h->itab, p, bmaps, nr, fs, cells, sums);
         if (apply) {
-            hipLaunchKernelGGL((k_combine2<true>), grid, dim3(CB2_THREADS), 0, h->stream, h->g, h->t, h->itab, p, bmaps, nr, fs, cells, sums);
+            if (split) hipLaunchKernelGGL((k_fold_groups<true>), fold_grid, dim3(CB2_THREADS), 0, h->stream, h->g, h->t, h->itab, p, fs.gmaps, nr, cells, sums);
+            else hipLaunchKernelGGL((k_combine2<true>), grid, dim3(CB2_THREADS), 0, h->stream, h->g, h->t, h->itab, p, bmaps, nr, fs, cells, sums);
             h->tables_version += 1;  // the kernel refreshes the rows of the per-infoset tables it changes
             if (h->itab_version + 1 == h->tables_version) h->itab_version = h->tables_version;
         } else {
-            hipLaunchKernelGGL((k_combine2<false>), grid, dim3(CB2_THREADS), 0, h->stream, h->g, h->t, h->itab, p, bmaps, nr, fs, cells, sums);
+            if (split) hipLaunchKernelGGL((k_fold_groups<false>), fold_grid, dim3(CB2_THREADS), 0, h->stream, h->g, h->t, h->itab, p, fs.gmaps, nr, cells, sums);
+            else hipLaunchKernelGGL((k_combine2<false>), grid, dim3(CB2_THREADS), 0, h->stream, h->g, h->t, h->itab, p, bmaps, nr, fs, cells, sums);
         }
     }
     clock_end(h, h->clk_update);
@@ -563,7 +577,7 @@ int enqueue_step(rp_mccfr* h) {
         if ((rc = launch_chain(h, p))) return rc;
         h->tables_version += 1;
     } else {
-        // the fold applies the summary to the tables itself (k_combine2<APPLY>: fold + k_fold + k_prepare_infos in one launch)
+        // the fold applies the summary to the tables itself (k_combine2<APPLY> or k_fold_groups<APPLY>: fold + k_fold + k_prepare_infos)
         if ((rc = launch_batch_summary(h, p, h->d_summary, true))) return rc;
     }
     h->epoch += 1;  // CfrSampling::increment via Solver::advance (solver.rs:103-104)
@@ -765,6 +779,9 @@ int rp_mccfr_create(const rp_game_table* game, rp_regret_kind r, rp_weight_kind 
     }
     h->use_lds_traverse = traverse_fits_lds(h) && getenv("RP_MCCFR_HBM_SCRATCH") == nullptr;
     h->fuse_maps = getenv("RP_TRAV_UNFUSED") == nullptr;
+    // read at creation, for tests: RP_FOLD_SPLIT=1 folds the group maps in k_fold_groups from one group upward, RP_FOLD_SPLIT=0 never
+    const char* fold_env = getenv("RP_FOLD_SPLIT");
+    h->fold_split_groups = !fold_env ? FOLD_SPLIT_GROUPS : (atoi(fold_env) ? 1u : UINT32_MAX);
     if (h->use_lds_traverse && getenv("RP_TRAV_GENERIC") == nullptr) {
         for (int k = 1; k <= 2 && !h->static_skel; ++k)
             with_skeleton(k, [&](auto gt) {
@@ -1256,6 +1273,12 @@ int rp_mccfr_traversal_rows_bytes(rp_mccfr* h, size_t* out) {
 int rp_mccfr_traversal_variant(rp_mccfr* h, int* out) {
     if (!h || !out) return rp::fail(RP_ERR_INVALID, "rp_mccfr_traversal_variant: NULL argument");
     *out = h->static_skel ? 2 : (h->use_lds_traverse ? 1 : 0);
+    return RP_OK;
+}
+
+int rp_mccfr_fold_variant(rp_mccfr* h, int* out) {
+    if (!h || !out) return rp::fail(RP_ERR_INVALID, "rp_mccfr_fold_variant: NULL argument");
+    *out = fold_split(h, h->batch) ? 1 : 0;
     return RP_OK;
 }
 

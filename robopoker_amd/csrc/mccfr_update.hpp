@@ -494,6 +494,7 @@ __global__ __launch_bounds__(128) void k_chain(DevGame g, DevTables t, DevSorted
 //   k_block_maps  one workgroup per (infoset, block of T consecutive Decisions): sequential composition inside the
 //                 block, all blocks of all infosets in parallel
 //   k_combine2    (group, infoset tile) workgroups: block maps -> group maps -> Cell / InfoSum blob, or straight into the tables
+//   k_fold_groups batches of many groups: the group maps -> ... as a launch of its own, one workgroup per infoset
 // ------------------------------------------------------------------------------------------------
 // Map / map_compose live in mccfr_kernels.hpp
 // block = the Decisions of infoset blockIdx.y produced by chunk blockIdx.x (RP_COMPOSE_CHUNK == CH_TREES trees):
@@ -684,12 +685,12 @@ struct FoldScratch {
     Map* gmaps;      // [group][rank][2A + 1]: bmap_index
     uint32_t* done;  // [tile] groups finished
 };
-// one lane's left fold, from the identity, of the n >= 1 slots load(0), load(1), ... : cell maps composed, or — sum — payoff sums
-// and counts added from 0.0f / 0.  The loads do not depend on the chain: two batches of D, the loads of one in flight while the
-// other is folded; the clamp keeps the loads of a ragged last batch inside the run.
+// one lane's left fold, continued from m (the identity, or the fold of the slots before these), of the n >= 1 slots load(0), load(1),
+// ... : cell maps composed, or — sum — payoff sums and counts added (from 0.0f / 0: the identity's b and n).  The loads do not depend
+// on the chain: two batches of D, the loads of one in flight while the other is folded; the clamp keeps the loads of a ragged last
+// batch inside the run.
 template <uint32_t D, class Load>
-__device__ __forceinline__ Map fold_slots(uint32_t n, bool sum, Load load) {
-    Map m = map_identity();
+__device__ __forceinline__ Map fold_slots(Map m, uint32_t n, bool sum, Load load) {
     uint4 va[D], vb[D];
     auto issue = [&](uint4* v, uint32_t k0) __attribute__((always_inline)) {
 #pragma unroll
@@ -733,61 +734,31 @@ __device__ __forceinline__ Map fold_slots(uint32_t n, bool sum, Load load) {
     }
     return m;
 }
-template <bool APPLY>
-__global__ __launch_bounds__(CB2_THREADS) void k_combine2(DevGame g, DevTables t, DevInfoTab it, StepParams p, const Map* bmaps, uint32_t nr,
-                                                          FoldScratch fs, Cell* cells, InfoSum* sums) {
-    __shared__ uint32_t role;
-    __shared__ float sh_ps[CB2_THREADS / 3u];
-    __shared__ uint32_t sh_len[CB2_THREADS / 3u];
-    const uint32_t grp = blockIdx.x, tile = blockIdx.y, tid = threadIdx.x;
+// the summary blob's entries of the other player's infosets, by one workgroup of CB2_THREADS: nothing happened to them
+__device__ __forceinline__ void blob_idle_entries(const DevGame& g, const StepParams& p, Cell* cells, InfoSum* sums) {
     const uint32_t A = g.A, W2 = 2 * A, SL = W2 + 1u;
-    if (!APPLY && grp == 0 && tile == 0) {  // not this walker's infosets: nothing happened to them
-        const Map ident = map_identity();
-        for (uint32_t e = tid; e < g.n_infos * SL; e += CB2_THREADS) {
-            const uint32_t info = e / SL, slot = e - info * SL;
-            if (g.info_player[info] == p.walker) continue;
-            if (slot == W2) {
-                sums[info] = InfoSum{0u, 0.0f};
-            } else {
-                Cell& cl = cells[(size_t)info * A + slot % A];
-                if (slot < A) cell_set_regret(cl, ident);
-                else cell_set_weight(cl, ident);
-            }
+    const Map ident = map_identity();
+    for (uint32_t e = threadIdx.x; e < g.n_infos * SL; e += CB2_THREADS) {
+        const uint32_t info = e / SL, slot = e - info * SL;
+        if (g.info_player[info] == p.walker) continue;
+        if (slot == W2) {
+            sums[info] = InfoSum{0u, 0.0f};
+        } else {
+            Cell& cl = cells[(size_t)info * A + slot % A];
+            if (slot < A) cell_set_regret(cl, ident);
+            else cell_set_weight(cl, ident);
         }
     }
-    const uint32_t nb = (p.batch + RP_COMPOSE_CHUNK - 1) / RP_COMPOSE_CHUNK;  // one block per chunk of trees
-    const uint32_t ngrp = (nb + RP_FOLD_GROUP - 1) / RP_FOLD_GROUP;
-    if (grp >= ngrp) return;
-    const uint32_t ntiles = cb2_tiles(nr, W2);
-    const uint32_t r_lo = (uint32_t)((uint64_t)tile * nr / ntiles), r_hi = (uint32_t)((uint64_t)(tile + 1u) * nr / ntiles);
-    const uint32_t li = tid / SL, slot = tid - li * SL, rank = r_lo + li;
-    const bool active = rank < r_hi, sum = slot == W2;
-    const size_t row = (size_t)g.rank_max * SL;  // 16-byte words from a block's (group's) row to the next
-    if (active) {
-        const uint32_t b_lo = grp * RP_FOLD_GROUP, n = min(nb, b_lo + RP_FOLD_GROUP) - b_lo;
-        const uint4* src = reinterpret_cast<const uint4*>(bmaps) + bmap_index(b_lo, rank, slot, g.rank_max, W2);
-        const Map m = fold_slots<CB2_DEPTH>(n, sum, [&](uint32_t k) { return src[(size_t)k * row]; });
-        st_map(&fs.gmaps[bmap_index(grp, rank, slot, g.rank_max, W2)], m);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the group maps are in memory before this group counts itself in
-    __syncthreads();
-    if (tid == 0) role = atomicAdd(&fs.done[tile], 1u) == ngrp - 1u ? 1u : 0u;
-    __syncthreads();
-    if (!role) return;
-    if (tid == 0) fs.done[tile] = 0;  // for the next launch
-    // the tile's group maps, folded in group order
-    Map tot = map_identity();
-    uint32_t info = 0;
-    if (active) {
-        const uint64_t* gm = reinterpret_cast<const uint64_t*>(fs.gmaps + bmap_index(0u, rank, slot, g.rank_max, W2));
-        tot = fold_slots<CB2_DEPTH2>(ngrp, sum, [&](uint32_t k) {
-            const uint64_t* w = gm + (size_t)k * row * 2u;
-            const uint64_t lo = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint64_t hi = __hip_atomic_load(w + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            return make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
-        });
-        info = g.rank_info[(size_t)p.walker * g.rank_max + rank];
-    }
+}
+// What follows the fold of the group maps, by every thread of the workgroup: lane (li, slot) of an `active` lane holds `tot`, the summary
+// of its cell of infoset `info` (slot 2A: the payoff sum and count).  !APPLY: the lane's entry of the summary blob.  APPLY: k_fold with
+// world = 1 for the rows of the workgroup's infosets, then their rows of the per-infoset tables (prepare_one).  sh_ps / sh_len: one
+// entry per infoset of the workgroup.
+template <bool APPLY>
+__device__ __forceinline__ void fold_finish(const DevGame& g, const DevTables& t, const DevInfoTab& it, const StepParams& p, bool active, uint32_t li,
+                                            uint32_t slot, uint32_t info, const Map& tot, Cell* cells, InfoSum* sums, float* sh_ps, uint32_t* sh_len) {
+    const uint32_t A = g.A, W2 = 2 * A;
+    const bool sum = slot == W2;
     if (!APPLY) {
         if (active) {
             if (sum) {
@@ -800,7 +771,6 @@ __global__ __launch_bounds__(CB2_THREADS) void k_combine2(DevGame g, DevTables t
         }
         return;
     }
-    // k_fold, world = 1, for the rows of this tile's infosets
     if (active && sum) {
         sh_ps[li] = tot.b;
         sh_len[li] = tot.n;
@@ -821,6 +791,112 @@ __global__ __launch_bounds__(CB2_THREADS) void k_combine2(DevGame g, DevTables t
     }
     __syncthreads();  // workgroup scope: the rows just written are what prepare_one reads
     if (active && slot == 0) prepare_one(g, t, p, it, info);
+}
+// TAIL: stages 1 and 2 and what follows, in one launch, as described above.  !TAIL (then !APPLY): stage 1 alone, the group maps stored
+// plainly, no arrival counter; k_fold_groups<APPLY>, the next launch on the stream, is stage 2 and what follows.
+template <bool APPLY, bool TAIL = true>
+__global__ __launch_bounds__(CB2_THREADS) void k_combine2(DevGame g, DevTables t, DevInfoTab it, StepParams p, const Map* bmaps, uint32_t nr,
+                                                          FoldScratch fs, Cell* cells, InfoSum* sums) {
+    static_assert(TAIL || !APPLY, "stage 1 alone applies nothing");
+    __shared__ uint32_t role;
+    __shared__ float sh_ps[CB2_THREADS / 3u];
+    __shared__ uint32_t sh_len[CB2_THREADS / 3u];
+    const uint32_t grp = blockIdx.x, tile = blockIdx.y, tid = threadIdx.x;
+    const uint32_t A = g.A, W2 = 2 * A, SL = W2 + 1u;
+    if (TAIL && !APPLY && grp == 0 && tile == 0) blob_idle_entries(g, p, cells, sums);
+    const uint32_t nb = (p.batch + RP_COMPOSE_CHUNK - 1) / RP_COMPOSE_CHUNK;  // one block per chunk of trees
+    const uint32_t ngrp = (nb + RP_FOLD_GROUP - 1) / RP_FOLD_GROUP;
+    if (grp >= ngrp) return;
+    const uint32_t ntiles = cb2_tiles(nr, W2);
+    const uint32_t r_lo = (uint32_t)((uint64_t)tile * nr / ntiles), r_hi = (uint32_t)((uint64_t)(tile + 1u) * nr / ntiles);
+    const uint32_t li = tid / SL, slot = tid - li * SL, rank = r_lo + li;
+    const bool active = rank < r_hi, sum = slot == W2;
+    const size_t row = (size_t)g.rank_max * SL;  // 16-byte words from a block's (group's) row to the next
+    if (active) {
+        const uint32_t b_lo = grp * RP_FOLD_GROUP, n = min(nb, b_lo + RP_FOLD_GROUP) - b_lo;
+        const uint4* src = reinterpret_cast<const uint4*>(bmaps) + bmap_index(b_lo, rank, slot, g.rank_max, W2);
+        const Map m = fold_slots<CB2_DEPTH>(map_identity(), n, sum, [&](uint32_t k) { return src[(size_t)k * row]; });
+        if (TAIL) st_map(&fs.gmaps[bmap_index(grp, rank, slot, g.rank_max, W2)], m);
+        else fs.gmaps[bmap_index(grp, rank, slot, g.rank_max, W2)] = m;
+    }
+    if (!TAIL) return;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the group maps are in memory before this group counts itself in
+    __syncthreads();
+    if (tid == 0) role = atomicAdd(&fs.done[tile], 1u) == ngrp - 1u ? 1u : 0u;
+    __syncthreads();
+    if (!role) return;
+    if (tid == 0) fs.done[tile] = 0;  // for the next launch
+    // the tile's group maps, folded in group order
+    Map tot = map_identity();
+    uint32_t info = 0;
+    if (active) {
+        const uint64_t* gm = reinterpret_cast<const uint64_t*>(fs.gmaps + bmap_index(0u, rank, slot, g.rank_max, W2));
+        tot = fold_slots<CB2_DEPTH2>(tot, ngrp, sum, [&](uint32_t k) {
+            const uint64_t* w = gm + (size_t)k * row * 2u;
+            const uint64_t lo = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint64_t hi = __hip_atomic_load(w + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+        });
+        info = g.rank_info[(size_t)p.walker * g.rank_max + rank];
+    }
+    fold_finish<APPLY>(g, t, it, p, active, li, slot, info, tot, cells, sums, sh_ps, sh_len);
+}
+
+// Stage 2 and what follows as a launch of its own, after k_combine2<false, false> on the same stream (the kernel boundary orders the
+// group maps: plain loads, no counter, no hand-over): one workgroup per infoset of the walker, in rank order.
+//   load    the infoset's group maps — ngrp x (2A + 1) slots, 2A + 1 contiguous per group — by all lanes, FG_LOADS 16-byte loads per
+//           lane, every one issued before the first is waited for: one memory round trip, where the tail of k_combine2 pulls a whole
+//           tile's maps through one CU eight at a time;
+//   stage   into LDS in group order: FG_SLOTS slots = FG_SLOTS * 16 B = 40 KB of static LDS (three workgroups fit a CU's 160 KB; the
+//           grid needs one per CU).  A slab is the FG_SLOTS / (2A + 1) whole groups that fit (Leduc: 512, i.e. 2^23 trees); more
+//           groups take further slabs in group order, the running maps carried across;
+//   fold    lanes 0 .. 2A continue their slot's left fold through the slab in group order out of LDS (fold_slots: the association
+//           and the payoff-lane rule of k_combine2's stage 2, the reads FG_DEPTH ahead of the dependent chain);
+//   finish  fold_finish, as the last workgroup of a tile does in k_combine2.
+#define FG_LOADS 10u
+#define FG_SLOTS (FG_LOADS * CB2_THREADS)
+#define FG_DEPTH 8u
+static_assert(2u * RP_MAX_ACTIONS + 1u <= FG_SLOTS, "a slab of k_fold_groups holds at least one group");
+__host__ __device__ inline uint32_t fg_slab_groups(uint32_t W2) { return FG_SLOTS / (W2 + 1u); }
+template <bool APPLY>
+__global__ __launch_bounds__(CB2_THREADS) void k_fold_groups(DevGame g, DevTables t, DevInfoTab it, StepParams p, const Map* gmaps, uint32_t nr,
+                                                             Cell* cells, InfoSum* sums) {
+    typedef uint32_t __attribute__((ext_vector_type(4))) Word4;  // (a plain vector: an array of uint4 in flight ends up in scratch)
+    __shared__ __attribute__((aligned(16))) Word4 slab[FG_SLOTS];
+    __shared__ float sh_ps[1];
+    __shared__ uint32_t sh_len[1];
+    const uint32_t rank = blockIdx.x, tid = threadIdx.x;
+    const uint32_t A = g.A, W2 = 2 * A, SL = W2 + 1u;
+    if (!APPLY && rank == 0) blob_idle_entries(g, p, cells, sums);
+    if (rank >= nr) return;
+    const uint32_t nb = (p.batch + RP_COMPOSE_CHUNK - 1) / RP_COMPOSE_CHUNK;
+    const uint32_t ngrp = (nb + RP_FOLD_GROUP - 1) / RP_FOLD_GROUP, per = fg_slab_groups(W2);
+    const size_t row = (size_t)g.rank_max * SL;
+    const Word4* src = reinterpret_cast<const Word4*>(gmaps) + bmap_index(0u, rank, 0u, g.rank_max, W2);
+    const bool active = tid < SL;
+    Map tot = map_identity();
+    for (uint32_t g0 = 0; g0 < ngrp; g0 += per) {
+        const uint32_t n = min(per, ngrp - g0), nel = n * SL;  // 1 <= nel <= FG_SLOTS
+        Word4 v[FG_LOADS];
+#pragma unroll
+        for (uint32_t q = 0; q < FG_LOADS; ++q) {  // the clamp keeps the loads of a ragged slab inside it: no branch between the loads
+            const uint32_t e = min(tid + q * CB2_THREADS, nel - 1u), k = e / SL;
+            v[q] = src[(size_t)(g0 + k) * row + (e - k * SL)];
+        }
+        if (g0) __syncthreads();  // the fold of the slab before is done with the LDS
+#pragma unroll
+        for (uint32_t q = 0; q < FG_LOADS; ++q) {
+            const uint32_t e = tid + q * CB2_THREADS;
+            if (e < nel) slab[e] = v[q];
+        }
+        __syncthreads();
+        if (active) tot = fold_slots<FG_DEPTH>(tot, n, tid == W2, [&](uint32_t k) {
+            const Word4 w = slab[k * SL + tid];
+            return make_uint4(w.x, w.y, w.z, w.w);
+        });
+    }
+    const uint32_t info = g.rank_info[(size_t)p.walker * g.rank_max + rank];
+    fold_finish<APPLY>(g, t, it, p, active, 0u, tid, info, tot, cells, sums, sh_ps, sh_len);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -198,6 +198,12 @@ class Solver:
         _lib.check(self._lib.rp_mccfr_traversal_variant(self._h, C.byref(v)))
         return ("hbm", "lds", "static")[v.value]
 
+    def fold_variant(self) -> str:
+        """how a composed step of the current batch size folds its group maps: "fused" (inside k_combine2) or "split" (k_fold_groups)"""
+        v = C.c_int()
+        _lib.check(self._lib.rp_mccfr_fold_variant(self._h, C.byref(v)))
+        return ("fused", "split")[v.value]
+
     def traversal_rows_bytes(self) -> int:
         """size of the packed-row game table of the "static" traversal; 0: it follows the child records (RP_TRAV_NO_FLAT=1)"""
         n = C.c_size_t()
