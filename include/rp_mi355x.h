@@ -446,6 +446,43 @@ RP_API int rp_nlhe_export(rp_nlhe* h, uint64_t cap, uint64_t* n, uint64_t* past,
 RP_API int rp_nlhe_import(rp_nlhe* h, uint64_t n, const uint64_t* past, const uint32_t* present, const uint64_t* choices,
                           const rp_encounter* enc, uint64_t epoch);
 
+/* THE TABLE ITSELF ON THE DEVICE (csrc/nlmc_table.hpp): the reference's profile is a HashMap that grows by itself
+ * (mccfr/src/strategy/macros.rs:13-16); here the table has 2^cap_log2 slots, and these five calls size it, grow it and move a blueprint
+ * in and out of it without the host walking a slot.  Each answers RP_ERR_INVALID for a NULL handle before a device is touched.
+ * rp_nlhe_export and rp_nlhe_import above stay what they are (host probing, their slot placement).
+ * rp_nlhe_capacity: *cap_log2 = the table's size now, *keys = the infosets in it (rp_nlhe_counters' third value; read from the device
+ *   only if something inserted without bringing the count to the host).  Either output may be NULL.
+ * rp_nlhe_resize: the handle continues on a fresh table of 2^new_cap_log2 slots, new_cap_log2 in 8..30 (else RP_ERR_INVALID): new key
+ *   slots, key count and profile rows; every infoset is rehashed on the device — its key to the new table's probe position, its
+ *   144-byte row verbatim.  Epoch, counters, settings and every answer by key are unchanged; slot ORDER (rp_nlhe_export's order, row
+ *   numbers of rp_nlhe_batch) is the new table's.  Shrinking is allowed while 2 * keys <= new slots, otherwise RP_ERR_CAPACITY before
+ *   anything is allocated; the same size is RP_OK without work.  BOTH tables are resident during the call: 176 B x (old + new slots)
+ *   of device memory; a failed allocation is RP_ERR_HIP and the handle stays on its old table.  The call synchronises the handle's
+ *   stream (the old arrays are freed only after the rehash has run).
+ * rp_nlhe_set_growth: off at creation.  With max_cap_log2 in cap_log2..30 (0 switches it off again; anything else RP_ERR_INVALID),
+ *   rp_nlhe_step — and so rp_nlhe_train — and rp_nlhe_import_device resize the table before they run: to the smallest doubling, at
+ *   most 2^max_cap_log2, with 2 * (keys + headroom) <= slots.  headroom = 0 selects batch x 1 536: every key a step inserts belongs
+ *   to a decision node it grew, and 1 536 nodes per tree is the budget of one pass (a batch traversed in several passes may grow
+ *   more).  rp_nlhe_import_device uses its n in place of headroom.  `keys` is the count the step before brought to the host with its
+ *   own counts: no synchronisation per step is added.  A step that fills the table anyway fails as it always did (RP_ERR_CAPACITY,
+ *   flag 32).  rp_nlhe_step_local / _apply / _comm do NOT grow: a sharded caller resizes every rank between steps.
+ * rp_nlhe_export_device: rp_nlhe_export into DEVICE arrays — the same infosets in the same (slot) order with the same bytes: count per
+ *   segment of 1 024 slots, scan, scatter.  *n (host) = the infosets in the table; the first min(cap, *n) are written; with cap = 0 or
+ *   any of the four arrays NULL only *n is answered.  enc_dev: 16-byte aligned.  Ordered after earlier work on the handle's stream;
+ *   synchronises it once, for *n.
+ * rp_nlhe_import_device: rp_nlhe_import from DEVICE arrays: every key is found or inserted on the device (the table's own hash and
+ *   linear probe; an inserted slot carries born = 0) and its row written whole from enc_dev[i][0..9).  A key named more than once
+ *   keeps its LAST Encounters.  Maintains the key count, sets the epoch, synchronises once.  If the probe runs out of slots the call
+ *   answers RP_ERR_CAPACITY and the epoch is unchanged; the keys inserted before that STAY, with their Encounters.  n = 0 sets the
+ *   epoch without a launch. */
+RP_API int rp_nlhe_capacity(rp_nlhe* h, uint32_t* cap_log2, uint64_t* keys);
+RP_API int rp_nlhe_resize(rp_nlhe* h, uint32_t new_cap_log2);
+RP_API int rp_nlhe_set_growth(rp_nlhe* h, uint32_t max_cap_log2, uint64_t headroom);
+RP_API int rp_nlhe_export_device(rp_nlhe* h, uint64_t cap, uint64_t* n /* host */, uint64_t* past_dev, uint32_t* present_dev,
+                                 uint64_t* choices_dev, rp_encounter* enc_dev /* [cap][9] */);
+RP_API int rp_nlhe_import_device(rp_nlhe* h, uint64_t n, const uint64_t* past_dev, const uint32_t* present_dev,
+                                 const uint64_t* choices_dev, const rp_encounter* enc_dev /* [n][9] */, uint64_t epoch);
+
 /* What the blueprint says, asked BY KEY (Brain::policy, parlor/src/players/brain.rs:45-55; Source::strategy / Source::memory,
  * nlhe/src/source.rs:40-87): n infosets (past[i], present[i], choices[i]) against the device-resident table, read-only — nothing is
  * inserted, epoch / counters / keys are unchanged, and no query can fail a later step.

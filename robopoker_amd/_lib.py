@@ -454,6 +454,11 @@ _SIGNATURES = {
     "rp_nlhe_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "rp_nlhe_export": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rp_nlhe_import": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "rp_nlhe_capacity": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "rp_nlhe_resize": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rp_nlhe_set_growth": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64]),
+    "rp_nlhe_export_device": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rp_nlhe_import_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     "rp_nlhe_policy": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64] + [C.c_void_p] * 7),
     "rp_nlhe_policy_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64] + [C.c_void_p] * 7),
     "rp_nlhe_memory": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6),

@@ -43,6 +43,7 @@
 #include "nlmc_match.hpp"
 #include "nlmc_search.hpp"
 #include "nlmc_census.hpp"
+#include "nlmc_table.hpp"
 #include "../../include/rp_libm_glibc.h"
 #include "rp_internal.h"
 #include "sortscan.hpp"
@@ -134,6 +135,15 @@ struct rp_nlhe {
     void* census_scratch = nullptr;  // rp_nlhe_table_census: one partial per segment of the table (grow-only)
     size_t census_scratch_bytes = 0;
     uint32_t grid_cap = 16384;  // workgroups of the grid-stride kernels (measured: 1024 -14 %, 4096 -4 %)
+    // the table itself (nlmc_table.hpp).  keys: *tab.n_keys as the host last saw it — with the counts a traversal brings to the host
+    // anyway, after an import, after a resize; keys_valid is false behind anything that may have inserted without telling (a failed
+    // step, rp_nlhe_step_apply), and the next reader then asks the device once.
+    uint64_t keys = 0;
+    bool keys_valid = true;
+    uint32_t grow_max = 0;       // rp_nlhe_set_growth: 0 = off
+    uint64_t grow_headroom = 0;  // 0 = the default, nl_default_headroom
+    void* table_scratch = nullptr;  // segment counts and offsets of an export, the rows of an import chunk, their flag words (grow-only)
+    size_t table_scratch_bytes = 0;
 };
 
 namespace {
@@ -234,6 +244,7 @@ int nl_wait_post(rp_nlhe* h, hipStream_t st) {
 // *flags: the traversal's error flags when the return code is RP_ERR_CAPACITY (the caller retries a spent node budget in chunks)
 int nl_traverse_chunk(rp_nlhe* h, uint32_t lo, uint32_t B, uint32_t d_base, uint32_t* n_dec, uint32_t* n_nod, uint32_t* n_lev, uint32_t* flags) {
     hipStream_t st = rp::profile_stream(h->prof);
+    h->keys_valid = false;  // until this pass has brought the table's key count to the host with its own counts
     NlNodes& lv = h->lv;
     NlParams prm = h->prm;
     prm.batch = B;
@@ -291,6 +302,8 @@ int nl_traverse_chunk(rp_nlhe* h, uint32_t lo, uint32_t B, uint32_t d_base, uint
                 return rp::fail(RP_ERR_CAPACITY, "rp_nlhe: %llu Decisions in one batch exceed the buffer (%u)", (unsigned long long)d_base + total0, h->out_cap);
             nl_clock_end(h, 3);
             HIP_TRY(hipGetLastError());
+            h->keys = h->post->keys;
+            h->keys_valid = true;
             *n_dec = total0;
             *n_nod = ctl.n_nodes;
             *n_lev = ctl.pad[0];
@@ -342,8 +355,10 @@ int nl_traverse_chunk(rp_nlhe* h, uint32_t lo, uint32_t B, uint32_t d_base, uint
     HIP_TRY(rp::ss::exclusive_scan<uint32_t>(lv.t_dcount, lv.t_doff, B, h->d_scan, st, h->d_total));
     HIP_TRY(hipGetLastError());
     uint32_t total[2] = {0, 0};
+    unsigned int keys_now = 0;  // no launch behind this point inserts
     HIP_TRY(hipMemcpyAsync(total, h->d_total, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&ctl, lv.ctl, sizeof(NlCtl), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&keys_now, h->tab.n_keys, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (ctl.err) {
         *flags = ctl.err;
@@ -362,6 +377,8 @@ int nl_traverse_chunk(rp_nlhe* h, uint32_t lo, uint32_t B, uint32_t d_base, uint
     hipLaunchKernelGGL(k_nl_emit, wide, blk, 0, st, lv, h->tab, total[1], d_base, lo, h->out_cap, h->out, 0u, (const float*)(lv.ex_k ? lv.wval : nullptr));
     nl_clock_end(h, 3);
     HIP_TRY(hipGetLastError());
+    h->keys = keys_now;
+    h->keys_valid = true;
     *n_dec = total[0];
     *n_nod = n_nodes;
     *n_lev = levels;
@@ -404,6 +421,8 @@ int nl_traverse_levels(rp_nlhe* h) {
     }
 }
 int nl_traverse(rp_nlhe* h) { return nl_traverse_levels(h); }
+int nl_grow_table(rp_nlhe* h, uint64_t headroom);  // with the table's own code, behind the census
+uint64_t nl_default_headroom(const rp_nlhe* h);
 }  // namespace
 
 extern "C" {
@@ -583,7 +602,7 @@ int rp_nlhe_destroy(rp_nlhe* h) {
     for (void* p : h->allocs) (void)hipFree(p);
     if (h->post) (void)hipHostFree(h->post);
     if (h->search_post) (void)hipHostFree(h->search_post);
-    for (void* p : {h->x_keys, h->x_counts, h->x_all, h->x_packed, h->depth_rows, h->subgame_rows, h->search_scratch, h->census_scratch})
+    for (void* p : {h->x_keys, h->x_counts, h->x_all, h->x_packed, h->depth_rows, h->subgame_rows, h->search_scratch, h->census_scratch, h->table_scratch})
         if (p) (void)hipFree(p);
     delete h;
     return RP_OK;
@@ -592,8 +611,8 @@ int rp_nlhe_destroy(rp_nlhe* h) {
 int rp_nlhe_step(rp_nlhe* h, rp_update_mode mode) {
     if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_step: NULL handle");
     HIP_TRY(hipSetDevice(h->device));
-    int rc = nl_traverse(h);
-    if (rc) return rc;
+    int rc = h->grow_max ? nl_grow_table(h, h->grow_headroom ? h->grow_headroom : nl_default_headroom(h)) : RP_OK;
+    if (rc || (rc = nl_traverse(h))) return rc;
     rp_decisions b{h->last_n, h->out.row, h->out.nact, h->out.expanded, h->out.regret, h->out.policy, h->out.payoff};
     nl_clock_begin(h, 4);
     rc = rp_profile_apply(h->prof, &b, mode);
@@ -797,6 +816,8 @@ int rp_nlhe_import(rp_nlhe* h, uint64_t n, const uint64_t* past, const uint32_t*
     HIP_TRY(hipMemcpy(&k, h->tab.n_keys, 4, hipMemcpyDeviceToHost));
     k += added;
     HIP_TRY(hipMemcpy(h->tab.n_keys, &k, 4, hipMemcpyHostToDevice));
+    h->keys = k;
+    h->keys_valid = true;
     if ((rc = rp_profile_set_rows(h->prof, n, rows.data(), enc))) return rc;
     return rp_profile_set_epoch(h->prof, epoch);
 }
@@ -844,6 +865,7 @@ int rp_nlhe_step_apply(rp_nlhe* h, void* entries_dev, const uint64_t* past_dev, 
                            reinterpret_cast<unsigned char*>(entries_dev), (uint32_t)eb, n_entries, past_dev, present_dev, choices_dev,
                            nl_next_tag(h), h->d_remap_err);
         HIP_TRY(hipGetLastError());
+        h->keys_valid = false;
     }
     return rp_profile_fold(h->prof, entries_dev, n_entries);
 }
@@ -2011,6 +2033,180 @@ int rp_census_grid_usage(const rp_census* c, rp_census_grid* rows, uint32_t* n) 
     }
     *n = k;
     return RP_OK;
+}
+
+}  // extern "C"
+
+// ---- the table itself (nlmc_table.hpp): compaction, bulk insertion, rehash into another size, growth in front of a step
+namespace {
+int nl_keys(rp_nlhe* h, uint64_t* keys) {
+    if (!h->keys_valid) {
+        hipStream_t st = rp::profile_stream(h->prof);
+        unsigned int k = 0;
+        HIP_TRY(hipMemcpyAsync(&k, h->tab.n_keys, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        h->keys = k;
+        h->keys_valid = true;
+    }
+    *keys = h->keys;
+    return RP_OK;
+}
+// every key a step inserts belongs to a decision node it grew, and a step that stays within one pass grows at most the 1 536 nodes
+// per tree the header names as its budget
+uint64_t nl_default_headroom(const rp_nlhe* h) { return (uint64_t)h->batch * 1536u; }
+uint32_t nt_blocks(const rp_nlhe* h, uint64_t lanes) {
+    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((lanes + NT_BLOCK - 1u) / NT_BLOCK, 1u), h->grid_cap);
+}
+// The handle moves onto a fresh table of 2^new_log2 slots.  Like nl_grow's regions, the old arrays may still be read by launches
+// queued earlier, and the rehash itself reads them: they are freed only after the stream has passed the rehash.
+int nl_resize(rp_nlhe* h, uint32_t new_log2) {
+    if (new_log2 == h->cap_log2) return RP_OK;
+    uint64_t keys = 0;
+    int rc = nl_keys(h, &keys);
+    if (rc) return rc;
+    const uint64_t slots = 1ull << new_log2;
+    if (2u * keys > slots)
+        return rp::fail(RP_ERR_CAPACITY, "rp_nlhe_resize: %llu infosets do not fit 2^%u slots at a fill of one half", (unsigned long long)keys, new_log2);
+    hipStream_t st = rp::profile_stream(h->prof);
+    NlTable to{};
+    to.mask = (uint32_t)(slots - 1u);
+    void *p_slots = nullptr, *p_keys = nullptr, *p_rows = nullptr;
+    const size_t row_bytes = (size_t)slots * 4u * NLMC_A * sizeof(float);
+    hipError_t e = hipMalloc(&p_slots, (size_t)slots * sizeof(NlSlot));
+    if (e == hipSuccess) e = hipMalloc(&p_keys, 8);  // the key count and, behind it, the rehash's error flags
+    if (e == hipSuccess) e = hipMalloc(&p_rows, row_bytes);
+    // a fresh table: empty slots, zero rows (the NLHE profile's default regrets are written by the insertion, not by the table)
+    if (e == hipSuccess) e = hipMemsetAsync(p_slots, 0, (size_t)slots * sizeof(NlSlot), st);
+    if (e == hipSuccess) e = hipMemsetAsync(p_keys, 0, 8, st);
+    if (e == hipSuccess) e = hipMemsetAsync(p_rows, 0, row_bytes, st);
+    uint32_t err = 0;
+    if (e == hipSuccess) {
+        to.slots = static_cast<NlSlot*>(p_slots);
+        to.n_keys = static_cast<unsigned int*>(p_keys);
+        to.rows = static_cast<float*>(p_rows);
+        hipLaunchKernelGGL(k_nl_table_rehash, dim3(nt_blocks(h, (uint64_t)h->tab.mask + 1u)), dim3(NT_BLOCK), 0, st, h->tab, to, to.n_keys + 1);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&err, to.n_keys + 1, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess || err) {  // the handle stays on its old table
+        (void)hipStreamSynchronize(st);
+        for (void* p : {p_slots, p_keys, p_rows})
+            if (p) (void)hipFree(p);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return rp::fail(RP_ERR_HIP, "rp_nlhe_resize: %s (a table of 2^%u slots needs %llu bytes beside the one in use)", hipGetErrorString(e),
+                            new_log2, (unsigned long long)(slots * 176u));
+        }
+        return rp::fail(RP_ERR_CAPACITY, "rp_nlhe_resize: the new table filled up (flags %u)", err);
+    }
+    void *old_slots = h->tab.slots, *old_keys = h->tab.n_keys;
+    void* old_rows = rp::profile_swap_table(h->prof, to.rows, slots);
+    h->allocs.erase(std::remove_if(h->allocs.begin(), h->allocs.end(), [&](void* p) { return p == old_slots || p == old_keys; }), h->allocs.end());
+    h->allocs.push_back(p_slots);
+    h->allocs.push_back(p_keys);
+    h->tab = to;
+    h->cap_log2 = new_log2;
+    for (void* p : {old_slots, old_keys, old_rows}) (void)hipFree(p);  // the stream has passed the rehash (synchronised above)
+    return RP_OK;
+}
+int nl_grow_table(rp_nlhe* h, uint64_t headroom) {
+    if (!h->grow_max || h->cap_log2 >= h->grow_max) return RP_OK;
+    uint64_t keys = 0;
+    int rc = nl_keys(h, &keys);
+    if (rc) return rc;
+    uint32_t want = h->cap_log2;
+    while (2u * (keys + headroom) > (1ull << want) && want < h->grow_max) want += 1;
+    return nl_resize(h, want);  // the doublings in one rehash
+}
+}  // namespace
+
+extern "C" {
+
+int rp_nlhe_capacity(rp_nlhe* h, uint32_t* cap_log2, uint64_t* keys) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_capacity: NULL handle");
+    if (cap_log2) *cap_log2 = h->cap_log2;
+    if (!keys) return RP_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    return nl_keys(h, keys);
+}
+
+int rp_nlhe_resize(rp_nlhe* h, uint32_t new_cap_log2) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_resize: NULL handle");
+    if (new_cap_log2 < 8 || new_cap_log2 > 30) return rp::fail(RP_ERR_INVALID, "rp_nlhe_resize: cap_log2 %u outside 8..30", new_cap_log2);
+    HIP_TRY(hipSetDevice(h->device));
+    return nl_resize(h, new_cap_log2);
+}
+
+int rp_nlhe_set_growth(rp_nlhe* h, uint32_t max_cap_log2, uint64_t headroom) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_set_growth: NULL handle");
+    if (max_cap_log2 != 0 && (max_cap_log2 < h->cap_log2 || max_cap_log2 > 30))
+        return rp::fail(RP_ERR_INVALID, "rp_nlhe_set_growth: max_cap_log2 %u outside %u..30 (0 switches growth off)", max_cap_log2, h->cap_log2);
+    h->grow_max = max_cap_log2;
+    h->grow_headroom = headroom;
+    return RP_OK;
+}
+
+int rp_nlhe_export_device(rp_nlhe* h, uint64_t cap, uint64_t* n, uint64_t* past_dev, uint32_t* present_dev, uint64_t* choices_dev,
+                          rp_encounter* enc_dev) {
+    if (!h || !n) return rp::fail(RP_ERR_INVALID, "rp_nlhe_export_device: NULL argument");
+    if ((uintptr_t)enc_dev % 16u) return rp::fail(RP_ERR_INVALID, "rp_nlhe_export_device: enc_dev is not 16-byte aligned");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    const uint64_t slots = 1ull << h->cap_log2;
+    const uint32_t nseg = (uint32_t)((slots + NT_SEGMENT - 1u) / NT_SEGMENT);
+    // [counts nseg][offsets nseg][total, pad][the scan's scratch]
+    const size_t words = (size_t)2 * nseg + 2;
+    int rc = nl_grow(h->table_scratch, h->table_scratch_bytes, words * 4u + rp::ss::scan_scratch_bytes(nseg), st);
+    if (rc) return rc;
+    uint32_t* seg_count = static_cast<uint32_t*>(h->table_scratch);
+    uint32_t *seg_off = seg_count + nseg, *total = seg_off + nseg;
+    const dim3 grid(nt_blocks(h, (uint64_t)nseg * 64u));
+    hipLaunchKernelGGL(k_nl_table_count, grid, dim3(NT_BLOCK), 0, st, h->tab, nseg, seg_count);
+    HIP_TRY(rp::ss::exclusive_scan<uint32_t>(seg_count, seg_off, nseg, total + 2, st, total));
+    if (cap && past_dev && present_dev && choices_dev && enc_dev)
+        hipLaunchKernelGGL(k_nl_table_compact, grid, dim3(NT_BLOCK), 0, st, h->tab, nseg, seg_off, cap, past_dev, present_dev, choices_dev, enc_dev);
+    HIP_TRY(hipGetLastError());
+    uint32_t found = 0;
+    HIP_TRY(hipMemcpyAsync(&found, total, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *n = found;
+    return RP_OK;
+}
+
+int rp_nlhe_import_device(rp_nlhe* h, uint64_t n, const uint64_t* past_dev, const uint32_t* present_dev, const uint64_t* choices_dev,
+                          const rp_encounter* enc_dev, uint64_t epoch) {
+    if (!h || (n && (!past_dev || !present_dev || !choices_dev || !enc_dev))) return rp::fail(RP_ERR_INVALID, "rp_nlhe_import_device: NULL argument");
+    if ((uintptr_t)enc_dev % 16u) return rp::fail(RP_ERR_INVALID, "rp_nlhe_import_device: enc_dev is not 16-byte aligned");
+    if (n == 0) return rp_profile_set_epoch(h->prof, epoch);
+    HIP_TRY(hipSetDevice(h->device));
+    int rc = h->grow_max ? nl_grow_table(h, n) : RP_OK;
+    if (rc) return rc;
+    hipStream_t st = rp::profile_stream(h->prof);
+    // items per pair of launches: a claim is the item's index in its chunk + 1 in 32 bits.  RP_NLHE_IMPORT_CHUNK (tests): a smaller one.
+    uint64_t chunk = 1ull << 26;
+    if (const char* env = getenv("RP_NLHE_IMPORT_CHUNK")) chunk = (uint64_t)std::min(1 << 26, std::max(1, atoi(env)));
+    chunk = std::min(chunk, n);
+    if ((rc = nl_grow(h->table_scratch, h->table_scratch_bytes, (size_t)(chunk + 2u) * 4u, st))) return rc;
+    uint32_t* rows = static_cast<uint32_t*>(h->table_scratch);
+    uint32_t* flags = rows + chunk;  // [0] error flags, [1] unused
+    HIP_TRY(hipMemsetAsync(flags, 0, 8, st));
+    h->keys_valid = false;
+    rc = nl_chunks(n, chunk, [&](uint64_t at, uint32_t m) {
+        const dim3 grid(nt_blocks(h, m));
+        hipLaunchKernelGGL(k_nl_table_find, grid, dim3(NT_BLOCK), 0, st, h->tab, m, past_dev + at, present_dev + at, choices_dev + at, rows, flags);
+        hipLaunchKernelGGL(k_nl_table_write, grid, dim3(NT_BLOCK), 0, st, h->tab, m, rows, enc_dev + at * NLMC_A);
+    });
+    if (rc) return rc;
+    uint32_t err = 0;
+    unsigned int keys = 0;
+    HIP_TRY(hipMemcpyAsync(&err, flags, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&keys, h->tab.n_keys, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    h->keys = keys;
+    h->keys_valid = true;
+    if (err) return rp::fail(RP_ERR_CAPACITY, "rp_nlhe_import_device: infoset table full (flags %u; the keys inserted before it stay)", err);
+    return rp_profile_set_epoch(h->prof, epoch);
 }
 
 }  // extern "C"

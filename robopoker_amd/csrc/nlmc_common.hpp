@@ -129,7 +129,9 @@ __device__ __forceinline__ uint32_t nl_peek32(const uint32_t* p) { return __hip_
 //     insertion (rows are 144 B, neighbours share lines) — an acquire fence drops it before the caller reads the row.  Keys from
 //     earlier launches need nothing: kernel boundaries already ordered their bytes.
 __device__ __forceinline__ uint32_t nl_row_of(const NlTable& t, uint64_t past, uint64_t choices, uint32_t present, uint64_t key_hash, uint32_t nch,
-                                              uint32_t tag, uint32_t* err, bool* settled = nullptr) {
+                                              uint32_t tag, uint32_t* err, bool* settled = nullptr, bool* inserted = nullptr) {
+    // *inserted (nlmc_table.hpp's bulk insertion): whether this lane inserted the key; the CALLER then counts it into *t.n_keys (one
+    // add per wavefront: millions of insertions in one launch would otherwise queue at that one word)
     // *settled: the key was found at its home slot by the optimistic read and was not born in this launch — row bytes a caller
     // loaded from the home slot BEFORE the probe (in parallel with it) are then the row's
     uint32_t s = (uint32_t)key_hash & t.mask, probes = 0, row = 0;
@@ -156,7 +158,8 @@ __device__ __forceinline__ uint32_t nl_row_of(const NlTable& t, uint64_t past, u
                 for (uint32_t a = 0; a < nch; ++a) r[a] = nl_default_regret((uint32_t)(choices >> (5u * a)) & 31u);
                 __threadfence();
                 atomicExch(&sl->state, 2u);
-                atomicAdd(t.n_keys, 1u);
+                if (inserted) *inserted = true;
+                else atomicAdd(t.n_keys, 1u);
                 row = s;
                 done = true;
             } else if (st == 2u) {

@@ -1057,11 +1057,12 @@ __device__ unsigned int g_nl_rec[2048 * 16];  // the last launch, per tree: tick
 // written into pinned host memory by the last workgroup of k_nl_tree, `seq` last; the host waits on that word.
 struct NlPost {
     uint32_t seq, total, err, n_nodes, levels, kinds[4], walker_kids;
+    uint32_t keys;  // infosets in the table behind this traversal's insertions (the growth rule of rp_nlhe_set_growth reads it)
 };
 // Every exit of k_nl_tree, by the whole workgroup: the workgroup that counts in last (ctl->pad[1]) scans the trees' Decisions counts
 // into their offsets, posts the batch's total and control block to the host and clears the block for the next step.
 template <uint32_t BT>
-__device__ __forceinline__ void nl_tree_exit(const NlNodes& nd, uint32_t B, uint32_t* total_out, NlPost* post, uint32_t seq) {
+__device__ __forceinline__ void nl_tree_exit(const NlNodes& nd, const unsigned int* n_keys, uint32_t B, uint32_t* total_out, NlPost* post, uint32_t seq) {
     __shared__ uint64_t x_wt[BT / 64u];
     __shared__ uint32_t x_last;
     __syncthreads();  // this workgroup's stores to the per-tree words are issued
@@ -1072,6 +1073,8 @@ __device__ __forceinline__ void nl_tree_exit(const NlNodes& nd, uint32_t B, uint
     __syncthreads();
     if (!x_last) return;
     __threadfence();  // the other workgroups' words
+    // the table's key count behind every insertion of this launch: asked for here, so that the scan below hides the way to L2
+    const uint32_t keys = threadIdx.x == 0 ? __hip_atomic_load(n_keys, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
     const uint32_t per = (B + BT - 1u) / BT, lo = min(B, threadIdx.x * per), hi = min(B, lo + per);
     uint64_t s = 0;
     for (uint32_t t = lo; t < hi; ++t) s += __hip_atomic_load(&nd.t_dcount[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1090,6 +1093,7 @@ __device__ __forceinline__ void nl_tree_exit(const NlNodes& nd, uint32_t B, uint
         post->levels = __hip_atomic_load(&ctl->pad[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         for (int k = 0; k < 4; ++k) post->kinds[k] = __hip_atomic_load(&ctl->kinds[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         post->walker_kids = __hip_atomic_load(&ctl->walker_kids, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        post->keys = keys;
         ctl->err = 0;
         ctl->n_nodes = 0;
         ctl->pad[0] = 0;
@@ -1229,7 +1233,7 @@ __global__ __launch_bounds__(BT) void k_nl_tree(NlParams p, NlTable t, NlNodes n
             nd.t_woff[tree] = tree * WC;
             nd.t_dcount[tree] = 0;
         }
-        nl_tree_exit<BT>(nd, gridDim.x, total_out, post, seq);
+        nl_tree_exit<BT>(nd, t.n_keys, gridDim.x, total_out, post, seq);
         return;
     }
     // ---- the sweeps: D(node) and subtree sizes bottom-up, creation indices top-down
@@ -1289,7 +1293,7 @@ __global__ __launch_bounds__(BT) void k_nl_tree(NlParams p, NlTable t, NlNodes n
     const uint32_t nw = s_nw;  // workgroup uniform (the barrier above)
     if (nw == 0 || nw > WC) {
         if (tid == 0) nd.t_dcount[tree] = 0;
-        nl_tree_exit<BT>(nd, gridDim.x, total_out, post, seq);
+        nl_tree_exit<BT>(nd, t.n_keys, gridDim.x, total_out, post, seq);
         return;
     }
     __syncthreads();  // t_woff[tree] and the walker list are read by other work-items below
@@ -1308,7 +1312,7 @@ __global__ __launch_bounds__(BT) void k_nl_tree(NlParams p, NlTable t, NlNodes n
         }
     }
 #endif
-    nl_tree_exit<BT>(nd, gridDim.x, total_out, post, seq);
+    nl_tree_exit<BT>(nd, t.n_keys, gridDim.x, total_out, post, seq);
 }
 
 }  // namespace rp

@@ -42,6 +42,7 @@ struct rp_profile;
 struct rp_lookup;
 namespace rp {
 float* profile_table(rp_profile* h);
+float* profile_swap_table(rp_profile* h, float* tab, uint64_t n_rows);
 ihipStream_t* profile_stream(rp_profile* h);
 uint64_t profile_epoch(const rp_profile* h);
 unsigned char* profile_entries(rp_profile* h);

@@ -867,6 +867,15 @@ namespace rp {
 
 // nlmc.hip: the NLHE traversal reads (and initialises the rows of) the table it feeds
 float* profile_table(rp_profile* h) { return h->tab; }
+// rp_nlhe_resize: the profile continues on a table of n_rows rows that the caller allocated with hipMalloc and filled on this
+// profile's stream; returns the table it had, which is the caller's to free once the stream has passed its last reader.  The
+// workspace is sized by the batch, not by the table, and stays.
+float* profile_swap_table(rp_profile* h, float* tab, uint64_t n_rows) {
+    float* old = h->tab;
+    h->tab = tab;
+    h->n_rows = n_rows;
+    return old;
+}
 hipStream_t profile_stream(rp_profile* h) { return h->stream; }
 uint64_t profile_epoch(const rp_profile* h) { return h->epoch; }
 unsigned char* profile_entries(rp_profile* h) { return h->entries; }  // the local summary buffer: max_batch entries

@@ -397,6 +397,46 @@ class NlheSolver:
         enc = np.ascontiguousarray(enc, dtype=ENC_DTYPE)
         _lib.check(self._lib.rp_nlhe_import(self._h, past.size, _p(past), _p(present), _p(choices), _p(enc), epoch))
 
+    # ---- the table itself on the device (include/rp_mi355x.h THE TABLE ITSELF ON THE DEVICE) ----
+    def capacity(self):
+        """(cap_log2, infosets in the table)"""
+        c, k = C.c_uint32(), C.c_uint64()
+        _lib.check(self._lib.rp_nlhe_capacity(self._h, C.byref(c), C.byref(k)))
+        return c.value, k.value
+
+    def resize(self, cap_log2: int):
+        """continue on a table of 2^cap_log2 slots, every infoset rehashed on the device (both tables resident during the call)"""
+        _lib.check(self._lib.rp_nlhe_resize(self._h, int(cap_log2)))
+
+    def set_growth(self, max_cap_log2: int, headroom: int = 0):
+        """``step`` / ``train`` / ``load_device`` double the table up to 2^max_cap_log2 while 2 * (keys + headroom) > slots; 0 = off"""
+        _lib.check(self._lib.rp_nlhe_set_growth(self._h, int(max_cap_log2), int(headroom)))
+
+    def export_device(self, cap=None):
+        """``export`` into torch tensors on the solver's device, in the same (slot) order: (past int64[m], present int32[m],
+        choices int64[m], enc uint8[m,9,16], n) — torch spells u64 / u32 as int64 / int32; ``enc.cpu().numpy().view(ENC_DTYPE)[..., 0]``.
+        n = the infosets in the table, m = min(cap, n) (cap None: all).  Synchronises the solver's stream."""
+        d = torch.device(f"cuda:{self.device}")
+        m = self.capacity()[1] if cap is None else min(int(cap), self.capacity()[1])
+        past, present, choices = (torch.empty(m, dtype=torch.int64, device=d), torch.empty(m, dtype=torch.int32, device=d),
+                                  torch.empty(m, dtype=torch.int64, device=d))
+        enc = torch.empty((m, A, ENC_DTYPE.itemsize), dtype=torch.uint8, device=d)
+        n = C.c_uint64()
+        torch.cuda.current_stream(d).synchronize()
+        _lib.check(self._lib.rp_nlhe_export_device(self._h, m, C.byref(n), _dptr(past, m), _dptr(present, m), _dptr(choices, m), _dptr(enc, m)))
+        return past, present, choices, enc, n.value
+
+    def load_device(self, past, present, choices, enc, epoch: int):
+        """``load`` from device tensors (``export_device``'s): keys found or inserted and rows written on the device; a key named more
+        than once keeps its last Encounters; sets the epoch.  Synchronises the solver's stream."""
+        dev, past, present, choices = self._keys(past, present, choices)
+        assert dev and isinstance(enc, torch.Tensor), "load_device takes device tensors (host arrays: load)"
+        enc = enc.contiguous()
+        n = past.numel()
+        assert enc.is_cuda and enc.element_size() * enc.numel() == n * A * ENC_DTYPE.itemsize
+        torch.cuda.current_stream(past.device).synchronize()
+        _lib.check(self._lib.rp_nlhe_import_device(self._h, n, _dptr(past, n), _dptr(present, n), _dptr(choices, n), _dptr(enc, n), int(epoch)))
+
     # ---- the read side: what the blueprint says about infosets given BY KEY (include/rp_mi355x.h rp_nlhe_policy / rp_nlhe_memory) ----
     def _keys(self, past, present, choices):
         """-> (on_device, past, present, choices): torch device tensors go to the _device forms, anything else through numpy to the host forms"""

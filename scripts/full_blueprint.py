@@ -8,7 +8,10 @@
       -> the hydrated solver answers policy queries by key for every exported infoset (rp_nlhe_policy)
       -> the next batch of both solvers is identical (every key, mask and the regret / policy bits).
 
-usage: full_blueprint.py [batch] [steps] [cap_log2]      -> one JSON object on stdout (stage times in seconds)"""
+usage: full_blueprint.py [batch] [steps] [cap_log2] [max_cap_log2]      -> one JSON object on stdout (stage times in seconds)
+
+With max_cap_log2 the trained solver starts two sizes below cap_log2 and grows in front of its steps (rp_nlhe_set_growth) up to
+2^max_cap_log2; the JSON then also says the table's size after every step.  Without it nothing changes."""
 import json
 import os
 import sys
@@ -26,6 +29,7 @@ from robopoker_amd.nlhe import NlheSolver  # noqa: E402
 batch = int(sys.argv[1]) if len(sys.argv) > 1 else 16384
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 16
 cap = int(sys.argv[3]) if len(sys.argv) > 3 else 26
+grow_to = int(sys.argv[4]) if len(sys.argv) > 4 else None
 say = lambda m: print(m, file=sys.stderr, flush=True)  # noqa: E731
 out = {"batch": batch, "steps": steps, "table_rows": 1 << cap, "solver": "Nlhe<LinearRegret, LinearWeight, PluribusSampling> (nlhe/src/lib.rs:86-90)"}
 t0 = time.perf_counter()
@@ -37,7 +41,11 @@ t0 = time.perf_counter()
 tables = [deuce.Lookup(name, art[name].obs, art[name].abstraction) for name in ("pref", "flop", "turn", "rive")]
 out["lookup_tables_s"] = time.perf_counter() - t0
 t0 = time.perf_counter()
-a = NlheSolver(cap_log2=cap, regret="linear", weight="linear", batch=batch, seed=2026, tables=tables, sampling="pluribus")
+a = NlheSolver(cap_log2=cap if grow_to is None else max(8, cap - 2), regret="linear", weight="linear", batch=batch, seed=2026, tables=tables,
+               sampling="pluribus")
+if grow_to is not None:
+    a.set_growth(grow_to)
+    out["growth"] = {"start_cap_log2": a.capacity()[0], "max_cap_log2": grow_to}
 out["solver_create_s"] = time.perf_counter() - t0
 per_step = []
 for s in range(steps):
@@ -45,6 +53,8 @@ for s in range(steps):
     a.step("composed")
     n, i, k = a.counters()  # synchronises
     per_step.append({"s": round(time.perf_counter() - t1, 4), "nodes": n, "infos": i, "infosets_in_table": k})
+    if grow_to is not None:
+        per_step[-1]["cap_log2"] = a.capacity()[0]
     say(f"step {s}: {per_step[-1]}")
 out["steps_s"] = sum(p["s"] for p in per_step)
 out["per_step"] = per_step
@@ -65,7 +75,7 @@ t0 = time.perf_counter()
 back = formats.read_blueprint(path)
 out["blueprint_read_s"] = time.perf_counter() - t0
 t0 = time.perf_counter()
-b = NlheSolver(cap_log2=cap, regret="linear", weight="linear", batch=batch, seed=2026, tables=tables, sampling="pluribus")
+b = NlheSolver(cap_log2=a.capacity()[0], regret="linear", weight="linear", batch=batch, seed=2026, tables=tables, sampling="pluribus")
 b.load(*back, epoch=a.epoch)
 out["hydrate_s"] = time.perf_counter() - t0
 os.remove(path)
