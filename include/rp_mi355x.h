@@ -275,6 +275,32 @@ typedef enum rp_dist_kind {
 RP_API int rp_mccfr_policy(rp_mccfr* h, uint32_t info, rp_dist_kind kind, float* out, uint32_t* n);
 /* Solver::exploitability (solver.rs:327-337) -> CfrNash::exploitability (nash.rs:31-38); host-side validation */
 RP_API int rp_mccfr_exploitability(rp_mccfr* h, float* out);
+/* ---- the same best response on the DEVICE (csrc/mccfr_nash.hpp): exploitability as a stopping rule -----------------------------
+ * CfrNash::exploitability restated as kernels over the expanded tree from exploit_root; every result below is bit for bit what
+ * rp_mccfr_exploitability computes on the host, which stays as the independent cross-check.  The expanded tree (one 16-byte record
+ * per node, its kids, the nodes by depth level, every infoset's nodes) is built on the host by the FIRST of these calls on a handle,
+ * uploaded once (that call synchronises) and kept until rp_mccfr_destroy: a handle that never asks pays nothing.  Limits: a tree of
+ * more than 2^24 nodes, or one whose arrays the device cannot hold (28 bytes per node + 4 per node and player), is RP_ERR_CAPACITY.
+ * Refused before a device is needed, rp_last_error naming the argument: NULL h, NULL out_dev / out, check_every == 0, a NaN target.
+ * A sharded handle (world > 1) is served like any other: the tables are replicas. */
+/* queued on the handle's stream, no host synchronisation; *out_dev (DEVICE memory) is written in stream order, so it reads the tables
+ * as every earlier step on this stream left them */
+RP_API int rp_mccfr_exploitability_device(rp_mccfr* h, float* out_dev);
+/* the same computation with its parts, to HOST memory (synchronises); any output may be NULL:
+ * values[n_players] = optimal_response_payoff per hero, choice[n_infos] = optimal_cfactual_choice (the action slot),
+ * cfv[n_infos][max_actions] = optimal_cfactual_payoff (slots past the infoset's actions are 0) */
+RP_API int rp_mccfr_best_response(rp_mccfr* h, float* exploitability, float* values, uint8_t* choice, float* cfv);
+/* 0 = one launch, one workgroup per hero, LDS; 1 = one launch per level; same bits.  0 is chosen when
+ * 4 * (tree nodes + 2 * n_infos * max_actions + n_infos) bytes are at most 64 KB (Leduc: 16 KB), 1 otherwise (wide Leduc: 249 KB);
+ * RP_NASH_VARIANT=one|levels, read when the tree is built, forces one (tests; "one" past the limit works out of device scratch). */
+RP_API int rp_mccfr_nash_variant(rp_mccfr* h, int* out);
+/* loop { check_every x Solver::step; exploitability on the device } until the FIRST check with exploitability < target or until
+ * max_steps (a multiple of check_every is not required: the last block is shorter and is checked too).  One 4-byte read of pinned
+ * host memory per check is the only host<->device traffic.  *steps = steps taken, *exploitability = the last check's value,
+ * *reached = 1 when it stopped on the target.  Uses the handle's current update mode and batch.  max_steps = 0 takes no step and
+ * checks the tables as they stand; the kernels' capacity flags are read once, on return (rp_mccfr_sync reads them per call). */
+RP_API int rp_mccfr_solve_to(rp_mccfr* h, float target, uint32_t check_every, uint64_t max_steps,
+                             uint64_t* steps, float* exploitability, int* reached);
 /* RefProf::sum_regret (book.rs:124-131), summed in (info, edge) order */
 RP_API int rp_mccfr_sum_regret(rp_mccfr* h, float* out);
 /* batch size may be changed between steps (no reference equivalent: batch_size is a const fn there) */

@@ -329,6 +329,11 @@ _SIGNATURES = {
     "rp_mccfr_import": (C.c_int, [C.c_void_p, C.POINTER(Encounter), C.c_uint64, C.c_uint64]),
     "rp_mccfr_policy": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "rp_mccfr_exploitability": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "rp_mccfr_exploitability_device": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rp_mccfr_best_response": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_float)]),
+    "rp_mccfr_nash_variant": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "rp_mccfr_solve_to": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_float),
+                                    C.POINTER(C.c_int)]),
     "rp_mccfr_sum_regret": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rp_mccfr_set_batch": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rp_mccfr_set_update_mode": (C.c_int, [C.c_void_p, C.c_int]),

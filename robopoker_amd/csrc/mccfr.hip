@@ -1,6 +1,6 @@
 // mccfr.hip — external-sampling MCCFR on MI355X (gfx950): the host side — the solver handle, the launchers, the rp_mccfr_* C ABI,
 // exploitability.  The kernels are in headers, in dependency order: mccfr_kernels.hpp (layouts, the per-cell map algebra and the
-// steps the kernels share), mccfr_traverse.hpp, mccfr_update.hpp, traverse_static.hpp.
+// steps the kernels share), mccfr_traverse.hpp, mccfr_update.hpp, traverse_static.hpp, mccfr_nash.hpp (the best response on the device).
 //
 // Reference path (crates/mccfr): Solver::step (solver/solver.rs:96-105) = batch() (:225-250) then the
 // sequential update_{regret,weight,payoff,visits} (:143-192).  MI355X mapping:
@@ -23,6 +23,7 @@
 #include "mccfr_traverse.hpp"
 #include "mccfr_update.hpp"
 #include "traverse_static.hpp"
+#include "mccfr_nash.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -110,6 +111,14 @@ struct rp_mccfr {
     int static_skel = 0;  // 0: none (k_traverse_lds / k_traverse), 1: KuhnSkel, 2: LeducSkel (traverse_static.hpp)
     bool profiling = false;
     KernelClock clk_traverse, clk_compact, clk_update;
+    // CfrNash on the device (mccfr_nash.hpp): built by the first call that asks (nash_prepare), kept until destroy
+    void* d_nash = nullptr;  // NashTree's arrays, then NashWork's
+    NashTree nt{};
+    NashWork nw{};
+    int nash_variant = -1;  // -1: not built; 0 one, 1 levels
+    bool nash_in_lds = false;
+    std::vector<uint32_t> nash_level_size;  // nodes per depth level: the grids of k_nash_level
+    float* nash_pinned = nullptr;  // rp_mccfr_solve_to: the check's value, mapped host memory
 };
 
 namespace {
@@ -823,6 +832,8 @@ int rp_mccfr_destroy(rp_mccfr* h) {
                     h->t.visits};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    if (h->d_nash) (void)hipFree(h->d_nash);
+    if (h->nash_pinned) (void)hipHostFree(h->nash_pinned);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return RP_OK;
@@ -1398,6 +1409,215 @@ int rp_mccfr_exploitability(rp_mccfr* h, float* out) {
     }
     *out = total / (float)h->tbl.n_players;
     return RP_OK;
+}
+
+}  // extern "C"
+
+// ---- CfrNash::exploitability on the device (mccfr_nash.hpp) ---------------------------------------------------------------------------
+namespace {
+
+size_t nash_one_bytes(const rp_mccfr* h, size_t n_nodes) {
+    return 4 * (n_nodes + 2 * (size_t)h->tbl.n_infos * h->tbl.max_actions + h->tbl.n_infos);
+}
+
+// The static data, on the first call that asks: the expansion (the loop of rp_mccfr_exploitability above, node for node), the level
+// lists, the spans, one upload.  Synchronises; every later call only launches.
+int nash_prepare(rp_mccfr* h) {
+    if (h->nash_variant >= 0) return RP_OK;
+    const char* force = getenv("RP_NASH_VARIANT");
+    if (force && std::string(force) != "one" && std::string(force) != "levels")
+        return rp::fail(RP_ERR_INVALID, "RP_NASH_VARIANT is '%s': one or levels", force);
+    // VanillaSampling tree in TreeBuilder's pop-last order (builder.rs:141-161)
+    std::vector<XNode> nodes;
+    std::vector<uint32_t> depth;
+    struct Leaf { uint32_t state; int32_t parent, edge; };
+    std::vector<Leaf> todo;
+    auto push = [&](uint32_t state, int32_t parent, int32_t edge) {
+        XNode nd{state, parent, edge, {}};
+        for (auto& k : nd.kids) k = -1;
+        nodes.push_back(nd);
+        depth.push_back(parent >= 0 ? depth[parent] + 1 : 0u);
+        const int32_t me = (int32_t)nodes.size() - 1;
+        if (parent >= 0) nodes[parent].kids[edge] = me;
+        const rp_state& st = h->states[state];
+        for (uint32_t k = 0; k < st.n_children; ++k) todo.push_back(Leaf{h->children[st.offset + k], me, (int32_t)k});
+    };
+    push(h->tbl.exploit_root, -1, -1);
+    while (!todo.empty()) {
+        if (nodes.size() >= NASH_MAX_NODES)
+            return rp::fail(RP_ERR_CAPACITY, "the tree from exploit_root has more than %u nodes: the best response on the device cannot hold it", NASH_MAX_NODES);
+        Leaf lf = todo.back();
+        todo.pop_back();
+        push(lf.state, lf.parent, lf.edge);
+    }
+    const size_t n = nodes.size(), NI = h->tbl.n_infos, cells = NI * h->tbl.max_actions, np = h->tbl.n_players;
+    uint32_t n_levels = 0;
+    for (uint32_t d : depth) n_levels = std::max(n_levels, d + 1);
+    const bool fits = nash_one_bytes(h, n) <= NASH_ONE_LDS_BYTES;
+    const int variant = force ? (std::string(force) == "one" ? 0 : 1) : (fits ? 0 : 1);
+    const bool in_lds = variant == 0 && fits;
+    // one image, in words: rec (16-byte records first), kids, level_nodes, level_off, span_nodes, span_off | avg (a copy per hero for
+    // k_nash_one<false>), cfv, values, expl, choice (bytes); v (not initialised) behind it
+    std::vector<uint32_t> img;
+    img.reserve(8 * n + 3 * cells + 2 * NI + n_levels + 64);
+    std::vector<uint32_t> level_off(n_levels + 1, 0u), span_off(NI + 1, 0u);
+    uint32_t kid0 = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const rp_state& st = h->states[nodes[i].state];
+        const uint32_t y = st.n_children == 0 ? st.offset : st.info;
+        img.insert(img.end(), {(uint32_t)st.turn | ((uint32_t)st.n_children << 8) | ((uint32_t)(nodes[i].edge < 0 ? 0 : nodes[i].edge) << 16), y,
+                               nodes[i].parent < 0 ? NASH_ROOT : (uint32_t)nodes[i].parent, kid0});
+        kid0 += st.n_children;
+        level_off[depth[i] + 1] += 1;
+        if (st.n_children != 0 && st.turn != RP_TURN_CHANCE) span_off[st.info + 1] += 1;
+    }
+    const size_t o_kids = img.size();
+    for (size_t i = 0; i < n; ++i)
+        for (uint32_t k = 0; k < h->states[nodes[i].state].n_children; ++k) img.push_back((uint32_t)nodes[i].kids[k]);
+    img.push_back(0u);  // a tree of one node has no kid
+    for (uint32_t l = 0; l < n_levels; ++l) level_off[l + 1] += level_off[l];
+    for (size_t i = 0; i < NI; ++i) span_off[i + 1] += span_off[i];
+    const size_t o_level_nodes = img.size();
+    img.resize(img.size() + n);
+    {
+        std::vector<uint32_t> at(level_off.begin(), level_off.end() - 1);
+        for (size_t i = 0; i < n; ++i) img[o_level_nodes + at[depth[i]]++] = (uint32_t)i;  // ascending node index inside a level
+    }
+    const size_t o_level_off = img.size();
+    img.insert(img.end(), level_off.begin(), level_off.end());
+    const size_t o_span_nodes = img.size();
+    img.resize(img.size() + span_off[NI] + 1);
+    {
+        std::vector<uint32_t> at(span_off.begin(), span_off.end() - 1);
+        for (size_t i = 0; i < n; ++i) {
+            const rp_state& st = h->states[nodes[i].state];
+            if (st.n_children != 0 && st.turn != RP_TURN_CHANCE) img[o_span_nodes + at[st.info]++] = (uint32_t)i;  // ascending node index
+        }
+    }
+    const size_t o_span_off = img.size();
+    img.insert(img.end(), span_off.begin(), span_off.end());
+    const size_t o_avg = img.size(), avg_words = (variant == 0 && !in_lds ? np : 1) * cells;
+    const size_t o_cfv = o_avg + avg_words, o_values = o_cfv + cells, o_expl = o_values + np, o_choice = o_expl + 1;
+    img.resize(o_choice + (NI + 3) / 4, 0u);
+    const size_t o_v = img.size(), v_words = in_lds ? 0 : np * n;
+    void* d = nullptr;
+    if (hipMalloc(&d, (o_v + v_words) * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return rp::fail(RP_ERR_CAPACITY, "the best response on the device needs %zu bytes for a tree of %zu nodes", (o_v + v_words) * 4, n);
+    }
+    if (hipMemcpy(d, img.data(), img.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        return rp::fail(RP_ERR_HIP, "nash_prepare: the upload of the tree failed");
+    }
+    uint32_t* w = reinterpret_cast<uint32_t*>(d);
+    h->d_nash = d;
+    h->nt = NashTree{reinterpret_cast<const uint4*>(w), w + o_kids, w + o_level_nodes, w + o_level_off, w + o_span_nodes, w + o_span_off,
+                     (uint32_t)n, n_levels};
+    h->nw = NashWork{reinterpret_cast<float*>(w + o_avg), reinterpret_cast<float*>(w + o_cfv), reinterpret_cast<uint8_t*>(w + o_choice),
+                     reinterpret_cast<float*>(w + o_values), reinterpret_cast<float*>(w + o_expl),
+                     v_words ? reinterpret_cast<float*>(w + o_v) : nullptr};
+    h->nash_level_size.resize(n_levels);
+    for (uint32_t l = 0; l < n_levels; ++l) h->nash_level_size[l] = level_off[l + 1] - level_off[l];
+    h->nash_in_lds = in_lds;
+    h->nash_variant = variant;
+    return RP_OK;
+}
+
+// every phase of one call, queued on the handle's stream; `out_dev` (may be NULL) receives the exploitability, as does NashWork::expl
+int launch_nash(rp_mccfr* h, float* out_dev) {
+    int rc = nash_prepare(h);
+    if (rc) return rc;
+    const NashTree& T = h->nt;
+    const uint32_t np = h->tbl.n_players, NI = h->tbl.n_infos, cells = NI * h->tbl.max_actions;
+    const auto blocks = [](uint32_t n) { return (n + NASH_THREADS - 1) / NASH_THREADS; };
+    if (h->nash_variant == 0) {
+        if (h->nash_in_lds)
+            hipLaunchKernelGGL((k_nash_one<true>), dim3(np), dim3(NASH_ONE_THREADS), nash_one_bytes(h, T.n_nodes), h->stream, T, h->g, h->t, h->nw);
+        else
+            hipLaunchKernelGGL((k_nash_one<false>), dim3(np), dim3(NASH_ONE_THREADS), 0, h->stream, T, h->g, h->t, h->nw);
+        hipLaunchKernelGGL(k_nash_final, dim3(1), dim3(1), 0, h->stream, h->g, h->nw, h->nw.values, (size_t)1, out_dev);
+    } else {
+        hipLaunchKernelGGL(k_nash_avg, dim3(blocks(NI)), dim3(NASH_THREADS), 0, h->stream, h->g, h->t, h->nw);
+        for (uint32_t level = T.n_levels; level-- > 0;)
+            hipLaunchKernelGGL((k_nash_level<false>), dim3(blocks(h->nash_level_size[level]), np), dim3(NASH_THREADS), 0, h->stream, T, h->g, h->nw, level);
+        hipLaunchKernelGGL(k_nash_term, dim3(blocks(T.n_nodes), np), dim3(NASH_THREADS), 0, h->stream, T, h->g, h->nw);
+        hipLaunchKernelGGL(k_nash_cfv, dim3(blocks(cells)), dim3(NASH_THREADS), 0, h->stream, T, h->g, h->nw);
+        hipLaunchKernelGGL(k_nash_choice, dim3(blocks(NI)), dim3(NASH_THREADS), 0, h->stream, h->g, h->nw);
+        for (uint32_t level = T.n_levels; level-- > 0;)
+            hipLaunchKernelGGL((k_nash_level<true>), dim3(blocks(h->nash_level_size[level]), np), dim3(NASH_THREADS), 0, h->stream, T, h->g, h->nw, level);
+        hipLaunchKernelGGL(k_nash_final, dim3(1), dim3(1), 0, h->stream, h->g, h->nw, h->nw.v, (size_t)T.n_nodes, out_dev);
+    }
+    HIP_TRY(hipGetLastError());
+    return RP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rp_mccfr_exploitability_device(rp_mccfr* h, float* out_dev) {
+    if (!out_dev) return rp::fail(RP_ERR_INVALID, "rp_mccfr_exploitability_device: out_dev is NULL");
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_mccfr_exploitability_device: h is NULL");
+    int rc = set_device(h);
+    if (rc) return rc;
+    return launch_nash(h, out_dev);
+}
+
+int rp_mccfr_best_response(rp_mccfr* h, float* exploitability, float* values, uint8_t* choice, float* cfv) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_mccfr_best_response: h is NULL");
+    int rc = set_device(h);
+    if (rc) return rc;
+    if ((rc = launch_nash(h, nullptr))) return rc;
+    const size_t NI = h->tbl.n_infos;
+    if (exploitability) HIP_TRY(hipMemcpyAsync(exploitability, h->nw.expl, 4, hipMemcpyDeviceToHost, h->stream));
+    if (values) HIP_TRY(hipMemcpyAsync(values, h->nw.values, 4 * (size_t)h->tbl.n_players, hipMemcpyDeviceToHost, h->stream));
+    if (choice) HIP_TRY(hipMemcpyAsync(choice, h->nw.choice, NI, hipMemcpyDeviceToHost, h->stream));
+    if (cfv) HIP_TRY(hipMemcpyAsync(cfv, h->nw.cfv, 4 * NI * h->tbl.max_actions, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return RP_OK;
+}
+
+int rp_mccfr_nash_variant(rp_mccfr* h, int* out) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_mccfr_nash_variant: h is NULL");
+    if (!out) return rp::fail(RP_ERR_INVALID, "rp_mccfr_nash_variant: out is NULL");
+    int rc = set_device(h);
+    if (rc) return rc;
+    if ((rc = nash_prepare(h))) return rc;
+    *out = h->nash_variant;
+    return RP_OK;
+}
+
+int rp_mccfr_solve_to(rp_mccfr* h, float target, uint32_t check_every, uint64_t max_steps, uint64_t* steps, float* exploitability,
+                      int* reached) {
+    if (check_every == 0) return rp::fail(RP_ERR_INVALID, "rp_mccfr_solve_to: check_every must be > 0");
+    if (target != target) return rp::fail(RP_ERR_INVALID, "rp_mccfr_solve_to: target is NaN");
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_mccfr_solve_to: h is NULL");
+    int rc = set_device(h);
+    if (rc) return rc;
+    if (h->mode == RP_UPDATE_COMPOSED && (rc = composed_supported(h))) return rc;
+    if ((rc = nash_prepare(h))) return rc;
+    if (!h->nash_pinned) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->nash_pinned), 4, hipHostMallocMapped));
+    void* pinned_dev = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(&pinned_dev, h->nash_pinned, 0));
+    uint64_t done = 0;
+    float value = 0.0f;
+    int hit = 0;
+    do {  // max_steps = 0: no step, one check of the table as it stands
+        const uint32_t n = (uint32_t)std::min<uint64_t>(check_every, max_steps - done);
+        for (uint32_t i = 0; i < n; ++i)
+            if ((rc = enqueue_step(h))) return rc;
+        done += n;
+        if ((rc = launch_nash(h, reinterpret_cast<float*>(pinned_dev)))) return rc;
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        value = *reinterpret_cast<volatile float*>(h->nash_pinned);
+        hit = value < target ? 1 : 0;
+    } while (!hit && done < max_steps);
+    if (steps) *steps = done;
+    if (exploitability) *exploitability = value;
+    if (reached) *reached = hit;
+    rc = check_device_errors(h);  // the capacity flags of the steps, once, as rp_mccfr_sync reads them
+    clock_drain_all(h);
+    return rc;
 }
 
 }  // extern "C"

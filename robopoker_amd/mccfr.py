@@ -103,6 +103,36 @@ class Solver:
         _lib.check(self._lib.rp_mccfr_exploitability(self._h, C.byref(out)))
         return out.value
 
+    # ---- CfrNash on the device (csrc/mccfr_nash.hpp): the same bits as exploitability(), in stream order --------------------------
+    def exploitability_device(self, out_dev_ptr: int):
+        """queues the best response on the solver's stream; one f32 lands at ``out_dev_ptr`` (device memory), no host sync"""
+        _lib.check(self._lib.rp_mccfr_exploitability_device(self._h, C.c_void_p(out_dev_ptr)))
+
+    def best_response(self) -> dict:
+        """``exploitability`` with its parts: ``values`` [n_players] (optimal_response_payoff), ``choice`` [n_infos]
+        (optimal_cfactual_choice, the action slot), ``cfv`` [n_infos, max_actions] (optimal_cfactual_payoff)"""
+        t = self.game.table
+        e = C.c_float()
+        values = np.zeros(t.n_players, dtype=np.float32)
+        choice = np.zeros(t.n_infos, dtype=np.uint8)
+        cfv = np.zeros((t.n_infos, t.max_actions), dtype=np.float32)
+        _lib.check(self._lib.rp_mccfr_best_response(self._h, C.byref(e), values.ctypes.data_as(C.POINTER(C.c_float)),
+                                                    choice.ctypes.data_as(C.POINTER(C.c_uint8)), cfv.ctypes.data_as(C.POINTER(C.c_float))))
+        return {"exploitability": np.float32(e.value), "values": values, "choice": choice, "cfv": cfv}
+
+    def nash_variant(self) -> str:
+        """the launch shape of the device best response: "one" (one workgroup per hero, LDS) or "levels" (a launch per level)"""
+        v = C.c_int()
+        _lib.check(self._lib.rp_mccfr_nash_variant(self._h, C.byref(v)))
+        return ("one", "levels")[v.value]
+
+    def solve_to(self, target: float, check_every: int, max_steps: int):
+        """step in blocks of ``check_every`` until the first device check below ``target`` or ``max_steps``;
+        returns (steps, exploitability, reached)"""
+        steps, e, hit = C.c_uint64(), C.c_float(), C.c_int()
+        _lib.check(self._lib.rp_mccfr_solve_to(self._h, target, check_every, max_steps, C.byref(steps), C.byref(e), C.byref(hit)))
+        return steps.value, e.value, bool(hit.value)
+
     # ---- RefProf / MutProf ----------------------------------------------------------------------
     @property
     def epoch(self) -> int:
