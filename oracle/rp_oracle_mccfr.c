@@ -1021,6 +1021,52 @@ ORA_API uint64_t ora_div_by_recip_mismatches(uint64_t n, uint64_t seed) {
     return bad;
 }
 
+/* What the device must DECIDE about one cell's Welford chain, computed without any kernel code (tests/welford_witness.py).
+ * The chain ev += (payoff[i] - ev) / (float)(visits + 1) is walked with plain division — by the contract the device's chain holds
+ * the same bits before every touch, whichever path it took — and every numerator is put to the two criteria of include/rp_math.h
+ * with the correctly rounded reciprocal the kernels prepare: the proof of rp_div_by_recip1 (mccfr_update.hpp's payoff chain replays a
+ * tile of PTILE touches with IEEE divisions when one quotient of it is unproven) and the precondition rp_div_by_recip_ok
+ * (sparse.hip's k_apply_hot replays a staging tile of HT touches when one numerator of it breaks it).  Tiles are runs of `tile`
+ * consecutive touches from the start of the chain, the last one partial.  flags (may be NULL): per tile, bit 0 = holds an unproven
+ * quotient, bit 1 = holds a numerator that breaks the precondition, bit 2 / bit 3 = holds a numerator whose quotient by
+ * rp_div_by_recip1 / rp_div_by_recip is NOT the IEEE quotient (subnormal quotients: the corrections round twice), so that a kernel
+ * which skipped the replay of that tile would leave other bits.  Returns the chain's final ev. */
+ORA_API float ora_welford_witness_tiles(uint64_t n, const float* payoff, float ev0, uint32_t visits0, uint32_t tile,
+                                        uint64_t* unproven_tiles, uint64_t* notok_tiles, uint64_t* tiles, uint8_t* flags) {
+    float ev = ev0;
+    uint32_t v = visits0;
+    uint64_t nu = 0, nk = 0, nt = 0;
+    if (!tile) tile = 1;
+    for (uint64_t s = 0; s < n; s += tile) {
+        uint64_t e = s + tile < n ? s + tile : n;
+        int unproven = 0, notok = 0, off1 = 0, off2 = 0;
+        for (uint64_t i = s; i < e; ++i) {
+            float b = (float)(v + 1u);
+            float a = payoff[i] - ev;
+            int proven = 0;
+            float q1 = rp_div_by_recip1(a, b, 1.0f / b, &proven);
+            unproven |= !proven;
+            notok |= !rp_div_by_recip_ok(a);
+            off1 |= rp_f2u(q1) != rp_f2u(a / b);
+            off2 |= rp_f2u(rp_div_by_recip(a, b, 1.0f / b)) != rp_f2u(a / b);
+            ev += a / b;
+            v += 1u;
+        }
+        if (flags) flags[nt] = (uint8_t)((unproven ? 1 : 0) | (notok ? 2 : 0) | (off1 ? 4 : 0) | (off2 ? 8 : 0));
+        nu += unproven ? 1 : 0;
+        nk += notok ? 1 : 0;
+        nt += 1;
+    }
+    if (unproven_tiles) *unproven_tiles = nu;
+    if (notok_tiles) *notok_tiles = nk;
+    if (tiles) *tiles = nt;
+    return ev;
+}
+ORA_API float ora_welford_witness(uint64_t n, const float* payoff, float ev0, uint32_t visits0, uint32_t tile,
+                                  uint64_t* unproven_tiles, uint64_t* notok_tiles, uint64_t* tiles) {
+    return ora_welford_witness_tiles(n, payoff, ev0, visits0, tile, unproven_tiles, notok_tiles, tiles, NULL);
+}
+
 /* ======================================================================================================
  * Sparse profile (include/rp_mi355x.h rp_profile_*): the update half of Solver::step (solver.rs:96-105,143-192)
  * on a table addressed by row index — the NLHE-scale shape, where the producer of the
@@ -1098,6 +1144,8 @@ void ora_profile_set_row(ora_mccfr* h, uint32_t row, const rp_encounter* in) {
         h->visits[k] = in[a].visits;
     }
 }
+/* rp_profile_set_rows, one row at a time: hydrates the oracle's profile like the device's (tests/oracle.py OracleProfile.set_rows) */
+ORA_API void ora_profile_set(ora_mccfr* h, uint32_t row, const rp_encounter* in) { ora_profile_set_row(h, row, in); }
 
 /* summary entry: [row u32][count u32][psum f32][n_actions u32][regret maps A x {a,b,m,n}][weight maps A x {a,b,m,n}] */
 ORA_API size_t ora_profile_entry_bytes(const ora_mccfr* h) { return 16 + (size_t)2 * h->g.max_actions * sizeof(ora_map); }

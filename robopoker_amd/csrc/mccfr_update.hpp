@@ -390,7 +390,7 @@ __global__ __launch_bounds__(128) void k_chain(DevGame g, DevTables t, DevSorted
         const uint32_t v0 = __shfl(visits, 0, 64);
         const float ev0 = __shfl(ev, 0, 64);
         // every edge of an infoset is always visited together, so all its (payoff, visits) cells hold the same
-        // value and ONE chain serves them; anything else (a hand-made import) takes the plain path below
+        // value and ONE chain serves them; anything else (a hand-made import: test_non_uniform_infosets_take_the_plain_path) takes the plain path below
         const bool uniform = __all(!chain || (visits == v0 && rp_f2u(ev) == rp_f2u(ev0)));
         float* hist = ptile + 6 * PTILE;  // [PTILE] ev after each touch of the current tile
         if (uniform) ev = ev0;
@@ -463,7 +463,8 @@ __global__ __launch_bounds__(128) void k_chain(DevGame g, DevTables t, DevSorted
                     const float q = rp_div_by_recip1(pt[k] - prev, pt[2 * PTILE + k], pt[PTILE + k], &proven);
                     bad |= !proven || (prev + q != hist[k]);
                 }
-                if (__any(bad)) {  // essentially never: redo this tile with IEEE divisions
+                if (__any(bad)) {  // rare (a quotient below 2^-97, or on a rounding tie): redo this tile with IEEE divisions.  Run by tests/test_gpu_resumed_update.py
+                                   // (every tile, walker 0's tiles only, a few tiles of a hydrated table), inputs proven by tests/welford_witness.py
                     ev = ev_tile;
                     for (uint32_t k = 0; k < n; ++k) ev += (pt[k] - ev) / pt[2 * PTILE + k];
                 }
@@ -474,7 +475,8 @@ __global__ __launch_bounds__(128) void k_chain(DevGame g, DevTables t, DevSorted
             }
         }
         if (chain) {
-            if (!uniform) {  // edges of one infoset with different visit counts (only after a hand-made import)
+            if (!uniform) {  // cells of one infoset that differ in visits or in payoff bits: only after a hand-made import (rp_mccfr_import;
+                             // test_non_uniform_infosets_take_the_plain_path steps such tables)
                 ev = ev_start;
                 uint32_t v = visits;
                 for (uint32_t i = 0; i < len; ++i) {

@@ -309,7 +309,8 @@ __global__ __launch_bounds__(128) void k_apply_hot(SparseParams p, DevBatch b, S
                     bad = bad || !rp_div_by_recip_ok(num);
                     ev += rp_div_by_recip(num, tden[buf][u], trcp[buf][u]);
                 }
-                if (bad) {  // replay the tile with IEEE divisions (none observed)
+                if (bad) {  // replay the tile with IEEE divisions: a numerator below 2^-60 or a row whose cells differ in visits
+                            // (tests/test_gpu_resumed_update.py: every tile, one planted tile, none; `v` is still the count before this tile)
                     ev = ev_in;
                     for (uint32_t q = 0; q < m; ++q) ev += (tpay[buf][q] - ev) / (float)(v + q + 1u);
                 }

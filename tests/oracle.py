@@ -112,6 +112,11 @@ def load() -> C.CDLL:
     o.ora_mccfr_sum_regret.argtypes = [vp]
     o.ora_mccfr_exploitability.restype = C.c_float
     o.ora_mccfr_exploitability.argtypes = [vp]
+    o.ora_welford_witness.restype = C.c_float
+    o.ora_welford_witness.argtypes = [C.c_uint64, vp, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                      C.POINTER(C.c_uint64)]
+    o.ora_welford_witness_tiles.restype = C.c_float
+    o.ora_welford_witness_tiles.argtypes = o.ora_welford_witness.argtypes + [vp]
     # lloyd
     o.ora_sinkhorn_cost.restype = C.c_float
     o.ora_sinkhorn_cost.argtypes = [C.c_uint32, vp, vp, vp, C.POINTER(_lib.SinkhornHP), C.POINTER(C.c_uint32)]
@@ -299,6 +304,7 @@ class OracleProfile:
         o.ora_profile_summarize.restype = C.c_int64
         o.ora_profile_summarize.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
         o.ora_profile_fold.argtypes = [vp, vp, C.c_uint64]
+        o.ora_profile_set.argtypes = [vp, C.c_uint32, vp]
         self.o, self.A, self.n_rows = o, max_actions, n_rows
         hp = hyper or default_hyper()
         dr = None if default_regret is None else np.ascontiguousarray(default_regret, dtype=np.float32)
@@ -350,6 +356,14 @@ class OracleProfile:
         for i, r in enumerate(rows):
             self.o.ora_profile_get(self.h, int(r), out[i].ctypes.data)
         return out
+
+    def set_rows(self, rows, enc):
+        """rp_profile_set_rows' counterpart: overwrite rows, enc structured [len(rows)][A] of (weight, regret, payoff, visits)"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        enc = np.ascontiguousarray(enc, dtype=ENC_DTYPE)
+        assert enc.shape == (rows.size, self.A)
+        for i, r in enumerate(rows):
+            self.o.ora_profile_set(self.h, int(r), enc[i].ctypes.data)
 
 
 class OracleProfileEngine(OracleProfile):
