@@ -565,5 +565,40 @@ def check(code: int) -> None:
         raise RpError(code, load().rp_last_error().decode("utf-8", "replace"))
 
 
+class Checkpoint(C.Structure):
+    _fields_ = [("epoch", C.c_uint64), ("nodes", C.c_uint64), ("infos", C.c_uint64), ("rate", C.c_double)]
+
+
+EVENT = C.CFUNCTYPE(None, C.c_int, C.c_void_p, C.c_char_p, C.c_void_p)
+
+
+def train(fn, handle, *leading, max_steps=0, max_seconds=0.0, log_interval=60.0, flush_interval=1800.0, on_checkpoint=None,
+          on_flush=None, interrupt=None) -> str:
+    """rp_mccfr_train / rp_nlhe_train (``fn``) on ``handle``; ``leading`` are the arguments in front of max_steps.
+    ``on_checkpoint(dict, line)`` gets the Checkpoint and its display line, ``on_flush(dict)`` fires at the flush cadence,
+    ``interrupt`` is a ctypes c_int the caller may set to stop.  Returns Progress::summary."""
+
+    def cb(event, cp, line, _user):
+        c = C.cast(cp, C.POINTER(Checkpoint)).contents
+        d = {"epoch": c.epoch, "nodes": c.nodes, "infos": c.infos, "rate": c.rate}
+        if event == 0 and on_checkpoint:
+            on_checkpoint(d, line.decode())
+        if event == 1 and on_flush:
+            on_flush(d)
+
+    trampoline = EVENT(cb)
+    buf = C.create_string_buffer(256)
+    check(fn(handle, *leading, int(max_steps), float(max_seconds), float(log_interval), float(flush_interval),
+             C.cast(trampoline, C.c_void_p), None, C.byref(interrupt) if interrupt is not None else None, buf, len(buf)))
+    return buf.value.decode()
+
+
+def kernel_time(fn, handle, name: str):
+    """(total_ms, launches) of one of the handle's kernel clocks (``fn``: the handle's rp_*_kernel_time)"""
+    ms, n = C.c_double(), C.c_uint64()
+    check(fn(handle, name.encode(), C.byref(ms), C.byref(n)))
+    return ms.value, n.value
+
+
 def declared_symbols() -> list[str]:
     return sorted(_SIGNATURES)

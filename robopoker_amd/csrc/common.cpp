@@ -1,6 +1,9 @@
-// common.cpp — error reporting, version and device probing for librp_mi355x.so
+// common.cpp — error reporting, the training loop, version and device probing for librp_mi355x.so
 #include "rp_internal.h"
 
+#include <algorithm>
+#include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <hip/hip_runtime_api.h>
 
@@ -24,6 +27,52 @@ void format_progress(char* buf, size_t cap, uint64_t epoch, uint64_t nodes, uint
     snprintf(f[2], sizeof f[2], "infos %llu", (unsigned long long)infos);
     snprintf(f[3], sizeof f[3], "I/sec %.1f", rate);
     snprintf(buf, cap, "%-20s%-20s%-20s%-20s", f[0], f[1], f[2], f[3]);
+}
+
+int train_loop(const std::function<int(TrainCounts&)>& step, const std::function<int(TrainCounts&)>& refresh, uint64_t max_steps,
+               double max_seconds, double log_interval, double flush_interval, rp_train_event_fn on_event, void* user,
+               const volatile int* interrupt, char* summary, size_t summary_cap) {
+    using clock = std::chrono::steady_clock;
+    const auto start = clock::now();
+    auto prior = start, flushed = start;
+    uint64_t prior_infos = 0, steps = 0;
+    TrainCounts c{0, 0, 0};
+    auto secs_since = [](clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); };
+    int rc;
+    for (;;) {
+        if ((rc = step(c))) return rc;  // Trainer::train: step, then checkpoint, then flush, then the interrupt test
+        steps += 1;
+        if (secs_since(prior) >= log_interval) {  // Metrics::checkpoint (metrics/mod.rs:67-80)
+            if ((rc = refresh(c))) return rc;
+            const double secs = std::max(1.0, std::floor(secs_since(prior)));  // elapsed().as_secs().max(1)
+            rp_checkpoint cp{c.epoch, c.nodes, c.infos, (double)(c.infos - prior_infos) / secs};
+            prior = clock::now();
+            prior_infos = c.infos;
+            if (on_event) {
+                char line[96];
+                format_progress(line, sizeof line, cp.epoch, cp.nodes, cp.infos, cp.rate);
+                on_event(RP_TRAIN_CHECKPOINT, &cp, line, user);
+            }
+        }
+        if (secs_since(flushed) >= flush_interval) {  // FastSession::flush cadence (forge/src/fast.rs:97-125)
+            flushed = clock::now();
+            if (on_event) {
+                rp_checkpoint cp{c.epoch, c.nodes, c.infos, 0.0};
+                on_event(RP_TRAIN_FLUSH, &cp, "", user);
+            }
+        }
+        const bool stop = (interrupt && *interrupt) || (max_steps && steps >= max_steps) ||
+                          (max_seconds > 0.0 && secs_since(start) >= max_seconds);
+        if (stop) break;
+    }
+    if ((rc = refresh(c))) return rc;
+    if (summary && summary_cap) {  // Progress::summary (progress.rs:24-26): rate over the whole run
+        char line[96];
+        const double secs = std::max(1.0, std::floor(secs_since(start)));
+        format_progress(line, sizeof line, c.epoch, c.nodes, c.infos, (double)c.infos / secs);
+        snprintf(summary, summary_cap, "training stopped\n%s", line);
+    }
+    return RP_OK;
 }
 
 }  // namespace rp

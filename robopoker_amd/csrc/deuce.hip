@@ -26,15 +26,9 @@
 
 #include "cards.hpp"
 #include "obs.hpp"
-#include "rp_internal.h"
+#include "host_util.hpp"
 
 namespace rp {
-
-#define HIP_TRY(expr)                                                                                 \
-    do {                                                                                              \
-        hipError_t _e = (expr);                                                                       \
-        if (_e != hipSuccess) return rp::fail(RP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
 
 static thread_local double g_last_ms = 0.0;
 

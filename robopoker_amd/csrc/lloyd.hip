@@ -24,18 +24,12 @@
 #include "../../include/rp_math.h"
 #include "../../include/rp_refrng.h"
 #include "../../include/rp_libm_glibc.h"
-#include "rp_internal.h"
+#include "host_util.hpp"
 
 #include "lloyd_shared.hpp"
 #include "lm_glibc_dev.hpp"
 
 namespace rp {
-
-#define HIP_TRY(expr)                                                                                 \
-    do {                                                                                              \
-        hipError_t _e = (expr);                                                                       \
-        if (_e != hipSuccess) return rp::fail(RP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
 
 // the device code, once per arithmetic (lloyd_kernels.hpp)
 namespace lm_contract {
@@ -60,12 +54,8 @@ using namespace lm_contract;  // unqualified kernel names below are the contract
 using namespace rp;
 
 namespace {
-struct Clock {
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> shared;  // pairs another clock owns (ck_begin's `also`): read here, destroyed there
-    double total_ms = 0.0;
-    uint64_t launches = 0;
-};
+// ref_draw counts as a second clock of its "kpp" interval (KernelClocks::begin's `also`): the reference draw is part of "kpp" and all
+// of "ref_draw"
 const char* const CLOCK_NAMES[] = {"pairwise", "step", "recompute", "bounds", "neighbor", "selfcost", "kpp", "drift", "mfma_bound", "kpp_bound", "refresh_bound", "ref_draw"};
 enum { CK_PAIRWISE, CK_STEP, CK_RECOMPUTE, CK_BOUNDS, CK_NEIGHBOR, CK_SELF, CK_KPP, CK_DRIFT, CK_BOUND, CK_KPP_BOUND, CK_REFRESH_BOUND, CK_REF_DRAW, CK_COUNT };
 }  // namespace
@@ -211,8 +201,7 @@ struct rp_kmeans {
     uint32_t* hist_stage = nullptr;
     bool bounds_ready = false, centroids_ready = false;
     int libm = RP_LIBM_CONTRACT;  // rp_kmeans_set_libm: which arithmetic pass of the kernels runs (KSEL)
-    bool profiling = false;
-    Clock clk[CK_COUNT];
+    KernelClocks clk{CLOCK_NAMES, CK_COUNT};  // rp_kmeans_profile
 };
 
 namespace {
@@ -224,44 +213,6 @@ int dev_alloc(rp_kmeans* h, T** out, size_t count) {
     h->allocs.push_back(p);
     *out = reinterpret_cast<T*>(p);
     return RP_OK;
-}
-
-// `also`: a second clock that counts the same interval (the reference draw is part of "kpp" and all of "ref_draw"): the SAME pair of
-// events, so that a clock inside a clock puts nothing more on the stream
-void ck_begin(rp_kmeans* h, int id, int also = -1) {
-    if (!h->profiling) return;
-    hipEvent_t a, b;
-    (void)hipEventCreate(&a);
-    (void)hipEventCreate(&b);
-    (void)hipEventRecord(a, h->stream);
-    h->clk[id].pending.emplace_back(a, b);
-    if (also >= 0) h->clk[also].shared.emplace_back(a, b);
-}
-void ck_end(rp_kmeans* h, int id, int also = -1) {
-    if (!h->profiling) return;
-    (void)hipEventRecord(h->clk[id].pending.back().second, h->stream);
-    h->clk[id].launches += 1;
-    if (also >= 0) h->clk[also].launches += 1;
-}
-void ck_drain(rp_kmeans* h) {
-    auto elapsed = [](const std::pair<hipEvent_t, hipEvent_t>& pr) {
-        float ms = 0.0f;
-        (void)hipEventSynchronize(pr.second);
-        (void)hipEventElapsedTime(&ms, pr.first, pr.second);
-        return ms;
-    };
-    for (auto& c : h->clk) {  // every reader first: a shared pair is destroyed by the clock that owns it
-        for (auto& pr : c.shared) c.total_ms += elapsed(pr);
-        c.shared.clear();
-    }
-    for (auto& c : h->clk) {
-        for (auto& pr : c.pending) {
-            c.total_ms += elapsed(pr);
-            (void)hipEventDestroy(pr.first);
-            (void)hipEventDestroy(pr.second);
-        }
-        c.pending.clear();
-    }
 }
 
 int alloc_centroid_set(rp_kmeans* h, CentroidSet* cs) {
@@ -303,14 +254,14 @@ int prepare_centroids(rp_kmeans* h, int set, bool replaces_other = false) {
         hipLaunchKernelGGL(k_centroid_versions, dim3(h->K), dim3(64), 0, h->stream, h->cs[set], h->cs[set ^ 1], true, h->bins, h->cver);
     else
         h->memo_dirty = true, h->pairw_seen = false;
-    ck_begin(h, CK_SELF);
+    h->clk.begin(h->stream, CK_SELF);
     if (h->kind == RP_METRIC_SINKHORN) {  // the tables by one wavefront per centroid, OT(c, c) by four (K solves of up to 256 x 256 bins)
         hipLaunchKernelGGL(KSEL(h, k_prepare_centroids), dim3(h->K), dim3(64), 0, h->stream, h->cs[set], h->K, h->M, h->kind, 0u,
                            (const float*)h->cs[set].self);
         hipLaunchKernelGGL(KSEL(h, k_self_block), dim3(h->K), dim3(256), 0, h->stream, h->cs[set], h->K, h->M);
     } else
         hipLaunchKernelGGL(KSEL(h, k_prepare_centroids), dim3(h->K), dim3(64), 0, h->stream, h->cs[set], h->K, h->M, h->kind, 0u, (const float*)nullptr);
-    ck_end(h, CK_SELF);
+    h->clk.end(h->stream, CK_SELF);
     HIP_TRY(hipGetLastError());
     return RP_OK;
 }
@@ -642,7 +593,7 @@ int launch_neighbor_list(rp_kmeans* h, const uint32_t* list, uint32_t n, uint8_t
 }
 
 int launch_neighbor_full(rp_kmeans* h, uint8_t* out_j, float* out_d, Bounds init) {
-    ck_begin(h, CK_NEIGHBOR);
+    h->clk.begin(h->stream, CK_NEIGHBOR);
     if (h->kind == RP_METRIC_VARIATION && h->bins == 101)  // turn layer: register-resident centroid CDFs
         hipLaunchKernelGGL(k_neighbor_var<101>, dim3((unsigned)((h->N + VB - 1) / VB)), dim3(256), 0, h->stream, h->P,
                            h->cs[h->cur], h->K, h->M, out_j, out_d, init);
@@ -659,7 +610,7 @@ int launch_neighbor_full(rp_kmeans* h, uint8_t* out_j, float* out_d, Bounds init
     } else
         hipLaunchKernelGGL(KSEL(h, k_neighbor), dim3((unsigned)h->N), dim3(64), 0, h->stream, h->P, h->cs[h->cur], h->K, h->M, h->kind, out_j,
                            out_d, init, (const uint32_t*)nullptr);
-    ck_end(h, CK_NEIGHBOR);
+    h->clk.end(h->stream, CK_NEIGHBOR);
     HIP_TRY(hipGetLastError());
     return RP_OK;
 }
@@ -705,7 +656,7 @@ int launch_bound(rp_kmeans* h, float* dbg_lo, float* dbg_hi, const float* ub0 = 
     const CentroidSet& cs = h->cs[h->cur];
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
-    ck_begin(h, CK_BOUND);
+    h->clk.begin(h->stream, CK_BOUND);
     for (int t = 3; t >= 0; --t) {  // the longest-running class first
         const uint32_t n = h->sb_count[t];
         if (!n) continue;
@@ -729,7 +680,7 @@ int launch_bound(rp_kmeans* h, float* dbg_lo, float* dbg_hi, const float* ub0 = 
 #undef SB_LAUNCH1
     }
     if (h->sb_nbig) hipLaunchKernelGGL(k_mask_all, dim3((h->sb_nbig + 255) / 256), dim3(256), 0, h->stream, h->sb_big, h->sb_nbig, h->sb_mask);
-    ck_end(h, CK_BOUND);
+    h->clk.end(h->stream, CK_BOUND);
     HIP_TRY(hipGetLastError());
     return RP_OK;
 }
@@ -751,11 +702,11 @@ int launch_neighbor(rp_kmeans* h, uint8_t* out_j, float* out_d, Bounds init, int
             // after the Elkan iterations: the exact distance to the point's assigned centroid (one solve per point, reused below)
             HIP_TRY(hipMemcpyAsync(h->sb_hint_j, h->B.j, h->N, hipMemcpyDeviceToDevice, h->stream));
             hipLaunchKernelGGL(k_hint_masks, dim3(nblk), dim3(256), 0, h->stream, h->sb_hint_j, h->N, h->K, h->sb_hint_mask);
-            ck_begin(h, CK_NEIGHBOR);
+            h->clk.begin(h->stream, CK_NEIGHBOR);
             Bounds none{};
             hipLaunchKernelGGL(KSEL(h, k_neighbor_masked), dim3((unsigned)h->N), dim3(64), 0, h->stream, h->P, h->cs[h->cur], h->K, h->M,
                                h->sb_hint_mask, (uint8_t*)nullptr, h->sb_ub0, none, (const uint8_t*)nullptr, (const float*)nullptr);
-            ck_end(h, CK_NEIGHBOR);
+            h->clk.end(h->stream, CK_NEIGHBOR);
             ub0 = h->sb_ub0;
             hint_j = h->sb_hint_j;
         }
@@ -763,16 +714,16 @@ int launch_neighbor(rp_kmeans* h, uint8_t* out_j, float* out_d, Bounds init, int
     int rc = centroid_order(h);
     if (rc || (rc = launch_bound(h, nullptr, nullptr, ub0))) return rc;
     float* dd = out_d ? out_d : h->sb_d;
-    ck_begin(h, CK_NEIGHBOR);
+    h->clk.begin(h->stream, CK_NEIGHBOR);
     hipLaunchKernelGGL(KSEL(h, k_neighbor_masked), dim3((unsigned)h->N), dim3(64), 0, h->stream, h->P, h->cs[h->cur], h->K, h->M, h->sb_mask,
                        out_j, dd, init, hint_j, hint_j ? ub0 : (const float*)nullptr);
-    ck_end(h, CK_NEIGHBOR);
+    h->clk.end(h->stream, CK_NEIGHBOR);
     HIP_TRY(hipGetLastError());
     if (!h->sb_audit && out_j && h->sb_nsample) {  // the sampled points once more, unpruned (k_neighbor takes a point list)
         Bounds none{};
-        ck_begin(h, CK_NEIGHBOR);
+        h->clk.begin(h->stream, CK_NEIGHBOR);
         if ((rc = launch_neighbor_list(h, h->sb_sample, h->sb_nsample, h->audit_j, h->audit_d, none))) return rc;
-        ck_end(h, CK_NEIGHBOR);
+        h->clk.end(h->stream, CK_NEIGHBOR);
         hipLaunchKernelGGL(k_audit_compare_list, dim3((h->sb_nsample + 255) / 256), dim3(256), 0, h->stream, out_j, dd, h->audit_j,
                            h->audit_d, h->sb_sample, h->sb_nsample, h->sb_bad + 1);
         HIP_TRY(hipGetLastError());
@@ -791,7 +742,7 @@ int launch_neighbor(rp_kmeans* h, uint8_t* out_j, float* out_d, Bounds init, int
 }
 
 int launch_recompute(rp_kmeans* h, const uint8_t* assign, int set) {
-    ck_begin(h, CK_RECOMPUTE);
+    h->clk.begin(h->stream, CK_RECOMPUTE);
     const unsigned slices = h->N >= (1ull << 17) ? 8u : 1u;  // workgroups per centroid (k_recompute adds into zeroed outputs when > 1)
     if (slices > 1) {
         HIP_TRY(hipMemsetAsync(h->cs[set].counts, 0, (size_t)h->K * h->bins * 4, h->stream));
@@ -800,7 +751,7 @@ int launch_recompute(rp_kmeans* h, const uint8_t* assign, int set) {
     }
     hipLaunchKernelGGL(k_recompute, dim3(h->K, slices), dim3(256), 0, h->stream, h->P, assign, h->bins, h->cs[set].counts,
                        h->cs[set].weight, h->sizes);
-    ck_end(h, CK_RECOMPUTE);
+    h->clk.end(h->stream, CK_RECOMPUTE);
     HIP_TRY(hipGetLastError());
     return RP_OK;
 }
@@ -816,15 +767,15 @@ int step_front(rp_kmeans* h) {
         if (h->B.im_ver) HIP_TRY(hipMemsetAsync(h->B.im_ver, 0, (size_t)h->N * 4, h->stream));
         h->memo_dirty = false;
     }
-    ck_begin(h, CK_PAIRWISE);
+    h->clk.begin(h->stream, CK_PAIRWISE);
     if (h->kind == RP_METRIC_VARIATION)
         hipLaunchKernelGGL(k_pairwise_var, dim3((h->K * h->K + 255) / 256), dim3(256), 0, h->stream, h->cs[cur], h->K, h->M, h->pairw);
     else
         hipLaunchKernelGGL(KSEL(h, k_pairwise), dim3(h->K * h->K), dim3(64), 0, h->stream, h->cs[cur], h->K, h->M, h->kind, h->pairw, h->cver, h->pver);
     hipLaunchKernelGGL(k_midpoints, dim3((h->K + 63) / 64), dim3(64), 0, h->stream, h->pairw, h->K, h->mid);
-    ck_end(h, CK_PAIRWISE);
+    h->clk.end(h->stream, CK_PAIRWISE);
     h->pairw_seen = true;
-    ck_begin(h, CK_STEP);
+    h->clk.begin(h->stream, CK_STEP);
     if (h->kind == RP_METRIC_VARIATION && h->bins == 101)
         hipLaunchKernelGGL(k_elkan_step_var<101>, dim3((unsigned)((h->N + VB - 1) / VB)), dim3(256), 0, h->stream, h->P, h->cs[cur],
                            h->K, h->M, h->B, h->pairw, h->mid);
@@ -855,10 +806,10 @@ int step_front(rp_kmeans* h) {
                                    h->M, h->B, h->refresh, 1, h->drift, h->mid, h->rb_code);
                 if ((rc = bucket(1))) return rc;
                 HIP_TRY(hipMemsetAsync(h->rb_cursor, 0, 8, h->stream));
-                ck_begin(h, CK_REFRESH_BOUND);
+                h->clk.begin(h->stream, CK_REFRESH_BOUND);
                 hipLaunchKernelGGL((k_refresh_interval<32>), dim3(4096), dim3(64), 0, h->stream, h->P, h->cs[cur], h->K, h->bins, h->M.Cm,
                                    h->sb, h->B, h->pairw, h->refresh.list, h->refresh.offset + h->K, h->rb_cursor, h->rb_code, h->rb_stats, h->stats);
-                ck_end(h, CK_REFRESH_BOUND);
+                h->clk.end(h->stream, CK_REFRESH_BOUND);
                 if ((rc = bucket(2))) return rc;
             } else {
                 h->refresh.code = nullptr;
@@ -871,7 +822,7 @@ int step_front(rp_kmeans* h) {
         hipLaunchKernelGGL(KSEL(h, k_elkan_step), dim3((unsigned)h->N), dim3(64), 0, h->stream, h->P, h->cs[cur], h->K, h->M, h->kind, h->B,
                            h->pairw, h->mid);
     }
-    ck_end(h, CK_STEP);
+    h->clk.end(h->stream, CK_STEP);
     HIP_TRY(hipGetLastError());
     return launch_recompute(h, h->B.j, cur ^ 1);
 }
@@ -881,15 +832,15 @@ int step_back(rp_kmeans* h, float* drift, uint64_t* sizes, double* reassigned) {
     const int cur = h->cur, nxt = cur ^ 1;
     int rc = prepare_centroids(h, nxt, true);
     if (rc) return rc;
-    ck_begin(h, CK_DRIFT);
+    h->clk.begin(h->stream, CK_DRIFT);
     if (h->kind == RP_METRIC_SINKHORN)
         hipLaunchKernelGGL(KSEL(h, k_drift_block), dim3(h->K), dim3(256), 0, h->stream, h->cs[nxt], h->cs[cur], h->K, h->M, h->drift);
     else
         hipLaunchKernelGGL(KSEL(h, k_drift), dim3(h->K), dim3(64), 0, h->stream, h->cs[nxt], h->cs[cur], h->K, h->M, h->kind, h->drift);
-    ck_end(h, CK_DRIFT);
-    ck_begin(h, CK_BOUNDS);
+    h->clk.end(h->stream, CK_DRIFT);
+    h->clk.begin(h->stream, CK_BOUNDS);
     hipLaunchKernelGGL(k_bounds_update, dim3(2048), dim3(256), 0, h->stream, h->B, h->N, h->K, h->drift);
-    ck_end(h, CK_BOUNDS);
+    h->clk.end(h->stream, CK_BOUNDS);
     HIP_TRY(hipMemsetAsync(h->scal + 1, 0, 8, h->stream));
     hipLaunchKernelGGL(k_tally, dim3(1024), dim3(256), 0, h->stream, h->B.j, h->prior, h->N, h->scal + 1);
     HIP_TRY(hipGetLastError());
@@ -903,7 +854,7 @@ int step_back(rp_kmeans* h, float* drift, uint64_t* sizes, double* reassigned) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (sizes) for (uint32_t k = 0; k < h->K; ++k) sizes[k] = sz[k];
     if (reassigned) *reassigned = (double)moved / (double)h->N;
-    ck_drain(h);
+    h->clk.drain();
     return RP_OK;
 }
 
@@ -924,7 +875,7 @@ int rp_kmeans_destroy(rp_kmeans* h) {
     if (!h) return RP_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    ck_drain(h);
+    h->clk.drain();
     for (void* p : h->allocs) (void)hipFree(p);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -1039,9 +990,9 @@ int rp_kmeans_kpp_ref_walk(rp_kmeans* h, float prefix_in, float* prefix_out) {
     if (rc) return rc;
     HIP_TRY(hipSetDevice(h->device));
     h->kr_walk_valid = false;
-    ck_begin(h, CK_KPP, CK_REF_DRAW);
+    h->clk.begin(h->stream, CK_KPP, CK_REF_DRAW);
     ref_walk_launch(h->stream, h->pot, h->N, h->kpp_cum, prefix_in, h->kr_out);
-    ck_end(h, CK_KPP, CK_REF_DRAW);
+    h->clk.end(h->stream, CK_KPP, CK_REF_DRAW);
     HIP_TRY(hipGetLastError());
     unsigned long long out[3] = {0, 0, 0};
     HIP_TRY(hipMemcpyAsync(out, h->kr_out, 24, hipMemcpyDeviceToHost, h->stream));
@@ -1069,9 +1020,9 @@ int rp_kmeans_kpp_ref_pick(rp_kmeans* h, float x, uint64_t* index) {
     if (!h->kr_walk_valid)
         return rp::fail(RP_ERR_INVALID, "rp_kmeans_kpp_ref_pick: call rp_kmeans_kpp_ref_walk first (and again after the potentials change)");
     HIP_TRY(hipSetDevice(h->device));
-    ck_begin(h, CK_KPP, CK_REF_DRAW);
+    h->clk.begin(h->stream, CK_KPP, CK_REF_DRAW);
     ref_find_launch(h->stream, h->pot, h->M.kpp_d, h->N, h->kpp_cum, h->kr_prefix, x, h->kr_out);
-    ck_end(h, CK_KPP, CK_REF_DRAW);
+    h->clk.end(h->stream, CK_KPP, CK_REF_DRAW);
     HIP_TRY(hipGetLastError());
     unsigned long long win = 0;
     HIP_TRY(hipMemcpyAsync(&win, h->kr_out, 8, hipMemcpyDeviceToHost, h->stream));
@@ -1085,10 +1036,10 @@ int rp_kmeans_kpp_total(rp_kmeans* h, uint64_t* total) {
     if (!h || !total) return rp::fail(RP_ERR_INVALID, "rp_kmeans_kpp_total: NULL argument");
     HIP_TRY(hipSetDevice(h->device));
     const uint32_t nblocks = (uint32_t)((h->N + KPP_BLOCK - 1) / KPP_BLOCK);
-    ck_begin(h, CK_KPP);
+    h->clk.begin(h->stream, CK_KPP);
     hipLaunchKernelGGL(k_kpp_blocksum, dim3(nblocks), dim3(256), 0, h->stream, h->pot, h->N, h->bsum);
     hipLaunchKernelGGL(k_kpp_total, dim3(1), dim3(1024), 0, h->stream, h->bsum, nblocks, h->scal);
-    ck_end(h, CK_KPP);
+    h->clk.end(h->stream, CK_KPP);
     HIP_TRY(hipGetLastError());
     unsigned long long t = 0;
     HIP_TRY(hipMemcpyAsync(&t, h->scal, 8, hipMemcpyDeviceToHost, h->stream));
@@ -1115,7 +1066,7 @@ int rp_kmeans_kpp_update(rp_kmeans* h, uint32_t k) {
     if (!h || k >= h->K) return rp::fail(RP_ERR_INVALID, "rp_kmeans_kpp_update: bad argument");
     HIP_TRY(hipSetDevice(h->device));
     h->kr_walk_valid = false;  // the potentials change
-    ck_begin(h, CK_KPP);
+    h->clk.begin(h->stream, CK_KPP);
     if (h->kind == RP_METRIC_VARIATION)
         hipLaunchKernelGGL(k_kpp_update_var, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, h->P, h->cs[h->cur], k, h->K,
                            h->M, h->pot);
@@ -1140,8 +1091,8 @@ int rp_kmeans_kpp_update(rp_kmeans* h, uint32_t k) {
                 HIP_TRY(hipStreamSynchronize(h->stream));
             }
             if (m && m <= 48u) {
-                ck_end(h, CK_KPP);  // the interval filter has its own clock ("kpp_bound"): it is not a softmin kernel
-                ck_begin(h, CK_KPP_BOUND);
+                h->clk.end(h->stream, CK_KPP);  // the interval filter has its own clock ("kpp_bound"): it is not a softmin kernel
+                h->clk.begin(h->stream, CK_KPP_BOUND);
                 HIP_TRY(hipMemsetAsync(h->kpp2.count, 0, 16, h->stream));
                 HIP_TRY(hipMemsetAsync(h->kb_cursor, 0, 16, h->stream));
                 int cus = 256;
@@ -1162,8 +1113,8 @@ int rp_kmeans_kpp_update(rp_kmeans* h, uint32_t k) {
                 }
                 todo = &h->kpp2;
                 if (h->M.kpp_claim) h->sb_check_pending = true;  // the solves below check the sampled claims (prune_check reads the counter)
-                ck_end(h, CK_KPP_BOUND);
-                ck_begin(h, CK_KPP);
+                h->clk.end(h->stream, CK_KPP_BOUND);
+                h->clk.begin(h->stream, CK_KPP);
             }
         }
         if (cap4)
@@ -1191,13 +1142,13 @@ int rp_kmeans_kpp_update(rp_kmeans* h, uint32_t k) {
                                h->pot, (const uint32_t*)nullptr, (const unsigned int*)nullptr);
         }
     }
-    ck_end(h, CK_KPP);
+    h->clk.end(h->stream, CK_KPP);
     HIP_TRY(hipGetLastError());
     if (k + 1 == h->K) {
         HIP_TRY(hipStreamSynchronize(h->stream));
         h->centroids_ready = true;
         h->pot_is_min_d2 = true;  // potentials = min_k d(c_k, x)^2 over the K centroids now installed
-        ck_drain(h);
+        h->clk.drain();
     }
     return RP_OK;
 }
@@ -1241,9 +1192,9 @@ int rp_kmeans_init_centroids(rp_kmeans* h, uint64_t* chosen) {
         uint64_t total = 0, pick = 0;
         if (h->rng == RP_RNG_REFERENCE) {
             const float v01 = rp_u2f((rp_smallrng_next_u32(&h->kr_rng) >> 9) | 0x3f800000u) - 1.0f;  // UniformFloat<f32>: [1, 2) - 1
-            ck_begin(h, CK_KPP, CK_REF_DRAW);
+            h->clk.begin(h->stream, CK_KPP, CK_REF_DRAW);
             ref_pick_launch(h->stream, h->pot, h->M.kpp_d, h->N, h->kpp_cum, v01, h->kr_out);
-            ck_end(h, CK_KPP, CK_REF_DRAW);
+            h->clk.end(h->stream, CK_KPP, CK_REF_DRAW);
             HIP_TRY(hipGetLastError());
             unsigned long long out[3] = {0, 0, 0};
             HIP_TRY(hipMemcpyAsync(out, h->kr_out, 24, hipMemcpyDeviceToHost, h->stream));
@@ -1273,7 +1224,7 @@ int rp_kmeans_init_centroids(rp_kmeans* h, uint64_t* chosen) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->centroids_ready = true;
     h->bounds_ready = false;
-    ck_drain(h);
+    h->clk.drain();
     return RP_OK;
 }
 
@@ -1287,7 +1238,7 @@ int rp_kmeans_init_bounds(rp_kmeans* h) {
         // (k_init_from_kpp); the exact search runs on the rest
         unsigned int n_todo = 0;
         HIP_TRY(hipMemsetAsync(h->kpp_ntodo, 0, 4, h->stream));
-        ck_begin(h, CK_NEIGHBOR);
+        h->clk.begin(h->stream, CK_NEIGHBOR);
         hipLaunchKernelGGL(k_zero_f32, dim3(2048), dim3(256), 0, h->stream, h->B.lower, (uint64_t)h->N * h->K);
         hipLaunchKernelGGL(k_init_from_kpp, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, h->M, h->N, h->K, h->prior, h->B,
                            h->kpp_todo, h->kpp_ntodo);
@@ -1298,7 +1249,7 @@ int rp_kmeans_init_bounds(rp_kmeans* h) {
             into.lower = nullptr;  // zeroed above
             if ((rc = launch_neighbor_list(h, h->kpp_todo, n_todo, h->prior, nullptr, into))) return rc;
         }
-        ck_end(h, CK_NEIGHBOR);
+        h->clk.end(h->stream, CK_NEIGHBOR);
         HIP_TRY(hipGetLastError());
         // the shortcut trusts the k-means++ column-marginal filter: checked like the MFMA prune — on the sample in production,
         // on every point under RP_LLOYD_AUDIT — against the unpruned search (bucket and upper bound, bit for bit)
@@ -1324,7 +1275,7 @@ int rp_kmeans_init_bounds(rp_kmeans* h) {
     if (h->rb_on) HIP_TRY(hipMemsetAsync(h->B.uiv, 0, h->N, h->stream));  // every upper bound is an exact distance again
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->bounds_ready = true;
-    ck_drain(h);
+    h->clk.drain();
     return prune_check(h, "rp_kmeans_init_bounds");
 }
 
@@ -1403,7 +1354,7 @@ int rp_kmeans_step_naive(rp_kmeans* h) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->cur = nxt;
     h->pot_is_min_d2 = false;
-    ck_drain(h);
+    h->clk.drain();
     return prune_check(h, "rp_kmeans_step_naive");
 }
 
@@ -1417,7 +1368,7 @@ int rp_kmeans_assign(rp_kmeans* h, uint8_t* bucket, float* distance) {
     if (bucket) HIP_TRY(hipMemcpyAsync(bucket, h->tmp_j, h->N, hipMemcpyDeviceToHost, h->stream));
     if (distance) HIP_TRY(hipMemcpyAsync(distance, h->pdist, h->N * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    ck_drain(h);
+    h->clk.drain();
     return prune_check(h, "rp_kmeans_assign");
 }
 
@@ -1451,9 +1402,9 @@ int rp_kmeans_metric(rp_kmeans* h, float* tri) {
     int rc = need_centroids(h, "rp_kmeans_metric");
     if (rc) return rc;
     HIP_TRY(hipSetDevice(h->device));
-    ck_begin(h, CK_PAIRWISE);
+    h->clk.begin(h->stream, CK_PAIRWISE);
     hipLaunchKernelGGL(KSEL(h, k_pairwise), dim3(h->K * h->K), dim3(64), 0, h->stream, h->cs[h->cur], h->K, h->M, h->kind, h->pairw, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-    ck_end(h, CK_PAIRWISE);
+    h->clk.end(h->stream, CK_PAIRWISE);
     HIP_TRY(hipGetLastError());
     std::vector<float> pw((size_t)h->K * h->K);
     HIP_TRY(hipMemcpyAsync(pw.data(), h->pairw, pw.size() * 4, hipMemcpyDeviceToHost, h->stream));
@@ -1468,7 +1419,7 @@ int rp_kmeans_metric(rp_kmeans* h, float* tri) {
             mx = rp_maxf(mx, d);
         }
     for (uint32_t t = 0; t < h->K * (h->K - 1) / 2; ++t) tri[t] = tri[t] / mx;
-    ck_drain(h);
+    h->clk.drain();
     return RP_OK;
 }
 
@@ -1792,7 +1743,7 @@ int rp_kmeans_bound_intervals(rp_kmeans* h, float* lo, float* hi) {
     const hipError_t e = hipStreamSynchronize(h->stream);
     (void)hipFree(d_lo);
     (void)hipFree(d_hi);
-    ck_drain(h);
+    h->clk.drain();
     if (rc) return rc;
     if (e != hipSuccess) return rp::fail(RP_ERR_HIP, "rp_kmeans_bound_intervals: %s", hipGetErrorString(e));
     return RP_OK;
@@ -1801,26 +1752,16 @@ int rp_kmeans_bound_intervals(rp_kmeans* h, float* lo, float* hi) {
 int rp_kmeans_set_stream(rp_kmeans* h, void* hip_stream) {
     if (!h) return rp::fail(RP_ERR_INVALID, "rp_kmeans_set_stream: NULL handle");
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->own_stream) {
-        HIP_TRY(hipStreamDestroy(h->stream));
-        h->own_stream = false;
-    }
-    if (hip_stream) h->stream = reinterpret_cast<hipStream_t>(hip_stream);
-    else {
-        HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->own_stream = true;
-    }
-    return RP_OK;
+    return swap_stream(h->stream, h->own_stream, hip_stream);
 }
 
 int rp_kmeans_profile(rp_kmeans* h, int enable) {
     if (!h) return rp::fail(RP_ERR_INVALID, "rp_kmeans_profile: NULL handle");
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    ck_drain(h);
-    h->profiling = enable != 0;
-    for (auto& c : h->clk) { c.total_ms = 0.0; c.launches = 0; }
+    h->clk.drain();
+    h->clk.on = enable != 0;
+    h->clk.reset();
     return RP_OK;
 }
 
@@ -1828,14 +1769,7 @@ int rp_kmeans_kernel_time(rp_kmeans* h, const char* name, double* total_ms, uint
     if (!h || !name) return rp::fail(RP_ERR_INVALID, "rp_kmeans_kernel_time: NULL argument");
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    ck_drain(h);
-    for (int i = 0; i < CK_COUNT; ++i)
-        if (std::string(name) == CLOCK_NAMES[i]) {
-            if (total_ms) *total_ms = h->clk[i].total_ms;
-            if (launches) *launches = h->clk[i].launches;
-            return RP_OK;
-        }
-    return rp::fail(RP_ERR_INVALID, "rp_kmeans_kernel_time: unknown kernel '%s'", name);
+    return kernel_time(h->clk, "rp_kmeans_kernel_time", name, total_ms, launches);
 }
 
 // ---- stand-alone batched distances -------------------------------------------------------------------

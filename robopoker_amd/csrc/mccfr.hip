@@ -24,6 +24,7 @@
 #include "mccfr_update.hpp"
 #include "traverse_static.hpp"
 #include "mccfr_nash.hpp"
+#include "host_util.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -33,22 +34,15 @@
 #include <type_traits>
 #include <vector>
 
-#define HIP_TRY(expr)                                                                                 \
-    do {                                                                                              \
-        hipError_t _e = (expr);                                                                       \
-        if (_e != hipSuccess) return rp::fail(RP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
-
 // =================================================================================================
 // host side
 // =================================================================================================
 using namespace rp;
 
-struct KernelClock {
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
-    double total_ms = 0.0;
-    uint64_t launches = 0;
-};
+namespace {
+const char* const CLOCK_NAMES[] = {"traverse", "compact", "update"};
+enum { CK_TRAVERSE, CK_COMPACT, CK_UPDATE, CK_COUNT };
+}  // namespace
 
 struct rp_mccfr {
     int device = 0;
@@ -109,8 +103,7 @@ struct rp_mccfr {
     bool fuse_maps = true;  // composed update: traversal + block maps in one kernel when the game allows (RP_TRAV_UNFUSED=1: never)
     uint32_t fold_split_groups = 0;  // composed update: batches of at least this many groups fold them in k_fold_groups (RP_FOLD_SPLIT=1 | 0: all | none)
     int static_skel = 0;  // 0: none (k_traverse_lds / k_traverse), 1: KuhnSkel, 2: LeducSkel (traverse_static.hpp)
-    bool profiling = false;
-    KernelClock clk_traverse, clk_compact, clk_update;
+    KernelClocks clk{CLOCK_NAMES, CK_COUNT};  // rp_mccfr_profile
     // CfrNash on the device (mccfr_nash.hpp): built by the first call that asks (nash_prepare), kept until destroy
     void* d_nash = nullptr;  // NashTree's arrays, then NashWork's
     NashTree nt{};
@@ -238,34 +231,6 @@ StepParams make_params(const rp_mccfr* h) {
         p.ref_chance = p.ref_info + h->tbl.n_infos;
     }
     return p;
-}
-
-void clock_begin(rp_mccfr* h, KernelClock& c) {
-    if (!h->profiling) return;
-    hipEvent_t a, b;
-    (void)hipEventCreate(&a);
-    (void)hipEventCreate(&b);
-    (void)hipEventRecord(a, h->stream);
-    c.pending.emplace_back(a, b);
-}
-void clock_end(rp_mccfr* h, KernelClock& c) {
-    if (!h->profiling) return;
-    (void)hipEventRecord(c.pending.back().second, h->stream);
-    c.launches += 1;
-}
-void clock_drain(KernelClock& c) {
-    for (auto& pr : c.pending) {
-        float ms = 0.0f;
-        (void)hipEventSynchronize(pr.second);
-        (void)hipEventElapsedTime(&ms, pr.first, pr.second);
-        c.total_ms += ms;
-        (void)hipEventDestroy(pr.first);
-        (void)hipEventDestroy(pr.second);
-    }
-    c.pending.clear();
-}
-void clock_drain_all(rp_mccfr* h) {
-    for (KernelClock* c : {&h->clk_traverse, &h->clk_compact, &h->clk_update}) clock_drain(*c);
 }
 
 // run-time flags -> template arguments: f(std::bool_constant<a>{}, std::bool_constant<b>{})
@@ -415,7 +380,7 @@ void launch_prepare(rp_mccfr* h, const StepParams& p) {
 
 int launch_traverse(rp_mccfr* h, const StepParams& p) {
     if (h->dc.slotmap) HIP_TRY(hipMemsetAsync(h->dc.slotmap, 0, (size_t)h->tbl.n_infos * h->dc.stride, h->stream));
-    clock_begin(h, h->clk_traverse);
+    h->clk.begin(h->stream, CK_TRAVERSE);
     if (h->static_skel) {
         launch_prepare(h, p);
         const dim3 grid((h->batch + 255) / 256), block(256);
@@ -436,7 +401,7 @@ int launch_traverse(rp_mccfr* h, const StepParams& p) {
         const uint32_t threads = 256, blocks = (h->batch + threads - 1) / threads;
         hipLaunchKernelGGL(k_traverse, dim3(blocks), dim3(threads), 0, h->stream, h->g, h->t, h->sc, h->dc, p);
     }
-    clock_end(h, h->clk_traverse);
+    h->clk.end(h->stream, CK_TRAVERSE);
     HIP_TRY(hipGetLastError());
     return RP_OK;
 }
@@ -445,7 +410,7 @@ int launch_traverse(rp_mccfr* h, const StepParams& p) {
 int launch_sort(rp_mccfr* h, const StepParams& p) {
     const uint32_t nchunks = (h->batch + CH_TREES - 1) / CH_TREES;
     h->so.n_chunks = nchunks;
-    clock_begin(h, h->clk_compact);
+    h->clk.begin(h->stream, CK_COMPACT);
     if (!h->dc.slotmap) {
         const size_t NI = h->tbl.n_infos;
         hipLaunchKernelGGL(k_count_small, dim3(nchunks), dim3(CH_THREADS), NI * SM_WORDS * 4, h->stream, h->g, h->dc, h->so, p);
@@ -457,7 +422,7 @@ int launch_sort(rp_mccfr* h, const StepParams& p) {
         hipLaunchKernelGGL(k_scan, dim3(h->tbl.n_infos), dim3(CH_THREADS), 0, h->stream, h->g, h->so, p);
         hipLaunchKernelGGL(k_compact, dim3(nchunks, h->tbl.n_infos), dim3(SLOT_THREADS), 0, h->stream, h->g, h->dc, h->so, p);
     }
-    clock_end(h, h->clk_compact);
+    h->clk.end(h->stream, CK_COMPACT);
     HIP_TRY(hipGetLastError());
     return RP_OK;
 }
@@ -467,11 +432,11 @@ int launch_chain(rp_mccfr* h, const StepParams& p) {
     const bool sgn = h->R == RP_REGRET_DISCOUNTED || h->R == RP_REGRET_ASYMMETRIC;
     const bool prn = h->S != RP_SAMPLING_EXTERNAL;
     const dim3 grid(h->tbl.n_infos), block(128);
-    clock_begin(h, h->clk_update);
+    h->clk.begin(h->stream, CK_UPDATE);
     with_bools(sgn, prn, [&](auto sg, auto pr) {
         hipLaunchKernelGGL((k_chain<decltype(sg)::value, decltype(pr)::value>), grid, block, lds, h->stream, h->g, h->t, h->so, p);
     });
-    clock_end(h, h->clk_update);
+    h->clk.end(h->stream, CK_UPDATE);
     HIP_TRY(hipGetLastError());
     return RP_OK;
 }
@@ -519,16 +484,16 @@ int launch_summarize(rp_mccfr* h, const StepParams& p, void* blob_dev, bool fuse
     Map* bmaps = reinterpret_cast<Map*>(h->d_bmaps);
     const bool pruned = h->S != RP_SAMPLING_EXTERNAL;
     if (fused) {
-        clock_begin(h, h->clk_traverse);
+        h->clk.begin(h->stream, CK_TRAVERSE);
         launch_prepare(h, p);
         const size_t lds = traverse_maps_lds_bytes(h);
         with_static_traversal(h->static_skel, p.walker, pruned, p.ref_info != nullptr, [&](auto gt, auto wk, auto pr, auto rf) {
             hipLaunchKernelGGL((k_traverse_maps_static<decltype(gt), decltype(wk)::value, decltype(pr)::value, decltype(rf)::value>), dim3(nblk),
                                dim3(256), lds, h->stream, h->g, h->itab, p, bmaps, h->maxdec, h->cell_pad);
         });
-        clock_end(h, h->clk_traverse);
+        h->clk.end(h->stream, CK_TRAVERSE);
     }
-    clock_begin(h, h->clk_update);
+    h->clk.begin(h->stream, CK_UPDATE);
     if (fused) {
     } else if (!h->dc.slotmap) {
         const size_t lds = chunk_maps_lds_bytes(h);
@@ -561,7 +526,7 @@ int launch_summarize(rp_mccfr* h, const StepParams& p, void* blob_dev, bool fuse
             else hipLaunchKernelGGL((k_combine2<false>), grid, dim3(CB2_THREADS), 0, h->stream, h->g, h->t, h->itab, p, bmaps, nr, fs, cells, sums);
         }
     }
-    clock_end(h, h->clk_update);
+    h->clk.end(h->stream, CK_UPDATE);
     HIP_TRY(hipGetLastError());
     return RP_OK;
 }
@@ -826,7 +791,7 @@ int rp_mccfr_destroy(rp_mccfr* h) {
     if (!h) return RP_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    clock_drain_all(h);
+    h->clk.drain();
     void* ptrs[] = {h->d_info_streams, h->d_chance_streams, h->d_ref_mid, h->d_rows, h->d_states, h->d_children, h->d_kids, h->d_payoffs, h->d_info_actions, h->d_info_player, h->d_info_rank, h->d_scratch,
                     h->d_dec, h->d_sorted, h->d_bmaps, h->d_itab, h->d_summary, h->d_window, h->d_counters, h->t.regret, h->t.weight, h->t.payoff,
                     h->t.visits};
@@ -888,7 +853,7 @@ int rp_mccfr_sync(rp_mccfr* h) {
     int rc = set_device(h);
     if (rc) return rc;
     rc = check_device_errors(h);
-    clock_drain_all(h);
+    h->clk.drain();
     return rc;
 }
 
@@ -928,53 +893,18 @@ int rp_mccfr_spend(rp_mccfr* h, double seconds, uint64_t* iterations, double* el
     return RP_OK;
 }
 
-// Checkpoint's Display / Progress::format: rp::format_progress (common.cpp), shared with rp_nlhe_train
-using rp::format_progress;
-
+// Trainer::train: rp::train_loop (common.cpp).  The counters live on the device: they are read back at a checkpoint and for the
+// summary only, so a flush reports those of the last checkpoint.
 int rp_mccfr_train(rp_mccfr* h, uint64_t max_steps, double max_seconds, double log_interval, double flush_interval,
                    rp_train_event_fn on_event, void* user, const volatile int* interrupt, char* summary, size_t summary_cap) {
     if (!h) return rp::fail(RP_ERR_INVALID, "rp_mccfr_train: NULL handle");
-    using clock = std::chrono::steady_clock;
-    const auto start = clock::now();
-    auto prior = start, flushed = start;
-    uint64_t prior_infos = 0, steps = 0, nodes = 0, infos = 0;
-    auto secs_since = [](clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); };
-    for (;;) {
-        int rc = rp_mccfr_step(h);  // Trainer::train: step, then checkpoint, then flush, then the interrupt test
-        if (rc) return rc;
-        steps += 1;
-        if (secs_since(prior) >= log_interval) {  // Metrics::checkpoint (metrics/mod.rs:67-80)
-            if ((rc = rp_mccfr_counters(h, &nodes, &infos))) return rc;
-            const double secs = std::max(1.0, std::floor(secs_since(prior)));  // elapsed().as_secs().max(1)
-            rp_checkpoint cp{h->epoch, nodes, infos, (double)(infos - prior_infos) / secs};
-            prior = clock::now();
-            prior_infos = infos;
-            if (on_event) {
-                char line[96];
-                format_progress(line, sizeof line, cp.epoch, cp.nodes, cp.infos, cp.rate);
-                on_event(RP_TRAIN_CHECKPOINT, &cp, line, user);
-            }
-        }
-        if (secs_since(flushed) >= flush_interval) {  // FastSession::flush cadence (forge/src/fast.rs:97-125)
-            flushed = clock::now();
-            if (on_event) {
-                rp_checkpoint cp{h->epoch, nodes, infos, 0.0};
-                on_event(RP_TRAIN_FLUSH, &cp, "", user);
-            }
-        }
-        const bool stop = (interrupt && *interrupt) || (max_steps && steps >= max_steps) ||
-                          (max_seconds > 0.0 && secs_since(start) >= max_seconds);
-        if (stop) break;
-    }
-    int rc = rp_mccfr_counters(h, &nodes, &infos);
-    if (rc) return rc;
-    if (summary && summary_cap) {  // Progress::summary (progress.rs:24-26): rate over the whole run
-        char line[96];
-        const double secs = std::max(1.0, std::floor(secs_since(start)));
-        format_progress(line, sizeof line, h->epoch, nodes, infos, (double)infos / secs);
-        snprintf(summary, summary_cap, "training stopped\n%s", line);
-    }
-    return RP_OK;
+    auto step = [h](TrainCounts& c) {
+        const int rc = rp_mccfr_step(h);
+        c.epoch = h->epoch;
+        return rc;
+    };
+    auto refresh = [h](TrainCounts& c) { return rp_mccfr_counters(h, &c.nodes, &c.infos); };
+    return train_loop(step, refresh, max_steps, max_seconds, log_interval, flush_interval, on_event, user, interrupt, summary, summary_cap);
 }
 
 int rp_mccfr_epoch(rp_mccfr* h, uint64_t* epoch) {
@@ -1143,18 +1073,7 @@ int rp_mccfr_set_stream(rp_mccfr* h, void* hip_stream) {
     if (!h) return rp::fail(RP_ERR_INVALID, "rp_mccfr_set_stream: NULL handle");
     int rc = set_device(h);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->own_stream) {
-        HIP_TRY(hipStreamDestroy(h->stream));
-        h->own_stream = false;
-    }
-    if (hip_stream) {
-        h->stream = reinterpret_cast<hipStream_t>(hip_stream);
-    } else {
-        HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->own_stream = true;
-    }
-    return RP_OK;
+    return swap_stream(h->stream, h->own_stream, hip_stream);
 }
 
 int rp_mccfr_set_shard(rp_mccfr* h, uint32_t rank, uint32_t world) {
@@ -1259,10 +1178,9 @@ int rp_mccfr_profile(rp_mccfr* h, int enable) {
     if (!h) return rp::fail(RP_ERR_INVALID, "rp_mccfr_profile: NULL handle");
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    clock_drain_all(h);
-    h->profiling = enable != 0;
-    h->clk_traverse.total_ms = h->clk_compact.total_ms = h->clk_update.total_ms = 0.0;
-    h->clk_traverse.launches = h->clk_compact.launches = h->clk_update.launches = 0;
+    h->clk.drain();
+    h->clk.on = enable != 0;
+    h->clk.reset();
     return RP_OK;
 }
 
@@ -1297,15 +1215,7 @@ int rp_mccfr_kernel_time(rp_mccfr* h, const char* name, double* total_ms, uint64
     if (!h || !name) return rp::fail(RP_ERR_INVALID, "rp_mccfr_kernel_time: NULL argument");
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    clock_drain_all(h);
-    const KernelClock* c = nullptr;
-    if (std::string(name) == "traverse") c = &h->clk_traverse;
-    else if (std::string(name) == "compact") c = &h->clk_compact;
-    else if (std::string(name) == "update") c = &h->clk_update;
-    else return rp::fail(RP_ERR_INVALID, "rp_mccfr_kernel_time: unknown kernel '%s'", name);
-    if (total_ms) *total_ms = c->total_ms;
-    if (launches) *launches = c->launches;
-    return RP_OK;
+    return kernel_time(h->clk, "rp_mccfr_kernel_time", name, total_ms, launches);
 }
 
 // ---- Solver::exploitability (solver.rs:327-337) on the host: validation, not the hot path -------------
@@ -1616,7 +1526,7 @@ int rp_mccfr_solve_to(rp_mccfr* h, float target, uint32_t check_every, uint64_t 
     if (exploitability) *exploitability = value;
     if (reached) *reached = hit;
     rc = check_device_errors(h);  // the capacity flags of the steps, once, as rp_mccfr_sync reads them
-    clock_drain_all(h);
+    h->clk.drain();
     return rc;
 }
 

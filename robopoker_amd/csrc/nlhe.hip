@@ -11,15 +11,9 @@
 #include "../../include/rp_math.h"
 #include "cards.hpp"
 #include "nlhe_engine.hpp"
-#include "rp_internal.h"
+#include "host_util.hpp"
 
 namespace rp {
-
-#define HIP_TRY(expr)                                                                                 \
-    do {                                                                                              \
-        hipError_t _e = (expr);                                                                       \
-        if (_e != hipSuccess) return rp::fail(RP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
 
 using NlGame = NlGameT<NL_MAXP>;
 

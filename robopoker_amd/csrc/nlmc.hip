@@ -45,16 +45,10 @@
 #include "nlmc_census.hpp"
 #include "nlmc_table.hpp"
 #include "../../include/rp_libm_glibc.h"
-#include "rp_internal.h"
+#include "host_util.hpp"
 #include "sortscan.hpp"
 
 namespace rp {
-
-#define HIP_TRY(expr)                                                                                 \
-    do {                                                                                              \
-        hipError_t _e = (expr);                                                                       \
-        if (_e != hipSuccess) return rp::fail(RP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
 
 // ---- the multi-GPU exchange by infoset key (every rank's table assigns rows in its own insertion order) ----
 // entries: rp_profile_summarize's records, [row u32][count u32][psum f32][n_actions u32][maps]; keys beside them
@@ -82,6 +76,12 @@ __global__ __launch_bounds__(256) void k_nlhe_entry_remap(NlTable t, unsigned ch
 
 using namespace rp;
 
+namespace {
+// sweeps: up + down; decide: scan + fill + group + emit
+const char* const CLOCK_NAMES[] = {"expand", "children", "sweeps", "decide", "apply"};
+enum { CK_EXPAND, CK_CHILDREN, CK_SWEEPS, CK_DECIDE, CK_APPLY, CK_COUNT };
+}  // namespace
+
 struct rp_nlhe {
     int device = 0;
     rp_profile* prof = nullptr;
@@ -105,13 +105,7 @@ struct rp_nlhe {
     uint64_t nodes = 0, infos = 0;  // Metrics (mccfr/src/metrics/mod.rs): nodes grown, Decisions recorded
     uint32_t last_levels = 0, last_nodes = 0;
     // profiling (rp_nlhe_profile): HIP event pairs around the launches of each kernel group, on the launch stream
-    struct Clock {
-        std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
-        double total_ms = 0.0;
-        uint64_t launches = 0;
-    };
-    bool profiling = false;
-    Clock clk[5];  // expand, children, sweeps (up + down), decide (scan + fill + group + emit), apply
+    KernelClocks clk{CLOCK_NAMES, CK_COUNT};
     uint64_t census[5] = {0, 0, 0, 0, 0};  // nodes by kind + walker children, summed over the profiled steps
     // small batches (the reference's 128): one tree per workgroup, the whole traversal in one launch (k_nl_tree); tree_cap = nodes of a
     // tree's region (0: the node arrays were not sized for it), level_ncap = the batch-wide path's own node budget (its launch sizes)
@@ -179,32 +173,6 @@ int nl_capacity_error(unsigned long long flags) {
                                      "16 illegal action, 32 infoset table full, 64 isomorphism not found in the encoder table, 128 tree deeper "
                                      "than the level table, 256 work list full, 512 more than 16 walker decisions on one path with the exact evaluation on)", flags);
 }
-void nl_clock_begin(rp_nlhe* h, int k) {
-    if (!h->profiling) return;
-    hipEvent_t a, b;
-    (void)hipEventCreate(&a);
-    (void)hipEventCreate(&b);
-    (void)hipEventRecord(a, rp::profile_stream(h->prof));
-    h->clk[k].pending.emplace_back(a, b);
-}
-void nl_clock_end(rp_nlhe* h, int k) {
-    if (!h->profiling) return;
-    (void)hipEventRecord(h->clk[k].pending.back().second, rp::profile_stream(h->prof));
-    h->clk[k].launches += 1;
-}
-void nl_clock_drain(rp_nlhe* h) {
-    for (auto& c : h->clk) {
-        for (auto& pr : c.pending) {
-            float ms = 0.0f;
-            (void)hipEventSynchronize(pr.second);
-            (void)hipEventElapsedTime(&ms, pr.first, pr.second);
-            c.total_ms += ms;
-            (void)hipEventDestroy(pr.first);
-            (void)hipEventDestroy(pr.second);
-        }
-        c.pending.clear();
-    }
-}
 void nl_begin_step(rp_nlhe* h) {
     h->prm.epoch = rp::profile_epoch(h->prof);
     h->prm.walker = (uint32_t)(h->prm.epoch % 2u);  // CfrSampling::walker (book.rs:142-144)
@@ -258,7 +226,7 @@ int nl_traverse_chunk(rp_nlhe* h, uint32_t lo, uint32_t B, uint32_t d_base, uint
         if (!h->ctl_clean) HIP_TRY(hipMemsetAsync(lv.ctl, 0, sizeof(NlCtl), st));
         h->ctl_clean = false;
         prm.tag = nl_next_tag(h);
-        nl_clock_begin(h, 0);
+        h->clk.begin(st, CK_EXPAND);
         // the workgroup that finishes last scans the trees' Decisions counts and posts the batch's total and control block to the host
         // through pinned memory: the host spins on the sequence word (a scan launch + two copies + hipStreamSynchronize until round 6:
         // three launches and an interrupt round trip per step)
@@ -267,8 +235,8 @@ int nl_traverse_chunk(rp_nlhe* h, uint32_t lo, uint32_t B, uint32_t d_base, uint
         if (h->tree_bt == 256u) hipLaunchKernelGGL(k_nl_tree<256>, dim3(B), blk, 0, st, prm, h->tab, lv, h->tree_cap, WC, h->d_total, h->post_dev, h->post_seq);
         else if (h->tree_bt == 1024u) hipLaunchKernelGGL(k_nl_tree<1024>, dim3(B), dim3(1024), 0, st, prm, h->tab, lv, h->tree_cap, WC, h->d_total, h->post_dev, h->post_seq);
         else hipLaunchKernelGGL(k_nl_tree<512>, dim3(B), dim3(512), 0, st, prm, h->tab, lv, h->tree_cap, WC, h->d_total, h->post_dev, h->post_seq);
-        nl_clock_end(h, 0);
-        nl_clock_begin(h, 3);
+        h->clk.end(st, CK_EXPAND);
+        h->clk.begin(st, CK_DECIDE);
         // the Decisions are emitted behind the traversal without waiting for the host (nothing of the launch depends on the counts; a
         // tree that failed has no Decisions, and the host discards the buffer of a failed step): the post's way to the host and the
         // update's launches hide behind this kernel
@@ -288,19 +256,19 @@ int nl_traverse_chunk(rp_nlhe* h, uint32_t lo, uint32_t B, uint32_t d_base, uint
         ctl.walker_kids = h->post->walker_kids;
         if (ctl.err & (NERR_NODES | NERR_WALKERS)) {
             h->tree_mode_off = true;  // a tree outgrew its region: this step and the following ones on the batch-wide path
-            nl_clock_end(h, 3);
+            h->clk.end(st, CK_DECIDE);
         } else {
             if (ctl.err) {
                 *flags = ctl.err;
                 return nl_capacity_error(ctl.err);
             }
-            if (h->profiling) {
+            if (h->clk.on) {
                 for (int k = 0; k < 4; ++k) h->census[k] += ctl.kinds[k];
                 h->census[4] += ctl.walker_kids;
             }
             if ((uint64_t)d_base + total0 > h->out_cap)
                 return rp::fail(RP_ERR_CAPACITY, "rp_nlhe: %llu Decisions in one batch exceed the buffer (%u)", (unsigned long long)d_base + total0, h->out_cap);
-            nl_clock_end(h, 3);
+            h->clk.end(st, CK_DECIDE);
             HIP_TRY(hipGetLastError());
             h->keys = h->post->keys;
             h->keys_valid = true;
@@ -321,12 +289,12 @@ int nl_traverse_chunk(rp_nlhe* h, uint32_t lo, uint32_t B, uint32_t d_base, uint
         const uint32_t stop = std::min<uint32_t>(NL_MAXL - 1u, L + (L == 0 ? 22u : 6u));
         for (; L < stop; ++L) {
             prm.tag = nl_next_tag(h);
-            nl_clock_begin(h, 0);
+            h->clk.begin(st, CK_EXPAND);
             hipLaunchKernelGGL((k_nl_expand<4, 256>), wide_x, blk, 0, st, prm, h->tab, lv, L);
-            nl_clock_end(h, 0);
-            nl_clock_begin(h, 1);
+            h->clk.end(st, CK_EXPAND);
+            h->clk.begin(st, CK_CHILDREN);
             hipLaunchKernelGGL(k_nl_children, wide, blk, 0, st, prm, lv, L);
-            nl_clock_end(h, 1);
+            h->clk.end(st, CK_CHILDREN);
         }
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(&ctl, lv.ctl, sizeof(NlCtl), hipMemcpyDeviceToHost, st));
@@ -343,11 +311,11 @@ int nl_traverse_chunk(rp_nlhe* h, uint32_t lo, uint32_t B, uint32_t d_base, uint
     uint32_t levels = 0;
     while (levels < NL_MAXL && ctl.lvl_node[levels + 1] > ctl.lvl_node[levels]) levels += 1;
     const uint32_t n_nodes = ctl.lvl_node[levels];
-    nl_clock_begin(h, 2);
+    h->clk.begin(st, CK_SWEEPS);
     for (uint32_t l = levels; l-- > 0;) hipLaunchKernelGGL(k_nl_up, wide, blk, 0, st, lv, l);
     for (uint32_t l = 0; l + 1 < levels; ++l) hipLaunchKernelGGL(k_nl_down, wide, blk, 0, st, lv, l);
-    nl_clock_end(h, 2);
-    nl_clock_begin(h, 3);
+    h->clk.end(st, CK_SWEEPS);
+    h->clk.begin(st, CK_DECIDE);
     HIP_TRY(rp::ss::exclusive_scan<uint32_t>(lv.t_nw, lv.t_woff, B, h->d_scan, st, h->d_total + 1));
     hipLaunchKernelGGL(k_nl_fill, dim3(std::min<uint32_t>(wide.x, 2048u)), blk, 0, st, lv, n_nodes);
     hipLaunchKernelGGL((k_nl_group<256>), dim3(B), dim3(64), 0, st, lv, B);
@@ -364,7 +332,7 @@ int nl_traverse_chunk(rp_nlhe* h, uint32_t lo, uint32_t B, uint32_t d_base, uint
         *flags = ctl.err;
         return nl_capacity_error(ctl.err);
     }
-    if (h->profiling) {
+    if (h->clk.on) {
         for (int k = 0; k < 4; ++k) h->census[k] += ctl.kinds[k];
         h->census[4] += ctl.walker_kids;
     }
@@ -375,7 +343,7 @@ int nl_traverse_chunk(rp_nlhe* h, uint32_t lo, uint32_t B, uint32_t d_base, uint
         return rp::fail(RP_ERR_CAPACITY, "rp_nlhe: %u walker nodes in one pass exceed the buffer (%u)", total[1], lv.lcap);
     }
     hipLaunchKernelGGL(k_nl_emit, wide, blk, 0, st, lv, h->tab, total[1], d_base, lo, h->out_cap, h->out, 0u, (const float*)(lv.ex_k ? lv.wval : nullptr));
-    nl_clock_end(h, 3);
+    h->clk.end(st, CK_DECIDE);
     HIP_TRY(hipGetLastError());
     h->keys = keys_now;
     h->keys_valid = true;
@@ -614,9 +582,9 @@ int rp_nlhe_step(rp_nlhe* h, rp_update_mode mode) {
     int rc = h->grow_max ? nl_grow_table(h, h->grow_headroom ? h->grow_headroom : nl_default_headroom(h)) : RP_OK;
     if (rc || (rc = nl_traverse(h))) return rc;
     rp_decisions b{h->last_n, h->out.row, h->out.nact, h->out.expanded, h->out.regret, h->out.policy, h->out.payoff};
-    nl_clock_begin(h, 4);
+    h->clk.begin(rp::profile_stream(h->prof), CK_APPLY);
     rc = rp_profile_apply(h->prof, &b, mode);
-    nl_clock_end(h, 4);
+    h->clk.end(rp::profile_stream(h->prof), CK_APPLY);
     return rc;
 }
 
@@ -627,44 +595,16 @@ int rp_nlhe_step(rp_nlhe* h, rp_update_mode mode) {
 int rp_nlhe_train(rp_nlhe* h, rp_update_mode mode, uint64_t max_steps, double max_seconds, double log_interval, double flush_interval,
                   rp_train_event_fn on_event, void* user, const volatile int* interrupt, char* summary, size_t summary_cap) {
     if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_train: NULL handle");
-    using clock = std::chrono::steady_clock;
-    const auto start = clock::now();
-    auto prior = start, flushed = start;
-    uint64_t prior_infos = 0, steps = 0;
-    auto secs_since = [](clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); };
-    for (;;) {
-        int rc = rp_nlhe_step(h, mode);
-        if (rc) return rc;
-        steps += 1;
-        const uint64_t epoch = rp::profile_epoch(h->prof);
-        if (secs_since(prior) >= log_interval) {
-            const double secs = std::max(1.0, std::floor(secs_since(prior)));  // elapsed().as_secs().max(1)
-            rp_checkpoint cp{epoch, h->nodes, h->infos, (double)(h->infos - prior_infos) / secs};
-            prior = clock::now();
-            prior_infos = h->infos;
-            if (on_event) {
-                char line[96];
-                rp::format_progress(line, sizeof line, cp.epoch, cp.nodes, cp.infos, cp.rate);
-                on_event(RP_TRAIN_CHECKPOINT, &cp, line, user);
-            }
-        }
-        if (secs_since(flushed) >= flush_interval) {  // FastSession::flush cadence (forge/src/fast.rs:97-125)
-            flushed = clock::now();
-            if (on_event) {
-                rp_checkpoint cp{epoch, h->nodes, h->infos, 0.0};
-                on_event(RP_TRAIN_FLUSH, &cp, "", user);
-            }
-        }
-        const bool stop = (interrupt && *interrupt) || (max_steps && steps >= max_steps) || (max_seconds > 0.0 && secs_since(start) >= max_seconds);
-        if (stop) break;
-    }
-    if (summary && summary_cap) {
-        char line[96];
-        const double secs = std::max(1.0, std::floor(secs_since(start)));
-        rp::format_progress(line, sizeof line, rp::profile_epoch(h->prof), h->nodes, h->infos, (double)h->infos / secs);
-        snprintf(summary, summary_cap, "training stopped\n%s", line);
-    }
-    return RP_OK;
+    auto counts = [h](TrainCounts& c) {
+        c = {rp::profile_epoch(h->prof), h->nodes, h->infos};
+        return RP_OK;
+    };
+    auto step = [&](TrainCounts& c) {
+        const int rc = rp_nlhe_step(h, mode);
+        counts(c);
+        return rc;
+    };
+    return train_loop(step, counts, max_steps, max_seconds, log_interval, flush_interval, on_event, user, interrupt, summary, summary_cap);
 }
 
 // ---- profiling hooks used by bench.py: HIP events on the launch stream around each kernel group
@@ -672,9 +612,9 @@ int rp_nlhe_profile(rp_nlhe* h, int enable) {
     if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_profile: NULL handle");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(rp::profile_stream(h->prof)));
-    nl_clock_drain(h);
-    h->profiling = enable != 0;
-    for (auto& c : h->clk) c.total_ms = 0.0, c.launches = 0;
+    h->clk.drain();
+    h->clk.on = enable != 0;
+    h->clk.reset();
     for (auto& c : h->census) c = 0;
     return RP_OK;
 }
@@ -682,15 +622,7 @@ int rp_nlhe_kernel_time(rp_nlhe* h, const char* name, double* total_ms, uint64_t
     if (!h || !name) return rp::fail(RP_ERR_INVALID, "rp_nlhe_kernel_time: NULL argument");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(rp::profile_stream(h->prof)));
-    nl_clock_drain(h);
-    static const char* names[5] = {"expand", "children", "sweeps", "decide", "apply"};
-    for (int k = 0; k < 5; ++k)
-        if (!strcmp(name, names[k])) {
-            if (total_ms) *total_ms = h->clk[k].total_ms;
-            if (launches) *launches = h->clk[k].launches;
-            return RP_OK;
-        }
-    return rp::fail(RP_ERR_INVALID, "rp_nlhe_kernel_time: unknown kernel group '%s'", name);
+    return kernel_time(h->clk, "rp_nlhe_kernel_time", name, total_ms, launches);
 }
 // nodes of the profiled steps by kind {terminal, chance, walker, opponent} and the children of their walker nodes
 int rp_nlhe_census(rp_nlhe* h, uint64_t* kinds4, uint64_t* walker_children) {

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 
 #include "../../include/rp_mi355x.h"
 #include "../../include/rp_mi355x_diag.h"
@@ -22,6 +23,16 @@ namespace rp {
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 // Checkpoint's display line / Progress::format (metrics/checkpoint.rs:39-50, progress.rs:8-18)
 void format_progress(char* buf, size_t cap, uint64_t epoch, uint64_t nodes, uint64_t infos, double rate);
+
+// Trainer::train (crates/forge/src/trainer.rs:18-66), the loop behind rp_mccfr_train and rp_nlhe_train: loop { step; checkpoint;
+// flush; interrupt? }, then Progress::summary.  step runs one step and may update the counts; refresh brings nodes and infos up
+// to date and is called at each checkpoint and once before the summary.  A flush reports the counts as last known.
+struct TrainCounts {
+    uint64_t epoch, nodes, infos;
+};
+int train_loop(const std::function<int(TrainCounts&)>& step, const std::function<int(TrainCounts&)>& refresh, uint64_t max_steps,
+               double max_seconds, double log_interval, double flush_interval, rp_train_event_fn on_event, void* user,
+               const volatile int* interrupt, char* summary, size_t summary_cap);
 
 // What one table says about the trees below `root` (games.cpp).  Walker states keep every child, all other states one
 // (external sampling); each sampled-tree figure is the maximum over the walkers 0..n_players-1, saturating at UINT32_MAX.

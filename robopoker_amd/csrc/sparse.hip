@@ -17,14 +17,9 @@
 #include "sortscan.hpp"
 #include "mccfr_kernels.hpp"
 #include "policy_dist.hpp"
+#include "host_util.hpp"
 
 namespace rp {
-
-#define HIP_TRY(expr)                                                                                 \
-    do {                                                                                              \
-        hipError_t _e = (expr);                                                                       \
-        if (_e != hipSuccess) return rp::fail(RP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
 
 #define GROUP 16u  // lanes per row (max_actions <= 16)
 #define PF 8       // touches fetched ahead of the sequential chain
@@ -826,15 +821,14 @@ __global__ __launch_bounds__(256) void k_row_policy(const float* tab, uint64_t n
     }
 }
 
-struct SpClock {
-    double total_ms = 0.0;
-    uint64_t launches = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
-};
-
 }  // namespace rp
 
 using namespace rp;
+
+namespace {
+const char* const CLOCK_NAMES[] = {"sort", "apply"};
+enum { CK_SORT, CK_APPLY, CK_COUNT };
+}  // namespace
 
 struct rp_profile {
     int device = 0;
@@ -860,8 +854,7 @@ struct rp_profile {
     void* sort_tmp = nullptr;
     size_t sort_bytes = 0;
     unsigned char* entries = nullptr;  // local composed apply
-    bool profiling = false;
-    SpClock clk_sort, clk_apply;
+    KernelClocks clk{CLOCK_NAMES, CK_COUNT};  // rp_profile_profile
 };
 
 namespace rp {
@@ -884,30 +877,6 @@ unsigned char* profile_entries(rp_profile* h) { return h->entries; }  // the loc
 static size_t entry_bytes_of(const rp_profile* h) { return 16 + (size_t)2 * h->A * sizeof(Map); }
 // sum over rows of ceil(count / RP_SPARSE_BLOCK) <= rows + n / RP_SPARSE_BLOCK <= n + n / RP_SPARSE_BLOCK
 static uint32_t max_blocks_of(uint32_t n) { return n + n / RP_SPARSE_BLOCK + 1u; }
-
-static void sp_begin(rp_profile* h, SpClock& c) {
-    if (!h->profiling) return;
-    hipEvent_t a, b;
-    (void)hipEventCreate(&a);
-    (void)hipEventCreate(&b);
-    (void)hipEventRecord(a, h->stream);
-    c.pending.emplace_back(a, b);
-}
-static void sp_end(rp_profile* h, SpClock& c) {
-    if (!h->profiling || c.pending.empty()) return;
-    (void)hipEventRecord(c.pending.back().second, h->stream);
-    c.launches += 1;
-}
-static void sp_drain(SpClock& c) {
-    for (auto& pr : c.pending) {
-        float ms = 0.0f;
-        if (hipEventSynchronize(pr.second) == hipSuccess && hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess)
-            c.total_ms += ms;
-        (void)hipEventDestroy(pr.first);
-        (void)hipEventDestroy(pr.second);
-    }
-    c.pending.clear();
-}
 
 static void free_workspace(rp_profile* h) {
     for (void* p : {(void*)h->iota, (void*)h->keys_out, (void*)h->perm, (void*)h->seg_rows, (void*)h->seg_counts,
@@ -1130,8 +1099,7 @@ int rp_profile_destroy(rp_profile* h) {
     if (!h) return RP_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    sp_drain(h->clk_sort);
-    sp_drain(h->clk_apply);
+    h->clk.drain();
     free_workspace(h);
     if (h->tab) (void)hipFree(h->tab);
     if (h->n_segs) (void)hipFree(h->n_segs);
@@ -1151,7 +1119,7 @@ int rp_profile_apply(rp_profile* h, const rp_decisions* batch, rp_update_mode mo
         const DevBatch b{batch->row, batch->n_actions, batch->expanded, batch->regret, batch->policy, batch->payoff};
         // a small batch (the reference's 128 trees): sort, run lengths and block index by one workgroup in one launch (k_prep_one)
         const bool one = mode == RP_UPDATE_COMPOSED && batch->n <= ss::SORT_ONE && key_bits(h->n_rows) <= 27u && !h->no_prep_one;
-        sp_begin(h, h->clk_sort);
+        h->clk.begin(h->stream, CK_SORT);
         if (one) {
             if ((rc = ensure_capacity(h, batch->n))) return rc;
             hipLaunchKernelGGL(k_prep_one, dim3(1), dim3(1024), 0, h->stream, batch->row, batch->n, key_bits(h->n_rows), h->keys_out, h->perm,
@@ -1159,9 +1127,9 @@ int rp_profile_apply(rp_profile* h, const rp_decisions* batch, rp_update_mode mo
         } else if ((rc = sort_and_segment(h, batch->row, batch->n, mode == RP_UPDATE_COMPOSED))) {
             return rc;
         }
-        sp_end(h, h->clk_sort);
+        h->clk.end(h->stream, CK_SORT);
         const Segments sg{h->seg_rows, h->seg_counts, h->seg_offsets, h->n_segs, h->perm};
-        sp_begin(h, h->clk_apply);
+        h->clk.begin(h->stream, CK_APPLY);
         if (mode == RP_UPDATE_ORDERED) {
             const SortedBatch sb{h->srt_regret, h->srt_policy, h->srt_payoff, h->srt_expanded};
             hipLaunchKernelGGL(k_permute, dim3((unsigned)(((uint64_t)batch->n * h->A + 255) / 256)), dim3(256), 0, h->stream, b,
@@ -1180,7 +1148,7 @@ int rp_profile_apply(rp_profile* h, const rp_decisions* batch, rp_update_mode mo
             // no k_fold launch (measured round 4: apply 0.118 -> 0.113 ms at 2^17 Decisions, profiles/r04_optin_ab.json)
             if ((rc = launch_summarize(h, p, b, sg, batch->n, h->entries, true, one))) return rc;
         }
-        sp_end(h, h->clk_apply);
+        h->clk.end(h->stream, CK_APPLY);
         HIP_TRY(hipGetLastError());
     }
     h->epoch += 1;  // CfrSampling::increment via Solver::advance (solver.rs:103-104)
@@ -1297,16 +1265,7 @@ int rp_profile_policy(rp_profile* h, rp_dist_kind kind, uint64_t n, const uint32
 int rp_profile_set_stream(rp_profile* h, void* hip_stream) {
     if (!h) return rp::fail(RP_ERR_INVALID, "rp_profile_set_stream: null handle");
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-    if (hip_stream) {
-        h->stream = reinterpret_cast<hipStream_t>(hip_stream);
-        h->own_stream = false;
-    } else {
-        HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->own_stream = true;
-    }
-    return RP_OK;
+    return swap_stream(h->stream, h->own_stream, hip_stream);
 }
 
 int rp_profile_entry_bytes(const rp_profile* h, size_t* bytes) {
@@ -1325,13 +1284,13 @@ int rp_profile_summarize(rp_profile* h, const rp_decisions* batch, void* entries
     *n_entries = 0;
     if (batch->n == 0) return RP_OK;
     const DevBatch b{batch->row, batch->n_actions, batch->expanded, batch->regret, batch->policy, batch->payoff};
-    sp_begin(h, h->clk_sort);
+    h->clk.begin(h->stream, CK_SORT);
     if ((rc = sort_and_segment(h, batch->row, batch->n, true))) return rc;
-    sp_end(h, h->clk_sort);
+    h->clk.end(h->stream, CK_SORT);
     const Segments sg{h->seg_rows, h->seg_counts, h->seg_offsets, h->n_segs, h->perm};
-    sp_begin(h, h->clk_apply);
+    h->clk.begin(h->stream, CK_APPLY);
     if ((rc = launch_summarize(h, p, b, sg, batch->n, reinterpret_cast<unsigned char*>(entries_dev)))) return rc;
-    sp_end(h, h->clk_apply);
+    h->clk.end(h->stream, CK_APPLY);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(n_entries, h->n_segs, 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1348,14 +1307,14 @@ int rp_profile_fold(rp_profile* h, const void* entries_dev, uint32_t n_entries) 
         const unsigned char* ent = reinterpret_cast<const unsigned char*>(entries_dev);
         const uint32_t eb = (uint32_t)entry_bytes_of(h);
         if ((rc = ensure_capacity(h, n_entries))) return rc;
-        sp_begin(h, h->clk_sort);
+        h->clk.begin(h->stream, CK_SORT);
         hipLaunchKernelGGL(k_entry_rows, dim3((n_entries + 255) / 256), dim3(256), 0, h->stream, ent, eb, n_entries, h->ent_rows);
         if ((rc = sort_and_segment(h, h->ent_rows, n_entries))) return rc;
-        sp_end(h, h->clk_sort);
-        sp_begin(h, h->clk_apply);
+        h->clk.end(h->stream, CK_SORT);
+        h->clk.begin(h->stream, CK_APPLY);
         hipLaunchKernelGGL(k_fold, dim3(group_blocks(n_entries)), dim3(256), 0, h->stream, p, ent, eb, h->perm, h->seg_offsets,
                            h->seg_counts, h->n_segs);
-        sp_end(h, h->clk_apply);
+        h->clk.end(h->stream, CK_APPLY);
         HIP_TRY(hipGetLastError());
     }
     h->epoch += 1;
@@ -1366,25 +1325,16 @@ int rp_profile_profile(rp_profile* h, int enable) {
     if (!h) return rp::fail(RP_ERR_INVALID, "rp_profile_profile: null handle");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    sp_drain(h->clk_sort);
-    sp_drain(h->clk_apply);
-    if (enable && !h->profiling) {
-        h->clk_sort = SpClock{};
-        h->clk_apply = SpClock{};
-    }
-    h->profiling = enable != 0;
+    h->clk.drain();
+    if (enable && !h->clk.on) h->clk.reset();  // off -> on only: after profile(0) the totals stay readable
+    h->clk.on = enable != 0;
     return RP_OK;
 }
 int rp_profile_kernel_time(rp_profile* h, const char* name, double* total_ms, uint64_t* launches) {
     if (!h || !name || !total_ms || !launches) return rp::fail(RP_ERR_INVALID, "rp_profile_kernel_time: null argument");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    SpClock* c = std::string(name) == "sort" ? &h->clk_sort : (std::string(name) == "apply" ? &h->clk_apply : nullptr);
-    if (!c) return rp::fail(RP_ERR_INVALID, "rp_profile_kernel_time: unknown kernel '%s'", name);
-    sp_drain(*c);
-    *total_ms = c->total_ms;
-    *launches = c->launches;
-    return RP_OK;
+    return kernel_time(h->clk, "rp_profile_kernel_time", name, total_ms, launches);
 }
 
 }  // extern "C"

@@ -265,9 +265,7 @@ class Layer:
         _lib.check(self._lib.rp_kmeans_profile(self._h, 1 if enable else 0))
 
     def kernel_time(self, name: str):
-        ms, n = C.c_double(), C.c_uint64()
-        _lib.check(self._lib.rp_kmeans_kernel_time(self._h, name.encode(), C.byref(ms), C.byref(n)))
-        return ms.value, n.value
+        return _lib.kernel_time(self._lib.rp_kmeans_kernel_time, self._h, name)
 
 
 def margin_audit(points, centroids, tri, hp=None, device=0, chunk=64) -> dict:

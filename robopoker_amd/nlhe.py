@@ -287,37 +287,17 @@ class NlheSolver:
     def train(self, mode="composed", max_steps=0, max_seconds=0.0, log_interval=60.0, flush_interval=1800.0, on_checkpoint=None,
               on_flush=None, interrupt=None):
         """``Trainer::train`` (crates/forge/src/trainer.rs:18-66) over this solver; returns Progress::summary"""
-        EVENT = C.CFUNCTYPE(None, C.c_int, C.c_void_p, C.c_char_p, C.c_void_p)
-
-        class Checkpoint(C.Structure):
-            _fields_ = [("epoch", C.c_uint64), ("nodes", C.c_uint64), ("infos", C.c_uint64), ("rate", C.c_double)]
-
-        def cb(event, cp, line, _user):
-            c = C.cast(cp, C.POINTER(Checkpoint)).contents
-            d = {"epoch": c.epoch, "nodes": c.nodes, "infos": c.infos, "rate": c.rate}
-            if event == 0 and on_checkpoint:
-                on_checkpoint(d, line.decode())
-            if event == 1 and on_flush:
-                on_flush(d)
-
-        fn = EVENT(cb)
-        buf = C.create_string_buffer(256)
-        _lib.check(self._lib.rp_nlhe_train(self._h, _lib.UPDATE[mode], int(max_steps), float(max_seconds), float(log_interval),
-                                           float(flush_interval), C.cast(fn, C.c_void_p), None,
-                                           C.byref(interrupt) if interrupt is not None else None, buf, len(buf)))
-        return buf.value.decode()
+        return _lib.train(self._lib.rp_nlhe_train, self._h, _lib.UPDATE[mode], max_steps=max_steps, max_seconds=max_seconds,
+                          log_interval=log_interval, flush_interval=flush_interval, on_checkpoint=on_checkpoint, on_flush=on_flush,
+                          interrupt=interrupt)
 
     def profile(self, enable: bool):
         _lib.check(self._lib.rp_nlhe_profile(self._h, 1 if enable else 0))
 
     def kernel_times(self):
         """{group: (total_ms, launches)} since profile(True); groups: expand, children, sweeps, decide, apply"""
-        out = {}
-        for name in ("expand", "children", "sweeps", "decide", "apply"):
-            ms, n = C.c_double(), C.c_uint64()
-            _lib.check(self._lib.rp_nlhe_kernel_time(self._h, name.encode(), C.byref(ms), C.byref(n)))
-            out[name] = (ms.value, n.value)
-        return out
+        return {name: _lib.kernel_time(self._lib.rp_nlhe_kernel_time, self._h, name)
+                for name in ("expand", "children", "sweeps", "decide", "apply")}
 
     def census(self):
         """nodes of the profiled steps by kind + children of their walker nodes"""

@@ -125,9 +125,7 @@ class SparseProfile:
         _lib.check(self._lib.rp_profile_profile(self._h, int(enable)))
 
     def kernel_time(self, name: str):
-        ms, n = C.c_double(), C.c_uint64()
-        _lib.check(self._lib.rp_profile_kernel_time(self._h, name.encode(), C.byref(ms), C.byref(n)))
-        return ms.value, n.value
+        return _lib.kernel_time(self._lib.rp_profile_kernel_time, self._h, name)
 
 
 def synthetic_batch(n: int, n_rows: int, max_actions: int = 9, zipf: float = 1.1, seed: int = 0):

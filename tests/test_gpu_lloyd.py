@@ -135,6 +135,18 @@ def test_reference_seed_kmeanspp_picks_equal_the_oracle(gpu, kind, K, N, bins, m
     _check_state(dev, ora)
 
 
+def test_the_reference_draw_is_timed_by_the_event_pairs_of_kpp(gpu):
+    # "ref_draw" is a clock inside "kpp": each of its intervals is the same pair of events as one of kpp's, which holds more besides.
+    # Reading twice answers the same: a drained pair is counted once.
+    dev, _ = _pair("variation", 7, 1024, 64, 30, seed=21)
+    dev.set_rng("reference", 2)
+    dev.profile(True)
+    dev.init_centroids()
+    (ms_r, n_r), (ms_k, n_k) = dev.kernel_time("ref_draw"), dev.kernel_time("kpp")
+    assert n_r > 0 and n_k >= n_r and ms_k >= ms_r
+    assert (dev.kernel_time("ref_draw"), dev.kernel_time("kpp")) == ((ms_r, n_r), (ms_k, n_k))
+
+
 def _host_weighted_index(w, v01):
     """rand 0.9.2 WeightedIndex<f32>::new + sample for a given value0_1: sequential f32 running sums, x = v01 * scale, partition_point"""
     cum = np.add.accumulate(w, dtype=np.float32)

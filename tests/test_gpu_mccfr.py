@@ -451,6 +451,40 @@ def test_trainer_loop_checkpoints_and_summary(gpu):
     assert a.epoch == 13
 
 
+def test_trainer_flush_reports_the_counts_of_the_last_checkpoint(gpu):
+    # the solver's counters live on the device and are read back at a checkpoint only: with no checkpoint due (log interval 1e9),
+    # a flush after every step carries the step's epoch and the counts as last known — zeros — and costs no read-back; the summary
+    # reads them once at the end
+    a = Solver(Game("kuhn"), "floored", "linear", "external", batch=64, seed=5)
+    seen, flushes = [], []
+    summary = a.train(max_steps=3, log_interval=1e9, flush_interval=0.0, on_checkpoint=lambda cp, line: seen.append(cp),
+                      on_flush=lambda cp: flushes.append(cp))
+    assert not seen
+    assert [cp["epoch"] for cp in flushes] == [1, 2, 3]
+    assert all(cp["nodes"] == 0 and cp["infos"] == 0 for cp in flushes)
+    nodes, infos = a.counters()
+    assert nodes > 0 and infos > 0
+    assert summary == "training stopped\n" + "".join(
+        f"{x:<20}" for x in ("batch 3", f"nodes {nodes}", f"infos {infos}", f"I/sec {float(infos):.1f}"))
+
+
+def test_profile_switch_resets_the_kernel_clocks_on_every_call(gpu):
+    # rp_mccfr_profile zeroes totals and launch counts whenever it is called, on or off; the clocks count only while it is on
+    a = Solver(Game("kuhn"), "floored", "linear", "external", batch=64, seed=5)
+    a.profile(True)
+    a.step()
+    ms, n = a.kernel_time("traverse")
+    assert n == 1 and ms >= 0.0
+    a.profile(True)
+    assert a.kernel_time("traverse")[1] == 0
+    a.profile(False)
+    a.step()
+    assert [a.kernel_time(k)[1] for k in ("traverse", "compact", "update")] == [0, 0, 0]
+    with pytest.raises(_lib.RpError) as e:
+        a.kernel_time("no_such_kernel")
+    assert e.value.code == _lib.RP_ERR_INVALID and "no_such_kernel" in str(e.value)
+
+
 def test_update_mode_chosen_at_creation(gpu):
     # rp_mccfr_create_mode: a caller that wants the fast, shardable composed update says so once; the result is the solver that
     # rp_mccfr_create + rp_mccfr_set_update_mode builds, and a schedule the composed mode cannot express is refused at creation

@@ -476,6 +476,21 @@ def test_trainer_loop_over_the_nlhe_solver(gpu):
     assert a.epoch == 6
 
 
+def test_trainer_flush_reports_live_counts(gpu):
+    # this solver's counters are host values, current after every step: with no checkpoint due (log interval 1e9) each flush still
+    # carries them, and the last one is what counters() answers
+    a = NlheSolver(cap_log2=18, batch=128, seed=6, sampling="pluribus")
+    seen, flushes = [], []
+    a.train("composed", max_steps=2, log_interval=1e9, flush_interval=0.0, on_checkpoint=lambda cp, line: seen.append(cp),
+            on_flush=lambda cp: flushes.append(cp))
+    assert not seen
+    assert [cp["epoch"] for cp in flushes] == [1, 2]
+    assert flushes[0]["nodes"] > 0 and flushes[0]["infos"] > 0
+    assert flushes[1]["nodes"] >= flushes[0]["nodes"] and flushes[1]["infos"] >= flushes[0]["infos"]
+    assert (flushes[1]["nodes"], flushes[1]["infos"]) == a.counters()[:2]
+    a.close()
+
+
 def test_a_batch_traversed_in_several_passes_is_the_same_batch(gpu, monkeypatch):
     # The node arrays hold 1 536 nodes per tree of the batch.  Trees grow with training; a pass that runs out of nodes makes the
     # library traverse the batch in twice as many passes from then on (a pass = a contiguous range of tree ids) instead of failing

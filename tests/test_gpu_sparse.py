@@ -166,6 +166,22 @@ def test_composed_rejects_sign_dependent_discount_and_bad_arguments(gpu):
         g.rows([64])
 
 
+def test_profile_switch_keeps_the_totals_until_it_is_turned_on_again(gpu):
+    # rp_profile_profile resets the clocks on an off -> on transition only: after profile(False) the totals of the profiled batches
+    # are still readable (the benchmark reads them there)
+    g = SparseProfile(64, 4, "linear", "linear")
+    g.profile(True)
+    g.apply(DeviceBatch(*synthetic_batch(256, 64, 4, seed=3)), "ordered")
+    g.profile(False)
+    assert g.kernel_time("sort")[1] == 1 and g.kernel_time("apply")[1] == 1
+    assert g.kernel_time("sort")[0] >= 0.0
+    g.profile(True)
+    assert g.kernel_time("sort")[1] == 0 and g.kernel_time("apply")[1] == 0
+    with pytest.raises(_lib.RpError) as e:
+        g.kernel_time("no_such_kernel")
+    assert e.value.code == _lib.RP_ERR_INVALID
+
+
 def test_full_size_table_properties(gpu):
     # BASELINE configs[3] scale: 2^27 rows x 9 actions (19.3 GB in HBM), one 192 000-Decision Zipf batch per mode.
     # Size-independent properties: visits count the touches exactly, untouched rows keep the default Encounter,
