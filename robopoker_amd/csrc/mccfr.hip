@@ -467,8 +467,8 @@ bool traverse_maps_fused(const rp_mccfr* h) {
 }
 
 // composed update: whether a batch's group maps are folded by a launch of their own (k_combine2<false, false> + k_fold_groups) or by the
-// last workgroup of each tile of k_combine2.  FOLD_SPLIT_GROUPS: DESIGN.md §3, "The group fold as a launch of its own"
-constexpr uint32_t FOLD_SPLIT_GROUPS = 128;
+// last workgroup of each tile of k_combine2.  FOLD_SPLIT_GROUPS: DESIGN.md §3, "The group fold as a launch of its own" and "Unit slabs"
+constexpr uint32_t FOLD_SPLIT_GROUPS = 64;
 bool fold_split(const rp_mccfr* h, uint32_t batch) {
     const uint32_t ngrp = (chunks_of(batch) + RP_FOLD_GROUP - 1) / RP_FOLD_GROUP;
     return ngrp >= h->fold_split_groups;

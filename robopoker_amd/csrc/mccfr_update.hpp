@@ -849,25 +849,113 @@ __global__ __launch_bounds__(CB2_THREADS) void k_combine2(DevGame g, DevTables t
 //   load    the infoset's group maps — ngrp x (2A + 1) slots, 2A + 1 contiguous per group — by all lanes, FG_LOADS 16-byte loads per
 //           lane, every one issued before the first is waited for: one memory round trip, where the tail of k_combine2 pulls a whole
 //           tile's maps through one CU eight at a time;
-//   stage   into LDS in group order: FG_SLOTS slots = FG_SLOTS * 16 B = 40 KB of static LDS (three workgroups fit a CU's 160 KB; the
-//           grid needs one per CU).  A slab is the FG_SLOTS / (2A + 1) whole groups that fit (Leduc: 512, i.e. 2^23 trees); more
-//           groups take further slabs in group order, the running maps carried across;
-//   fold    lanes 0 .. 2A continue their slot's left fold through the slab in group order out of LDS (fold_slots: the association
-//           and the payoff-lane rule of k_combine2's stage 2, the reads FG_DEPTH ahead of the dependent chain);
+//   stage   into LDS in group order: FG_SLOTS slots = FG_SLOTS * 16 B = 40 KB of static LDS, 60.3 KB with the 20 KB of compacted
+//           operands of a unit slab, below (two workgroups fit a CU's 160 KB; the grid needs one per CU).  A slab is the
+//           FG_SLOTS / (2A + 1) whole groups that fit (Leduc: 512, i.e. 2^23 trees); more groups take further slabs in group order,
+//           the running maps carried across;
+//   fold    lanes 0 .. 2A continue their slot's left fold through the slab in group order out of LDS: a unit slab (below) compacted
+//           and by fold_unit_ops, any other by fold_slots (the association and the payoff-lane rule of k_combine2's stage 2); the
+//           reads FG_DEPTH ahead of the dependent chain in both;
 //   finish  fold_finish, as the last workgroup of a tile does in k_combine2.
+// Unit slabs.  With unit discounts (Summed / Floored regret, Constant / Linear / Quadratic weight: chain_params) every map has
+// a == 1.0f, and a step of the fold needs two dependent operations where map_compose_select spends six.  A slab is `unit` when every
+// non-empty map (n != 0) of its cell slots, and every non-empty running map carried into it, has a == 1.0f bitwise, a finite b and an m
+// that is not NaN.  The workgroup decides that once per slab, from the data, for all its cells together (a wavefront with lanes of both
+// kinds would run both loops one after the other); a slab that is not unit is folded by fold_slots as before.  For a unit slab
+//   compact  wavefront w packs the (b, m) of the non-empty maps of cell slots w, w + 4, ... in group order into LDS (ballot + popcount
+//            per 64 groups) and sums their counts: the chain meets no empty map, and the counts are off it;
+//   chain    lane `slot` folds its operands with fold_unit_ops, the reads FG_DEPTH ahead;
+//   payoff   a lane of the last wavefront adds the b and n of EVERY group's payoff slot in group order, from the carried sum:
+//            fold_slots' payoff-lane rule, beside the cell chains instead of in lock step with them.
+// The bits are those of fold_slots (map_compose_select) on the same slots:
+//   - an empty map is skipped and an empty running map becomes the first non-empty one: map_compose's first two lines;
+//   - x * 1.0f == x for every float, so with a == 1.0f on both sides map_compose_touched gives a' = 1.0f, b' = first.b + second.b
+//     and t = first.m + second.b: fold_unit_ops' operations on the same operands in the same order;
+//   - the one other difference is map_compose_touched's test for first.m == -inf, and with second.b finite -inf + second.b is -inf,
+//     the bits of first.m;
+//   - every b is finite and no m is NaN, so the running m never becomes NaN (+-inf + finite == +-inf; an overflowing running b is
+//     +-inf on both paths): rp_maxf never has a NaN to drop.
+// So the two differ only on operands that the test sends to fold_slots.
+typedef float __attribute__((ext_vector_type(2))) FgOp;  // (b, m) of a compacted operand (a plain vector, as Word4 below)
+__device__ __forceinline__ bool unit_operand(uint32_t a, uint32_t b, uint32_t m) {
+    return a == 0x3f800000u && (b & 0x7f800000u) != 0x7f800000u && (m & 0x7fffffffu) <= 0x7f800000u;
+}
+// one lane's left fold, continued from `tot`, of the cnt compacted operands (b, m) at op[0 .. cnt) of a unit slab; nsum: the sum of
+// their counts.  Two batches of D as in fold_slots, but whole batches only: the ragged rest has a loop of its own.
+template <uint32_t D>
+__device__ __forceinline__ void fold_unit_ops(Map& tot, const FgOp* op, uint32_t cnt, uint32_t nsum) {
+    float B = tot.b, M = tot.m;
+    uint32_t k = 0;
+    if (tot.n == 0 && cnt) {  // map_compose: first.n == 0
+        B = op[0].x;
+        M = op[0].y;
+        k = 1;
+    }
+    FgOp va[D], vb[D];
+    auto issue = [&](FgOp* v, uint32_t k0) __attribute__((always_inline)) {
+#pragma unroll
+        for (uint32_t q = 0; q < D; ++q) v[q] = op[k0 + q];
+    };
+    auto fold = [&](const FgOp* v) __attribute__((always_inline)) {
+#pragma unroll
+        for (uint32_t q = 0; q < D; ++q) {
+            B = B + v[q].x;
+            M = rp_maxf(M + v[q].x, v[q].y);
+        }
+    };
+    if (k + D <= cnt) {
+        issue(va, k);
+        for (; k + 3u * D <= cnt; k += 2u * D) {
+            issue(vb, k + D);
+            __builtin_amdgcn_sched_barrier(0);
+            fold(va);
+            __builtin_amdgcn_sched_barrier(0);
+            issue(va, k + 2u * D);
+            __builtin_amdgcn_sched_barrier(0);
+            fold(vb);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (k + 2u * D <= cnt) {
+            issue(vb, k + D);
+            __builtin_amdgcn_sched_barrier(0);
+            fold(va);
+            fold(vb);
+            k += 2u * D;
+        } else {
+            fold(va);
+            k += D;
+        }
+    }
+    for (; k < cnt; ++k) {
+        const FgOp v = op[k];
+        B = B + v.x;
+        M = rp_maxf(M + v.x, v.y);
+    }
+    tot.b = B;
+    tot.m = M;
+    tot.n += nsum;
+}
 #define FG_LOADS 10u
 #define FG_SLOTS (FG_LOADS * CB2_THREADS)
 #define FG_DEPTH 8u
+#define FG_WAVES (CB2_THREADS / 64u)
+#define FG_PAY_LANE (CB2_THREADS - 64u)  // the payoff lane of a unit slab: a wavefront of its own beside the cell lanes 0 .. 2A - 1
 static_assert(2u * RP_MAX_ACTIONS + 1u <= FG_SLOTS, "a slab of k_fold_groups holds at least one group");
+static_assert(2u * RP_MAX_ACTIONS <= FG_PAY_LANE, "the cell lanes of k_fold_groups end before its payoff lane's wavefront");
 __host__ __device__ inline uint32_t fg_slab_groups(uint32_t W2) { return FG_SLOTS / (W2 + 1u); }
 template <bool APPLY>
 __global__ __launch_bounds__(CB2_THREADS) void k_fold_groups(DevGame g, DevTables t, DevInfoTab it, StepParams p, const Map* gmaps, uint32_t nr,
                                                              Cell* cells, InfoSum* sums) {
     typedef uint32_t __attribute__((ext_vector_type(4))) Word4;  // (a plain vector: an array of uint4 in flight ends up in scratch)
     __shared__ __attribute__((aligned(16))) Word4 slab[FG_SLOTS];
+    __shared__ __attribute__((aligned(8))) FgOp ops[FG_SLOTS];  // unit slab: [cell slot][operand], n per slot (n * 2A < FG_SLOTS)
+    __shared__ uint32_t op_cnt[2u * RP_MAX_ACTIONS], op_n[2u * RP_MAX_ACTIONS];  // operands of a cell slot, and the sum of their counts
+    __shared__ uint32_t sh_general[FG_WAVES];
+    __shared__ float pay_b;
+    __shared__ uint32_t pay_n;
     __shared__ float sh_ps[1];
     __shared__ uint32_t sh_len[1];
-    const uint32_t rank = blockIdx.x, tid = threadIdx.x;
+    const uint32_t rank = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const uint32_t A = g.A, W2 = 2 * A, SL = W2 + 1u;
     if (!APPLY && rank == 0) blob_idle_entries(g, p, cells, sums);
     if (rank >= nr) return;
@@ -880,22 +968,78 @@ __global__ __launch_bounds__(CB2_THREADS) void k_fold_groups(DevGame g, DevTable
     for (uint32_t g0 = 0; g0 < ngrp; g0 += per) {
         const uint32_t n = min(per, ngrp - g0), nel = n * SL;  // 1 <= nel <= FG_SLOTS
         Word4 v[FG_LOADS];
+        uint32_t vslot[FG_LOADS];
 #pragma unroll
         for (uint32_t q = 0; q < FG_LOADS; ++q) {  // the clamp keeps the loads of a ragged slab inside it: no branch between the loads
             const uint32_t e = min(tid + q * CB2_THREADS, nel - 1u), k = e / SL;
-            v[q] = src[(size_t)(g0 + k) * row + (e - k * SL)];
+            vslot[q] = e - k * SL;
+            v[q] = src[(size_t)(g0 + k) * row + vslot[q]];
         }
         if (g0) __syncthreads();  // the fold of the slab before is done with the LDS
+        // is the slab unit?  A lane tests the maps it stages (a clamped load repeats the slab's last map: tested twice) and its running map
+        bool general = tid < W2 && tot.n != 0u && !unit_operand(rp_f2u(tot.a), rp_f2u(tot.b), rp_f2u(tot.m));
 #pragma unroll
         for (uint32_t q = 0; q < FG_LOADS; ++q) {
             const uint32_t e = tid + q * CB2_THREADS;
             if (e < nel) slab[e] = v[q];
+            general |= vslot[q] != W2 && v[q].w != 0u && !unit_operand(v[q].x, v[q].y, v[q].z);
+        }
+        const bool wave_general = __ballot(general) != 0ull;
+        if (lane == 0) sh_general[wave] = wave_general ? 1u : 0u;
+        __syncthreads();
+        uint32_t any_general = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < FG_WAVES; ++w) any_general |= sh_general[w];
+        if (__builtin_amdgcn_readfirstlane(any_general)) {  // the same for the whole workgroup
+            if (active) tot = fold_slots<FG_DEPTH>(tot, n, tid == W2, [&](uint32_t k) {
+                const Word4 w = slab[k * SL + tid];
+                return make_uint4(w.x, w.y, w.z, w.w);
+            });
+            continue;
+        }
+        for (uint32_t s = wave; s < W2; s += FG_WAVES) {  // compact
+            uint32_t base = 0, nsum = 0;
+            for (uint32_t k0 = 0; k0 < n; k0 += 64u) {
+                const uint32_t k = k0 + lane;
+                const Word4 w = slab[min(k, n - 1u) * SL + s];
+                const bool on = k < n && w.w != 0u;
+                const uint64_t mask = __ballot(on);
+                if (on) {
+                    const uint32_t at = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+                    ops[s * n + at] = FgOp{rp_u2f(w.y), rp_u2f(w.z)};
+                    nsum += w.w;
+                }
+                base += (uint32_t)__popcll(mask);
+            }
+            for (int d = 32; d > 0; d >>= 1) nsum += __shfl_xor(nsum, d, 64);
+            if (lane == 0) {
+                op_cnt[s] = base;
+                op_n[s] = nsum;
+            }
+        }
+        if (tid == W2) {  // the carried payoff sum and count, handed to the payoff lane
+            pay_b = tot.b;
+            pay_n = tot.n;
         }
         __syncthreads();
-        if (active) tot = fold_slots<FG_DEPTH>(tot, n, tid == W2, [&](uint32_t k) {
-            const Word4 w = slab[k * SL + tid];
-            return make_uint4(w.x, w.y, w.z, w.w);
-        });
+        if (tid < W2) fold_unit_ops<FG_DEPTH>(tot, ops + tid * n, op_cnt[tid], op_n[tid]);
+        if (tid == FG_PAY_LANE) {
+            float b = pay_b;
+            uint32_t cn = pay_n;
+#pragma unroll 8
+            for (uint32_t k = 0; k < n; ++k) {
+                const Word4 w = slab[k * SL + W2];
+                b += rp_u2f(w.y);
+                cn += w.w;
+            }
+            pay_b = b;
+            pay_n = cn;
+        }
+        __syncthreads();
+        if (tid == W2) {
+            tot.b = pay_b;
+            tot.n = pay_n;
+        }
     }
     const uint32_t info = g.rank_info[(size_t)p.walker * g.rank_max + rank];
     fold_finish<APPLY>(g, t, it, p, active, 0u, tid, info, tot, cells, sums, sh_ps, sh_len);
