@@ -535,8 +535,9 @@ RP_API int rp_nlhe_memory_device(rp_nlhe* h, uint64_t n, const uint64_t* past_de
 /* Ranges: what the blueprint says about every hole a seat could hold, given what the other seat has seen (Nlhe::reach,
  * opponent_reaches, opponent_range, opponent_observations, signalled_observations, signalled_reaches, normalize:
  * nlhe/src/solver.rs:137-260).  One recall is the edge-level content of a Witness (kicker/src/witness.rs:36-44) after
- * Recall::history(); translating actions to edges is the caller's.  Read-only exactly as the key queries above: nothing is inserted,
- * epoch / counters / keys are unchanged, no query can fail a later step.  One workgroup per recall (csrc/nlmc_range.hpp).
+ * Recall::history(); translating actions to edges is the caller's (rp_nlhe_translate does it on the device).  Read-only exactly
+ * as the key queries above: nothing is inserted, epoch / counters / keys are unchanged, no query can fail a later step.  One
+ * workgroup per recall (csrc/nlmc_range.hpp).
  *
  * CANDIDATES, in HandIterator order (deuce/src/hand_iter.rs: ascending numeric value of the two-bit mask), count[r] of them.
  *   `board` = the union of draws[0 .. k), k = the larger of the number of Draw edges in the history (at most 3) and the street the
@@ -1147,6 +1148,79 @@ typedef struct rp_match_summary {
     double   total_bb, bb_per_100, stddev, confidence;
 } rp_match_summary;         /* 40 bytes */
 RP_API int rp_match_summarize(uint64_t n, const int16_t* won, rp_match_summary* out);
+
+/* TRANSLATION: played hands (chip amounts) to recalls (edges) — the step rp_nlhe_reaches leaves to the caller, on the device.  An
+ * rp_aivat_hand exactly as rp_nlhe_match writes it and rp_nlhe_aivat reads it becomes the rp_nlhe_recall of seat pov[i] after the
+ * first upto[i] plays, with the key of its head.  Reference: Recall::history() (kicker/src/recall.rs:81-100), which calls
+ * Game::translate(action, past.aggression(), &translation, rng) (kicker/src/game.rs:778-811) under one of the three policies of
+ * pokerkit/src/translation.rs and translate/lattice.rs; Size::translate (kicker/src/size.rs:48-92); the key of
+ * NlheInfo::from((&recall, abstraction)) (nlhe/src/info.rs:117-122).  One lane per hand (csrc/nlmc_translate.hpp).  Read-only on the
+ * table exactly as rp_nlhe_policy: nothing is inserted, epoch / counters / keys are unchanged.
+ *
+ * INPUT.  hole[pov] is two cards; the other seat's hole may be 0 (unknown, as in a hand that ended in a fold), and is checked as
+ *   rp_nlhe_aivat checks it where it is not.  board_mode is ignored.  pov == NULL: pov[i] = hands[i].seat; upto == NULL:
+ *   upto[i] = hands[i].n_plays.
+ * THE REPLAY GAME is the hand's real game, Game::from_start(dealer, stacks) with 0,0 = STACK (Witness::initial_with,
+ *   kicker/src/witness.rs:77) — rp_nlhe_aivat's walker, NOT its default-stack witness game.
+ * PER PLAY j < upto, in this order:  while the game is at a chance node of street s: draws[s] == 0 gives RP_RECALL_DRAW, otherwise
+ *   draws[s] is dealt and a Draw edge appended to the recall's edges and to the running path.  A play at a terminal state, or one
+ *   is_allowed refuses, gives RP_RECALL_ILLEGAL.  depth = aggression() of the running path: the FIRST 12 edges of the whole history,
+ *   Draws included (MAX_PATH_EDGES), its trailing choice edges that are aggressive (kicker/src/path.rs:32-38) — the `run` count
+ *   stated above rp_nlhe_aivat.  edge = TRANSLATE(game before the play, play, depth); it is appended to the recall and to the running
+ *   path, and to the street's first-12 path (subgame()).  The play is applied.  After the last included play, while the game is at a
+ *   chance node whose street has cards in draws, that street is dealt and a Draw appended (an all-in run-out; the decision at the
+ *   start of the next street).  More than RP_NLHE_MAX_HISTORY edges give RP_RECALL_LENGTH, and so does upto > n_plays.
+ * TRANSLATE (game.rs:788-810, size.rs:48-92, lattice.rs:118-189).  Fold, Check, Call and Shove map to their edges.  Raise(chips): the
+ *   grid is Edge::raises(street, depth); an empty grid (depth above MAX_RAISE_REPEATS) gives Shove.  The cell (preflop, depth 0) is
+ *   the OPENING axis: x = (double)chips / 2.0, anchors (double)n over OPENS.  Every other cell is the POT-FRACTION axis:
+ *   x = (double)chips / (double)pot, anchors (double)n / (double)d in the cell's ascending order.  f64, one rounding per operation,
+ *   nothing contracted.
+ *   RP_TRANSLATE_SNAP      the first anchor with minimal |a - x|.
+ *   bracket                x <= the first anchor: (first, first); x >= the last: (last, last); otherwise hi = the first anchor not
+ *                          < x and lo the one before it.  p = ((b - x) * (1.0 + a)) / ((b - a) * (1.0 + x)), a = lo, b = hi: the
+ *                          pseudo-harmonic mapping of Ganzfried and Sandholm.
+ *   RP_TRANSLATE_PHARGMAX  lo if the bracket is clamped or p >= 0.5, else hi.
+ *   RP_TRANSLATE_HARMONIC  lo if the bracket is clamped or u < p, else hi.
+ *   RP_TRANSLATE_SNAP is Translation::Snap, NOT edgify: edgify takes the grid edge nearest IN CHIPS, with Edge::into_chips' truncation.
+ *   Dealer 0, stacks 200/200, Raise(5), Call(4), check, check, a turn pot of 12 and Raise(5): edgify answers edge 11 (1/3 pot: the
+ *   chip distances tie at |4 - 5| = |6 - 5| and the first wins), Snap answers edge 12 (1/2 pot: 5/12 - 1/3 = 0.08333333333333337,
+ *   1/2 - 5/12 = 0.08333333333333331).  rp_nlhe_aivat's and the matches' own histories keep edgify, as their contracts state.
+ * RANDOM NUMBERS.  The reference draws from the thread RNG: there is nothing of it to reproduce, so the library's counter contract
+ *   (include/rp_math.h) applies: u_j = (double)(rp_node_hash(seed, 3, first_id + i, j) >> 11) * 2^-53, j the index of the play in
+ *   the hand, counted whether or not the play is a raise, so that a hand's draws do not depend on its content (rp_node_hash carries
+ *   32 random bits, so u is a multiple of 2^-32).  Epoch 3 is a stream no other entry point names.  A hand's outputs depend on
+ *   seed, first_id + i and the args only: a batch split into calls with matching first_id answers the same bytes.
+ * OUTPUTS per hand, each pointer may be NULL.  recalls[i]: hole = hands[i].hole[pov], draws = the streets the replay dealt (0
+ *   elsewhere), stacks, dealer as given, pov, n_edges and the translated edges, zeros past them.  play_edges[i][RP_AIVAT_MAX_PLAYS]:
+ *   the edge of each included play without the Draws, 0 past upto.  The head's key: past = the street's first 12 edges;
+ *   choices = head.choices(aggression of that path), n_choices their number, both 0 where the head is no decision node;
+ *   present = the bucket of (hole, the head's board).
+ * STATUS per hand, rp_recall_status.  Checked before the replay, in this order: n_plays above RP_AIVAT_MAX_PLAYS or upto above
+ *   n_plays LENGTH; seat, dealer or pov above 1, stacks neither 0,0 nor both positive SEAT; hole[pov] not two cards, a non-zero other
+ *   hole not two cards, holes or draws that overlap, draws with wrong popcounts or out of street order CARDS; a kind (of any of the
+ *   n_plays plays) that is no rp_aivat_play EDGE.  Then the first refusal of the replay in the order above; last RP_RECALL_LOOKUP
+ *   where the lookup-table encoder does not hold (hole, the head's board).  A refused hand yields zero outputs and its status; the
+ *   call is still RP_OK and the other hands are answered.  No input causes an out-of-bounds access or an unbounded loop.
+ * THE CALL.  RP_ERR_INVALID, and nothing per hand, checked before a device is touched: NULL h or args, kind above
+ *   RP_TRANSLATE_PHARGMAX, reserved != 0; then, with n > 0, NULL hands.  n = 0 is RP_OK without a launch.  The _device form takes
+ *   every array pointer in DEVICE memory (args stay on the host), queues its launches on the handle's stream and returns, ordered
+ *   exactly like rp_nlhe_policy_device; the host form stages, launches and synchronises. */
+typedef enum { RP_TRANSLATE_SNAP = 0, RP_TRANSLATE_HARMONIC = 1, RP_TRANSLATE_PHARGMAX = 2 } rp_translation_kind;
+typedef struct rp_nlhe_translate_args {
+    uint64_t seed, first_id;
+    uint8_t  kind;          /* rp_translation_kind */
+    uint8_t  reserved[7];   /* 0 */
+} rp_nlhe_translate_args;   /* 24 bytes */
+/* seed 0, first_id 0, RP_TRANSLATE_SNAP */
+RP_API void rp_nlhe_translate_args_default(rp_nlhe_translate_args* out);
+RP_API int rp_nlhe_translate(rp_nlhe* h, uint64_t n, const rp_nlhe_translate_args* args /* host */, const rp_aivat_hand* hands,
+                             const uint8_t* pov /* [n] or NULL */, const uint8_t* upto /* [n] or NULL */, rp_nlhe_recall* recalls,
+                             uint8_t* play_edges /* [n][RP_AIVAT_MAX_PLAYS] */, uint64_t* past, uint32_t* present, uint64_t* choices,
+                             uint8_t* n_choices, uint8_t* status);
+RP_API int rp_nlhe_translate_device(rp_nlhe* h, uint64_t n, const rp_nlhe_translate_args* args /* host */, const rp_aivat_hand* hands_dev,
+                                    const uint8_t* pov_dev, const uint8_t* upto_dev, rp_nlhe_recall* recalls_dev, uint8_t* play_edges_dev,
+                                    uint64_t* past_dev, uint32_t* present_dev, uint64_t* choices_dev, uint8_t* n_choices_dev,
+                                    uint8_t* status_dev);
 
 /* SEARCH MATCHES: rp_nlhe_match in which a seat may re-solve every postflop decision — Agent<World<Blueprint>>,
  * Agent<World<Depth<Blueprint>>> and their Dirac<..> forms (parlor/src/players/{brain,world,solved,dirac,agent}.rs) — on the device from

@@ -52,6 +52,7 @@ RP_AIVAT_WITNESS = 11
 PLAY = {"fold": 1, "call": 2, "check": 3, "raise": 4, "shove": 5}  # rp_aivat_play
 AGENT = {"blueprint": 0, "dirac": 1, "fish": 2}  # rp_agent_kind
 SEARCH = {"none": 0, "world": 1}  # rp_search_kind
+TRANSLATE = {"snap": 0, "harmonic": 1, "phargmax": 2}  # rp_translation_kind
 RP_NLHE_SEARCH_MAX_SOLVES = 48
 
 
@@ -93,6 +94,11 @@ class NlheMatchArgs(C.Structure):
     """rp_nlhe_match_args: one per call (32 bytes)"""
     _fields_ = [("seed", C.c_uint64), ("first_id", C.c_uint64), ("stacks", C.c_int16 * 2), ("agent", C.c_uint8 * 2), ("dealer", C.c_uint8),
                 ("hero", C.c_uint8), ("mirror", C.c_uint8), ("snap", C.c_uint8), ("board_mode", C.c_uint8), ("reserved", C.c_uint8 * 5)]
+
+
+class NlheTranslateArgs(C.Structure):
+    """rp_nlhe_translate_args: one per call (24 bytes)"""
+    _fields_ = [("seed", C.c_uint64), ("first_id", C.c_uint64), ("kind", C.c_uint8), ("reserved", C.c_uint8 * 7)]
 
 
 class NlheSearchArgs(C.Structure):
@@ -491,6 +497,9 @@ _SIGNATURES = {
     "rp_nlhe_search_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(NlheSearchArgs)] + [C.c_void_p] * 7),
     "rp_nlhe_search_match_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(NlheSearchArgs)] + [C.c_void_p] * 7),
     "rp_match_summarize": (C.c_int, [C.c_uint64, C.c_void_p, C.POINTER(MatchSummary)]),
+    "rp_nlhe_translate_args_default": (None, [C.POINTER(NlheTranslateArgs)]),
+    "rp_nlhe_translate": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(NlheTranslateArgs)] + [C.c_void_p] * 10),
+    "rp_nlhe_translate_device": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(NlheTranslateArgs)] + [C.c_void_p] * 10),
     "rp_nlhe_table_census": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rp_nlhe_table_census_device": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rp_census_stats": (C.c_int, [C.c_void_p, C.POINTER(CensusTotals)]),

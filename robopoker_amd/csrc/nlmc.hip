@@ -41,6 +41,7 @@
 #include "nlmc_subgame.hpp"
 #include "nlmc_aivat.hpp"
 #include "nlmc_match.hpp"
+#include "nlmc_translate.hpp"
 #include "nlmc_search.hpp"
 #include "nlmc_census.hpp"
 #include "nlmc_table.hpp"
@@ -1652,6 +1653,71 @@ int rp_match_summarize(uint64_t n, const int16_t* won, rp_match_summary* out) {
     }
     out->confidence = 1.96 * out->stddev / sqrt(nf) * 100.0;
     return RP_OK;
+}
+
+}  // extern "C"
+
+// ---- translation (nlmc_translate.hpp): one lane per hand, at most NR_CHUNK hands per launch
+namespace {
+int nx_check(const rp_nlhe* h, uint64_t n, const rp_nlhe_translate_args* a, const void* hands) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_nlhe_translate: NULL handle");
+    if (!a) return rp::fail(RP_ERR_INVALID, "rp_nlhe_translate: NULL args");
+    if (a->kind > (uint8_t)RP_TRANSLATE_PHARGMAX) return rp::fail(RP_ERR_INVALID, "rp_nlhe_translate: kind %u is no rp_translation_kind", a->kind);
+    for (uint8_t r : a->reserved)
+        if (r != 0u) return rp::fail(RP_ERR_INVALID, "rp_nlhe_translate: reserved must be 0");
+    if (n == 0) return RP_OK;
+    if (!hands) return rp::fail(RP_ERR_INVALID, "rp_nlhe_translate: NULL hands with n > 0");
+    return RP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void rp_nlhe_translate_args_default(rp_nlhe_translate_args* out) {
+    if (!out) return;
+    *out = rp_nlhe_translate_args{};
+    out->kind = (uint8_t)RP_TRANSLATE_SNAP;
+}
+
+int rp_nlhe_translate_device(rp_nlhe* h, uint64_t n, const rp_nlhe_translate_args* args, const rp_aivat_hand* hands, const uint8_t* pov,
+                             const uint8_t* upto, rp_nlhe_recall* recalls, uint8_t* play_edges, uint64_t* past, uint32_t* present,
+                             uint64_t* choices, uint8_t* n_choices, uint8_t* status) {
+    int rc = nx_check(h, n, args, hands);
+    if (rc || n == 0) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = rp::profile_stream(h->prof);
+    return nl_chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
+        NxArgs q{};
+        q.hands = hands + at;
+        q.pov = nl_at(pov, at);
+        q.upto = nl_at(upto, at);
+        q.hash = rp_node_hash_step(args->seed, 3);
+        q.first_id = args->first_id + at;
+        q.n = m;
+        q.kind = args->kind;
+        q.recalls = nl_at(recalls, at);
+        q.play_edges = nl_at(play_edges, at * RP_AIVAT_MAX_PLAYS);
+        q.past = nl_at(past, at);
+        q.present = nl_at(present, at);
+        q.choices = nl_at(choices, at);
+        q.n_choices = nl_at(n_choices, at);
+        q.status = nl_at(status, at);
+        hipLaunchKernelGGL(k_nl_translate, dim3((m + NX_BLOCK - 1u) / NX_BLOCK), dim3(NX_BLOCK), 0, st, h->prm, q);
+    });
+}
+
+int rp_nlhe_translate(rp_nlhe* h, uint64_t n, const rp_nlhe_translate_args* args, const rp_aivat_hand* hands, const uint8_t* pov,
+                      const uint8_t* upto, rp_nlhe_recall* recalls, uint8_t* play_edges, uint64_t* past, uint32_t* present, uint64_t* choices,
+                      uint8_t* n_choices, uint8_t* status) {
+    int rc = nx_check(h, n, args, hands);
+    if (rc || n == 0) return rc;
+    Stage s(h);
+    s.in(hands, n).in(pov, n).in(upto, n);
+    s.out(recalls, n).out(play_edges, n * RP_AIVAT_MAX_PLAYS).out(past, n).out(present, n).out(choices, n).out(n_choices, n).out(status, n);
+    if ((rc = s.up()) ||
+        (rc = rp_nlhe_translate_device(h, n, args, hands, pov, upto, recalls, play_edges, past, present, choices, n_choices, status)))
+        return rc;
+    return s.down();
 }
 
 }  // extern "C"

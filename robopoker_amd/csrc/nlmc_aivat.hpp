@@ -61,6 +61,15 @@ struct NaCounts {
         act_aggr += (a.kind == NA_RAISE || a.kind == NA_SHOVE) ? 1u : 0u;
         return e;
     }
+    // note() for a history whose edges come from Game::translate (nlmc_translate.hpp): the action joins as the edge given
+    __device__ __forceinline__ void note_edge(const NlAction& a, uint32_t e) {
+        run.push(e);
+        if (sub_len < 12u) {
+            sub |= (uint64_t)e << (5u * sub_len++);
+            sub_aggr += (e == NE_SHOVE || e >= NE_OPEN0) ? 1u : 0u;
+        }
+        act_aggr += (a.kind == NA_RAISE || a.kind == NA_SHOVE) ? 1u : 0u;
+    }
     // a street was dealt into the witness game
     __device__ __forceinline__ void dealt() {
         run.push(NE_DRAW);

@@ -609,6 +609,49 @@ class NlheSolver:
                                                   *[_dptr(out[k], n) for k in ("hands", "won", "rejected", "status")]))
         return out
 
+    # ---- translation (include/rp_mi355x.h rp_nlhe_translate): played hands to the recalls the ranges, beliefs and re-solves read ----
+    @staticmethod
+    def _translate_args(kind="snap", seed=0, first_id=0):
+        """rp_nlhe_translate_args; ``kind``: "snap" / "harmonic" / "phargmax" (or an rp_translation_kind code)"""
+        a = _lib.NlheTranslateArgs()
+        _lib.load().rp_nlhe_translate_args_default(C.byref(a))
+        a.seed, a.first_id, a.kind = seed, first_id, _lib.TRANSLATE[kind] if isinstance(kind, str) else kind
+        return a
+
+    def translate(self, hands, kind="snap", pov=None, upto=None, seed=0, first_id=0):
+        """``Recall::history()`` under ``Translation::Snap`` / ``Harmonic`` / ``Phargmax`` for n played hands (``AivatHand``s, or the
+        records ``match`` writes): dict(recalls RECALL_DTYPE[n], the records ``reaches`` and ``belief`` take, seen from seat ``pov[i]``
+        (None: the hand's ``seat``) after the first ``upto[i]`` plays (None: all); play_edges uint8[n,48], the edge of each play;
+        past uint64[n], present uint32[n], choices uint64[n], the key of the recall's head as ``policy`` takes it; n_choices uint8[n];
+        status uint8[n]).  Harmonic draws for hand i from the counter stream of ``first_id + i``.  Read-only."""
+        hd = AivatHand.pack(hands)
+        n = hd.size
+        pov = None if pov is None else np.ascontiguousarray(pov, np.uint8)
+        upto = None if upto is None else np.ascontiguousarray(upto, np.uint8)
+        assert (pov is None or pov.size == n) and (upto is None or upto.size == n)
+        out = dict(recalls=np.zeros(n, RECALL_DTYPE), play_edges=np.zeros((n, MAX_PLAYS), np.uint8), past=np.zeros(n, np.uint64),
+                   present=np.zeros(n, np.uint32), choices=np.zeros(n, np.uint64), n_choices=np.zeros(n, np.uint8), status=np.zeros(n, np.uint8))
+        _lib.check(self._lib.rp_nlhe_translate(self._h, n, C.byref(self._translate_args(kind, seed, first_id)), _p(hd), _p(pov), _p(upto),
+                                               *[_p(out[k]) for k in ("recalls", "play_edges", "past", "present", "choices", "n_choices",
+                                                                      "status")]))
+        return out
+
+    def translate_device(self, hands_dev, kind="snap", pov=None, upto=None, seed=0, first_id=0):
+        """rp_nlhe_translate_device: ``hands_dev`` a device uint8 tensor [n, 192] (``match_device``'s ``hands``), ``pov`` / ``upto`` device
+        uint8 tensors [n] or None; -> the same dict of device tensors (recalls uint8[n, 88], which ``reaches_device`` and
+        ``belief_device`` take as it is; past / choices int64[n], present int32[n], which ``policy`` takes), queued on the solver's
+        stream (``sync()`` waits)"""
+        hd, n, d = _records(hands_dev, AIVAT_DTYPE)
+        pov, upto = (None if t is None else t.contiguous() for t in (pov, upto))
+        assert all(t is None or (t.is_cuda and t.element_size() == 1 and t.numel() == n) for t in (pov, upto))
+        out = dict(recalls=torch.empty((n, RECALL_DTYPE.itemsize), dtype=torch.uint8, device=d),
+                   play_edges=torch.empty((n, MAX_PLAYS), dtype=torch.uint8, device=d), past=torch.empty(n, dtype=torch.int64, device=d),
+                   present=torch.empty(n, dtype=torch.int32, device=d), choices=torch.empty(n, dtype=torch.int64, device=d),
+                   n_choices=torch.empty(n, dtype=torch.uint8, device=d), status=torch.empty(n, dtype=torch.uint8, device=d))
+        self._queue(self._lib.rp_nlhe_translate_device, d, n, (hd, pov, upto), n, C.byref(self._translate_args(kind, seed, first_id)), hd,
+                    pov, upto, *[out[k] for k in ("recalls", "play_edges", "past", "present", "choices", "n_choices", "status")])
+        return out
+
     # ---- search matches (include/rp_mi355x.h rp_nlhe_search_match): a seat may re-solve every postflop decision ----
     @staticmethod
     def _search_args(search=("none", "none"), origin_mode=0, iterations=None, rollouts=None, bias=None, prior=None, visit_threshold=None,
