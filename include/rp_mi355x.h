@@ -358,6 +358,131 @@ RP_API int rp_mccfr_fold_variant(rp_mccfr* h, int* out);
  * needed): 0 none (the generic traversal kernels), 1 Kuhn's, 2 Leduc's (any number of ranks). */
 RP_API int rp_game_skeleton(const rp_game_table* game, int* out);
 
+/* ---- safe subgame re-solve for table games (csrc/mccfr_subgame.hpp) ------------------------------------------------------------------
+ * SubGameSolver::<_, 1, ..>::new(blueprint, external, belief, recall) with origin = None, step x iterations, Harvest::harvest
+ * (subgame/src/solver.rs:47-49,146-229) over an rp_game_table game, with the handle's tables as the blueprint — what the reference's
+ * own known-answer tests run (kuhn/src/solver.rs:280-517, leduc/src/solver.rs:153-285).  Both calls are READ-ONLY on the handle
+ * exactly as rp_mccfr_policy is: tables, epoch and counters are unchanged, a sharded handle (world > 1) is served like any other (the
+ * tables are replicas).  They queue on the handle's stream.  One wavefront per belief entry / per solve.  A table with n_players != 2
+ * is RP_ERR_UNSUPPORTED (the reference's "two player game" expect).  The paragraphs named in capitals are those of the NLHE blocks
+ * below (PARTITION, RESTRICT, TREE, DRAWS, PROFILE, VALUES, UPDATE, RESULT); only the deltas are stated here.
+ *
+ * BELIEF = Posterior, then Partition::partition::<W> (subgame/src/world/partition.rs:26-52).  Per entry: n_prior <= 16 candidates
+ *   {root_state, secret < 16}, one shared path[n_path <= 16] of child slots, internal, mode, n_worlds = W in 1..4.  The mass of a
+ *   candidate: mode 0 (`baseline`, kuhn/src/encoder.rs:74, leduc/src/encoder.rs:71-81) 1.0f; mode 1 (Solver::external_reach,
+ *   mccfr/src/solver/solver.rs:198-210) the f32 product, from 1.0f in path order, of RP_DIST_AVERAGED(info)[slot] at the states on the
+ *   path from root_state whose turn is the seat other than `internal`; chance states on the path are stepped through and contribute
+ *   nothing.  The path is walked (and checked) in both modes.  Masses are added per secret in candidate order, from 0.0f
+ *   (Posterior::add).  The entries of PARTITION are the secrets some candidate has, in ascending secret; 4 is W: total <= 0 gives
+ *   world 0 to every entry and weights[w < W] = 1.0f / (float)W; otherwise segment = total / (float)W, the entries sorted by mass
+ *   descending and stable (equal masses keep ascending secret), at most one advance per entry, index < W - 1.  world_of[s] =
+ *   RP_WORLD_NONE for a secret no candidate has; weights are zero from W on.  Masses that are NaN are unspecified in value.
+ *   Statuses (first that applies): RP_MSUB_SEAT internal > 1, RP_MSUB_MODE mode > 1, RP_MSUB_WORLDS, RP_MSUB_COUNT n_prior or n_path
+ *   > 16, then per candidate in order RP_MSUB_SECRET, RP_MSUB_STATE, RP_MSUB_PATH (a slot >= n_children, which includes a terminal
+ *   before the path ends): never an out-of-bounds read.  A failed entry answers every world_of RP_WORLD_NONE and zero weights.
+ *
+ * SOLVE, per solve i with id = first_id + i.  rp_mccfr_subgame_entry: observed = the state of recall.game(); external; candidate[] =
+ *   the states the encoder's `restrict` enumerates (Card::ALL order, the other seat's card and the board excluded) with secret[];
+ *   world_of[16], weights[4], n_worlds as BELIEF writes them; harvest_info (RP_NO_INFO = the info of the restricted entry state of the
+ *   last iteration); harvest_order[16], whose first n_actions bytes are the slots of the harvest infoset in E's derived Ord (Harvest
+ *   folds regret over BTreeMap<E, _> keys; Kuhn's Call < Fold is not slot order).  A world_of byte >= n_worlds reads as RP_WORLD_NONE.
+ *   World of iteration t: the World rule of RESTRICT over weights[0 .. W) with h = rp_node_hash(seed, 1, id, t) (the reference uses
+ *     the thread RNG: the counter contract applies; the construction-time draw of `build` is discarded by the first step).
+ *   Restrict (leduc/src/encoder.rs:48-68, Kuhn's the same): if every world_of byte is RP_WORLD_NONE every candidate is remembered
+ *     (Belief::remember's empty-members clause) and the first candidate wins; otherwise the first candidate with world_of[secret] ==
+ *     world; if no candidate is chosen (n_candidates = 0 included) the entry state is `observed` and `fallbacks` counts it.
+ *   TREE without frontiers and Pick edges: node 0 is the entry state; a decision state's branches are its children in slot order, a
+ *     chance or terminal state has none (world/encoder.rs:100-107: a Leduc round-1 subgame ends at the board deal).  A node's infoset
+ *     is (world_t, rp_state.info).  walker = t % 2 keeps every branch, the other seat one by the weighted draw of DRAWS with h(node) =
+ *     rp_node_hash(seed, 2, id * RP_MCCFR_SUBGAME_MAX_ITERATIONS + t, node number), wrapping.  More than RP_MCCFR_SUBGAME_MAX_NODES
+ *     nodes is RP_MSUB_TREE.
+ *   PROFILE, VALUES, UPDATE word for word, "the blueprint row" being what rp_mccfr_get returns and "epoch" rp_mccfr_epoch: a local
+ *     row shadows the blueprint for its world only; a miss reads max(blueprint, EPSILON) for weight and regret, the blueprint's value
+ *     for payoff and visits; the first write warm-starts the row (mccfr/src/strategy/profile.rs:94-104); regret Summed, weight Linear
+ *     at local t, sampling External whatever the handle's R / W / S; tau, beta, eps from the handle's rp_hyper.  A chance leaf is
+ *     valued by cum_payoff(info, slot 0) of its parent's infoset — the local row of that world, else the blueprint (nash.rs:50-79).
+ *     A chance or terminal entry state is a valid solve that updates nothing.
+ *   RESULT with 4 = W: n_actions = the harvest infoset's (0 and info = RP_NO_INFO where the entry state is chance or terminal);
+ *     refined[a] = the fold from 0.0f over w < W of p_w[a] / (float)W; visits[a] the wrapping sum over w; regret ONE fold of
+ *     max(cum_regret, 0.0f), edges outer in harvest_order, worlds inner; sum_regret over the exported rows (slots ascending) divided by
+ *     (float)max(t, 1); drawn[w], fallbacks, nodes, infosets (updated), n_rows.  rows[i][..] sorted by (world, info), zero past n_rows;
+ *     n_rows is the true count even past rows_cap.  A failed solve yields a zero result with its status; the call is still RP_OK.
+ *   Statuses (first that applies): RP_MSUB_SEAT external > 1, RP_MSUB_WORLDS n_worlds outside 1..4, RP_MSUB_COUNT n_candidates > 16,
+ *     RP_MSUB_STATE observed or a candidate >= n_states, RP_MSUB_SECRET a candidate's secret >= 16, RP_MSUB_WEIGHT one of weights[0 ..
+ *     W) negative, NaN or infinite, RP_MSUB_INFO harvest_info neither RP_NO_INFO nor an infoset; while solving RP_MSUB_TREE,
+ *     RP_MSUB_ROWS (more than min(RP_MCCFR_SUBGAME_MAX_ROWS, 4 * n_infos) local rows); at the harvest RP_MSUB_ORDER (the first
+ *     n_actions bytes of harvest_order are no permutation).  No input causes an out-of-bounds access or an unbounded loop.
+ *   INVARIANCES.  A T-iteration solve is the first T iterations of a longer one; nothing depends on n, on the batch around a solve,
+ *     on how a batch is split over calls with matching first_id, or on the launch segments below.
+ * LAUNCHES.  A launch runs at most 8 192 iterations of every solve (RP_MCCFR_SUBGAME_SEGMENT = 1 .. 2^20 overrides; tests) and at
+ *   most 2 048 solves; the solver state between the launches of one call — the local profile, its (world, info) -> row index, the
+ *   counters — lives in a per-solve device region, allocated on first use, grown on demand, freed with the handle.  A table with more
+ *   than RP_MCCFR_SUBGAME_MAX_INFOS infosets is RP_ERR_CAPACITY (the index keeps u16 row numbers, 4 x n_infos of them per solve).
+ * Arguments.  solve: args first, without a device — NULL args, iterations outside 1 .. RP_MCCFR_SUBGAME_MAX_ITERATIONS, a prior not
+ *   finite and positive, reserved != 0: RP_ERR_INVALID; then n = 0 is RP_OK without a launch; then a NULL handle, entries or results,
+ *   or rows == NULL with rows_cap > 0: RP_ERR_INVALID; then n_players != 2: RP_ERR_UNSUPPORTED.  belief: n = 0 is RP_OK; a NULL handle,
+ *   priors, world_of or weights is RP_ERR_INVALID (status may be NULL); then n_players != 2.  The host forms stage, launch and
+ *   synchronise; the _device forms take every array in DEVICE memory (args on the host) and return without synchronising.
+ * OUT OF SCOPE: SubGameSolver::with_origin, DepthSolver / DepthEncoder for table games (Payoffs::uniform(frontier_payoff) and the
+ *   Pick game), the reference-seed RNG for these draws, more than two players, tests/emul. */
+#define RP_MCCFR_SUBGAME_MAX_ITERATIONS (1u << 20)
+#define RP_MCCFR_SUBGAME_MAX_NODES 62u
+#define RP_MCCFR_SUBGAME_MAX_ROWS 1024u
+#define RP_MCCFR_SUBGAME_MAX_INFOS 8192u
+#define RP_MCCFR_SUBGAME_MAX_CANDIDATES 16u
+#ifndef RP_WORLD_NONE
+#define RP_WORLD_NONE 0xffu
+#endif
+enum { RP_MSUB_OK = 0, RP_MSUB_SEAT = 1, RP_MSUB_MODE = 2, RP_MSUB_WORLDS = 3, RP_MSUB_COUNT = 4, RP_MSUB_STATE = 5, RP_MSUB_SECRET = 6,
+       RP_MSUB_PATH = 7, RP_MSUB_WEIGHT = 8, RP_MSUB_INFO = 9, RP_MSUB_TREE = 10, RP_MSUB_ROWS = 11, RP_MSUB_ORDER = 12 };
+typedef struct rp_mccfr_subgame_prior { /* one belief entry */
+    uint32_t root_state[16];
+    uint8_t secret[16];
+    uint8_t path[16];
+    uint8_t n_prior, n_path, internal, mode, n_worlds, pad[3];
+} rp_mccfr_subgame_prior;  /* 104 bytes */
+typedef struct rp_mccfr_subgame_entry { /* one solve */
+    uint32_t observed, harvest_info;
+    uint32_t candidate[16];
+    uint8_t secret[16], world_of[16], harvest_order[16];
+    float weights[4];
+    uint8_t external, n_candidates, n_worlds, pad;
+} rp_mccfr_subgame_entry;  /* 140 bytes */
+typedef struct rp_mccfr_subgame_args { /* one per call */
+    uint32_t iterations; /* 1 .. RP_MCCFR_SUBGAME_MAX_ITERATIONS */
+    float prior;         /* WarmstartHyperParams::prior_strength as f32: finite, > 0 */
+    uint64_t seed, first_id;
+    uint32_t rows_cap;   /* local-profile rows exported per solve; 0 = none */
+    uint32_t reserved;   /* 0 */
+} rp_mccfr_subgame_args;   /* 32 bytes */
+typedef struct rp_mccfr_subgame_result {
+    uint32_t info;       /* the harvest infoset; RP_NO_INFO where there is none */
+    uint8_t n_actions, status, pad[2];
+    float refined[16];
+    uint32_t visits[16];
+    float regret, sum_regret;
+    uint32_t iterations, n_rows;
+    uint64_t nodes, infosets;
+    uint32_t drawn[4];
+    uint32_t fallbacks, pad2;
+} rp_mccfr_subgame_result; /* 192 bytes */
+typedef struct rp_mccfr_subgame_row {
+    uint8_t world, n_actions, pad[2];
+    uint32_t info;
+    rp_encounter enc[16]; /* zero from n_actions on */
+} rp_mccfr_subgame_row;    /* 264 bytes */
+/* 1 iteration, prior 2^14 (WarmstartHyperParams::default), seed 0, first_id 0, no rows */
+RP_API void rp_mccfr_subgame_args_default(rp_mccfr_subgame_args* out);
+RP_API int rp_mccfr_subgame_belief(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_prior* priors, uint8_t* world_of /* [n][16] */,
+                                   float* weights /* [n][4] */, uint8_t* status /* [n] or NULL */);
+RP_API int rp_mccfr_subgame_belief_device(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_prior* priors_dev, uint8_t* world_of_dev,
+                                          float* weights_dev, uint8_t* status_dev);
+RP_API int rp_mccfr_subgame_solve(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries, const rp_mccfr_subgame_args* args,
+                                  rp_mccfr_subgame_result* results, rp_mccfr_subgame_row* rows /* [n][rows_cap] or NULL */);
+RP_API int rp_mccfr_subgame_solve_device(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries_dev,
+                                         const rp_mccfr_subgame_args* args /* host */, rp_mccfr_subgame_result* results_dev,
+                                         rp_mccfr_subgame_row* rows_dev);
+
 /* ============================================================= sparse profile ==
  * The update half of Solver::step (solver/solver.rs:96-105,143-192: update_regret, update_weight, update_payoff,
  * update_visits in batch order, then epoch += 1) for tables addressed by ROW INDEX: the NLHE-scale shape

@@ -47,6 +47,10 @@ RP_NLHE_DEPTH_ORIGIN_ENTRY = 127
 RP_DEPTH_NODES, RP_DEPTH_ROWS, RP_DEPTH_FRONTIERS = 8, 9, 10
 RP_NLHE_SUBGAME_MAX_ROWS = 2048
 RP_NLHE_SUBGAME_ORIGIN_NONE = 126
+RP_MCCFR_SUBGAME_MAX_ITERATIONS = 1 << 20
+RP_MCCFR_SUBGAME_MAX_NODES, RP_MCCFR_SUBGAME_MAX_ROWS, RP_MCCFR_SUBGAME_MAX_INFOS, RP_MCCFR_SUBGAME_MAX_CANDIDATES = 62, 1024, 8192, 16
+(RP_MSUB_OK, RP_MSUB_SEAT, RP_MSUB_MODE, RP_MSUB_WORLDS, RP_MSUB_COUNT, RP_MSUB_STATE, RP_MSUB_SECRET, RP_MSUB_PATH, RP_MSUB_WEIGHT, RP_MSUB_INFO,
+ RP_MSUB_TREE, RP_MSUB_ROWS, RP_MSUB_ORDER) = range(13)
 RP_AIVAT_MAX_PLAYS = 48
 RP_AIVAT_WITNESS = 11
 PLAY = {"fold": 1, "call": 2, "check": 3, "raise": 4, "shove": 5}  # rp_aivat_play
@@ -71,6 +75,11 @@ class Hyper(C.Structure):
 
 class Encounter(C.Structure):
     _fields_ = [("weight", C.c_float), ("regret", C.c_float), ("payoff", C.c_float), ("visits", C.c_uint32)]
+
+
+class MccfrSubgameArgs(C.Structure):  # rp_mccfr_subgame_args, 32 bytes
+    _fields_ = [("iterations", C.c_uint32), ("prior", C.c_float), ("seed", C.c_uint64), ("first_id", C.c_uint64), ("rows_cap", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 
 class NlheRecall(C.Structure):
@@ -341,6 +350,11 @@ _SIGNATURES = {
     "rp_mccfr_solve_to": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_float),
                                     C.POINTER(C.c_int)]),
     "rp_mccfr_sum_regret": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "rp_mccfr_subgame_args_default": (None, [C.POINTER(MccfrSubgameArgs)]),
+    "rp_mccfr_subgame_belief": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rp_mccfr_subgame_belief_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rp_mccfr_subgame_solve": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(MccfrSubgameArgs), C.c_void_p, C.c_void_p]),
+    "rp_mccfr_subgame_solve_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(MccfrSubgameArgs), C.c_void_p, C.c_void_p]),
     "rp_mccfr_set_batch": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rp_mccfr_set_update_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "rp_mccfr_set_rng": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(HashStreams)]),

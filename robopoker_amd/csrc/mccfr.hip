@@ -24,6 +24,7 @@
 #include "mccfr_update.hpp"
 #include "traverse_static.hpp"
 #include "mccfr_nash.hpp"
+#include "mccfr_subgame.hpp"
 #include "host_util.hpp"
 
 #include <algorithm>
@@ -40,8 +41,8 @@
 using namespace rp;
 
 namespace {
-const char* const CLOCK_NAMES[] = {"traverse", "compact", "update"};
-enum { CK_TRAVERSE, CK_COMPACT, CK_UPDATE, CK_COUNT };
+const char* const CLOCK_NAMES[] = {"traverse", "compact", "update", "subgame"};
+enum { CK_TRAVERSE, CK_COMPACT, CK_UPDATE, CK_SUBGAME, CK_COUNT };
 }  // namespace
 
 struct rp_mccfr {
@@ -112,6 +113,9 @@ struct rp_mccfr {
     bool nash_in_lds = false;
     std::vector<uint32_t> nash_level_size;  // nodes per depth level: the grids of k_nash_level
     float* nash_pinned = nullptr;  // rp_mccfr_solve_to: the check's value, mapped host memory
+    // the safe subgame re-solve (mccfr_subgame.hpp): the per-solve regions of one launch, grow-only
+    void* d_msub = nullptr;
+    size_t msub_bytes = 0;
 };
 
 namespace {
@@ -798,6 +802,7 @@ int rp_mccfr_destroy(rp_mccfr* h) {
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->d_nash) (void)hipFree(h->d_nash);
+    if (h->d_msub) (void)hipFree(h->d_msub);
     if (h->nash_pinned) (void)hipHostFree(h->nash_pinned);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -1526,6 +1531,188 @@ int rp_mccfr_solve_to(rp_mccfr* h, float target, uint32_t check_every, uint64_t 
     if (exploitability) *exploitability = value;
     if (reached) *reached = hit;
     rc = check_device_errors(h);  // the capacity flags of the steps, once, as rp_mccfr_sync reads them
+    h->clk.drain();
+    return rc;
+}
+
+}  // extern "C"
+
+// ---- the safe subgame re-solve for table games (mccfr_subgame.hpp) ------------------------------------------------------------------
+namespace {
+
+size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// iterations per launch: RP_MCCFR_SUBGAME_SEGMENT (tests), else 8 192
+int msub_segment(uint32_t* out) {
+    *out = 8192;
+    const char* s = getenv("RP_MCCFR_SUBGAME_SEGMENT");
+    if (!s || !*s) return RP_OK;
+    char* end = nullptr;
+    const long v = strtol(s, &end, 10);
+    if (*end || v < 1 || v > (long)RP_MCCFR_SUBGAME_MAX_ITERATIONS)
+        return rp::fail(RP_ERR_INVALID, "RP_MCCFR_SUBGAME_SEGMENT is '%s': 1 .. %u", s, RP_MCCFR_SUBGAME_MAX_ITERATIONS);
+    *out = (uint32_t)v;
+    return RP_OK;
+}
+
+int msub_check_args(const char* who, const rp_mccfr_subgame_args* args) {
+    if (!args) return rp::fail(RP_ERR_INVALID, "%s: args is NULL", who);
+    if (args->iterations < 1 || args->iterations > RP_MCCFR_SUBGAME_MAX_ITERATIONS)
+        return rp::fail(RP_ERR_INVALID, "%s: iterations %u outside 1 .. %u", who, args->iterations, RP_MCCFR_SUBGAME_MAX_ITERATIONS);
+    if (!(args->prior > 0.0f) || args->prior > RP_F32_MAX) return rp::fail(RP_ERR_INVALID, "%s: prior must be finite and positive", who);
+    if (args->reserved != 0) return rp::fail(RP_ERR_INVALID, "%s: reserved must be 0", who);
+    return RP_OK;
+}
+
+int msub_check_game(const char* who, const rp_mccfr* h) {
+    if (h->tbl.n_players != 2) return rp::fail(RP_ERR_UNSUPPORTED, "%s: two player game expected, the table has %u", who, h->tbl.n_players);
+    return RP_OK;
+}
+
+// every launch of one call, queued on the handle's stream; every array in device memory
+int msub_launch_solve(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries, const rp_mccfr_subgame_args* a, rp_mccfr_subgame_result* results,
+                      rp_mccfr_subgame_row* rows) {
+    const uint32_t NI = h->tbl.n_infos, A = h->tbl.max_actions;
+    if (NI > RP_MCCFR_SUBGAME_MAX_INFOS)
+        return rp::fail(RP_ERR_CAPACITY, "rp_mccfr_subgame_solve: %u infosets, the local profile's index holds %u", NI, RP_MCCFR_SUBGAME_MAX_INFOS);
+    uint32_t segment = 0;
+    int rc = msub_segment(&segment);
+    if (rc) return rc;
+    MsRegion R{};
+    R.rows_alloc = std::min<uint32_t>(RP_MCCFR_SUBGAME_MAX_ROWS, 4 * NI);
+    R.off_index = (uint32_t)sizeof(MsHead);
+    R.off_keys = (uint32_t)align16(R.off_index + 2 * (size_t)4 * NI);
+    R.off_perm = (uint32_t)align16(R.off_keys + 4 * (size_t)R.rows_alloc);
+    R.off_rows = (uint32_t)align16(R.off_perm + 2 * (size_t)R.rows_alloc);
+    R.stride = align16(R.off_rows + (size_t)R.rows_alloc * A * sizeof(rp_encounter));
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(n, MS_MAX_CHUNK);
+    const size_t need = R.stride * chunk;
+    if (need > h->msub_bytes) {
+        if (h->d_msub) HIP_TRY(hipFree(h->d_msub));  // waits for the launches that still use it
+        h->d_msub = nullptr;
+        h->msub_bytes = 0;
+        if (hipMalloc(&h->d_msub, need) != hipSuccess) {
+            (void)hipGetLastError();
+            return rp::fail(RP_ERR_CAPACITY, "rp_mccfr_subgame_solve: %zu bytes of local profiles for %u solves do not fit", need, chunk);
+        }
+        h->msub_bytes = need;
+    }
+    R.base = reinterpret_cast<uint8_t*>(h->d_msub);
+    MsParams p{};
+    p.rows_cap = a->rows_cap;
+    p.n_states = h->tbl.n_states;
+    p.n_terminals = h->tbl.n_terminals;
+    p.seed = a->seed;
+    p.iterations = a->iterations;
+    p.prior = a->prior;
+    p.hp = DistParams{h->hp.temperature, h->hp.smoothing, h->hp.curiosity};
+    h->clk.begin(h->stream, CK_SUBGAME);
+    for (uint64_t at = 0; at < n; at += chunk) {
+        p.n = (uint32_t)std::min<uint64_t>(chunk, n - at);
+        p.entries = entries + at;
+        p.results = results + at;
+        p.rows = rows ? rows + at * a->rows_cap : nullptr;
+        p.first_id = a->first_id + at;
+        for (uint32_t t = 0; t < a->iterations; t += segment) {
+            p.t_begin = t;
+            p.t_end = (uint32_t)std::min<uint64_t>((uint64_t)t + segment, a->iterations);
+            hipLaunchKernelGGL(k_mccfr_subgame_solve, dim3(p.n), dim3(MS_LANES), 0, h->stream, h->g, h->t, R, p);
+        }
+    }
+    h->clk.end(h->stream, CK_SUBGAME);
+    HIP_TRY(hipGetLastError());
+    return RP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void rp_mccfr_subgame_args_default(rp_mccfr_subgame_args* out) {
+    if (!out) return;
+    *out = rp_mccfr_subgame_args{};
+    out->iterations = 1;
+    out->prior = 16384.0f;
+}
+
+int rp_mccfr_subgame_belief_device(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_prior* priors_dev, uint8_t* world_of_dev, float* weights_dev,
+                                   uint8_t* status_dev) {
+    if (n == 0) return RP_OK;
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_belief: h is NULL");
+    if (!priors_dev || !world_of_dev || !weights_dev) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_belief: priors, world_of or weights is NULL");
+    if (n > 0x7fffffffull) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_belief: n is larger than 2^31 - 1");
+    int rc = msub_check_game("rp_mccfr_subgame_belief", h);
+    if (rc) return rc;
+    if ((rc = set_device(h))) return rc;
+    hipLaunchKernelGGL(k_mccfr_subgame_belief, dim3((uint32_t)n), dim3(MS_LANES), 0, h->stream, h->g, h->t, h->tbl.n_states, (uint32_t)n, priors_dev,
+                       world_of_dev, weights_dev, status_dev);
+    HIP_TRY(hipGetLastError());
+    return RP_OK;
+}
+
+int rp_mccfr_subgame_belief(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_prior* priors, uint8_t* world_of, float* weights, uint8_t* status) {
+    if (n == 0) return RP_OK;
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_belief: h is NULL");
+    if (!priors || !world_of || !weights) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_belief: priors, world_of or weights is NULL");
+    int rc = msub_check_game("rp_mccfr_subgame_belief", h);
+    if (rc) return rc;
+    if ((rc = set_device(h))) return rc;
+    const size_t b_in = n * sizeof(rp_mccfr_subgame_prior), b_wo = n * 16, b_wt = n * 16, b_st = n;
+    uint8_t* d = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), align16(b_in) + b_wo + b_wt + align16(b_st)));
+    uint8_t *d_wo = d + align16(b_in), *d_wt = d_wo + b_wo, *d_st = d_wt + b_wt;
+    rc = RP_OK;
+    if (hipMemcpyAsync(d, priors, b_in, hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = rp::fail(RP_ERR_HIP, "rp_mccfr_subgame_belief: upload failed");
+    if (!rc) rc = rp_mccfr_subgame_belief_device(h, n, reinterpret_cast<const rp_mccfr_subgame_prior*>(d), d_wo, reinterpret_cast<float*>(d_wt), d_st);
+    if (!rc && (hipMemcpyAsync(world_of, d_wo, b_wo, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+                hipMemcpyAsync(weights, d_wt, b_wt, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+                (status && hipMemcpyAsync(status, d_st, b_st, hipMemcpyDeviceToHost, h->stream) != hipSuccess)))
+        rc = rp::fail(RP_ERR_HIP, "rp_mccfr_subgame_belief: download failed");
+    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = rp::fail(RP_ERR_HIP, "rp_mccfr_subgame_belief: the launch failed: %s", hipGetErrorString(hipGetLastError()));
+    (void)hipFree(d);
+    return rc;
+}
+
+int rp_mccfr_subgame_solve_device(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries_dev, const rp_mccfr_subgame_args* args,
+                                  rp_mccfr_subgame_result* results_dev, rp_mccfr_subgame_row* rows_dev) {
+    int rc = msub_check_args("rp_mccfr_subgame_solve", args);
+    if (rc) return rc;
+    if (n == 0) return RP_OK;
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_solve: h is NULL");
+    if (!entries_dev || !results_dev) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_solve: entries or results is NULL");
+    if (!rows_dev && args->rows_cap > 0) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_solve: rows is NULL with rows_cap > 0");
+    if ((rc = msub_check_game("rp_mccfr_subgame_solve", h))) return rc;
+    if ((rc = set_device(h))) return rc;
+    return msub_launch_solve(h, n, entries_dev, args, results_dev, rows_dev);
+}
+
+int rp_mccfr_subgame_solve(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries, const rp_mccfr_subgame_args* args,
+                           rp_mccfr_subgame_result* results, rp_mccfr_subgame_row* rows) {
+    int rc = msub_check_args("rp_mccfr_subgame_solve", args);
+    if (rc) return rc;
+    if (n == 0) return RP_OK;
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_solve: h is NULL");
+    if (!entries || !results) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_solve: entries or results is NULL");
+    if (!rows && args->rows_cap > 0) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_solve: rows is NULL with rows_cap > 0");
+    if ((rc = msub_check_game("rp_mccfr_subgame_solve", h))) return rc;
+    if ((rc = set_device(h))) return rc;
+    const size_t b_in = align16(n * sizeof(rp_mccfr_subgame_entry)), b_res = align16(n * sizeof(rp_mccfr_subgame_result)),
+                 b_rows = n * (size_t)args->rows_cap * sizeof(rp_mccfr_subgame_row);
+    uint8_t* d = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), b_in + b_res + b_rows + 16) != hipSuccess) {
+        (void)hipGetLastError();
+        return rp::fail(RP_ERR_CAPACITY, "rp_mccfr_subgame_solve: %zu bytes of staging do not fit", b_in + b_res + b_rows);
+    }
+    rp_mccfr_subgame_result* d_res = reinterpret_cast<rp_mccfr_subgame_result*>(d + b_in);
+    rp_mccfr_subgame_row* d_rows = args->rows_cap ? reinterpret_cast<rp_mccfr_subgame_row*>(d + b_in + b_res) : nullptr;
+    if (hipMemcpyAsync(d, entries, n * sizeof(rp_mccfr_subgame_entry), hipMemcpyHostToDevice, h->stream) != hipSuccess)
+        rc = rp::fail(RP_ERR_HIP, "rp_mccfr_subgame_solve: upload failed");
+    if (!rc) rc = msub_launch_solve(h, n, reinterpret_cast<const rp_mccfr_subgame_entry*>(d), args, d_res, d_rows);
+    if (!rc && (hipMemcpyAsync(results, d_res, n * sizeof(rp_mccfr_subgame_result), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+                (d_rows && hipMemcpyAsync(rows, d_rows, b_rows, hipMemcpyDeviceToHost, h->stream) != hipSuccess)))
+        rc = rp::fail(RP_ERR_HIP, "rp_mccfr_subgame_solve: download failed");
+    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = rp::fail(RP_ERR_HIP, "rp_mccfr_subgame_solve: a launch failed: %s", hipGetErrorString(hipGetLastError()));
+    (void)hipFree(d);
     h->clk.drain();
     return rc;
 }

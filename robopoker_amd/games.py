@@ -59,3 +59,93 @@ class Game:
 
     def player(self, info: int) -> int:
         return self.table.info_player[info]
+
+
+# ---- entries of the safe subgame re-solve (Solver.subgame_belief / subgame_solve) for the built-in Kuhn and Leduc ---------------------
+_CARDS = {"kuhn": 6, "leduc": 6, "leduc_wide": 14}  # Card::ALL = two suits per rank, rank = card // 2
+
+
+def _child(table, state: int, slot: int) -> int:
+    st = table.states[state]
+    if slot >= st.n_children:
+        raise ValueError(f"state {state} has no child slot {slot}")
+    return table.children[st.offset + slot]
+
+
+def deal_state(game: Game, holes) -> int:
+    """the first decision state after the two private cards `holes` = (seat 0's, seat 1's), Card::ALL indices"""
+    c0, c1 = holes
+    if c0 == c1:
+        raise ValueError("the two hole cards must differ")
+    t = game.table
+    return _child(t, _child(t, t.train_root, c0), c1 - (1 if c1 > c0 else 0))
+
+
+def play(game: Game, holes, prefix) -> int:
+    """the state after `prefix` from deal_state(holes): an int is an action slot, ("board", card) the Leduc board deal"""
+    s = deal_state(game, holes)
+    for step in prefix:
+        if isinstance(step, tuple):
+            card = step[1]
+            if card in holes:
+                raise ValueError("the board card is one of the hole cards")
+            step = card - sum(1 for h in holes if h < card)
+        s = _child(game.table, s, step)
+    return s
+
+
+def harvest_order(game: Game, info: int):
+    """the slots of `info` in the derived Ord of the game's edge enum: Kuhn Check < Bet < Call < Fold (kuhn/src/edge.rs:10-16) against
+    the slot order [Fold, Call] of a bet-facing infoset; Leduc Fold < Check < Call < Raise agrees with both of its slot orders"""
+    order = list(range(16))
+    if game.kind == "kuhn" and game.info_name(info).split("|")[1] in ("B", "XB"):
+        order[0], order[1] = 1, 0
+    return order
+
+
+def subgame_entry(game: Game, holes, prefix=(), external=1, reach=False, n_worlds=2, harvest_info=None):
+    """-> (prior, entry) records (mccfr.SUBGAME_PRIOR_DTYPE / SUBGAME_ENTRY_DTYPE, one element each) for the subgame at the state after
+    `prefix`, as the reference's tests build them (kuhn/src/solver.rs:318-517, leduc/src/solver.rs:165-285).  The candidates are
+    Card::ALL minus the other seat's card and the board, in that order, `external` holding each in turn (the encoders' `restrict`), the
+    secret a card's rank.  reach = False is `baseline` (mass 1 per candidate); reach = True conditions on the prefix: each candidate's
+    root is its deal and the path the prefix (Solver::external_reach) — a prefix with a board deal has no shared path and is refused.
+    entry.world_of / weights are left for Solver.subgame_belief's answer (see fill_belief)."""
+    import numpy as np
+
+    from .mccfr import SUBGAME_ENTRY_DTYPE, SUBGAME_PRIOR_DTYPE
+
+    if game.kind not in _CARDS:
+        raise ValueError("subgame_entry knows the built-in card games only")
+    holes, internal = tuple(holes), 1 - external
+    board = [step[1] for step in prefix if isinstance(step, tuple)]
+    cards = [c for c in range(_CARDS[game.kind]) if c != holes[internal] and c not in board]
+    if len(cards) > 16:
+        raise ValueError("more than 16 candidates")
+    with_card = [tuple(c if seat == external else holes[seat] for seat in (0, 1)) for c in cards]
+    prior, entry = np.zeros(1, SUBGAME_PRIOR_DTYPE), np.zeros(1, SUBGAME_ENTRY_DTYPE)
+    p, e = prior[0], entry[0]
+    p["n_prior"], p["internal"], p["mode"], p["n_worlds"] = len(cards), internal, 1 if reach else 0, n_worlds
+    p["secret"][:len(cards)] = [c // 2 for c in cards]
+    if reach:
+        if board:
+            raise ValueError("a reach-conditioned prior needs a prefix without a board deal")
+        p["root_state"][:len(cards)] = [deal_state(game, h) for h in with_card]
+        p["path"][:len(prefix)], p["n_path"] = list(prefix), len(prefix)
+    else:
+        p["root_state"][:len(cards)] = [play(game, h, prefix) for h in with_card]
+    e["observed"], e["external"], e["n_candidates"], e["n_worlds"] = play(game, holes, prefix), external, len(cards), n_worlds
+    e["candidate"][:len(cards)] = [play(game, h, prefix) for h in with_card]
+    e["secret"][:len(cards)] = [c // 2 for c in cards]
+    e["world_of"][:] = _lib.RP_WORLD_NONE
+    e["harvest_info"] = _lib.RP_NO_INFO if harvest_info is None else harvest_info
+    st = game.table.states[int(e["observed"])]
+    shown = harvest_info if harvest_info is not None else (st.info if st.turn < 2 else None)
+    e["harvest_order"][:] = harvest_order(game, shown) if shown is not None else list(range(16))
+    return prior, entry
+
+
+def fill_belief(entries, belief):
+    """copies Solver.subgame_belief's answer (or the model's) into the entries, element by element"""
+    entries["world_of"][...] = belief["world_of"]
+    entries["weights"][...] = belief["weights"]
+    return entries

@@ -15,6 +15,17 @@ from . import _lib
 from .games import Game
 
 ENC_DTYPE = np.dtype([("weight", "<f4"), ("regret", "<f4"), ("payoff", "<f4"), ("visits", "<u4")])
+# the safe subgame re-solve's records (include/rp_mi355x.h: rp_mccfr_subgame_prior 104, _entry 140, _result 192, _row 264 bytes)
+SUBGAME_PRIOR_DTYPE = np.dtype([("root_state", "<u4", 16), ("secret", "u1", 16), ("path", "u1", 16), ("n_prior", "u1"), ("n_path", "u1"),
+                                ("internal", "u1"), ("mode", "u1"), ("n_worlds", "u1"), ("pad", "u1", 3)])
+SUBGAME_ENTRY_DTYPE = np.dtype([("observed", "<u4"), ("harvest_info", "<u4"), ("candidate", "<u4", 16), ("secret", "u1", 16),
+                                ("world_of", "u1", 16), ("harvest_order", "u1", 16), ("weights", "<f4", 4), ("external", "u1"),
+                                ("n_candidates", "u1"), ("n_worlds", "u1"), ("pad", "u1")])
+SUBGAME_RESULT_DTYPE = np.dtype([("info", "<u4"), ("n_actions", "u1"), ("status", "u1"), ("pad", "u1", 2), ("refined", "<f4", 16),
+                                 ("visits", "<u4", 16), ("regret", "<f4"), ("sum_regret", "<f4"), ("iterations", "<u4"), ("n_rows", "<u4"),
+                                 ("nodes", "<u8"), ("infosets", "<u8"), ("drawn", "<u4", 4), ("fallbacks", "<u4"), ("pad2", "<u4")])
+SUBGAME_ROW_DTYPE = np.dtype([("world", "u1"), ("n_actions", "u1"), ("pad", "u1", 2), ("info", "<u4"), ("enc", ENC_DTYPE, 16)])
+assert (SUBGAME_PRIOR_DTYPE.itemsize, SUBGAME_ENTRY_DTYPE.itemsize, SUBGAME_RESULT_DTYPE.itemsize, SUBGAME_ROW_DTYPE.itemsize) == (104, 140, 192, 264)
 
 
 def default_hyper() -> _lib.Hyper:
@@ -156,6 +167,43 @@ class Solver:
         out = C.c_float()
         _lib.check(self._lib.rp_mccfr_sum_regret(self._h, C.byref(out)))
         return out.value
+
+    # ---- the safe subgame re-solve with this solver's tables as the blueprint (csrc/mccfr_subgame.hpp); read-only on the solver -------
+    def subgame_args(self, iterations=1, prior=float(1 << 14), seed=0, first_id=0, rows_cap=0) -> _lib.MccfrSubgameArgs:
+        a = _lib.MccfrSubgameArgs()
+        self._lib.rp_mccfr_subgame_args_default(C.byref(a))
+        a.iterations, a.prior, a.seed, a.first_id, a.rows_cap = iterations, prior, seed, first_id, rows_cap
+        return a
+
+    def subgame_belief(self, priors: np.ndarray) -> dict:
+        """``Posterior`` -> ``partition::<W>`` per entry of ``priors`` (SUBGAME_PRIOR_DTYPE; games.subgame_entry builds them):
+        {"world_of" [n, 16] u8, "weights" [n, 4] f32, "status" [n] u8}"""
+        buf = np.ascontiguousarray(priors, dtype=SUBGAME_PRIOR_DTYPE).reshape(-1)
+        n = buf.size
+        out = {"world_of": np.zeros((n, 16), np.uint8), "weights": np.zeros((n, 4), np.float32), "status": np.zeros(n, np.uint8)}
+        _lib.check(self._lib.rp_mccfr_subgame_belief(self._h, n, buf.ctypes.data, out["world_of"].ctypes.data, out["weights"].ctypes.data,
+                                                     out["status"].ctypes.data))
+        return out
+
+    def subgame_belief_device(self, n: int, priors_ptr: int, world_of_ptr: int, weights_ptr: int, status_ptr: int = 0):
+        """the same, every array in device memory; queued on the solver's stream, no host synchronisation"""
+        _lib.check(self._lib.rp_mccfr_subgame_belief_device(self._h, n, priors_ptr, world_of_ptr, weights_ptr, status_ptr or None))
+
+    def subgame_solve(self, entries: np.ndarray, iterations=1, prior=float(1 << 14), seed=0, first_id=0, rows_cap=0):
+        """``SubGameSolver`` (origin = None) x ``iterations`` and its harvest, one solve per entry (SUBGAME_ENTRY_DTYPE):
+        (results [n] SUBGAME_RESULT_DTYPE, rows [n, rows_cap] SUBGAME_ROW_DTYPE)"""
+        buf = np.ascontiguousarray(entries, dtype=SUBGAME_ENTRY_DTYPE).reshape(-1)
+        n = buf.size
+        results, rows = np.zeros(n, SUBGAME_RESULT_DTYPE), np.zeros((n, rows_cap), SUBGAME_ROW_DTYPE)
+        a = self.subgame_args(iterations, prior, seed, first_id, rows_cap)
+        _lib.check(self._lib.rp_mccfr_subgame_solve(self._h, n, buf.ctypes.data, C.byref(a), results.ctypes.data,
+                                                    rows.ctypes.data if rows_cap else None))
+        return results, rows
+
+    def subgame_solve_device(self, n: int, entries_ptr: int, results_ptr: int, rows_ptr: int = 0, **args):
+        """the same, every array in device memory (``args`` as subgame_args); queued on the solver's stream, no host synchronisation"""
+        a = self.subgame_args(**args)
+        _lib.check(self._lib.rp_mccfr_subgame_solve_device(self._h, n, entries_ptr, C.byref(a), results_ptr, rows_ptr or None))
 
     # ---- knobs ----------------------------------------------------------------------------------
     def set_batch(self, batch: int):

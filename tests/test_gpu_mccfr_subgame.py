@@ -1,0 +1,328 @@
+"""rp_mccfr_subgame_belief / rp_mccfr_subgame_solve on the device (include/rp_mi355x.h, robopoker_amd/csrc/mccfr_subgame.hpp):
+bit-exact parity with tests/mccfr_subgame_model.py at the smallest shapes that can go wrong, the invariances (device against device),
+the malformed entries, and the reference's own subgame known answers (kuhn/src/solver.rs:294-517, leduc/src/solver.rs:165-285)."""
+import os
+import time
+
+import numpy as np
+import pytest
+import torch  # before the library's first HIP call: one HIP runtime per process
+
+import game_tables
+import mccfr_subgame_cases as K
+import mccfr_subgame_model as M
+from robopoker_amd import Game, _lib, games
+from robopoker_amd.mccfr import SUBGAME_ENTRY_DTYPE, SUBGAME_PRIOR_DTYPE, SUBGAME_RESULT_DTYPE, SUBGAME_ROW_DTYPE, Solver
+
+pytestmark = pytest.mark.gpu
+ROWS_CAP = 24
+SEED, FIRST_ID = 11, 5
+
+
+def make_game(name):
+    return game_tables.game(name) if name == "chance16_mid" else Game(name)
+
+
+class Bench:
+    """one game, one blueprint: the solver, the model's view of both and the cases"""
+
+    def __init__(self, name, blueprint):
+        self.game = make_game(name)
+        self.solver = Solver(self.game, "floored", "linear", "external", batch=1, seed=3)
+        self.table = M.Table(self.game.table)
+        if blueprint == "trained":
+            self.solver.solve(2000)
+        elif blueprint == "imported":
+            self.solver.load_rows(K.corner_rows(self.table), (1 << 24) + 3)
+        self.bp = M.Blueprint(self.table, self.solver.export())
+        self.cases = K.custom_cases(self.table, self.bp) if name == "chance16_mid" else K.builtin_cases(self.game, self.table, self.bp)
+        self.entries = K.stack(self.cases)
+
+
+_benches = {}
+
+
+def bench(name, blueprint):
+    if (name, blueprint) not in _benches:
+        _benches[name, blueprint] = Bench(name, blueprint)
+    return _benches[name, blueprint]
+
+
+def check_against_model(b, entries, iterations, labels=None, rows_cap=ROWS_CAP):
+    results, rows = b.solver.subgame_solve(entries, iterations=iterations, seed=SEED, first_id=FIRST_ID, rows_cap=rows_cap)
+    for i, e in enumerate(entries):
+        want = M.solve(b.table, b.bp, e, index=i, iterations=iterations, seed=SEED, first_id=FIRST_ID)
+        try:
+            M.compare(results[i], rows[i], want, rows_cap)
+        except AssertionError as err:
+            raise AssertionError(f"solve {i} ({labels[i] if labels else ''}), {iterations} iterations: {err}") from err
+    return results, rows
+
+
+@pytest.mark.parametrize("iterations", K.ITERATIONS)
+@pytest.mark.parametrize("name,blueprint", [("kuhn", "fresh"), ("kuhn", "trained"), ("kuhn", "imported"), ("leduc", "fresh"), ("leduc", "trained"),
+                                            ("leduc", "imported"), ("chance16_mid", "trained"), ("chance16_mid", "imported")])
+def test_solve_equals_the_model(gpu, name, blueprint, iterations):
+    b = bench(name, blueprint)
+    results, _ = check_against_model(b, b.entries, iterations, [label for label, _ in b.cases])
+    assert not results["status"].any()
+    labels = [label for label, _ in b.cases]
+    if name != "chance16_mid" and iterations == 64:  # the cases do what they are there for
+        assert results["fallbacks"][labels.index("root, a world without a member")] > 0
+        assert results["fallbacks"][labels.index("root, no candidates")] == 64
+        assert all(r["n_actions"] == 0 and r["n_rows"] == 0 for r, l in zip(results, labels) if "observed" in l)
+
+
+def test_wide_leduc_once(gpu):
+    b = bench("leduc_wide", "trained")
+    check_against_model(b, b.entries[:8], 7)
+
+
+def test_belief_equals_the_model(gpu):
+    for name in ("kuhn", "leduc"):
+        b = bench(name, "trained")
+        priors = []
+        for _, holes, prefix, external, reach in (K.KUHN if name == "kuhn" else K.LEDUC):
+            for W in (1, 2, 4):
+                p, _ = games.subgame_entry(b.game, holes, prefix, external, reach, n_worlds=W)
+                priors.append(p[0])
+        bad = [priors[9].copy() for _ in range(6)]  # the reach-conditioned prior (after check, bet | raise) at W = 1, one field broken each
+        bad[0]["path"][1], bad[1]["root_state"][2], bad[2]["secret"][0], bad[3]["n_worlds"], bad[4]["mode"], bad[5]["path"][0] = 2, 1 << 30, 16, 5, 2, 200
+        nothing = priors[1].copy()  # no candidate at all: total <= 0, no entry, uniform weights over W = 2
+        nothing["n_prior"] = 0
+        priors = np.array(priors + [nothing] + bad, SUBGAME_PRIOR_DTYPE)
+        got = b.solver.subgame_belief(priors)
+        for i, p in enumerate(priors):
+            want = M.belief(b.table, b.bp, p)
+            assert got["status"][i] == want["status"], (name, i)
+            assert np.array_equal(got["world_of"][i], want["world_of"]), (name, i, got["world_of"][i], want["world_of"])
+            assert np.array_equal(got["weights"][i].view(np.uint32), want["weights"].view(np.uint32)), (name, i, got["weights"][i], want["weights"])
+        assert list(got["status"][-6:]) == [M.PATH, M.STATE, M.SECRET, M.WORLDS, M.MODE, M.PATH]
+        assert got["status"][-7] == M.OK and (got["world_of"][-7] == _lib.RP_WORLD_NONE).all() and list(got["weights"][-7]) == [0.5, 0.5, 0, 0]
+
+
+def mixed70(b):
+    """70 solves: the cases in turn, every seventh one malformed"""
+    bad = K.malformed(b.entries[1], b.table)  # the root at W = 2
+    entries, statuses = [], []
+    for i in range(70):
+        if i % 7 == 3:
+            status, e = bad[(i // 7) % len(bad)]
+        else:
+            status, e = M.OK, b.entries[i % len(b.entries)]
+        entries.append(e)
+        statuses.append(status)
+    return np.array(entries, SUBGAME_ENTRY_DTYPE), statuses
+
+
+def test_batch_of_70_with_malformed_entries(gpu):
+    b = bench("leduc", "trained")
+    entries, statuses = mixed70(b)
+    results, _ = check_against_model(b, entries, 7)
+    assert list(results["status"]) == statuses
+
+
+def test_every_malformed_entry_gets_its_status(gpu):
+    b = bench("kuhn", "trained")
+    bad = K.malformed(b.entries[1], b.table)  # the root at W = 2
+    entries = np.array([b.entries[0]] + [e for _, e in bad] + [b.entries[1]], SUBGAME_ENTRY_DTYPE)
+    results, _ = check_against_model(b, entries, 7)
+    assert list(results["status"]) == [M.OK] + [s for s, _ in bad] + [M.OK]
+    big = game_tables.TableGame(2, [("act", 0, 8), ("act", 0, 8)])  # 1 + 8 + 64 nodes under walker 0: one tree too large
+    solver = Solver(big, batch=1)
+    entry = np.zeros(1, SUBGAME_ENTRY_DTYPE)
+    entry["n_worlds"], entry["weights"], entry["harvest_info"], entry["harvest_order"] = 1, (1, 0, 0, 0), _lib.RP_NO_INFO, np.arange(16)
+    entry["world_of"] = _lib.RP_WORLD_NONE
+    results, _ = solver.subgame_solve(entry, iterations=3)
+    table = M.Table(big.table)
+    want = M.solve(table, M.Blueprint(table, solver.export()), entry[0], iterations=3)
+    assert results["status"][0] == want["status"] == M.TREE
+
+
+def test_more_than_1024_local_rows_is_a_status(gpu):
+    """RP_MSUB_ROWS.  A 15-way decision of seat 1, a 14-way one of seat 0 and a single action of each give 1 + 15 + 210 + 210 infosets,
+    1 744 (world, info) pairs under four equally likely worlds, in sampled trees of at most 61 nodes; the 1 025th row ends the solve.
+    A shorter solve of the same entry (969 rows) is answered."""
+    wide = game_tables.TableGame(2, [("act", 1, 15), ("act", 0, 14), ("act", 1, 1), ("act", 0, 1)])
+    solver = Solver(wide, batch=1)
+    table = M.Table(wide.table)
+    bp = M.Blueprint(table, solver.export())
+    entry = np.zeros(1, SUBGAME_ENTRY_DTYPE)
+    entry["n_worlds"], entry["weights"], entry["harvest_info"], entry["harvest_order"] = 4, (0.25, 0.25, 0.25, 0.25), _lib.RP_NO_INFO, np.arange(16)
+    entry["world_of"] = _lib.RP_WORLD_NONE
+    assert 4 * table.n_infos > _lib.RP_MCCFR_SUBGAME_MAX_ROWS
+    for iterations, status in ((100, M.OK), (300, M.ROWS)):
+        results, rows = solver.subgame_solve(entry, iterations=iterations, seed=SEED, rows_cap=4)
+        want = M.solve(table, bp, entry[0], iterations=iterations, seed=SEED)
+        assert want["status"] == status
+        M.compare(results[0], rows[0], want, 4)
+
+
+def test_rows_cap_zero_and_below_n_rows(gpu):
+    b = bench("leduc", "trained")
+    full, _ = check_against_model(b, b.entries[:4], 64)
+    assert full["n_rows"].min() > 2
+    for cap in (0, 2):
+        results, rows = check_against_model(b, b.entries[:4], 64, rows_cap=cap)
+        assert results.tobytes() == full.tobytes() and rows.shape == (4, cap)
+
+
+# ---- invariances: device against device ----
+def solve(b, entries, iterations, first_id=FIRST_ID):
+    return b.solver.subgame_solve(entries, iterations=iterations, seed=SEED, first_id=first_id, rows_cap=ROWS_CAP)
+
+
+def test_a_short_solve_is_the_start_of_a_long_one(gpu):
+    b = bench("leduc", "trained")
+    long = []
+    M_long = M.solve(b.table, b.bp, b.entries[0], index=0, iterations=200, seed=SEED, first_id=FIRST_ID, keep=long)
+    short, _ = solve(b, b.entries[:1], 64)
+    # the model's 200-iteration solve, stopped after 64: the device's 64-iteration answer
+    stopped = M.Solve(b.table, b.bp, b.entries[0], 0, seed=SEED, first_id=FIRST_ID)
+    for _ in range(64):
+        stopped.step()
+    assert [[n.state for n in t] for t in stopped.trees] == [[n.state for n in t] for t in long[0].trees[:64]]
+    M.compare(short[0], np.zeros(0, SUBGAME_ROW_DTYPE), stopped.harvest(), 0)
+    got, _ = solve(b, b.entries[:1], 200)
+    M.compare(got[0], np.zeros(0, SUBGAME_ROW_DTYPE), M_long, 0)
+
+
+def test_split_and_reversed_batches(gpu):
+    b = bench("leduc", "trained")
+    entries, _ = mixed70(b)
+    whole, whole_rows = solve(b, entries, 7)
+    head, head_rows = solve(b, entries[:1], 7)
+    tail, tail_rows = solve(b, entries[1:], 7, first_id=FIRST_ID + 1)
+    assert np.concatenate([head, tail]).tobytes() == whole.tobytes()
+    assert np.concatenate([head_rows, tail_rows]).tobytes() == whole_rows.tobytes()
+    # the batch reversed, in one call.  Ids are positional (id = first_id + position), so solve j of the reversed batch is the entry
+    # entries[69 - j] under id FIRST_ID + j: it must answer what that entry answers alone under that id, whatever surrounds it
+    flipped = entries[::-1].copy()
+    back, back_rows = solve(b, flipped, 7)
+    for j in range(70):
+        one, one_rows = solve(b, flipped[j:j + 1], 7, first_id=FIRST_ID + j)
+        assert one.tobytes() == back[j:j + 1].tobytes() and one_rows.tobytes() == back_rows[j:j + 1].tobytes(), j
+    again, again_rows = solve(b, entries, 7)
+    assert again.tobytes() == whole.tobytes() and again_rows.tobytes() == whole_rows.tobytes()
+
+
+def test_the_answer_does_not_depend_on_the_segment_length(gpu):
+    """a 200-iteration solve in launches of 5 and of 64 iterations against the default (one launch); RP_MCCFR_SUBGAME_SEGMENT is read by
+    every call"""
+    b = bench("leduc", "trained")
+    entries, _ = mixed70(b)
+    outs = []
+    saved = os.environ.pop("RP_MCCFR_SUBGAME_SEGMENT", None)
+    try:
+        for segment in (None, "5", "64"):
+            if segment:
+                os.environ["RP_MCCFR_SUBGAME_SEGMENT"] = segment
+            results, rows = solve(b, entries[:12], 200)
+            outs.append(results.tobytes() + rows.tobytes())
+        os.environ["RP_MCCFR_SUBGAME_SEGMENT"] = "0"
+        with pytest.raises(_lib.RpError):
+            solve(b, entries[:1], 2)
+    finally:
+        os.environ.pop("RP_MCCFR_SUBGAME_SEGMENT", None)
+        if saved is not None:
+            os.environ["RP_MCCFR_SUBGAME_SEGMENT"] = saved
+    assert (results["status"][[0, 1, 2]] == 0).all() and results["iterations"][0] == 200
+    assert outs[0] == outs[1] == outs[2]
+
+
+def test_host_form_equals_device_form_and_the_blueprint_is_untouched(gpu):
+    b = bench("kuhn", "trained")
+    before = (b.solver.export().tobytes(), b.solver.epoch, b.solver.counters())
+    entries, _ = mixed70(b)
+    priors = np.array([games.subgame_entry(b.game, (1, 4), (K.CHECK, K.BET), 1, True)[0][0]] * 3, SUBGAME_PRIOR_DTYPE)
+    host, host_rows = solve(b, entries, 7)
+    host_belief = b.solver.subgame_belief(priors)
+    dev = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).cuda()
+    d_entries, d_priors = dev(entries), dev(priors)
+    d_results = torch.zeros(host.nbytes, dtype=torch.uint8, device="cuda")
+    d_rows = torch.zeros(host_rows.nbytes, dtype=torch.uint8, device="cuda")
+    d_world, d_weights, d_status = (torch.zeros(n, dtype=torch.uint8, device="cuda") for n in (3 * 16, 3 * 16, 3))
+    torch.cuda.synchronize()
+    b.solver.subgame_belief_device(3, d_priors.data_ptr(), d_world.data_ptr(), d_weights.data_ptr(), d_status.data_ptr())
+    b.solver.subgame_solve_device(70, d_entries.data_ptr(), d_results.data_ptr(), d_rows.data_ptr(), iterations=7, seed=SEED, first_id=FIRST_ID,
+                                  rows_cap=ROWS_CAP)
+    b.solver.sync()
+    assert d_results.cpu().numpy().tobytes() == host.tobytes() and d_rows.cpu().numpy().tobytes() == host_rows.tobytes()
+    assert d_world.cpu().numpy().tobytes() == host_belief["world_of"].tobytes()
+    assert d_weights.cpu().numpy().tobytes() == host_belief["weights"].tobytes() and not d_status.cpu().numpy().any()
+    assert (b.solver.export().tobytes(), b.solver.epoch, b.solver.counters()) == before
+
+
+# ---- known answers: the reference's own subgame tests ----
+N18, N16, WORLDS = 1 << 18, 1 << 16, 2
+DEALS = [(c0, c1) for c0 in range(6) for c1 in range(6) if c0 != c1]  # all 30 ordered deals
+
+
+@pytest.fixture(scope="module")
+def blueprints(gpu):
+    """FlooredRegret, LinearWeight, ExternalSampling, rp_mccfr_solve(h, 1 << 18) at batch 1, once per module for both games (the
+    reference's `Kuhn::default().solve(N18)`).  The fixture prints the seconds each took (run with -s);
+    scripts/mccfr_subgame_rate.py records the per-step time of the same batch-1 ORDERED step."""
+    out = {}
+    for name in ("kuhn", "leduc"):
+        game = Game(name)
+        t0 = time.time()
+        solver = Solver(game, "floored", "linear", "external", batch=1, seed=0).solve(N18)
+        table = M.Table(game.table)
+        out[name] = (game, solver, table, M.Blueprint(table, solver.export()))
+        print(f"{name}: the 2^18-step batch-1 blueprint took {time.time() - t0:.1f} s")
+    return out
+
+
+def known_answer_solves(bp, prefix, external, reach):
+    game, solver, table, blue = bp
+    priors, entries = zip(*(games.subgame_entry(game, holes, prefix, external, reach, n_worlds=WORLDS) for holes in DEALS))
+    priors, entries = np.concatenate(priors), np.concatenate(entries)
+    belief = solver.subgame_belief(priors)
+    assert not belief["status"].any()
+    games.fill_belief(entries, belief)
+    t0 = time.time()
+    results, rows = solver.subgame_solve(entries, iterations=N16, seed=1, rows_cap=32)
+    print(f"{game.kind} {prefix} external {external} reach {reach}: 30 solves of 2^16 iterations took {time.time() - t0:.2f} s; "
+          f"sum_regret max {results['sum_regret'].max():.6f}")
+    assert not results["status"].any() and (results["n_rows"] <= 32).all()
+    return game, table, blue, results, rows
+
+
+def kuhn_call(game, table, blue, rows_of_solve, name):
+    rows = [(int(r["world"]), int(r["n_actions"]), int(r["info"]), r["enc"]) for r in rows_of_solve if r["n_actions"]]
+    return M.averaged_policy(table, blue, rows, game.info_id(name), WORLDS)[K.CALL]
+
+
+@pytest.mark.parametrize("prefix,external", [((), 1), ((K.CHECK,), 0), ((K.BET,), 0)])
+def test_known_answers_kuhn(blueprints, prefix, external):
+    """kuhn/src/solver.rs:294-383: the world-averaged averaged_policy of K|B Call and K|XB Call > 0.90, for every one of the 30 deals"""
+    game, table, blue, results, rows = known_answer_solves(blueprints["kuhn"], prefix, external, False)
+    for i, holes in enumerate(DEALS):
+        for name in ("K|B", "K|XB"):
+            p = kuhn_call(game, table, blue, rows[i], name)
+            assert p > 0.90, f"deal {holes}: {name} calls with {p:.4f}"
+
+
+def test_known_answers_kuhn_reach_conditioned(blueprints):
+    """kuhn/src/solver.rs:462-517: after check-bet, sum_regret < 0.01 and K|XB Call > 0.90"""
+    game, table, blue, results, rows = known_answer_solves(blueprints["kuhn"], (K.CHECK, K.BET), 1, True)
+    for i, holes in enumerate(DEALS):
+        assert results["sum_regret"][i] < 0.01, f"deal {holes}: sum_regret {results['sum_regret'][i]:.6f}"
+        p = kuhn_call(game, table, blue, rows[i], "K|XB")
+        assert p > 0.90, f"deal {holes}: K|XB calls with {p:.4f}"
+
+
+@pytest.mark.parametrize("prefix,external", [((), 1), ((K.CHECK,), 0), ((K.BET,), 0)])
+def test_known_answers_leduc(blueprints, prefix, external):
+    """leduc/src/solver.rs:165-231: sum_regret < 0.5"""
+    _, _, _, results, _ = known_answer_solves(blueprints["leduc"], prefix, external, False)
+    for i, holes in enumerate(DEALS):
+        assert results["sum_regret"][i] < 0.5, f"deal {holes}: sum_regret {results['sum_regret'][i]:.4f}"
+
+
+def test_known_answers_leduc_reach_conditioned(blueprints):
+    """leduc/src/solver.rs:252-285: after check-raise, sum_regret < 0.03"""
+    _, _, _, results, _ = known_answer_solves(blueprints["leduc"], (K.CHECK, K.BET), 1, True)
+    for i, holes in enumerate(DEALS):
+        assert results["sum_regret"][i] < 0.03, f"deal {holes}: sum_regret {results['sum_regret'][i]:.6f}"
