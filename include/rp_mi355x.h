@@ -1791,6 +1791,11 @@ RP_API int rp_sinkhorn_divergence(uint32_t bins, uint64_t pairs, const uint32_t*
 RP_API int rp_sinkhorn_cost(uint32_t bins, uint64_t pairs, const uint32_t* mu, const uint32_t* nu,
                             const float* tri_metric, const rp_sinkhorn_hp* hp, int device, float* out,
                             uint32_t* iterations);
+/* the same with mu, nu, out and iterations (may be NULL) in DEVICE memory, used in place: the same kernels, the same bits.
+ * tri_metric and hp stay host arguments.  Returns after the device finished. */
+RP_API int rp_sinkhorn_cost_device(uint32_t bins, uint64_t pairs, const uint32_t* mu_dev, const uint32_t* nu_dev,
+                                   const float* tri_metric, const rp_sinkhorn_hp* hp, int device, float* out_dev,
+                                   uint32_t* iterations_dev);
 /* impl Coupling for Sinkhorn (monge/src/coupling.rs:23-51; lloyd/src/sinkhorn.rs:194-218): minimize() one pair, then
  * flow(x, y) = coupling(x, y) * raw_distance(x, y) with coupling = exp(lhs(x) + rhs(y) - C/T) (sinkhorn.rs:114-116).
  * flow[bins*bins] row-major over (x, y), 0 outside supp(mu) x supp(nu); coupling (same shape) may be NULL.  The x-major
@@ -1852,6 +1857,113 @@ RP_API int rp_lookup_project(rp_lookup* h, uint64_t n, const int64_t* obs_dev, u
 RP_API int rp_deuce_kernel_ms(double* ms);
 
 /* =================================================================================================
+ * Abstraction atlas: the reference's derived tables over one street's Lookup, and the batched queries of its abstraction
+ * explorer, answered from device memory.
+ *   crates/daybook/src/schema.rs:78-173 — the `abstraction` table (population, equity via get_equity);
+ *   crates/lloyd/src/lookup.rs:86-119   — isomorphism.position = ROW_NUMBER() OVER (PARTITION BY abs ORDER BY obs) - 1;
+ *   crates/portal/src/topology/api.rs   — TopologyAPI (obs_to_abs, *_equity, *_population, abs_distance, *_histogram,
+ *                                         exp_wrt_*, *_nearby, *_similar, nbr_*_wrt_abs, knn_ / kfn_ / kgn_wrt_abs).
+ * One handle per street.  Derived once at create, on the device:
+ *   population[k]  rows with abs == k
+ *   position[i]    rows j with abs[j] == abs[i] and obs[j] < obs[i], compared as signed 64-bit (the BIGINT order; the table's
+ *                  own IsomorphismIterator order is NOT that order)
+ *   offset[K + 1], members[n]   members[offset[k] + p] = the row of bucket k at position p: the (abs, position) index
+ *   equity[k]      river: (float)k / 100.0f.  Elsewhere get_equity (schema.rs:100-107) in f32, one rounding per operation:
+ *                  over the bucket's transition rows (bins with a count, dx = (float)count / (float)weight), the left fold
+ *                  from 0.0f of dx * next.equity[bin] divided by the left fold from 0.0f of dx; 0.0f for a bucket without
+ *                  rows or with a zero divisor.
+ * Three things SQL leaves open and this library fixes:
+ *   fold order   PostgreSQL's SUM(REAL) folds in REAL in an unspecified row order; here the order is the one
+ *                rp_artifact_write_transitions writes: dx descending, stable over the ascending bin.
+ *   ties         neighbours at equal distance go to the smaller bucket index, nearest and farthest alike.
+ *   draws        a RANDOM() is a caller-supplied uint64 `draw`: u = (double)(draw >> 11) * 2^-53,
+ *                i = (uint32)floor(u * (double)population).  The library draws nothing itself.
+ * The reference's *_similar predicate (position < LEAST(6, population) AND position >= FLOOR(RANDOM() *
+ * GREATEST(population - 6, 1))) is a caller's choice of `start` for rp_atlas_members; it is not built in.
+ * Every query is batched and fills a per-answer status; the plain forms take host arrays, the _device forms device arrays
+ * the caller has finished writing, and return after the device finished.
+ * ================================================================================================= */
+typedef struct rp_atlas rp_atlas;
+typedef struct rp_atlas_sample {
+    int64_t obs;         /* the table's (canonical) observation; 0 where there is none */
+    float equity;        /* equity[k] of the record's bucket */
+    float density;       /* (float)population / (float)n_observations(street) from describe (api.rs:266), / n_isomorphisms(street)
+                            from pick and neighbours (api.rs:299) */
+    float distance;      /* tri[Pair::merge(abs, wrt)], 0 without a wrt */
+    uint32_t position;
+    uint32_t population;
+    int16_t abs;         /* street << 8 | k */
+    uint8_t reserved[2];
+} rp_atlas_sample; /* 32 bytes */
+#if defined(__cplusplus)
+static_assert(sizeof(rp_atlas_sample) == 32, "rp_atlas_sample is 32 bytes");
+#else
+_Static_assert(sizeof(rp_atlas_sample) == 32, "rp_atlas_sample is 32 bytes");
+#endif
+typedef enum rp_atlas_status {
+    RP_ATLAS_OK = 0,
+    RP_ATLAS_MISS = 1,  /* the observation is not one of the street, or not in the table: a zero record */
+    RP_ATLAS_SAME = 2,  /* describe: wrt is the observation's own bucket, distance 0 */
+    RP_ATLAS_EMPTY = 3, /* the bucket has no member (pick, neighbours with draws) or no transition row (obs_equity, histograms) */
+    RP_ATLAS_RANGE = 4  /* a bucket index >= K: a zero record */
+} rp_atlas_status;
+typedef enum rp_atlas_hist_kind { RP_ATLAS_HIST_ABS = 0, RP_ATLAS_HIST_OBS = 1 } rp_atlas_hist_kind;
+#define RP_ATLAS_MAX_K 256u
+#define RP_ATLAS_MAX_ROWS (1ull << 27) /* sortscan's row indices are 27 bits; the river's 123 156 254 fit */
+#define RP_ATLAS_MAX_NEIGHBORS 16u
+#define RP_ATLAS_MAX_WINDOW 16u
+/* (obs_dev, abs_dev): what rp_lookup_create takes, under the same check (a prefix of a street's list is a valid table); K <= 256 and
+ * every abs < K, else RP_ERR_INVALID; n > 2^27: RP_ERR_UNSUPPORTED.  future_counts [K][bins] / future_weight [K] (host) are what
+ * rp_kmeans_centroids returns, tri [K (K - 1) / 2] (host) what rp_kmeans_metric returns; bins must equal next's K, next must be the
+ * atlas of street + 1 on the same device (it is read at create only).  River: future_*, tri and next are NULL, bins 0; row_equity_dev
+ * [n] may be rp_river_equity's equities (the isomorphism.equity column), it is copied.  Elsewhere future_* and next are required;
+ * tri may be NULL (neighbours, distance and describe-with-wrt then answer RP_ERR_UNSUPPORTED). */
+RP_API int rp_atlas_create(int device, int street, uint64_t n, const int64_t* obs_dev, const uint8_t* abs_dev, uint32_t K,
+                           const uint32_t* future_counts, const uint64_t* future_weight, uint32_t bins, const float* tri,
+                           const float* row_equity_dev, const rp_atlas* next, rp_atlas** out);
+RP_API int rp_atlas_destroy(rp_atlas* h);
+/* n, K, bins, street of the handle; any output may be NULL */
+RP_API int rp_atlas_shape(const rp_atlas* h, uint64_t* n, uint32_t* K, uint32_t* bins, int* street);
+/* the derived tables, copied to host OR device memory (any may be NULL): population[K], offset[K + 1], equity[K],
+ * position[n], members[n] */
+RP_API int rp_atlas_tables(rp_atlas* h, uint32_t* population, uint32_t* offset, float* equity, uint32_t* position, uint32_t* members);
+/* device time of this handle's create: the (abs, obs) sort, and everything else (histogram, scan, positions, equity) */
+RP_API int rp_atlas_create_ms(const rp_atlas* h, double* sort_ms, double* rest_ms);
+/* obs_to_abs, obs_population, exp_wrt_obs, nbr_obs_wrt_abs, kgn_wrt_abs: the record of each observation (any suit labelling);
+ * wrt u8[n] or NULL: distance = tri[Pair(abs, wrt)], status SAME and distance 0 when wrt is the observation's own bucket */
+RP_API int rp_atlas_describe(rp_atlas* h, uint64_t n, const int64_t* obs, const uint8_t* wrt, rp_atlas_sample* out, uint8_t* status);
+RP_API int rp_atlas_describe_device(rp_atlas* h, uint64_t n, const int64_t* obs, const uint8_t* wrt, rp_atlas_sample* out, uint8_t* status);
+/* obs_equity (api.rs:91-115).  River: the row's row_equity (RP_ERR_UNSUPPORTED if none was given).  Elsewhere the un-normalised
+ * left fold of dx * next.equity over the rows of the observation's bucket (no division), 0 with status EMPTY if it has none */
+RP_API int rp_atlas_obs_equity(rp_atlas* h, uint64_t n, const int64_t* obs, float* out, uint8_t* status);
+RP_API int rp_atlas_obs_equity_device(rp_atlas* h, uint64_t n, const int64_t* obs, float* out, uint8_t* status);
+/* exp_wrt_abs, replace_obs, nbr_abs_wrt_abs, hst_wrt_abs_on_river: the member of bucket abs[q] at the position draw[q] selects;
+ * population 0: status EMPTY (abs, equity and zeros) */
+RP_API int rp_atlas_pick(rp_atlas* h, uint64_t n, const uint8_t* abs, const uint64_t* draw, rp_atlas_sample* out, uint8_t* status);
+RP_API int rp_atlas_pick_device(rp_atlas* h, uint64_t n, const uint8_t* abs, const uint64_t* draw, rp_atlas_sample* out, uint8_t* status);
+/* abs_nearby, knn_wrt_abs, kfn_wrt_abs: the k <= min(K - 1, 16) other buckets of the street by tri ascending (farthest != 0:
+ * descending), ties to the smaller index; out / status [n][k].  draws [n][k] or NULL: slot j comes with the member draws[q][j]
+ * selects; an empty neighbour keeps its slot with status EMPTY (the reference drops it after the LIMIT).  Without draws obs and
+ * position are 0. */
+RP_API int rp_atlas_neighbors(rp_atlas* h, uint64_t n, const uint8_t* wrt, uint32_t k, int farthest, const uint64_t* draws,
+                              rp_atlas_sample* out, uint8_t* status);
+RP_API int rp_atlas_neighbors_device(rp_atlas* h, uint64_t n, const uint8_t* wrt, uint32_t k, int farthest, const uint64_t* draws,
+                                     rp_atlas_sample* out, uint8_t* status);
+/* abs_distance: 0 for a == b, else tri[Pair::merge(a, b)]; NaN where an index is >= K */
+RP_API int rp_atlas_distance(rp_atlas* h, uint64_t n, const uint8_t* a, const uint8_t* b, float* out);
+RP_API int rp_atlas_distance_device(rp_atlas* h, uint64_t n, const uint8_t* a, const uint8_t* b, float* out);
+/* abs_histogram (kind ABS, ids u8[n]): count = (uint32)(dx * 1000.0f), truncated (api.rs:207); obs_histogram (kind OBS, ids i64[n]):
+ * count = roundf(dx * (float)n_children(street)) of the observation's bucket (api.rs:227-237; 19 600 / 47 / 46).  counts [n][bins];
+ * a bucket without transition rows: zeros with status EMPTY.  River atlases: RP_ERR_UNSUPPORTED */
+RP_API int rp_atlas_histograms(rp_atlas* h, uint64_t n, int kind, const void* ids, uint32_t* counts, uint8_t* status);
+RP_API int rp_atlas_histograms_device(rp_atlas* h, uint64_t n, int kind, const void* ids, uint32_t* counts, uint8_t* status);
+/* the window [start, start + count) ∩ [0, population) of bucket abs[q] in position order: out i64 [n][count] (0 beyond the window),
+ * got[q] = observations written; count <= 16 */
+RP_API int rp_atlas_members(rp_atlas* h, uint64_t n, const uint8_t* abs, const uint32_t* start, uint32_t count, int64_t* out, uint8_t* got);
+RP_API int rp_atlas_members_device(rp_atlas* h, uint64_t n, const uint8_t* abs, const uint32_t* start, uint32_t count, int64_t* out,
+                                   uint8_t* got);
+
+/* =================================================================================================
  * Artifact files: what the reference streams to PostgreSQL, written as files in the same
  * byte format — daybook::Streamable::stream (daybook/src/traits/streamable.rs:36-46) over
  * tokio_postgres::binary_copy::BinaryCopyInWriter, i.e. PostgreSQL's binary COPY format: load with
@@ -1860,7 +1972,10 @@ RP_API int rp_deuce_kernel_ms(double* ms);
  * ================================================================================================= */
 /* Generic writer / reader, struct-of-arrays.  `types`: one character per column — 'h' int2, 'i' int4, 'q' int8,
  * 'f' float4 (the shapes of daybook/src/traits/row.rs:21-57 are "qh", "if", "hhf", "qhqqfffi").  columns[c] points
- * at n_rows values of column c.  read(): fills up to `cap` rows (columns may be NULL to count) and reports *n_rows. */
+ * at n_rows values of column c.  read(): fills up to `cap` rows (columns may be NULL to count) and reports *n_rows.
+ * read() takes an SQL NULL (field length -1) in an 'f' column and stores the NaN with the bits RP_PGCOPY_NULL_F32; a NULL in any
+ * other column is RP_ERR_INVALID as before.  write() writes no NULLs. */
+#define RP_PGCOPY_NULL_F32 0xffffffffu
 RP_API int rp_pgcopy_write(const char* path, const char* types, uint64_t n_rows, const void* const* columns);
 RP_API int rp_pgcopy_read(const char* path, const char* types, uint64_t cap, void* const* columns, uint64_t* n_rows);
 /* Lookup rows (lloyd/src/lookup.rs:141-147): (obs i64, abs i16 = street << 8 | index) in table order */
@@ -1873,6 +1988,13 @@ RP_API int rp_artifact_write_metric(const char* path, int street, uint32_t K, co
  * descending, stable) as (prev i16, next i16, dx f32); counts/weight as rp_kmeans_centroids returns them */
 RP_API int rp_artifact_write_transitions(const char* path, int street, uint32_t K, uint32_t bins,
                                          const uint32_t* counts, const uint64_t* weight);
+/* The derived `abstraction` table (daybook/src/schema.rs:87-92): rows (abs i16 = street << 8 | k, street i16, population i32,
+ * equity f32), k ascending; population / equity as rp_atlas_tables returns them.  Read back with rp_pgcopy_read(path, "hhif", ...). */
+RP_API int rp_artifact_write_abstraction(const char* path, int street, uint32_t K, const uint32_t* population, const float* equity);
+/* The `isomorphism` table with its derived columns (lloyd/src/lookup.rs:91-96): rows (obs i64, abs i16, equity f32, position i32) in
+ * table order; equity NULL writes SQL NULL in every row (the column is the river's).  Read back with rp_pgcopy_read(path, "qhfi", ...). */
+RP_API int rp_artifact_write_isomorphism(const char* path, int street, uint64_t n, const int64_t* obs, const uint8_t* abs_index,
+                                         const float* equity, const uint32_t* position);
 /* NlheProfile::rows (nlhe/src/profile.rs:144-163) as the blueprint table's COPY file: columns (past BIGINT, present SMALLINT,
  * choices BIGINT, edge BIGINT, weight REAL, regret REAL, payoff REAL, visits INTEGER) (profile.rs:20-31), one row per
  * (infoset, edge of its choices); edge = From<Edge> for u64 (kicker/src/edge.rs:122-160).  Input: rp_nlhe_export's arrays.

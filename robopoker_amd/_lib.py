@@ -287,6 +287,15 @@ class SinkhornHP(C.Structure):
     _fields_ = [("temperature", C.c_float), ("iterations", C.c_uint32), ("tolerance", C.c_float)]
 
 
+class AtlasSample(C.Structure):  # rp_atlas_sample, 32 bytes
+    _fields_ = [("obs", C.c_int64), ("equity", C.c_float), ("density", C.c_float), ("distance", C.c_float), ("position", C.c_uint32),
+                ("population", C.c_uint32), ("abs", C.c_int16), ("reserved", C.c_uint8 * 2)]
+
+
+ATLAS_STATUS = {"ok": 0, "miss": 1, "same": 2, "empty": 3, "range": 4}  # rp_atlas_status
+ATLAS_HIST = {"abs": 0, "obs": 1}  # rp_atlas_hist_kind
+
+
 class RpError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"rp_mi355x error {code}: {msg}")
@@ -453,6 +462,11 @@ _SIGNATURES = {
         [C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SinkhornHP), C.c_int, C.c_void_p,
          C.c_void_p],
     ),
+    "rp_sinkhorn_cost_device": (
+        C.c_int,
+        [C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SinkhornHP), C.c_int, C.c_void_p,
+         C.c_void_p],
+    ),
     "rp_sinkhorn_flow": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SinkhornHP), C.c_int, C.c_void_p, C.c_void_p]),
     "rp_equity_variation": (C.c_int, [C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "rp_mccfr_train": (C.c_int, [C.c_void_p, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
@@ -545,9 +559,25 @@ _SIGNATURES = {
     "rp_lookup_get": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "rp_lookup_project": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rp_deuce_kernel_ms": (C.c_int, [C.POINTER(C.c_double)]),
+    "rp_atlas_create": (C.c_int, [C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "rp_atlas_destroy": (C.c_int, [C.c_void_p]),
+    "rp_atlas_shape": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
+    "rp_atlas_tables": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5),
+    "rp_atlas_create_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    **{name + form: (C.c_int, [C.c_void_p, C.c_uint64] + args) for form in ("", "_device") for name, args in (
+        ("rp_atlas_describe", [C.c_void_p] * 4),
+        ("rp_atlas_obs_equity", [C.c_void_p] * 3),
+        ("rp_atlas_pick", [C.c_void_p] * 4),
+        ("rp_atlas_neighbors", [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+        ("rp_atlas_distance", [C.c_void_p] * 3),
+        ("rp_atlas_histograms", [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+        ("rp_atlas_members", [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]))},
     "rp_pgcopy_write": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p)]),
     "rp_pgcopy_read": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "rp_artifact_write_lookup": (C.c_int, [C.c_char_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "rp_artifact_write_abstraction": (C.c_int, [C.c_char_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rp_artifact_write_isomorphism": (C.c_int, [C.c_char_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rp_artifact_write_metric": (C.c_int, [C.c_char_p, C.c_int, C.c_uint32, C.c_void_p]),
     "rp_artifact_write_blueprint": (C.c_int, [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                               C.POINTER(C.c_uint64)]),

@@ -67,6 +67,10 @@ struct Writer {
         put_be(be, v, w);
         buf.insert(buf.end(), be, be + w);
     }
+    void null_field() {  // SQL NULL: length -1, no bytes
+        const unsigned char len[4] = {0xff, 0xff, 0xff, 0xff};
+        buf.insert(buf.end(), len, len + 4);
+    }
     bool close() {
         const unsigned char trailer[2] = {0xff, 0xff};
         buf.insert(buf.end(), trailer, trailer + 2);
@@ -133,7 +137,13 @@ int rp_pgcopy_read(const char* path, const char* types, uint64_t cap, void* cons
         for (size_t c = 0; c < nc && rc == RP_OK; ++c) {
             unsigned char len[4], be[8];
             const size_t wd = width_of(types[c]);
-            if (std::fread(len, 1, 4, f) != 4 || len[0] || len[1] || len[2] || len[3] != wd || std::fread(be, 1, wd, f) != wd) {
+            if (std::fread(len, 1, 4, f) != 4) std::memset(len, 0, 4);  // refused below: no width is 0
+            if (types[c] == 'f' && (len[0] & len[1] & len[2] & len[3]) == 0xff) {  // SQL NULL in a float4 column
+                const uint32_t null_bits = RP_PGCOPY_NULL_F32;
+                if (columns && n < cap && columns[c]) std::memcpy(static_cast<unsigned char*>(columns[c]) + n * wd, &null_bits, 4);
+                continue;
+            }
+            if (len[0] || len[1] || len[2] || len[3] != wd || std::fread(be, 1, wd, f) != wd) {
                 rc = rp::fail(RP_ERR_INVALID, "%s: tuple %llu field %zu is not a %zu-byte value", path, (unsigned long long)n, c, wd);
                 break;
             }
@@ -203,6 +213,48 @@ int rp_artifact_write_transitions(const char* path, int street, uint32_t K, uint
             w.field(&next, 2);
             w.field(&e.second, 4);
         }
+    }
+    if (!w.close()) return rp::fail(RP_ERR_INVALID, "short write to %s", path);
+    return RP_OK;
+}
+
+// The derived `abstraction` table (daybook/src/schema.rs:87-92; the reference fills it with INSERTs of get_equity / get_population):
+// one row per bucket, columns (abs, street, population, equity) in the table's order; population / equity as rp_atlas_tables returns them.
+int rp_artifact_write_abstraction(const char* path, int street, uint32_t K, const uint32_t* population, const float* equity) {
+    if (!path || !population || !equity) return rp::fail(RP_ERR_INVALID, "null argument");
+    if (street < 0 || street > 3 || K == 0 || K > 256) return rp::fail(RP_ERR_INVALID, "street %d, K %u", street, K);
+    Writer w;
+    if (!w.open(path)) return rp::fail(RP_ERR_INVALID, "cannot create %s", path);
+    for (uint32_t k = 0; k < K; ++k) {
+        const int16_t a = (int16_t)((uint16_t)street << 8 | k), s = (int16_t)street;
+        const int32_t p = (int32_t)population[k];
+        w.begin_row(4);
+        w.field(&a, 2);
+        w.field(&s, 2);
+        w.field(&p, 4);
+        w.field(&equity[k], 4);
+    }
+    if (!w.close()) return rp::fail(RP_ERR_INVALID, "short write to %s", path);
+    return RP_OK;
+}
+
+// The `isomorphism` table with its derived columns (lloyd/src/lookup.rs:91-96): (obs, abs, equity, position) in table order; equity
+// NULL writes SQL NULL in every row (the column is the river's).
+int rp_artifact_write_isomorphism(const char* path, int street, uint64_t n, const int64_t* obs, const uint8_t* abs_index, const float* equity,
+                                  const uint32_t* position) {
+    if (!path || ((!obs || !abs_index || !position) && n)) return rp::fail(RP_ERR_INVALID, "null argument");
+    if (street < 0 || street > 3) return rp::fail(RP_ERR_INVALID, "street %d", street);
+    Writer w;
+    if (!w.open(path)) return rp::fail(RP_ERR_INVALID, "cannot create %s", path);
+    for (uint64_t r = 0; r < n; ++r) {
+        const int16_t a = (int16_t)((uint16_t)street << 8 | abs_index[r]);
+        const int32_t p = (int32_t)position[r];
+        w.begin_row(4);
+        w.field(&obs[r], 8);
+        w.field(&a, 2);
+        if (equity) w.field(&equity[r], 4);
+        else w.null_field();
+        w.field(&p, 4);
     }
     if (!w.close()) return rp::fail(RP_ERR_INVALID, "short write to %s", path);
     return RP_OK;

@@ -1776,7 +1776,8 @@ int rp_kmeans_kernel_time(rp_kmeans* h, const char* name, double* total_ms, uint
 namespace {
 std::atomic<int> g_pair_libm{RP_LIBM_CONTRACT};
 int pair_common(uint32_t bins, uint64_t pairs, const uint32_t* mu, const uint32_t* nu, const float* tri, const rp_sinkhorn_hp* hp,
-                int device, float* out, uint32_t* iterations, int divergence) {
+                int device, float* out, uint32_t* iterations, int divergence, bool on_device = false) {
+    // on_device: mu, nu, out and iterations are device arrays, used in place
     if (!mu || !nu || !out || pairs == 0 || bins == 0 || bins > MAXB || (!tri && bins > 1))
         return rp::fail(RP_ERR_INVALID, "rp_sinkhorn_*: bad argument");
     if (rp_device_count() <= 0) return rp::fail(RP_ERR_NO_DEVICE, "rp_sinkhorn_*: no HIP device visible; no CPU fallback");
@@ -1796,31 +1797,41 @@ int pair_common(uint32_t bins, uint64_t pairs, const uint32_t* mu, const uint32_
     const size_t hb = (size_t)pairs * bins * 4;
     HIP_TRY(hipMalloc(&dC, C.size() * 4));
     HIP_TRY(hipMalloc(&dR, R.size() * 4));
-    HIP_TRY(hipMalloc(&dout, pairs * 4));
-    HIP_TRY(hipMalloc(&dmu, hb));
-    HIP_TRY(hipMalloc(&dnu, hb));
+    if (on_device) {
+        dout = out, dmu = const_cast<uint32_t*>(mu), dnu = const_cast<uint32_t*>(nu), dit = iterations;
+    } else {
+        HIP_TRY(hipMalloc(&dout, pairs * 4));
+        HIP_TRY(hipMalloc(&dmu, hb));
+        HIP_TRY(hipMalloc(&dnu, hb));
+        HIP_TRY(hipMemcpy(dmu, mu, hb, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dnu, nu, hb, hipMemcpyHostToDevice));
+    }
     HIP_TRY(hipMalloc(&dstats, 32));
     HIP_TRY(hipMemset(dstats, 0, 32));
     HIP_TRY(hipMemcpy(dC, C.data(), C.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dR, R.data(), R.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dmu, mu, hb, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dnu, nu, hb, hipMemcpyHostToDevice));
     Metric M{dC, dR, bins, hh.iterations, hh.tolerance, dstats, 1u};
     const bool glibc = g_pair_libm.load() == RP_LIBM_GLIBC;
     hipLaunchKernelGGL(KSEL_IF(glibc, k_pair_sinkhorn), dim3((unsigned)pairs), dim3(64), 0, 0, dmu, dnu, M, divergence, dout, (uint32_t*)nullptr);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, dout, pairs * 4, hipMemcpyDeviceToHost));
+    if (!on_device) HIP_TRY(hipMemcpy(out, dout, pairs * 4, hipMemcpyDeviceToHost));
     if (iterations) {
-        HIP_TRY(hipMalloc(&dit, pairs * 4));
+        if (!on_device) HIP_TRY(hipMalloc(&dit, pairs * 4));
         HIP_TRY(hipMalloc(&dscr, pairs * 32));
         HIP_TRY(hipMemset(dscr, 0, pairs * 32));
         hipLaunchKernelGGL(KSEL_IF(glibc, k_pair_iters), dim3((unsigned)pairs), dim3(64), 0, 0, dmu, dnu, M, dscr, dit);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(iterations, dit, pairs * 4, hipMemcpyDeviceToHost));
-        (void)hipFree(dit);
-        (void)hipFree(dscr);
+        if (!on_device) {
+            HIP_TRY(hipMemcpy(iterations, dit, pairs * 4, hipMemcpyDeviceToHost));
+            (void)hipFree(dit);
+        }
     }
-    (void)hipFree(dC); (void)hipFree(dR); (void)hipFree(dout); (void)hipFree(dmu); (void)hipFree(dnu); (void)hipFree(dstats);
+    if (on_device) HIP_TRY(hipDeviceSynchronize());  // the host form's copies back have waited already
+    if (dscr) (void)hipFree(dscr);
+    (void)hipFree(dC); (void)hipFree(dR); (void)hipFree(dstats);
+    if (!on_device) {
+        (void)hipFree(dout); (void)hipFree(dmu); (void)hipFree(dnu);
+    }
     return RP_OK;
 }
 }  // namespace
@@ -1837,6 +1848,10 @@ int rp_sinkhorn_divergence(uint32_t bins, uint64_t pairs, const uint32_t* mu, co
 int rp_sinkhorn_cost(uint32_t bins, uint64_t pairs, const uint32_t* mu, const uint32_t* nu, const float* tri_metric,
                      const rp_sinkhorn_hp* hp, int device, float* out, uint32_t* iterations) {
     return pair_common(bins, pairs, mu, nu, tri_metric, hp, device, out, iterations, 0);
+}
+int rp_sinkhorn_cost_device(uint32_t bins, uint64_t pairs, const uint32_t* mu_dev, const uint32_t* nu_dev, const float* tri_metric,
+                            const rp_sinkhorn_hp* hp, int device, float* out_dev, uint32_t* iterations_dev) {
+    return pair_common(bins, pairs, mu_dev, nu_dev, tri_metric, hp, device, out_dev, iterations_dev, 0, true);
 }
 int rp_sinkhorn_flow(uint32_t bins, const uint32_t* mu, const uint32_t* nu, const float* tri, const rp_sinkhorn_hp* hp, int device,
                      float* flow, float* coupling) {

@@ -18,6 +18,21 @@ __device__ __forceinline__ int64_t obs_encode(uint64_t pocket, uint64_t public_)
     return (int64_t)acc;
 }
 
+// From<i64> for Observation (observation.rs:144-165): one byte (card + 1) per card, the two lowest are the pocket
+__device__ __forceinline__ void obs_decode(int64_t bits, uint64_t* pocket, uint64_t* public_) {
+    uint64_t po = 0, pu = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint64_t b = (uint64_t)bits >> (8 * i);
+        if (bits <= 0 || b == 0) break;
+        const uint32_t c = (uint32_t)(b & 0xffu) - 1u;
+        const uint64_t card = c < 52u ? 1ull << c : 0ull;  // a byte that is no card leaves the hand short: callers check sizes
+        if (i < 2) po |= card;
+        else pu |= card;
+    }
+    *pocket = po, *public_ = pu;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Permutation::from(&Observation) (permutation.rs:9-21,45-60).  A suit's sort key packs, most significant first:
 // pocket size, public size, pocket min rank, public min rank, pocket max rank, public max rank (None < Some: +1),
