@@ -423,8 +423,56 @@ RP_API int rp_game_skeleton(const rp_game_table* game, int* out);
  *   or rows == NULL with rows_cap > 0: RP_ERR_INVALID; then n_players != 2: RP_ERR_UNSUPPORTED.  belief: n = 0 is RP_OK; a NULL handle,
  *   priors, world_of or weights is RP_ERR_INVALID (status may be NULL); then n_players != 2.  The host forms stage, launch and
  *   synchronise; the _device forms take every array in DEVICE memory (args on the host) and return without synchronising.
- * OUT OF SCOPE: SubGameSolver::with_origin, DepthSolver / DepthEncoder for table games (Payoffs::uniform(frontier_payoff) and the
- *   Pick game), the reference-seed RNG for these draws, more than two players, tests/emul. */
+ *   rp_mccfr_subgame_solve writes 0 to the row's `kind` byte and to the result's `frontiers` word (both were padding before the
+ *   depth-limited call below gave them a meaning).
+ *
+ * DEPTH-LIMITED: rp_mccfr_depth_solve = SubGameSolver::with_origin (subgame/src/solver.rs: build(.., Some(origin))) and, as one of its
+ *   entries, DepthSolver (subgame/src/depth/solver.rs) over DepthEncoder / DepthGame (depth/encoder.rs, depth/game.rs) for table games.
+ *   Every paragraph above applies word for word (RESTRICT, world draw, TREE numbering, DRAWS, PROFILE, VALUES, UPDATE, RESULT,
+ *   INVARIANCES, LAUNCHES, the argument checks and their order); the deltas are the table-game form of rp_nlhe_depth_solve's
+ *   paragraphs below, reproduced, not repaired.
+ *   FRONTIER TABLES, on the handle (rp_mccfr_set_frontiers; host arrays, copied): depth[state] = CfrGame::depth(); for a chance state
+ *     pick_info[state] < n_pick = the id of DepthInfo::Pick(inner), inner = resume(prefix ++ game edges, the chance game), and
+ *     payoff_ref[state] names the D x D matrix DepthSampler::payoffs answers there ("the implementor decides what each index means"):
+ *     an infoset id i < n_infos is Payoffs::uniform(the BLUEPRINT's cum_payoff(i, slot 0)) (frontier_payoff reads the blueprint, not the
+ *     local profile), RP_NO_INFO is uniform(0.0f), 0x80000000u | m is matrices[m], row = internal's k, column = external's j.
+ *     D = leaves in 1..4.  rp_mccfr_set_frontiers checks the struct's own fields first and needs no handle for them (leaves, reserved, a
+ *     NULL array, n_pick > RP_MCCFR_SUBGAME_MAX_INFOS, a matrix entry that is not finite), then the handle (NULL: RP_ERR_INVALID), then
+ *     against the handle's game table every chance state with depth > 0 (pick_info < n_pick) and every chance state's payoff_ref: all
+ *     RP_ERR_INVALID with the field's name in rp_last_error, before the device is touched.  It synchronises the handle's stream,
+ *     replaces any earlier tables (f = NULL clears them), and the tables are freed with the handle.  Read-only on the solver's tables,
+ *     epoch and counters, like the solves.
+ *     rp_game_frontiers (host only) answers the reference's values for the built-in games: Kuhn and RPS keep CfrGame::depth()'s
+ *     default 0 everywhere and have no Pick infoset (n_pick = 0: no origin makes a frontier there); Leduc and wide Leduc answer 0 at
+ *     Start, Dealt and R1(_), 1 everywhere else (leduc/src/game.rs:232-237), one Pick id per (seat 0's rank, round-1 spot) at the
+ *     board-deal states — the chance game's info is (acting = false, seat 0's rank, board None, r1, None), leduc/src/encoder.rs:20-31,
+ *     so frontier states that differ only in seat 1's card share one — numbered by the lowest-numbered state that carries them, and
+ *     payoff_ref = RP_NO_INFO everywhere: leduc/src/solver.rs:7-25 asks blueprint.frontier_payoff(inner) for an infoset with acting =
+ *     false, which training never writes, so unwrap_or_default makes Payoffs::uniform(0.0).  The three arrays are [n_states].
+ *   ORIGIN, per solve: a value in 0 .. 253 is SubGameSolver::with_origin(origin); RP_MCCFR_ORIGIN_ENTRY (or origin == NULL for the whole
+ *     batch) is depth[observed] (DepthSolver::new: origin = Some(entry.depth())); RP_MCCFR_ORIGIN_NONE is rp_mccfr_subgame_solve byte
+ *     for byte.
+ *   TREE.  A chance state with depth[state] > origin is a FRONTIER, at node 0 too (DepthGame::at_frontier).  It has D Pick(k) edges to
+ *     Internal(k) nodes and, staying the chance node it was grown as, keeps ONE: k = rp_pick_uniform(h(node), D) — internal's
+ *     continuation is never learnt.  The Internal(k) node's turn is the seat `external`; it has D Pick(j) edges to External(k, j)
+ *     nodes, all kept when the walker is `external`, otherwise one by the weighted draw of DRAWS over the Pick infoset.  External(k, j)
+ *     is a leaf.  Any other chance state stays the leaf it is above.  The node limit stays RP_MCCFR_SUBGAME_MAX_NODES.
+ *   PROFILE.  A Pick infoset is (world, kind 1, pick id) and has D slots, slot c = continuation c.  Absent edges read weight 1.0f /
+ *     (float)D, regret EPSILON, payoff 0.0f, visits 0 (DepthView); the first write creates all-zero encounters (Encounter::default()).
+ *     The index grows to 4 x (n_infos + n_pick) and the row limit becomes min(RP_MCCFR_SUBGAME_MAX_ROWS, 4 * (n_infos + n_pick)).
+ *   VALUES.  A frontier node multiplies neither rr nor sr and its edge is left out of the ancestor reach (a chance node);
+ *     terminal_value at External(k, j) is +payoffs[k][j] for hero == 1 - external and the f32 negation otherwise, payoffs being the
+ *     matrix payoff_ref of the frontier's state names, read from the handle's table, never from a local row.
+ *   RESULT.  rp_mccfr_subgame_row.kind: 0 Game, 1 Pick; for a Pick row info = the pick id and n_actions = D; rows sort by (world,
+ *     kind, info).  rp_mccfr_subgame_result.frontiers = the wrapping count of frontier nodes over all iterations.  A frontier entry
+ *     state is a valid solve with n_actions = 0 that updates Pick rows.
+ *   DEPTHSOLVER is not a second code path: DepthSolver::new(source, prefix, internal, entry) is the entry {observed = the entry state,
+ *     external = 1 - internal, n_candidates = 0, n_worlds = 1, weights = {1}} with origin = RP_MCCFR_ORIGIN_ENTRY; world 0 is drawn
+ *     every iteration, the entry state is `observed` every iteration and `fallbacks` counts every iteration.
+ *   Statuses: those above, and RP_MSUB_FRONTIER for a frontier state whose tables are inconsistent at run time (a pick_info not below
+ *     n_pick, a payoff_ref that names nothing) — unreachable after rp_mccfr_set_frontiers' validation, and checked all the same.
+ *   Arguments: rp_mccfr_subgame_solve's checks in their order, then a handle without frontier tables: RP_ERR_INVALID.
+ * OUT OF SCOPE: the reference-seed RNG for these draws, more than two players, tests/emul. */
 #define RP_MCCFR_SUBGAME_MAX_ITERATIONS (1u << 20)
 #define RP_MCCFR_SUBGAME_MAX_NODES 62u
 #define RP_MCCFR_SUBGAME_MAX_ROWS 1024u
@@ -434,7 +482,8 @@ RP_API int rp_game_skeleton(const rp_game_table* game, int* out);
 #define RP_WORLD_NONE 0xffu
 #endif
 enum { RP_MSUB_OK = 0, RP_MSUB_SEAT = 1, RP_MSUB_MODE = 2, RP_MSUB_WORLDS = 3, RP_MSUB_COUNT = 4, RP_MSUB_STATE = 5, RP_MSUB_SECRET = 6,
-       RP_MSUB_PATH = 7, RP_MSUB_WEIGHT = 8, RP_MSUB_INFO = 9, RP_MSUB_TREE = 10, RP_MSUB_ROWS = 11, RP_MSUB_ORDER = 12 };
+       RP_MSUB_PATH = 7, RP_MSUB_WEIGHT = 8, RP_MSUB_INFO = 9, RP_MSUB_TREE = 10, RP_MSUB_ROWS = 11, RP_MSUB_ORDER = 12,
+       RP_MSUB_FRONTIER = 13 };
 typedef struct rp_mccfr_subgame_prior { /* one belief entry */
     uint32_t root_state[16];
     uint8_t secret[16];
@@ -464,10 +513,10 @@ typedef struct rp_mccfr_subgame_result {
     uint32_t iterations, n_rows;
     uint64_t nodes, infosets;
     uint32_t drawn[4];
-    uint32_t fallbacks, pad2;
+    uint32_t fallbacks, frontiers; /* frontiers: 0 from rp_mccfr_subgame_solve */
 } rp_mccfr_subgame_result; /* 192 bytes */
 typedef struct rp_mccfr_subgame_row {
-    uint8_t world, n_actions, pad[2];
+    uint8_t world, n_actions, kind /* 0 Game, 1 Pick */, pad;
     uint32_t info;
     rp_encounter enc[16]; /* zero from n_actions on */
 } rp_mccfr_subgame_row;    /* 264 bytes */
@@ -482,6 +531,26 @@ RP_API int rp_mccfr_subgame_solve(rp_mccfr* h, uint64_t n, const rp_mccfr_subgam
 RP_API int rp_mccfr_subgame_solve_device(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries_dev,
                                          const rp_mccfr_subgame_args* args /* host */, rp_mccfr_subgame_result* results_dev,
                                          rp_mccfr_subgame_row* rows_dev);
+/* the depth-limited re-solve (DEPTH-LIMITED above) */
+#define RP_MCCFR_ORIGIN_ENTRY 254u  /* origin = depth[observed]: DepthSolver::new */
+#define RP_MCCFR_ORIGIN_NONE  255u  /* no frontier: rp_mccfr_subgame_solve, byte for byte */
+typedef struct rp_mccfr_frontiers {   /* host struct, host arrays; copied */
+    const uint8_t*  depth;      /* [n_states] CfrGame::depth() of every state */
+    const uint32_t* pick_info;  /* [n_states] chance states: the Pick infoset, < n_pick; RP_NO_INFO elsewhere */
+    const uint32_t* payoff_ref; /* [n_states] chance states: < n_infos: uniform(blueprint payoff of that infoset, slot 0);
+                                   RP_NO_INFO: uniform(0.0f); 0x80000000u | m: matrices[m] */
+    const float*    matrices;   /* [n_matrices][leaves][leaves], row = internal's k; NULL when n_matrices == 0 */
+    uint32_t n_pick, n_matrices, leaves /* D, 1..4 */, reserved /* 0 */;
+} rp_mccfr_frontiers;
+RP_API int rp_mccfr_set_frontiers(rp_mccfr* h, const rp_mccfr_frontiers* f);  /* NULL f clears */
+/* host only: the reference's depth / Pick infosets / payoffs of a built-in game, three arrays of [n_states] */
+RP_API int rp_game_frontiers(const rp_game* g, uint8_t* depth, uint32_t* pick_info, uint32_t* payoff_ref, uint32_t* n_pick);
+RP_API int rp_mccfr_depth_solve(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries, const uint8_t* origin /* [n] or NULL = ENTRY */,
+                                const rp_mccfr_subgame_args* args, rp_mccfr_subgame_result* results,
+                                rp_mccfr_subgame_row* rows /* [n][rows_cap] or NULL */);
+RP_API int rp_mccfr_depth_solve_device(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries_dev, const uint8_t* origin_dev,
+                                       const rp_mccfr_subgame_args* args /* host */, rp_mccfr_subgame_result* results_dev,
+                                       rp_mccfr_subgame_row* rows_dev);
 
 /* ============================================================= sparse profile ==
  * The update half of Solver::step (solver/solver.rs:96-105,143-192: update_regret, update_weight, update_payoff,

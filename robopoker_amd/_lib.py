@@ -50,7 +50,8 @@ RP_NLHE_SUBGAME_ORIGIN_NONE = 126
 RP_MCCFR_SUBGAME_MAX_ITERATIONS = 1 << 20
 RP_MCCFR_SUBGAME_MAX_NODES, RP_MCCFR_SUBGAME_MAX_ROWS, RP_MCCFR_SUBGAME_MAX_INFOS, RP_MCCFR_SUBGAME_MAX_CANDIDATES = 62, 1024, 8192, 16
 (RP_MSUB_OK, RP_MSUB_SEAT, RP_MSUB_MODE, RP_MSUB_WORLDS, RP_MSUB_COUNT, RP_MSUB_STATE, RP_MSUB_SECRET, RP_MSUB_PATH, RP_MSUB_WEIGHT, RP_MSUB_INFO,
- RP_MSUB_TREE, RP_MSUB_ROWS, RP_MSUB_ORDER) = range(13)
+ RP_MSUB_TREE, RP_MSUB_ROWS, RP_MSUB_ORDER, RP_MSUB_FRONTIER) = range(14)
+RP_MCCFR_ORIGIN_ENTRY, RP_MCCFR_ORIGIN_NONE = 254, 255
 RP_AIVAT_MAX_PLAYS = 48
 RP_AIVAT_WITNESS = 11
 PLAY = {"fold": 1, "call": 2, "check": 3, "raise": 4, "shove": 5}  # rp_aivat_play
@@ -80,6 +81,11 @@ class Encounter(C.Structure):
 class MccfrSubgameArgs(C.Structure):  # rp_mccfr_subgame_args, 32 bytes
     _fields_ = [("iterations", C.c_uint32), ("prior", C.c_float), ("seed", C.c_uint64), ("first_id", C.c_uint64), ("rows_cap", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class MccfrFrontiers(C.Structure):  # rp_mccfr_frontiers: host arrays, copied by rp_mccfr_set_frontiers
+    _fields_ = [("depth", C.c_void_p), ("pick_info", C.c_void_p), ("payoff_ref", C.c_void_p), ("matrices", C.c_void_p), ("n_pick", C.c_uint32),
+                ("n_matrices", C.c_uint32), ("leaves", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class NlheRecall(C.Structure):
@@ -364,6 +370,10 @@ _SIGNATURES = {
     "rp_mccfr_subgame_belief_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rp_mccfr_subgame_solve": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(MccfrSubgameArgs), C.c_void_p, C.c_void_p]),
     "rp_mccfr_subgame_solve_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(MccfrSubgameArgs), C.c_void_p, C.c_void_p]),
+    "rp_mccfr_set_frontiers": (C.c_int, [C.c_void_p, C.POINTER(MccfrFrontiers)]),
+    "rp_game_frontiers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "rp_mccfr_depth_solve": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(MccfrSubgameArgs), C.c_void_p, C.c_void_p]),
+    "rp_mccfr_depth_solve_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(MccfrSubgameArgs), C.c_void_p, C.c_void_p]),
     "rp_mccfr_set_batch": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rp_mccfr_set_update_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "rp_mccfr_set_rng": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(HashStreams)]),

@@ -29,6 +29,17 @@ struct Builder {
     std::vector<rp_hash_stream> info_streams, chance_streams;
     std::map<std::string, uint16_t> chance_by_bytes;
     uint32_t n_players = 2;
+    // rp_game_frontiers: CfrGame::depth() of the states that do not keep its default 0, and the key of DepthInfo::Pick at a chance state
+    std::vector<uint8_t> depth;
+    std::vector<uint32_t> pick_key;
+    void mark_depth(uint32_t first, uint32_t end, uint8_t d) {
+        if (depth.size() < end) depth.resize(end, 0);
+        for (uint32_t s = first; s < end; ++s) depth[s] = d;
+    }
+    void mark_pick(uint32_t state, uint32_t key) {
+        if (pick_key.size() <= state) pick_key.resize((size_t)state + 1, 0xffffffffu);
+        pick_key[state] = key;
+    }
 
     uint32_t info(const std::string& name, uint8_t actions, uint8_t player, const rp_hash_stream& stream) {
         auto it = info_by_name.find(name);
@@ -246,6 +257,10 @@ uint32_t leduc_deal(Builder& b, int c0, int c1, Spot r1) {
         if (c == c0 || c == c1) continue;
         b.set_child(s, k++, leduc_r2(b, c0, c1, c, r1, S_OPEN));
     }
+    // depth() is 1 at Deal(_), R2(..) and Over(_) (game.rs:232-237): this state and the whole of its subtree, built behind it; the
+    // Pick infoset of the chance game is (seat 0's rank, r1) — the chance node's info above
+    b.mark_depth(s, (uint32_t)b.states.size(), 1);
+    b.mark_pick(s, (uint32_t)rank_of(c0) * 4u + (uint32_t)r1);
     return s;
 }
 uint32_t leduc_r1(Builder& b, int c0, int c1, Spot spot) {
@@ -267,11 +282,13 @@ uint32_t leduc_r1(Builder& b, int c0, int c1, Spot spot) {
         case S_RAISED:
             leduc_fold1(1, pay);
             b.set_child(s, 0, b.terminal(pay[0], pay[1]));
+            b.mark_depth((uint32_t)b.states.size() - 1, (uint32_t)b.states.size(), 1);  // Over(FoldR1)
             b.set_child(s, 1, leduc_deal(b, c0, c1, S_RAISED));
             break;
         case S_CHECKRAISED:
             leduc_fold1(0, pay);
             b.set_child(s, 0, b.terminal(pay[0], pay[1]));
+            b.mark_depth((uint32_t)b.states.size() - 1, (uint32_t)b.states.size(), 1);  // Over(FoldR1)
             b.set_child(s, 1, leduc_deal(b, c0, c1, S_CHECKRAISED));
             break;
     }
@@ -436,6 +453,23 @@ int rp_game_info_name(const rp_game* g, uint32_t info, char* buf, size_t cap) {
     size_t n = std::min(cap - 1, s.size());
     memcpy(buf, s.data(), n);
     buf[n] = 0;
+    return RP_OK;
+}
+
+int rp_game_frontiers(const rp_game* g, uint8_t* depth, uint32_t* pick_info, uint32_t* payoff_ref, uint32_t* n_pick) {
+    if (!g || !depth || !pick_info || !payoff_ref || !n_pick) return rp::fail(RP_ERR_INVALID, "rp_game_frontiers: NULL argument");
+    const Builder& b = g->b;
+    std::map<uint32_t, uint32_t> ids;  // Pick key -> id, numbered by the lowest-numbered state that carries it
+    for (uint32_t s = 0; s < b.states.size(); ++s) {
+        depth[s] = s < b.depth.size() ? b.depth[s] : 0;
+        payoff_ref[s] = RP_NO_INFO;  // blueprint.frontier_payoff of an infoset training never writes: Payoffs::uniform(0.0)
+        pick_info[s] = RP_NO_INFO;
+        if (s >= b.pick_key.size() || b.pick_key[s] == 0xffffffffu) continue;
+        auto it = ids.find(b.pick_key[s]);
+        if (it == ids.end()) it = ids.emplace(b.pick_key[s], (uint32_t)ids.size()).first;
+        pick_info[s] = it->second;
+    }
+    *n_pick = (uint32_t)ids.size();
     return RP_OK;
 }
 

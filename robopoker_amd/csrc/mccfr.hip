@@ -116,6 +116,9 @@ struct rp_mccfr {
     // the safe subgame re-solve (mccfr_subgame.hpp): the per-solve regions of one launch, grow-only
     void* d_msub = nullptr;
     size_t msub_bytes = 0;
+    // rp_mccfr_set_frontiers: the frontier tables of the depth-limited re-solve, one allocation; fr.depth == nullptr: none
+    void* d_front = nullptr;
+    MsFrontiers fr{};
 };
 
 namespace {
@@ -803,6 +806,7 @@ int rp_mccfr_destroy(rp_mccfr* h) {
         if (p) (void)hipFree(p);
     if (h->d_nash) (void)hipFree(h->d_nash);
     if (h->d_msub) (void)hipFree(h->d_msub);
+    if (h->d_front) (void)hipFree(h->d_front);
     if (h->nash_pinned) (void)hipHostFree(h->nash_pinned);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -1569,22 +1573,26 @@ int msub_check_game(const char* who, const rp_mccfr* h) {
     return RP_OK;
 }
 
-// every launch of one call, queued on the handle's stream; every array in device memory
-int msub_launch_solve(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries, const rp_mccfr_subgame_args* a, rp_mccfr_subgame_result* results,
-                      rp_mccfr_subgame_row* rows) {
+// every launch of one call, queued on the handle's stream; every array in device memory.  FR: the depth-limited call's instantiation
+// over the handle's frontier tables (`origin` in device memory or nullptr)
+template <bool FR>
+int msub_launch_solve(const char* who, rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries, const uint8_t* origin,
+                      const rp_mccfr_subgame_args* a, rp_mccfr_subgame_result* results, rp_mccfr_subgame_row* rows) {
     const uint32_t NI = h->tbl.n_infos, A = h->tbl.max_actions;
     if (NI > RP_MCCFR_SUBGAME_MAX_INFOS)
-        return rp::fail(RP_ERR_CAPACITY, "rp_mccfr_subgame_solve: %u infosets, the local profile's index holds %u", NI, RP_MCCFR_SUBGAME_MAX_INFOS);
+        return rp::fail(RP_ERR_CAPACITY, "%s: %u infosets, the local profile's index holds %u", who, NI, RP_MCCFR_SUBGAME_MAX_INFOS);
     uint32_t segment = 0;
     int rc = msub_segment(&segment);
     if (rc) return rc;
+    // a world's keys and a local row's slots: with frontiers the Pick infosets follow the infosets and a Pick row has D slots
+    const uint32_t NK = FR ? NI + h->fr.n_pick : NI, RA = FR ? std::max(A, h->fr.D) : A;
     MsRegion R{};
-    R.rows_alloc = std::min<uint32_t>(RP_MCCFR_SUBGAME_MAX_ROWS, 4 * NI);
+    R.rows_alloc = std::min<uint32_t>(RP_MCCFR_SUBGAME_MAX_ROWS, 4 * NK);
     R.off_index = (uint32_t)sizeof(MsHead);
-    R.off_keys = (uint32_t)align16(R.off_index + 2 * (size_t)4 * NI);
+    R.off_keys = (uint32_t)align16(R.off_index + 2 * (size_t)4 * NK);
     R.off_perm = (uint32_t)align16(R.off_keys + 4 * (size_t)R.rows_alloc);
     R.off_rows = (uint32_t)align16(R.off_perm + 2 * (size_t)R.rows_alloc);
-    R.stride = align16(R.off_rows + (size_t)R.rows_alloc * A * sizeof(rp_encounter));
+    R.stride = align16(R.off_rows + (size_t)R.rows_alloc * RA * sizeof(rp_encounter));
     const uint32_t chunk = (uint32_t)std::min<uint64_t>(n, MS_MAX_CHUNK);
     const size_t need = R.stride * chunk;
     if (need > h->msub_bytes) {
@@ -1593,12 +1601,12 @@ int msub_launch_solve(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* ent
         h->msub_bytes = 0;
         if (hipMalloc(&h->d_msub, need) != hipSuccess) {
             (void)hipGetLastError();
-            return rp::fail(RP_ERR_CAPACITY, "rp_mccfr_subgame_solve: %zu bytes of local profiles for %u solves do not fit", need, chunk);
+            return rp::fail(RP_ERR_CAPACITY, "%s: %zu bytes of local profiles for %u solves do not fit", who, need, chunk);
         }
         h->msub_bytes = need;
     }
     R.base = reinterpret_cast<uint8_t*>(h->d_msub);
-    MsParams p{};
+    MsParamsOf<FR> p{};
     p.rows_cap = a->rows_cap;
     p.n_states = h->tbl.n_states;
     p.n_terminals = h->tbl.n_terminals;
@@ -1606,6 +1614,7 @@ int msub_launch_solve(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* ent
     p.iterations = a->iterations;
     p.prior = a->prior;
     p.hp = DistParams{h->hp.temperature, h->hp.smoothing, h->hp.curiosity};
+    if constexpr (FR) p.fr = h->fr;
     h->clk.begin(h->stream, CK_SUBGAME);
     for (uint64_t at = 0; at < n; at += chunk) {
         p.n = (uint32_t)std::min<uint64_t>(chunk, n - at);
@@ -1613,15 +1622,71 @@ int msub_launch_solve(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* ent
         p.results = results + at;
         p.rows = rows ? rows + at * a->rows_cap : nullptr;
         p.first_id = a->first_id + at;
+        if constexpr (FR) p.origin = origin ? origin + at : nullptr;
         for (uint32_t t = 0; t < a->iterations; t += segment) {
             p.t_begin = t;
             p.t_end = (uint32_t)std::min<uint64_t>((uint64_t)t + segment, a->iterations);
-            hipLaunchKernelGGL(k_mccfr_subgame_solve, dim3(p.n), dim3(MS_LANES), 0, h->stream, h->g, h->t, R, p);
+            hipLaunchKernelGGL(k_mccfr_subgame_solve<FR>, dim3(p.n), dim3(MS_LANES), 0, h->stream, h->g, h->t, R, p);
         }
     }
     h->clk.end(h->stream, CK_SUBGAME);
     HIP_TRY(hipGetLastError());
     return RP_OK;
+}
+
+// the checks every solve makes after its args, in the header's order
+int msub_check_solve(const char* who, const rp_mccfr* h, const void* entries, const void* results, const void* rows, const rp_mccfr_subgame_args* args,
+                     bool frontiers) {
+    if (!h) return rp::fail(RP_ERR_INVALID, "%s: h is NULL", who);
+    if (!entries || !results) return rp::fail(RP_ERR_INVALID, "%s: entries or results is NULL", who);
+    if (!rows && args->rows_cap > 0) return rp::fail(RP_ERR_INVALID, "%s: rows is NULL with rows_cap > 0", who);
+    int rc = msub_check_game(who, h);
+    if (rc) return rc;
+    if (frontiers && !h->fr.depth) return rp::fail(RP_ERR_INVALID, "%s: the handle has no frontier tables (rp_mccfr_set_frontiers)", who);
+    return RP_OK;
+}
+
+// the host form of both solves: stage, launch, download, synchronise; origin is a host array or nullptr
+template <bool FR>
+int msub_solve_host(const char* who, rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries, const uint8_t* origin,
+                    const rp_mccfr_subgame_args* args, rp_mccfr_subgame_result* results, rp_mccfr_subgame_row* rows) {
+    int rc = msub_check_args(who, args);
+    if (rc) return rc;
+    if (n == 0) return RP_OK;
+    if ((rc = msub_check_solve(who, h, entries, results, rows, args, FR))) return rc;
+    if ((rc = set_device(h))) return rc;
+    const size_t b_in = align16(n * sizeof(rp_mccfr_subgame_entry)), b_res = align16(n * sizeof(rp_mccfr_subgame_result)),
+                 b_rows = align16(n * (size_t)args->rows_cap * sizeof(rp_mccfr_subgame_row)), b_org = FR && origin ? align16(n) : 0;
+    uint8_t* d = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), b_in + b_res + b_rows + b_org + 16) != hipSuccess) {
+        (void)hipGetLastError();
+        return rp::fail(RP_ERR_CAPACITY, "%s: %zu bytes of staging do not fit", who, b_in + b_res + b_rows + b_org);
+    }
+    rp_mccfr_subgame_result* d_res = reinterpret_cast<rp_mccfr_subgame_result*>(d + b_in);
+    rp_mccfr_subgame_row* d_rows = args->rows_cap ? reinterpret_cast<rp_mccfr_subgame_row*>(d + b_in + b_res) : nullptr;
+    uint8_t* d_org = b_org ? d + b_in + b_res + b_rows : nullptr;
+    if (hipMemcpyAsync(d, entries, n * sizeof(rp_mccfr_subgame_entry), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        (d_org && hipMemcpyAsync(d_org, origin, n, hipMemcpyHostToDevice, h->stream) != hipSuccess))
+        rc = rp::fail(RP_ERR_HIP, "%s: upload failed", who);
+    if (!rc) rc = msub_launch_solve<FR>(who, h, n, reinterpret_cast<const rp_mccfr_subgame_entry*>(d), d_org, args, d_res, d_rows);
+    if (!rc && (hipMemcpyAsync(results, d_res, n * sizeof(rp_mccfr_subgame_result), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+                (d_rows && hipMemcpyAsync(rows, d_rows, n * (size_t)args->rows_cap * sizeof(rp_mccfr_subgame_row), hipMemcpyDeviceToHost, h->stream) != hipSuccess)))
+        rc = rp::fail(RP_ERR_HIP, "%s: download failed", who);
+    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = rp::fail(RP_ERR_HIP, "%s: a launch failed: %s", who, hipGetErrorString(hipGetLastError()));
+    (void)hipFree(d);
+    h->clk.drain();
+    return rc;
+}
+
+template <bool FR>
+int msub_solve_device(const char* who, rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries_dev, const uint8_t* origin_dev,
+                      const rp_mccfr_subgame_args* args, rp_mccfr_subgame_result* results_dev, rp_mccfr_subgame_row* rows_dev) {
+    int rc = msub_check_args(who, args);
+    if (rc) return rc;
+    if (n == 0) return RP_OK;
+    if ((rc = msub_check_solve(who, h, entries_dev, results_dev, rows_dev, args, FR))) return rc;
+    if ((rc = set_device(h))) return rc;
+    return msub_launch_solve<FR>(who, h, n, entries_dev, origin_dev, args, results_dev, rows_dev);
 }
 
 }  // namespace
@@ -1675,46 +1740,82 @@ int rp_mccfr_subgame_belief(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_prio
 
 int rp_mccfr_subgame_solve_device(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries_dev, const rp_mccfr_subgame_args* args,
                                   rp_mccfr_subgame_result* results_dev, rp_mccfr_subgame_row* rows_dev) {
-    int rc = msub_check_args("rp_mccfr_subgame_solve", args);
-    if (rc) return rc;
-    if (n == 0) return RP_OK;
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_solve: h is NULL");
-    if (!entries_dev || !results_dev) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_solve: entries or results is NULL");
-    if (!rows_dev && args->rows_cap > 0) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_solve: rows is NULL with rows_cap > 0");
-    if ((rc = msub_check_game("rp_mccfr_subgame_solve", h))) return rc;
-    if ((rc = set_device(h))) return rc;
-    return msub_launch_solve(h, n, entries_dev, args, results_dev, rows_dev);
+    return msub_solve_device<false>("rp_mccfr_subgame_solve", h, n, entries_dev, nullptr, args, results_dev, rows_dev);
 }
 
 int rp_mccfr_subgame_solve(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries, const rp_mccfr_subgame_args* args,
                            rp_mccfr_subgame_result* results, rp_mccfr_subgame_row* rows) {
-    int rc = msub_check_args("rp_mccfr_subgame_solve", args);
-    if (rc) return rc;
-    if (n == 0) return RP_OK;
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_solve: h is NULL");
-    if (!entries || !results) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_solve: entries or results is NULL");
-    if (!rows && args->rows_cap > 0) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_solve: rows is NULL with rows_cap > 0");
-    if ((rc = msub_check_game("rp_mccfr_subgame_solve", h))) return rc;
-    if ((rc = set_device(h))) return rc;
-    const size_t b_in = align16(n * sizeof(rp_mccfr_subgame_entry)), b_res = align16(n * sizeof(rp_mccfr_subgame_result)),
-                 b_rows = n * (size_t)args->rows_cap * sizeof(rp_mccfr_subgame_row);
-    uint8_t* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), b_in + b_res + b_rows + 16) != hipSuccess) {
-        (void)hipGetLastError();
-        return rp::fail(RP_ERR_CAPACITY, "rp_mccfr_subgame_solve: %zu bytes of staging do not fit", b_in + b_res + b_rows);
+    return msub_solve_host<false>("rp_mccfr_subgame_solve", h, n, entries, nullptr, args, results, rows);
+}
+
+int rp_mccfr_depth_solve_device(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries_dev, const uint8_t* origin_dev,
+                                const rp_mccfr_subgame_args* args, rp_mccfr_subgame_result* results_dev, rp_mccfr_subgame_row* rows_dev) {
+    return msub_solve_device<true>("rp_mccfr_depth_solve", h, n, entries_dev, origin_dev, args, results_dev, rows_dev);
+}
+
+int rp_mccfr_depth_solve(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries, const uint8_t* origin, const rp_mccfr_subgame_args* args,
+                         rp_mccfr_subgame_result* results, rp_mccfr_subgame_row* rows) {
+    return msub_solve_host<true>("rp_mccfr_depth_solve", h, n, entries, origin, args, results, rows);
+}
+
+// the frontier tables: the struct's own fields (no handle needed), the handle, then every chance state against the game table — all
+// on the host, before the device is touched
+int rp_mccfr_set_frontiers(rp_mccfr* h, const rp_mccfr_frontiers* f) {
+    const char* who = "rp_mccfr_set_frontiers";
+    if (f) {
+        if (f->leaves < 1 || f->leaves > 4) return rp::fail(RP_ERR_INVALID, "%s: leaves %u outside 1 .. 4", who, f->leaves);
+        if (f->reserved != 0) return rp::fail(RP_ERR_INVALID, "%s: reserved must be 0", who);
+        if (!f->depth) return rp::fail(RP_ERR_INVALID, "%s: depth is NULL", who);
+        if (!f->pick_info) return rp::fail(RP_ERR_INVALID, "%s: pick_info is NULL", who);
+        if (!f->payoff_ref) return rp::fail(RP_ERR_INVALID, "%s: payoff_ref is NULL", who);
+        if (f->n_matrices > 0 && !f->matrices) return rp::fail(RP_ERR_INVALID, "%s: matrices is NULL with n_matrices > 0", who);
+        if (f->n_pick > RP_MCCFR_SUBGAME_MAX_INFOS)
+            return rp::fail(RP_ERR_INVALID, "%s: n_pick %u above %u", who, f->n_pick, RP_MCCFR_SUBGAME_MAX_INFOS);
+        if (f->n_matrices >= 0x7fffffffu) return rp::fail(RP_ERR_INVALID, "%s: n_matrices %u cannot be named by a payoff_ref", who, f->n_matrices);
+        const size_t cells = (size_t)f->n_matrices * f->leaves * f->leaves;
+        for (size_t i = 0; i < cells; ++i)
+            if (!(f->matrices[i] >= -RP_F32_MAX && f->matrices[i] <= RP_F32_MAX))
+                return rp::fail(RP_ERR_INVALID, "%s: matrices[%zu][%zu][%zu] is not finite", who, i / (f->leaves * f->leaves),
+                                i / f->leaves % f->leaves, i % f->leaves);
     }
-    rp_mccfr_subgame_result* d_res = reinterpret_cast<rp_mccfr_subgame_result*>(d + b_in);
-    rp_mccfr_subgame_row* d_rows = args->rows_cap ? reinterpret_cast<rp_mccfr_subgame_row*>(d + b_in + b_res) : nullptr;
-    if (hipMemcpyAsync(d, entries, n * sizeof(rp_mccfr_subgame_entry), hipMemcpyHostToDevice, h->stream) != hipSuccess)
-        rc = rp::fail(RP_ERR_HIP, "rp_mccfr_subgame_solve: upload failed");
-    if (!rc) rc = msub_launch_solve(h, n, reinterpret_cast<const rp_mccfr_subgame_entry*>(d), args, d_res, d_rows);
-    if (!rc && (hipMemcpyAsync(results, d_res, n * sizeof(rp_mccfr_subgame_result), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-                (d_rows && hipMemcpyAsync(rows, d_rows, b_rows, hipMemcpyDeviceToHost, h->stream) != hipSuccess)))
-        rc = rp::fail(RP_ERR_HIP, "rp_mccfr_subgame_solve: download failed");
-    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = rp::fail(RP_ERR_HIP, "rp_mccfr_subgame_solve: a launch failed: %s", hipGetErrorString(hipGetLastError()));
-    (void)hipFree(d);
-    h->clk.drain();
-    return rc;
+    if (!h) return rp::fail(RP_ERR_INVALID, "%s: h is NULL", who);
+    const uint32_t NS = h->tbl.n_states;
+    if (f)
+        for (uint32_t s = 0; s < NS; ++s) {
+            if (h->states[s].turn != RP_TURN_CHANCE) continue;
+            if (f->depth[s] > 0 && f->pick_info[s] >= f->n_pick)
+                return rp::fail(RP_ERR_INVALID, "%s: pick_info[%u] = %u of a chance state with depth %u is not below n_pick %u", who, s,
+                                f->pick_info[s], (unsigned)f->depth[s], f->n_pick);
+            const uint32_t ref = f->payoff_ref[s];
+            const bool named = ref == RP_NO_INFO || ((ref & 0x80000000u) ? (ref & 0x7fffffffu) < f->n_matrices : ref < h->tbl.n_infos);
+            if (!named)
+                return rp::fail(RP_ERR_INVALID, "%s: payoff_ref[%u] = 0x%08x is neither RP_NO_INFO, an infoset nor a matrix below n_matrices %u", who,
+                                s, ref, f->n_matrices);
+        }
+    int rc = set_device(h);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));  // no solve still reads the tables this call replaces
+    if (h->d_front) HIP_TRY(hipFree(h->d_front));
+    h->d_front = nullptr;
+    h->fr = MsFrontiers{};
+    if (!f) return RP_OK;
+    const size_t b_ref = (size_t)NS * 4, b_mat = align16((size_t)f->n_matrices * f->leaves * f->leaves * 4), b_dep = align16(NS);
+    const size_t off_ref = align16(b_ref), off_mat = off_ref + align16(b_ref), off_dep = off_mat + b_mat;
+    uint8_t* d = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), off_dep + b_dep + 16));
+    h->d_front = d;
+    HIP_TRY(hipMemcpy(d, f->pick_info, b_ref, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d + off_ref, f->payoff_ref, b_ref, hipMemcpyHostToDevice));
+    if (f->n_matrices) HIP_TRY(hipMemcpy(d + off_mat, f->matrices, (size_t)f->n_matrices * f->leaves * f->leaves * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d + off_dep, f->depth, NS, hipMemcpyHostToDevice));
+    h->fr.pick_info = reinterpret_cast<const uint32_t*>(d);
+    h->fr.payoff_ref = reinterpret_cast<const uint32_t*>(d + off_ref);
+    h->fr.matrices = reinterpret_cast<const float*>(d + off_mat);
+    h->fr.depth = d + off_dep;
+    h->fr.n_pick = f->n_pick;
+    h->fr.n_matrices = f->n_matrices;
+    h->fr.D = f->leaves;
+    return RP_OK;
 }
 
 }  // extern "C"

@@ -15,8 +15,17 @@
 //                   from the handle's tables in place; there is no LDS copy of either (what that costs has not been measured).
 // A launch runs iterations [t_begin, t_end) of every solve; the last one harvests.  Every loop is bounded by a constant of this file
 // or a count the table check has validated; every index an entry supplies is checked before it is used.
+//
+// The kernel is instantiated twice.  FR = false is rp_mccfr_subgame_solve's and carries none of what follows (same registers, LDS and
+// code as before the frontiers existed).  FR = true is rp_mccfr_depth_solve's (SubGameSolver::with_origin, DepthSolver): a chance state
+// deeper than the solve's origin grows the Pick game — the frontier node keeps one Internal(k) child, that node D External(k, j)
+// leaves — so a node carries a kind beside its state (k and j are the slots of the Internal and the External node), a Pick infoset is
+// numbered n_infos + pick id in the index, the keys and the Decisions, and the matrix is read in place at the leaf.  64 + 4 bytes of
+// LDS more (16 608 B, still nine solves per CU), no scratch.
 #ifndef RP_MCCFR_SUBGAME_HPP
 #define RP_MCCFR_SUBGAME_HPP
+
+#include <type_traits>
 
 #include "mccfr_kernels.hpp"
 #include "policy_dist.hpp"
@@ -35,14 +44,14 @@ struct MsHead {
     uint32_t status, n_rows;
     unsigned long long nodes, infosets;
     uint32_t drawn[4];
-    uint32_t fallbacks, pad[5];
+    uint32_t fallbacks, frontiers, pad[4];
 };  // 64 bytes
 
 struct MsRegion {
     uint8_t* base;
     size_t stride;       // bytes per solve
-    uint32_t off_index;  // u16 [4][n_infos]
-    uint32_t off_keys;   // u32 [rows_alloc]: world * n_infos + info
+    uint32_t off_index;  // u16 [4][n_keys]: n_keys = n_infos, + n_pick with frontiers
+    uint32_t off_keys;   // u32 [rows_alloc]: world * n_keys + info
     uint32_t off_perm;   // u16 [rows_alloc]: the rows in exported order
     uint32_t off_rows;   // rp_encounter [rows_alloc][A]
     uint32_t rows_alloc;
@@ -58,6 +67,23 @@ struct MsParams {
     float prior;  // k of the warmstart; its regret (blueprint * k / epoch) is unobservable (PROFILE) and is not computed
     DistParams hp;
 };
+
+// the handle's frontier tables (rp_mccfr_set_frontiers), validated on the host against the game table
+struct MsFrontiers {
+    const uint8_t* depth;        // [n_states]
+    const uint32_t* pick_info;   // [n_states]
+    const uint32_t* payoff_ref;  // [n_states]
+    const float* matrices;       // [n_matrices][D][D]
+    uint32_t n_pick, n_matrices, D;
+};
+struct MsParamsDepth : MsParams {
+    MsFrontiers fr;
+    const uint8_t* origin;  // [n] or nullptr = RP_MCCFR_ORIGIN_ENTRY
+};
+template <bool FR>
+using MsParamsOf = typename std::conditional<FR, MsParamsDepth, MsParams>::type;
+
+enum : uint32_t { MS_GAME = 0, MS_FRONTIER = 1, MS_INTERNAL = 2, MS_EXTERNAL = 3 };  // a node's kind
 
 __device__ __forceinline__ void ms_sync() {  // orders this wavefront's LDS and region traffic
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -80,26 +106,44 @@ struct MsLds {
     float dec_pay[MS_LANES], dec_delta[MS_LANES][MS_A];
     uint32_t n_nodes, n_dec, max_depth, fail;
 };
+template <bool FR>
+struct MsLdsOf : MsLds {};
+template <>
+struct MsLdsOf<true> : MsLds {
+    uint8_t kind[MS_LANES];
+    uint32_t n_front;  // the frontier nodes of this tree
+};
 
-// one solve's view of the profile: the handle's tables under the region's local rows
+// one solve's view of the profile: the handle's tables under the region's local rows.  With frontiers `info` at or past n_infos is
+// the Pick infoset info - n_infos, which the blueprint does not hold: DepthView's constants answer for an absent edge.
+template <bool FR>
 struct MsProfile {
     DevTables t;
     uint32_t A, n_infos;
     uint16_t* index;
     rp_encounter* rows;
+    uint32_t n_keys;    // the index's stride: n_infos (+ n_pick)
+    uint32_t row_A;     // the slots of a local row: max(A, D), a Pick row has D
+    float pick_weight;  // 1.0f / (float)D
 
-    __device__ __forceinline__ uint32_t row(uint32_t world, uint32_t info) const { return index[(size_t)world * n_infos + info]; }
+    __device__ __forceinline__ uint32_t row_slots() const { return FR ? row_A : A; }
+
+    __device__ __forceinline__ uint32_t row(uint32_t world, uint32_t info) const { return index[(size_t)world * (FR ? n_keys : n_infos) + info]; }
     __device__ __forceinline__ float cum_regret(uint32_t r, uint32_t info, uint32_t a) const {
-        return r != MS_NO_ROW ? rows[(size_t)r * A + a].regret : rp_maxf(t.regret[(size_t)info * A + a], RP_EPSILON);
+        if (FR && r == MS_NO_ROW && info >= n_infos) return RP_EPSILON;
+        return r != MS_NO_ROW ? rows[(size_t)r * row_slots() + a].regret : rp_maxf(t.regret[(size_t)info * A + a], RP_EPSILON);
     }
     __device__ __forceinline__ float cum_weight(uint32_t r, uint32_t info, uint32_t a) const {
-        return r != MS_NO_ROW ? rows[(size_t)r * A + a].weight : rp_maxf(t.weight[(size_t)info * A + a], RP_EPSILON);
+        if (FR && r == MS_NO_ROW && info >= n_infos) return pick_weight;
+        return r != MS_NO_ROW ? rows[(size_t)r * row_slots() + a].weight : rp_maxf(t.weight[(size_t)info * A + a], RP_EPSILON);
     }
     __device__ __forceinline__ float cum_payoff(uint32_t r, uint32_t info, uint32_t a) const {
-        return r != MS_NO_ROW ? rows[(size_t)r * A + a].payoff : t.payoff[(size_t)info * A + a];
+        if (FR && r == MS_NO_ROW && info >= n_infos) return 0.0f;
+        return r != MS_NO_ROW ? rows[(size_t)r * row_slots() + a].payoff : t.payoff[(size_t)info * A + a];
     }
     __device__ __forceinline__ uint32_t cum_visits(uint32_t r, uint32_t info, uint32_t a) const {
-        return r != MS_NO_ROW ? rows[(size_t)r * A + a].visits : t.visits[(size_t)info * A + a];
+        if (FR && r == MS_NO_ROW && info >= n_infos) return 0u;
+        return r != MS_NO_ROW ? rows[(size_t)r * row_slots() + a].visits : t.visits[(size_t)info * A + a];
     }
     // iterated_distribution of regret() / sampling_distribution of weight(): out[a], a < na
     __device__ __forceinline__ void iterated(uint32_t r, uint32_t info, uint32_t na, float* out) const {
@@ -149,18 +193,39 @@ __device__ __forceinline__ uint32_t ms_draw_world(const rp_mccfr_subgame_entry& 
     return last;
 }
 
-// lane 0: TreeBuilder with ExternalSampling; false when the tree outgrows MS_NODES
-__device__ inline bool ms_build(MsLds& L, const DevGame& g, const MsProfile& P, const MsParams& p, uint32_t entry_state, uint32_t world, uint32_t walker,
-                                uint64_t tree_hash) {
+// the weighted draw of DRAWS over q[0 .. nch) with the node's hash; q is kept for the node's sr
+template <bool FR>
+__device__ __forceinline__ uint32_t ms_weighted_pick(MsLdsOf<FR>& L, uint32_t idx, const float* q, uint32_t nch, uint64_t tree_hash) {
+    float total = 0.0f;
+    for (uint32_t a = 0; a < nch; ++a) {
+        L.q[idx][a] = q[a];
+        total += rp_maxf(q[a], RP_EPSILON);
+    }
+    const float u = rp_u01(rp_node_hash_key(tree_hash, idx)) * total;
+    float cum = 0.0f;
+    uint32_t pick = 0;
+    for (uint32_t a = 0; a + 1 < nch; ++a) {
+        cum += rp_maxf(q[a], RP_EPSILON);
+        if (pick == a && cum <= u) pick = a + 1;
+    }
+    return pick;
+}
+
+// lane 0: TreeBuilder with ExternalSampling; RP_MSUB_OK, RP_MSUB_TREE when the tree outgrows MS_NODES, with frontiers RP_MSUB_FRONTIER
+// too, and a node under a frontier keeps the frontier's state (the Internal node and its External leaves).
+template <bool FR>
+__device__ inline uint32_t ms_build(MsLdsOf<FR>& L, const DevGame& g, const MsProfile<FR>& P, const MsParamsOf<FR>& p, uint32_t entry_state,
+                                    uint32_t world, uint32_t walker, uint64_t tree_hash, uint32_t origin, uint32_t external) {
     uint32_t n = 0, sp = 0, max_depth = 0;
     L.st_state[0] = entry_state;
     L.st_parent[0] = (uint8_t)MS_NONE;
     L.st_slot[0] = 0;
     sp = 1;
+    if constexpr (FR) L.n_front = 0;
     while (sp > 0) {
         sp -= 1;
         const uint32_t state = L.st_state[sp], parent = L.st_parent[sp], slot = L.st_slot[sp];
-        if (n >= MS_NODES) return false;
+        if (n >= MS_NODES) return RP_MSUB_TREE;
         const uint32_t idx = n++;
         const uint4 rec = g.states[state];
         const uint32_t turn = rec.x & 255u, nch = (rec.x >> 8) & 255u;
@@ -175,6 +240,53 @@ __device__ inline bool ms_build(MsLds& L, const DevGame& g, const MsProfile& P, 
         L.depth[idx] = (uint8_t)depth;
         for (uint32_t a = 0; a < MS_A; ++a) L.kid[idx][a] = (uint8_t)MS_NONE;
         if (parent != MS_NONE) L.kid[parent][slot] = (uint8_t)idx;
+        if constexpr (FR) {
+            const MsFrontiers& f = p.fr;
+            const uint32_t above = parent == MS_NONE ? (uint32_t)MS_GAME : (uint32_t)L.kind[parent];
+            if (above == MS_INTERNAL) {  // External(k, j): k the Internal node's slot, j this node's
+                L.kind[idx] = (uint8_t)MS_EXTERNAL;
+                L.turn[idx] = (uint8_t)RP_TURN_TERMINAL;
+                L.nch[idx] = 0;
+                continue;
+            }
+            if (above == MS_FRONTIER) {  // Internal(k): the seat `external` picks j, by the Pick infoset of the frontier's state
+                const uint32_t D = f.D, info = P.n_infos + f.pick_info[state];  // checked when the frontier was grown
+                L.kind[idx] = (uint8_t)MS_INTERNAL;
+                L.turn[idx] = (uint8_t)external;
+                L.info[idx] = info;
+                L.nch[idx] = (uint8_t)D;
+                uint32_t first = 0, count = D;
+                if (external != walker) {
+                    float q[MS_A];
+                    P.sampling(p.hp, P.row(world, info), info, D, q);
+                    first = ms_weighted_pick<FR>(L, idx, q, D, tree_hash);
+                    count = 1;
+                }
+                if (n + sp + count > MS_NODES) return RP_MSUB_TREE;
+                for (uint32_t k = first; k < first + count; ++k) {
+                    L.st_state[sp] = state;
+                    L.st_parent[sp] = (uint8_t)idx;
+                    L.st_slot[sp] = (uint8_t)k;
+                    sp += 1;
+                }
+                continue;
+            }
+            L.kind[idx] = (uint8_t)MS_GAME;
+            if (turn == RP_TURN_CHANCE && (uint32_t)f.depth[state] > origin) {  // DepthGame::at_frontier
+                const uint32_t ref = f.payoff_ref[state];
+                const bool named = ref == RP_NO_INFO || ((ref & 0x80000000u) ? (ref & 0x7fffffffu) < f.n_matrices : ref < P.n_infos);
+                if (f.pick_info[state] >= f.n_pick || !named || f.D < 1 || f.D > 4) return RP_MSUB_FRONTIER;
+                L.kind[idx] = (uint8_t)MS_FRONTIER;
+                L.nch[idx] = 0;
+                L.n_front += 1;
+                if (n + sp + 1 > MS_NODES) return RP_MSUB_TREE;
+                L.st_state[sp] = state;
+                L.st_parent[sp] = (uint8_t)idx;
+                L.st_slot[sp] = (uint8_t)rp_pick_uniform(rp_node_hash_key(tree_hash, idx), f.D);
+                sp += 1;
+                continue;
+            }
+        }
         // rp_game_table_check (games.cpp) refuses a state that is not terminal and has no child, or more than RP_MAX_ACTIONS: the two
         // conditions on nch only keep the loops below bounded for a table that was not checked; such a node would read as a leaf of value 0
         const bool decision = turn < 2u && nch > 0 && nch <= MS_A;
@@ -184,22 +296,10 @@ __device__ inline bool ms_build(MsLds& L, const DevGame& g, const MsProfile& P, 
         if (turn != walker) {  // the weighted draw of DRAWS
             float q[MS_A];
             P.sampling(p.hp, P.row(world, rec.y), rec.y, nch, q);
-            float total = 0.0f;
-            for (uint32_t a = 0; a < nch; ++a) {
-                L.q[idx][a] = q[a];
-                total += rp_maxf(q[a], RP_EPSILON);
-            }
-            const float u = rp_u01(rp_node_hash_key(tree_hash, idx)) * total;
-            float cum = 0.0f;
-            uint32_t pick = 0;
-            for (uint32_t a = 0; a + 1 < nch; ++a) {
-                cum += rp_maxf(q[a], RP_EPSILON);
-                if (pick == a && cum <= u) pick = a + 1;
-            }
-            first = pick;
+            first = ms_weighted_pick<FR>(L, idx, q, nch, tree_hash);
             count = 1;
         }
-        if (n + sp + count > MS_NODES) return false;  // every pending branch becomes a node
+        if (n + sp + count > MS_NODES) return RP_MSUB_TREE;  // every pending branch becomes a node
         for (uint32_t k = first; k < first + count; ++k) {
             L.st_state[sp] = g.children[rec.z + k];
             L.st_parent[sp] = (uint8_t)idx;
@@ -209,12 +309,30 @@ __device__ inline bool ms_build(MsLds& L, const DevGame& g, const MsProfile& P, 
     }
     L.n_nodes = n;
     L.max_depth = max_depth;
-    return true;
+    return RP_MSUB_OK;
 }
 
 // CfrNash::terminal_value of a leaf for hero
-__device__ __forceinline__ float ms_leaf_value(const MsLds& L, const DevGame& g, const MsProfile& P, const MsParams& p, uint32_t node, uint32_t world,
-                                               uint32_t hero) {
+template <bool FR>
+__device__ __forceinline__ float ms_leaf_value(const MsLdsOf<FR>& L, const DevGame& g, const MsProfile<FR>& P, const MsParamsOf<FR>& p, uint32_t node,
+                                               uint32_t world, uint32_t hero, uint32_t external) {
+    if constexpr (FR) {
+        if (L.kind[node] == MS_EXTERNAL) {  // DepthGame::payoff at External(k, j): payoffs[k][j] to `internal`, negated to the other seat
+            const MsFrontiers& f = p.fr;
+            const uint32_t par = L.parent[node], j = L.slot[node], k = par < MS_LANES ? (uint32_t)L.slot[par] : 0u;
+            const uint32_t ref = f.payoff_ref[L.state[node]];  // checked when the frontier was grown
+            float v = 0.0f;  // RP_NO_INFO: Payoffs::uniform(0.0)
+            if (ref != RP_NO_INFO) {
+                if (ref & 0x80000000u) {
+                    const uint32_t m = ref & 0x7fffffffu;
+                    if (m < f.n_matrices && k < f.D && j < f.D) v = f.matrices[((size_t)m * f.D + k) * f.D + j];
+                } else if (ref < P.n_infos) {
+                    v = P.t.payoff[(size_t)ref * P.A];  // the blueprint's cum_payoff(info, slot 0), never a local row
+                }
+            }
+            return hero == 1u - external ? v : -v;
+        }
+    }
     const uint32_t turn = L.turn[node];
     if (turn == RP_TURN_TERMINAL) return L.off[node] < p.n_terminals ? g.payoffs[(size_t)L.off[node] * 2 + hero] : 0.0f;
     const uint32_t par = L.parent[node];
@@ -223,16 +341,28 @@ __device__ __forceinline__ float ms_leaf_value(const MsLds& L, const DevGame& g,
     return P.cum_payoff(P.row(world, info), info, 0);
 }
 
-__global__ __launch_bounds__(MS_LANES) void k_mccfr_subgame_solve(DevGame g, DevTables tab, MsRegion R, MsParams p) {
-    __shared__ MsLds L;
+template <bool FR>
+__global__ __launch_bounds__(MS_LANES) void k_mccfr_subgame_solve(DevGame g, DevTables tab, MsRegion R, MsParamsOf<FR> p) {
+    __shared__ MsLdsOf<FR> L;
     const uint32_t lane = threadIdx.x, solve = blockIdx.x;
     if (solve >= p.n) return;
     uint8_t* reg = R.base + (size_t)solve * R.stride;
     MsHead* head = reinterpret_cast<MsHead*>(reg);
-    MsProfile P{tab, g.A, g.n_infos, reinterpret_cast<uint16_t*>(reg + R.off_index), reinterpret_cast<rp_encounter*>(reg + R.off_rows)};
+    MsProfile<FR> P{tab, g.A, g.n_infos, reinterpret_cast<uint16_t*>(reg + R.off_index), reinterpret_cast<rp_encounter*>(reg + R.off_rows)};
     uint32_t* keys = reinterpret_cast<uint32_t*>(reg + R.off_keys);
     uint16_t* perm = reinterpret_cast<uint16_t*>(reg + R.off_perm);
     const uint32_t A = g.A, NI = g.n_infos;
+    uint32_t NK = NI, PD = 0, RA = A;  // the keys of one world (infosets, then Pick infosets), the Pick game's D, a local row's slots
+    if constexpr (FR) {
+        PD = p.fr.D;
+        NK = NI + p.fr.n_pick;
+        RA = A > PD ? A : PD;
+        P.n_keys = NK;
+        P.row_A = RA;
+        P.pick_weight = 1.0f / (float)PD;
+    }
+    // the slots of a key: an infoset's actions, D at a Pick infoset
+    const auto actions_of = [&](uint32_t info) -> uint32_t { return FR && info >= NI ? PD : (uint32_t)g.info_actions[info]; };
 
     {  // the entry, once per launch
         const uint32_t* src = reinterpret_cast<const uint32_t*>(p.entries + solve);
@@ -240,7 +370,7 @@ __global__ __launch_bounds__(MS_LANES) void k_mccfr_subgame_solve(DevGame g, Dev
         for (uint32_t i = lane; i < sizeof(rp_mccfr_subgame_entry) / 4; i += MS_LANES) dst[i] = src[i];
     }
     if (p.t_begin == 0) {  // a new solve: an empty local profile
-        for (uint32_t i = lane; i < 4 * NI; i += MS_LANES) P.index[i] = (uint16_t)MS_NO_ROW;
+        for (uint32_t i = lane; i < 4 * NK; i += MS_LANES) P.index[i] = (uint16_t)MS_NO_ROW;
         if (lane < sizeof(MsHead) / 4) reinterpret_cast<uint32_t*>(head)[lane] = 0u;
     }
     ms_sync();
@@ -253,6 +383,12 @@ __global__ __launch_bounds__(MS_LANES) void k_mccfr_subgame_solve(DevGame g, Dev
     if (status == RP_MSUB_OK)
         for (uint32_t s = 0; s < 16; ++s) members_empty = members_empty && E.world_of[s] >= E.n_worlds;
     uint32_t entry_state = 0;
+    uint32_t origin = RP_MCCFR_ORIGIN_NONE, frontiers = 0;
+    if constexpr (FR) {
+        frontiers = head->frontiers;
+        origin = p.origin ? (uint32_t)p.origin[solve] : (uint32_t)RP_MCCFR_ORIGIN_ENTRY;
+        if (origin == RP_MCCFR_ORIGIN_ENTRY) origin = status == RP_MSUB_OK ? (uint32_t)p.fr.depth[E.observed] : (uint32_t)RP_MCCFR_ORIGIN_NONE;
+    }
 
     for (uint32_t t = p.t_begin; t < p.t_end && status == RP_MSUB_OK; ++t) {
         const uint32_t walker = t & 1u;
@@ -269,15 +405,17 @@ __global__ __launch_bounds__(MS_LANES) void k_mccfr_subgame_solve(DevGame g, Dev
         if (lane == 0) {
             const uint64_t tree_hash = rp_node_hash_tree(rp_node_hash_step(p.seed, 2), id * RP_MCCFR_SUBGAME_MAX_ITERATIONS + t);
             L.n_dec = 0;
-            L.fail = ms_build(L, g, P, p, entry_state, world, walker, tree_hash) ? 0u : 1u;
+            const uint32_t built = ms_build<FR>(L, g, P, p, entry_state, world, walker, tree_hash, origin, E.external);
+            L.fail = FR ? built : (built != RP_MSUB_OK ? 1u : 0u);
         }
         ms_sync();
         if (L.fail) {
-            status = RP_MSUB_TREE;
+            status = FR ? L.fail : (uint32_t)RP_MSUB_TREE;
             break;
         }
         const uint32_t N = L.n_nodes, max_depth = L.max_depth;
         nodes += N;
+        if constexpr (FR) frontiers += L.n_front;
         // pol = iterated_distribution (= regret(a) / rd, the same operations) of every decision node
         if (lane < N && L.nch[lane] > 0) {
             float out[MS_A];
@@ -301,8 +439,15 @@ __global__ __launch_bounds__(MS_LANES) void k_mccfr_subgame_solve(DevGame g, Dev
                         L.sr[lane] = 1.0f;
                         L.in[lane] = 1;
                     } else if (L.in[par]) {
-                        L.rr[lane] = L.rr[par] * L.pol[par][s];
-                        L.sr[lane] = L.turn[par] != walker ? L.sr[par] * L.q[par][s] : L.sr[par];
+                        bool chance = false;  // a frontier node is the chance node it was grown as: neither rr nor sr moves
+                        if constexpr (FR) chance = L.kind[par] == MS_FRONTIER;
+                        if (chance) {
+                            L.rr[lane] = L.rr[par];
+                            L.sr[lane] = L.sr[par];
+                        } else {
+                            L.rr[lane] = L.rr[par] * L.pol[par][s];
+                            L.sr[lane] = L.turn[par] != walker ? L.sr[par] * L.q[par][s] : L.sr[par];
+                        }
                         L.in[lane] = 1;
                     }
                 }
@@ -311,8 +456,10 @@ __global__ __launch_bounds__(MS_LANES) void k_mccfr_subgame_solve(DevGame g, Dev
             for (uint32_t d = max_depth; d > d0; --d) {  // recursed_value, the deepest level first
                 if (mine && L.depth[lane] == d && L.in[lane]) {
                     float v;
-                    if (L.nch[lane] == 0) {
-                        v = (L.rr[lane] / L.sr[lane]) * ms_leaf_value(L, g, P, p, lane, world, walker);
+                    bool leaf = L.nch[lane] == 0;
+                    if constexpr (FR) leaf = leaf && L.kind[lane] != MS_FRONTIER;  // a frontier node folds its one child
+                    if (leaf) {
+                        v = (L.rr[lane] / L.sr[lane]) * ms_leaf_value<FR>(L, g, P, p, lane, world, walker, E.external);
                     } else {
                         v = 0.0f;
                         for (uint32_t a = 0; a < MS_A; ++a)
@@ -325,7 +472,9 @@ __global__ __launch_bounds__(MS_LANES) void k_mccfr_subgame_solve(DevGame g, Dev
             if (lane == 0) {
                 float cf = 1.0f, sm = 1.0f;  // ancestor_reach, nearest first
                 for (uint32_t child = root, par = L.parent[root], s = 0; par != MS_NONE && s < MS_NODES; ++s) {
-                    if (L.turn[par] != walker) {
+                    bool sampled = L.turn[par] != walker;
+                    if constexpr (FR) sampled = sampled && L.kind[par] != MS_FRONTIER;
+                    if (sampled) {
                         cf = cf * L.pol[par][L.slot[child]];
                         sm = sm * L.q[par][L.slot[child]];
                     }
@@ -368,8 +517,8 @@ __global__ __launch_bounds__(MS_LANES) void k_mccfr_subgame_solve(DevGame g, Dev
                         break;
                     }
                     r = r_count++;
-                    P.index[(size_t)world * NI + info] = (uint16_t)r;
-                    keys[r] = world * NI + info;
+                    P.index[(size_t)world * NK + info] = (uint16_t)r;
+                    keys[r] = world * NK + info;
                     L.dec_new[k] = 1;
                 }
                 L.dec_row[k] = (uint16_t)r;
@@ -385,16 +534,19 @@ __global__ __launch_bounds__(MS_LANES) void k_mccfr_subgame_solve(DevGame g, Dev
         const uint32_t n_dec = L.n_dec;
         infosets += n_dec;
         for (uint32_t pair = lane; pair < n_dec * MS_A; pair += MS_LANES) {
-            const uint32_t k = pair / MS_A, a = pair % MS_A, info = L.dec_info[k], na = g.info_actions[info];
-            if (a >= A) continue;
-            rp_encounter* cell = P.rows + (size_t)L.dec_row[k] * A + a;
+            const uint32_t k = pair / MS_A, a = pair % MS_A, info = L.dec_info[k], na = actions_of(info);
+            if (a >= RA) continue;
+            rp_encounter* cell = P.rows + (size_t)L.dec_row[k] * RA + a;
             if (a >= na) {
                 if (L.dec_new[k]) *cell = rp_encounter{0.0f, 0.0f, 0.0f, 0u};
                 continue;
             }
             rp_encounter e = *cell;
             float cum = e.regret;
-            if (L.dec_new[k]) {  // warmstart; update_regret has read cum_regret before the edge existed
+            if (FR && L.dec_new[k] && info >= NI) {  // a Pick edge: DepthView's absent regret, then Encounter::default()
+                cum = RP_EPSILON;
+                e = rp_encounter{0.0f, 0.0f, 0.0f, 0u};
+            } else if (L.dec_new[k]) {  // warmstart; update_regret has read cum_regret before the edge existed
                 float sum = 0.0f;
                 for (uint32_t b = 0; b < na; ++b) sum += rp_maxf(tab.weight[(size_t)info * A + b], RP_EPSILON);
                 const float avg = rp_maxf(tab.weight[(size_t)info * A + a], RP_EPSILON) / sum;
@@ -420,6 +572,7 @@ __global__ __launch_bounds__(MS_LANES) void k_mccfr_subgame_solve(DevGame g, Dev
             head->infosets = infosets;
             head->fallbacks = fallbacks;
             for (uint32_t w = 0; w < 4; ++w) head->drawn[w] = drawn[w];
+            if constexpr (FR) head->frontiers = frontiers;
         }
         return;
     }
@@ -460,7 +613,7 @@ __global__ __launch_bounds__(MS_LANES) void k_mccfr_subgame_solve(DevGame g, Dev
         return;
     }
     const uint32_t W = E.n_worlds;
-    // the rows in (world, info) order: keys are distinct, a row's rank is the number of smaller keys
+    // the rows in (world, info) order — (world, kind, info) with frontiers, a Pick infoset's key lying past the infosets': keys are distinct, a row's rank is the number of smaller keys
     for (uint32_t i = lane; i < n_rows; i += MS_LANES) {
         const uint32_t key = keys[i];
         uint32_t rank = 0;
@@ -470,12 +623,17 @@ __global__ __launch_bounds__(MS_LANES) void k_mccfr_subgame_solve(DevGame g, Dev
     ms_sync();
     if (out_rows)
         for (uint32_t i = lane; i < n_rows && i < p.rows_cap; i += MS_LANES) {
-            const uint32_t r = perm[i], key = keys[r], info = key % NI, na = g.info_actions[info];
+            const uint32_t r = perm[i], key = keys[r], info = key % NK, na = actions_of(info);
             rp_mccfr_subgame_row* o = out_rows + i;
-            o->world = (uint8_t)(key / NI);
+            o->world = (uint8_t)(key / NK);
             o->n_actions = (uint8_t)na;
             o->info = info;
-            for (uint32_t a = 0; a < na && a < A; ++a) o->enc[a] = P.rows[(size_t)r * A + a];
+            if constexpr (FR)
+                if (info >= NI) {  // a Pick row: its kind and the pick id
+                    o->kind = 1;
+                    o->info = info - NI;
+                }
+            for (uint32_t a = 0; a < na && a < RA; ++a) o->enc[a] = P.rows[(size_t)r * RA + a];
         }
     if (lane < hna) {
         float refined = 0.0f;
@@ -498,8 +656,8 @@ __global__ __launch_bounds__(MS_LANES) void k_mccfr_subgame_solve(DevGame g, Dev
             for (uint32_t w = 0; w < W; ++w) regret += rp_maxf(P.cum_regret(P.row(w, hinfo), hinfo, E.harvest_order[k]), 0.0f);
         float sum = 0.0f;
         for (uint32_t i = 0; i < n_rows; ++i) {
-            const uint32_t r = perm[i], na = g.info_actions[keys[r] % NI];
-            for (uint32_t a = 0; a < na && a < A; ++a) sum += rp_maxf(P.rows[(size_t)r * A + a].regret, 0.0f);
+            const uint32_t r = perm[i], na = actions_of(keys[r] % NK);
+            for (uint32_t a = 0; a < na && a < RA; ++a) sum += rp_maxf(P.rows[(size_t)r * RA + a].regret, 0.0f);
         }
         out->info = hinfo;
         out->n_actions = (uint8_t)hna;
@@ -512,6 +670,7 @@ __global__ __launch_bounds__(MS_LANES) void k_mccfr_subgame_solve(DevGame g, Dev
         out->infosets = infosets;
         for (uint32_t w = 0; w < 4; ++w) out->drawn[w] = drawn[w];
         out->fallbacks = fallbacks;
+        if constexpr (FR) out->frontiers = frontiers;
     }
 }
 

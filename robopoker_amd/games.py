@@ -144,6 +144,41 @@ def subgame_entry(game: Game, holes, prefix=(), external=1, reach=False, n_world
     return prior, entry
 
 
+def frontiers(game: Game) -> dict:
+    """rp_game_frontiers: the reference's frontier tables of a built-in game, as Solver.set_frontiers takes them —
+    {"depth" u8 [n_states], "pick_info" u32 [n_states], "payoff_ref" u32 [n_states], "n_pick"}"""
+    import numpy as np
+
+    n = game.table.n_states
+    out = {"depth": np.zeros(n, np.uint8), "pick_info": np.zeros(n, np.uint32), "payoff_ref": np.zeros(n, np.uint32)}
+    n_pick = C.c_uint32()
+    _lib.check(_lib.load().rp_game_frontiers(game._h, out["depth"].ctypes.data, out["pick_info"].ctypes.data, out["payoff_ref"].ctypes.data,
+                                             C.byref(n_pick)))
+    out["n_pick"] = n_pick.value
+    return out
+
+
+def depth_entry(game: Game, holes, prefix=(), internal=0):
+    """-> entry record (mccfr.SUBGAME_ENTRY_DTYPE, one element) of ``DepthSolver::new(source, prefix, internal, entry)`` at the state
+    after `prefix`: no candidates, one world of weight 1, external = 1 - internal.  Solver.depth_solve(entry) (origin None: the
+    entry state's depth) is that solver's steps and harvest."""
+    import numpy as np
+
+    from .mccfr import SUBGAME_ENTRY_DTYPE
+
+    if game.kind not in _CARDS:
+        raise ValueError("depth_entry knows the built-in card games only")
+    entry = np.zeros(1, SUBGAME_ENTRY_DTYPE)
+    e = entry[0]
+    e["observed"], e["external"], e["n_candidates"], e["n_worlds"] = play(game, tuple(holes), prefix), 1 - internal, 0, 1
+    e["weights"] = (1, 0, 0, 0)
+    e["world_of"][:] = _lib.RP_WORLD_NONE
+    e["harvest_info"] = _lib.RP_NO_INFO
+    st = game.table.states[int(e["observed"])]
+    e["harvest_order"][:] = harvest_order(game, st.info) if st.turn < 2 else list(range(16))
+    return entry
+
+
 def fill_belief(entries, belief):
     """copies Solver.subgame_belief's answer (or the model's) into the entries, element by element"""
     entries["world_of"][...] = belief["world_of"]

@@ -23,8 +23,8 @@ SUBGAME_ENTRY_DTYPE = np.dtype([("observed", "<u4"), ("harvest_info", "<u4"), ("
                                 ("n_candidates", "u1"), ("n_worlds", "u1"), ("pad", "u1")])
 SUBGAME_RESULT_DTYPE = np.dtype([("info", "<u4"), ("n_actions", "u1"), ("status", "u1"), ("pad", "u1", 2), ("refined", "<f4", 16),
                                  ("visits", "<u4", 16), ("regret", "<f4"), ("sum_regret", "<f4"), ("iterations", "<u4"), ("n_rows", "<u4"),
-                                 ("nodes", "<u8"), ("infosets", "<u8"), ("drawn", "<u4", 4), ("fallbacks", "<u4"), ("pad2", "<u4")])
-SUBGAME_ROW_DTYPE = np.dtype([("world", "u1"), ("n_actions", "u1"), ("pad", "u1", 2), ("info", "<u4"), ("enc", ENC_DTYPE, 16)])
+                                 ("nodes", "<u8"), ("infosets", "<u8"), ("drawn", "<u4", 4), ("fallbacks", "<u4"), ("frontiers", "<u4")])
+SUBGAME_ROW_DTYPE = np.dtype([("world", "u1"), ("n_actions", "u1"), ("kind", "u1"), ("pad", "u1"), ("info", "<u4"), ("enc", ENC_DTYPE, 16)])
 assert (SUBGAME_PRIOR_DTYPE.itemsize, SUBGAME_ENTRY_DTYPE.itemsize, SUBGAME_RESULT_DTYPE.itemsize, SUBGAME_ROW_DTYPE.itemsize) == (104, 140, 192, 264)
 
 
@@ -204,6 +204,60 @@ class Solver:
         """the same, every array in device memory (``args`` as subgame_args); queued on the solver's stream, no host synchronisation"""
         a = self.subgame_args(**args)
         _lib.check(self._lib.rp_mccfr_subgame_solve_device(self._h, n, entries_ptr, C.byref(a), results_ptr, rows_ptr or None))
+
+    # ---- the depth-limited re-solve (SubGameSolver::with_origin, DepthSolver) over the same records; read-only on the solver ------------
+    def set_frontiers(self, depth=None, pick_info=None, payoff_ref=None, matrices=None, leaves=4, n_pick=None):
+        """rp_mccfr_set_frontiers: per state ``depth`` (u8), ``pick_info`` and ``payoff_ref`` (u32; games.frontiers answers the three
+        for a built-in game), ``matrices`` [m, leaves, leaves] f32 named by payoff_ref 0x80000000 | m.  ``n_pick`` defaults to
+        the largest pick id + 1.  ``depth=None`` clears."""
+        if depth is None:
+            _lib.check(self._lib.rp_mccfr_set_frontiers(self._h, None))
+            return
+        depth = np.ascontiguousarray(depth, np.uint8)
+        pick_info, payoff_ref = np.ascontiguousarray(pick_info, np.uint32), np.ascontiguousarray(payoff_ref, np.uint32)
+        n = self.game.table.n_states
+        if not depth.shape == pick_info.shape == payoff_ref.shape == (n,):
+            raise ValueError(f"depth, pick_info and payoff_ref hold one element per state ({n})")
+        mats = np.zeros((0, leaves, leaves), np.float32) if matrices is None else np.ascontiguousarray(matrices, np.float32)
+        if mats.ndim != 3 or mats.shape[1:] != (leaves, leaves):
+            raise ValueError("matrices is [m, leaves, leaves]")
+        if n_pick is None:
+            picks = pick_info[pick_info != _lib.RP_NO_INFO]
+            n_pick = int(picks.max()) + 1 if picks.size else 0
+        f = _lib.MccfrFrontiers(depth.ctypes.data, pick_info.ctypes.data, payoff_ref.ctypes.data, mats.ctypes.data if len(mats) else None,
+                                n_pick, len(mats), leaves, 0)
+        _lib.check(self._lib.rp_mccfr_set_frontiers(self._h, C.byref(f)))
+
+    @staticmethod
+    def _origin(origin, n):
+        """-> uint8[n] or None (the whole batch at RP_MCCFR_ORIGIN_ENTRY); a None among per-entry origins reads as ORIGIN_ENTRY"""
+        if origin is None:
+            return None
+        if np.isscalar(origin):
+            origin = [origin] * n
+        o = np.array([_lib.RP_MCCFR_ORIGIN_ENTRY if x is None else x for x in origin], np.uint8)
+        if o.shape != (n,):
+            raise ValueError(f"{n} entries, {o.size} origins")
+        return o
+
+    def depth_solve(self, entries: np.ndarray, origin=None, iterations=1, prior=float(1 << 14), seed=0, first_id=0, rows_cap=0):
+        """``SubGameSolver::with_origin(origin)`` x ``iterations`` and its harvest, one solve per entry (SUBGAME_ENTRY_DTYPE;
+        games.depth_entry builds the ``DepthSolver`` form).  ``origin``: None = every entry at its own depth (ORIGIN_ENTRY), a number
+        or one per entry (0 .. 253, ORIGIN_ENTRY, ORIGIN_NONE).  -> (results [n] SUBGAME_RESULT_DTYPE, rows [n, rows_cap]
+        SUBGAME_ROW_DTYPE sorted by (world, kind, info)).  Needs set_frontiers."""
+        buf = np.ascontiguousarray(entries, dtype=SUBGAME_ENTRY_DTYPE).reshape(-1)
+        n = buf.size
+        o = self._origin(origin, n)
+        results, rows = np.zeros(n, SUBGAME_RESULT_DTYPE), np.zeros((n, rows_cap), SUBGAME_ROW_DTYPE)
+        a = self.subgame_args(iterations, prior, seed, first_id, rows_cap)
+        _lib.check(self._lib.rp_mccfr_depth_solve(self._h, n, buf.ctypes.data, o.ctypes.data if o is not None else None, C.byref(a),
+                                                  results.ctypes.data, rows.ctypes.data if rows_cap else None))
+        return results, rows
+
+    def depth_solve_device(self, n: int, entries_ptr: int, results_ptr: int, rows_ptr: int = 0, origin_ptr: int = 0, **args):
+        """the same, every array in device memory (``args`` as subgame_args); queued on the solver's stream, no host synchronisation"""
+        a = self.subgame_args(**args)
+        _lib.check(self._lib.rp_mccfr_depth_solve_device(self._h, n, entries_ptr, origin_ptr or None, C.byref(a), results_ptr, rows_ptr or None))
 
     # ---- knobs ----------------------------------------------------------------------------------
     def set_batch(self, batch: int):
