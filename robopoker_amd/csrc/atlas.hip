@@ -30,7 +30,7 @@ const double N_OBSERVATIONS[4] = {1326.0, 25989600.0, 305377800.0, 2809475760.0}
 const double N_ISOMORPHISMS[4] = {169.0, 1286792.0, 13960050.0, 123156254.0};       // street.rs:129-136
 const double N_CHILDREN[4] = {19600.0, 47.0, 46.0, 0.0};                            // street.rs:120-127
 
-// device allocations of one call that free themselves
+// sort_rows' temporaries: device allocations that free themselves
 struct Arena {
     std::vector<void*> ptrs;
     ~Arena() {
@@ -42,17 +42,6 @@ struct Arena {
         const hipError_t e = hipMalloc(&p, count * sizeof(T) ? count * sizeof(T) : 1);
         if (e == hipSuccess) ptrs.push_back(p);
         *out = static_cast<T*>(p);
-        return e;
-    }
-    // a device copy of a host array (NULL stays NULL)
-    template <class T>
-    hipError_t upload(const T** out, const T* host, size_t count) {
-        *out = nullptr;
-        if (!host) return hipSuccess;
-        T* d = nullptr;
-        hipError_t e = alloc(&d, count);
-        if (e == hipSuccess) e = hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice);
-        *out = d;
         return e;
     }
 };
@@ -161,13 +150,12 @@ int derive(rp_atlas* h, const float* next_equity) {
     return RP_OK;
 }
 
-// the checks every query shares; returns RP_OK with *skip set when there is nothing to do
-int begin(rp_atlas* h, const char* who, uint64_t n, bool nulls, bool* skip) {
-    *skip = true;
+// ---- the queries: pairs by the rule of host_util.hpp ("entry points in pairs"), on the null stream.  begin and need_* are what the
+// pairs' checks share; the _device forms return after the device finished (finish)
+int begin(const rp_atlas* h, const char* who, uint64_t n, bool nulls) {
     if (!h) return rp::fail(RP_ERR_INVALID, "%s: NULL handle", who);
     if (n && nulls) return rp::fail(RP_ERR_INVALID, "%s: null argument", who);
     if (n > (1ull << 32)) return rp::fail(RP_ERR_INVALID, "%s: at most 2^32 queries per call", who);
-    *skip = n == 0;
     return RP_OK;
 }
 int finish() {
@@ -181,28 +169,43 @@ int need_tri(const rp_atlas* h, const char* who) {
 int need_future(const rp_atlas* h, const char* who) {
     return h->future ? RP_OK : rp::fail(RP_ERR_UNSUPPORTED, "%s: a river atlas has no transitions", who);
 }
-int check_neighbors(rp_atlas* h, uint32_t k) {
+int check_describe(const rp_atlas* h, uint64_t n, const void* obs, const void* wrt, const void* out, const void* status) {
+    if (int rc = begin(h, "rp_atlas_describe", n, !obs || !out || !status)) return rc;
+    return wrt ? need_tri(h, "rp_atlas_describe") : RP_OK;
+}
+int check_obs_equity(const rp_atlas* h, uint64_t n, const void* obs, const void* out, const void* status) {
+    if (int rc = begin(h, "rp_atlas_obs_equity", n, !obs || !out || !status)) return rc;
+    if (h->street == RP_STREET_RIVE && !h->row_equity)
+        return rp::fail(RP_ERR_UNSUPPORTED, "rp_atlas_obs_equity: this river atlas was created without row_equity");
+    return RP_OK;
+}
+int check_pick(const rp_atlas* h, uint64_t n, const void* abs, const void* draw, const void* out, const void* status) {
+    return begin(h, "rp_atlas_pick", n, !abs || !draw || !out || !status);
+}
+int check_neighbors(const rp_atlas* h, uint64_t n, const void* wrt, uint32_t k, const void* out, const void* status) {
+    if (int rc = begin(h, "rp_atlas_neighbors", n, !wrt || !out || !status)) return rc;
     if (int rc = need_tri(h, "rp_atlas_neighbors")) return rc;
     const uint32_t most = h->K - 1u < atlas::MAX_NEIGHBORS ? h->K - 1u : atlas::MAX_NEIGHBORS;
     if (k == 0 || k > most) return rp::fail(RP_ERR_INVALID, "rp_atlas_neighbors: k = %u, must be in 1..min(K - 1, 16) = %u", k, most);
     return RP_OK;
 }
-int check_window(uint32_t count) {
-    if (count == 0 || count > atlas::MAX_WINDOW) return rp::fail(RP_ERR_INVALID, "rp_atlas_members: count = %u, must be in 1..16", count);
-    return RP_OK;
+int check_distance(const rp_atlas* h, uint64_t n, const void* a, const void* b, const void* out) {
+    if (int rc = begin(h, "rp_atlas_distance", n, !a || !b || !out)) return rc;
+    return need_tri(h, "rp_atlas_distance");
 }
-int check_kind(rp_atlas* h, int kind) {
+int check_histograms(const rp_atlas* h, uint64_t n, int kind, const void* ids, const void* counts, const void* status) {
+    if (int rc = begin(h, "rp_atlas_histograms", n, !ids || !counts || !status)) return rc;
     if (int rc = need_future(h, "rp_atlas_histograms")) return rc;
     if (kind != RP_ATLAS_HIST_ABS && kind != RP_ATLAS_HIST_OBS) return rp::fail(RP_ERR_INVALID, "rp_atlas_histograms: kind %d (0 ABS, 1 OBS)", kind);
     return RP_OK;
 }
+int check_members(const rp_atlas* h, uint64_t n, const void* abs, const void* start, uint32_t count, const void* out, const void* got) {
+    if (int rc = begin(h, "rp_atlas_members", n, !abs || !start || !out || !got)) return rc;
+    if (count == 0 || count > atlas::MAX_WINDOW) return rp::fail(RP_ERR_INVALID, "rp_atlas_members: count = %u, must be in 1..16", count);
+    return RP_OK;
+}
 
 }  // namespace
-
-// the host form of a query: its checks, device copies of the inputs, the _device form, the outputs copied back
-#define ATLAS_UP(arena, dst, src, count) HIP_TRY((arena).upload(&(dst), (src), (size_t)(count)))
-#define ATLAS_OUT(arena, dst, count) HIP_TRY((arena).alloc(&(dst), (size_t)(count)))
-#define ATLAS_DOWN(dst, src, count) HIP_TRY(hipMemcpy((dst), (src), (size_t)(count) * sizeof(*(dst)), hipMemcpyDeviceToHost))
 
 extern "C" {
 
@@ -289,209 +292,118 @@ int rp_atlas_create_ms(const rp_atlas* h, double* sort_ms, double* rest_ms) {
 }
 
 int rp_atlas_describe_device(rp_atlas* h, uint64_t n, const int64_t* obs, const uint8_t* wrt, rp_atlas_sample* out, uint8_t* status) {
-    bool skip;
-    if (int rc = begin(h, "rp_atlas_describe", n, !obs || !out || !status, &skip)) return rc;
-    if (wrt)
-        if (int rc = need_tri(h, "rp_atlas_describe")) return rc;
-    if (skip) return RP_OK;
+    int rc = check_describe(h, n, obs, wrt, out, status);
+    if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipLaunchKernelGGL(atlas::k_atlas_describe, dim3(blocks_of(n, 256)), dim3(256), 0, nullptr, h->view, n, obs, wrt, out, status);
     return finish();
 }
 int rp_atlas_describe(rp_atlas* h, uint64_t n, const int64_t* obs, const uint8_t* wrt, rp_atlas_sample* out, uint8_t* status) {
-    bool skip;
-    if (int rc = begin(h, "rp_atlas_describe", n, !obs || !out || !status, &skip)) return rc;
-    if (wrt)
-        if (int rc = need_tri(h, "rp_atlas_describe")) return rc;
-    if (skip) return RP_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    Arena a;
-    const int64_t* d_obs;
-    const uint8_t* d_wrt;
-    rp_atlas_sample* d_out;
-    uint8_t* d_status;
-    ATLAS_UP(a, d_obs, obs, n);
-    ATLAS_UP(a, d_wrt, wrt, n);
-    ATLAS_OUT(a, d_out, n);
-    ATLAS_OUT(a, d_status, n);
-    if (int rc = rp_atlas_describe_device(h, n, d_obs, d_wrt, d_out, d_status)) return rc;
-    ATLAS_DOWN(out, d_out, n);
-    ATLAS_DOWN(status, d_status, n);
-    return RP_OK;
+    int rc = check_describe(h, n, obs, wrt, out, status);
+    if (rc || n == 0) return rc;
+    Stage s(h->device, nullptr);
+    s.in(obs, n).in(wrt, n).out(out, n).out(status, n);
+    if ((rc = s.up()) || (rc = rp_atlas_describe_device(h, n, obs, wrt, out, status))) return rc;
+    return s.down();
 }
 
 int rp_atlas_obs_equity_device(rp_atlas* h, uint64_t n, const int64_t* obs, float* out, uint8_t* status) {
-    bool skip;
-    if (int rc = begin(h, "rp_atlas_obs_equity", n, !obs || !out || !status, &skip)) return rc;
-    if (h->street == RP_STREET_RIVE && !h->row_equity)
-        return rp::fail(RP_ERR_UNSUPPORTED, "rp_atlas_obs_equity: this river atlas was created without row_equity");
-    if (skip) return RP_OK;
+    int rc = check_obs_equity(h, n, obs, out, status);
+    if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipLaunchKernelGGL(atlas::k_atlas_obs_equity, dim3(blocks_of(n, 256)), dim3(256), 0, nullptr, h->view, n, obs, out, status);
     return finish();
 }
 int rp_atlas_obs_equity(rp_atlas* h, uint64_t n, const int64_t* obs, float* out, uint8_t* status) {
-    bool skip;
-    if (int rc = begin(h, "rp_atlas_obs_equity", n, !obs || !out || !status, &skip)) return rc;
-    if (h->street == RP_STREET_RIVE && !h->row_equity)
-        return rp::fail(RP_ERR_UNSUPPORTED, "rp_atlas_obs_equity: this river atlas was created without row_equity");
-    if (skip) return RP_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    Arena a;
-    const int64_t* d_obs;
-    float* d_out;
-    uint8_t* d_status;
-    ATLAS_UP(a, d_obs, obs, n);
-    ATLAS_OUT(a, d_out, n);
-    ATLAS_OUT(a, d_status, n);
-    if (int rc = rp_atlas_obs_equity_device(h, n, d_obs, d_out, d_status)) return rc;
-    ATLAS_DOWN(out, d_out, n);
-    ATLAS_DOWN(status, d_status, n);
-    return RP_OK;
+    int rc = check_obs_equity(h, n, obs, out, status);
+    if (rc || n == 0) return rc;
+    Stage s(h->device, nullptr);
+    s.in(obs, n).out(out, n).out(status, n);
+    if ((rc = s.up()) || (rc = rp_atlas_obs_equity_device(h, n, obs, out, status))) return rc;
+    return s.down();
 }
 
 int rp_atlas_pick_device(rp_atlas* h, uint64_t n, const uint8_t* abs, const uint64_t* draw, rp_atlas_sample* out, uint8_t* status) {
-    bool skip;
-    if (int rc = begin(h, "rp_atlas_pick", n, !abs || !draw || !out || !status, &skip)) return rc;
-    if (skip) return RP_OK;
+    int rc = check_pick(h, n, abs, draw, out, status);
+    if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipLaunchKernelGGL(atlas::k_atlas_pick, dim3(blocks_of(n, 256)), dim3(256), 0, nullptr, h->view, n, abs, draw, out, status);
     return finish();
 }
 int rp_atlas_pick(rp_atlas* h, uint64_t n, const uint8_t* abs, const uint64_t* draw, rp_atlas_sample* out, uint8_t* status) {
-    bool skip;
-    if (int rc = begin(h, "rp_atlas_pick", n, !abs || !draw || !out || !status, &skip)) return rc;
-    if (skip) return RP_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    Arena a;
-    const uint8_t* d_abs;
-    const uint64_t* d_draw;
-    rp_atlas_sample* d_out;
-    uint8_t* d_status;
-    ATLAS_UP(a, d_abs, abs, n);
-    ATLAS_UP(a, d_draw, draw, n);
-    ATLAS_OUT(a, d_out, n);
-    ATLAS_OUT(a, d_status, n);
-    if (int rc = rp_atlas_pick_device(h, n, d_abs, d_draw, d_out, d_status)) return rc;
-    ATLAS_DOWN(out, d_out, n);
-    ATLAS_DOWN(status, d_status, n);
-    return RP_OK;
+    int rc = check_pick(h, n, abs, draw, out, status);
+    if (rc || n == 0) return rc;
+    Stage s(h->device, nullptr);
+    s.in(abs, n).in(draw, n).out(out, n).out(status, n);
+    if ((rc = s.up()) || (rc = rp_atlas_pick_device(h, n, abs, draw, out, status))) return rc;
+    return s.down();
 }
 
 int rp_atlas_neighbors_device(rp_atlas* h, uint64_t n, const uint8_t* wrt, uint32_t k, int farthest, const uint64_t* draws, rp_atlas_sample* out,
                               uint8_t* status) {
-    bool skip;
-    if (int rc = begin(h, "rp_atlas_neighbors", n, !wrt || !out || !status, &skip)) return rc;
-    if (int rc = check_neighbors(h, k)) return rc;
-    if (skip) return RP_OK;
+    int rc = check_neighbors(h, n, wrt, k, out, status);
+    if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipLaunchKernelGGL(atlas::k_atlas_neighbors, dim3(blocks_of(n, 4)), dim3(256), 0, nullptr, h->view, n, wrt, k, farthest, draws, out, status);
     return finish();
 }
 int rp_atlas_neighbors(rp_atlas* h, uint64_t n, const uint8_t* wrt, uint32_t k, int farthest, const uint64_t* draws, rp_atlas_sample* out,
                        uint8_t* status) {
-    bool skip;
-    if (int rc = begin(h, "rp_atlas_neighbors", n, !wrt || !out || !status, &skip)) return rc;
-    if (int rc = check_neighbors(h, k)) return rc;
-    if (skip) return RP_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    Arena a;
-    const uint8_t* d_wrt;
-    const uint64_t* d_draws;
-    rp_atlas_sample* d_out;
-    uint8_t* d_status;
-    ATLAS_UP(a, d_wrt, wrt, n);
-    ATLAS_UP(a, d_draws, draws, n * k);
-    ATLAS_OUT(a, d_out, n * k);
-    ATLAS_OUT(a, d_status, n * k);
-    if (int rc = rp_atlas_neighbors_device(h, n, d_wrt, k, farthest, d_draws, d_out, d_status)) return rc;
-    ATLAS_DOWN(out, d_out, n * k);
-    ATLAS_DOWN(status, d_status, n * k);
-    return RP_OK;
+    int rc = check_neighbors(h, n, wrt, k, out, status);
+    if (rc || n == 0) return rc;
+    Stage s(h->device, nullptr);
+    s.in(wrt, n).in(draws, n * k).out(out, n * k).out(status, n * k);
+    if ((rc = s.up()) || (rc = rp_atlas_neighbors_device(h, n, wrt, k, farthest, draws, out, status))) return rc;
+    return s.down();
 }
 
 int rp_atlas_distance_device(rp_atlas* h, uint64_t n, const uint8_t* a, const uint8_t* b, float* out) {
-    bool skip;
-    if (int rc = begin(h, "rp_atlas_distance", n, !a || !b || !out, &skip)) return rc;
-    if (int rc = need_tri(h, "rp_atlas_distance")) return rc;
-    if (skip) return RP_OK;
+    int rc = check_distance(h, n, a, b, out);
+    if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipLaunchKernelGGL(atlas::k_atlas_distance, dim3(blocks_of(n, 256)), dim3(256), 0, nullptr, h->view, n, a, b, out);
     return finish();
 }
 int rp_atlas_distance(rp_atlas* h, uint64_t n, const uint8_t* a, const uint8_t* b, float* out) {
-    bool skip;
-    if (int rc = begin(h, "rp_atlas_distance", n, !a || !b || !out, &skip)) return rc;
-    if (int rc = need_tri(h, "rp_atlas_distance")) return rc;
-    if (skip) return RP_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    Arena ar;
-    const uint8_t *d_a, *d_b;
-    float* d_out;
-    ATLAS_UP(ar, d_a, a, n);
-    ATLAS_UP(ar, d_b, b, n);
-    ATLAS_OUT(ar, d_out, n);
-    if (int rc = rp_atlas_distance_device(h, n, d_a, d_b, d_out)) return rc;
-    ATLAS_DOWN(out, d_out, n);
-    return RP_OK;
+    int rc = check_distance(h, n, a, b, out);
+    if (rc || n == 0) return rc;
+    Stage s(h->device, nullptr);
+    s.in(a, n).in(b, n).out(out, n);
+    if ((rc = s.up()) || (rc = rp_atlas_distance_device(h, n, a, b, out))) return rc;
+    return s.down();
 }
 
 int rp_atlas_histograms_device(rp_atlas* h, uint64_t n, int kind, const void* ids, uint32_t* counts, uint8_t* status) {
-    bool skip;
-    if (int rc = begin(h, "rp_atlas_histograms", n, !ids || !counts || !status, &skip)) return rc;
-    if (int rc = check_kind(h, kind)) return rc;
-    if (skip) return RP_OK;
+    int rc = check_histograms(h, n, kind, ids, counts, status);
+    if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipLaunchKernelGGL(atlas::k_atlas_histograms, dim3(blocks_of(n, 4)), dim3(256), 0, nullptr, h->view, n, kind, ids, counts, status);
     return finish();
 }
 int rp_atlas_histograms(rp_atlas* h, uint64_t n, int kind, const void* ids, uint32_t* counts, uint8_t* status) {
-    bool skip;
-    if (int rc = begin(h, "rp_atlas_histograms", n, !ids || !counts || !status, &skip)) return rc;
-    if (int rc = check_kind(h, kind)) return rc;
-    if (skip) return RP_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    Arena a;
-    const uint8_t* d_ids;
-    uint32_t* d_counts;
-    uint8_t* d_status;
-    ATLAS_UP(a, d_ids, static_cast<const uint8_t*>(ids), n * (kind == RP_ATLAS_HIST_OBS ? 8u : 1u));
-    ATLAS_OUT(a, d_counts, n * h->bins);
-    ATLAS_OUT(a, d_status, n);
-    if (int rc = rp_atlas_histograms_device(h, n, kind, d_ids, d_counts, d_status)) return rc;
-    ATLAS_DOWN(counts, d_counts, n * h->bins);
-    ATLAS_DOWN(status, d_status, n);
-    return RP_OK;
+    int rc = check_histograms(h, n, kind, ids, counts, status);
+    if (rc || n == 0) return rc;
+    const uint8_t* id_bytes = static_cast<const uint8_t*>(ids);  // 1 byte an abstraction, 8 an observation
+    Stage s(h->device, nullptr);
+    s.in(id_bytes, n * (kind == RP_ATLAS_HIST_OBS ? 8u : 1u)).out(counts, n * h->bins).out(status, n);
+    if ((rc = s.up()) || (rc = rp_atlas_histograms_device(h, n, kind, id_bytes, counts, status))) return rc;
+    return s.down();
 }
 
 int rp_atlas_members_device(rp_atlas* h, uint64_t n, const uint8_t* abs, const uint32_t* start, uint32_t count, int64_t* out, uint8_t* got) {
-    bool skip;
-    if (int rc = begin(h, "rp_atlas_members", n, !abs || !start || !out || !got, &skip)) return rc;
-    if (int rc = check_window(count)) return rc;
-    if (skip) return RP_OK;
+    int rc = check_members(h, n, abs, start, count, out, got);
+    if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipLaunchKernelGGL(atlas::k_atlas_members, dim3(blocks_of(n, 256)), dim3(256), 0, nullptr, h->view, n, abs, start, count, out, got);
     return finish();
 }
 int rp_atlas_members(rp_atlas* h, uint64_t n, const uint8_t* abs, const uint32_t* start, uint32_t count, int64_t* out, uint8_t* got) {
-    bool skip;
-    if (int rc = begin(h, "rp_atlas_members", n, !abs || !start || !out || !got, &skip)) return rc;
-    if (int rc = check_window(count)) return rc;
-    if (skip) return RP_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    Arena a;
-    const uint8_t* d_abs;
-    const uint32_t* d_start;
-    int64_t* d_out;
-    uint8_t* d_got;
-    ATLAS_UP(a, d_abs, abs, n);
-    ATLAS_UP(a, d_start, start, n);
-    ATLAS_OUT(a, d_out, n * count);
-    ATLAS_OUT(a, d_got, n);
-    if (int rc = rp_atlas_members_device(h, n, d_abs, d_start, count, d_out, d_got)) return rc;
-    ATLAS_DOWN(out, d_out, n * count);
-    ATLAS_DOWN(got, d_got, n);
-    return RP_OK;
+    int rc = check_members(h, n, abs, start, count, out, got);
+    if (rc || n == 0) return rc;
+    Stage s(h->device, nullptr);
+    s.in(abs, n).in(start, n).out(out, n * count).out(got, n);
+    if ((rc = s.up()) || (rc = rp_atlas_members_device(h, n, abs, start, count, out, got))) return rc;
+    return s.down();
 }
 
 }  // extern "C"

@@ -1,10 +1,12 @@
 // host_util.hpp — the host plumbing the .hip files share (host only, not part of the ABI): HIP_TRY, the event-pair kernel clocks
-// behind the *_profile / *_kernel_time hooks, and the body of the *_set_stream functions.
+// behind the *_profile / *_kernel_time hooks, the body of the *_set_stream functions, and what the entry points that come in a host
+// and a _device form share: the staging arena, the chunk loop, the grow-only region.
 #ifndef RP_HOST_UTIL_HPP
 #define RP_HOST_UTIL_HPP
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <utility>
 #include <vector>
 
@@ -102,6 +104,93 @@ inline int swap_stream(hipStream_t& stream, bool& own, void* hip_stream) {
         HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         own = true;
     }
+    return RP_OK;
+}
+
+// ---- entry points in pairs.  The _device form takes every array in device memory and queues its launches on its handle's stream; the
+// host form stages the same arrays through one device allocation (Stage), calls the _device form and synchronises.  The two forms of
+// a pair share ONE check of their arguments: the refusals of include/rp_mi355x.h in its order, made before a device is touched,
+// naming the un-suffixed function; RP_OK from a check with n == 0 is the call's answer.  Every entry point that may need more than
+// one launch runs chunks, whatever its chunk size.
+
+inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// device scratch of one host-form call.  The host form names its arrays — in(p, count): copied to the device, out(p, count): copied
+// back from it; a NULL array (an optional argument left out) or an empty one is no bytes and stays, or becomes, NULL — then up()
+// makes the ONE allocation, queues the uploads and points every named p at its device copy (16-byte aligned each), so that the
+// _device form is called with the host form's own arguments; down() queues the downloads and synchronises.  The allocation is freed
+// on every way out, a refusal after a launch was queued included: hipFree waits for the device.
+struct Stage {
+    struct Part {
+        void* p;  // the caller's pointer variable, whatever it points to
+        void* host;
+        size_t bytes, at;
+        bool in;
+    };
+    int device;
+    hipStream_t st;
+    std::vector<Part> parts;
+    size_t bytes = 0;
+    unsigned char* base = nullptr;
+    Stage(int device_, hipStream_t stream) : device(device_), st(stream) {}
+    Stage(const Stage&) = delete;
+    ~Stage() {
+        if (base) (void)hipFree(base);
+    }
+    template <typename T>
+    Stage& add(T*& p, size_t count, bool in) {
+        parts.push_back(Part{(void*)&p, (void*)p, p ? count * sizeof(T) : 0, bytes, in});
+        bytes += align16(parts.back().bytes);
+        return *this;
+    }
+    template <typename T>
+    Stage& in(const T*& p, size_t count) {
+        return add(p, count, true);
+    }
+    template <typename T>
+    Stage& out(T*& p, size_t count) {
+        return add(p, count, false);
+    }
+    int up() {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipMalloc(&base, bytes));
+        for (const Part& p : parts) {
+            void* dev = p.bytes ? base + p.at : nullptr;
+            memcpy(p.p, &dev, sizeof(dev));
+            if (p.in && p.bytes) HIP_TRY(hipMemcpyAsync(base + p.at, p.host, p.bytes, hipMemcpyHostToDevice, st));
+        }
+        return RP_OK;
+    }
+    int down() {
+        for (const Part& p : parts)
+            if (!p.in && p.bytes) HIP_TRY(hipMemcpyAsync(p.host, base + p.at, p.bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return RP_OK;
+    }
+};
+// items at .. at + m of n, at most `chunk` per launch: f(at, m) queues one launch
+template <typename F>
+int chunks(uint64_t n, uint64_t chunk, F f) {
+    for (uint64_t at = 0; at < n; at += chunk) {
+        f(at, (uint32_t)std::min<uint64_t>(chunk, n - at));
+        HIP_TRY(hipGetLastError());
+    }
+    return RP_OK;
+}
+// an optional array from its item i on
+template <typename T>
+T* from(T* p, uint64_t i) {
+    return p ? p + i : nullptr;
+}
+// a grow-only region of the handle that queued launches write: an earlier call's launch may still write the old one
+inline int grow(void*& region, size_t& bytes, size_t need, hipStream_t st) {
+    if (need <= bytes) return RP_OK;
+    HIP_TRY(hipStreamSynchronize(st));
+    if (region) HIP_TRY(hipFree(region));
+    region = nullptr;
+    bytes = 0;
+    HIP_TRY(hipMalloc(&region, need));
+    bytes = need;
     return RP_OK;
 }
 

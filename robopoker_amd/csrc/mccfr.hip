@@ -1541,10 +1541,8 @@ int rp_mccfr_solve_to(rp_mccfr* h, float target, uint32_t check_every, uint64_t 
 
 }  // extern "C"
 
-// ---- the safe subgame re-solve for table games (mccfr_subgame.hpp) ------------------------------------------------------------------
+// ---- the safe subgame re-solve for table games (mccfr_subgame.hpp): pairs by the rule of host_util.hpp ("entry points in pairs") ----
 namespace {
-
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // iterations per launch: RP_MCCFR_SUBGAME_SEGMENT (tests), else 8 192
 int msub_segment(uint32_t* out) {
@@ -1616,77 +1614,65 @@ int msub_launch_solve(const char* who, rp_mccfr* h, uint64_t n, const rp_mccfr_s
     p.hp = DistParams{h->hp.temperature, h->hp.smoothing, h->hp.curiosity};
     if constexpr (FR) p.fr = h->fr;
     h->clk.begin(h->stream, CK_SUBGAME);
-    for (uint64_t at = 0; at < n; at += chunk) {
-        p.n = (uint32_t)std::min<uint64_t>(chunk, n - at);
+    rc = rp::chunks(n, chunk, [&](uint64_t at, uint32_t m) {
+        p.n = m;
         p.entries = entries + at;
         p.results = results + at;
-        p.rows = rows ? rows + at * a->rows_cap : nullptr;
+        p.rows = rp::from(rows, at * a->rows_cap);
         p.first_id = a->first_id + at;
-        if constexpr (FR) p.origin = origin ? origin + at : nullptr;
+        if constexpr (FR) p.origin = rp::from(origin, at);
         for (uint32_t t = 0; t < a->iterations; t += segment) {
             p.t_begin = t;
             p.t_end = (uint32_t)std::min<uint64_t>((uint64_t)t + segment, a->iterations);
             hipLaunchKernelGGL(k_mccfr_subgame_solve<FR>, dim3(p.n), dim3(MS_LANES), 0, h->stream, h->g, h->t, R, p);
         }
-    }
+    });
     h->clk.end(h->stream, CK_SUBGAME);
-    HIP_TRY(hipGetLastError());
-    return RP_OK;
+    return rc;
 }
 
-// the checks every solve makes after its args, in the header's order
-int msub_check_solve(const char* who, const rp_mccfr* h, const void* entries, const void* results, const void* rows, const rp_mccfr_subgame_args* args,
-                     bool frontiers) {
+// the ONE check of a solve pair, in the header's order: the args, n == 0 (RP_OK is the call's answer), then the handle and the arrays
+int msub_check_solve(const char* who, const rp_mccfr* h, uint64_t n, const void* entries, const void* results, const void* rows,
+                     const rp_mccfr_subgame_args* args, bool frontiers) {
+    int rc = msub_check_args(who, args);
+    if (rc || n == 0) return rc;
     if (!h) return rp::fail(RP_ERR_INVALID, "%s: h is NULL", who);
     if (!entries || !results) return rp::fail(RP_ERR_INVALID, "%s: entries or results is NULL", who);
     if (!rows && args->rows_cap > 0) return rp::fail(RP_ERR_INVALID, "%s: rows is NULL with rows_cap > 0", who);
-    int rc = msub_check_game(who, h);
-    if (rc) return rc;
+    if ((rc = msub_check_game(who, h))) return rc;
     if (frontiers && !h->fr.depth) return rp::fail(RP_ERR_INVALID, "%s: the handle has no frontier tables (rp_mccfr_set_frontiers)", who);
     return RP_OK;
 }
 
-// the host form of both solves: stage, launch, download, synchronise; origin is a host array or nullptr
-template <bool FR>
-int msub_solve_host(const char* who, rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries, const uint8_t* origin,
-                    const rp_mccfr_subgame_args* args, rp_mccfr_subgame_result* results, rp_mccfr_subgame_row* rows) {
-    int rc = msub_check_args(who, args);
-    if (rc) return rc;
+// the ONE check of the belief pair
+int msub_check_belief(const rp_mccfr* h, uint64_t n, const void* priors, const void* world_of, const void* weights) {
     if (n == 0) return RP_OK;
-    if ((rc = msub_check_solve(who, h, entries, results, rows, args, FR))) return rc;
-    if ((rc = set_device(h))) return rc;
-    const size_t b_in = align16(n * sizeof(rp_mccfr_subgame_entry)), b_res = align16(n * sizeof(rp_mccfr_subgame_result)),
-                 b_rows = align16(n * (size_t)args->rows_cap * sizeof(rp_mccfr_subgame_row)), b_org = FR && origin ? align16(n) : 0;
-    uint8_t* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), b_in + b_res + b_rows + b_org + 16) != hipSuccess) {
-        (void)hipGetLastError();
-        return rp::fail(RP_ERR_CAPACITY, "%s: %zu bytes of staging do not fit", who, b_in + b_res + b_rows + b_org);
-    }
-    rp_mccfr_subgame_result* d_res = reinterpret_cast<rp_mccfr_subgame_result*>(d + b_in);
-    rp_mccfr_subgame_row* d_rows = args->rows_cap ? reinterpret_cast<rp_mccfr_subgame_row*>(d + b_in + b_res) : nullptr;
-    uint8_t* d_org = b_org ? d + b_in + b_res + b_rows : nullptr;
-    if (hipMemcpyAsync(d, entries, n * sizeof(rp_mccfr_subgame_entry), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-        (d_org && hipMemcpyAsync(d_org, origin, n, hipMemcpyHostToDevice, h->stream) != hipSuccess))
-        rc = rp::fail(RP_ERR_HIP, "%s: upload failed", who);
-    if (!rc) rc = msub_launch_solve<FR>(who, h, n, reinterpret_cast<const rp_mccfr_subgame_entry*>(d), d_org, args, d_res, d_rows);
-    if (!rc && (hipMemcpyAsync(results, d_res, n * sizeof(rp_mccfr_subgame_result), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-                (d_rows && hipMemcpyAsync(rows, d_rows, n * (size_t)args->rows_cap * sizeof(rp_mccfr_subgame_row), hipMemcpyDeviceToHost, h->stream) != hipSuccess)))
-        rc = rp::fail(RP_ERR_HIP, "%s: download failed", who);
-    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = rp::fail(RP_ERR_HIP, "%s: a launch failed: %s", who, hipGetErrorString(hipGetLastError()));
-    (void)hipFree(d);
-    h->clk.drain();
-    return rc;
+    if (!h) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_belief: h is NULL");
+    if (!priors || !world_of || !weights) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_belief: priors, world_of or weights is NULL");
+    if (n > 0x7fffffffull) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_belief: n is larger than 2^31 - 1");
+    return msub_check_game("rp_mccfr_subgame_belief", h);
 }
 
 template <bool FR>
 int msub_solve_device(const char* who, rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries_dev, const uint8_t* origin_dev,
                       const rp_mccfr_subgame_args* args, rp_mccfr_subgame_result* results_dev, rp_mccfr_subgame_row* rows_dev) {
-    int rc = msub_check_args(who, args);
-    if (rc) return rc;
-    if (n == 0) return RP_OK;
-    if ((rc = msub_check_solve(who, h, entries_dev, results_dev, rows_dev, args, FR))) return rc;
+    int rc = msub_check_solve(who, h, n, entries_dev, results_dev, rows_dev, args, FR);
+    if (rc || n == 0) return rc;
     if ((rc = set_device(h))) return rc;
     return msub_launch_solve<FR>(who, h, n, entries_dev, origin_dev, args, results_dev, rows_dev);
+}
+
+// the host form of both solves; origin is a host array or nullptr.  The clocks are drained on every way out past the check
+template <bool FR>
+int msub_solve_host(const char* who, rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries, const uint8_t* origin,
+                    const rp_mccfr_subgame_args* args, rp_mccfr_subgame_result* results, rp_mccfr_subgame_row* rows) {
+    int rc = msub_check_solve(who, h, n, entries, results, rows, args, FR);
+    if (rc || n == 0) return rc;
+    Stage s(h->device, h->stream);
+    s.in(entries, n).in(origin, n).out(results, n).out(rows, n * (size_t)args->rows_cap);
+    if (!(rc = s.up()) && !(rc = msub_solve_device<FR>(who, h, n, entries, origin, args, results, rows))) rc = s.down();
+    h->clk.drain();
+    return rc;
 }
 
 }  // namespace
@@ -1702,12 +1688,8 @@ void rp_mccfr_subgame_args_default(rp_mccfr_subgame_args* out) {
 
 int rp_mccfr_subgame_belief_device(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_prior* priors_dev, uint8_t* world_of_dev, float* weights_dev,
                                    uint8_t* status_dev) {
-    if (n == 0) return RP_OK;
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_belief: h is NULL");
-    if (!priors_dev || !world_of_dev || !weights_dev) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_belief: priors, world_of or weights is NULL");
-    if (n > 0x7fffffffull) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_belief: n is larger than 2^31 - 1");
-    int rc = msub_check_game("rp_mccfr_subgame_belief", h);
-    if (rc) return rc;
+    int rc = msub_check_belief(h, n, priors_dev, world_of_dev, weights_dev);
+    if (rc || n == 0) return rc;
     if ((rc = set_device(h))) return rc;
     hipLaunchKernelGGL(k_mccfr_subgame_belief, dim3((uint32_t)n), dim3(MS_LANES), 0, h->stream, h->g, h->t, h->tbl.n_states, (uint32_t)n, priors_dev,
                        world_of_dev, weights_dev, status_dev);
@@ -1716,26 +1698,12 @@ int rp_mccfr_subgame_belief_device(rp_mccfr* h, uint64_t n, const rp_mccfr_subga
 }
 
 int rp_mccfr_subgame_belief(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_prior* priors, uint8_t* world_of, float* weights, uint8_t* status) {
-    if (n == 0) return RP_OK;
-    if (!h) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_belief: h is NULL");
-    if (!priors || !world_of || !weights) return rp::fail(RP_ERR_INVALID, "rp_mccfr_subgame_belief: priors, world_of or weights is NULL");
-    int rc = msub_check_game("rp_mccfr_subgame_belief", h);
-    if (rc) return rc;
-    if ((rc = set_device(h))) return rc;
-    const size_t b_in = n * sizeof(rp_mccfr_subgame_prior), b_wo = n * 16, b_wt = n * 16, b_st = n;
-    uint8_t* d = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), align16(b_in) + b_wo + b_wt + align16(b_st)));
-    uint8_t *d_wo = d + align16(b_in), *d_wt = d_wo + b_wo, *d_st = d_wt + b_wt;
-    rc = RP_OK;
-    if (hipMemcpyAsync(d, priors, b_in, hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = rp::fail(RP_ERR_HIP, "rp_mccfr_subgame_belief: upload failed");
-    if (!rc) rc = rp_mccfr_subgame_belief_device(h, n, reinterpret_cast<const rp_mccfr_subgame_prior*>(d), d_wo, reinterpret_cast<float*>(d_wt), d_st);
-    if (!rc && (hipMemcpyAsync(world_of, d_wo, b_wo, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-                hipMemcpyAsync(weights, d_wt, b_wt, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-                (status && hipMemcpyAsync(status, d_st, b_st, hipMemcpyDeviceToHost, h->stream) != hipSuccess)))
-        rc = rp::fail(RP_ERR_HIP, "rp_mccfr_subgame_belief: download failed");
-    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = rp::fail(RP_ERR_HIP, "rp_mccfr_subgame_belief: the launch failed: %s", hipGetErrorString(hipGetLastError()));
-    (void)hipFree(d);
-    return rc;
+    int rc = msub_check_belief(h, n, priors, world_of, weights);
+    if (rc || n == 0) return rc;
+    Stage s(h->device, h->stream);
+    s.in(priors, n).out(world_of, n * 16).out(weights, n * 4).out(status, n);  // world_of[n][16], weights[n][4]
+    if ((rc = s.up()) || (rc = rp_mccfr_subgame_belief_device(h, n, priors, world_of, weights, status))) return rc;
+    return s.down();
 }
 
 int rp_mccfr_subgame_solve_device(rp_mccfr* h, uint64_t n, const rp_mccfr_subgame_entry* entries_dev, const rp_mccfr_subgame_args* args,

@@ -926,91 +926,8 @@ extern "C" RP_API int rp_nl_tree_rec(uint32_t* out, uint32_t trees) {
 }
 #endif
 
-// ---- the read side: read-only entry points in pairs.  The _device form takes every array in device memory and queues its launches
-// on the profile's stream; the host form stages the same arrays through one device allocation (Stage), calls the _device form and
-// synchronises.  The two forms of a pair share ONE check of their arguments: the refusals of include/rp_mi355x.h in its order, made
-// before a device is touched, naming the un-suffixed function; RP_OK from a check with n == 0 is the call's answer.  Every entry
-// point that may need more than one launch runs nl_chunks, whatever its chunk size.
+// ---- the read side: read-only entry points in pairs, by the rule of host_util.hpp ("entry points in pairs"), on the profile's stream
 namespace {
-// device scratch of one host-form call.  The host form names its arrays — in(p, count): copied to the device, out(p, count): copied
-// back from it; a NULL array (an optional argument left out) or an empty one is no bytes and stays, or becomes, NULL — then up()
-// makes the ONE allocation, queues the uploads and points every named p at its device copy (16-byte aligned each), so that the
-// _device form is called with the host form's own arguments; down() queues the downloads and synchronises.  The allocation is freed
-// on every way out, a refusal after a launch was queued included: hipFree waits for the device.
-struct Stage {
-    struct Part {
-        void* p;  // the caller's pointer variable, whatever it points to
-        void* host;
-        size_t bytes, at;
-        bool in;
-    };
-    int device;
-    hipStream_t st;
-    std::vector<Part> parts;
-    size_t bytes = 0;
-    unsigned char* base = nullptr;
-    explicit Stage(const rp_nlhe* h) : device(h->device), st(rp::profile_stream(h->prof)) {}
-    Stage(const Stage&) = delete;
-    ~Stage() {
-        if (base) (void)hipFree(base);
-    }
-    template <typename T>
-    Stage& add(T*& p, size_t count, bool in) {
-        parts.push_back(Part{(void*)&p, (void*)p, p ? count * sizeof(T) : 0, bytes, in});
-        bytes += (parts.back().bytes + 15) & ~(size_t)15;
-        return *this;
-    }
-    template <typename T>
-    Stage& in(const T*& p, size_t count) {
-        return add(p, count, true);
-    }
-    template <typename T>
-    Stage& out(T*& p, size_t count) {
-        return add(p, count, false);
-    }
-    int up() {
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipMalloc(&base, bytes));
-        for (const Part& p : parts) {
-            void* dev = p.bytes ? base + p.at : nullptr;
-            memcpy(p.p, &dev, sizeof(dev));
-            if (p.in && p.bytes) HIP_TRY(hipMemcpyAsync(base + p.at, p.host, p.bytes, hipMemcpyHostToDevice, st));
-        }
-        return RP_OK;
-    }
-    int down() {
-        for (const Part& p : parts)
-            if (!p.in && p.bytes) HIP_TRY(hipMemcpyAsync(p.host, base + p.at, p.bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return RP_OK;
-    }
-};
-// items at .. at + m of n, at most `chunk` per launch: f(at, m) queues one launch
-template <typename F>
-int nl_chunks(uint64_t n, uint64_t chunk, F f) {
-    for (uint64_t at = 0; at < n; at += chunk) {
-        f(at, (uint32_t)std::min<uint64_t>(chunk, n - at));
-        HIP_TRY(hipGetLastError());
-    }
-    return RP_OK;
-}
-// an optional array from its item i on
-template <typename T>
-T* nl_at(T* p, uint64_t i) {
-    return p ? p + i : nullptr;
-}
-// a grow-only region of the handle that queued launches write: an earlier call's launch may still write the old one
-int nl_grow(void*& region, size_t& bytes, size_t need, hipStream_t st) {
-    if (need <= bytes) return RP_OK;
-    HIP_TRY(hipStreamSynchronize(st));
-    if (region) HIP_TRY(hipFree(region));
-    region = nullptr;
-    bytes = 0;
-    HIP_TRY(hipMalloc(&region, need));
-    bytes = need;
-    return RP_OK;
-}
-
 // ---- queries by NlheInfo key (nlmc_query.hpp): one launch
 uint32_t nlq_blocks(const rp_nlhe* h, uint64_t n, uint32_t per_block) {
     return (uint32_t)std::min<uint64_t>((n + per_block - 1) / per_block, h->grid_cap);
@@ -1058,7 +975,7 @@ int rp_nlhe_policy(rp_nlhe* h, rp_dist_kind kind, uint64_t n, const uint64_t* pa
                    float* policy, uint8_t* edges, uint8_t* n_actions, uint8_t* found) {
     int rc = nlq_policy_check(h, kind, n, past, present, choices, policy);
     if (rc || n == 0) return rc;
-    Stage s(h);
+    rp::Stage s(h->device, rp::profile_stream(h->prof));
     s.in(past, n).in(present, n).in(choices, n).out(policy, n * NLMC_A).out(edges, n * NLMC_A).out(n_actions, n).out(found, n);
     if ((rc = s.up()) || (rc = rp_nlhe_policy_device(h, kind, n, past, present, choices, policy, edges, n_actions, found))) return rc;
     return s.down();
@@ -1079,7 +996,7 @@ int rp_nlhe_memory(rp_nlhe* h, uint64_t n, const uint64_t* past, const uint32_t*
                    uint8_t* n_actions, uint8_t* found) {
     int rc = nlq_memory_check(h, n, past, present, choices, enc);
     if (rc || n == 0) return rc;
-    Stage s(h);
+    rp::Stage s(h->device, rp::profile_stream(h->prof));
     s.in(past, n).in(present, n).in(choices, n).out(enc, n * NLMC_A).out(n_actions, n).out(found, n);
     if ((rc = s.up()) || (rc = rp_nlhe_memory_device(h, n, past, present, choices, enc, n_actions, found))) return rc;
     return s.down();
@@ -1094,17 +1011,17 @@ int nr_launch(rp_nlhe* h, int kind, int normalize, uint64_t n, const rp_nlhe_rec
               float* mass, uint8_t* seen, uint8_t* status) {
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = rp::profile_stream(h->prof);
-    return nl_chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
+    return rp::chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
         NrArgs q{};
         q.recalls = recalls + at;
         q.kind = kind;
         q.normalize = normalize;
-        q.count = nl_at(count, at);
-        q.holes = nl_at(holes, at * RP_NLHE_MAX_HOLES);
-        q.reach = nl_at(reach, at * RP_NLHE_MAX_HOLES);
-        q.mass = nl_at(mass, at * 256u);
-        q.seen = nl_at(seen, at * 256u);
-        q.status = nl_at(status, at);
+        q.count = rp::from(count, at);
+        q.holes = rp::from(holes, at * RP_NLHE_MAX_HOLES);
+        q.reach = rp::from(reach, at * RP_NLHE_MAX_HOLES);
+        q.mass = rp::from(mass, at * 256u);
+        q.seen = rp::from(seen, at * 256u);
+        q.status = rp::from(status, at);
         hipLaunchKernelGGL(k_nl_range, dim3(m), dim3(NR_BLOCK), 0, st, h->tab, h->prm, q);
     });
 }
@@ -1136,7 +1053,7 @@ int rp_nlhe_reaches(rp_nlhe* h, rp_reach_kind kind, int normalize, uint64_t n, c
                     float* reach, uint8_t* status) {
     int rc = nr_reaches_check(h, kind, n, recalls, count, reach);
     if (rc || n == 0) return rc;
-    Stage s(h);
+    rp::Stage s(h->device, rp::profile_stream(h->prof));
     s.in(recalls, n).out(holes, n * RP_NLHE_MAX_HOLES).out(reach, n * RP_NLHE_MAX_HOLES).out(count, n).out(status, n);
     if ((rc = s.up()) || (rc = rp_nlhe_reaches_device(h, kind, normalize, n, recalls, count, holes, reach, status))) return rc;
     return s.down();
@@ -1151,7 +1068,7 @@ int rp_nlhe_opponent_range_device(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* 
 int rp_nlhe_opponent_range(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, float* mass, uint8_t* seen, uint8_t* status) {
     int rc = nr_range_check(h, n, recalls, mass, seen);
     if (rc || n == 0) return rc;
-    Stage s(h);
+    rp::Stage s(h->device, rp::profile_stream(h->prof));
     s.in(recalls, n).out(mass, n * 256u).out(seen, n * 256u).out(status, n);
     if ((rc = s.up()) || (rc = rp_nlhe_opponent_range_device(h, n, recalls, mass, seen, status))) return rc;
     return s.down();
@@ -1181,7 +1098,7 @@ int rp_nlhe_frontier_payoffs_device(rp_nlhe* h, uint64_t n, const rp_nlhe_fronti
     if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = rp::profile_stream(h->prof);
-    return nl_chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
+    return rp::chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
         NfArgs q{};
         q.frontiers = frontiers + at;
         q.bias = bias;
@@ -1189,8 +1106,8 @@ int rp_nlhe_frontier_payoffs_device(rp_nlhe* h, uint64_t n, const rp_nlhe_fronti
         q.step_hash = rp_node_hash_step(seed, 0);
         q.first_id = first_id + at;
         q.payoffs = payoffs + at * NF_CELLS;
-        q.won = nl_at(won, at * NF_CELLS * rollouts);
-        q.status = nl_at(status, at);
+        q.won = rp::from(won, at * NF_CELLS * rollouts);
+        q.status = rp::from(status, at);
         hipLaunchKernelGGL(k_nl_frontier, dim3(m), dim3(NF_BLOCK), 0, st, h->tab, h->prm, q);
     });
 }
@@ -1199,7 +1116,7 @@ int rp_nlhe_frontier_payoffs(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* fro
                              uint64_t first_id, float* payoffs, int16_t* won, uint8_t* status) {
     int rc = nf_check(h, n, frontiers, bias, &rollouts, payoffs);
     if (rc || n == 0) return rc;
-    Stage s(h);
+    rp::Stage s(h->device, rp::profile_stream(h->prof));
     s.in(frontiers, n).out(payoffs, n * NF_CELLS).out(won, n * NF_CELLS * rollouts).out(status, n);
     if ((rc = s.up()) || (rc = rp_nlhe_frontier_payoffs_device(h, n, frontiers, bias, rollouts, seed, first_id, payoffs, won, status))) return rc;
     return s.down();
@@ -1258,11 +1175,11 @@ int rp_nlhe_depth_solve_device(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* e
     hipStream_t st = rp::profile_stream(h->prof);
     // the overflow rows of one launch's solves: launches of one call follow each other on the stream and share the region
     const size_t need = (size_t)std::min<uint64_t>(ND_CHUNK, n) * ND_ROWS_OVF * sizeof(NdRow);
-    if ((rc = nl_grow(h->depth_rows, h->depth_rows_bytes, need, st))) return rc;
-    return nl_chunks(n, ND_CHUNK, [&](uint64_t at, uint32_t m) {
+    if ((rc = rp::grow(h->depth_rows, h->depth_rows_bytes, need, st))) return rc;
+    return rp::chunks(n, ND_CHUNK, [&](uint64_t at, uint32_t m) {
         NdArgs q{};
         q.entries = entries + at;
-        q.origin = nl_at(origin, at);
+        q.origin = rp::from(origin, at);
         q.iterations = args->iterations;
         q.rollouts = rollouts;
         q.rows_cap = rows ? args->rows_cap : 0u;
@@ -1273,7 +1190,7 @@ int rp_nlhe_depth_solve_device(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* e
         q.first_id = args->first_id + at;
         q.overflow = static_cast<NdRow*>(h->depth_rows);
         q.results = results + at;
-        q.rows = nl_at(rows, at * args->rows_cap);
+        q.rows = rp::from(rows, at * args->rows_cap);
         hipLaunchKernelGGL(k_nl_depth, dim3(m), dim3(ND_BLOCK), 0, st, h->tab, h->prm, q);
     });
 }
@@ -1283,7 +1200,7 @@ int rp_nlhe_depth_solve(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* entries,
     uint32_t rollouts = 0;
     int rc = nd_check(h, n, entries, args, results, rows, &rollouts);
     if (rc || n == 0) return rc;
-    Stage s(h);
+    rp::Stage s(h->device, rp::profile_stream(h->prof));
     s.in(entries, n).in(origin, n).out(results, n).out(rows, n * args->rows_cap);
     if ((rc = s.up()) || (rc = rp_nlhe_depth_solve_device(h, n, entries, origin, args, results, rows))) return rc;
     return s.down();
@@ -1299,20 +1216,20 @@ int nw_launch(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, uint8_t* wo
               const uint8_t* worlds, uint64_t seed, uint64_t first_id, uint64_t* holes, uint8_t* world_out, uint16_t* attempts, uint8_t* status) {
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = rp::profile_stream(h->prof);
-    return nl_chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
+    return rp::chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
         NwArgs q{};
         q.recalls = recalls + at;
-        q.world = nl_at(world, at * 256u);
-        q.weights = nl_at(weights, at * RP_NLHE_WORLDS);
-        q.hole_world = nl_at(hole_world, at * RP_NLHE_MAX_HOLES);
+        q.world = rp::from(world, at * 256u);
+        q.weights = rp::from(weights, at * RP_NLHE_WORLDS);
+        q.hole_world = rp::from(hole_world, at * RP_NLHE_MAX_HOLES);
         q.deals = deals;
-        q.worlds = nl_at(worlds, at * deals);
+        q.worlds = rp::from(worlds, at * deals);
         q.step_hash = rp_node_hash_step(seed, 1);
         q.first_id = first_id + at;
-        q.holes = nl_at(holes, at * deals);
-        q.world_out = nl_at(world_out, at * deals);
-        q.attempts = nl_at(attempts, at * deals);
-        q.status = nl_at(status, at);
+        q.holes = rp::from(holes, at * deals);
+        q.world_out = rp::from(world_out, at * deals);
+        q.attempts = rp::from(attempts, at * deals);
+        q.status = rp::from(status, at);
         hipLaunchKernelGGL(k_nl_world, dim3(m), dim3(NW_BLOCK), 0, st, h->tab, h->prm, q);
     });
 }
@@ -1345,7 +1262,7 @@ int rp_nlhe_partition_device(rp_nlhe* h, uint64_t n, const float* mass, const ui
     if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = rp::profile_stream(h->prof);
-    return nl_chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
+    return rp::chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
         hipLaunchKernelGGL(k_nl_partition, dim3(m), dim3(NW_BLOCK), 0, st, mass + at * 256u, seen + at * 256u, world + at * 256u,
                            weights + at * RP_NLHE_WORLDS);
     });
@@ -1354,7 +1271,7 @@ int rp_nlhe_partition_device(rp_nlhe* h, uint64_t n, const float* mass, const ui
 int rp_nlhe_partition(rp_nlhe* h, uint64_t n, const float* mass, const uint8_t* seen, uint8_t* world, float* weights) {
     int rc = nw_partition_check(h, n, mass, seen, world, weights);
     if (rc || n == 0) return rc;
-    Stage s(h);
+    rp::Stage s(h->device, rp::profile_stream(h->prof));
     s.in(mass, n * 256u).in(seen, n * 256u).out(world, n * 256u).out(weights, n * RP_NLHE_WORLDS);
     if ((rc = s.up()) || (rc = rp_nlhe_partition_device(h, n, mass, seen, world, weights))) return rc;
     return s.down();
@@ -1370,7 +1287,7 @@ int rp_nlhe_belief_device(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls,
 int rp_nlhe_belief(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, uint8_t* world, float* weights, uint8_t* hole_world, uint8_t* status) {
     int rc = nw_belief_check(h, n, recalls, world, weights);
     if (rc || n == 0) return rc;
-    Stage s(h);
+    rp::Stage s(h->device, rp::profile_stream(h->prof));
     s.in(recalls, n).out(world, n * 256u).out(weights, n * RP_NLHE_WORLDS).out(hole_world, n * RP_NLHE_MAX_HOLES).out(status, n);
     if ((rc = s.up()) || (rc = rp_nlhe_belief_device(h, n, recalls, world, weights, hole_world, status))) return rc;
     return s.down();
@@ -1387,7 +1304,7 @@ int rp_nlhe_restrict(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, uint
                      uint64_t* holes, uint8_t* world_out, uint16_t* attempts, uint8_t* status) {
     int rc = nw_restrict_check(h, n, recalls, deals, holes);
     if (rc || n == 0 || deals == 0) return rc;
-    Stage s(h);
+    rp::Stage s(h->device, rp::profile_stream(h->prof));
     s.in(recalls, n).in(worlds, n * deals).out(holes, n * deals).out(world_out, n * deals).out(attempts, n * deals).out(status, n);
     if ((rc = s.up()) || (rc = rp_nlhe_restrict_device(h, n, recalls, deals, worlds, seed, first_id, holes, world_out, attempts, status))) return rc;
     return s.down();
@@ -1432,13 +1349,13 @@ int rp_nlhe_subgame_solve_device(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier*
     hipStream_t st = rp::profile_stream(h->prof);
     // the overflow rows of one launch's solves: launches of one call follow each other on the stream and share the region
     const size_t need = (size_t)std::min<uint64_t>(NS_CHUNK, n) * NS_ROWS_OVF * sizeof(NdRow);
-    if ((rc = nl_grow(h->subgame_rows, h->subgame_rows_bytes, need, st))) return rc;
-    return nl_chunks(n, NS_CHUNK, [&](uint64_t at, uint32_t m) {
+    if ((rc = rp::grow(h->subgame_rows, h->subgame_rows_bytes, need, st))) return rc;
+    return rp::chunks(n, NS_CHUNK, [&](uint64_t at, uint32_t m) {
         NsArgs q{};
         q.entries = entries + at;
         q.hole_world = hole_world + at * RP_NLHE_MAX_HOLES;
         q.weights = weights + at * RP_NLHE_WORLDS;
-        q.origin = nl_at(origin, at);
+        q.origin = rp::from(origin, at);
         q.iterations = args->iterations;
         q.rollouts = rollouts;
         q.rows_cap = rows ? args->rows_cap : 0u;
@@ -1462,7 +1379,7 @@ int rp_nlhe_subgame_solve(rp_nlhe* h, uint64_t n, const rp_nlhe_frontier* entrie
     uint32_t rollouts = 0;
     int rc = ns_check(h, n, entries, hole_world, weights, args, results, rows, deals, &rollouts);
     if (rc || n == 0) return rc;
-    Stage s(h);
+    rp::Stage s(h->device, rp::profile_stream(h->prof));
     s.in(entries, n).in(hole_world, n * RP_NLHE_MAX_HOLES).in(weights, n * RP_NLHE_WORLDS).in(origin, n);
     s.out(results, n).out(rows, n * args->rows_cap).out(deals, n * args->deals_cap);
     if ((rc = s.up()) || (rc = rp_nlhe_subgame_solve_device(h, n, entries, hole_world, weights, origin, args, results, rows, deals))) return rc;
@@ -1499,8 +1416,8 @@ int rp_nlhe_aivat_device(rp_nlhe* h, uint64_t n, const rp_aivat_hand* hands, flo
     if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = rp::profile_stream(h->prof);
-    return nl_chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
-        const NaArgs q{hands + at, hero + at, villain + at, chance + at, total + at, nl_at(n_action, at), nl_at(n_chance, at), nl_at(status, at)};
+    return rp::chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
+        const NaArgs q{hands + at, hero + at, villain + at, chance + at, total + at, rp::from(n_action, at), rp::from(n_chance, at), rp::from(status, at)};
         hipLaunchKernelGGL(k_nl_aivat, dim3(m), dim3(NA_BLOCK), 0, st, h->tab, h->prm, q);
     });
 }
@@ -1509,7 +1426,7 @@ int rp_nlhe_aivat(rp_nlhe* h, uint64_t n, const rp_aivat_hand* hands, float* her
                   uint8_t* n_chance, uint8_t* status) {
     int rc = na_check(h, n, hands, hero, villain, chance, total);
     if (rc || n == 0) return rc;
-    Stage s(h);
+    rp::Stage s(h->device, rp::profile_stream(h->prof));
     s.in(hands, n).out(hero, n).out(villain, n).out(chance, n).out(total, n).out(n_action, n).out(n_chance, n).out(status, n);
     if ((rc = s.up()) || (rc = rp_nlhe_aivat_device(h, n, hands, hero, villain, chance, total, n_action, n_chance, status))) return rc;
     return s.down();
@@ -1590,10 +1507,10 @@ NmArgs nm_args(const rp_nlhe_match_args* args, uint64_t at, uint32_t m, rp_aivat
     q.stacks[0] = args->stacks[0], q.stacks[1] = args->stacks[1];
     q.agent[0] = args->agent[0], q.agent[1] = args->agent[1];
     q.dealer = args->dealer, q.hero = args->hero, q.mirror = args->mirror, q.snap = args->snap, q.board_mode = args->board_mode;
-    q.hands = nl_at(hands, at);
-    q.won = nl_at(won, at);
-    q.rejected = nl_at(rejected, at);
-    q.status = nl_at(status, at);
+    q.hands = rp::from(hands, at);
+    q.won = rp::from(won, at);
+    q.rejected = rp::from(rejected, at);
+    q.status = rp::from(status, at);
     return q;
 }
 }  // namespace
@@ -1615,7 +1532,7 @@ int rp_nlhe_match_device(rp_nlhe* h0, rp_nlhe* h1, uint64_t n, const rp_nlhe_mat
     HIP_TRY(hipSetDevice(h0->device));
     hipStream_t st = rp::profile_stream(h0->prof), st1 = rp::profile_stream(h1->prof);
     if ((rc = nm_after(st, st1))) return rc;
-    return nl_chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
+    return rp::chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
         const NmArgs q = nm_args(args, at, m, hands, won, rejected, status);
         hipLaunchKernelGGL(k_nl_match, dim3((m + NM_BLOCK - 1u) / NM_BLOCK), dim3(NM_BLOCK), 0, st, h0->tab, h1->tab, h0->prm, q);
     });
@@ -1625,7 +1542,7 @@ int rp_nlhe_match(rp_nlhe* h0, rp_nlhe* h1, uint64_t n, const rp_nlhe_match_args
                   uint8_t* status) {
     int rc = nm_check(h0, h1, args);
     if (rc || n == 0) return rc;
-    Stage s(h0);
+    rp::Stage s(h0->device, rp::profile_stream(h0->prof));
     s.out(hands, n).out(won, n).out(rejected, n).out(status, n);
     if ((rc = s.up()) || (rc = rp_nlhe_match_device(h0, h1, n, args, hands, won, rejected, status))) return rc;
     return s.down();
@@ -1686,22 +1603,22 @@ int rp_nlhe_translate_device(rp_nlhe* h, uint64_t n, const rp_nlhe_translate_arg
     if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = rp::profile_stream(h->prof);
-    return nl_chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
+    return rp::chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
         NxArgs q{};
         q.hands = hands + at;
-        q.pov = nl_at(pov, at);
-        q.upto = nl_at(upto, at);
+        q.pov = rp::from(pov, at);
+        q.upto = rp::from(upto, at);
         q.hash = rp_node_hash_step(args->seed, 3);
         q.first_id = args->first_id + at;
         q.n = m;
         q.kind = args->kind;
-        q.recalls = nl_at(recalls, at);
-        q.play_edges = nl_at(play_edges, at * RP_AIVAT_MAX_PLAYS);
-        q.past = nl_at(past, at);
-        q.present = nl_at(present, at);
-        q.choices = nl_at(choices, at);
-        q.n_choices = nl_at(n_choices, at);
-        q.status = nl_at(status, at);
+        q.recalls = rp::from(recalls, at);
+        q.play_edges = rp::from(play_edges, at * RP_AIVAT_MAX_PLAYS);
+        q.past = rp::from(past, at);
+        q.present = rp::from(present, at);
+        q.choices = rp::from(choices, at);
+        q.n_choices = rp::from(n_choices, at);
+        q.status = rp::from(status, at);
         hipLaunchKernelGGL(k_nl_translate, dim3((m + NX_BLOCK - 1u) / NX_BLOCK), dim3(NX_BLOCK), 0, st, h->prm, q);
     });
 }
@@ -1711,7 +1628,7 @@ int rp_nlhe_translate(rp_nlhe* h, uint64_t n, const rp_nlhe_translate_args* args
                       uint8_t* n_choices, uint8_t* status) {
     int rc = nx_check(h, n, args, hands);
     if (rc || n == 0) return rc;
-    Stage s(h);
+    rp::Stage s(h->device, rp::profile_stream(h->prof));
     s.in(hands, n).in(pov, n).in(upto, n);
     s.out(recalls, n).out(play_edges, n * RP_AIVAT_MAX_PLAYS).out(past, n).out(present, n).out(choices, n).out(n_choices, n).out(status, n);
     if ((rc = s.up()) ||
@@ -1809,12 +1726,12 @@ int rp_nlhe_search_match_device(rp_nlhe* h0, rp_nlhe* h1, uint64_t n, const rp_n
         h0->search_post = reinterpret_cast<NsmPost*>(hp_);
         h0->search_post_dev = reinterpret_cast<NsmPost*>(dp_);
     }
-    if ((rc = nl_grow(h0->search_scratch, h0->search_scratch_bytes, NsmScratch(nullptr).bytes, st))) return rc;
+    if ((rc = rp::grow(h0->search_scratch, h0->search_scratch_bytes, NsmScratch(nullptr).bytes, st))) return rc;
     const NsmScratch sc(static_cast<unsigned char*>(h0->search_scratch));
     const bool any_search = args->search[0] != 0u || args->search[1] != 0u;
     if (any_search) {  // the overflow rows of one launch's solves, as rp_nlhe_subgame_solve_device sizes them
         const size_t need = (size_t)std::min<uint64_t>(NSM_CHUNK, n) * NS_ROWS_OVF * sizeof(NdRow);
-        if ((rc = nl_grow(h0->subgame_rows, h0->subgame_rows_bytes, need, st))) return rc;
+        if ((rc = rp::grow(h0->subgame_rows, h0->subgame_rows_bytes, need, st))) return rc;
     }
     rp_nlhe* seat[2] = {h0, h1};
     for (uint64_t at = 0; at < n; at += NSM_CHUNK) {
@@ -1826,8 +1743,8 @@ int rp_nlhe_search_match_device(rp_nlhe* h0, rp_nlhe* h1, uint64_t n, const rp_n
         q.visit_threshold = args->visit_threshold;
         q.steps_cap = steps ? args->steps_cap : 0u;
         q.hands = sc.hands;
-        q.searched = nl_at(searched, at);
-        q.unsolved = nl_at(unsolved, at);
+        q.searched = rp::from(searched, at);
+        q.unsolved = rp::from(unsolved, at);
         q.steps = q.steps_cap ? steps + at * args->steps_cap : nullptr;
         q.results = sc.results;
         q.belief_status = sc.belief_status;
@@ -1890,7 +1807,7 @@ int rp_nlhe_search_match(rp_nlhe* h0, rp_nlhe* h1, uint64_t n, const rp_nlhe_sea
     if (rc || n == 0) return rc;
     if (!h0) return rp::fail(RP_ERR_INVALID, "rp_nlhe_search_match: NULL handle");
     if ((rc = nm_pair_check("rp_nlhe_search_match", h0, h1))) return rc;
-    Stage s(h0);
+    rp::Stage s(h0->device, rp::profile_stream(h0->prof));
     s.out(hands, n).out(won, n).out(rejected, n).out(status, n).out(searched, n).out(unsolved, n).out(steps, n * args->steps_cap);
     if ((rc = s.up()) || (rc = rp_nlhe_search_match_device(h0, h1, n, args, hands, won, rejected, status, searched, unsolved, steps))) return rc;
     return s.down();
@@ -1940,7 +1857,7 @@ int rp_nlhe_table_census_device(rp_nlhe* h, rp_census* out) {
     hipStream_t st = rp::profile_stream(h->prof);
     const uint64_t slots = 1ull << h->cap_log2;
     const uint32_t nseg = (uint32_t)((slots + RP_NLHE_CENSUS_SEGMENT - 1u) / RP_NLHE_CENSUS_SEGMENT);
-    int rc = nl_grow(h->census_scratch, h->census_scratch_bytes, nc_partial_bytes(nseg), st);
+    int rc = rp::grow(h->census_scratch, h->census_scratch_bytes, nc_partial_bytes(nseg), st);
     if (rc) return rc;
     const NcPartials part = nc_partials(h->census_scratch, nseg);
     hipLaunchKernelGGL(k_nl_census_scan, dim3(nseg), dim3(NC_SCAN_BLOCK), 0, st, h->tab, nseg, part);
@@ -1951,7 +1868,7 @@ int rp_nlhe_table_census_device(rp_nlhe* h, rp_census* out) {
 
 int rp_nlhe_table_census(rp_nlhe* h, rp_census* out) {
     if (!h || !out) return rp::fail(RP_ERR_INVALID, "rp_nlhe_table_census: NULL argument");
-    Stage s(h);
+    rp::Stage s(h->device, rp::profile_stream(h->prof));
     s.out(out, 1);
     int rc;
     if ((rc = s.up()) || (rc = rp_nlhe_table_census_device(h, out))) return rc;
@@ -2055,7 +1972,7 @@ uint64_t nl_default_headroom(const rp_nlhe* h) { return (uint64_t)h->batch * 153
 uint32_t nt_blocks(const rp_nlhe* h, uint64_t lanes) {
     return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((lanes + NT_BLOCK - 1u) / NT_BLOCK, 1u), h->grid_cap);
 }
-// The handle moves onto a fresh table of 2^new_log2 slots.  Like nl_grow's regions, the old arrays may still be read by launches
+// The handle moves onto a fresh table of 2^new_log2 slots.  Like rp::grow's regions, the old arrays may still be read by launches
 // queued earlier, and the rehash itself reads them: they are freed only after the stream has passed the rehash.
 int nl_resize(rp_nlhe* h, uint32_t new_log2) {
     if (new_log2 == h->cap_log2) return RP_OK;
@@ -2155,7 +2072,7 @@ int rp_nlhe_export_device(rp_nlhe* h, uint64_t cap, uint64_t* n, uint64_t* past_
     const uint32_t nseg = (uint32_t)((slots + NT_SEGMENT - 1u) / NT_SEGMENT);
     // [counts nseg][offsets nseg][total, pad][the scan's scratch]
     const size_t words = (size_t)2 * nseg + 2;
-    int rc = nl_grow(h->table_scratch, h->table_scratch_bytes, words * 4u + rp::ss::scan_scratch_bytes(nseg), st);
+    int rc = rp::grow(h->table_scratch, h->table_scratch_bytes, words * 4u + rp::ss::scan_scratch_bytes(nseg), st);
     if (rc) return rc;
     uint32_t* seg_count = static_cast<uint32_t*>(h->table_scratch);
     uint32_t *seg_off = seg_count + nseg, *total = seg_off + nseg;
@@ -2185,12 +2102,12 @@ int rp_nlhe_import_device(rp_nlhe* h, uint64_t n, const uint64_t* past_dev, cons
     uint64_t chunk = 1ull << 26;
     if (const char* env = getenv("RP_NLHE_IMPORT_CHUNK")) chunk = (uint64_t)std::min(1 << 26, std::max(1, atoi(env)));
     chunk = std::min(chunk, n);
-    if ((rc = nl_grow(h->table_scratch, h->table_scratch_bytes, (size_t)(chunk + 2u) * 4u, st))) return rc;
+    if ((rc = rp::grow(h->table_scratch, h->table_scratch_bytes, (size_t)(chunk + 2u) * 4u, st))) return rc;
     uint32_t* rows = static_cast<uint32_t*>(h->table_scratch);
     uint32_t* flags = rows + chunk;  // [0] error flags, [1] unused
     HIP_TRY(hipMemsetAsync(flags, 0, 8, st));
     h->keys_valid = false;
-    rc = nl_chunks(n, chunk, [&](uint64_t at, uint32_t m) {
+    rc = rp::chunks(n, chunk, [&](uint64_t at, uint32_t m) {
         const dim3 grid(nt_blocks(h, m));
         hipLaunchKernelGGL(k_nl_table_find, grid, dim3(NT_BLOCK), 0, st, h->tab, m, past_dev + at, present_dev + at, choices_dev + at, rows, flags);
         hipLaunchKernelGGL(k_nl_table_write, grid, dim3(NT_BLOCK), 0, st, h->tab, m, rows, enc_dev + at * NLMC_A);

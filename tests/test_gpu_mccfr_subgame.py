@@ -237,6 +237,9 @@ def test_host_form_equals_device_form_and_the_blueprint_is_untouched(gpu):
     priors = np.array([games.subgame_entry(b.game, (1, 4), (K.CHECK, K.BET), 1, True)[0][0]] * 3, SUBGAME_PRIOR_DTYPE)
     host, host_rows = solve(b, entries, 7)
     host_belief = b.solver.subgame_belief(priors)
+    bare = {"world_of": np.zeros((3, 16), np.uint8), "weights": np.zeros((3, 4), np.float32)}  # status is optional: the host form without it
+    _lib.check(b.solver._lib.rp_mccfr_subgame_belief(b.solver._h, 3, priors.ctypes.data, bare["world_of"].ctypes.data, bare["weights"].ctypes.data, None))
+    assert all(bare[f].tobytes() == host_belief[f].tobytes() for f in bare)
     dev = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).cuda()
     d_entries, d_priors = dev(entries), dev(priors)
     d_results = torch.zeros(host.nbytes, dtype=torch.uint8, device="cuda")
