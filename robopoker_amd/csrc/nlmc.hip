@@ -1007,11 +1007,27 @@ int rp_nlhe_memory(rp_nlhe* h, uint64_t n, const uint64_t* past, const uint32_t*
 // ---- ranges (nlmc_range.hpp): one workgroup per recall, at most NR_CHUNK recalls per launch
 namespace {
 constexpr uint64_t NR_CHUNK = 1ull << 20;
+// items per launch of the calls cut by NR_CHUNK (ranges, frontier payoffs, worlds, AIVAT, matches, translation): RP_NLHE_READ_CHUNK
+// (tests: a batch of a few items in several launches), 1 .. 2^20, else NR_CHUNK.  Read at every call
+int nr_chunk(uint64_t* out) {
+    *out = NR_CHUNK;
+    const char* s = getenv("RP_NLHE_READ_CHUNK");
+    if (!s || !*s) return RP_OK;
+    char* end = nullptr;
+    const long long v = strtoll(s, &end, 10);
+    if (*end || v < 1 || v > (long long)NR_CHUNK)
+        return rp::fail(RP_ERR_INVALID, "RP_NLHE_READ_CHUNK is '%s': 1 .. %llu", s, (unsigned long long)NR_CHUNK);
+    *out = (uint64_t)v;
+    return RP_OK;
+}
 int nr_launch(rp_nlhe* h, int kind, int normalize, uint64_t n, const rp_nlhe_recall* recalls, uint32_t* count, uint64_t* holes, float* reach,
               float* mass, uint8_t* seen, uint8_t* status) {
+    uint64_t chunk = 0;
+    int rc = nr_chunk(&chunk);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = rp::profile_stream(h->prof);
-    return rp::chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
+    return rp::chunks(n, chunk, [&](uint64_t at, uint32_t m) {
         NrArgs q{};
         q.recalls = recalls + at;
         q.kind = kind;
@@ -1096,9 +1112,11 @@ int rp_nlhe_frontier_payoffs_device(rp_nlhe* h, uint64_t n, const rp_nlhe_fronti
                                     uint64_t first_id, float* payoffs, int16_t* won, uint8_t* status) {
     int rc = nf_check(h, n, frontiers, bias, &rollouts, payoffs);
     if (rc || n == 0) return rc;
+    uint64_t chunk = 0;
+    if ((rc = nr_chunk(&chunk))) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = rp::profile_stream(h->prof);
-    return rp::chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
+    return rp::chunks(n, chunk, [&](uint64_t at, uint32_t m) {
         NfArgs q{};
         q.frontiers = frontiers + at;
         q.bias = bias;
@@ -1214,9 +1232,12 @@ constexpr uint32_t NW_MAX_DEALS = 4096u;
 // belief (deals == 0) and restrict (deals > 0) are one kernel: every pointer in device memory
 int nw_launch(rp_nlhe* h, uint64_t n, const rp_nlhe_recall* recalls, uint8_t* world, float* weights, uint8_t* hole_world, uint32_t deals,
               const uint8_t* worlds, uint64_t seed, uint64_t first_id, uint64_t* holes, uint8_t* world_out, uint16_t* attempts, uint8_t* status) {
+    uint64_t chunk = 0;
+    int rc = nr_chunk(&chunk);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = rp::profile_stream(h->prof);
-    return rp::chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
+    return rp::chunks(n, chunk, [&](uint64_t at, uint32_t m) {
         NwArgs q{};
         q.recalls = recalls + at;
         q.world = rp::from(world, at * 256u);
@@ -1260,9 +1281,11 @@ extern "C" {
 int rp_nlhe_partition_device(rp_nlhe* h, uint64_t n, const float* mass, const uint8_t* seen, uint8_t* world, float* weights) {
     int rc = nw_partition_check(h, n, mass, seen, world, weights);
     if (rc || n == 0) return rc;
+    uint64_t chunk = 0;
+    if ((rc = nr_chunk(&chunk))) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = rp::profile_stream(h->prof);
-    return rp::chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
+    return rp::chunks(n, chunk, [&](uint64_t at, uint32_t m) {
         hipLaunchKernelGGL(k_nl_partition, dim3(m), dim3(NW_BLOCK), 0, st, mass + at * 256u, seen + at * 256u, world + at * 256u,
                            weights + at * RP_NLHE_WORLDS);
     });
@@ -1414,9 +1437,11 @@ int rp_nlhe_aivat_device(rp_nlhe* h, uint64_t n, const rp_aivat_hand* hands, flo
                          uint8_t* n_action, uint8_t* n_chance, uint8_t* status) {
     int rc = na_check(h, n, hands, hero, villain, chance, total);
     if (rc || n == 0) return rc;
+    uint64_t chunk = 0;
+    if ((rc = nr_chunk(&chunk))) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = rp::profile_stream(h->prof);
-    return rp::chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
+    return rp::chunks(n, chunk, [&](uint64_t at, uint32_t m) {
         const NaArgs q{hands + at, hero + at, villain + at, chance + at, total + at, rp::from(n_action, at), rp::from(n_chance, at), rp::from(status, at)};
         hipLaunchKernelGGL(k_nl_aivat, dim3(m), dim3(NA_BLOCK), 0, st, h->tab, h->prm, q);
     });
@@ -1529,10 +1554,12 @@ int rp_nlhe_match_device(rp_nlhe* h0, rp_nlhe* h1, uint64_t n, const rp_nlhe_mat
     int rc = nm_check(h0, h1, args);
     if (rc || n == 0) return rc;
     if (!h1) h1 = h0;
+    uint64_t chunk = 0;
+    if ((rc = nr_chunk(&chunk))) return rc;
     HIP_TRY(hipSetDevice(h0->device));
     hipStream_t st = rp::profile_stream(h0->prof), st1 = rp::profile_stream(h1->prof);
     if ((rc = nm_after(st, st1))) return rc;
-    return rp::chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
+    return rp::chunks(n, chunk, [&](uint64_t at, uint32_t m) {
         const NmArgs q = nm_args(args, at, m, hands, won, rejected, status);
         hipLaunchKernelGGL(k_nl_match, dim3((m + NM_BLOCK - 1u) / NM_BLOCK), dim3(NM_BLOCK), 0, st, h0->tab, h1->tab, h0->prm, q);
     });
@@ -1601,9 +1628,11 @@ int rp_nlhe_translate_device(rp_nlhe* h, uint64_t n, const rp_nlhe_translate_arg
                              uint64_t* choices, uint8_t* n_choices, uint8_t* status) {
     int rc = nx_check(h, n, args, hands);
     if (rc || n == 0) return rc;
+    uint64_t chunk = 0;
+    if ((rc = nr_chunk(&chunk))) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = rp::profile_stream(h->prof);
-    return rp::chunks(n, NR_CHUNK, [&](uint64_t at, uint32_t m) {
+    return rp::chunks(n, chunk, [&](uint64_t at, uint32_t m) {
         NxArgs q{};
         q.hands = hands + at;
         q.pov = rp::from(pov, at);

@@ -286,3 +286,64 @@ def test_a_tree_of_frontiers_overflows_and_the_row_limit_is_a_status(gpu):
         want = D.solve(table, bp, fr, entry, 0, iterations=iterations, seed=SEED)
         assert want["status"] == status
         D.compare(results[0], rows[0], want, 4)
+
+
+# ---- more solves than one launch takes ----
+MS_MAX_CHUNK = 2048  # solves per launch (robopoker_amd/csrc/mccfr_subgame.hpp)
+
+
+def cycle(b, n):
+    """n solves: the cases in turn under origin 0, every seventh one malformed, every fifth at another origin"""
+    bad = K.malformed(b.entries[1], b.table)
+    entries = [bad[(i // 7) % len(bad)][1] if i % 7 == 3 else b.entries[i % len(b.entries)] for i in range(n)]
+    origin = [(NONE, ENTRY, 1)[i % 3] if i % 5 == 0 else 0 for i in range(n)]  # solve 0 without frontiers: not what the last one wants
+    return np.array(entries, SUBGAME_ENTRY_DTYPE), np.array(origin, np.uint8)
+
+
+def test_one_solve_more_than_a_launch_chunk(gpu):
+    """2 049 Leduc solves of 7 iterations with frontiers: the second launch chunk holds one solve, whose local profile (Pick rows
+    included) lies where solve 0 of the first chunk left its own; in launches of 3 + 3 + 1 iterations the profiles also cross launches.
+    The handle is a new one, so that its profile region grows from the 5 solves of the first call to the 2 048 of a full chunk."""
+    b = bench("leduc", "trained")
+    n, cap, first_id = MS_MAX_CHUNK + 1, 4, 1000
+    entries, origin = cycle(b, n)
+    assert origin[MS_MAX_CHUNK] == 0 and origin[0] == NONE and {0, ENTRY, NONE} <= set(origin)
+    solver = Solver(b.game, "floored", "linear", "external", batch=1, seed=3)
+    solver.load_rows(b.solver.export(), b.solver.epoch)
+    assert solver.export().tobytes() == b.solver.export().tobytes()
+    fr = C.builtin_frontiers(b.game, 4)
+    C.set_frontiers(solver, fr)
+    run = lambda at, end, first: solver.depth_solve(entries[at:end], origin[at:end], iterations=7, seed=SEED, first_id=first, rows_cap=cap)
+    both = lambda out: out[0].tobytes() + out[1].tobytes()
+    saved = os.environ.pop("RP_MCCFR_SUBGAME_SEGMENT", None)
+    try:
+        few = run(0, 5, first_id)
+        os.environ["RP_MCCFR_SUBGAME_SEGMENT"] = "3"
+        whole = run(0, n, first_id)  # the region grows
+        again = run(0, n, first_id)  # both chunks start in what the call before left there
+        dev = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).cuda()
+        d_entries, d_origin = dev(entries), dev(origin)
+        d_results, d_rows = (torch.zeros(x.nbytes, dtype=torch.uint8, device="cuda") for x in whole)
+        torch.cuda.synchronize()
+        solver.depth_solve_device(n, d_entries.data_ptr(), d_results.data_ptr(), d_rows.data_ptr(), d_origin.data_ptr(), iterations=7, seed=SEED,
+                                  first_id=first_id, rows_cap=cap)
+        solver.sync()
+        head, tail = run(0, MS_MAX_CHUNK, first_id), run(MS_MAX_CHUNK, n, first_id + MS_MAX_CHUNK)
+        unshifted = run(MS_MAX_CHUNK, n, first_id)
+        os.environ.pop("RP_MCCFR_SUBGAME_SEGMENT")
+        one_launch_per_chunk = run(0, n, first_id)
+    finally:
+        os.environ.pop("RP_MCCFR_SUBGAME_SEGMENT", None)
+        if saved is not None:
+            os.environ["RP_MCCFR_SUBGAME_SEGMENT"] = saved
+    results, rows = whole
+    last = results[MS_MAX_CHUNK]
+    assert last["status"] == M.OK and last["n_actions"] > 1 and last["n_rows"] > 1 and last["frontiers"] > 0 and last["iterations"] == 7
+    assert len(set(results["status"])) > 3 and few[0].tobytes() == results[:5].tobytes() and few[1].tobytes() == rows[:5].tobytes()
+    for f in (0, 1):
+        assert np.concatenate([head[f], tail[f]]).tobytes() == whole[f].tobytes(), ("results", "rows")[f]
+    assert both(again) == both(whole) == both(one_launch_per_chunk)
+    assert d_results.cpu().numpy().tobytes() == results.tobytes() and d_rows.cpu().numpy().tobytes() == rows.tobytes()
+    assert unshifted[0].tobytes() != tail[0].tobytes()  # the id matters
+    want = D.solve(b.table, b.bp, fr, entries[MS_MAX_CHUNK], 0, index=MS_MAX_CHUNK, iterations=7, seed=SEED, first_id=first_id)
+    D.compare(last, rows[MS_MAX_CHUNK], want, cap)

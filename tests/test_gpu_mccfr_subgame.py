@@ -329,3 +329,62 @@ def test_known_answers_leduc_reach_conditioned(blueprints):
     _, _, _, results, _ = known_answer_solves(blueprints["leduc"], (K.CHECK, K.BET), 1, True)
     for i, holes in enumerate(DEALS):
         assert results["sum_regret"][i] < 0.03, f"deal {holes}: sum_regret {results['sum_regret'][i]:.6f}"
+
+
+# ---- more solves than one launch takes ----
+MS_MAX_CHUNK = 2048  # solves per launch (robopoker_amd/csrc/mccfr_subgame.hpp)
+
+
+def cycle(b, n, shift=0):
+    """n solves: the cases in turn from case `shift` on, every seventh one malformed"""
+    bad = K.malformed(b.entries[1], b.table)
+    entries = [bad[(i // 7) % len(bad)][1] if i % 7 == 3 else b.entries[(i + shift) % len(b.entries)] for i in range(n)]
+    return np.array(entries, SUBGAME_ENTRY_DTYPE)
+
+
+def test_one_solve_more_than_a_launch_chunk(gpu):
+    """2 049 Kuhn solves of 7 iterations: the second launch chunk holds one solve, whose local profile lies where solve 0 of the first
+    chunk left its own; in launches of 3 + 3 + 1 iterations the profiles also cross launches.  The handle is a new one, so that its
+    profile region grows from the 5 solves of the first call to the 2 048 of a full chunk."""
+    b = bench("kuhn", "trained")
+    n, cap, first_id = MS_MAX_CHUNK + 1, 4, 1000
+    labels = [label for label, _ in b.cases]
+    entries = cycle(b, n, (labels.index("root, W=4") - MS_MAX_CHUNK) % len(labels))  # the last solve: four worlds to draw from by its id
+    assert entries[MS_MAX_CHUNK].tobytes() == b.entries[labels.index("root, W=4")].tobytes()
+    solver = Solver(b.game, "floored", "linear", "external", batch=1, seed=3)
+    solver.load_rows(b.solver.export(), b.solver.epoch)
+    assert solver.export().tobytes() == b.solver.export().tobytes()
+    run = lambda part, first: solver.subgame_solve(part, iterations=7, seed=SEED, first_id=first, rows_cap=cap)
+    both = lambda out: out[0].tobytes() + out[1].tobytes()
+    saved = os.environ.pop("RP_MCCFR_SUBGAME_SEGMENT", None)
+    try:
+        few = run(entries[:5], first_id)
+        os.environ["RP_MCCFR_SUBGAME_SEGMENT"] = "3"
+        whole = run(entries, first_id)  # the region grows
+        again = run(entries, first_id)  # both chunks start in what the call before left there
+        dev = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).cuda()
+        d_entries = dev(entries)
+        d_results, d_rows = (torch.zeros(x.nbytes, dtype=torch.uint8, device="cuda") for x in whole)
+        torch.cuda.synchronize()
+        solver.subgame_solve_device(n, d_entries.data_ptr(), d_results.data_ptr(), d_rows.data_ptr(), iterations=7, seed=SEED, first_id=first_id,
+                                    rows_cap=cap)
+        solver.sync()
+        head, tail = run(entries[:MS_MAX_CHUNK], first_id), run(entries[MS_MAX_CHUNK:], first_id + MS_MAX_CHUNK)
+        unshifted = run(entries[MS_MAX_CHUNK:], first_id)
+        os.environ.pop("RP_MCCFR_SUBGAME_SEGMENT")
+        one_launch_per_chunk = run(entries, first_id)
+    finally:
+        os.environ.pop("RP_MCCFR_SUBGAME_SEGMENT", None)
+        if saved is not None:
+            os.environ["RP_MCCFR_SUBGAME_SEGMENT"] = saved
+    results, rows = whole
+    last = results[MS_MAX_CHUNK]
+    assert last["status"] == M.OK and last["n_actions"] > 1 and last["n_rows"] > 1 and last["iterations"] == 7
+    assert len(set(results["status"])) > 3 and few[0].tobytes() == results[:5].tobytes() and few[1].tobytes() == rows[:5].tobytes()
+    for f in (0, 1):
+        assert np.concatenate([head[f], tail[f]]).tobytes() == whole[f].tobytes(), ("results", "rows")[f]
+    assert both(again) == both(whole) == both(one_launch_per_chunk)
+    assert d_results.cpu().numpy().tobytes() == results.tobytes() and d_rows.cpu().numpy().tobytes() == rows.tobytes()
+    assert unshifted[0].tobytes() != tail[0].tobytes()  # the id matters
+    want = M.solve(b.table, b.bp, entries[MS_MAX_CHUNK], index=MS_MAX_CHUNK, iterations=7, seed=SEED, first_id=first_id)
+    M.compare(last, rows[MS_MAX_CHUNK], want, cap)

@@ -12,6 +12,7 @@ import torch
 
 import nlhe_aivat_cases as K
 import nlhe_aivat_model as AM
+import nlhe_read_chunk as RC
 from robopoker_amd import _lib
 from robopoker_amd.nlhe import AivatHand, NlheSolver
 
@@ -120,3 +121,33 @@ def test_arguments(gpu):
     s.step()
     assert s.epoch == 1 and s.counters()[2] > 0
 
+
+def test_the_corrections_do_not_depend_on_the_launch_chunk(gpu):
+    """RP_NLHE_READ_CHUNK (tests/nlhe_read_chunk.py) cuts the batch into launches of 1, 3, n - 1 and n hands: every launch reads its
+    hands and writes its seven outputs from its own item on"""
+    m, s = K.model(), solver()
+    n = len(HANDS)
+    dev_in = torch.from_numpy(AivatHand.pack(HANDS).view(np.uint8).copy()).to("cuda")
+    with RC.read_chunk(None):
+        want = s.aivat(HANDS)
+    assert n >= 7 and len(set(want["status"])) > 3
+    for chunk in RC.cuts(n):
+        with RC.read_chunk(chunk):
+            host, dev = s.aivat(HANDS), s.aivat_device(dev_in)
+            s.sync()
+        RC.same(host, want, (chunk, "host"))
+        RC.same({k: v.cpu().numpy() for k, v in dev.items()}, want, (chunk, "device"))
+        for j, name in enumerate(K.NAMES):  # the model itself, on every hand of every launch
+            check(host, j, m.want[j], (chunk, name))
+    # 15 hands and one: the one-byte arrays (n_action, n_chance, status) end off the staging arena's alignment
+    with RC.read_chunk(3):
+        RC.same(s.aivat(HANDS[1:]), RC.tail(want, 1), "15 hands")
+    with RC.read_chunk(1):
+        RC.same(s.aivat(HANDS[-1:]), RC.tail(want, n - 1), "one hand")
+    # n_action, n_chance and status left out, in launches of 3
+    lib, hd = _lib.load(), AivatHand.pack(HANDS)
+    f = [np.zeros(n, np.float32) for _ in FLOATS]
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    with RC.read_chunk(3):
+        assert lib.rp_nlhe_aivat(s._h, n, p(hd), *map(p, f), None, None, None) == _lib.RP_OK
+    RC.same(f, [want[k] for k in FLOATS], "without the counts and the status")

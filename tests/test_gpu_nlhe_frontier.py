@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import nlhe_policy_model as PM
+import nlhe_read_chunk as RC
 import nlhe_rollout_model as FM
 import oracle_nlhe as ON
 from robopoker_amd import _lib
@@ -244,3 +245,42 @@ def test_arguments(gpu):
     assert (pay4096 == np.float32(-2.0)).all() and status4096[0] == FM.OK
     s.step()
     assert s.epoch == 1 and s.counters()[2] > 0
+
+
+def test_the_payoffs_do_not_depend_on_the_launch_chunk(gpu, model):
+    """RP_NLHE_READ_CHUNK (tests/nlhe_read_chunk.py) cuts the batch into launches of 1, 3, n - 1 and n frontiers: every launch counts its
+    ids on from first_id and writes payoffs, won and status from its own item on"""
+    m, s = model, model.solver()
+    fr, n = frontiers(), len(CASES)
+    dev_in = on_device(fr)
+    call = lambda part, first_id: s.frontier_payoffs(part, BIAS, ROLLOUTS, SEED, first_id, return_won=True)
+    with RC.read_chunk(None):
+        want = call(fr, FIRST_ID)
+    assert n % 16 and FIRST_ID and len(set(want[1])) == 4
+
+    def against_the_model(got, what):
+        for i, name in enumerate(NAMES):
+            want_status, want_pay, want_won = m.want[i]
+            assert got[1][i] == want_status and np.array_equal(got[2][i], want_won) and np.array_equal(bits(got[0][i]), bits(want_pay)), (what, name)
+
+    for chunk in RC.cuts(n):
+        with RC.read_chunk(chunk):
+            host = call(fr, FIRST_ID)
+            dev = s.frontier_payoffs_device(dev_in, BIAS, ROLLOUTS, SEED, FIRST_ID, return_won=True)
+            s.sync()
+        RC.same(host, want, (chunk, "host"))
+        RC.same([t.cpu().numpy() for t in dev], want, (chunk, "device"))
+        against_the_model(host, chunk)  # the river decision is the first frontier of the third launch of 3
+        if chunk < n:  # the items from the first cut on: a call of their own under first_id + chunk, in one launch
+            with RC.read_chunk(None):
+                RC.same(call(fr[chunk:], FIRST_ID + chunk), RC.tail(want, chunk), (chunk, "ids"))
+                assert chunk == n - 1 or not equal(call(fr[chunk:], FIRST_ID), RC.tail(want, chunk))  # the last frontier is malformed
+    at = NAMES.index("river")
+    with RC.read_chunk(1):  # one frontier: the status byte ends the staging arena off its alignment
+        RC.same(call(fr[at: at + 1], FIRST_ID + at), [x[at: at + 1] for x in want], "one frontier")
+    # won and status left out, in launches of 3
+    lib, packed, pay = _lib.load(), Frontier.pack(fr), np.zeros((n, 4, 4), np.float32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    with RC.read_chunk(3):
+        assert lib.rp_nlhe_frontier_payoffs(s._h, n, p(packed), BIAS, ROLLOUTS, SEED, FIRST_ID, p(pay), None, None) == _lib.RP_OK
+    assert pay.tobytes() == want[0].tobytes()

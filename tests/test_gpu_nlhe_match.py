@@ -13,6 +13,7 @@ import torch
 import nlhe_aivat_model as AM
 import nlhe_match_cases as K
 import nlhe_match_model as MM
+import nlhe_read_chunk as RC
 from robopoker_amd import _lib
 from robopoker_amd.nlhe import AIVAT_DTYPE, AivatHand, NlheSolver
 
@@ -230,3 +231,55 @@ def test_lookup_table_encoders(gpu):
         s.close()
     for t in ta + tb:
         t.close()
+
+
+def test_the_hands_do_not_depend_on_the_launch_chunk(pair):
+    """RP_NLHE_READ_CHUNK (tests/nlhe_read_chunk.py) cuts the 65 hands of "main" into launches of 1, 3, 64 and 65: every launch counts
+    its hand ids on from first_id.  The first id is odd and the hands are mirrored, so the pairs are the hands (1, 2), (3, 4), ...:
+    launches of 3 keep (3, 4) together and part (5, 6)"""
+    s0, s1 = pair
+    _, n, args, one = K.CONFIGS[K.NAMES.index("main")]
+    assert n % 16 and args.first_id % 2 == 1 and args.mirror and not one
+    fields = ("hands", "won", "rejected", "status")
+
+    def device(count, **kw):
+        dev = s0.match_device(count, s1, **kw)
+        s0.sync()
+        out = {k: v.cpu().numpy() for k, v in dev.items()}
+        return dict(out, hands=out["hands"].reshape(-1).view(AIVAT_DTYPE))
+
+    with RC.read_chunk(None):
+        want = s0.match(n, s1, **args.kwargs())
+    check(want, "main")
+    assert want["rejected"].any() and tuple(want["hands"][5]["hole"]) == tuple(want["hands"][6]["hole"][::-1])
+    for chunk in RC.cuts(n):
+        with RC.read_chunk(chunk):
+            host, dev = s0.match(n, s1, **args.kwargs()), device(n, **args.kwargs())
+        RC.same(host, want, (chunk, "host"))
+        RC.same(dev, want, (chunk, "device"))
+        check(host, "main")  # the model itself, on every hand of every launch
+        if chunk < n:  # the hands from the first cut on: a call of their own under first_id + chunk, in one launch
+            with RC.read_chunk(None):
+                alone = s0.match(n - chunk, s1, **dict(args.kwargs(), first_id=args.first_id + chunk))
+                RC.same(alone, RC.tail(want, chunk), (chunk, "ids"))
+                unshifted = s0.match(n - chunk, s1, **args.kwargs())
+                assert unshifted["hands"].tobytes() != want["hands"][chunk:].tobytes()
+    with RC.read_chunk(1):  # one hand: the one-byte arrays end off the staging arena's alignment
+        RC.same(s0.match(1, s1, **dict(args.kwargs(), first_id=args.first_id + 6)), {k: want[k][6:7] for k in fields}, "one hand")
+    # the short-stacked mirrored hands of an even first id, 17 of them, in launches of 3: pairs (2, 3), (8, 9), (14, 15) are parted
+    name = "fish dirac snap 1 mirror 1"
+    _, n17, args17, _ = K.CONFIGS[K.NAMES.index(name)]
+    assert n17 == 17 and args17.first_id % 2 == 0 and args17.mirror
+    with RC.read_chunk(3):
+        check(s0.match(n17, s1, **args17.kwargs()), name)
+        check(device(n17, **args17.kwargs()), name)
+    # every output but one left out, in launches of 3
+    lib, a = _lib.load(), NlheSolver._match_args(**args.kwargs())
+    p = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
+    won, hands = np.zeros(n, np.int16), np.zeros(n, AIVAT_DTYPE)
+    with RC.read_chunk(3):
+        assert lib.rp_nlhe_match(s0._h, s1._h, n, C.byref(a), None, p(won), None, None) == _lib.RP_OK
+        assert lib.rp_nlhe_match(s0._h, s1._h, n, C.byref(a), p(hands), None, None, None) == _lib.RP_OK
+        assert lib.rp_nlhe_match_device(s0._h, s1._h, n, C.byref(a), None, None, None, None) == _lib.RP_OK
+        s0.sync()
+    RC.same((won, hands), (want["won"], want["hands"]), "one output alone")

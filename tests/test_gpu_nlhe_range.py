@@ -8,6 +8,7 @@ infosets has a row, and two malformed recalls between valid ones.  The table has
 infosets the model asks for (chosen by a hash of the key; never more than 960), which leaves found, absent, off-home-slot and
 all-zero-weight infosets in every recall but the absent one.  Each of these is asserted to occur."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -15,6 +16,7 @@ import torch
 
 import nlhe_policy_model as PM
 import nlhe_range_model as RM
+import nlhe_read_chunk as RC
 import oracle_nlhe as ON
 from robopoker_amd import _lib
 from robopoker_amd.nlhe import A, ENC_DTYPE, MAX_HOLES, NlheSolver, Recall
@@ -310,3 +312,87 @@ def test_arguments(gpu):
     assert s.reaches(long)[0][2] == RM.LENGTH and s.opponent_range(long)[2][0] == RM.LENGTH
     s.step()
     assert s.epoch == 1 and s.counters()[2] > 0
+
+
+# ---- the launch chunk (tests/nlhe_read_chunk.py): a batch cut into several launches answers what one launch answers ----
+def device_recalls(recalls):
+    return torch.from_numpy(Recall.pack(recalls).view(np.uint8).copy()).to("cuda")
+
+
+def from_device(s, out):
+    s.sync()
+    return {k: v.cpu().numpy() for k, v in out.items()} if isinstance(out, dict) else [v.cpu().numpy() for v in out]
+
+
+def ending_with(kind):
+    """every case's recall, turned so that the hardest case of `kind` comes last: (recalls, the last one's index in CASES)"""
+    last = [i for i, c in enumerate(CASES) if c[:2] == (("river", kind) if kind == "signalled" else ("corners", kind))][0]
+    order = [(last + 1 + j) % len(CASES) for j in range(len(CASES))]
+    assert order[-1] == last and len({CASES[i][0] for i in order[:3]}) > 1
+    return [CASES[i][2] for i in order], last
+
+
+@pytest.mark.parametrize("kind,normalize", [("opponent", False), ("opponent", True), ("signalled", False), ("signalled", True)])
+def test_reaches_do_not_depend_on_the_launch_chunk(gpu, model, kind, normalize):
+    m, s = model, model.solver()
+    recalls, last = ending_with(kind)
+    n, dev_in = len(recalls), device_recalls(recalls)
+    with RC.read_chunk(None):
+        want = s.reaches_raw(recalls, kind, normalize)
+    assert n % 16 and len(set(want["status"])) == 3 and len(set(want["count"])) > 3
+    # the model itself on the item that every cut puts into a later launch
+    check_stream(tuple(want[f][-1] for f in ("count", "holes", "reach", "status")), (m.normed if normalize else m.raw)[last], "the last recall")
+    for chunk in RC.cuts(n):
+        with RC.read_chunk(chunk):
+            RC.same(s.reaches_raw(recalls, kind, normalize), want, (chunk, "host"))
+            RC.same(from_device(s, s.reaches_device(dev_in, kind, normalize)), want, (chunk, "device"))
+    with RC.read_chunk(1):  # one recall: the one-byte arrays of the staging arena end off its alignment
+        RC.same(s.reaches_raw(recalls[-1:], kind, normalize), RC.tail(want, n - 1), "one recall")
+    # holes and status left out, in launches of 3
+    lib, rec = _lib.load(), Recall.pack(recalls)
+    count, reach = np.zeros(n, np.uint32), np.zeros((n, MAX_HOLES), np.float32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    with RC.read_chunk(3):
+        assert lib.rp_nlhe_reaches(s._h, _lib.REACH[kind], int(normalize), n, p(rec), p(count), None, p(reach), None) == _lib.RP_OK
+    RC.same((count, reach), (want["count"], want["reach"]), "without holes and status")
+
+
+def test_the_opponent_range_does_not_depend_on_the_launch_chunk(gpu, model):
+    m, s = model, model.solver()
+    recalls, last = ending_with("opponent")
+    n, dev_in = len(recalls), device_recalls(recalls)
+    with RC.read_chunk(None):
+        want = [np.ascontiguousarray(x).view(np.uint8) for x in s.opponent_range(recalls)]
+    assert want[2][-1] == m.range[last][0] == RM.OK and len(set(want[2])) == 3
+    assert np.array_equal(bits(want[0][-1].view(np.float32)), bits(m.range[last][1])) and np.array_equal(want[1][-1], m.range[last][2])
+    view = lambda out: [np.ascontiguousarray(x).view(np.uint8) for x in out]
+    for chunk in RC.cuts(n):
+        with RC.read_chunk(chunk):
+            RC.same(view(s.opponent_range(recalls)), want, (chunk, "host"))
+            RC.same(view(from_device(s, s.opponent_range_device(dev_in))), want, (chunk, "device"))
+    with RC.read_chunk(1):
+        RC.same(view(s.opponent_range(recalls[-1:])), RC.tail(want, n - 1), "one recall")
+    lib, rec = _lib.load(), Recall.pack(recalls)
+    mass, seen = np.zeros((n, 256), np.float32), np.zeros((n, 256), np.uint8)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    with RC.read_chunk(3):
+        assert lib.rp_nlhe_opponent_range(s._h, n, p(rec), p(mass), p(seen), None) == _lib.RP_OK
+    RC.same((mass.view(np.uint8), seen), want[:2], "without status")
+
+
+def test_a_launch_chunk_outside_its_range_is_refused(gpu, model):
+    """RP_NLHE_READ_CHUNK is read by every call: 1 .. 2^20; anything else is refused, and the handle answers afterwards"""
+    s = model.solver()
+    recalls = [c[2] for c in CASES[:3]]
+    with RC.read_chunk(None):
+        want = s.reaches_raw(recalls)
+    for bad in ("0", "x", "3x", "-1", str((1 << 20) + 1)):
+        with RC.read_chunk(bad):
+            with pytest.raises(_lib.RpError, match=RC.ENV):
+                s.reaches_raw(recalls)
+            with pytest.raises(_lib.RpError, match=RC.ENV):
+                s.opponent_range_device(device_recalls(recalls))
+    for good in (None, "", "2", str(1 << 20)):
+        with RC.read_chunk(good):
+            RC.same(s.reaches_raw(recalls), want, good)
+    assert RC.ENV not in os.environ

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import nlhe_read_chunk as RC
 import nlhe_translate_cases as TC
 import nlhe_translate_model as TM
 from robopoker_amd.nlhe import AIVAT_DTYPE, MAX_HOLES, RECALL_DTYPE, AivatHand, NlheSolver
@@ -207,3 +208,39 @@ def test_the_table_is_untouched(solver, played):
     after = (solver.export(), solver.epoch, solver.counters())
     assert all(np.array_equal(x, y) for x, y in zip(before[0][:3], after[0][:3])) and before[0][3].tobytes() == after[0][3].tobytes()
     assert before[1:] == after[1:]
+
+
+@pytest.mark.parametrize("kind", ("harmonic", "phargmax"))
+def test_small_launch_chunks_cut_the_optional_inputs(solver, played, kind):
+    """RP_NLHE_READ_CHUNK (tests/nlhe_read_chunk.py) cuts the refused-hand batch into launches of 1, 3, n - 1 and n hands: every launch
+    reads pov and upto, and counts the ids of its harmonic draws, from its own hand on.  Against the model, not only against one launch"""
+    bad = TC.refusals()
+    hands, pov = [], []
+    for i, (hand, p, _) in enumerate(bad):
+        hands += [played[2 * i], hand, played[2 * i + 1]]
+        pov += [1 - played[2 * i].seat, hand.seat if p is None else p, played[2 * i + 1].seat]
+    hands += [TC.THREE_BET, TC.POT12]
+    pov += [1, 0]
+    n = len(hands)
+    upto = np.array([len(h.plays) - (i % 3 == 2) for i, h in enumerate(hands)], np.uint8)  # every third hand before its last play
+    upto[-1] = len(TC.POT12.plays) + 1  # more plays asked for than the hand has: refused, in a launch of its own at n - 1
+    expected = want(hands, kind, pov, upto)
+    assert n % 16 and list(expected["status"][1:-2:3]) == [s for _, _, s in bad] and expected["status"][-1] == TM.LENGTH
+    assert expected["recalls"].tobytes() != want(hands, kind, None, upto)["recalls"].tobytes()
+    assert expected["recalls"].tobytes() != want(hands, kind, pov, None)["recalls"].tobytes()
+    if kind == "harmonic":  # the ids matter: counted from first_id again at the first cut of 3, some draw decides otherwise
+        again = want(hands[3:], kind, pov[3:], upto[3:])
+        assert again["play_edges"].tobytes() != expected["play_edges"][3:].tobytes()
+    with RC.read_chunk(None):
+        same(on_host(solver, hands, kind, pov, upto), expected, "one launch")
+    for chunk in RC.cuts(n):
+        with RC.read_chunk(chunk):
+            same(on_host(solver, hands, kind, pov, upto), expected, (chunk, "host"))
+            same(on_device(solver, hands, kind, pov, upto), expected, (chunk, "device"))
+    with RC.read_chunk(3):  # pov and upto left out, alone and together; one hand
+        same(on_host(solver, hands, kind, None, upto), want(hands, kind, None, upto), "without pov")
+        same(on_device(solver, hands, kind, pov, None), want(hands, kind, pov, None), "without upto")
+        same(on_device(solver, hands, kind), want(hands, kind), "without either")
+    with RC.read_chunk(1):
+        same(on_host(solver, hands[-2:-1], kind, pov[-2:-1], upto[-2:-1], first_id=FIRST_ID + n - 2),
+             {f: expected[f][-2:-1] for f in FIELDS}, "one hand")

@@ -14,6 +14,7 @@ import torch
 
 import nlhe_policy_model as PM
 import nlhe_range_model as RM
+import nlhe_read_chunk as RC
 import nlhe_world_model as WM
 import oracle_nlhe as ON
 from robopoker_amd import _lib
@@ -452,3 +453,93 @@ def test_arguments(gpu):
     assert s.belief(long)["status"][0] == RM.LENGTH and s.restrict(long, 2)["status"][0] == RM.LENGTH and not s.restrict(long, 2)["holes"].any()
     s.step()
     assert s.epoch == 1 and s.counters()[2] > 0
+
+
+# ---- the launch chunk (tests/nlhe_read_chunk.py): a batch cut into several launches answers what one launch answers ----
+def from_device(s, out):
+    s.sync()
+    return {k: v.cpu().numpy() for k, v in out.items()} if isinstance(out, dict) else [v.cpu().numpy() for v in out]
+
+
+def test_the_partition_does_not_depend_on_the_launch_chunk(gpu):
+    rows = partition_rows()[1:]  # 15 rows: not a multiple of the staging arena's alignment
+    n = len(rows)
+    mass, seen = np.stack([r[1] for r in rows]), np.stack([r[2] for r in rows])
+    d_mass, d_seen = torch.from_numpy(mass).to("cuda"), torch.from_numpy(seen.astype(np.uint8)).to("cuda")
+    s = NlheSolver(cap_log2=CAP_LOG2, batch=1, seed=1)
+    with RC.read_chunk(None):
+        want = s.partition(mass, seen)
+    assert n % 16 and n >= 7
+    for chunk in RC.cuts(n):
+        with RC.read_chunk(chunk):
+            host, dev = s.partition(mass, seen), from_device(s, s.partition_device(d_mass, d_seen))
+        RC.same(host, want, (chunk, "host"))
+        RC.same(dev, want, (chunk, "device"))
+        for i, (name, row_mass, row_seen) in enumerate(rows):  # the model itself, on every row of every launch
+            world, weights, _ = WM.partition(row_mass, row_seen)
+            assert np.array_equal(host[0][i], world) and np.array_equal(bits(host[1][i]), bits(weights)), (chunk, name)
+    with RC.read_chunk(1):
+        RC.same(s.partition(mass[-1:], seen[-1:]), RC.tail(want, n - 1), "one row")
+
+
+def test_the_belief_does_not_depend_on_the_launch_chunk(gpu, model):
+    m, s = model, model.solver()
+    n = len(RECALLS)
+    rec = torch.from_numpy(Recall.pack(RECALLS).view(np.uint8).copy()).to("cuda")
+    with RC.read_chunk(None):
+        want = s.belief(RECALLS)
+    assert n % 16 and n >= 7 and len(set(want["status"])) == 3
+    for chunk in RC.cuts(n):
+        with RC.read_chunk(chunk):
+            host, dev = s.belief(RECALLS), from_device(s, s.belief_device(rec))
+        RC.same(host, want, (chunk, "host"))
+        RC.same(dev, want, (chunk, "device"))
+        for i, name in enumerate(NAMES):  # the model itself; the zero-total recall is the last launch of n - 1
+            check_belief(host, i, m.belief[i], (chunk, name))
+    with RC.read_chunk(1):
+        RC.same(s.belief(RECALLS[ZERO]), {k: v[ZERO: ZERO + 1] for k, v in want.items()}, "one recall")
+    # hole_world and status left out, in launches of 3
+    lib, packed = _lib.load(), Recall.pack(RECALLS)
+    world, weights = np.zeros((n, 256), np.uint8), np.zeros((n, WORLDS), F)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    with RC.read_chunk(3):
+        assert lib.rp_nlhe_belief(s._h, n, p(packed), p(world), p(weights), None, None) == _lib.RP_OK
+    RC.same((world, weights), (want["world"], want["weights"]), "without hole_world and status")
+
+
+@pytest.mark.parametrize("deals,columns", [(1, slice(7, 8)), (5, slice(3, 8))])
+def test_the_deals_do_not_depend_on_the_launch_chunk(gpu, model, deals, columns):
+    """the columns hold the malformed request of "flop pov 0" and, with 5 deals, the zero-total recall's request for an empty world"""
+    m, s = model, model.solver()
+    n = len(RECALLS)
+    worlds = np.ascontiguousarray(m.worlds[:, columns])
+    assert worlds.shape == (n, deals) and FIRST_ID and (worlds == 9).any() and (deals == 1 or worlds[ZERO].any())
+    rec, d_worlds = torch.from_numpy(Recall.pack(RECALLS).view(np.uint8).copy()).to("cuda"), torch.from_numpy(worlds).to("cuda")
+    call = lambda recalls, asked, first_id: s.restrict(recalls, deals, asked, SEED, first_id & WM.M64)
+    with RC.read_chunk(None):
+        want, drawn = call(RECALLS, worlds, FIRST_ID), call(RECALLS, None, FIRST_ID)
+    for i, (name, r) in enumerate(CASES):  # one launch against the model at this number of deals: the ids are (first_id + r) * deals + d
+        assert want["status"][i] == m.belief[i]["status"], name
+        check_deals(want, i, WM.restrict(r, m.belief[i], i, deals, worlds[i], SEED, FIRST_ID), name)
+    for chunk in RC.cuts(n):
+        with RC.read_chunk(chunk):
+            host = call(RECALLS, worlds, FIRST_ID)
+            dev = from_device(s, s.restrict_device(rec, deals, d_worlds, SEED, FIRST_ID))
+        RC.same(host, want, (chunk, "host"))
+        RC.same(dev, want, (chunk, "device"))
+        if chunk < n:  # the recalls from the first cut on: a call of their own under first_id + chunk, in one launch
+            with RC.read_chunk(None):
+                RC.same(call(RECALLS[chunk:], worlds[chunk:], FIRST_ID + chunk), RC.tail(want, chunk), (chunk, "ids"))
+                if chunk == 1:
+                    assert call(RECALLS[chunk:], worlds[chunk:], FIRST_ID)["holes"].tobytes() != want["holes"][chunk:].tobytes()
+    at = NAMES.index("river")
+    with RC.read_chunk(1):
+        RC.same(call(RECALLS[at], worlds[at: at + 1], FIRST_ID + at), {k: v[at: at + 1] for k, v in want.items()}, "one recall")
+    # worlds, world_out, attempts and status left out, in launches of 3: the drawn worlds' holes
+    lib, packed, holes = _lib.load(), Recall.pack(RECALLS), np.zeros((n, deals), np.uint64)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    with RC.read_chunk(3):
+        assert lib.rp_nlhe_restrict(s._h, n, p(packed), deals, None, SEED, FIRST_ID, p(holes), None, None, None) == _lib.RP_OK
+        RC.same(call(RECALLS, None, FIRST_ID), drawn, "drawn worlds, host")
+        RC.same(from_device(s, s.restrict_device(rec, deals, None, SEED, FIRST_ID)), drawn, "drawn worlds, device")
+    assert holes.tobytes() == drawn["holes"].tobytes() and holes.tobytes() != want["holes"].tobytes()
